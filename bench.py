@@ -17,15 +17,21 @@ neighbour lists of a map it can verify to be bit for bit last frame's) is faster
 changes; that figure is the extra key `reuse_of_an_unchanged_map`, beside `one_point_edited_every_frame` and
 `keyframe_every_3rd_frame` (what it gives when the map does change), each timed exactly like `value`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--configs c1,c3,c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--configs c1,c3,c5]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the workload); --dump-outputs DIR
+also writes the last timed step's motion, world pose, fitness and iteration count as DIR/<name>.npy (rank r > 0: <name>_rank<r>.npy).
+The inputs depend on the arguments only (seeded).  A sequence has at most SCAN_POOL distinct scans: a longer one goes forth and back
+over the first SCAN_POOL poses of its trajectory (scan_schedule), so that the setup does not grow with K.  Everything else below --
+the extra keys, the CPU baseline and parity check, the other configurations -- runs with --full only.
 
 N > 1: one process per GPU, one independent sequence per rank (different seed), no data-path collective
 (the path shards across sequences); torch.distributed (RCCL) is used only for the barrier and the
 MAX over ranks of the elapsed time.  Rank 0 prints ONE JSON line.
 
-Extra keys beside the contract's: `one_frame_at_a_time` (the same steps on one context through the blocking calls: a frame's latency),
+Extra keys beside the contract's (--full): `one_frame_at_a_time` (the same steps on one context through the blocking calls: a frame's latency),
 `replay_of_preframed_maps` (round 2's figure: targets that do NOT depend on the previous pose -- three translated copies of the map in
 turn -- so that a whole frame's preparation overlaps the previous solve; what a replay of pre-framed sub-maps reaches, not a live
 sequence), `scan_h2d_and_output` (the dependent steps with each scan uploaded from pinned host memory inside the step and align()'s
@@ -59,6 +65,7 @@ MIX_FILE = "r06_knn_isa_mix.json"  # its full- / half-rate instruction mix (scri
 FRAME_TRAFFIC_FILE = "r06_frame_traffic.json"  # measured HBM bytes of a whole dependent frame, every kernel (scripts/frame_traffic.sh)
 KERNEL_STATS_FILE = "r06_frame_kernel_times.json"  # GPU time per kernel and frame of the timed workload under rocprofv3 (scripts/frame_kernel_times.sh)
 REUSE_NONE, REUSE_SEEDS, REUSE_LISTS = 0, 1, 2   # rgc_set_knn_reuse
+SCAN_POOL = 128    # distinct synthetic scans of a sequence (make_sequence): longer sequences go forth and back over them
 
 
 def profile_json(name):
@@ -163,6 +170,36 @@ def compose_world(Tw, T):
     return W
 
 
+def make_scans(world, poses, n_source, seeds):
+    """synth.make_scan_n(world, poses[i], n_source, seed=seeds[i])["xyz"] for every i, cast on up to 16 host threads (numpy releases the
+    interpreter lock in the ray casting; every scan has a generator of its own) -- the arrays one thread would cast, bit for bit."""
+    import rgc_slam_amd.synth as synth
+    from concurrent.futures import ThreadPoolExecutor
+    n_threads = max(1, min(16 // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))), len(os.sched_getaffinity(0)), len(poses)))
+    with ThreadPoolExecutor(n_threads) as ex:
+        return list(ex.map(lambda ps: synth.make_scan_n(world, ps[0], n_source, seed=ps[1])["xyz"], zip(poses, seeds)))
+
+
+def scan_schedule(n_frames, pool):
+    """Which of `pool` distinct scans frame i of an n_frames sequence registers: 0, 1, ..., n_frames - 1 while n_frames <= pool; beyond that
+    the trajectory's first `pool` poses forth and back (0 .. pool - 1, pool - 2 .. 0, 1 ..), so that the setup is bounded whatever the number
+    of steps and the vehicle never leaves the synthetic world."""
+    if n_frames <= pool:
+        return list(range(n_frames))
+    period = 2 * (pool - 1)
+    return [i % period if i % period < pool else period - i % period for i in range(n_frames)]
+
+
+def make_sequence(synth, world, n_frames, n_source, seed):
+    """(poses, scans) of an n_frames dependent sequence: poses[0] the start, scans[i] taken at poses[i + 1] (seed + 100 + its pool index).
+    At most SCAN_POOL distinct scans (scan_schedule): entries of a longer sequence repeat the same arrays."""
+    pool = min(n_frames, SCAN_POOL)
+    poses_pool = synth.make_trajectory(pool + 1, seed=seed)
+    scans_pool = make_scans(world, poses_pool[1:], n_source, [seed + 100 + i for i in range(pool)])
+    sched = scan_schedule(n_frames, pool)
+    return [poses_pool[0]] + [poses_pool[j + 1] for j in sched], [scans_pool[j] for j in sched]
+
+
 class DependentSequence:
     """The odometer's frame loop on device-resident clouds (RGC_odometer.cpp:976-1023, 1201-1203, 1248-1256):
     frame i: target = the local map re-expressed in the body frame of world pose i - 1 and rebuilt in full (rgc_set_target_reframed,
@@ -173,6 +210,7 @@ class DependentSequence:
         self.v = contexts
         self.d_map, self.n_map, self.d_scans, self.n_scans, self.pinned, self.d_aligned = d_map, n_map, d_scans, n_scans, pinned, d_aligned
         self.d_body = {id(w): w.device_alloc(16 * n_map) for w in contexts}
+        self.fitness = self.iterations = None   # (per frame of the last run_cpp)
 
     def close(self):
         for w in self.v:
@@ -207,11 +245,13 @@ class DependentSequence:
         mot = np.empty((count, 4, 4), np.float32)
         wor = np.empty((count, 4, 4), np.float64)
         st = np.empty(count, np.float64)
+        self.fitness, self.iterations = np.empty(count, np.float64), np.empty(count, np.int32)   # (each frame's getFitnessScore and nr_iterations)
         fp, dp, ip = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int)
         t_call = time.perf_counter()
         rc = S.rgc_seq_run_dependent(a._h, b._h if b is not None else None, C.c_void_p(self.d_map), int(self.n_map), 16, C.c_void_p(self.d_body[id(a)]),
                                      C.c_void_p(self.d_body[id(b)]) if b is not None else None, ptrs, ns, 16, count, Tw.ctypes.data_as(dp),
-                                     g0.ctypes.data_as(fp), 1, mot.ctypes.data_as(fp), wor.ctypes.data_as(dp), None, None, st.ctypes.data_as(dp))
+                                     g0.ctypes.data_as(fp), 1, mot.ctypes.data_as(fp), wor.ctypes.data_as(dp), self.fitness.ctypes.data_as(dp),
+                                     self.iterations.ctypes.data_as(ip), st.ctypes.data_as(dp))
         if rc != 0:
             raise RuntimeError(f"rgc_seq_run_dependent: status {rc}: {a._L.rgc_last_error(a._h).decode()} / "
                                f"{b._L.rgc_last_error(b._h).decode() if b is not None else ''}")
@@ -641,6 +681,52 @@ def run_extra_configs(registration, synth, oracle, keys):
     return res
 
 
+def pose_checksums(np, worlds, world_size, dist):
+    """(this rank's checksum of its world poses, every rank's): one small object per rank, for the record that the ranks ran DIFFERENT sequences"""
+    checksum = float(np.sum(np.abs(np.asarray(worlds, np.float64))))
+    rank_checksums = [checksum]
+    if world_size > 1:
+        rank_checksums = [None] * world_size
+        dist.all_gather_object(rank_checksums, checksum)
+    return checksum, rank_checksums
+
+
+def dump_outputs(out_dir, suffix, np, motion, world, fitness, iterations):
+    """What a caller of the timed path receives for its last step: the motion (fp32 4x4), the world pose (fp64 4x4), getFitnessScore and
+    nr_iterations (fp64), as <out_dir>/<name><suffix>.npy"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"motion": np.asarray(motion, np.float32), "world_pose": np.asarray(world, np.float64)}
+    if fitness is not None:
+        arrays["fitness"] = np.asarray(fitness[-1:], np.float64)
+        arrays["iterations"] = np.asarray(iterations[-1:], np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+
+
+def headline(args, K, W, world_size, elapsed, step_stamps, prewarm, searched, host_loop, checksum, rank_checksums, np):
+    """The keys of every result line: the metric and what it was measured on"""
+    return {
+        "metric": "registered scans/sec (16-beam -> 1M-pt map)", "value": round(K * world_size / elapsed, 3), "unit": "scans/s",
+        "n_gpus": world_size, "steps": K, "warmup": W, "prewarm_frames_before_the_warmup": 4 * prewarm, "ms_per_step": round(1e3 * elapsed / K, 3),
+        "timed_steps_ms": {"median": round(1e3 * float(np.median(np.diff(step_stamps))), 4), "max": round(1e3 * float(np.max(np.diff(step_stamps))), 4),
+                           "slowest_step": int(np.argmax(np.diff(step_stamps))),
+                           "what": "host time between consecutive results inside the timed region of rank 0 (a one-off stall -- an allocation, a speculative-grid miss -- shows here, not in the kernels)"},
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32 points and neighbour search, f64 covariances and solve",
+        "data": "synthetic",
+        "config": {"workload": f"c-main: a dependent sequence of synthetic VLP-16 {args.n_source}-pt scans, each registered to the {args.n_target}-pt local "
+                               f"map re-expressed in the previous pose's body frame on the device and rebuilt in full, nothing kept from one "
+                               f"frame's target to the next (rgc_set_knn_reuse(RGC_REUSE_NONE): all {args.n_target} queries searched every frame, as for "
+                               f"a map whose point set changes every frame -- the reference's does; BASELINE.md c-main; RGC_odometer.cpp:976-1256; one "
+                               f"independent sequence per GPU; only the next scan's preparation overlaps a solve)",
+                   "n_source": args.n_source, "n_target": args.n_target, "voxel_res": 1.0, "k": 20, "max_iterations": 25,
+                   "knn_reuse": "none", "queries_searched_per_frame": searched, "host_frame_loop": host_loop,
+                   "parallelism": f"sequences x{world_size}", "distinct_scans": min(K + W, SCAN_POOL)},
+        "final_pose_checksum": checksum,
+        "final_pose_checksum_per_rank": rank_checksums,
+        "sequence_of_rank0": args.sequence,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -648,9 +734,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)   # (a few milliseconds of the same steps in front of the timed ones: the first steps behind an idle GPU run at lower clocks)
     ap.add_argument("--n-target", type=int, default=N_TARGET)
     ap.add_argument("--n-source", type=int, default=N_SOURCE)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--configs", default="c1,c3,c5", help="extra single-GPU configurations of BASELINE.json to run after the metric (c1,c3,c5 or 'none')")
-    ap.add_argument("--no-two-sequences", action="store_true", help="skip the extra key two_sequences_per_gpu (a second sequence's data and contexts)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, everything else this benchmark measures and checks: the extra keys "
+                    "of the module docstring, the CPU baseline and the other configurations; without it the line holds the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step (motion, world pose, fitness, "
+                    "iterations) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--configs", default="c1,c3,c5", help="with --full: extra single-GPU configurations of BASELINE.json to run after the metric (c1,c3,c5 or 'none')")
+    ap.add_argument("--no-two-sequences", action="store_true", help="with --full: skip the extra key two_sequences_per_gpu (a second sequence's data and contexts)")
     ap.add_argument("--sequence", type=int, default=0, help="number of the first rank's sequence (rank r runs sequence --sequence + r: seed offset)")
     args = ap.parse_args()
 
@@ -691,9 +781,8 @@ def main():
     seed = synth.SEED + args.sequence + rank  # one independent sequence per rank
     t0 = time.time()
     world, tgt = synth.make_world_and_map(args.n_target, seed=seed)
-    poses = synth.make_trajectory(K + W + 1, seed=seed)
-    scans = [synth.make_scan_n(world, poses[i + 1], args.n_source, seed=seed + 100 + i)["xyz"] for i in range(K + W)]
-    maps = [(tgt - np.asarray(d, np.float32)).astype(np.float32) for d in MAP_SHIFTS]
+    poses, scans = make_sequence(synth, world, K + W, args.n_source, seed)
+    maps = [(tgt - np.asarray(d, np.float32)).astype(np.float32) for d in (MAP_SHIFTS if args.full else MAP_SHIFTS[:1])]
     log(f"[rank {rank}] synthetic data: map {tgt.shape}, {len(scans)} scans of {scans[0].shape[0]} pts, world half-extent "
         f"{world.half_extent:.1f} m, {time.time() - t0:.1f} s, NUMA node {numa}")
 
@@ -710,14 +799,22 @@ def main():
         v.upload(p, a)
         return p
     d_maps = [to_dev(m) for m in maps]   # [0] is the map in the world frame; the others only serve `replay_of_preframed_maps`
-    d_scans = [to_dev(s) for s in scans]
-    # scan_h2d_and_output's inputs: every scan in pinned host memory (x,y,z,pad), one device buffer per context for align()'s output cloud
-    pinned = []
+    d_pool = {}                          # (one device copy of each distinct scan: a sequence longer than SCAN_POOL repeats them)
     for s in scans:
-        t = torch.zeros((s.shape[0], 4), dtype=torch.float32).pin_memory()
-        t[:, :3] = torch.from_numpy(s)
-        pinned.append(t)
-    d_aligned = {id(w): w.device_alloc(16 * args.n_source) for w in pv.v}
+        if id(s) not in d_pool:
+            d_pool[id(s)] = to_dev(s)
+    d_scans = [d_pool[id(s)] for s in scans]
+    pinned = d_aligned = None
+    if args.full:
+        # scan_h2d_and_output's inputs: every scan in pinned host memory (x,y,z,pad), one device buffer per context for align()'s output cloud
+        pinned_pool = {}
+        for s in scans:
+            if id(s) not in pinned_pool:
+                t = torch.zeros((s.shape[0], 4), dtype=torch.float32).pin_memory()
+                t[:, :3] = torch.from_numpy(s)
+                pinned_pool[id(s)] = t
+        pinned = [pinned_pool[id(s)] for s in scans]
+        d_aligned = {id(w): w.device_alloc(16 * args.n_source) for w in pv.v}
     seq = DependentSequence(pv.v, d_maps[0], tgt.shape[0], d_scans, [s.shape[0] for s in scans], pinned, d_aligned)
     I4 = np.eye(4, dtype=np.float32)
     Tw_init = np.asarray(poses[0], np.float64)
@@ -773,6 +870,18 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "" if rank == 0 else f"_rank{rank}", np, motions[-1], worlds[-1], seq.fitness, seq.iterations)
+    if not args.full:
+        checksum, rank_checksums = pose_checksums(np, worlds, world_size, dist)
+        searched = int(pv.v[(K - 1) % len(pv.v)].stats()["searched_target"]) if K > 0 else 0   # (the target of the last timed frame)
+        seq.close()
+        pv.close()
+        if rank == 0:
+            print(json.dumps(headline(args, K, W, world_size, elapsed, step_stamps, PREWARM, searched, host_loop, checksum, rank_checksums, np)), flush=True)
+        if world_size > 1:
+            dist.destroy_process_group()
+        return
     prof_dom = {"total_ms": 0.0, "launches": 0, "points": 0}
     for w in pv.v:
         d = w.profile()[DOMINANT]
@@ -1019,11 +1128,7 @@ def main():
     for w in pv.v:
         w.setNeighbourReuse(REUSE_NONE)
 
-    checksum = float(np.sum(np.abs(np.asarray(worlds, np.float64))))
-    rank_checksums = [checksum]
-    if world_size > 1:  # (after every timed region: one small object per rank, for the record that the ranks ran DIFFERENT sequences)
-        rank_checksums = [None] * world_size
-        dist.all_gather_object(rank_checksums, checksum)
+    checksum, rank_checksums = pose_checksums(np, worlds, world_size, dist)   # (after every timed region)
     if rank != 0:
         if world_size > 1:
             dist.destroy_process_group()
@@ -1098,22 +1203,8 @@ def main():
     # are in kernel_ms_per_step.
     by_kernel = roofline_by_kernel(args.n_source, args.n_target, n_vox, mean_corr, t_cells, s_cells, def_src, ft)
 
-    out = {
-        "metric": "registered scans/sec (16-beam -> 1M-pt map)", "value": round(scans_per_s, 3), "unit": "scans/s",
-        "n_gpus": world_size, "steps": K, "warmup": W, "prewarm_frames_before_the_warmup": 4 * PREWARM, "ms_per_step": round(1e3 * elapsed / K, 3),
-        "timed_steps_ms": {"median": round(1e3 * float(np.median(np.diff(step_stamps))), 4), "max": round(1e3 * float(np.max(np.diff(step_stamps))), 4),
-                           "slowest_step": int(np.argmax(np.diff(step_stamps))),
-                           "what": "host time between consecutive results inside the timed region of rank 0 (a one-off stall -- an allocation, a speculative-grid miss -- shows here, not in the kernels)"},
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32 points and neighbour search, f64 covariances and solve",
-        "data": "synthetic",
-        "config": {"workload": f"c-main: a dependent sequence of synthetic VLP-16 {args.n_source}-pt scans, each registered to the {args.n_target}-pt local "
-                               f"map re-expressed in the previous pose's body frame on the device and rebuilt in full, nothing kept from one "
-                               f"frame's target to the next (rgc_set_knn_reuse(RGC_REUSE_NONE): all {args.n_target} queries searched every frame, as for "
-                               f"a map whose point set changes every frame -- the reference's does; BASELINE.md c-main; RGC_odometer.cpp:976-1256; one "
-                               f"independent sequence per GPU; only the next scan's preparation overlaps a solve)",
-                   "n_source": args.n_source, "n_target": args.n_target, "voxel_res": 1.0, "k": 20, "max_iterations": 25,
-                   "knn_reuse": "none", "queries_searched_per_frame": searched_alone, "host_frame_loop": host_loop,
-                   "parallelism": f"sequences x{world_size}"},
+    out = headline(args, K, W, world_size, elapsed, step_stamps, PREWARM, searched_alone, host_loop, checksum, rank_checksums, np)
+    out.update({
         "algorithmic_bytes_per_scan": round(B), "hbm_gbps_algorithmic": round(B * scans_per_s / world_size / 1e9, 3),
         "hbm_frac_whole_frame": round(B * scans_per_s / world_size / 1e9 / HBM_PEAK_GBS, 6),
         "mean_outer_iterations": round(mean_outer, 2), "mean_linearize": round(mean_lin, 2), "mean_compute_error": round(mean_err, 2),
@@ -1129,10 +1220,7 @@ def main():
         "scan_h2d_and_output": {"scans_per_s": round(K / elapsed_h2d, 3), "ms_per_step": round(1e3 * elapsed_h2d / K, 3), "same_final_pose": h2d_same,
                                 "what": "the dependent steps; each scan uploaded from pinned host memory inside the step, align()'s output cloud written to a device buffer"},
         "steady_state": steady, "lazy_target": lazy, "reuse_of_an_unchanged_map": reuse,
-        "final_pose_checksum": checksum,
-        "final_pose_checksum_per_rank": rank_checksums,
-        "sequence_of_rank0": args.sequence,
-    }
+    })
 
     oracle = None
     if world_size == 1 and not args.no_cpu_baseline:
@@ -1186,8 +1274,7 @@ def main():
     if world_size == 1 and not args.no_two_sequences:
         K2 = min(K, 20)
         world_b, tgt_b = synth.make_world_and_map(args.n_target, seed=seed + 1)
-        poses_b = synth.make_trajectory(K2 + W + 1, seed=seed + 1)
-        scans_b = [synth.make_scan_n(world_b, poses_b[i + 1], args.n_source, seed=seed + 1 + 100 + i)["xyz"] for i in range(K2 + W)]
+        poses_b, scans_b = make_sequence(synth, world_b, K2 + W, args.n_source, seed + 1)
         out["two_sequences_per_gpu"] = two_sequences_per_gpu(registration, synth, np, device_index, seq, pv, tgt.shape[0], args.n_source, seed, W,
                                                              K2, Tw_init, I4, second=(tgt_b, poses_b, scans_b))
         try:

@@ -5,6 +5,7 @@
 #   usage: scripts/refresh_profiles.sh [quick]     (quick: skip the long runs, c3 / c5 traffic and the side benches)
 TAG=${RGC_ROUND_TAG:-r06}
 cd "$GRAFT_REPO_ROOT"
+ROOT=$(pwd)
 O=$GRAFT_REPO_ROOT/gpurun_out/${TAG}f
 rm -rf $O; mkdir -p $O
 # 1. counters and executed instruction mix of the dominant kernel FIRST: bench.py quotes them (traffic, VALU per query, mix-weighted peak)
@@ -28,9 +29,9 @@ timeout 600 bash scripts/frame_traffic.sh 10 cmain lists > $O/frame_traffic_cmai
 timeout 600 bash scripts/frame_kernel_times.sh 40 1 cmain > $O/frame_kernel_times.log 2>&1; cp gpurun_out/frame_kernel_times.json $O/frame_kernel_times.json
 cp $O/pmc_knn.json profiles/${TAG}_pmc_knn.json; cp $O/knn_isa_mix.json profiles/${TAG}_knn_isa_mix.json; cp $O/frame_traffic.json profiles/${TAG}_frame_traffic.json; cp $O/frame_kernel_times.json profiles/${TAG}_frame_kernel_times.json   # (this box's copy of the tree: what bench.py reads)
 # 3. the bench line, and the same command under rocprofv3
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.log
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.log
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --configs none > $O/bench_under_rocprof.json 2> $O/rocprof.log
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python3 $ROOT/bench.py --full --no-cpu-baseline --configs none > $O/bench_under_rocprof.json 2> $O/rocprof.log
 cd $GRAFT_REPO_ROOT
 find $O/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats.csv
 find $O/stats -name "*domain_stats.csv" | head -1 | xargs -I{} cp {} $O/domain_stats.csv

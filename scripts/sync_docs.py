@@ -182,7 +182,7 @@ s = open(P("DESIGN.md")).read()
 open(P("DESIGN.md"), "w").write(put(s, numbers + "\n"))
 
 B = d["algorithmic_bytes_per_scan"] / 1e6
-base = f'''Round 6, one MI355X, `python bench.py` (`profiles/{TAG}_bench.json`; everything under `profiles/{TAG}_*` is from the same run of `scripts/refresh_profiles.sh`; this block is
+base = f'''Round 6, one MI355X, `python bench.py --full` (`profiles/{TAG}_bench.json`; everything under `profiles/{TAG}_*` is from the same run of `scripts/refresh_profiles.sh`; this block is
 generated from those files by `scripts/sync_docs.py`).  HIP = this repository's gfx950 path; the target is rebuilt in full every frame and **nothing is kept from one frame's
 target to the next** (`rgc_set_knn_reuse(RGC_REUSE_NONE)`): every frame pays the exact 20-NN of every map point, as the reference does and as a caller does whose map's point
 set changes every frame (the reference re-filters its sub-map in the new body frame every frame, `RGC_odometer.cpp:985-991`).  c-main, c3 and c5 run as **dependent sequences** —
