@@ -683,13 +683,14 @@ __device__ __forceinline__ void min_eigenvector(const double S[6], double n[3]) 
     jacobi_rot<0, 2, 1>(A, V);
     jacobi_rot<1, 2, 0>(A, V);
   }
-  double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
-  // column of the smallest eigenvalue; on exact ties take the LAST one in descending sort order like the
-  // oracle's stable selection (ord[] keeps index order for equal values, so the smallest is the highest index)
-  int m = 0;
-  double em = e0;
-  if (e1 <= em) { m = 1; em = e1; }
-  if (e2 <= em) { m = 2; em = e2; }
+  const double ev[3] = {A[0][0], A[1][1], A[2][2]};
+  // column of the smallest eigenvalue: the last of the oracle's descending selection sort (orc_eig3, eig3_sym below), exact ties
+  // included -- which is not "the highest index among the smallest": diag(0, 0, s) (an exactly collinear neighbourhood along z) sorts to
+  // columns {2, 1, 0} and its normal is column 0, as Eigen's JacobiSVD orders it (tests/test_gpu_knn_k_range.py)
+  int o0 = 0, o1 = 1, m = 2;
+  if (ev[o1] > ev[o0]) { const int t = o0; o0 = o1; o1 = t; }
+  if (ev[m] > ev[o0]) { const int t = o0; o0 = m; m = t; }
+  if (ev[m] > ev[o1]) m = o1;
   n[0] = m == 0 ? V[0][0] : (m == 1 ? V[0][1] : V[0][2]);
   n[1] = m == 0 ? V[1][0] : (m == 1 ? V[1][1] : V[1][2]);
   n[2] = m == 0 ? V[2][0] : (m == 1 ? V[2][1] : V[2][2]);
@@ -711,6 +712,10 @@ __device__ __forceinline__ bool min_eigenvector_direct(const double S[6], double
   const double m0 = d * f - e * e, m1 = b * f - c * e, m2 = b * e - c * d;
   const double c1 = (a * d - b * b) + (a * f - c * c) + m0;  // sum of the principal 2x2 minors
   const double c0 = a * m0 - b * m1 + c * m2;                // determinant
+  // rank <= 1 (c1 = l1 l2 + l1 l3 + l2 l3 ~ l2: two neighbours, a collinear set): p'(0) is rounding noise and Newton's step can leave
+  // for the LARGEST root, whose null vector then passes the cross-product test below -- the normal along the line
+  // (tests/test_gpu_knn_k_range.py, k = 2).  Such rows fail that test at the smallest root anyway: the fallback's.
+  if (!(c1 > 1.0e-7)) return false;
   // p(x) = x^3 - x^2 + c1 x - c0
   double x = 0.0;
   bool settled = false;
@@ -724,7 +729,7 @@ __device__ __forceinline__ bool min_eigenvector_direct(const double S[6], double
     // it while the two smallest eigenvalues are at least ~1e-3 apart, which the cross-product test below insists on
     if (!(fabs(dx) > 1.0e-13)) { settled = dp > 0.0; break; }  // also leaves on NaN
   }
-  if (!settled) return false;
+  if (!settled || !(x <= 0.34)) return false;  // (the smallest eigenvalue at trace 1 is at most 1/3)
   const double r0[3] = {a - x, b, c}, r1[3] = {b, d - x, e}, r2[3] = {c, e, f - x};
   const double u[3] = {r0[1] * r1[2] - r0[2] * r1[1], r0[2] * r1[0] - r0[0] * r1[2], r0[0] * r1[1] - r0[1] * r1[0]};
   const double v[3] = {r0[1] * r2[2] - r0[2] * r2[1], r0[2] * r2[0] - r0[0] * r2[2], r0[0] * r2[1] - r0[1] * r2[0]};
