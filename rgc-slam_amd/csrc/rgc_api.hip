@@ -1661,7 +1661,9 @@ int rgc_set_params(rgc_ctx* c, const rgc_params* p) {
   if (redo) HIPCHK(c, hipSetDevice(c->device));  // (the re-preparation launches kernels: like every entry point that does, whatever device the calling thread had current)
   if (p->voxel_res != c->prm.voxel_res) c->src_res_auto = 0.0;
   c->prm = *p;
-  c->corr_valid = false;
+  // The correspondences the last linearisation froze stay what rgc_compute_error uses (with their own offset count, corr_noff) unless the
+  // clouds are prepared again: the reference's setters, setNeighborSearchMethod among them, leave voxel_correspondences_ alone.
+  if (redo) c->corr_valid = false;
   if (redo) {  // covariances / voxel map depend on these: recompute from the resident inputs
     if (c->tgt_owner) {
       // a BORROWED target (rgc_share_target) is the owner's, prepared under the owner's settings, and its input buffer is the owner's to
