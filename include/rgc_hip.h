@@ -262,6 +262,35 @@ RGC_API int rgc_voxelgrid(rgc_ctx* ctx, const float* xyzi, int n, int stride_byt
  * in between; one begin may be open per context. */
 RGC_API int rgc_voxelgrid_begin(rgc_ctx* ctx, const float* d_xyzi, int n, int stride_bytes, float leaf, float* d_out);
 RGC_API int rgc_voxelgrid_end(rgc_ctx* ctx, int* n_out);
+/* What the last leaf filter on this context did: filled by every rgc_voxelgrid and rgc_voxelgrid_end (an rgc_voxelgrid_begin alone does not
+ * change it), from the variables the filter itself used.  For tests and tuning: the filter's OUTPUT never depends on the route.
+ * The filter sorts the points by counting them into buckets of the leaf grid (the leaves themselves for a dense cloud, whole grid rows
+ * along x for a sweep, segments of 2^seg_shift leaves of a row for a large sparse cloud) and ranks them inside a bucket through one 64-bit
+ * record per point, packed (13 bits of leaf x, the bucket's extent inside the record) or unpacked (32 bits of leaf x). */
+#define RGC_VG_PATH_NONE 0       /* no filter has run on this context, or n == 0 */
+#define RGC_VG_PATH_KEPT 1       /* filtered on the padded box kept from an earlier cloud of this leaf size: no bounding-box pass */
+#define RGC_VG_PATH_MEASURED 2   /* the cloud's own leaf box was measured first */
+#define RGC_VG_PATH_UNFILTERED 3 /* that box has more than INT_MAX leaves: output = input, like PCL */
+typedef struct rgc_vg_route {
+  int path;            /* RGC_VG_PATH_*: where the result (or the refusal) came from */
+  int status;          /* what the call returned (RGC_OK, RGC_ERR_NONFINITE, RGC_ERR_GRID_TOO_LARGE, ...) */
+  int repeated;        /* 1: a chain ran on the kept box first, a point lay outside it (bit 1 of kept_flags), and the filter ran again */
+  int kept_box;        /* the box kept for this leaf size when the call began: 0 none, 1 used, 2 valid but its padded grid is neither
+                        * sparse nor within max_cells (not used), 3 invalidated by an earlier call */
+  int kept_flags;      /* flags word of the chain on the kept box (0 when there was none): 1 non-finite point, 2 point outside the box,
+                        * 4 point within half the padding of a face */
+  int box_invalidated; /* 1: this call dropped the kept box (kept_flags & 6): the next cloud of this leaf size is measured */
+  int chain;           /* 1: the fields below describe the chain that produced the output; 0: no chain did (unfiltered copy, refusal) */
+  int leaf_buckets;    /* 1: the sort's buckets are the leaves (dense cloud); 0: rows, or segments of rows */
+  int seg_shift;       /* 0 leaves, 3..30 segments of 2^seg_shift leaves, 31 whole rows */
+  int nseg;            /* buckets per grid row */
+  int packed;          /* 1: packed records, 0: unpacked */
+  int edge;            /* > 0: a kept box, points within `edge` leaves of its faces set flag 4 */
+  int flags;           /* flags word of that chain */
+  int minb[3], div[3]; /* the leaf grid used: a measured box also when chain == 0 and path != RGC_VG_PATH_NONE */
+  int n, n_out;
+} rgc_vg_route;
+RGC_API int rgc_voxelgrid_route(rgc_ctx* ctx, rgc_vg_route* out);
 /* B9  vg_ICP::transformPointCloud(cloud, q, t) (src/RGC_odometer.cpp:1495-1514): q * p + t in fp64, stored fp32,
  * intensity copied; out_xyzi: n*4 floats.  on_device: both pointers are device memory and the call returns once the kernel is enqueued
  * on rgc_stream(ctx), like rgc_deskew. */

@@ -102,6 +102,16 @@ class MapInfo(C.Structure):
                 ("oldest_id", C.c_int), ("newest_id", C.c_int), ("origin", C.c_double * 3)]
 
 
+class VgRoute(C.Structure):
+    """rgc_vg_route: what the last leaf filter on a context did (rgc_voxelgrid_route)"""
+    _fields_ = [("path", C.c_int), ("status", C.c_int), ("repeated", C.c_int), ("kept_box", C.c_int), ("kept_flags", C.c_int), ("box_invalidated", C.c_int),
+                ("chain", C.c_int), ("leaf_buckets", C.c_int), ("seg_shift", C.c_int), ("nseg", C.c_int), ("packed", C.c_int), ("edge", C.c_int), ("flags", C.c_int),
+                ("minb", C.c_int * 3), ("div", C.c_int * 3), ("n", C.c_int), ("n_out", C.c_int)]
+
+
+VG_PATH_NONE, VG_PATH_KEPT, VG_PATH_MEASURED, VG_PATH_UNFILTERED = 0, 1, 2, 3
+
+
 class RgcError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"rgc_hip status {status}: {msg}")
@@ -117,7 +127,7 @@ SYMBOLS = [
     "rgc_clear_source", "rgc_clear_target", "rgc_swap_source_and_target", "rgc_get_voxels",
     "rgc_get_stats", "rgc_device_alloc", "rgc_device_free", "rgc_host_alloc", "rgc_host_free", "rgc_upload", "rgc_download", "rgc_synchronize",
     "rgc_stream", "rgc_default_fe_params", "rgc_frontend", "rgc_extract_pose", "rgc_imu_preintegrate", "rgc_imu_filter_init", "rgc_imu_filter_push", "rgc_ground_gate_init", "rgc_ground_gate_remember", "rgc_ground_gate_step", "rgc_default_fuse_in", "rgc_fuse_pose", "rgc_compose_pose",
-    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
+    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
 _lib = None
@@ -259,6 +269,7 @@ def load():
     L.rgc_voxelgrid.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp, ip, C.c_int]
     L.rgc_voxelgrid_begin.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp]
     L.rgc_voxelgrid_end.argtypes = [vp, ip]
+    L.rgc_voxelgrid_route.argtypes = [vp, C.POINTER(VgRoute)]
     L.rgc_transform_cloud.argtypes = [vp, vp, C.c_int, C.c_int, dp, dp, vp, C.c_int]
     L.rgc_set_target_reframed.argtypes = [vp, vp, C.c_int, C.c_int, dp, dp, vp]
     L.rgc_default_icp_params.argtypes = [C.POINTER(IcpParams)]

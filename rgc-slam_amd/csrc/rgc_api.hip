@@ -248,7 +248,10 @@ struct rgc_ctx {
   // rgc_voxelgrid_begin / _end: one filter of a device cloud in flight (enqueued on its kept box, result not yet looked at)
   struct VgPending { bool active = false, ready = false; const float* d_in = nullptr; int n = 0, stride_bytes = 0; float leaf = 0.f; float* d_out = nullptr;
                      rgck::LeafGrid g{};  // the leaf grid the pending filter was enqueued on
-                     int n_out = 0; } vg_pend;
+                     int n_out = 0;
+                     rgc_vg_route route{};  // what rgc_voxelgrid_route reports once the pending filter is ended
+                     } vg_pend;
+  rgc_vg_route vg_route{};  // the last finished leaf filter (rgc_voxelgrid_route)
   hipEvent_t vg_done = nullptr;
   int* h_vg = nullptr;  // pinned: the pending filter's three result ints (h_small's words are all taken: the front-end stages 16 ints at +32)
   DevBuf fe[34];              // front-end buffers
@@ -2718,7 +2721,7 @@ int rgc_align_end_reframe(rgc_ctx* c, rgc_ctx* next, double Tw[16], const float*
 // h_result (nullable): the chain is only ENQUEUED -- its three result ints go to h_result (pinned), c->vg_done is recorded behind the
 // copy, and the caller picks them up later (rgc_voxelgrid_begin / _end); flags / n_out are not written then.
 static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, float inv, const rgck::LeafGrid& g, int edge, bool dense, float* d_out,
-                          int* flags, int* n_out, int* h_result = nullptr) {
+                          int* flags, int* n_out, rgc_vg_route* rt, int* h_result = nullptr) {
   hipStream_t s = c->stream;
   int* dsm = c->d_small + 24;
   int* hsm = c->h_small + 24;
@@ -2754,9 +2757,12 @@ static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, fl
   cl.cnt_clean = std::max(cl.cnt_clean, nr1);  // (what lies beyond this call's rows was not touched: the scan's and the map's filter take turns)
   if (!c->vg_flags_clean) HIPCHK(c, hipMemsetAsync(dsm + 6, 0, sizeof(int), s));
   c->vg_flags_clean = false;
-  rgck::vg_rows(s, d_in, stride_f, n, inv, g, edge, seg_shift, (int*)cl.cell_of.p, (int*)cl.slot_of.p, (int*)c->vg_pos.p, (int*)cl.cnt.p, (int*)cl.start.p,
-                cl.block_sums.p, (unsigned long long*)c->vg_tmp.p, (int*)c->vg_order.p, (unsigned long long*)c->vg_leaf.p,
-                (int*)((char*)cl.block_sums.p + row_bs), d_out, dsm + 5);
+  const bool packed = rgck::vg_rows(s, d_in, stride_f, n, inv, g, edge, seg_shift, (int*)cl.cell_of.p, (int*)cl.slot_of.p, (int*)c->vg_pos.p, (int*)cl.cnt.p,
+                                    (int*)cl.start.p, cl.block_sums.p, (unsigned long long*)c->vg_tmp.p, (int*)c->vg_order.p, (unsigned long long*)c->vg_leaf.p,
+                                    (int*)((char*)cl.block_sums.p + row_bs), d_out, dsm + 5);
+  rt->chain = 1; rt->leaf_buckets = dense ? 1 : 0; rt->seg_shift = seg_shift; rt->nseg = rgck::vg_segments(g, seg_shift); rt->packed = packed ? 1 : 0;
+  rt->edge = edge; rt->flags = 0;
+  for (int a = 0; a < 3; a++) { rt->minb[a] = g.minb[a]; rt->div[a] = g.div[a]; }
   if (h_result) {  // (the finished chain leaves the flag word zeroed: the next chain on this stream finds it so)
     HIPCHK(c, hipMemcpyAsync(h_result, dsm + 5, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipEventRecord(c->vg_done, s));
@@ -2768,6 +2774,7 @@ static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, fl
   c->vg_flags_clean = true;
   *flags = hsm[5];
   *n_out = hsm[7];
+  rt->flags = hsm[5];
   return RGC_OK;
 }
 static bool vg_rows_fit(const rgck::LeafGrid& g, int n) {  // sparse enough for the sort over rows (else: over the leaves)
@@ -2775,11 +2782,8 @@ static bool vg_rows_fit(const rgck::LeafGrid& g, int n) {  // sparse enough for 
   return ncell <= 2147483647.0 && ncell > 64.0 * (double)n && nrows <= 64.0e6;
 }
 
-int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device) {
-  if (!c || !xyzi || !out_xyzi || !n_out || n < 0) return RGC_ERR_INVALID;
-  if (stride_bytes < 12 || (stride_bytes & 3) || stride_bytes > 4096 || !(leaf > 0.f) || !std::isfinite(leaf)) return fail(c, RGC_ERR_INVALID, "bad stride or leaf size");
-  *n_out = 0;
-  if (n == 0) return RGC_OK;
+// rgc_voxelgrid after its argument checks; rt: what rgc_voxelgrid_route reports, filled as the call goes (the caller adds status and n_out)
+static int voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt) {
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const float* d_in;
@@ -2805,6 +2809,7 @@ int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float 
   rgc_ctx::VgBox* box = nullptr;
   for (auto& b : c->vg_box) if (b.leaf == leaf) box = &b;
   bool done = false;
+  rt.kept_box = !box ? 0 : box->valid ? 2 : 3;
   if (box && box->valid) {
     // the box of an earlier cloud: no bounding-box pass, no read-back before the filter (the frames of a sequence span the same volume)
     const rgck::LeafGrid ps = padded(box->g, kPadSparse), pd = padded(box->g, kPadDense);
@@ -2812,13 +2817,19 @@ int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float 
     const double dcell = (double)pd.div[0] * (double)pd.div[1] * (double)pd.div[2];
     if (sparse || dcell <= (double)c->prm.max_cells) {
       int flags = 0, no = 0;
-      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, sparse ? ps : pd, (sparse ? kPadSparse : kPadDense) / 2, !sparse, d_out, &flags, &no))) return rc;
+      rt.kept_box = 1;
+      rt.path = RGC_VG_PATH_KEPT;
+      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, sparse ? ps : pd, (sparse ? kPadSparse : kPadDense) / 2, !sparse, d_out, &flags, &no, &rt))) return rc;
+      rt.kept_flags = flags;
       if (flags & 1) return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)");
-      if (flags & 6) box->valid = false;  // outside: measure and repeat now; near a face: measure at the next call
+      if (flags & 6) { box->valid = false; rt.box_invalidated = 1; }  // outside: measure and repeat now; near a face: measure at the next call
       if (!(flags & 2)) { *n_out = no; done = true; hint_from_leaf_grid(c, out_xyzi, no, sparse ? ps : pd, leaf); }
     }
   }
   if (!done) {
+    rt.repeated = rt.path == RGC_VG_PATH_KEPT ? 1 : 0;
+    rt.path = RGC_VG_PATH_MEASURED;
+    rt.chain = rt.leaf_buckets = rt.seg_shift = rt.nseg = rt.packed = rt.edge = rt.flags = 0;  // (of the chain on the kept box)
     int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
     memcpy(hsm, init, sizeof(init));
     c->vg_flags_clean = false;
@@ -2831,6 +2842,7 @@ int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float 
     rgck::LeafGrid g{};
     double ncell = 1.0;
     for (int a = 0; a < 3; a++) { g.minb[a] = hsm[a]; g.div[a] = hsm[3 + a] - hsm[a] + 1; ncell *= (double)g.div[a]; }
+    for (int a = 0; a < 3; a++) { rt.minb[a] = g.minb[a]; rt.div[a] = g.div[a]; }
     {  // keep the measured box for the next cloud of this leaf size
       if (!box) { box = &c->vg_box[c->vg_box_next]; c->vg_box_next = (c->vg_box_next + 1) % 4; box->leaf = leaf; }
       bool ok = ncell <= 2.0e9;
@@ -2840,18 +2852,19 @@ int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float 
     }
     if (ncell > 2147483647.0) {
       // PCL: "Leaf size is too small for the input dataset. Integer indices would overflow." -> output = input
+      rt.path = RGC_VG_PATH_UNFILTERED;
       rgck::transform_q(s, d_in, stride_f, n, rgck::Quat{0, 0, 0, 1}, (const double[3]){0, 0, 0}, d_out, 4);
       *n_out = n;
       HIPCHK(c, hipStreamSynchronize(s));
     } else if (vg_rows_fit(g, n)) {
       int flags = 0;
-      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, false, d_out, &flags, n_out))) return rc;
+      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, false, d_out, &flags, n_out, &rt))) return rc;
       hint_from_leaf_grid(c, out_xyzi, *n_out, g, leaf);
     } else {
       // a dense cloud: the same chain with the leaves themselves as the sort's buckets
       if (ncell > (double)c->prm.max_cells) return fail(c, RGC_ERR_GRID_TOO_LARGE, "leaf grid %d x %d x %d exceeds max_cells", g.div[0], g.div[1], g.div[2]);
       int flags = 0;
-      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, true, d_out, &flags, n_out))) return rc;
+      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, true, d_out, &flags, n_out, &rt))) return rc;
       hint_from_leaf_grid(c, out_xyzi, *n_out, g, leaf);
     }
   }
@@ -2860,6 +2873,25 @@ int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float 
     HIPCHK(c, hipStreamSynchronize(s));
   }
   HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+
+int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device) {
+  if (!c || !xyzi || !out_xyzi || !n_out || n < 0) return RGC_ERR_INVALID;
+  if (stride_bytes < 12 || (stride_bytes & 3) || stride_bytes > 4096 || !(leaf > 0.f) || !std::isfinite(leaf)) return fail(c, RGC_ERR_INVALID, "bad stride or leaf size");
+  *n_out = 0;
+  rgc_vg_route rt{};
+  rt.n = n;
+  const int rc = n == 0 ? RGC_OK : voxelgrid_run(c, xyzi, n, stride_bytes, leaf, out_xyzi, n_out, on_device, rt);
+  rt.status = rc;
+  rt.n_out = *n_out;
+  c->vg_route = rt;
+  return rc;
+}
+
+int rgc_voxelgrid_route(rgc_ctx* c, rgc_vg_route* out) {
+  if (!c || !out) return RGC_ERR_INVALID;
+  *out = c->vg_route;
   return RGC_OK;
 }
 
@@ -2889,16 +2921,22 @@ int rgc_voxelgrid_begin(rgc_ctx* c, const float* d_xyzi, int n, int stride_bytes
     const bool sparse = vg_rows_fit(ps, n);
     const double dcell = (double)pdg.div[0] * (double)pdg.div[1] * (double)pdg.div[2];
     if (sparse || dcell <= (double)c->prm.max_cells) {
+      pd_.route.n = n;
+      pd_.route.kept_box = 1;
+      pd_.route.path = RGC_VG_PATH_KEPT;
       int rc = voxelgrid_rows(c, d_xyzi, stride_bytes / 4, n, 1.0f / leaf, sparse ? ps : pdg, (sparse ? kPadSparse : kPadDense) / 2, !sparse, d_out, nullptr,
-                              nullptr, c->h_vg);
+                              nullptr, &pd_.route, c->h_vg);
       if (rc) return rc;
       pd_.g = sparse ? ps : pdg;
       enqueued = true;
     }
   }
   if (!enqueued) {  // no box to trust yet: the whole filter now
+    const rgc_vg_route last = c->vg_route;
     int rc = rgc_voxelgrid(c, d_xyzi, n, stride_bytes, leaf, d_out, &pd_.n_out, 1);
     if (rc) return rc;
+    pd_.route = c->vg_route;  // reported when this filter is ended; until then the context shows the filter before it
+    c->vg_route = last;
     pd_.ready = true;
   }
   pd_.active = true;
@@ -2910,16 +2948,23 @@ int rgc_voxelgrid_end(rgc_ctx* c, int* n_out) {
   rgc_ctx::VgPending& pd_ = c->vg_pend;
   if (!pd_.active) return fail(c, RGC_ERR_INVALID, "rgc_voxelgrid_end without rgc_voxelgrid_begin");
   pd_.active = false;
-  if (pd_.ready) { *n_out = pd_.n_out; return RGC_OK; }
+  if (pd_.ready) { *n_out = pd_.n_out; c->vg_route = pd_.route; return RGC_OK; }
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventSynchronize(c->vg_done));
   const int flags = c->h_vg[0], no = c->h_vg[2];
-  if (flags & 1) return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)");
+  rgc_vg_route& rt = pd_.route;
+  rt.flags = rt.kept_flags = flags;
+  if (flags & 1) { rt.status = RGC_ERR_NONFINITE; c->vg_route = rt; return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)"); }
   rgc_ctx::VgBox* box = nullptr;
   for (auto& b : c->vg_box) if (b.leaf == pd_.leaf) box = &b;
-  if (box && (flags & 6)) box->valid = false;  // outside: measure and repeat now; near a face: measure at the next call
-  if (!(flags & 2)) { *n_out = no; hint_from_leaf_grid(c, pd_.d_out, no, pd_.g, pd_.leaf); return RGC_OK; }
-  return rgc_voxelgrid(c, pd_.d_in, pd_.n, pd_.stride_bytes, pd_.leaf, pd_.d_out, n_out, 1);
+  if (box && (flags & 6)) { box->valid = false; rt.box_invalidated = 1; }  // outside: measure and repeat now; near a face: measure at the next call
+  if (!(flags & 2)) { *n_out = no; rt.n_out = no; c->vg_route = rt; hint_from_leaf_grid(c, pd_.d_out, no, pd_.g, pd_.leaf); return RGC_OK; }
+  const int rc = rgc_voxelgrid(c, pd_.d_in, pd_.n, pd_.stride_bytes, pd_.leaf, pd_.d_out, n_out, 1);  // (the kept box is invalid now: measured)
+  c->vg_route.repeated = 1;
+  c->vg_route.kept_box = 1;
+  c->vg_route.kept_flags = flags;
+  c->vg_route.box_invalidated = rt.box_invalidated;
+  return rc;
 }
 
 

@@ -309,14 +309,15 @@ void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int
   hipLaunchKernelGGL(k_vg_bbox, dim3(min(nblk(n, 256), 1024)), dim3(256), 0, s, in, stride_f, n, inv, mm6, flags);
 }
 int vg_segments(const LeafGrid& g, int seg_shift) { return seg_shift >= 31 ? 1 : (int)(((long long)g.div[0] + (1ll << seg_shift) - 1) >> seg_shift); }
-void vg_rows(hipStream_t s, const float* in, int stride_f, int n, float inv, LeafGrid g, int edge, int seg_shift, int* row_of, int* lx, int* slot_then_pos, int* cnt,
+bool vg_rows(hipStream_t s, const float* in, int stride_f, int n, float inv, LeafGrid g, int edge, int seg_shift, int* row_of, int* lx, int* slot_then_pos, int* cnt,
              int* start, void* row_block_sums, unsigned long long* tmp, int* order, unsigned long long* leaf, int* head_block_sums, float* out,
              int* res) {
   const int nseg = vg_segments(g, seg_shift);
   const int nr1 = g.div[1] * g.div[2] * nseg + 1;
   hipLaunchKernelGGL(k_vg_rows_count, dim3(nblk(n, 256)), dim3(256), 0, s, in, stride_f, n, inv, g, edge, seg_shift, nseg, row_of, lx, cnt, slot_then_pos, res + 1);
   scan_cells(s, cnt, start, nr1, row_block_sums, nullptr, nullptr, 0, nullptr);
-  if ((seg_shift <= 13 || g.div[0] <= (1 << 13)) && n <= (1 << kVgIdxBits)) {  // (the packed record holds 13 bits of leaf x inside the bucket and 27 of point index)
+  const bool packed = (seg_shift <= 13 || g.div[0] <= (1 << 13)) && n <= (1 << kVgIdxBits);
+  if (packed) {  // (the packed record holds 13 bits of leaf x inside the bucket and 27 of point index)
     hipLaunchKernelGGL(k_vg_rows_place<true>, dim3(nblk(n, 256)), dim3(256), 0, s, n, row_of, lx, slot_then_pos, start, tmp);
     hipLaunchKernelGGL(k_vg_rows_rank<true>, dim3(nblk(n, 256)), dim3(256), 0, s, n, row_of, start, tmp, order, leaf);
   } else {
@@ -325,6 +326,7 @@ void vg_rows(hipStream_t s, const float* in, int stride_f, int n, float inv, Lea
   }
   hipLaunchKernelGGL(k_vg_rows_heads, dim3(nblk(n, VG_SCAN_B)), dim3(VG_SCAN_T), 0, s, leaf, n, slot_then_pos, head_block_sums);
   hipLaunchKernelGGL(k_vg_rows_centroid, dim3(nblk(n, 256)), dim3(256), 0, s, in, stride_f, n, order, leaf, slot_then_pos, head_block_sums, out, res);
+  return packed;
 }
 
 

@@ -54,6 +54,12 @@ class Preprocessor:
         self._chk(self._L.rgc_voxelgrid(self._h, a.ctypes.data, a.shape[0], a.strides[0], float(leaf), out.ctypes.data, C.byref(n), 0))
         return out[:n.value].copy()
 
+    def voxelGridRoute(self):
+        """what the last voxelGridFilter on this object did (rgc_voxelgrid_route), as a dict of the rgc_vg_route fields"""
+        r = _lib.VgRoute()
+        self._chk(self._L.rgc_voxelgrid_route(self._h, C.byref(r)))
+        return {k: (list(getattr(r, k)) if k in ("minb", "div") else int(getattr(r, k))) for k, _ in _lib.VgRoute._fields_}
+
     def transformPointCloud(self, xyzi, q_xyzw, t):
         """RGC_odometer.cpp:1495-1514."""
         a = np.ascontiguousarray(xyzi, dtype=np.float32)

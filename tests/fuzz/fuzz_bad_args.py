@@ -54,6 +54,7 @@ feat = np.zeros((500, 4), np.float32); feat[:, :3] = tgt[:500]
 fac8, n_valid, kid, n_ev = np.zeros(500 * 8), np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
 big_out = np.zeros((4 * nt + 64, 4), np.float32)
 fe_p = _lib.FeParams(16, 0.5, 80.0, 1)
+vg_route = _lib.VgRoute()
 fe_o = _lib.FeOut()      # (the optional per-point outputs NULL; the feature clouds need room)
 fe_sharp, fe_flat, fe_inten = (np.zeros((nt, 5), np.float32) for _ in range(3))
 fp_ = C.POINTER(C.c_float)
@@ -81,6 +82,7 @@ def cases():
     # (the last argument of these three says which memory the pointers are in: a caller who gets THAT wrong hands device code a host address --
     #  nothing a library can check for the price of a call; left alone)
     yield "rgc_voxelgrid", [vp, vp, ci, ci, cf, vp, vp, ci], [h, P(xyzi), nt, 16, 0.3, P(vg_out), P(n_out), 0], (7,)
+    yield "rgc_voxelgrid_route", [vp, vp], [h, C.addressof(vg_route)]
     yield "rgc_deskew", [vp, vp, ci, ci, vp, vp, ci], [h, P(deskew_buf), nt, 16, P(q4), P(t3), 0], (6,)
     yield "rgc_transform_cloud", [vp, vp, ci, ci, vp, vp, vp, ci], [h, P(xyzi), nt, 16, P(q4), P(t3), P(vg_out), 0], (7,)
     # ---- the rows either side: wire, loop-closure ICP, the mapping node's registration, the resident map ----

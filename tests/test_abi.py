@@ -67,6 +67,7 @@ def test_null_arguments_are_rejected_without_a_gpu(lib):
     assert L.rgc_align_end(None, None, None, None, None, None, None) == -1
     assert L.rgc_share_target(None, None) == -1
     assert L.rgc_align(None, g, None, None, None, None, None, None) == -1
+    assert L.rgc_voxelgrid_route(None, C.byref(lib.VgRoute())) == -1
 
 
 def test_knob_inventory_is_current():
@@ -188,7 +189,7 @@ def test_python_mirror_struct_layouts_match_the_header(lib, tmp_path):
     pairs = {"rgc_params": lib.Params, "rgc_stats": lib.Stats, "rgc_fuse_in": lib.FuseIn, "rgc_imu_filter": lib.ImuFilter, "rgc_ground_gate": lib.GroundGate,
              "rgc_fe_params": lib.FeParams, "rgc_fe_out": lib.FeOut, "rgc_mapreg_report": lib.MapregReport, "rgc_icp_params": lib.IcpParams,
              "rgc_icp_result": lib.IcpResult, "rgc_pc2_layout": lib.Pc2Layout, "rgc_pc2_field": lib.Pc2Field, "rgc_mapreg_ground": lib.MapregGround,
-             "rgc_mapreg_imu": lib.MapregImu, "rgc_map_info": lib.MapInfo}
+             "rgc_mapreg_imu": lib.MapregImu, "rgc_map_info": lib.MapInfo, "rgc_vg_route": lib.VgRoute}
     h = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rgc_hip.h")).read(), flags=re.S)
     fields = {}
     for m in re.finditer(r"typedef struct (rgc_\w+)\s*\{(.*?)\}\s*\1\s*;", h, re.S):
