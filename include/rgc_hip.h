@@ -610,6 +610,65 @@ RGC_API int rgc_map_get_info(rgc_ctx* ctx, rgc_map_info* out);
 /* which = 0: the stored keyframe points, 1: the committed target; up to cap points (x,y,z,intensity) to the host, *n = total */
 RGC_API int rgc_map_download(rgc_ctx* ctx, int which, float* out_xyzi, int cap, int* n);
 
+/* ---- f5: the mapping node's keyframe store resident on the device, with batched sub-map assembly ----
+ * The mapping node keeps, per keyframe, a BODY-frame corner / surf / scan cloud (cornerCloudKeyFrames, surfCloudKeyFrames,
+ * scanCloudKeyFrames) and a 6-DoF key pose (cloudKeyPoses6D) that the pose graph keeps correcting (correctKeyFramePoseGraph,
+ * src/RGC_mapping.cpp:1618-1686), and assembles the clouds it registers against from them in three places: the surrounding maps of f1
+ * (extractSurroundingKeyFramesAndMap, :1503-1616), the source and target of f4 (detectLoopClosure, :2180-2216) and the global map
+ * (publishGlobalMap, :2508-2537).  Each is: for every selected keyframe transformPointCloud(cloud, &pose6D) (:2567-2612), concatenated
+ * in selection order, then a pcl::VoxelGrid.  Here the keyframes stay in HBM in their body frames, the poses are mutable, and ONE launch
+ * transforms any selection under the CURRENT poses; rgc_mapreg_set_maps_device / rgc_icp_align_device consume the result where it lies.
+ * (The odometer's rgc_map_* store above holds world-frame points and cannot move a keyframe.)
+ *   Points: a keyframe's clouds are stored as 16-byte points {x, y, z, c} in the body frame; c is whatever the caller keeps in the fourth
+ * float (intensity for scans, normal_x for features: both are copied by :2585,2608-2609).  Input stride >= 16, host or device memory
+ * (on_device: every cloud pointer of the call); a kind may be empty (n = 0, pointer NULL).  Ids are the caller's (cloudKeyPoses3D's
+ * intensity, :1876,1584); pushing an id twice is RGC_ERR_INVALID.  Storage grows geometrically, earlier keyframes keep their content; a kind
+ * holds at most 2^27 points.  A host cloud is on the device when rgc_kf_push returns, a device cloud is read in stream order on
+ * rgc_stream(ctx).
+ *   Poses: rgc_kf_pose = PointXYZIRPYT's x, y, z, roll, pitch, yaw (include/rgc_slam/utility.h:284-293), radians.  The rotation is computed
+ * on the HOST in fp64 by the reference's chain (:2575-2576): float roll / pitch / yaw -> * rad2deg (180.0 / M_PI, :197) -> Utility::ypr2R
+ * in degrees (utility.h:123-147: rgc_ypr2R) -> Eigen quaternion; the device then applies q * p + t with rgc_transform_cloud's
+ * arithmetic (:2581), so that assembling ONE keyframe equals rgc_transform_cloud with that quaternion bit for bit.  A non-finite pose is
+ * RGC_ERR_NONFINITE at rgc_kf_push / rgc_kf_set_poses, and the store is as it was.
+ *   rgc_kf_assemble: for each id IN THE ORDER GIVEN (an id may repeat), for each kind in kind_mask (bit k = kind k) in ASCENDING kind
+ * order, the keyframe's points in stored order.  {CORNER} and {SURF} separately give the surrounding maps (:1584-1602), {CORNER, SURF}
+ * the loop clouds (:2186-2191, 2209-2214) and the global map (:2516-2521), {SCAN} the global scan map (:2526).  *n_raw = points before
+ * the filter.  leaf > 0: the concatenation goes through the library's leaf filter on the device (rgc_voxelgrid: same output, same
+ * refusals, rgc_voxelgrid_route tells); leaf <= 0: the concatenation itself.  *n_out points {x, y, z, c} are written to out_xyzc (host,
+ * or 16-byte aligned device memory if on_device; stream-ordered then, like rgc_transform_cloud).  cap (points) too small -- below n_raw
+ * without a filter, below n_out with one -- is RGC_ERR_INVALID with *n_raw / *n_out still reported, nothing written: size the buffer and
+ * call again (cap = 0 with out_xyzc NULL asks for the counts).  An id that is not in the store, kind_mask outside 1..7, a selection
+ * of more than 2^27 points: RGC_ERR_INVALID, nothing written.  n_ids = 0 is an empty cloud.
+ *   ALWAYS the current poses: the reference caches the transformed surrounding clouds by id (:1551-1595) and so keeps a stale transform
+ * for a keyframe that stays in the neighbourhood across a pose-graph correction; that quirk is NOT reproduced.
+ *   State machine: the rgc_kf_* calls touch the store, staging of their own, the leaf filter's scratch and the caller's output -- never a
+ * cloud or a solve of the registration.  With a solve in flight (rgc_align_begin .. rgc_align_end) every one of them RUNS, and the solve's
+ * result is what it would have been (rgc_kf_assemble waits for the context's stream like rgc_voxelgrid does). */
+enum { RGC_KF_CORNER = 0, RGC_KF_SURF = 1, RGC_KF_SCAN = 2, RGC_KF_KINDS = 3 };
+typedef struct rgc_kf_pose { float x, y, z, roll, pitch, yaw; } rgc_kf_pose;
+typedef struct rgc_kf_info {
+  int n_keyframes;
+  long long n_points[3];         /* body-frame points held, per kind */
+  unsigned long long revision;   /* bumped by every push / set_poses / reset that changed the store */
+} rgc_kf_info;
+/* drops every keyframe (the buffers are kept) */
+RGC_API int rgc_kf_reset(rgc_ctx* ctx);
+/* cornerCloudKeyFrames / surfCloudKeyFrames / scanCloudKeyFrames [keyFrameNum] = ... and cloudKeyPoses6D->push_back (src/RGC_mapping.cpp:1909-1924) */
+RGC_API int rgc_kf_push(rgc_ctx* ctx, int id, const rgc_kf_pose* pose, const float* corner, int n_corner, const float* surf, int n_surf,
+                        const float* scan, int n_scan, int stride_bytes, int on_device);
+/* correctKeyFramePoseGraph (src/RGC_mapping.cpp:1618-1686): new poses for n keyframes; all or nothing (an unknown id, a non-finite pose: no
+ * pose changes).  n = 0 is a no-op. */
+RGC_API int rgc_kf_set_poses(rgc_ctx* ctx, const int* ids, const rgc_kf_pose* poses, int n);
+RGC_API int rgc_kf_get_info(rgc_ctx* ctx, rgc_kf_info* out);
+RGC_API int rgc_kf_assemble(rgc_ctx* ctx, const int* ids, int n_ids, unsigned kind_mask, float leaf, float* out_xyzc, int cap, int on_device,
+                            int* n_raw, int* n_out);
+/* rgc_mapreg_set_maps for maps that lie on the context's device (what rgc_kf_assemble(..., on_device = 1) wrote): the same checks, the same
+ * grids, bit for bit, minus the upload.  The buffers are read in stream order on rgc_stream(ctx) and not kept. */
+RGC_API int rgc_mapreg_set_maps_device(rgc_ctx* ctx, const float* d_corner, int n_corner, const float* d_surf, int n_surf, int stride_bytes);
+/* rgc_icp_align for a source and a target on the context's device: the same checks, the same result, bit for bit, minus the uploads */
+RGC_API int rgc_icp_align_device(rgc_ctx* ctx, const float* d_source, int n_source, const float* d_target, int n_target, int stride_bytes,
+                                 const rgc_icp_params* params, float final_T[16], rgc_icp_result* result);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

@@ -102,6 +102,18 @@ class MapInfo(C.Structure):
                 ("oldest_id", C.c_int), ("newest_id", C.c_int), ("origin", C.c_double * 3)]
 
 
+class KfPose(C.Structure):
+    """rgc_kf_pose: PointXYZIRPYT's pose fields, radians"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("roll", C.c_float), ("pitch", C.c_float), ("yaw", C.c_float)]
+
+
+class KfInfo(C.Structure):
+    _fields_ = [("n_keyframes", C.c_int), ("n_points", C.c_longlong * 3), ("revision", C.c_ulonglong)]
+
+
+KF_CORNER, KF_SURF, KF_SCAN, KF_KINDS = 0, 1, 2, 3
+
+
 class VgRoute(C.Structure):
     """rgc_vg_route: what the last leaf filter on a context did (rgc_voxelgrid_route)"""
     _fields_ = [("path", C.c_int), ("status", C.c_int), ("repeated", C.c_int), ("kept_box", C.c_int), ("kept_flags", C.c_int), ("box_invalidated", C.c_int),
@@ -127,7 +139,7 @@ SYMBOLS = [
     "rgc_clear_source", "rgc_clear_target", "rgc_swap_source_and_target", "rgc_get_voxels",
     "rgc_get_stats", "rgc_device_alloc", "rgc_device_free", "rgc_host_alloc", "rgc_host_free", "rgc_upload", "rgc_download", "rgc_synchronize",
     "rgc_stream", "rgc_default_fe_params", "rgc_frontend", "rgc_extract_pose", "rgc_imu_preintegrate", "rgc_imu_filter_init", "rgc_imu_filter_push", "rgc_ground_gate_init", "rgc_ground_gate_remember", "rgc_ground_gate_step", "rgc_default_fuse_in", "rgc_fuse_pose", "rgc_compose_pose",
-    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
+    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_kf_reset", "rgc_kf_push", "rgc_kf_set_poses", "rgc_kf_get_info", "rgc_kf_assemble", "rgc_mapreg_set_maps_device", "rgc_icp_align_device", "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
 _lib = None
@@ -292,6 +304,13 @@ def load():
     L.rgc_map_commit.argtypes = [vp, C.c_float, ip]
     L.rgc_map_get_info.argtypes = [vp, C.POINTER(MapInfo)]
     L.rgc_map_download.argtypes = [vp, C.c_int, vp, C.c_int, ip]
+    L.rgc_kf_reset.argtypes = [vp]
+    L.rgc_kf_push.argtypes = [vp, C.c_int, C.POINTER(KfPose), vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
+    L.rgc_kf_set_poses.argtypes = [vp, ip, C.POINTER(KfPose), C.c_int]
+    L.rgc_kf_get_info.argtypes = [vp, C.POINTER(KfInfo)]
+    L.rgc_kf_assemble.argtypes = [vp, ip, C.c_int, C.c_uint, C.c_float, vp, C.c_int, C.c_int, ip, ip]
+    L.rgc_mapreg_set_maps_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int]
+    L.rgc_icp_align_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(IcpParams), fp, C.POINTER(IcpResult)]
     L.rgc_profile_enable.argtypes = [vp, C.c_int]
     L.rgc_profile_select.argtypes = [vp, C.c_uint]
     L.rgc_profile_reset.argtypes = [vp]

@@ -1,0 +1,132 @@
+// keyframe_store.hpp -- header-only C++ adaptor over the C-ABI (include/rgc_hip.h, rgc_kf_*): the mapping node's keyframe store kept on
+// the device.  Stands in for cornerCloudKeyFrames / surfCloudKeyFrames / scanCloudKeyFrames + cloudKeyPoses6D and for the three loops that
+// assemble a cloud from them with transformPointCloud per keyframe, `+=` and a pcl::VoxelGrid
+// (rgc_slam/src/RGC_mapping.cpp:1503-1616, 2180-2216, 2508-2537), WITHOUT requiring PCL/Eigen at build time:
+//
+//   rgc::KeyframeStore store(ctx);                         // in the context that consumes its clouds (FastVGICPHip::context()), or its own
+//   store.push(keyFrameNum, pose6D, corner, surf, scan);   // any cloud with ->points / ->size() of 16-byte-or-wider x,y,z,c points
+//   store.setPoses(ids, poses);                            // correctKeyFramePoseGraph (:1618-1686)
+//   rgc::DeviceCloud target = store.assembleDevice(ids, rgc::KeyframeStore::CORNER | rgc::KeyframeStore::SURF, 0.4f);
+//   rgc_icp_align_device(ctx, source.data(), source.size(), target.data(), target.size(), 16, &icp_params, T, &result);
+//
+// Errors throw std::runtime_error carrying rgc_last_error().  No CPU fallback.
+#pragma once
+#include <cstddef>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/rgc_hip.h"
+
+namespace rgc {
+
+// n points {x, y, z, c} in device memory of a context; frees them with the object
+class DeviceCloud {
+public:
+  DeviceCloud() = default;
+  DeviceCloud(rgc_ctx* ctx, float* d, int n, int n_raw) : ctx_(ctx), d_(d), n_(n), n_raw_(n_raw) {}
+  ~DeviceCloud() { reset(); }
+  DeviceCloud(const DeviceCloud&) = delete;
+  DeviceCloud& operator=(const DeviceCloud&) = delete;
+  DeviceCloud(DeviceCloud&& o) noexcept : ctx_(o.ctx_), d_(o.d_), n_(o.n_), n_raw_(o.n_raw_) { o.d_ = nullptr; o.n_ = o.n_raw_ = 0; }
+  DeviceCloud& operator=(DeviceCloud&& o) noexcept {
+    if (this != &o) { reset(); ctx_ = o.ctx_; d_ = o.d_; n_ = o.n_; n_raw_ = o.n_raw_; o.d_ = nullptr; o.n_ = o.n_raw_ = 0; }
+    return *this;
+  }
+  const float* data() const { return d_; }
+  int size() const { return n_; }          // points after the leaf filter (or of the concatenation)
+  int rawSize() const { return n_raw_; }   // points before it
+  std::vector<float> download() const {
+    std::vector<float> h((std::size_t)n_ * 4);
+    if (n_ > 0 && rgc_download(ctx_, h.data(), d_, h.size() * sizeof(float)) != RGC_OK) throw std::runtime_error(std::string("rgc_download: ") + rgc_last_error(ctx_));
+    return h;
+  }
+
+private:
+  void reset() { if (d_) (void)rgc_device_free(ctx_, d_); d_ = nullptr; }
+  rgc_ctx* ctx_ = nullptr;
+  float* d_ = nullptr;
+  int n_ = 0, n_raw_ = 0;
+};
+
+class KeyframeStore {
+public:
+  enum Kind : unsigned { CORNER = 1u << RGC_KF_CORNER, SURF = 1u << RGC_KF_SURF, SCAN = 1u << RGC_KF_SCAN };
+
+  // a store in an existing context (not owned: it must outlive the store) ...
+  explicit KeyframeStore(rgc_ctx* ctx) : ctx_(ctx), own_(false) {
+    if (!ctx) throw std::runtime_error("rgc::KeyframeStore: null context");
+  }
+  // ... or in a context of its own
+  explicit KeyframeStore(int hip_device = 0) : own_(true) {
+    const int rc = rgc_create(hip_device, nullptr, &ctx_);
+    if (rc != RGC_OK) throw std::runtime_error(std::string("rgc_create: ") + rgc_status_string(rc));
+  }
+  ~KeyframeStore() { if (own_) rgc_destroy(ctx_); }
+  KeyframeStore(const KeyframeStore&) = delete;
+  KeyframeStore& operator=(const KeyframeStore&) = delete;
+
+  rgc_ctx* context() { return ctx_; }
+  void reset() { chk(rgc_kf_reset(ctx_)); }
+
+  // body-frame clouds, host memory (on_device = false) or device memory of the context; a kind may be empty (nullptr, 0)
+  void push(int id, const rgc_kf_pose& pose, const float* corner, int n_corner, const float* surf, int n_surf, const float* scan, int n_scan,
+            int stride_bytes, bool on_device = false) {
+    chk(rgc_kf_push(ctx_, id, &pose, corner, n_corner, surf, n_surf, scan, n_scan, stride_bytes, on_device ? 1 : 0));
+  }
+  // pcl-style clouds: anything with ->points[i].x and ->points.size(), all three of one point type; a null pointer is an empty kind
+  template <class CloudPtr>
+  void push(int id, const rgc_kf_pose& pose, const CloudPtr& corner, const CloudPtr& surf, const CloudPtr& scan) {
+    push(id, pose, first(corner), count(corner), first(surf), count(surf), first(scan), count(scan), (int)sizeof(corner->points[0]));
+  }
+  // PointXYZIRPYT-like poses (x, y, z, roll, pitch, yaw members)
+  template <class Pose6D>
+  static rgc_kf_pose pose(const Pose6D& p) { return rgc_kf_pose{(float)p.x, (float)p.y, (float)p.z, (float)p.roll, (float)p.pitch, (float)p.yaw}; }
+
+  void setPoses(const std::vector<int>& ids, const std::vector<rgc_kf_pose>& poses) {
+    if (ids.size() != poses.size()) throw std::runtime_error("rgc::KeyframeStore::setPoses: one pose per id");
+    chk(rgc_kf_set_poses(ctx_, ids.data(), poses.data(), (int)ids.size()));
+  }
+  rgc_kf_info info() { rgc_kf_info i; chk(rgc_kf_get_info(ctx_, &i)); return i; }
+
+  // the selection's point count before the filter (nothing runs on the device)
+  int rawSize(const std::vector<int>& ids, unsigned kind_mask) {
+    int n_raw = 0, n_out = 0;
+    const int rc = rgc_kf_assemble(ctx_, ids.data(), (int)ids.size(), kind_mask, 0.f, nullptr, 0, 0, &n_raw, &n_out);
+    if (rc != RGC_OK && n_raw == 0) chk(rc);
+    return n_raw;
+  }
+  // n x 4 floats on the host
+  std::vector<float> assemble(const std::vector<int>& ids, unsigned kind_mask, float leaf = 0.f) {
+    const int cap = rawSize(ids, kind_mask);
+    std::vector<float> out((std::size_t)cap * 4);
+    int n_raw = 0, n_out = 0;
+    chk(rgc_kf_assemble(ctx_, ids.data(), (int)ids.size(), kind_mask, leaf, cap ? out.data() : nullptr, cap, 0, &n_raw, &n_out));
+    out.resize((std::size_t)n_out * 4);
+    return out;
+  }
+  // the same cloud left on the device, for rgc_icp_align_device / rgc_mapreg_set_maps_device / rgc_set_target_device on this context
+  DeviceCloud assembleDevice(const std::vector<int>& ids, unsigned kind_mask, float leaf = 0.f) {
+    const int cap = rawSize(ids, kind_mask);
+    void* d = nullptr;
+    chk(rgc_device_alloc(ctx_, (std::size_t)(cap > 0 ? cap : 1) * 16, &d));
+    int n_raw = 0, n_out = 0;
+    const int rc = rgc_kf_assemble(ctx_, ids.data(), (int)ids.size(), kind_mask, leaf, (float*)d, cap, 1, &n_raw, &n_out);
+    if (rc != RGC_OK) { (void)rgc_device_free(ctx_, d); chk(rc); }
+    return DeviceCloud(ctx_, (float*)d, n_out, n_raw);
+  }
+
+private:
+  template <class CloudPtr>
+  static const float* first(const CloudPtr& c) { return c && !c->points.empty() ? &c->points[0].x : nullptr; }
+  template <class CloudPtr>
+  static int count(const CloudPtr& c) { return c ? (int)c->points.size() : 0; }
+  void chk(int rc) {
+    if (rc != RGC_OK) throw std::runtime_error(std::string("rgc_hip: ") + rgc_status_string(rc) + ": " + rgc_last_error(ctx_));
+  }
+  rgc_ctx* ctx_ = nullptr;
+  bool own_ = false;
+};
+
+}  // namespace rgc

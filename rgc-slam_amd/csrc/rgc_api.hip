@@ -19,6 +19,7 @@
 #include <chrono>
 #include <mutex>
 #include <new>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -281,6 +282,20 @@ struct rgc_ctx {
   float map_leaf = 0.f;
   int map_ntarget = 0;
   unsigned long long map_rev = 0;
+  // f5: the mapping node's keyframe store.  Body-frame points (x,y,z,c, 16 B) per kind in kf_store[kind], a keyframe's clouds as one
+  // contiguous run each; the key poses (and the quaternions the reference's chain makes of them) stay on the host and travel with every
+  // assembly's segment table.
+  struct KfRec { int id; size_t off[RGC_KF_KINDS]; int n[RGC_KF_KINDS]; rgc_kf_pose pose; double q[4]; };
+  DevBuf kf_store[RGC_KF_KINDS];
+  size_t kf_n[RGC_KF_KINDS] = {0, 0, 0};
+  std::vector<KfRec> kf;
+  std::unordered_map<int, int> kf_index;   // id -> position in kf
+  unsigned long long kf_rev = 0;
+  DevBuf kf_table, kf_raw, kf_filt;        // the segment table on the device; the unfiltered / filtered assembly when it is not written to the caller's buffer
+  unsigned char* kf_h_table = nullptr;     // pinned staging of the segment table
+  size_t kf_h_cap = 0;
+  hipEvent_t kf_uploaded = nullptr;        // recorded behind the table's copy: the staging is rewritten only after it
+  bool kf_upload_pending = false;
   rgc_stats stats{};
   // profiling
   bool prof_on = false;
@@ -291,6 +306,8 @@ struct rgc_ctx {
   double prof_ms[kProfKinds] = {0};
   long long prof_points[kProfKinds] = {0};
 };
+
+void rgc_host_key_pose_quat(float roll, float pitch, float yaw, double q_xyzw[4]);  // rgc_host.cpp: the reference's key pose -> quaternion chain (f5)
 
 namespace {
 
@@ -1592,6 +1609,7 @@ int rgc_create(int hip_device, const rgc_params* params, rgc_ctx** out) {
   ok = ok && hipEventCreateWithFlags(&c->tgt_prepared, kDevEvent) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->vg_done, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipHostMalloc((void**)&c->h_vg, 4 * sizeof(int), hipHostMallocDefault) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&c->kf_uploaded, hipEventDisableTiming) == hipSuccess;
   if (const char* e = getenv("RGC_SPEC_GRID")) c->spec_on = atoi(e) != 0;
   if (const char* e = getenv("RGC_KNN_SEEDS")) c->seeds_on = atoi(e) != 0;
   if (const char* e = getenv("RGC_KNN_CACHE")) c->cache_on = atoi(e) != 0;
@@ -1642,6 +1660,9 @@ void rgc_destroy(rgc_ctx* c) {
   release(c->fit_partials);
   if (c->vg_done) (void)hipEventDestroy(c->vg_done);
   if (c->h_vg) (void)hipHostFree(c->h_vg);
+  for (DevBuf* b : {&c->kf_store[0], &c->kf_store[1], &c->kf_store[2], &c->kf_table, &c->kf_raw, &c->kf_filt}) release(*b);
+  if (c->kf_h_table) (void)hipHostFree(c->kf_h_table);
+  if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->main_mark) (void)hipEventDestroy(c->main_mark);
@@ -3322,7 +3343,8 @@ const char* rgc_profile_name(int kind) {
 }
 
 // ---- f1: scan-to-map FEATURE registration of the mapping node (RGC_mapping.cpp:1069-1358) --------------------------------
-int rgc_mapreg_set_maps(rgc_ctx* c, const float* corner_map, int n_corner, const float* surf_map, int n_surf, int stride_bytes) {
+// rgc_mapreg_set_maps / rgc_mapreg_set_maps_device: one body; on_device: the maps are read where they lie instead of being uploaded first
+static int mapreg_set_maps_impl(rgc_ctx* c, const float* corner_map, int n_corner, const float* surf_map, int n_surf, int stride_bytes, bool on_device) {
   if (!c || !corner_map || !surf_map) return RGC_ERR_INVALID;
   if (stride_bytes < 12 || (stride_bytes & 3) || stride_bytes > 4096) return fail(c, RGC_ERR_INVALID, "stride_bytes must be a multiple of 4 and >= 12");
   if (n_corner < 5 || n_surf < 5) return fail(c, RGC_ERR_TOO_FEW_POINTS, "feature maps need at least 5 points each (5-NN)");
@@ -3334,15 +3356,26 @@ int rgc_mapreg_set_maps(rgc_ctx* c, const float* corner_map, int n_corner, const
     Cloud& cl = c->mr_map[m];
     cl.ready = false;
     const size_t bytes = (size_t)n[m] * stride_bytes;
-    int rc = ensure(c, cl.in_copy, bytes);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(cl.in_copy.p, src[m], bytes - (stride_bytes - 12), hipMemcpyHostToDevice, c->stream));
-    cl.in = (const float*)cl.in_copy.p;
+    int rc;
+    if (on_device) {
+      if ((rc = check_device_range(c, src[m], bytes - (stride_bytes - 12), "rgc_mapreg_set_maps_device: feature map"))) return rc;
+      cl.in = src[m];
+    } else {
+      if ((rc = ensure(c, cl.in_copy, bytes))) return rc;
+      HIPCHK(c, hipMemcpyAsync(cl.in_copy.p, src[m], bytes - (stride_bytes - 12), hipMemcpyHostToDevice, c->stream));
+      cl.in = (const float*)cl.in_copy.p;
+    }
     cl.stride_f = stride_bytes / 4;
     cl.n = n[m];
     if ((rc = prepare_map_grid(c, cl, kMapregCell[m]))) return rc;
   }
   return RGC_OK;
+}
+int rgc_mapreg_set_maps(rgc_ctx* c, const float* corner_map, int n_corner, const float* surf_map, int n_surf, int stride_bytes) {
+  return mapreg_set_maps_impl(c, corner_map, n_corner, surf_map, n_surf, stride_bytes, false);
+}
+int rgc_mapreg_set_maps_device(rgc_ctx* c, const float* d_corner, int n_corner, const float* d_surf, int n_surf, int stride_bytes) {
+  return mapreg_set_maps_impl(c, d_corner, n_corner, d_surf, n_surf, stride_bytes, true);
 }
 
 static int mapreg_upload_features(rgc_ctx* c, int slot, const float* feat, int n) {
@@ -3780,8 +3813,9 @@ void rgc_default_icp_params(rgc_icp_params* p) {
   p->euclidean_fitness_epsilon = 1e-6;        // :2055
 }
 
-int rgc_icp_align(rgc_ctx* c, const float* source, int ns, const float* target, int nt, int stride_bytes, const rgc_icp_params* prm,
-                  float final_T[16], rgc_icp_result* res) {
+// rgc_icp_align / rgc_icp_align_device: one body; on_device: source and target are read where they lie instead of being uploaded first
+static int icp_align_impl(rgc_ctx* c, const float* source, int ns, const float* target, int nt, int stride_bytes, const rgc_icp_params* prm,
+                          float final_T[16], rgc_icp_result* res, bool on_device) {
   if (!c || !source || !target || !prm || !final_T || !res) return RGC_ERR_INVALID;
   if (stride_bytes < 12 || (stride_bytes & 3) || stride_bytes > 4096) return fail(c, RGC_ERR_INVALID, "stride_bytes must be a multiple of 4 and >= 12");
   if (ns < 1 || nt < 1) return fail(c, RGC_ERR_TOO_FEW_POINTS, "ICP needs a non-empty source and target");
@@ -3796,16 +3830,21 @@ int rgc_icp_align(rgc_ctx* c, const float* source, int ns, const float* target, 
   tg.ready = false;
   {
     const size_t bytes = (size_t)nt * stride_bytes;
-    if ((rc = ensure(c, tg.in_copy, bytes))) return rc;
-    HIPCHK(c, hipMemcpyAsync(tg.in_copy.p, target, bytes - (stride_bytes - 12), hipMemcpyHostToDevice, s));
-    tg.in = (const float*)tg.in_copy.p;
+    if (on_device) {
+      if ((rc = check_device_range(c, target, bytes - (stride_bytes - 12), "rgc_icp_align_device: target"))) return rc;
+      tg.in = target;
+    } else {
+      if ((rc = ensure(c, tg.in_copy, bytes))) return rc;
+      HIPCHK(c, hipMemcpyAsync(tg.in_copy.p, target, bytes - (stride_bytes - 12), hipMemcpyHostToDevice, s));
+      tg.in = (const float*)tg.in_copy.p;
+    }
     tg.stride_f = stride_bytes / 4;
     tg.n = nt;
     if ((rc = prepare_map_grid(c, tg, 1.0))) return rc;
   }
   // the source as float4, transformed in place every iteration (pcl::transformPointCloud, fp32)
   const float* d_src;
-  if ((rc = stage_in(c, source, ns, stride_bytes, 0, &d_src))) return rc;  // the raw source, kept for the fitness score
+  if ((rc = stage_in(c, source, ns, stride_bytes, on_device ? 1 : 0, &d_src))) return rc;  // the raw source, kept for the fitness score
   if ((rc = ensure(c, c->pre_out, sizeof(float4) * (size_t)ns))) return rc;
   float4* cur = (float4*)c->pre_out.p;
   const rgck::PoseF I{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
@@ -3858,6 +3897,221 @@ int rgc_icp_align(rgc_ctx* c, const float* source, int ns, const float* target, 
   HIPCHK(c, hipGetLastError());
   res->fitness = c->h_out[0] / (double)ns;
   memcpy(final_T, fin, sizeof(fin));
+  return RGC_OK;
+}
+int rgc_icp_align(rgc_ctx* c, const float* source, int ns, const float* target, int nt, int stride_bytes, const rgc_icp_params* prm,
+                  float final_T[16], rgc_icp_result* res) {
+  return icp_align_impl(c, source, ns, target, nt, stride_bytes, prm, final_T, res, false);
+}
+int rgc_icp_align_device(rgc_ctx* c, const float* d_source, int ns, const float* d_target, int nt, int stride_bytes, const rgc_icp_params* prm,
+                         float final_T[16], rgc_icp_result* res) {
+  return icp_align_impl(c, d_source, ns, d_target, nt, stride_bytes, prm, final_T, res, true);
+}
+
+// ---- f5: the mapping node's keyframe store with batched sub-map assembly (src/RGC_mapping.cpp:1503-1616, 2180-2216, 2508-2537) ----------
+static bool kf_pose_finite(const rgc_kf_pose& p) {
+  return std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z) && std::isfinite(p.roll) && std::isfinite(p.pitch) && std::isfinite(p.yaw);
+}
+
+// room for `points` 16-byte points of one kind; the content held so far moves along (like map_reserve)
+static int kf_reserve(rgc_ctx* c, int kind, size_t points) {
+  DevBuf& b = c->kf_store[kind];
+  const size_t bytes = points * 16;
+  if (bytes <= b.cap && b.p) return RGC_OK;
+  void* np = nullptr;
+  const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 20);
+  HIPCHK(c, hipMalloc(&np, want));
+  if (b.p) {
+    if (c->kf_n[kind]) HIPCHK(c, hipMemcpyAsync(np, b.p, c->kf_n[kind] * 16, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipFree(b.p));
+  }
+  b.p = np;
+  b.cap = want;
+  return RGC_OK;
+}
+
+int rgc_kf_reset(rgc_ctx* c) {
+  if (!c) return RGC_ERR_INVALID;
+  if (!c->kf.empty()) c->kf_rev++;
+  c->kf.clear();
+  c->kf_index.clear();
+  for (int k = 0; k < RGC_KF_KINDS; k++) c->kf_n[k] = 0;
+  return RGC_OK;
+}
+
+int rgc_kf_push(rgc_ctx* c, int id, const rgc_kf_pose* pose, const float* corner, int n_corner, const float* surf, int n_surf, const float* scan,
+                int n_scan, int stride_bytes, int on_device) {
+  if (!c || !pose || n_corner < 0 || n_surf < 0 || n_scan < 0) return RGC_ERR_INVALID;
+  if ((n_corner && !corner) || (n_surf && !surf) || (n_scan && !scan)) return fail(c, RGC_ERR_INVALID, "rgc_kf_push: a cloud with points and no pointer");
+  if (stride_bytes < 16 || (stride_bytes & 3) || stride_bytes > 4096) return fail(c, RGC_ERR_INVALID, "a keyframe point is x,y,z,c: stride_bytes >= 16");
+  if (!kf_pose_finite(*pose)) return fail(c, RGC_ERR_NONFINITE, "rgc_kf_push: the key pose is not finite");
+  if (c->kf_index.count(id)) return fail(c, RGC_ERR_INVALID, "rgc_kf_push: keyframe %d is in the store already", id);
+  const float* src[RGC_KF_KINDS] = {corner, surf, scan};
+  const int n[RGC_KF_KINDS] = {n_corner, n_surf, n_scan};
+  for (int k = 0; k < RGC_KF_KINDS; k++)
+    if ((unsigned long long)c->kf_n[k] + (unsigned long long)n[k] > (1ull << 27)) return fail(c, RGC_ERR_INVALID, "the keyframe store would exceed 2^27 points of kind %d", k);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  for (int k = 0; k < RGC_KF_KINDS; k++) {
+    if (!n[k]) continue;
+    if (on_device && (rc = check_device_range(c, src[k], (size_t)n[k] * stride_bytes - (stride_bytes - 16), "rgc_kf_push: cloud"))) return rc;
+    if ((rc = kf_reserve(c, k, c->kf_n[k] + n[k]))) return rc;
+  }
+  rgc_ctx::KfRec rec{};
+  rec.id = id;
+  rec.pose = *pose;
+  rgc_host_key_pose_quat(pose->roll, pose->pitch, pose->yaw, rec.q);
+  bool copied = false;
+  for (int k = 0; k < RGC_KF_KINDS; k++) {
+    rec.off[k] = c->kf_n[k];
+    rec.n[k] = n[k];
+    if (!n[k]) continue;
+    char* dst = (char*)c->kf_store[k].p + c->kf_n[k] * 16;
+    const hipMemcpyKind dir = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (stride_bytes == 16) HIPCHK(c, hipMemcpyAsync(dst, src[k], (size_t)n[k] * 16, dir, c->stream));
+    else HIPCHK(c, hipMemcpy2DAsync(dst, 16, src[k], (size_t)stride_bytes, 16, (size_t)n[k], dir, c->stream));
+    copied = true;
+  }
+  if (copied && !on_device) HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's host buffers are the caller's again on return
+  for (int k = 0; k < RGC_KF_KINDS; k++) c->kf_n[k] += n[k];
+  c->kf_index[id] = (int)c->kf.size();
+  c->kf.push_back(rec);
+  c->kf_rev++;
+  return RGC_OK;
+}
+
+int rgc_kf_set_poses(rgc_ctx* c, const int* ids, const rgc_kf_pose* poses, int n) {
+  if (!c || n < 0 || (n && (!ids || !poses))) return RGC_ERR_INVALID;
+  for (int i = 0; i < n; i++) {
+    if (!c->kf_index.count(ids[i])) return fail(c, RGC_ERR_INVALID, "rgc_kf_set_poses: keyframe %d is not in the store", ids[i]);
+    if (!kf_pose_finite(poses[i])) return fail(c, RGC_ERR_NONFINITE, "rgc_kf_set_poses: the pose of keyframe %d is not finite", ids[i]);
+  }
+  for (int i = 0; i < n; i++) {
+    rgc_ctx::KfRec& r = c->kf[c->kf_index[ids[i]]];
+    r.pose = poses[i];
+    rgc_host_key_pose_quat(poses[i].roll, poses[i].pitch, poses[i].yaw, r.q);
+  }
+  if (n) c->kf_rev++;
+  return RGC_OK;
+}
+
+int rgc_kf_get_info(rgc_ctx* c, rgc_kf_info* out) {
+  if (!c || !out) return RGC_ERR_INVALID;
+  out->n_keyframes = (int)c->kf.size();
+  for (int k = 0; k < RGC_KF_KINDS; k++) out->n_points[k] = (long long)c->kf_n[k];
+  out->revision = c->kf_rev;
+  return RGC_OK;
+}
+
+int rgc_kf_assemble(rgc_ctx* c, const int* ids, int n_ids, unsigned kind_mask, float leaf, float* out_xyzc, int cap, int on_device, int* n_raw,
+                    int* n_out) {
+  if (!c || !n_raw || !n_out || n_ids < 0 || cap < 0 || (n_ids && !ids) || (cap && !out_xyzc)) return RGC_ERR_INVALID;
+  *n_raw = *n_out = 0;
+  if (kind_mask == 0 || kind_mask >= (1u << RGC_KF_KINDS)) return fail(c, RGC_ERR_INVALID, "rgc_kf_assemble: kind_mask must name one to three of the kinds (1..7)");
+  if (!std::isfinite(leaf)) return fail(c, RGC_ERR_INVALID, "rgc_kf_assemble: the leaf size is not finite");
+  if (on_device && (((uintptr_t)out_xyzc) & 15)) return fail(c, RGC_ERR_INVALID, "rgc_kf_assemble: a device output must be 16-byte aligned");
+  // the selection: one segment per (id, kind) that holds points, in the order given and in ascending kind order; counts first, nothing is touched
+  unsigned long long total = 0, blocks = 0;
+  size_t nseg = 0;
+  for (int i = 0; i < n_ids; i++) {
+    const auto it = c->kf_index.find(ids[i]);
+    if (it == c->kf_index.end()) return fail(c, RGC_ERR_INVALID, "rgc_kf_assemble: keyframe %d is not in the store", ids[i]);
+    const rgc_ctx::KfRec& r = c->kf[it->second];
+    for (int k = 0; k < RGC_KF_KINDS; k++)
+      if (((kind_mask >> k) & 1u) && r.n[k]) {
+        total += (unsigned long long)r.n[k];
+        blocks += ((unsigned long long)r.n[k] + rgck::kKfBlock - 1) / rgck::kKfBlock;
+        nseg++;
+      }
+  }
+  if (total > (1ull << 27)) return fail(c, RGC_ERR_INVALID, "rgc_kf_assemble: the selection has %llu points, the limit is 2^27", total);
+  const int nr = (int)total;
+  *n_raw = nr;
+  const bool filter = leaf > 0.f;
+  if (!filter) {
+    *n_out = nr;
+    if (nr > cap) return fail(c, RGC_ERR_INVALID, "rgc_kf_assemble: %d points, room for %d", nr, cap);
+  }
+  if (nr == 0) {
+    if (filter) { rgc_vg_route rt{}; c->vg_route = rt; }
+    return RGC_OK;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  int rc;
+  if (on_device && (rc = check_device_range(c, out_xyzc, (size_t)std::min(cap, nr) * 16, "rgc_kf_assemble: out_xyzc"))) return rc;
+  // where the concatenation is written: the caller's device buffer when it is the result, else a buffer of the store (the leaf filter's input,
+  // or the staging of a host result)
+  float4* d_raw = (float4*)out_xyzc;
+  if (filter || !on_device) {
+    if ((rc = ensure(c, c->kf_raw, (size_t)nr * 16))) return rc;
+    d_raw = (float4*)c->kf_raw.p;
+  }
+  // the segment table through pinned staging: [nseg segments][nseg + 1 first workgroups]
+  const size_t seg_bytes = nseg * sizeof(rgck::KfSegment), tab_bytes = seg_bytes + (nseg + 1) * sizeof(int);
+  if (c->kf_upload_pending) { HIPCHK(c, hipEventSynchronize(c->kf_uploaded)); c->kf_upload_pending = false; }
+  if (tab_bytes > c->kf_h_cap) {
+    if (c->kf_h_table) { HIPCHK(c, hipHostFree(c->kf_h_table)); c->kf_h_table = nullptr; c->kf_h_cap = 0; }
+    const size_t want = tab_bytes + tab_bytes / 2 + 4096;
+    HIPCHK(c, hipHostMalloc((void**)&c->kf_h_table, want, hipHostMallocDefault));
+    c->kf_h_cap = want;
+  }
+  if ((rc = ensure(c, c->kf_table, tab_bytes))) return rc;
+  rgck::KfSegment* hs = (rgck::KfSegment*)c->kf_h_table;
+  int* hb = (int*)(c->kf_h_table + seg_bytes);
+  size_t si = 0;
+  int out0 = 0, b0 = 0;
+  for (int i = 0; i < n_ids; i++) {
+    const rgc_ctx::KfRec& r = c->kf[c->kf_index.find(ids[i])->second];
+    for (int k = 0; k < RGC_KF_KINDS; k++) {
+      if (!((kind_mask >> k) & 1u) || !r.n[k]) continue;
+      rgck::KfSegment& S = hs[si];
+      S.src = (const float4*)c->kf_store[k].p + r.off[k];
+      S.n = r.n[k];
+      S.out0 = out0;
+      S.q = rgck::Quat{r.q[0], r.q[1], r.q[2], r.q[3]};
+      S.t[0] = (double)r.pose.x; S.t[1] = (double)r.pose.y; S.t[2] = (double)r.pose.z;   // Eigen::Vector3d t_temp(x, y, z), :2575
+      hb[si] = b0;
+      out0 += r.n[k];
+      b0 += (r.n[k] + rgck::kKfBlock - 1) / rgck::kKfBlock;
+      si++;
+    }
+  }
+  hb[nseg] = b0;
+  HIPCHK(c, hipMemcpyAsync(c->kf_table.p, c->kf_h_table, tab_bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipEventRecord(c->kf_uploaded, s));
+  c->kf_upload_pending = true;
+  if (c->main_has_target_prep && map_prep_finished(c)) c->main_has_target_prep = false;  // it has drained
+  rgck::kf_assemble(s, (const rgck::KfSegment*)c->kf_table.p, (const int*)((const char*)c->kf_table.p + seg_bytes), (int)nseg, (int)blocks, d_raw);
+  HIPCHK(c, hipGetLastError());
+  if (!filter) {
+    if (!on_device) HIPCHK(c, hipMemcpyAsync(out_xyzc, d_raw, (size_t)nr * 16, hipMemcpyDeviceToHost, s));
+    // device memory: stream-ordered like rgc_transform_cloud, with the same exception (a pending map preparation, see rgc_deskew)
+    if (!on_device || c->main_has_target_prep) HIPCHK(c, hipStreamSynchronize(s));
+    return RGC_OK;
+  }
+  // downSizeFilter*.setInputCloud(assembled); filter (:1608-1614, 2530-2537): the library's leaf filter, device to device -- into the caller's
+  // buffer when it has room for the unfiltered count (the filter may write that many), else into the store's own and copied once the count is known
+  const bool direct = on_device && cap >= nr;
+  float* d_f = out_xyzc;
+  if (!direct) {
+    if ((rc = ensure(c, c->kf_filt, (size_t)nr * 16))) return rc;
+    d_f = (float*)c->kf_filt.p;
+  }
+  rgc_vg_route rt{};
+  rt.n = nr;
+  int no = 0;
+  rc = voxelgrid_run(c, (const float*)d_raw, nr, 16, leaf, d_f, &no, 1, rt);
+  rt.status = rc;
+  rt.n_out = no;
+  c->vg_route = rt;
+  if (rc) return rc;
+  *n_out = no;
+  if (direct) return RGC_OK;
+  if (no > cap) return fail(c, RGC_ERR_INVALID, "rgc_kf_assemble: %d points after the filter, room for %d", no, cap);
+  if (no > 0) HIPCHK(c, hipMemcpyAsync(out_xyzc, d_f, (size_t)no * 16, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+  if (!on_device) HIPCHK(c, hipStreamSynchronize(s));
   return RGC_OK;
 }
 

@@ -227,6 +227,12 @@ void pc2_unpack(hipStream_t s, const unsigned char* data, int n, const Pc2Layout
 void pc2_pack(hipStream_t s, const float* in, int cols, int n, int kind, unsigned char* out);
 void deskew(hipStream_t s, float* xyzi, int stride_f, int n, Quat qinv, const double t[3]);
 void transform_q(hipStream_t s, const float* in, int stride_f, int n, Quat q, const double t[3], float* out, int ostride_f);
+// f5 (rgc_keyframes.hip): one launch re-expresses and concatenates a selection of stored keyframe clouds.  One KfSegment per (keyframe, kind)
+// with points: src (16-byte points, body frame), n of them, written to out[out0 ..) as q * p + t (transform_q's arithmetic).  blk0[s] = first
+// workgroup (kKfBlock points each) of segment s, blk0[nseg] = nblocks.  seg / blk0: device memory.
+constexpr int kKfBlock = 256;
+struct KfSegment { const float4* src; int n; int out0; Quat q; double t[3]; };
+void kf_assemble(hipStream_t s, const KfSegment* seg, const int* blk0, int nseg, int nblocks, float4* out);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,

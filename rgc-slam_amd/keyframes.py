@@ -1,0 +1,203 @@
+"""f5: the mapping node's keyframe store kept resident on the device -- host-side mirror of the rgc_kf_* entry points of include/rgc_hip.h.
+Replaces the three places where the mapping node assembles a cloud from its keyframes with transformPointCloud per keyframe, `+=` and a
+pcl::VoxelGrid (src/RGC_mapping.cpp:1503-1616 the surrounding maps of f1, :2180-2216 source and target of f4, :2508-2537 the global map):
+
+    store = KeyframeStore(icp)                               # lives in the context of the object that consumes its clouds (or its own)
+    store.push(key_id, pose, corner, surf, scan)             # body-frame clouds (n, >=4) float32; pose = (x, y, z, roll, pitch, yaw), radians
+    store.set_poses(ids, poses)                              # correctKeyFramePoseGraph (:1618-1686)
+    target = store.assemble(history_ids, (KF_CORNER, KF_SURF), leaf=0.4, device=True)
+    icp.setInputTarget(target)                               # rgc_icp_align_device: no download, no upload
+
+Nothing is computed on the CPU; without librgc_hip.so / an MI355X this raises."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import KF_CORNER, KF_SURF, KF_SCAN, RgcError  # noqa: F401  (re-exported)
+
+_ip = C.POINTER(C.c_int)
+
+
+def _poses(poses):
+    p = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 6)
+    return p, p.ctypes.data_as(C.POINTER(_lib.KfPose))
+
+
+class DeviceCloud:
+    """(n, 4) float32 points {x, y, z, c} in device memory of the context that assembled them; what ``assemble(device=True)`` returns and
+    ``IterativeClosestPoint.setInputSource / setInputTarget`` and ``MapFeatureRegistration.setInputMaps`` accept.  Frees its buffer with
+    ``close()`` (or when collected); the context must still be alive then."""
+
+    def __init__(self, L, h, ptr, n, n_raw, cap):
+        self._L, self._h, self.ptr, self.n, self.n_raw, self.cap = L, h, ptr, int(n), int(n_raw), int(cap)
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def stride_bytes(self):
+        return 16
+
+    def synchronize(self):
+        """wait for the assembly (a consumer on ANOTHER context of the same device calls this; on the same context stream order does)"""
+        rc = self._L.rgc_synchronize(self._h)
+        if rc:
+            raise RgcError(rc, self._L.rgc_last_error(self._h).decode())
+
+    def numpy(self):
+        out = np.empty((self.n, 4), np.float32)
+        if self.n:
+            rc = self._L.rgc_download(self._h, out.ctypes.data, self.ptr, out.nbytes)
+            if rc:
+                raise RgcError(rc, self._L.rgc_last_error(self._h).decode())
+        return out
+
+    def close(self):
+        if self.ptr:
+            self._L.rgc_device_free(self._h, self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KeyframeStore:
+    """``owner``: an object with a context (``FastVGICP``, ``IterativeClosestPoint``, ``MapFeatureRegistration``) whose stream the store's
+    work is ordered on, or None for a context of the store's own on ``device``."""
+
+    def __init__(self, owner=None, device: int = 0):
+        self._L = _lib.load()
+        self._own = owner is None
+        if owner is None:
+            h = C.c_void_p()
+            rc = self._L.rgc_create(device, None, C.byref(h))
+            if rc:
+                raise RgcError(rc, self._L.rgc_status_string(rc).decode())
+            self._h = h
+        else:
+            self._h = owner._h
+            self._owner = owner   # keeps the context alive
+
+    def close(self):
+        if self._own and getattr(self, "_h", None):
+            self._L.rgc_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise RgcError(rc, self._L.rgc_last_error(self._h).decode() or self._L.rgc_status_string(rc).decode())
+
+    def reset(self):
+        self._chk(self._L.rgc_kf_reset(self._h))
+
+    def push(self, key_id, pose, corner=None, surf=None, scan=None):
+        clouds, stride = [], None
+        for a in (corner, surf, scan):
+            if a is None or len(a) == 0:
+                clouds.append((None, 0))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] < 4:
+                raise RgcError(_lib.ERR_INVALID, "a keyframe cloud is (n, >=4) float32: x, y, z, c")
+            if stride not in (None, a.strides[0]):
+                raise RgcError(_lib.ERR_INVALID, "the clouds of one keyframe must have the same point layout")
+            stride = a.strides[0]
+            clouds.append((a, a.shape[0]))
+        p, pp = _poses(pose)
+        (c, nc), (s, ns), (k, nk) = clouds
+        self._chk(self._L.rgc_kf_push(self._h, int(key_id), pp, c.ctypes.data if nc else None, nc, s.ctypes.data if ns else None, ns,
+                                      k.ctypes.data if nk else None, nk, stride or 16, 0))
+
+    def set_poses(self, ids, poses):
+        i = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        p, pp = _poses(poses)
+        if p.shape[0] != i.shape[0]:
+            raise RgcError(_lib.ERR_INVALID, "one pose per id")
+        self._chk(self._L.rgc_kf_set_poses(self._h, i.ctypes.data_as(_ip), pp, i.shape[0]))
+
+    def info(self) -> dict:
+        i = _lib.KfInfo()
+        self._chk(self._L.rgc_kf_get_info(self._h, C.byref(i)))
+        return dict(n_keyframes=i.n_keyframes, n_points=list(i.n_points), revision=i.revision)
+
+    @staticmethod
+    def kind_mask(kinds) -> int:
+        if isinstance(kinds, (int, np.integer)):
+            kinds = (int(kinds),)
+        m = 0
+        for k in kinds:
+            if not 0 <= int(k) < _lib.KF_KINDS:
+                raise RgcError(_lib.ERR_INVALID, f"no keyframe cloud kind {k}")
+            m |= 1 << int(k)
+        return m
+
+    def assemble(self, ids, kinds, leaf=0.0, device=False):
+        """The clouds of ``kinds`` of the keyframes ``ids``, in that order (kinds ascending inside a keyframe), under the current poses,
+        through the leaf filter when ``leaf`` > 0: an (n, 4) float32 array, or a ``DeviceCloud`` when ``device``."""
+        i = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        ipp = i.ctypes.data_as(_ip) if i.shape[0] else None
+        mask = self.kind_mask(kinds)
+        n_raw, n_out = C.c_int(0), C.c_int(0)
+        # the counts first (no filter, no room: nothing runs on the device), then a buffer the unfiltered selection fits into
+        rc = self._L.rgc_kf_assemble(self._h, ipp, i.shape[0], mask, 0.0, None, 0, 0, C.byref(n_raw), C.byref(n_out))
+        if rc and n_raw.value == 0:
+            self._chk(rc)
+        cap = n_raw.value
+        if device:
+            d = C.c_void_p()
+            self._chk(self._L.rgc_device_alloc(self._h, max(cap, 1) * 16, C.byref(d)))
+            rc = self._L.rgc_kf_assemble(self._h, ipp, i.shape[0], mask, float(leaf), d, cap, 1, C.byref(n_raw), C.byref(n_out))
+            if rc:
+                self._L.rgc_device_free(self._h, d)
+                self._chk(rc)
+            return DeviceCloud(self._L, self._h, d, n_out.value, n_raw.value, cap)
+        out = np.empty((cap, 4), np.float32)
+        self._chk(self._L.rgc_kf_assemble(self._h, ipp, i.shape[0], mask, float(leaf), out.ctypes.data if cap else None, cap, 0, C.byref(n_raw), C.byref(n_out)))
+        return out[:n_out.value]
+
+
+def pose_of(T):
+    """(x, y, z, roll, pitch, yaw) float32 of a 4x4 sensor->world pose with R = Rz(yaw) Ry(pitch) Rx(roll) (Utility::R2ypr's convention)"""
+    R = np.asarray(T, np.float64)
+    yaw = np.arctan2(R[1, 0], R[0, 0])
+    pitch = np.arctan2(-R[2, 0], np.hypot(R[0, 0], R[1, 0]))
+    roll = np.arctan2(R[2, 1], R[2, 2])
+    return np.array([R[0, 3], R[1, 3], R[2, 3], roll, pitch, yaw], np.float32)
+
+
+def synthetic_keyframes(n_keyframes, seed=None, n_az=600, every=3, device=0, scan_stride=4):
+    """Keyframes of a synthetic drive (synth.make_world / make_trajectory / make_scan), as the mapping node would store them: per keyframe the
+    front-end's sharp and flat features {x, y, z, normal_x} and a thinned sweep {x, y, z, intensity}, all in the BODY frame, and the key pose.
+    Data for tests and scripts/bench_keyframes.py; the features come from the library's own front-end (needs the GPU).
+    Returns (ids, poses (n, 6) float32, clouds {id: [corner, surf, scan]})."""
+    from . import synth
+    from .frontend import ScanRegistration
+    seed = synth.SEED if seed is None else seed
+    world = synth.make_world(seed=seed)
+    traj = synth.make_trajectory(n_keyframes * every, seed=seed)[::every]
+    fe = ScanRegistration(device=device)
+    ids, poses, clouds = [], [], {}
+    try:
+        for i, T in enumerate(traj):
+            sc = synth.make_scan(world, T, n_az=n_az, seed=seed + 10 + i)
+            xyzi = np.concatenate([sc["xyz"], sc["intensity"][:, None]], axis=1).astype(np.float32)
+            f = fe.laserCloudHandler(xyzi, diagnostics=False)
+            ids.append(i)
+            poses.append(pose_of(T))
+            clouds[i] = [np.ascontiguousarray(f["sharp"][:, [0, 1, 2, 4]], np.float32), np.ascontiguousarray(f["flat"][:, [0, 1, 2, 4]], np.float32),
+                         np.ascontiguousarray(f["cloud"][::scan_stride], np.float32)]
+    finally:
+        fe.close()
+    return ids, np.array(poses, np.float32), clouds

@@ -49,12 +49,37 @@ class IterativeClosestPoint:
     def setEuclideanFitnessEpsilon(self, e): self._p.euclidean_fitness_epsilon = float(e)
     def setRANSACIterations(self, n): pass  # 0 in the reference (:2056): no outlier rejection stage
 
-    def setInputSource(self, cloud): self._src = np.ascontiguousarray(cloud, dtype=np.float32)
-    def setInputTarget(self, cloud): self._tgt = np.ascontiguousarray(cloud, dtype=np.float32)
+    @staticmethod
+    def _cloud(cloud):
+        """a numpy array as before, or a device cloud (keyframes.DeviceCloud: what KeyframeStore.assemble(device=True) returns) kept as it is"""
+        return cloud if hasattr(cloud, "ptr") else np.ascontiguousarray(cloud, dtype=np.float32)
+
+    def setInputSource(self, cloud): self._src = self._cloud(cloud)
+    def setInputTarget(self, cloud): self._tgt = self._cloud(cloud)
+
+    def _align_device(self):
+        """both clouds on the device: rgc_icp_align_device, nothing crosses PCIe but the result"""
+        src, tgt = self._src, self._tgt
+        for cl in (src, tgt):
+            if cl._h.value != self._h.value:
+                cl.synchronize()      # assembled on another context's stream
+        T = np.zeros(16, np.float32)
+        res = _lib.IcpResult()
+        rc = self._L.rgc_icp_align_device(self._h, src.ptr, len(src), tgt.ptr, len(tgt), src.stride_bytes, C.byref(self._p),
+                                          T.ctypes.data_as(C.POINTER(C.c_float)), C.byref(res))
+        if rc:
+            raise _lib.RgcError(rc, self._L.rgc_last_error(self._h).decode() or self._L.rgc_status_string(rc).decode())
+        self._T, self._res = T.reshape(4, 4), res
+        return self._T
 
     def align(self):
         if self._src is None or self._tgt is None:
             raise ValueError("setInputSource / setInputTarget first")
+        dev = [hasattr(cl, "ptr") for cl in (self._src, self._tgt)]
+        if all(dev):
+            return self._align_device()
+        if any(dev):
+            raise ValueError("source and target must both be numpy arrays or both be device clouds")
         if self._src.shape[1] != self._tgt.shape[1]:
             raise ValueError("source and target must have the same point layout")
         T = np.zeros(16, np.float32)

@@ -48,7 +48,18 @@ class MapFeatureRegistration:
             raise _lib.RgcError(rc, self._L.rgc_last_error(self._h).decode() or self._L.rgc_status_string(rc).decode())
 
     def setInputMaps(self, corner_map, surf_map):
-        """kdtreeCornerFromMap / kdtreeSurfFromMap ->setInputCloud (:1073-1074); (n,3) or (n,4) float32"""
+        """kdtreeCornerFromMap / kdtreeSurfFromMap ->setInputCloud (:1073-1074); (n,3) or (n,4) float32, or two device clouds
+        (keyframes.DeviceCloud: what KeyframeStore.assemble(device=True) returns), which are read where they lie"""
+        dev = [hasattr(m, "ptr") for m in (corner_map, surf_map)]
+        if all(dev):
+            for m in (corner_map, surf_map):
+                if m._h.value != self._h.value:
+                    m.synchronize()      # assembled on another context's stream
+            self._chk(self._L.rgc_mapreg_set_maps_device(self._h, corner_map.ptr, len(corner_map), surf_map.ptr, len(surf_map), corner_map.stride_bytes))
+            self._ready = True
+            return
+        if any(dev):
+            raise ValueError("both maps must be numpy arrays or both be device clouds")
         cm, cp = _f32(corner_map)
         sm, sp = _f32(surf_map)
         if cm.shape[1] != sm.shape[1]:
