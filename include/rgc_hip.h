@@ -669,6 +669,67 @@ RGC_API int rgc_mapreg_set_maps_device(rgc_ctx* ctx, const float* d_corner, int 
 RGC_API int rgc_icp_align_device(rgc_ctx* ctx, const float* d_source, int n_source, const float* d_target, int n_target, int stride_bytes,
                                  const rgc_icp_params* params, float final_T[16], rgc_icp_result* result);
 
+/* ---- NDT registration (P2D / D2D) on a Gaussian voxel map: fast_gicp::NDTCuda (include/fast_gicp/ndt/ndt_cuda.hpp:27-60,
+ * include/fast_gicp/ndt/impl/ndt_cuda_impl.hpp:10-90, src/fast_gicp/cuda/ndt_cuda.cu:13-177, src/fast_gicp/cuda/ndt_compute_derivatives.cu:33-231), the one
+ * registration of the vendored tree whose only body is CUDA ----
+ * A block of its own on the context, beside the VGICP clouds, the local map and the keyframe store: the rgc_ndt_* calls touch the NDT clouds,
+ * their voxel maps and scratch of their own -- never a cloud or a solve of the registration above.  With a solve in flight (rgc_align_begin ..
+ * rgc_align_end) every one of them RUNS and the solve's result is what it would have been.  The LM and convergence settings are the
+ * context's rgc_params: max_iterations, lm_max_iterations, rotation_eps, translation_eps, lm_init_lambda_factor, max_cells.
+ *   Voxel map (src/fast_gicp/cuda/gaussian_voxelmap.cu:122-148,178-198,209-231), resolution res: voxel of a point = floor(x / res - 0.5) per axis
+ * (include/fast_gicp/cuda/vector3_hash.cuh:35-37, the VGICP map's coordinate); per voxel n, mean = sum p / n, cov = (sum p p^T - mean (sum p)^T) / n,
+ * then MIN_EIG (src/fast_gicp/cuda/covariance_regularization.cu:83-100; src/fast_gicp/cuda/ndt_cuda.cu:128,139): every eigenvalue raised to at
+ * least 1e-3.  Input points fp32, everything after them fp64; every per-voxel sum in ascending point index, every reduction in a fixed order:
+ * results are bit-identical from run to run and between host- and device-pointer inputs.  Both maps are built lazily by the first call that
+ * needs them (include/fast_gicp/ndt/impl/ndt_cuda_impl.hpp:76-79), the source's only in D2D; RGC_ERR_NONFINITE / RGC_ERR_GRID_TOO_LARGE for a
+ * cloud are therefore returned by that call.
+ *   Terms (src/fast_gicp/cuda/find_voxel_correspondences.cu:55-60,92-110; src/fast_gicp/cuda/ndt_compute_derivatives.cu:50-91,120-163): for every
+ * source element a -- a source point in P2D, the mean of a voxel of the source's own map in D2D -- and EVERY offset o of the neighbour
+ * method, the voxel at coord(T a) + o if it exists and holds more than 6 points: e = mean_B - (R a + t); M = cov_B^-1 (P2D) or
+ * (cov_B + R_lin cov_A R_lin^T)^-1 (D2D, R_lin the rotation of the last rgc_ndt_linearize); w = res^2 / (res^2 + |e|^2); cost += w e^T M e,
+ * J = [skew(R a + t), -I], H += w J^T M J, b += w J^T M e.  RGC_NDT_DIRECT_RADIUS (src/fast_gicp/cuda/ndt_cuda.cu:70-84): all integer offsets
+ * of [-ceil(r), ceil(r)]^3 with |o| <= r + 1e-3, in nested i, j, k order; at most RGC_NDT_MAX_OFFSETS of them (r < 4.9).
+ *   Frozen terms: rgc_ndt_compute_error re-uses the (element, voxel) list and R_lin of the last rgc_ndt_linearize; the weights follow the pose
+ * it is given (src/fast_gicp/cuda/ndt_cuda.cu:162-177).  A new neighbour method or radius between the two calls leaves the frozen list in force
+ * (as rgc_set_params does for the VGICP list); a new resolution or distance mode, and setting, clearing or swapping a cloud, drop it
+ * (rgc_ndt_compute_error: RGC_ERR_INVALID until the next rgc_ndt_linearize). */
+enum { RGC_NDT_P2D = 0, RGC_NDT_D2D = 1 };                                           /* fast_gicp::NDTDistanceMode, include/fast_gicp/ndt/ndt_settings.hpp:6 */
+enum { RGC_NDT_DIRECT27 = 0, RGC_NDT_DIRECT7 = 1, RGC_NDT_DIRECT1 = 2, RGC_NDT_DIRECT_RADIUS = 3 };  /* fast_gicp::NeighborSearchMethod, include/fast_gicp/gicp/gicp_settings.hpp:8 */
+#define RGC_NDT_MAX_OFFSETS 512
+typedef struct rgc_ndt_params {
+  double resolution;       /* setResolution (1.0)            src/fast_gicp/cuda/ndt_cuda.cu:15,31-33 */
+  int    distance_mode;    /* setDistanceMode (RGC_NDT_D2D)  src/fast_gicp/cuda/ndt_cuda.cu:21,27-29 */
+  int    neighbor_method;  /* setNeighborSearchMethod (RGC_NDT_DIRECT7) src/fast_gicp/cuda/ndt_cuda.cu:22,35-88 */
+  double neighbor_radius;  /* ... its radius, read under RGC_NDT_DIRECT_RADIUS only (0.0) */
+} rgc_ndt_params;
+RGC_API void rgc_default_ndt_params(rgc_ndt_params* p);
+RGC_API int rgc_ndt_set_params(rgc_ctx* ctx, const rgc_ndt_params* params);
+RGC_API int rgc_ndt_get_params(const rgc_ctx* ctx, rgc_ndt_params* params);
+/* setInputTarget / setInputSource (include/fast_gicp/ndt/impl/ndt_cuda_impl.hpp:50-73; src/fast_gicp/cuda/ndt_cuda.cu:95-113): x, y, z first, stride in
+ * bytes, like rgc_set_target*.  The cloud is copied: a host cloud is on the device when the call returns, a device cloud is read in stream
+ * order on rgc_stream(ctx) (what rgc_kf_assemble(..., on_device = 1) wrote is consumed where it lies).  1 <= n <= 2^27. */
+RGC_API int rgc_ndt_set_target(rgc_ctx* ctx, const float* xyz, int n, int stride_bytes);
+RGC_API int rgc_ndt_set_source(rgc_ctx* ctx, const float* xyz, int n, int stride_bytes);
+RGC_API int rgc_ndt_set_target_device(rgc_ctx* ctx, const float* d_xyz, int n, int stride_bytes);
+RGC_API int rgc_ndt_set_source_device(rgc_ctx* ctx, const float* d_xyz, int n, int stride_bytes);
+/* clearSource / clearTarget / swapSourceAndTarget (include/fast_gicp/ndt/impl/ndt_cuda_impl.hpp:34-48; src/fast_gicp/cuda/ndt_cuda.cu:90-93: the clouds
+ * and their voxel maps change roles) */
+RGC_API int rgc_ndt_clear_source(rgc_ctx* ctx);
+RGC_API int rgc_ndt_clear_target(rgc_ctx* ctx);
+RGC_API int rgc_ndt_swap_source_and_target(rgc_ctx* ctx);
+/* linearize / compute_error (include/fast_gicp/ndt/impl/ndt_cuda_impl.hpp:81-90): T row-major 4x4; H, b as rgc_linearize (both or neither) */
+RGC_API int rgc_ndt_linearize(rgc_ctx* ctx, const double T[16], double H[36], double b[6], double* cost);
+RGC_API int rgc_ndt_compute_error(rgc_ctx* ctx, const double T[16], double* cost);
+RGC_API int rgc_ndt_num_correspondences(rgc_ctx* ctx, int* n_terms);   /* terms of the last rgc_ndt_linearize */
+/* computeTransformation (include/fast_gicp/ndt/impl/ndt_cuda_impl.hpp:75-79): LsqRegistration's driver as rgc_align runs it (lsq_registration_impl.hpp:53-79,
+ * LM step :125-172), outputs as rgc_align's.  Any output pointer may be NULL. */
+RGC_API int rgc_ndt_align(rgc_ctx* ctx, const float guess[16], float final_T[16], double final_H[36], int* iterations, int* converged, int* lm_failed);
+/* voxel map read-out, which = 0 target, 1 source (built if need be, in either mode): up to cap voxels, unordered; coords 3*cap ints, n cap ints,
+ * mean 3*cap doubles, cov9 9*cap doubles (after MIN_EIG); *count = total voxels.  rgc_ndt_get_raw_covariances: the covariances BEFORE MIN_EIG,
+ * in the same voxel order. */
+RGC_API int rgc_ndt_get_voxels(rgc_ctx* ctx, int which, int cap, int* coords, int* n, double* mean, double* cov9, int* count);
+RGC_API int rgc_ndt_get_raw_covariances(rgc_ctx* ctx, int which, int cap, double* cov9, int* count);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

@@ -121,6 +121,15 @@ class VgRoute(C.Structure):
                 ("minb", C.c_int * 3), ("div", C.c_int * 3), ("n", C.c_int), ("n_out", C.c_int)]
 
 
+class NdtParams(C.Structure):
+    """rgc_ndt_params: the settings of the NDT registration (rgc_ndt_set_params)"""
+    _fields_ = [("resolution", C.c_double), ("distance_mode", C.c_int), ("neighbor_method", C.c_int), ("neighbor_radius", C.c_double)]
+
+
+NDT_P2D, NDT_D2D = 0, 1
+NDT_DIRECT27, NDT_DIRECT7, NDT_DIRECT1, NDT_DIRECT_RADIUS = 0, 1, 2, 3
+NDT_MAX_OFFSETS = 512
+
 VG_PATH_NONE, VG_PATH_KEPT, VG_PATH_MEASURED, VG_PATH_UNFILTERED = 0, 1, 2, 3
 
 
@@ -139,7 +148,9 @@ SYMBOLS = [
     "rgc_clear_source", "rgc_clear_target", "rgc_swap_source_and_target", "rgc_get_voxels",
     "rgc_get_stats", "rgc_device_alloc", "rgc_device_free", "rgc_host_alloc", "rgc_host_free", "rgc_upload", "rgc_download", "rgc_synchronize",
     "rgc_stream", "rgc_default_fe_params", "rgc_frontend", "rgc_extract_pose", "rgc_imu_preintegrate", "rgc_imu_filter_init", "rgc_imu_filter_push", "rgc_ground_gate_init", "rgc_ground_gate_remember", "rgc_ground_gate_step", "rgc_default_fuse_in", "rgc_fuse_pose", "rgc_compose_pose",
-    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_kf_reset", "rgc_kf_push", "rgc_kf_set_poses", "rgc_kf_get_info", "rgc_kf_assemble", "rgc_mapreg_set_maps_device", "rgc_icp_align_device", "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
+    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_kf_reset", "rgc_kf_push", "rgc_kf_set_poses", "rgc_kf_get_info", "rgc_kf_assemble", "rgc_mapreg_set_maps_device", "rgc_icp_align_device",
+    "rgc_default_ndt_params", "rgc_ndt_set_params", "rgc_ndt_get_params", "rgc_ndt_set_target", "rgc_ndt_set_source", "rgc_ndt_set_target_device", "rgc_ndt_set_source_device", "rgc_ndt_clear_source", "rgc_ndt_clear_target", "rgc_ndt_swap_source_and_target", "rgc_ndt_linearize", "rgc_ndt_compute_error", "rgc_ndt_num_correspondences", "rgc_ndt_align", "rgc_ndt_get_voxels", "rgc_ndt_get_raw_covariances",
+    "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
 _lib = None
@@ -311,6 +322,20 @@ def load():
     L.rgc_kf_assemble.argtypes = [vp, ip, C.c_int, C.c_uint, C.c_float, vp, C.c_int, C.c_int, ip, ip]
     L.rgc_mapreg_set_maps_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int]
     L.rgc_icp_align_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(IcpParams), fp, C.POINTER(IcpResult)]
+    L.rgc_default_ndt_params.argtypes = [C.POINTER(NdtParams)]
+    L.rgc_default_ndt_params.restype = None
+    L.rgc_ndt_set_params.argtypes = [vp, C.POINTER(NdtParams)]
+    L.rgc_ndt_get_params.argtypes = [vp, C.POINTER(NdtParams)]
+    for f in (L.rgc_ndt_set_target, L.rgc_ndt_set_source, L.rgc_ndt_set_target_device, L.rgc_ndt_set_source_device):
+        f.argtypes = [vp, vp, C.c_int, C.c_int]
+    for f in (L.rgc_ndt_clear_source, L.rgc_ndt_clear_target, L.rgc_ndt_swap_source_and_target):
+        f.argtypes = [vp]
+    L.rgc_ndt_linearize.argtypes = [vp, dp, dp, dp, dp]
+    L.rgc_ndt_compute_error.argtypes = [vp, dp, dp]
+    L.rgc_ndt_num_correspondences.argtypes = [vp, ip]
+    L.rgc_ndt_align.argtypes = [vp, fp, fp, dp, ip, ip, ip]
+    L.rgc_ndt_get_voxels.argtypes = [vp, C.c_int, C.c_int, ip, ip, dp, dp, ip]
+    L.rgc_ndt_get_raw_covariances.argtypes = [vp, C.c_int, C.c_int, dp, ip]
     L.rgc_profile_enable.argtypes = [vp, C.c_int]
     L.rgc_profile_select.argtypes = [vp, C.c_uint]
     L.rgc_profile_reset.argtypes = [vp]

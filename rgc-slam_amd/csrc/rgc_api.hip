@@ -296,6 +296,21 @@ struct rgc_ctx {
   size_t kf_h_cap = 0;
   hipEvent_t kf_uploaded = nullptr;        // recorded behind the table's copy: the staging is rewritten only after it
   bool kf_upload_pending = false;
+  // NDT registration (rgc_ndt_*): two clouds of its own (0 target, 1 source) with their grids and voxel maps (Cloud::cell_voxel / vox / vox_cell,
+  // records of rgck::kNdtRec doubles), the offsets of the neighbour method, the frozen term list of the last linearisation
+  rgc_ndt_params ndt_prm{1.0, RGC_NDT_D2D, RGC_NDT_DIRECT7, 0.0};
+  Cloud ndt_cl[2];
+  bool ndt_set[2] = {false, false};       // a cloud has been handed over (its points are in Cloud::in_copy, 12-byte stride)
+  bool ndt_built[2] = {false, false};     // ... and its voxel map is built, at resolution ndt_built_res
+  double ndt_built_res[2] = {0.0, 0.0};
+  std::vector<int> ndt_offs_h;            // 3 ints per offset, the order of the reference's list
+  DevBuf ndt_offs, ndt_corr, ndt_partials, ndt_ipartials, ndt_small, ndt_out;
+  bool ndt_offs_dirty = true;
+  double* ndt_h_out = nullptr;            // pinned: 32 doubles
+  int* ndt_h_small = nullptr;             // pinned: 8 ints
+  bool ndt_corr_valid = false;            // ndt_corr holds the list of ndt_corr_n elements x ndt_corr_noff offsets made under ndt_corr_mode at ndt_Tlin
+  int ndt_corr_n = 0, ndt_corr_noff = 0, ndt_corr_mode = 0, ndt_terms = 0;
+  double ndt_Tlin[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   rgc_stats stats{};
   // profiling
   bool prof_on = false;
@@ -1662,6 +1677,11 @@ void rgc_destroy(rgc_ctx* c) {
   if (c->h_vg) (void)hipHostFree(c->h_vg);
   for (DevBuf* b : {&c->kf_store[0], &c->kf_store[1], &c->kf_store[2], &c->kf_table, &c->kf_raw, &c->kf_filt}) release(*b);
   if (c->kf_h_table) (void)hipHostFree(c->kf_h_table);
+  release_cloud(c->ndt_cl[0]);
+  release_cloud(c->ndt_cl[1]);
+  for (DevBuf* b : {&c->ndt_offs, &c->ndt_corr, &c->ndt_partials, &c->ndt_ipartials, &c->ndt_small, &c->ndt_out}) release(*b);
+  if (c->ndt_h_out) (void)hipHostFree(c->ndt_h_out);
+  if (c->ndt_h_small) (void)hipHostFree(c->ndt_h_small);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -4112,6 +4132,415 @@ int rgc_kf_assemble(rgc_ctx* c, const int* ids, int n_ids, unsigned kind_mask, f
   if (no > cap) return fail(c, RGC_ERR_INVALID, "rgc_kf_assemble: %d points after the filter, room for %d", no, cap);
   if (no > 0) HIPCHK(c, hipMemcpyAsync(out_xyzc, d_f, (size_t)no * 16, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
   if (!on_device) HIPCHK(c, hipStreamSynchronize(s));
+  return RGC_OK;
+}
+
+// ---- NDT registration (P2D / D2D) on a Gaussian voxel map: fast_gicp::NDTCuda (src/fast_gicp/cuda/ndt_cuda.cu, ndt_compute_derivatives.cu) ----
+void rgc_default_ndt_params(rgc_ndt_params* p) {
+  if (!p) return;
+  p->resolution = 1.0;                     // src/fast_gicp/cuda/ndt_cuda.cu:15
+  p->distance_mode = RGC_NDT_D2D;          // :21
+  p->neighbor_method = RGC_NDT_DIRECT7;    // :22
+  p->neighbor_radius = 0.0;
+}
+
+// the offsets of a neighbour method in the reference's order (src/fast_gicp/cuda/ndt_cuda.cu:35-88); false: more than RGC_NDT_MAX_OFFSETS
+static bool ndt_offsets_of(int method, double radius, std::vector<int>& o) {
+  o.clear();
+  if (method == RGC_NDT_DIRECT1) { o = {0, 0, 0}; return true; }
+  if (method == RGC_NDT_DIRECT7) { o = {0, 0, 0, 1, 0, 0, -1, 0, 0, 0, 1, 0, 0, -1, 0, 0, 0, 1, 0, 0, -1}; return true; }
+  if (method == RGC_NDT_DIRECT27) {
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++)
+        for (int k = 0; k < 3; k++) { o.push_back(i - 1); o.push_back(j - 1); o.push_back(k - 1); }
+    return true;
+  }
+  if (radius > 16.0) return false;
+  const int range = (int)std::ceil(radius);
+  for (int i = -range; i <= range; i++)
+    for (int j = -range; j <= range; j++)
+      for (int k = -range; k <= range; k++)
+        if (std::sqrt((double)(i * i + j * j + k * k)) <= radius + 1e-3) {
+          if ((int)o.size() / 3 >= RGC_NDT_MAX_OFFSETS) return false;
+          o.push_back(i); o.push_back(j); o.push_back(k);
+        }
+  return true;
+}
+
+static void ndt_drop_terms(rgc_ctx* c) { c->ndt_corr_valid = false; c->ndt_terms = 0; }
+
+int rgc_ndt_set_params(rgc_ctx* c, const rgc_ndt_params* p) {
+  if (!c || !p) return RGC_ERR_INVALID;
+  if (!std::isfinite(p->resolution) || !(p->resolution > 0.0)) return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: resolution must be finite and > 0");
+  if (p->distance_mode != RGC_NDT_P2D && p->distance_mode != RGC_NDT_D2D) return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: no distance mode %d", p->distance_mode);
+  if (p->neighbor_method < RGC_NDT_DIRECT27 || p->neighbor_method > RGC_NDT_DIRECT_RADIUS) return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: no neighbour method %d", p->neighbor_method);
+  std::vector<int> offs;
+  if (p->neighbor_method == RGC_NDT_DIRECT_RADIUS) {
+    if (!std::isfinite(p->neighbor_radius) || p->neighbor_radius < 0.0) return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: DIRECT_RADIUS needs a finite radius >= 0");
+  }
+  if (!ndt_offsets_of(p->neighbor_method, p->neighbor_radius, offs))
+    return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: radius %g has more than %d offsets", p->neighbor_radius, RGC_NDT_MAX_OFFSETS);
+  if (p->resolution != c->ndt_prm.resolution || p->distance_mode != c->ndt_prm.distance_mode) ndt_drop_terms(c);
+  c->ndt_prm = *p;
+  c->ndt_offs_h.swap(offs);
+  c->ndt_offs_dirty = true;
+  return RGC_OK;
+}
+
+int rgc_ndt_get_params(const rgc_ctx* c, rgc_ndt_params* p) {
+  if (!c || !p) return RGC_ERR_INVALID;
+  *p = c->ndt_prm;
+  return RGC_OK;
+}
+
+// one body of the four setters: the points packed to 12 bytes each in the cloud's own buffer, in stream order on the context's stream
+static int ndt_set_cloud(rgc_ctx* c, int which, const float* xyz, int n, int stride_bytes, bool on_device) {
+  if (!c || !xyz) return RGC_ERR_INVALID;
+  if (stride_bytes < 12 || (stride_bytes & 3) || stride_bytes > 4096) return fail(c, RGC_ERR_INVALID, "stride_bytes must be a multiple of 4 between 12 and 4096");
+  if (n < 1) return fail(c, n < 0 ? RGC_ERR_INVALID : RGC_ERR_TOO_FEW_POINTS, "rgc_ndt_set_*: a cloud needs at least one point");
+  if (n > (1 << 27)) return fail(c, RGC_ERR_INVALID, "cloud has %d points, the limit is 2^27", n);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if (on_device && (rc = check_device_range(c, xyz, (size_t)n * stride_bytes - (stride_bytes - 12), which ? "rgc_ndt_set_source_device" : "rgc_ndt_set_target_device"))) return rc;
+  Cloud& cl = c->ndt_cl[which];
+  if ((rc = ensure(c, cl.in_copy, (size_t)n * 12))) return rc;
+  HIPCHK(c, hipMemcpy2DAsync(cl.in_copy.p, 12, xyz, (size_t)stride_bytes, 12, (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  if (!on_device) HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller owns a host buffer for the duration of the call only
+  cl.in = (const float*)cl.in_copy.p;
+  cl.stride_f = 3;
+  cl.n = n;
+  cl.ready = false;
+  c->ndt_set[which] = true;
+  c->ndt_built[which] = false;
+  ndt_drop_terms(c);
+  return RGC_OK;
+}
+int rgc_ndt_set_target(rgc_ctx* c, const float* xyz, int n, int stride_bytes) { return ndt_set_cloud(c, 0, xyz, n, stride_bytes, false); }
+int rgc_ndt_set_source(rgc_ctx* c, const float* xyz, int n, int stride_bytes) { return ndt_set_cloud(c, 1, xyz, n, stride_bytes, false); }
+int rgc_ndt_set_target_device(rgc_ctx* c, const float* d_xyz, int n, int stride_bytes) { return ndt_set_cloud(c, 0, d_xyz, n, stride_bytes, true); }
+int rgc_ndt_set_source_device(rgc_ctx* c, const float* d_xyz, int n, int stride_bytes) { return ndt_set_cloud(c, 1, d_xyz, n, stride_bytes, true); }
+
+int rgc_ndt_clear_source(rgc_ctx* c) {
+  if (!c) return RGC_ERR_INVALID;
+  c->ndt_set[1] = c->ndt_built[1] = false;
+  ndt_drop_terms(c);
+  return RGC_OK;
+}
+int rgc_ndt_clear_target(rgc_ctx* c) {
+  if (!c) return RGC_ERR_INVALID;
+  c->ndt_set[0] = c->ndt_built[0] = false;
+  ndt_drop_terms(c);
+  return RGC_OK;
+}
+int rgc_ndt_swap_source_and_target(rgc_ctx* c) {
+  if (!c) return RGC_ERR_INVALID;
+  std::swap(c->ndt_cl[0], c->ndt_cl[1]);
+  std::swap(c->ndt_set[0], c->ndt_set[1]);
+  std::swap(c->ndt_built[0], c->ndt_built[1]);
+  std::swap(c->ndt_built_res[0], c->ndt_built_res[1]);
+  ndt_drop_terms(c);
+  return RGC_OK;
+}
+
+static int ndt_scratch(rgc_ctx* c) {
+  int rc;
+  if ((rc = ensure(c, c->ndt_small, 64))) return rc;
+  if ((rc = ensure(c, c->ndt_out, sizeof(double) * 32))) return rc;
+  if (!c->ndt_h_out) HIPCHK(c, hipHostMalloc((void**)&c->ndt_h_out, sizeof(double) * 32, hipHostMallocDefault));
+  if (!c->ndt_h_small) HIPCHK(c, hipHostMalloc((void**)&c->ndt_h_small, sizeof(int) * 8, hipHostMallocDefault));
+  return RGC_OK;
+}
+
+// the voxel map of NDT cloud `which` at the current resolution, if it is not there yet: the VGICP target's table construction (bounding box,
+// counting sort by voxel, points of a voxel in ascending index) and one segmented pass (rgck::ndt_voxels)
+static int ndt_build(rgc_ctx* c, int which) {
+  Cloud& cl = c->ndt_cl[which];
+  const double res = c->ndt_prm.resolution;
+  if (c->ndt_built[which] && c->ndt_built_res[which] == res) return RGC_OK;
+  c->ndt_built[which] = false;
+  int rc;
+  if ((rc = ndt_scratch(c))) return rc;
+  hipStream_t s = c->stream;
+  const int n = cl.n;
+  int* dsm = (int*)c->ndt_small.p;
+  int* hsm = c->ndt_h_small;
+  const int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
+  memcpy(hsm, init, sizeof(init));
+  HIPCHK(c, hipMemcpyAsync(dsm, hsm, 8 * sizeof(int), hipMemcpyHostToDevice, s));
+  rgck::bbox(s, cl.in, cl.stride_f, n, res, dsm, dsm + 6);
+  HIPCHK(c, hipMemcpyAsync(hsm, dsm, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (hsm[6]) return fail(c, RGC_ERR_NONFINITE, "NDT %s contains non-finite or absurd coordinates", which ? "source" : "target");
+  int minc[3], dim[3];
+  double ncell = 1.0;
+  for (int a = 0; a < 3; a++) {
+    minc[a] = hsm[a];
+    dim[a] = hsm[3 + a] - hsm[a] + 1;
+    ncell *= (double)dim[a];
+  }
+  if (ncell > (double)c->prm.max_cells || ncell > 2.0e9) return fail(c, RGC_ERR_GRID_TOO_LARGE, "NDT %s: voxel grid exceeds max_cells", which ? "source" : "target");
+  const rgck::Grid g = rgck::make_grid(minc, dim, res);
+  cl.grid = g;
+  const size_t nc1 = (size_t)g.ncell + 1;
+  if ((rc = ensure(c, cl.cell_of, sizeof(int) * n))) return rc;
+  if ((rc = ensure(c, cl.slot_of, sizeof(int) * n))) return rc;
+  if ((rc = ensure(c, cl.cnt, sizeof(int) * nc1 + 256))) return rc;
+  if ((rc = ensure(c, cl.start, sizeof(int) * nc1))) return rc;
+  if ((rc = ensure(c, cl.cell_voxel, sizeof(int) * nc1))) return rc;
+  if ((rc = ensure(c, cl.block_sums, sizeof(long long) * (nc1 / 2048 + 2)))) return rc;
+  if ((rc = ensure(c, cl.order_tmp, sizeof(long long) * n))) return rc;
+  if ((rc = ensure(c, cl.P, sizeof(float4) * ((size_t)n + 4)))) return rc;
+  HIPCHK(c, hipMemsetAsync(cl.cnt.p, 0, (sizeof(int) * nc1 + 255) & ~(size_t)255, s));
+  rgck::count_cells(s, cl.in, cl.stride_f, n, g, (int*)cl.cell_of.p, (int*)cl.slot_of.p, (int*)cl.cnt.p);
+  rgck::scan_cells(s, (int*)cl.cnt.p, (int*)cl.start.p, (int)nc1, cl.block_sums.p, (int*)cl.cell_voxel.p, dsm + 7);
+  rgck::place(s, n, (const int*)cl.cell_of.p, (const int*)cl.slot_of.p, (const int*)cl.start.p, (unsigned long long*)cl.order_tmp.p);
+  rgck::rank_gather(s, cl.in, cl.stride_f, n, (const int*)cl.cell_of.p, (const int*)cl.start.p, (const unsigned long long*)cl.order_tmp.p, (float4*)cl.P.p);
+  HIPCHK(c, hipMemcpyAsync(hsm + 7, dsm + 7, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  const int nvox = hsm[7];
+  if (nvox < 1 || nvox > n) return fail(c, RGC_ERR_HIP, "NDT voxel count %d out of range", nvox);
+  if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kNdtRec * (size_t)nvox))) return rc;
+  if ((rc = ensure(c, cl.vox_cell, sizeof(int) * (size_t)nvox))) return rc;
+  rgck::ndt_voxels(s, (const float4*)cl.P.p, (const int*)cl.start.p, g, (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p);
+  HIPCHK(c, hipGetLastError());
+  cl.nvox = nvox;
+  cl.ready = true;
+  c->ndt_built[which] = true;
+  c->ndt_built_res[which] = res;
+  return RGC_OK;
+}
+
+static bool ndt_pose_finite(const double T[16]) {
+  for (int i = 0; i < 12; i++)
+    if (!std::isfinite(T[i])) return false;
+  return true;
+}
+
+static int ndt_need_inputs(rgc_ctx* c) {
+  if (!c->ndt_set[0]) return fail(c, RGC_ERR_NO_INPUT, "NDT target not set");
+  if (!c->ndt_set[1]) return fail(c, RGC_ERR_NO_INPUT, "NDT source not set");
+  int rc;
+  if ((rc = ndt_build(c, 0))) return rc;
+  if (c->ndt_prm.distance_mode == RGC_NDT_D2D && (rc = ndt_build(c, 1))) return rc;
+  return RGC_OK;
+}
+
+// find != 0: linearize at T (the term list and R_lin are made); else the cost at T over the frozen list.  out: 28 sums + the number of terms.
+static int ndt_run_terms(rgc_ctx* c, const double T[16], bool find, bool want_H, double out[29]) {
+  int rc;
+  if ((rc = ndt_scratch(c))) return rc;
+  const int d2d = find ? (c->ndt_prm.distance_mode == RGC_NDT_D2D) : c->ndt_corr_mode;
+  const Cloud& tg = c->ndt_cl[0];
+  const Cloud& sc = c->ndt_cl[1];
+  const int n = find ? (d2d ? sc.nvox : sc.n) : c->ndt_corr_n;
+  if (find) {
+    if (c->ndt_offs_h.empty()) ndt_offsets_of(c->ndt_prm.neighbor_method, c->ndt_prm.neighbor_radius, c->ndt_offs_h);
+    if (c->ndt_offs_dirty) {
+      if ((rc = ensure(c, c->ndt_offs, sizeof(int) * 3 * RGC_NDT_MAX_OFFSETS))) return rc;
+      HIPCHK(c, hipStreamSynchronize(c->stream));  // (a launch that reads the former list may still run)
+      HIPCHK(c, hipMemcpy(c->ndt_offs.p, c->ndt_offs_h.data(), sizeof(int) * c->ndt_offs_h.size(), hipMemcpyHostToDevice));
+      c->ndt_offs_dirty = false;
+    }
+    c->ndt_corr_valid = false;
+    c->ndt_corr_noff = (int)c->ndt_offs_h.size() / 3;
+    c->ndt_corr_n = n;
+    c->ndt_corr_mode = d2d;
+    memcpy(c->ndt_Tlin, T, sizeof(double) * 16);
+    if ((rc = ensure(c, c->ndt_corr, sizeof(int) * (size_t)n * c->ndt_corr_noff))) return rc;
+  }
+  const int noff = c->ndt_corr_noff;
+  const int nb = rgck::ndt_blocks(n);
+  if ((rc = ensure(c, c->ndt_partials, sizeof(double) * rgck::kAccum * (size_t)nb))) return rc;
+  if ((rc = ensure(c, c->ndt_ipartials, sizeof(int) * (size_t)nb))) return rc;
+  rgck::ndt_terms(c->stream, d2d, find ? 1 : 0, sc.in, sc.stride_f, (const double*)sc.vox.p, n, pose_from(T), pose_from(c->ndt_Tlin), tg.grid,
+                  (const int*)tg.cell_voxel.p, (const double*)tg.vox.p, (const int*)c->ndt_offs.p, noff, (int*)c->ndt_corr.p, want_H ? 1 : 0,
+                  (double*)c->ndt_partials.p, (int*)c->ndt_ipartials.p, (double*)c->ndt_out.p);
+  HIPCHK(c, hipMemcpyAsync(c->ndt_h_out, c->ndt_out.p, sizeof(double) * 29, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  memcpy(out, c->ndt_h_out, sizeof(double) * 29);
+  if (find) {
+    c->ndt_corr_valid = true;
+    c->ndt_terms = (int)out[28];
+  }
+  return RGC_OK;
+}
+
+static int ndt_do_linearize(rgc_ctx* c, const double T[16], double* H, double* b, double* cost) {
+  int rc = ndt_need_inputs(c);
+  if (rc) return rc;
+  double out[29];
+  const bool want = H && b;
+  if ((rc = ndt_run_terms(c, T, true, want, out))) return rc;
+  if (want) {
+    int u = 0;
+    for (int a = 0; a < 6; a++)
+      for (int d = a; d < 6; d++) { H[a * 6 + d] = out[u]; H[d * 6 + a] = out[u]; u++; }
+    for (int a = 0; a < 6; a++) b[a] = out[21 + a];
+  }
+  if (cost) *cost = out[27];
+  return RGC_OK;
+}
+
+static int ndt_do_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c->ndt_set[0] || !c->ndt_set[1]) return fail(c, RGC_ERR_NO_INPUT, "NDT source or target not set");
+  if (!c->ndt_corr_valid) return fail(c, RGC_ERR_INVALID, "rgc_ndt_compute_error needs a preceding rgc_ndt_linearize");
+  double out[29];
+  const int rc = ndt_run_terms(c, T, false, false, out);
+  if (rc) return rc;
+  *cost = out[27];
+  return RGC_OK;
+}
+
+int rgc_ndt_linearize(rgc_ctx* c, const double T[16], double H[36], double b[6], double* cost) {
+  if (!c || !T) return RGC_ERR_INVALID;
+  if (!ndt_pose_finite(T)) return fail(c, RGC_ERR_NONFINITE, "rgc_ndt_linearize: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  return ndt_do_linearize(c, T, H, b, cost);
+}
+
+int rgc_ndt_compute_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c || !T || !cost) return RGC_ERR_INVALID;
+  if (!ndt_pose_finite(T)) return fail(c, RGC_ERR_NONFINITE, "rgc_ndt_compute_error: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  return ndt_do_error(c, T, cost);
+}
+
+int rgc_ndt_num_correspondences(rgc_ctx* c, int* n) {
+  if (!c || !n) return RGC_ERR_INVALID;
+  if (!c->ndt_corr_valid) return fail(c, RGC_ERR_INVALID, "rgc_ndt_num_correspondences needs a preceding rgc_ndt_linearize");
+  *n = c->ndt_terms;
+  return RGC_OK;
+}
+
+// LsqRegistration::computeTransformation + step_lm (lsq_registration_impl.hpp:53-79, 125-172), the loop of rgc_align's host-driven route
+int rgc_ndt_align(rgc_ctx* c, const float guess[16], float final_T[16], double final_H[36], int* iterations, int* converged, int* lm_failed) {
+  if (!c || !guess) return RGC_ERR_INVALID;
+  for (int i = 0; i < 12; i++)
+    if (!std::isfinite(guess[i])) return fail(c, RGC_ERR_NONFINITE, "rgc_ndt_align: the guess is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = ndt_need_inputs(c);  // create_voxelmaps() (include/fast_gicp/ndt/impl/ndt_cuda_impl.hpp:77)
+  if (rc) return rc;
+  const rgc_params& P = c->prm;
+  double x0[16];
+  for (int i = 0; i < 12; i++) x0[i] = (double)guess[i];
+  x0[12] = x0[13] = x0[14] = 0.0;
+  x0[15] = 1.0;
+  double lambda = -1.0;  // :56
+  bool conv = false, failed = false;
+  int iters = 0;
+  double Hfin[36];
+  memset(Hfin, 0, sizeof(Hfin));
+  for (int i = 0; i < 6; i++) Hfin[i * 7] = 1.0;  // final_hessian_.setIdentity(), :21
+  for (int it = 0; it < P.max_iterations && !conv; it++) {  // :65
+    iters = it + 1;
+    double H[36], b[6], y0, delta[16], d[6], xi[16], yi;
+    if ((rc = ndt_do_linearize(c, x0, H, b, &y0))) return rc;  // :128
+    if (lambda < 0.0) {  // :130-132
+      double m = 0;
+      for (int a = 0; a < 6; a++) m = std::fmax(m, std::fabs(H[a * 7]));
+      lambda = P.lm_init_lambda_factor * m;
+    }
+    double nu = 2.0;
+    bool ok = false;
+    memset(delta, 0, sizeof(delta));
+    for (int k = 0; k < P.lm_max_iterations; k++) {  // :135
+      rgclm::lm_try(H, b, lambda, x0, d, delta, xi);  // :136-143
+      if ((rc = ndt_do_error(c, xi, &yi))) return rc;  // :144
+      double den = 0;
+      for (int i = 0; i < 6; i++) den += d[i] * (lambda * d[i] - b[i]);
+      const double rho = (y0 - yi) / den;  // :145
+      if (rho < 0) {  // :155-163
+        if (is_converged(delta, P.rotation_eps, P.translation_eps)) { ok = true; break; }
+        lambda = nu * lambda;
+        nu = 2 * nu;
+        continue;
+      }
+      memcpy(x0, xi, sizeof(xi));  // :165
+      lambda = lambda * std::fmax(1.0 / 3.0, 1 - std::pow(2 * rho - 1, 3));  // :166
+      memcpy(Hfin, H, sizeof(Hfin));  // :167
+      ok = true;
+      break;
+    }
+    if (!ok) { failed = true; break; }  // :69-72 "lm not converged!!"
+    conv = is_converged(delta, P.rotation_eps, P.translation_eps);  // :74
+  }
+  if (final_T)
+    for (int i = 0; i < 16; i++) final_T[i] = (float)x0[i];  // :77
+  if (final_H) memcpy(final_H, Hfin, sizeof(Hfin));
+  if (iterations) *iterations = iters;
+  if (converged) *converged = conv ? 1 : 0;
+  if (lm_failed) *lm_failed = failed ? 1 : 0;
+  return RGC_OK;
+}
+
+// the records of map `which` on the host (m of them); cells: their grid cells
+static int ndt_fetch_voxels(rgc_ctx* c, int which, int cap, std::vector<double>& rec, std::vector<int>& cell, int* count) {
+  if (which != 0 && which != 1) return fail(c, RGC_ERR_INVALID, "which: 0 target, 1 source");
+  if (cap < 0) return fail(c, RGC_ERR_INVALID, "negative capacity");
+  if (!c->ndt_set[which]) return fail(c, RGC_ERR_NO_INPUT, "NDT %s not set", which ? "source" : "target");
+  int rc = ndt_build(c, which);
+  if (rc) return rc;
+  const Cloud& cl = c->ndt_cl[which];
+  *count = cl.nvox;
+  const int m = cl.nvox < cap ? cl.nvox : cap;
+  rec.resize((size_t)m * rgck::kNdtRec);
+  cell.resize((size_t)m);
+  if (m <= 0) return RGC_OK;
+  HIPCHK(c, hipMemcpyAsync(rec.data(), cl.vox.p, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(cell.data(), cl.vox_cell.p, sizeof(int) * cell.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RGC_OK;
+}
+
+static void ndt_cov9(const double* r6, double* C) {
+  C[0] = r6[0]; C[1] = r6[1]; C[2] = r6[2];
+  C[3] = r6[1]; C[4] = r6[3]; C[5] = r6[4];
+  C[6] = r6[2]; C[7] = r6[4]; C[8] = r6[5];
+}
+
+int rgc_ndt_get_voxels(rgc_ctx* c, int which, int cap, int* coords, int* num, double* mean, double* cov9, int* count) {
+  if (!c || !count) return RGC_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<double> rec;
+  std::vector<int> cell;
+  int total = 0;
+  const int rc = ndt_fetch_voxels(c, which, cap, rec, cell, &total);
+  if (rc) return rc;
+  *count = total;
+  const rgck::Grid& g = c->ndt_cl[which].grid;
+  for (size_t v = 0; v < cell.size(); v++) {
+    const double* r = &rec[v * rgck::kNdtRec];
+    const int ci = cell[v];
+    if (coords) {
+      coords[v * 3 + 0] = ci % g.dim[0] + g.minc[0];
+#if defined(RGC_Y_SLOWEST) && RGC_Y_SLOWEST  // the cell order of rgck::cell_index
+      coords[v * 3 + 2] = (ci / g.dim[0]) % g.dim[2] + g.minc[2];
+      coords[v * 3 + 1] = ci / (g.dim[0] * g.dim[2]) + g.minc[1];
+#else
+      coords[v * 3 + 1] = (ci / g.dim[0]) % g.dim[1] + g.minc[1];
+      coords[v * 3 + 2] = ci / (g.dim[0] * g.dim[1]) + g.minc[2];
+#endif
+    }
+    if (num) num[v] = (int)r[9];
+    if (mean) { mean[v * 3] = r[0]; mean[v * 3 + 1] = r[1]; mean[v * 3 + 2] = r[2]; }
+    if (cov9) ndt_cov9(r + 3, cov9 + v * 9);
+  }
+  return RGC_OK;
+}
+
+int rgc_ndt_get_raw_covariances(rgc_ctx* c, int which, int cap, double* cov9, int* count) {
+  if (!c || !count) return RGC_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<double> rec;
+  std::vector<int> cell;
+  int total = 0;
+  const int rc = ndt_fetch_voxels(c, which, cap, rec, cell, &total);
+  if (rc) return rc;
+  *count = total;
+  if (cov9)
+    for (size_t v = 0; v < cell.size(); v++) ndt_cov9(&rec[v * rgck::kNdtRec] + 16, cov9 + v * 9);
   return RGC_OK;
 }
 

@@ -233,6 +233,18 @@ void transform_q(hipStream_t s, const float* in, int stride_f, int n, Quat q, co
 constexpr int kKfBlock = 256;
 struct KfSegment { const float4* src; int n; int out0; Quat q; double t[3]; };
 void kf_assemble(hipStream_t s, const KfSegment* seg, const int* blk0, int nseg, int nblocks, float4* out);
+// ---- NDT registration on a Gaussian voxel map (rgc_ndt.hip; fast_gicp::NDTCuda, src/fast_gicp/cuda/ndt_cuda.cu) ----
+// voxel record = kNdtRec doubles: mean(3), covariance after MIN_EIG (6: xx xy xz yy yz zz), number of points, its inverse (6), the covariance
+// before MIN_EIG (6), two unused.  The voxels are those of the grid's occupied cells (cell_voxel / vox_cell as for the VGICP map).
+constexpr int kNdtRec = 24;
+void ndt_voxels(hipStream_t s, const float4* P, const int* start, Grid g, const int* cell_voxel, double* vox, int* vox_cell);
+int  ndt_blocks(int n);
+// the terms of n source elements (d2d: the records svox of the source's own map; else the points in / stride_f) against the target map
+// (g, cell_voxel, vox) at T.  find != 0: the voxels at T + offs[3 * o ..] are looked up and written to corr_v[o * n + i]; else that list is
+// read.  Tlin: the pose of the last linearisation (its rotation enters the D2D matrices).  partials: ndt_blocks(n) rows of kAccum doubles,
+// ipartials: as many ints; out29: the 28 sums and the number of terms.
+void ndt_terms(hipStream_t s, int d2d, int find, const float* in, int stride_f, const double* svox, int n, Pose T, Pose Tlin, Grid g, const int* cell_voxel,
+               const double* vox, const int* offs, int noff, int* corr_v, int want_H, double* partials, int* ipartials, double* out29);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,
