@@ -39,22 +39,11 @@ constexpr unsigned kDevEvent = hipEventDisableTiming | hipEventReleaseToDevice;
 #ifndef RGC_LM_POST
 #define RGC_LM_POST 1          // 0: rgc_align_end always waits for the stream and its copy of the state (round 2)
 #endif
-#ifndef RGC_SMALL_COPY
-#define RGC_SMALL_COPY 0       // 1: the 32-byte host-to-device copy in front of every preparation
-#endif
 #ifndef RGC_FE_SPEC
 #define RGC_FE_SPEC 1          // 0: the front-end reads every sweep's size back before its stencil kernels
 #endif
 #ifndef RGC_SOLVE_BEHIND_MAP
 #define RGC_SOLVE_BEHIND_MAP 1 // 0: the solve always on the scan's (high-priority) stream (round 2)
-#endif
-#ifndef RGC_LM_SPARE_ASIDE
-#define RGC_LM_SPARE_ASIDE 1   // 0: a solve's spare step launches stay on its own stream, in front of whatever comes next there (round 3)
-#endif
-#ifndef RGC_MARK_BEHIND_COUNT
-#define RGC_MARK_BEHIND_COUNT 0  // 1: the map's stream mark is recorded BEHIND its counting pass (round 4).  An event record between two kernels of one
-                                 // stream holds the second one back ~5.8 us (the timeline of round 5); in front of the frame's first launch the record is
-                                 // processed while the GPU waits for the host anyway: two contexts steady 0.340 -> 0.334 ms per frame
 #endif
 #ifndef RGC_KNN_SEEDS
 #define RGC_KNN_SEEDS 1        // 0: the map's exact search never starts from the previous search's k-th distances (round 4)
@@ -214,7 +203,6 @@ struct rgc_ctx {
   struct { bool active = false; bool want_fitness = false; float guess[16]; } pend;  // rgc_align_begin .. rgc_align_end
   struct { bool on = false; int rc = 0; float T[16]; double H[36]; double fitness = 0; int iterations = 0, converged = 0, lm_failed = 0; bool has_fit = false; } gen_res;  // general route: rgc_align_begin solves at once, rgc_align_end hands this over
   int lm_last_outer = 0;      // outer iterations of the previous solve: sizes the next blind batch
-  bool small_copy_always = RGC_SMALL_COPY != 0;  // (build flag) 1: the 32-byte copy in front of every preparation, as before
   bool small_clean[2] = {false, false};  // d_small block of the map / the scan holds its initial image (the last solve's first step restored it)
   hipStream_t solve_stream = nullptr;  // where the pending solve was enqueued (rgc_align_begin)
   bool solve_behind_map = RGC_SOLVE_BEHIND_MAP != 0;  // (build flag) 0: the solve always on the scan's (high-priority) stream, as in round 2
@@ -528,13 +516,10 @@ int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox = false
   // recorded on the main stream BEFORE this frame's map preparation was enqueued (waiting for the map's kNN launch would serialise
   // the two) -- i.e. at rgc_set_target*, or here when no map preparation is pending.  See rgc_set_source_device in rgc_hip.h.
   if (!is_target && c->main_has_target_prep && map_prep_finished(c)) c->main_has_target_prep = false;  // it has drained
-  // (RGC_MARK_BEHIND_COUNT=1, round 4: the map's own mark BEHIND its counting pass -- the record is a call of its own in front of the dependent
-  // sequence's first launch, and a scan that waits for one 17 us kernel more has lost nothing; round 5 measured the record's cost on the
-  // GPU between the two kernels and put it back in front)
-  bool mark_behind_count = false;
+  // (The map's own mark sits in FRONT of its counting pass: an event record between two kernels of one stream holds the second one back
+  // ~5.8 us; in front of the frame's first launch it is processed while the GPU waits for the host anyway.)
   if (is_target || !c->main_has_target_prep || c->main_late_producer) {
-    if (is_target && RGC_MARK_BEHIND_COUNT) mark_behind_count = true;
-    else HIPCHK(c, hipEventRecord(c->main_mark, c->stream));
+    HIPCHK(c, hipEventRecord(c->main_mark, c->stream));
     c->mark_valid = true;
     c->main_late_producer = false;
   }
@@ -546,7 +531,7 @@ int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox = false
     // bbox accumulators + flag; the map's copy also zeroes [7], its voxel counter ([8] ncorr stays untouched; the scan's
     // block lives at +16 and must not touch the map's counter)
     // ... unless the previous solve's first step has already put the block back to this image on the device (reinit_small_blocks)
-    if (!c->small_clean[is_target ? 0 : 1] || c->small_copy_always) {
+    if (!c->small_clean[is_target ? 0 : 1]) {
       const int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
       const size_t init_bytes = 8 * sizeof(int);  // the scan's eighth int (d_small[23]) is its sum of count^2, a float accumulated by the cell scan
       memcpy(hsm, init, init_bytes);
@@ -759,7 +744,6 @@ int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox = false
     }  // (a smaller grid leaves the counters beyond it as clean as they were: a re-framed map's box breathes with the yaw)
     rgck::count_cells(s, cl.in, cl.stride_f, n, g, (int*)cl.cell_of.p, (int*)cl.slot_of.p, (int*)cl.cnt.p, hi, spec ? dsm + 6 : nullptr,
                       fuse_reframe ? &cl.rf : nullptr);
-    if (mark_behind_count) HIPCHK(c, hipEventRecord(c->main_mark, c->stream));
     rgck::scan_cells(s, (int*)cl.cnt.p, (int*)cl.start.p, (int)ntot, cl.block_sums.p, is_target ? (int*)cl.cell_voxel.p : nullptr,
                      is_target ? c->d_small + 7 : nullptr, hi, is_target ? nullptr : (float*)(c->d_small + 23));
     const bool with_cache = is_target && &cl == &c->tgt && cl.cache_on;
@@ -1923,7 +1907,7 @@ static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, boo
     // drain beside whatever the caller enqueues next on the solve's stream (the next frame's map preparation) instead of in front of it.
     // (Not a third stream: two contexts with three streams each outnumber the hardware queues, and streams that share a queue serialise --
     // the two-context sequence lost 130 us per frame that way.)
-    const int spare = (RGC_LM_SPARE_ASIDE && batch > kSpare + 1) ? kSpare : 0;
+    const int spare = batch > kSpare + 1 ? kSpare : 0;
     hipStream_t other = s == c->stream ? c->stream2 : c->stream;
     for (int k = 0; k < batch - spare; k++) { step(open, s); open = nullptr; }
     if (spare > 0) {
@@ -2493,16 +2477,7 @@ int rgc_get_voxels(rgc_ctx* c, int cap, int* coords, int* num, double* mean, dou
   for (int v = 0; v < m; v++) {
     const double* r = &rec[(size_t)v * rgck::kVoxRec];
     const int ci = cell[v];
-    if (coords) {
-      coords[v * 3 + 0] = ci % g.dim[0] + g.minc[0];
-#if defined(RGC_Y_SLOWEST) && RGC_Y_SLOWEST  // the cell order of rgck::cell_index
-      coords[v * 3 + 2] = (ci / g.dim[0]) % g.dim[2] + g.minc[2];
-      coords[v * 3 + 1] = ci / (g.dim[0] * g.dim[2]) + g.minc[1];
-#else
-      coords[v * 3 + 1] = (ci / g.dim[0]) % g.dim[1] + g.minc[1];
-      coords[v * 3 + 2] = ci / (g.dim[0] * g.dim[1]) + g.minc[2];
-#endif
-    }
+    if (coords) rgck::cell_coords(g, ci, coords + v * 3);
     if (num) num[v] = (int)r[9];
     if (mean) { mean[v * 3] = r[0]; mean[v * 3 + 1] = r[1]; mean[v * 3 + 2] = r[2]; }
     if (cov9) {
@@ -4513,16 +4488,7 @@ int rgc_ndt_get_voxels(rgc_ctx* c, int which, int cap, int* coords, int* num, do
   for (size_t v = 0; v < cell.size(); v++) {
     const double* r = &rec[v * rgck::kNdtRec];
     const int ci = cell[v];
-    if (coords) {
-      coords[v * 3 + 0] = ci % g.dim[0] + g.minc[0];
-#if defined(RGC_Y_SLOWEST) && RGC_Y_SLOWEST  // the cell order of rgck::cell_index
-      coords[v * 3 + 2] = (ci / g.dim[0]) % g.dim[2] + g.minc[2];
-      coords[v * 3 + 1] = ci / (g.dim[0] * g.dim[2]) + g.minc[1];
-#else
-      coords[v * 3 + 1] = (ci / g.dim[0]) % g.dim[1] + g.minc[1];
-      coords[v * 3 + 2] = ci / (g.dim[0] * g.dim[1]) + g.minc[2];
-#endif
-    }
+    if (coords) rgck::cell_coords(g, ci, coords + v * 3);
     if (num) num[v] = (int)r[9];
     if (mean) { mean[v * 3] = r[0]; mean[v * 3 + 1] = r[1]; mean[v * 3 + 2] = r[2]; }
     if (cov9) ndt_cov9(r + 3, cov9 + v * 9);

@@ -29,6 +29,16 @@ inline Grid make_grid(const int minc[3], const int dim[3], double res) {
   g.ncell = nc <= 2.0e9 ? (int)nc : -1;
   return g;
 }
+// Cell order: x fastest (a grid row = the cells of one (y, z) = one contiguous range of the sorted array), then y, then z.
+// (x, z, y was measured: 43 MB of HBM traffic per 1 M-query kNN launch instead of 73, but the launch 3 % slower -- the populated
+// neighbour rows of a surface are the y-neighbours, which that order moves apart; the kernel is bound by instruction issue, not bytes.)
+__host__ __device__ __forceinline__ int cell_index(const Grid& g, int cx, int cy, int cz) { return (cz * g.dim[1] + cy) * g.dim[0] + cx; }
+// ... and its inverse: the integer cell coordinates (minc included) of cell ci
+inline void cell_coords(const Grid& g, int ci, int out3[3]) {
+  out3[0] = ci % g.dim[0] + g.minc[0];
+  out3[1] = (ci / g.dim[0]) % g.dim[1] + g.minc[1];
+  out3[2] = ci / (g.dim[0] * g.dim[1]) + g.minc[2];
+}
 
 struct Pose {  // row-major rotation + translation, fp64 (Eigen::Isometry3d in the reference)
   double R[9];

@@ -95,12 +95,10 @@ __device__ __forceinline__ double quad_sum_f64(double v) {  // (l0 + l1) + (l2 +
 // source kernels finish while the big kernel soaks up what is left.
 // Three levels: the map's throughput kernels stay at 0, the scan's preparation runs at 2, the solve's steps and the score -- the
 // frame's critical chain, which with two contexts share the chip with the NEXT scan's preparation -- at 3.
-#ifndef RGC_SCAN_PRIO
-#define RGC_SCAN_PRIO 2
-#endif
+constexpr int kScanPrio = 2;
 __device__ __forceinline__ void wave_prio(int hi) {
   if (hi >= 2) __builtin_amdgcn_s_setprio(3);
-  else if (hi) __builtin_amdgcn_s_setprio(RGC_SCAN_PRIO);
+  else if (hi) __builtin_amdgcn_s_setprio(kScanPrio);
 }
 
 // Developer build (-DRGC_LAB_TURN): the turn-around of a dependent sequence -- from the moment a solve's deciding launch posts its final pose to
@@ -202,22 +200,9 @@ __global__ void __launch_bounds__(256) k_bbox(const float* __restrict__ in, int 
   if (bad) atomicOr(flags, 1);
 }
 
-// Cell order: x fastest (a grid row = the cells of one (y, z) = one contiguous range of the sorted array), then y, then z.
-// -DRGC_Y_SLOWEST=1 makes it x, z, y: a lidar map is flat (hundreds of cells in x and y, ten or twenty in z), so with y slowest a
-// contiguous run of queries keeps its candidates in a ~0.5 MB window of the array, and with one long run per XCD (-DRGC_XCD_RUN=496)
-// the bulk kNN launch re-reads almost nothing: 43 MB of HBM traffic per 1 M-query launch instead of 73 (algorithmic 36) -- but the
-// launch is 3 % SLOWER (0.163-0.169 ms against 0.157: the populated neighbour rows of a surface are the y-neighbours, which that
-// order moves apart) and the frame 2-3 % (scripts/exp_xcd_run.sh).  The kernel is bound by instruction issue, not bytes: the default
-// keeps the faster order.
-#ifndef RGC_Y_SLOWEST
-#define RGC_Y_SLOWEST 0
-#endif
-__device__ __forceinline__ int cell_index(const Grid& g, int cx, int cy, int cz) {
-  return RGC_Y_SLOWEST ? (cy * g.dim[2] + cz) * g.dim[0] + cx : (cz * g.dim[1] + cy) * g.dim[0] + cx;
-}
-// which (dy, dz) the r-th row of a D x D block is, rows counted in MEMORY order
-__device__ __forceinline__ constexpr int row_dy(int r, int D, int R) { return (RGC_Y_SLOWEST ? r / D : r % D) - R; }
-__device__ __forceinline__ constexpr int row_dz(int r, int D, int R) { return (RGC_Y_SLOWEST ? r % D : r / D) - R; }
+// which (dy, dz) the r-th row of a D x D block is, rows counted in MEMORY order (cell_index, rgc_kernels.h: x fastest, then y, then z)
+__device__ __forceinline__ constexpr int row_dy(int r, int D, int R) { return r % D - R; }
+__device__ __forceinline__ constexpr int row_dz(int r, int D, int R) { return r / D - R; }
 
 // guard (nullable): the grid was NOT derived from this cloud (a speculative grid kept from the previous one): a point with
 // non-finite / absurd coordinates sets bit 0, a point outside the grid bit 1 -- the host re-prepares the cloud when it
@@ -846,16 +831,8 @@ __device__ __forceinline__ void for_each_cube_row(const Grid& g, const int c[3],
   }
 }
 
-#ifndef RGC_KNN_T
-#define RGC_KNN_T 256
-#endif
-#ifndef RGC_SP_ONE_EXIT
-#define RGC_SP_ONE_EXIT 0  // (1: the unseeded search's candidate loop with one exit like the seeded one's -- 0.172 against 0.156 ms per 1 M-query launch: it loses there)
-#endif
-constexpr int KNN_T = RGC_KNN_T;  // (64- and 128-thread workgroups: the same launch time, round 3)
-#ifndef RGC_XCD_RUN
-#define RGC_XCD_RUN 16
-#endif
+constexpr int KNN_T = 256;  // (64- and 128-thread workgroups: the same launch time, round 3)
+constexpr int kXcdRunQueries = 16 * KNN_T;  // consecutive queries one XCD takes at a time (k_knn_sp), whatever the workgroup size
 
 // Queries the lane-per-query kernel cannot finish -- a sparse neighbourhood whose k-th neighbour is not provably inside the 3x3x3
 // block (the search cube must grow), several candidates at exactly the k-th distance (the original index decides), more candidates
@@ -924,19 +901,9 @@ constexpr unsigned long long kSlotEmpty = 0x8080808080808080ull;  // (what hipMe
 // they are legitimate candidates and need no masking.
 // kTarget separates the two instantiations by NAME (map vs scan) for the profiles and picks the ordinal width.
 // ------------------------------------------------------------------------------------------------
-#ifndef RGC_ROW_SKIP
-#define RGC_ROW_SKIP 1
-#endif
-constexpr bool kRowSkip = RGC_ROW_SKIP != 0;  // the map's search (whole rows, no piece machinery) skips rows by their distance bound
 constexpr int kPieceQuads = 1023;  // a piece's length in quads shares its table entry with the piece's distance bound (fp32, low 10 bits cut)
-#ifndef RGC_SPBUF
-#define RGC_SPBUF 12
-#endif
-constexpr int kSpBuf = RGC_SPBUF;   // keys waiting to enter the chain, per lane
-#ifndef RGC_SPLOW
-#define RGC_SPLOW 8
-#endif
-constexpr int kSpLow = RGC_SPLOW;   // the map's kernel drains a full buffer down to this many keys (0: to the bottom), knn_point_sp
+constexpr int kSpBuf = 12;  // keys waiting to enter the chain, per lane
+constexpr int kSpLow = 8;   // the map's kernel drains a full buffer down to this many keys (0: to the bottom), knn_point_sp
 static_assert(kSpLow >= 0 && kSpLow <= kSpBuf - 4, "a quad of four keys must fit above the drained level");
 // Block geometry and LDS layout of one instantiation.  R = block radius in cells, kClip as described at knn_point_sp.
 // LDS per lane, as columns [slot][lane]: the append buffer, the piece table (padded with INT_MAX for the ordinal -> piece search)
@@ -1050,14 +1017,12 @@ __device__ __forceinline__ void sp_pieces(const int* __restrict__ start, const G
   // of it -- so pieces OWN, OWN + 1, OWN + 2, and the rows behind it shifted by two. ----
   const int xl = max(c[0] - R, 0), xh = min(c[0] + R, g.dim[0] - 1);
   // distance from the query to the walls of its cell; a row / piece at offset d cells is at least (|d| - 1) cells + that away
-  double wlo[3] = {0, 0, 0}, whi[3] = {0, 0, 0};
-  if (kClip || kRowSkip || kXCut) {
+  double wlo[3], whi[3];
 #pragma unroll
-    for (int a = 0; a < 3; a++) {
-      const double wall = cell_wall(g, a, c[a]);
-      wlo[a] = fmax(q[a] - wall, 0.0);
-      whi[a] = fmax(wall + g.res - q[a], 0.0);
-    }
+  for (int a = 0; a < 3; a++) {
+    const double wall = cell_wall(g, a, c[a]);
+    wlo[a] = fmax(q[a] - wall, 0.0);
+    whi[a] = fmax(wall + g.res - q[a], 0.0);
   }
   auto axis_gap = [&](int a, int d) { return d == 0 ? 0.0 : (d < 0 ? wlo[a] + (double)(-d - 1) * g.res : whi[a] + (double)(d - 1) * g.res); };
   auto bound2 = [&](double gy, double gz) { return (float)((gy * gy + gz * gz) * (1.0 - 1.0e-6)); };  // rounded down a little: never too high
@@ -1095,7 +1060,7 @@ __device__ __forceinline__ void sp_pieces(const int* __restrict__ start, const G
       const int p = (!kClip || r < OWN) ? r : r + 2;
       lo[p] = in ? a : 0;
       hi[p] = in ? b : 0;
-      min2[p] = (kClip || kRowSkip) ? bound2(axis_gap(1, dy), axis_gap(2, dz)) : 0.f;
+      min2[p] = bound2(axis_gap(1, dy), axis_gap(2, dz));
     }
   }
   // A piece's last quad may read up to 3 points past the piece.  Where the next piece of this block (in memory order) starts closer
@@ -1116,7 +1081,7 @@ __device__ __forceinline__ void sp_pieces(const int* __restrict__ start, const G
     for (int p = 0; p < NP; p++) {
       if (hi[p] > lo[p]) {
         const int a = carry >= 0 ? carry : lo[p];
-        if ((kClip || kRowSkip) && carry >= 0 && carry < lo[p]) min2[p] = fminf(min2[p], carry_min2);
+        if (carry >= 0 && carry < lo[p]) min2[p] = fminf(min2[p], carry_min2);
         const int len = hi[p] - a;
         const bool tight = next_lo[p] - hi[p] < 3;
         const int keep = tight ? (len & ~3) : len;
@@ -1157,7 +1122,7 @@ __device__ __forceinline__ int sp_piece_table(const int* __restrict__ start, con
       if (!kClip) heavy_piece |= quads > (kRowRel + 1) / 4;  // the row's candidates must fit the ordinal's row-relative part
       tlo[nr * T] = lo[p];
       // (whole rows: at most 32 quads, six bits; the row's distance bound, rounded down, in the rest)
-      tmix[nr * T] = kClip ? ((__float_as_int(min2[p]) & ~kPieceQuads) | quads) : (kRowSkip ? ((__float_as_int(min2[p]) & ~63) | quads) : quads);
+      tmix[nr * T] = (__float_as_int(min2[p]) & ~(kClip ? kPieceQuads : 63)) | quads;
       nr++;
     }
   }
@@ -1233,9 +1198,6 @@ __device__ __forceinline__ bool list_certified(float a_up, float b_lo, double bo
 // searches everything): its list says so, and it goes onto the todo list the later frames search (by rank = its position in this frame:
 // the lists outlive the frame's order).  ~1 % of the queries, an atomic each on one of kTodoLists words.
 constexpr int kListCertified = (int)0x80000000;
-#ifndef RGC_CACHE_XCD_EIGHTHS
-#define RGC_CACHE_XCD_EIGHTHS 0  // 1: the list look-ups of each XCD cover one contiguous eighth of the map (measured: 2 % slower than the searches' runs)
-#endif
 #ifndef RGC_KNN_CACHE
 #define RGC_KNN_CACHE 1  // 0: the neighbour-list workgroups are not compiled into k_knn_sp (rgc_api.hip's flag of the same name keeps the host from asking for them)
 #endif
@@ -1328,7 +1290,7 @@ __device__ __forceinline__ void knn_point_sp(const float4* __restrict__ P, const
       // next row -- as an EMPTY one if nothing in it can be among the k + 2 nearest any more (its distance bound is not below the
       // chain's tail): the lane idles for this quad and moves on with the next; ordinals are {row, position}, so skipping renumbers nothing
       const int mix = tmix[ri * T];
-      const int quads = kRowSkip ? ((__int_as_float(mix & ~63) >= __int_as_float(tau | kKeyOrd)) ? 0 : (mix & 63)) : mix;
+      const int quads = (__int_as_float(mix & ~63) >= __int_as_float(tau | kKeyOrd)) ? 0 : (mix & 63);
       off = (unsigned)tlo[ri * T] << 4;
       end = off + ((unsigned)quads << 6);
       ordn = ri << 7;
@@ -1390,9 +1352,7 @@ __device__ __forceinline__ void knn_point_sp(const float4* __restrict__ P, const
     if (!__any(qa.live)) break;
     fetch(qb);
     process(qa);
-#if !RGC_SP_ONE_EXIT
     if (!__any(qb.live)) break;
-#endif
     fetch(qa);
     process(qb);
   }
@@ -1495,34 +1455,14 @@ struct SeedShape {
   static constexpr int BUF = KC + kSeedExtra + 5;  // k + kSeedExtra + 1 = "too many", and a quad appends up to four before the count is clamped
   static constexpr int LDS = BUF + SpShape<1, false>::NP;  // ints per lane
 };
-#ifndef RGC_SEED_ROW_SKIP
-#define RGC_SEED_ROW_SKIP 1
-#endif
-constexpr bool kSeedRowSkip = RGC_SEED_ROW_SKIP != 0;
 // a candidate's coordinates: the first 12 bytes of its 16-byte record (global_load_dwordx3: three quarters of the vector-memory
 // pipe's cycles of a 16-byte load; the original index is only needed of the query itself)
-#ifndef RGC_SEED_X3
-#define RGC_SEED_X3 1
-#endif
-#if RGC_SEED_X3
 struct Cand { float x, y, z; };
 __device__ __forceinline__ Cand cand_at(const float4* __restrict__ P, unsigned byte_off) {
   typedef float f32x3 __attribute__((ext_vector_type(3)));
   const f32x3 v = *reinterpret_cast<const f32x3*>(reinterpret_cast<const char*>(P) + byte_off);
   return Cand{v.x, v.y, v.z};
 }
-#else
-typedef float4 Cand;
-__device__ __forceinline__ Cand cand_at(const float4* __restrict__ P, unsigned byte_off) { return point_at(P, byte_off); }
-#endif
-#ifndef RGC_SEED_XCUT
-#define RGC_SEED_XCUT 1
-#endif
-constexpr bool kSeedXCut = RGC_SEED_XCUT != 0;  // rows also cut in x (sp_pieces)
-#ifndef RGC_SEED_DEPTH
-#define RGC_SEED_DEPTH 2
-#endif
-constexpr int kSeedDepth = RGC_SEED_DEPTH;  // quads of candidates in flight (2: one being processed, one loading; 3)
 constexpr int kSeedMaxPoints = (1 << 26) - 8;  // a table entry holds a position in 26 bits
 
 template <int KC, int KB, int T>
@@ -1553,7 +1493,7 @@ __device__ __forceinline__ bool knn_point_seeded(const float4* __restrict__ P, c
   {
     int lo[NP], hi[NP];
     float min2[NP];
-    sp_pieces<false, R, kSeedXCut>(start, g, c, q, lo, hi, min2, tauf);
+    sp_pieces<false, R, true>(start, g, c, q, lo, hi, min2, tauf);  // rows also cut in x
     bool heavy = false;
     // rows in MEMORY order (the bound is known: nothing is gained by visiting the nearest first): the admitted keys then come out in
     // ascending position in the sorted array -- the order the moments are summed in on every route
@@ -1562,7 +1502,7 @@ __device__ __forceinline__ bool knn_point_seeded(const float4* __restrict__ P, c
       const int len = hi[p] - lo[p];
       const int quads = (len + 3) >> 2;
       heavy |= quads > (kRowRel + 1) / 4;
-      if (len > 0 && (!kSeedRowSkip || min2[p] < tauf)) {  // (a row handed a neighbour's tail inherited its bound: sp_pieces)
+      if (len > 0 && min2[p] < tauf) {  // (a row handed a neighbour's tail inherited its bound: sp_pieces)
         tab[nv * T] = (lo[p] << 6) | quads;
         nv++;
       }
@@ -1610,29 +1550,15 @@ __device__ __forceinline__ bool knn_point_seeded(const float4* __restrict__ P, c
   // block, where the compiler's scoreboard merges "the first set's loads are pending" with "the second set's are" and puts an
   // s_waitcnt vmcnt(0) at the loop's head -- every other trip waited for the loads it had just issued (the loop of rounds 2-4 did).
   // A wave may run one trip more than its longest lane needs (sentinel loads, nothing appended).
-  if constexpr (kSeedDepth == 3) {  // two quads' loads in flight behind the one being processed
-    Quad qa, qb, qc;
-    fetch(qa);
+  // (two quads in flight: one being processed, one loading; three were measured and dropped)
+  Quad qa, qb;
+  fetch(qa);
+  for (;;) {
+    if (!__any(qa.live)) break;
     fetch(qb);
-    for (;;) {
-      if (!__any(qa.live)) break;
-      fetch(qc);
-      process(qa);
-      fetch(qa);
-      process(qb);
-      fetch(qb);
-      process(qc);
-    }
-  } else {
-    Quad qa, qb;
+    process(qa);
     fetch(qa);
-    for (;;) {
-      if (!__any(qa.live)) break;
-      fetch(qb);
-      process(qa);
-      fetch(qa);
-      process(qb);
-    }
+    process(qb);
   }
   int m = (int)(bp - buf) / T;
   if (m < KC) {
@@ -2088,13 +2014,8 @@ __device__ __forceinline__ bool knn_point_split(const float4* __restrict__ P, co
 //   scan : 3x3x3 block as 11 pieces with distance bounds, 12 ordinal bits (4095 candidates) -- a raw sweep: hundreds of points per
 //          cell next to the sensor (done after the own piece), metres between neighbours on its far rings (cooperative kernel).
 template <bool kTarget> struct SpConfig {
-#ifndef RGC_SCAN_KB
-#define RGC_SCAN_KB 12
-#endif
-#ifndef RGC_SCAN_R
-#define RGC_SCAN_R 1
-#endif
-  static constexpr int KB = kTarget ? 11 : RGC_SCAN_KB, R = kTarget ? 1 : RGC_SCAN_R;  // (R = 2, 3 work; for a VLP-16 sweep beside the map's launch they lose to R = 1 at 1 m cells)
+  static constexpr int KB = kTarget ? 11 : 12;  // (the scan with 13: measured and dropped)
+  static constexpr int R = 1;  // (the scan with R = 2, 3: for a VLP-16 sweep beside the map's launch they lose to R = 1 at 1 m cells)
   static constexpr bool kClip = !kTarget;
   // The scan's launch runs beside the map's, which fills every CU's LDS with four 256-thread workgroups: one-wave workgroups
   // (18 KiB of LDS each) are admitted as soon as ONE of those retires, a 256-thread one (73 KiB) would wait for two.
@@ -2122,19 +2043,9 @@ void lab_wave_ts(long long* out, hipStream_t s) {
 // and a slot freed by a finished wave is refilled only when a whole workgroup's worth is free; smaller ones refill sooner.  128, not 64:
 // one-wave workgroups refill so promptly that the SCAN's one-wave kernels, which run beside this launch on the other stream, no longer
 // get in -- a frame one at a time 0.354 -> 0.394 ms (the launch alone 0.122 -> 0.120; 256: 0.123 / 0.361).
-#ifndef RGC_SEED_T
-#define RGC_SEED_T 128
-#endif
-constexpr int kSeedT = RGC_SEED_T;
-#ifndef RGC_SEED_WAVES
-#define RGC_SEED_WAVES 1
-#endif
-#ifndef RGC_SP_WAVES
-#define RGC_SP_WAVES 1  // the map's full search: 86 VGPRs and 30 KB of LDS per 256 threads = five waves per SIMD either way
-#endif
+constexpr int kSeedT = 128;
 template <bool kTarget, bool kSeeded> struct SpLaunch : SpConfig<kTarget> {
   static constexpr int T = kSeeded ? kSeedT : SpConfig<kTarget>::T;
-  static constexpr int W = kSeeded ? RGC_SEED_WAVES : (kTarget ? RGC_SP_WAVES : 1);  // waves per SIMD the register allocation must leave room for (1: whatever it takes)
 };
 struct CoopRows {  // per-wave LDS scratch of the cooperative search (coop_run)
   int pref[WAVE + 1];
@@ -2430,7 +2341,8 @@ k_knn_coop(const float4* __restrict__ P, const int* __restrict__ start, Grid g, 
 }
 
 template <int KC, bool kTarget, bool kExact, bool kSeeded = false>
-__global__ void __launch_bounds__((SpLaunch<kTarget, kSeeded>::T), (SpLaunch<kTarget, kSeeded>::W))
+__global__ void __launch_bounds__((SpLaunch<kTarget, kSeeded>::T), 1)  // (1 wave per SIMD: no cap on the registers -- the map's full search,
+                                                                        // 86 VGPRs and 30 KB of LDS per 256 threads, runs five waves per SIMD either way)
 k_knn_sp(const float4* __restrict__ P, const int* __restrict__ start, Grid g, int n, int k, Deferred df,
          double* __restrict__ nx, double* __restrict__ ny, double* __restrict__ nz) {
   extern __shared__ int slist_sp[];  // [SpShape::LDS][T]
@@ -2441,7 +2353,7 @@ k_knn_sp(const float4* __restrict__ P, const int* __restrict__ start, Grid g, in
   // XCD-aware block order: workgroups are dealt round-robin over the 8 XCDs (b and b + 8 share one) and queries are in cell order.
   // Each XCD takes runs of kXcdRun CONSECUTIVE query blocks (neighbouring cells: their candidates are re-used out of that XCD's L2),
   // the runs themselves dealt round-robin (whole contiguous eighths of the map differ too much in work: 7 % slower).
-  constexpr int kXcdRun = RGC_XCD_RUN * KNN_T / Cfg::T;  // (a run is RGC_XCD_RUN x 256 consecutive queries whatever the workgroup size)
+  constexpr int kXcdRun = kXcdRunQueries / Cfg::T;
   int b = (int)blockIdx.x, slot = b >> 3;
   const int x = b & 7;
   if constexpr (!kTarget) {  // four lanes per query, queries in cell order
@@ -2461,9 +2373,8 @@ k_knn_sp(const float4* __restrict__ P, const int* __restrict__ start, Grid g, in
     // displace: the sparse far field of a sweep, 12 % of a VLP-16's queries -- is searched again on the 5x5x5 block by the same four lanes,
     // at once: 97 % of them settle there, and a wave of the far field has few candidates either way.  (They used to go to the
     // cooperative kernel, a wave per query and four dependent passes each: the longest launch of the scan's preparation.)
-    if (i < n && knn_point_split<KC, Cfg::KB, Cfg::R, Cfg::T, kExact, Cfg::R >= 2>(P, start, g, n, k, i, t & 3, slist_sp + threadIdx.x, df, nx, ny, nz)) {
-      if constexpr (Cfg::R < 2) knn_point_split<KC, Cfg::KB, 2, Cfg::T, kExact, true>(P, start, g, n, k, i, t & 3, slist_sp + threadIdx.x, df, nx, ny, nz);
-    }
+    if (i < n && knn_point_split<KC, Cfg::KB, Cfg::R, Cfg::T, kExact, false>(P, start, g, n, k, i, t & 3, slist_sp + threadIdx.x, df, nx, ny, nz))
+      knn_point_split<KC, Cfg::KB, 2, Cfg::T, kExact, true>(P, start, g, n, k, i, t & 3, slist_sp + threadIdx.x, df, nx, ny, nz);
 #ifdef RGC_LAB
     if (threadIdx.x == 0 && b < 8192) { g_lab_wave[2 * b] = lab_t0; g_lab_wave[2 * b + 1] = wall_clock64(); }
 #endif
@@ -2518,11 +2429,7 @@ k_knn_sp(const float4* __restrict__ P, const int* __restrict__ start, Grid g, in
 #endif
   if constexpr (kSeeded) {
     if (cached) {
-#if RGC_CACHE_XCD_EIGHTHS
-      // every list look-up costs the same: each XCD takes one contiguous eighth of the map (the searches' runs are dealt round-robin because
-      // their work differs from region to region) -- neighbouring queries' look-ups then stay in ONE XCD's L2
-      i = (x * (((int)gridDim.x - df.cache_nb) >> 3) + slot) * Cfg::T + (int)threadIdx.x;
-#endif
+      // (the look-ups of each XCD covering one contiguous eighth of the map: measured, 2 % slower than the searches' runs)
       if (i < n) knn_point_cached<KC>(P, i, df, nx, ny, nz);
       return;
     }
@@ -2643,18 +2550,8 @@ __global__ void __launch_bounds__(kListT) k_lazy_lists(const float4* __restrict_
   if (head) cell_list[base_s[1] + wc[w] + __popcll(mh & below)] = s;
 }
 
-#ifndef RGC_GRID_T
-#define RGC_GRID_T 256  // workgroup size of the grid build's per-point passes (k_count, k_place, k_rank_gather)
-#endif
-#ifndef RGC_VOX_T
-#define RGC_VOX_T 256
-#endif
-constexpr int VOX_T = RGC_VOX_T;
-#ifndef RGC_VOX_WAVES
-#define RGC_VOX_WAVES 1  // waves per SIMD k_voxel_build_coop's register allocation must leave room for.  6 (rounds 3-5) held the launch to 80
-                         // VGPRs -- and its cooperative half, the deferred queries everything behind the launch waits for, to 180 bytes of
-                         // scratch spills; without the cap (128 VGPRs, no scratch) a frame is 8 us shorter
-#endif
+constexpr int kGridT = 256;  // workgroup size of the grid build's per-point passes (k_count, k_place, k_rank_gather)
+constexpr int VOX_T = 256;   // workgroup size of the voxel pass (measured against 128 / 512: no difference)
 // LDS of a voxel-building workgroup: the nine terms of its points (rows one element longer than the block: the nine rows of one point
 // fall into nine different bank pairs) and the list of the cells that START in the block.
 struct VoxLds {
@@ -2755,7 +2652,8 @@ k_voxel_build(const float4* __restrict__ P, const double* __restrict__ nx, const
 // afterwards (k_voxel_patch).  Two streams and events did the same 20 us SLOWER than the serial chain (a cross-stream dependency costs
 // ~10 us here); one launch has no such hop.
 template <int KC>
-__global__ void __launch_bounds__(VOX_T, RGC_VOX_WAVES)
+__global__ void __launch_bounds__(VOX_T, 1)  // (no cap on the registers: 6 waves per SIMD held the launch to 80 VGPRs and its cooperative half to
+                                             // 180 bytes of scratch spills; without it -- 128 VGPRs, no scratch -- a frame is 8 us shorter)
 k_voxel_build_coop(const float4* __restrict__ P, double* __restrict__ nx, double* __restrict__ ny, double* __restrict__ nz,
                    const int* __restrict__ start, Grid g, int n, const int* __restrict__ cell_voxel, double* __restrict__ vox,
                    int* __restrict__ vox_cell, int nb_coop, int k, Deferred df) {
@@ -4468,8 +4366,8 @@ void bbox(hipStream_t s, const float* in, int stride_f, int n, double res, int* 
 }
 void count_cells(hipStream_t s, const float* in, int stride_f, int n, Grid g, int* cell_of, int* slot_of, int* cnt, int hi, int* guard,
                  const Reframe* rf) {
-  if (rf) hipLaunchKernelGGL(k_count<true>, dim3(nblk(n, RGC_GRID_T)), dim3(RGC_GRID_T), 0, s, in, 4, n, g, cell_of, slot_of, cnt, guard, hi, *rf);
-  else hipLaunchKernelGGL(k_count<false>, dim3(nblk(n, RGC_GRID_T)), dim3(RGC_GRID_T), 0, s, in, stride_f, n, g, cell_of, slot_of, cnt, guard, hi, Reframe{});
+  if (rf) hipLaunchKernelGGL(k_count<true>, dim3(nblk(n, kGridT)), dim3(kGridT), 0, s, in, 4, n, g, cell_of, slot_of, cnt, guard, hi, *rf);
+  else hipLaunchKernelGGL(k_count<false>, dim3(nblk(n, kGridT)), dim3(kGridT), 0, s, in, stride_f, n, g, cell_of, slot_of, cnt, guard, hi, Reframe{});
 }
 void scan_cells(hipStream_t s, int* cnt, int* start, int n, void* block_sums, int* cell_voxel, int* nvox, int hi, float* sum_sq) {
   const int nb = nblk(n, SCAN_B);
@@ -4483,7 +4381,7 @@ void scan_cells(hipStream_t s, int* cnt, int* start, int n, void* block_sums, in
   }
 }
 void place(hipStream_t s, int n, const int* cell_of, const int* slot_of, const int* start, unsigned long long* order_tmp, int hi, const KnnCache* cache) {
-  hipLaunchKernelGGL(k_place, dim3(nblk(n, RGC_GRID_T)), dim3(RGC_GRID_T), 0, s, n, cell_of, slot_of, start, order_tmp, hi, cache ? *cache : KnnCache{});
+  hipLaunchKernelGGL(k_place, dim3(nblk(n, kGridT)), dim3(kGridT), 0, s, n, cell_of, slot_of, start, order_tmp, hi, cache ? *cache : KnnCache{});
 }
 void exclusive_scan(hipStream_t s, const int* in, int* out, int n, int* block_sums, int hi) {
   const int nb = nblk(n, SCAN_B);
@@ -4495,7 +4393,7 @@ void exclusive_scan(hipStream_t s, const int* in, int* out, int n, int* block_su
 }
 void rank_gather(hipStream_t s, const float* in, int stride_f, int n, const int* cell_of, const int* start,
                  const unsigned long long* order_tmp, float4* P, int* zero_me, int hi, const KnnCache* cache) {
-  hipLaunchKernelGGL(k_rank_gather, dim3(nblk(n, RGC_GRID_T)), dim3(RGC_GRID_T), 0, s, in, stride_f, n, cell_of, start, order_tmp, P, zero_me, hi,
+  hipLaunchKernelGGL(k_rank_gather, dim3(nblk(n, kGridT)), dim3(kGridT), 0, s, in, stride_f, n, cell_of, start, order_tmp, P, zero_me, hi,
                      cache ? *cache : KnnCache{});
 }
 size_t deferred_bytes(int n) { return sizeof(int) * (2 * (size_t)n + 16); }
@@ -4532,10 +4430,10 @@ static void knn_bulk_kc(hipStream_t s, bool is_target, const float4* P, const in
   // (the scan's launch lays its per-lane LDS columns out for the 3x3x3 block and again, for the queries that block does not settle, for the 5x5x5 one)
   const size_t lds = (size_t)(is_target ? (seeded ? std::max(SpShape<CT::R, CT::kClip>::LDS, SeedShape<KC>::LDS) : SpShape<CT::R, CT::kClip>::LDS)
                                         : std::max(SpShape<CS::R, CS::kClip>::LDS, SpShape<2, CS::kClip>::LDS)) * T * sizeof(int);
-  // whole rounds of 8 XCDs x RGC_XCD_RUN blocks (excess blocks fall out at i >= n); lazy target: as many blocks as the listed queries are
+  // whole rounds of 8 XCDs x xcd_run blocks (excess blocks fall out at i >= n); lazy target: as many blocks as the listed queries are
   // expected to fill (the kernel strides over the list whatever its true length)
   const int n_launch = (is_target && qlist) ? (q_est < T ? T : (q_est > n ? n : q_est)) : n;
-  const int xcd_run = RGC_XCD_RUN * KNN_T / T;
+  const int xcd_run = kXcdRunQueries / T;
   int nb = (is_target && qlist) ? nblk(n_launch, T) : 8 * xcd_run * nblk(nblk(n, T), 8 * xcd_run);
   if (seeded && !qlist && df.cache.nbr) {
     // the workgroups in front of the bulk ones search the listed queries: sized for 4 % of the map (they stride over longer lists)

@@ -12,14 +12,6 @@ namespace rgck {
 constexpr int NDT_T = 256;   // threads per workgroup of the term kernels
 constexpr int NDT_WAVE = 64;
 
-__device__ __forceinline__ int ndt_cell_index(const Grid& g, int cx, int cy, int cz) {
-#if defined(RGC_Y_SLOWEST) && RGC_Y_SLOWEST  // the cell order of rgc_kernels.hip's cell_index
-  return (cy * g.dim[2] + cz) * g.dim[0] + cx;
-#else
-  return (cz * g.dim[1] + cy) * g.dim[0] + cx;
-#endif
-}
-
 // One Jacobi rotation in the (P, Q) plane of the symmetric A, accumulated into V (columns = eigenvectors).  Every index is a template
 // argument: A and V live in registers.
 template <int P, int Q>
@@ -210,7 +202,7 @@ __global__ void __launch_bounds__(NDT_T) k_ndt_terms(const float* __restrict__ i
       int v = -1;
       if (kFind) {
         const int x = cx + offs[3 * o], y = cy + offs[3 * o + 1], z = cz + offs[3 * o + 2];
-        if (in_range && x >= 0 && x < g.dim[0] && y >= 0 && y < g.dim[1] && z >= 0 && z < g.dim[2]) v = cell_voxel[ndt_cell_index(g, x, y, z)];
+        if (in_range && x >= 0 && x < g.dim[0] && y >= 0 && y < g.dim[1] && z >= 0 && z < g.dim[2]) v = cell_voxel[cell_index(g, x, y, z)];
         if (v >= 0 && !(vox[(size_t)v * kNdtRec + 9] > 6.0)) v = -1;  // num_points <= 6: no term (:61-63, :132-134)
         corr_v[slot] = v;
       } else {

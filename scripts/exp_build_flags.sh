@@ -9,7 +9,7 @@ cd "$(dirname "$0")/.."
 MODE=${1:-both}
 D=${RGC_FLAG_LIB_DIR:-$PWD/exp_flags}
 mkdir -p gpurun_out "$D"
-FLAGS="-DRGC_SMALL_COPY=1 -DRGC_SRC_RES=0.5 -DRGC_SRC_RES=2.0 -DRGC_MAP_WIDE=0 -DRGC_MAP_WIDE=1000 -DRGC_MAP_WIDE_R=0 -DRGC_LM_POST=0 -DRGC_SOLVE_BEHIND_MAP=0 -DRGC_FE_SPEC=0 -DRGC_LM_SPARE_ASIDE=0"
+FLAGS="-DRGC_SRC_RES=0.5 -DRGC_SRC_RES=2.0 -DRGC_MAP_WIDE=0 -DRGC_MAP_WIDE=1000 -DRGC_MAP_WIDE_R=0 -DRGC_LM_POST=0 -DRGC_SOLVE_BEHIND_MAP=0 -DRGC_FE_SPEC=0"
 if [ $MODE != run ]; then
   for flag in $FLAGS; do
     out=$D/librgc_alt_$(echo "$flag" | tr -c 'A-Za-z0-9' '_').so

@@ -81,7 +81,13 @@ def test_knob_inventory_is_current():
     import make_knobs
     readme = open(os.path.join(ROOT, "README.md")).read()
     assert [n for n, _ in make_knobs.env_vars() if n not in readme] == []
-    assert len(make_knobs.build_flags()) >= 30
+    # the generator still finds the flags (by name: the routes README.md, scripts/exp_build_flags.sh, scripts/isa_mix.py or a test lean on;
+    # RGC_KNN_CACHE is defined in two files) -- and the inventory stays what it was pruned to: a new measured-and-dropped variant is an
+    # EXPERIMENTS.md entry and a commit hash, not a new flag
+    flags = [n for n, _, _, _ in make_knobs.build_flags()]
+    assert set(flags) >= {"RGC_LM_POST", "RGC_FE_SPEC", "RGC_SOLVE_BEHIND_MAP", "RGC_EARLY_POSE", "RGC_KNN_SEEDS", "RGC_KNN_CACHE", "RGC_MAP_WIDE",
+                          "RGC_MAP_WIDE_R", "RGC_SRC_RES", "RGC_PREP_EVENT_EXT", "RGC_JOIN_SPIN_US"}
+    assert flags.count("RGC_KNN_CACHE") == 2 and len(flags) <= 13
 
 
 def test_every_entry_point_selects_its_device():
