@@ -1119,12 +1119,16 @@ void orc_rigid_from_sums(double n, const double sp[3], const double sq[3], const
       for (int k = 0; k < 3; k++) HtH[a * 3 + b] += H[k * 3 + a] * H[k * 3 + b];
   orc_eig3(HtH, ev, V); /* descending, V columns */
   double U[9];
+  double s0 = 0.0; /* the largest singular value, |H v0| */
   for (int j = 0; j < 2; j++) {
     double u[3] = {0, 0, 0};
     for (int a = 0; a < 3; a++)
       for (int k = 0; k < 3; k++) u[a] += H[a * 3 + k] * V[k * 3 + j];
     double nn = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    if (!(nn > 1e-300)) { /* rank deficient: any unit vector orthogonal to the previous columns */
+    if (j == 0) s0 = nn;
+    /* rank deficient: any unit vector orthogonal to the previous columns.  The second singular value is judged relative to the first:
+     * of a rank-1 correlation H v1 is rounding noise of the sums, not 0, and normalising it gives a U that is not orthogonal */
+    if (!(nn > 1e-300) || (j == 1 && !(nn > 1e-6 * s0))) {
       if (j == 0) { u[0] = 1; u[1] = 0; u[2] = 0; }
       else {
         const double a0 = fabs(U[0]), a1 = fabs(U[3]), a2 = fabs(U[6]);

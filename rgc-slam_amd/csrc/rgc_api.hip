@@ -3771,12 +3771,18 @@ static void rigid_from_sums(double n, const double sp[3], const double sq[3], co
   host_eig3_sym(S6, ev, Va);  // ascending
   for (int a = 0; a < 3; a++) { V[a * 3 + 0] = Va[a * 3 + 2]; V[a * 3 + 1] = Va[a * 3 + 1]; V[a * 3 + 2] = Va[a * 3 + 0]; }  // descending
   double U[9];
+  double s0 = 0.0;  // the largest singular value, |H v0|
   for (int j = 0; j < 2; j++) {
     double w[3] = {0, 0, 0};
     for (int a = 0; a < 3; a++)
       for (int k = 0; k < 3; k++) w[a] += H[a * 3 + k] * V[k * 3 + j];
     double nn = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    if (!(nn > 1e-300)) {  // rank deficient: any unit vector orthogonal to the previous column
+    if (j == 0) s0 = nn;
+    // rank deficient: any unit vector orthogonal to the previous column.  The second singular value is judged RELATIVE to the first: of a
+    // rank-1 correlation (a target of two points, a kept set on one line) H v1 is rounding noise of the sums, not 0, and normalising
+    // that noise gave a U that was not orthogonal (det R = 0.9976 on a 2-point target).  Singular values that come from the
+    // eigenvalues of H^T H are known to ~1.5e-8 of the largest, so below 1e-6 of it the direction is not information.
+    if (!(nn > 1e-300) || (j == 1 && !(nn > 1e-6 * s0))) {
       if (j == 0) { w[0] = 1; w[1] = 0; w[2] = 0; }
       else {
         const double a0 = std::fabs(U[0]), a1 = std::fabs(U[3]), a2 = std::fabs(U[6]);
