@@ -730,6 +730,36 @@ RGC_API int rgc_ndt_align(rgc_ctx* ctx, const float guess[16], float final_T[16]
 RGC_API int rgc_ndt_get_voxels(rgc_ctx* ctx, int which, int cap, int* coords, int* n, double* mean, double* cov9, int* count);
 RGC_API int rgc_ndt_get_raw_covariances(rgc_ctx* ctx, int which, int cap, double* cov9, int* count);
 
+/* ---- FastGICP: GICP on exact nearest-neighbour correspondences: fast_gicp::FastGICP (include/fast_gicp/gicp/fast_gicp.hpp:25-87,
+ * include/fast_gicp/gicp/impl/fast_gicp_impl.hpp:103-237), the registration FastVGICP derives from ----
+ * On the context's OWN source and target (rgc_set_source* / rgc_set_target*, as FastVGICP inherits FastGICP's clouds) and their covariances as
+ * they are: computed from the k nearest neighbours on either covariance route, or given by rgc_set_source_covariances / rgc_set_target_covariances.
+ * No second copy of a cloud, no voxel look-up.  A lazy target is completed first; re-framed, borrowed (rgc_share_target) and map-bound targets
+ * are used where they lie.  With a solve in flight (rgc_align_begin .. rgc_align_end) these calls are refused like the getters
+ * (RGC_ERR_INVALID).  No source, no target, a NULL or non-finite pose: RGC_ERR_INVALID.  The LM and convergence settings are the context's rgc_params.
+ *   For a pose T (row-major 4x4) and every source point p_i (include/fast_gicp/gicp/impl/fast_gicp_impl.hpp:115-211):
+ *   q = float(T) p_i in fp32, ((m0 x + m1 y) + m2 z) + m3, never contracted (:119,131); j = the target point with the smallest fp32
+ * ((dx dx + dy dy) + dz dz), ties to the smaller index (:133); kept iff (double)key < d_max^2 (:136, strict).  For a kept pair, in fp64:
+ * a = R p_i + t, e = b_j - a, M = (C_B[j] + R C_A[i] R^T)^-1 (the 3x3 block of :146-150), cost += e^T M e, J = [skew(a), -I],
+ * H += J^T M J, b += J^T M e (:179-198).  Every reduction runs in a fixed order: results are bit-identical from run to run and between
+ * host- and device-pointer inputs.  No kept pair: cost 0, H = 0, b = 0.
+ *   Frozen cost: rgc_gicp_compute_error re-uses the pairs and the M of the last rgc_gicp_linearize at the pose it is given (:214-237).
+ * Setting, clearing or swapping a cloud, setting covariances and a setting that prepares a cloud again drop them (RGC_ERR_INVALID until the
+ * next rgc_gicp_linearize); a new maximum distance does not. */
+RGC_API int rgc_gicp_set_max_correspondence_distance(rgc_ctx* ctx, double d_max);   /* setMaxCorrespondenceDistance; default FLT_MAX (:18): nothing rejected; >= 0 */
+RGC_API int rgc_gicp_get_max_correspondence_distance(const rgc_ctx* ctx, double* d_max);
+/* linearize / compute_error: H, b as rgc_linearize (both or neither) */
+RGC_API int rgc_gicp_linearize(rgc_ctx* ctx, const double T[16], double H[36], double b[6], double* cost);
+RGC_API int rgc_gicp_compute_error(rgc_ctx* ctx, const double T[16], double* cost);
+RGC_API int rgc_gicp_num_correspondences(rgc_ctx* ctx, int* n_kept);               /* kept pairs of the last rgc_gicp_linearize */
+/* the pairs of the last rgc_gicp_linearize in caller order, n_source entries each (either may be NULL): idx = the target point's index or -1
+ * where rejected, sq_dist = the key even where rejected (:135) */
+RGC_API int rgc_gicp_get_correspondences(rgc_ctx* ctx, int* idx, float* sq_dist);
+/* computeTransformation (:103-112): LsqRegistration's driver as rgc_align's host route runs it (lsq_registration_impl.hpp:53-79, LM step :125-172),
+ * outputs as rgc_align's.  Any output pointer may be NULL. */
+RGC_API int rgc_gicp_align(rgc_ctx* ctx, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged,
+                           int* lm_failed);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

@@ -1,0 +1,139 @@
+// fast_gicp_hip.hpp -- header-only C++ adaptor over the C-ABI (include/rgc_hip.h, rgc_gicp_*): GICP on exact nearest-neighbour correspondences.
+// Stands in for fast_gicp::FastGICP<PointSource, PointTarget> (rgc_slam/include/fast_gicp/gicp/fast_gicp.hpp:25-87, impl/fast_gicp_impl.hpp:103-237) WITHOUT
+// requiring PCL/Eigen at build time, shaped like ndt_hip.hpp:
+//
+//   rgc::FastGICPHip gicp(0);                              // its own context on device 0, or FastGICPHip(vgicp.context()) on the clouds of a FastVGICPHip (not owned)
+//   gicp.setCorrespondenceRandomness(20); gicp.setMaxCorrespondenceDistance(1.0);
+//   gicp.setInputTarget(map); gicp.setInputSource(scan);   // any cloud with ->points / ->size() of x,y,z-first points
+//   gicp.align(guess);  gicp.getFinalTransformation();  gicp.hasConverged();
+//
+// The clouds and covariances are the context's own (rgc_set_source / rgc_set_target): what a FastVGICPHip on the same context has set is what
+// GICP registers.  Errors throw std::runtime_error carrying rgc_last_error().  No CPU fallback.
+#pragma once
+#include <array>
+#include <cstddef>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/rgc_hip.h"
+
+namespace rgc {
+
+class FastGICPHip {
+public:
+  typedef std::array<float, 16> Matrix4f;    // row-major
+  typedef std::array<double, 16> Matrix4d;   // row-major
+  typedef std::array<double, 36> Matrix6d;
+  typedef std::array<double, 6> Vector6d;
+
+  explicit FastGICPHip(int hip_device = 0, const rgc_params* params = nullptr) : own_(true) {
+    const int rc = rgc_create(hip_device, params, &ctx_);
+    if (rc != RGC_OK) throw std::runtime_error(std::string("rgc_create: ") + rgc_status_string(rc));
+    init();
+  }
+  explicit FastGICPHip(rgc_ctx* ctx) : ctx_(ctx), own_(false) {
+    if (!ctx) throw std::runtime_error("rgc::FastGICPHip: null context");
+    init();
+  }
+  ~FastGICPHip() { if (own_ && ctx_) rgc_destroy(ctx_); }
+  FastGICPHip(const FastGICPHip&) = delete;
+  FastGICPHip& operator=(const FastGICPHip&) = delete;
+
+  rgc_ctx* context() const { return ctx_; }
+
+  void setCorrespondenceRandomness(int k) { rgc_params p = params(); p.k_correspondences = k; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
+  void setMaximumIterations(int n) { rgc_params p = params(); p.max_iterations = n; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
+  void setTransformationEpsilon(double e) { rgc_params p = params(); p.translation_eps = e; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
+  void setRotationEpsilon(double e) { rgc_params p = params(); p.rotation_eps = e; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
+  void setRegularizationMethod(int method) { check(rgc_set_regularization_method(ctx_, method), "rgc_set_regularization_method"); }
+  void setMaxCorrespondenceDistance(double d) { check(rgc_gicp_set_max_correspondence_distance(ctx_, d), "rgc_gicp_set_max_correspondence_distance"); }
+  double getMaxCorrespondenceDistance() const {
+    double d = 0.0;
+    check(rgc_gicp_get_max_correspondence_distance(ctx_, &d), "rgc_gicp_get_max_correspondence_distance");
+    return d;
+  }
+
+  template <typename CloudPtr> void setInputTarget(const CloudPtr& cloud) {
+    check(rgc_set_target(ctx_, &cloud->points[0].x, (int)cloud->points.size(), (int)sizeof(cloud->points[0])), "rgc_set_target");
+  }
+  template <typename CloudPtr> void setInputSource(const CloudPtr& cloud) {
+    n_source_ = (int)cloud->points.size();
+    check(rgc_set_source(ctx_, &cloud->points[0].x, n_source_, (int)sizeof(cloud->points[0])), "rgc_set_source");
+  }
+  void setInputTargetDevice(const float* d_xyz, int n, int stride_bytes) { check(rgc_set_target_device(ctx_, d_xyz, n, stride_bytes), "rgc_set_target_device"); }
+  void setInputSourceDevice(const float* d_xyz, int n, int stride_bytes) {
+    n_source_ = n;
+    check(rgc_set_source_device(ctx_, d_xyz, n, stride_bytes), "rgc_set_source_device");
+  }
+  // row-major 3x3 per point (the upper-left block of the reference's Matrix4d)
+  void setSourceCovariances(const std::vector<double>& cov9) { check(rgc_set_source_covariances(ctx_, cov9.data(), (int)(cov9.size() / 9)), "rgc_set_source_covariances"); }
+  void setTargetCovariances(const std::vector<double>& cov9) { check(rgc_set_target_covariances(ctx_, cov9.data(), (int)(cov9.size() / 9)), "rgc_set_target_covariances"); }
+  void clearSource() { n_source_ = 0; check(rgc_clear_source(ctx_), "rgc_clear_source"); }
+  void clearTarget() { check(rgc_clear_target(ctx_), "rgc_clear_target"); }
+  void swapSourceAndTarget() {
+    check(rgc_swap_source_and_target(ctx_), "rgc_swap_source_and_target");
+    rgc_stats st;
+    check(rgc_get_stats(ctx_, &st), "rgc_get_stats");
+    n_source_ = st.n_source;
+  }
+
+  double linearize(const Matrix4d& T, Matrix6d* H = nullptr, Vector6d* b = nullptr) {
+    double cost = 0.0;
+    check(rgc_gicp_linearize(ctx_, T.data(), H && b ? H->data() : nullptr, H && b ? b->data() : nullptr, &cost), "rgc_gicp_linearize");
+    return cost;
+  }
+  double compute_error(const Matrix4d& T) {
+    double cost = 0.0;
+    check(rgc_gicp_compute_error(ctx_, T.data(), &cost), "rgc_gicp_compute_error");
+    return cost;
+  }
+  int numCorrespondences() {
+    int n = 0;
+    check(rgc_gicp_num_correspondences(ctx_, &n), "rgc_gicp_num_correspondences");
+    return n;
+  }
+  // the pairs of the last linearize in the source's order: idx -1 where rejected, sq_dist the key even there
+  void getCorrespondences(std::vector<int>& idx, std::vector<float>& sq_dist) {
+    idx.assign((size_t)n_source_, -1);
+    sq_dist.assign((size_t)n_source_, 0.f);
+    check(rgc_gicp_get_correspondences(ctx_, idx.data(), sq_dist.data()), "rgc_gicp_get_correspondences");
+  }
+
+  void align(const Matrix4f& guess) {
+    check(rgc_gicp_align(ctx_, guess.data(), final_.data(), hessian_.data(), &fitness_, &iterations_, &converged_, &lm_failed_), "rgc_gicp_align");
+  }
+  void align() {
+    const Matrix4f I = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+    align(I);
+  }
+  const Matrix4f& getFinalTransformation() const { return final_; }
+  const Matrix6d& getFinalHessian() const { return hessian_; }
+  double getFitnessScore() const { return fitness_; }
+  bool hasConverged() const { return converged_ != 0; }
+  bool lmFailed() const { return lm_failed_ != 0; }
+  int iterations() const { return iterations_; }
+
+private:
+  void init() {
+    final_ = Matrix4f{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+    hessian_.fill(0.0);
+  }
+  rgc_params params() const {
+    rgc_params p;
+    check(rgc_get_params(ctx_, &p), "rgc_get_params");
+    return p;
+  }
+  void check(int rc, const char* what) const {
+    if (rc != RGC_OK) throw std::runtime_error(std::string(what) + ": " + rgc_last_error(ctx_));
+  }
+  rgc_ctx* ctx_ = nullptr;
+  bool own_ = false;
+  int n_source_ = 0;
+  Matrix4f final_;
+  Matrix6d hessian_;
+  double fitness_ = 0.0;
+  int iterations_ = 0, converged_ = 0, lm_failed_ = 0;
+};
+
+}  // namespace rgc

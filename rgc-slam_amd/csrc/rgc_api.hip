@@ -299,6 +299,14 @@ struct rgc_ctx {
   bool ndt_corr_valid = false;            // ndt_corr holds the list of ndt_corr_n elements x ndt_corr_noff offsets made under ndt_corr_mode at ndt_Tlin
   int ndt_corr_n = 0, ndt_corr_noff = 0, ndt_corr_mode = 0, ndt_terms = 0;
   double ndt_Tlin[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  // FastGICP (rgc_gicp_*) on the context's own source and target: the pair list of the last rgc_gicp_linearize (per sorted source point the
+  // neighbour's position in the target's sorted array or -1, and the fp32 key), its Mahalanobis matrices, scratch of its own.  gicp_valid
+  // falls wherever corr_valid falls: a cloud set, cleared, swapped, given covariances or prepared again
+  double gicp_dmax = (double)FLT_MAX;     // corr_dist_threshold_ (fast_gicp_impl.hpp:18: std::numeric_limits<float>::max())
+  DevBuf gicp_corr, gicp_key, gicp_M, gicp_partials, gicp_out;
+  double* gicp_h_out = nullptr;           // pinned: 32 doubles
+  bool gicp_valid = false;
+  int gicp_n = 0, gicp_kept = 0;
   rgc_stats stats{};
   // profiling
   bool prof_on = false;
@@ -993,7 +1001,7 @@ int set_cloud(rgc_ctx* c, Cloud& cl, bool is_target, const float* xyz, int n, in
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
   cl.ready = false;
   cl.n = 0;
-  c->corr_valid = false;
+  c->corr_valid = c->gicp_valid = false;
   c->deferred_known = false;
   if (is_target) c->map_bound = false;
   { const int rs = check_supported(c); if (rs) return rs; }
@@ -1093,7 +1101,7 @@ int resolve_guards(rgc_ctx* c, int guard_t, int guard_s) {
     if (!cl[a]->ready || cl[a]->n <= 0) continue;  // (a cloud cleared since -- rgc_clear_source / _target --: its guard word is the last cloud's, there is nothing to prepare again)
     if (!gd[a]) continue;
     cl[a]->ready = false;
-    c->corr_valid = false;
+    c->corr_valid = c->gicp_valid = false;
     c->deferred_known = false;
     if (gd[a] & 1) { cl[a]->n = 0; return fail(c, RGC_ERR_NONFINITE, "%s cloud contains non-finite or absurd coordinates", a == 0 ? "target" : "source"); }
     static const bool trace = getenv("RGC_TRACE_ALLOC") != nullptr;
@@ -1666,6 +1674,8 @@ void rgc_destroy(rgc_ctx* c) {
   for (DevBuf* b : {&c->ndt_offs, &c->ndt_corr, &c->ndt_partials, &c->ndt_ipartials, &c->ndt_small, &c->ndt_out}) release(*b);
   if (c->ndt_h_out) (void)hipHostFree(c->ndt_h_out);
   if (c->ndt_h_small) (void)hipHostFree(c->ndt_h_small);
+  for (DevBuf* b : {&c->gicp_corr, &c->gicp_key, &c->gicp_M, &c->gicp_partials, &c->gicp_out}) release(*b);
+  if (c->gicp_h_out) (void)hipHostFree(c->gicp_h_out);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1691,7 +1701,7 @@ int rgc_set_params(rgc_ctx* c, const rgc_params* p) {
   c->prm = *p;
   // The correspondences the last linearisation froze stay what rgc_compute_error uses (with their own offset count, corr_noff) unless the
   // clouds are prepared again: the reference's setters, setNeighborSearchMethod among them, leave voxel_correspondences_ alone.
-  if (redo) c->corr_valid = false;
+  if (redo) c->corr_valid = c->gicp_valid = false;
   if (redo) {  // covariances / voxel map depend on these: recompute from the resident inputs
     if (c->tgt_owner) {
       // a BORROWED target (rgc_share_target) is the owner's, prepared under the owner's settings, and its input buffer is the owner's to
@@ -1758,7 +1768,7 @@ int rgc_share_target(rgc_ctx* c, rgc_ctx* owner) {
   c->tgt_owner_gen = owner->tgt_generation;
   c->tgt_owner_uid = owner->uid;
   c->map_bound = false;
-  c->corr_valid = false;
+  c->corr_valid = c->gicp_valid = false;
   c->deferred_known = false;
   c->main_has_target_prep = false;
   c->stats.n_target = o.n; c->stats.target_cells = o.grid.ncell; c->stats.n_voxels = o.nvox;
@@ -1782,7 +1792,7 @@ int rgc_set_regularization_method(rgc_ctx* c, int method) {
   if (method < RGC_REG_NONE || method > RGC_REG_FROBENIUS) return fail(c, RGC_ERR_INVALID, "rgc_set_regularization_method: %d is not a RegularizationMethod", method);
   if (method != c->reg_method) {  // the covariances of the clouds set so far were computed under the other method (the reference computes them at align())
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; c->corr_valid = false; c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; c->corr_valid = c->gicp_valid = false; c->deferred_known = false; c->map_bound = false;
   }
   c->reg_method = method;
   return RGC_OK;
@@ -1794,7 +1804,7 @@ int rgc_set_voxel_accumulation_mode(rgc_ctx* c, int mode) {
   const bool was = c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE, is = mode == RGC_VOXEL_MULTIPLICATIVE;
   if (was != is) {  // (ADDITIVE <-> ADDITIVE_WEIGHTED changes nothing: one voxel class in the vendored FastVGICP, fast_vgicp_voxel.hpp:137-141)
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; c->corr_valid = false; c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; c->corr_valid = c->gicp_valid = false; c->deferred_known = false; c->map_bound = false;
   }
   c->voxel_mode = mode;
   return RGC_OK;
@@ -2315,7 +2325,7 @@ static int set_covs(rgc_ctx* c, Cloud& cl, bool is_target, const double* cov9, i
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's array is read until here)
     HIPCHK(c, hipGetLastError());
-    c->corr_valid = false;
+    c->corr_valid = c->gicp_valid = false;
     cl.covs_user = true;
     return RGC_OK;
   }
@@ -2348,7 +2358,7 @@ static int set_covs(rgc_ctx* c, Cloud& cl, bool is_target, const double* cov9, i
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));   // (the host vector goes out of scope)
   HIPCHK(c, hipGetLastError());
-  c->corr_valid = false;
+  c->corr_valid = c->gicp_valid = false;
   cl.covs_user = true;
   return RGC_OK;
 }
@@ -2359,13 +2369,13 @@ int rgc_set_target_covariances(rgc_ctx* c, const double* cov9, int n) { return c
 int rgc_clear_source(rgc_ctx* c) {
   if (!c) return RGC_ERR_INVALID;
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-  c->src.ready = false; c->src.n = 0; c->src.spec_used = false; c->corr_valid = false; c->deferred_known = false;
+  c->src.ready = false; c->src.n = 0; c->src.spec_used = false; c->corr_valid = c->gicp_valid = false; c->deferred_known = false;
   return RGC_OK;
 }
 int rgc_clear_target(rgc_ctx* c) {
   if (!c) return RGC_ERR_INVALID;
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-  c->tgt.ready = false; c->tgt.n = 0; c->tgt.spec_used = false; c->corr_valid = false; c->deferred_known = false; c->map_bound = false;
+  c->tgt.ready = false; c->tgt.n = 0; c->tgt.spec_used = false; c->corr_valid = c->gicp_valid = false; c->deferred_known = false; c->map_bound = false;
   return RGC_OK;
 }
 
@@ -2413,7 +2423,7 @@ int rgc_swap_source_and_target(rgc_ctx* c) {
   std::swap(c->src.stride_f, c->tgt.stride_f);
   std::swap(c->src.n, c->tgt.n);
   c->src.ready = c->tgt.ready = false;
-  c->corr_valid = false; c->deferred_known = false; c->map_bound = false;
+  c->corr_valid = c->gicp_valid = false; c->deferred_known = false; c->map_bound = false;
   if ((rc = prepare_cloud(c, c->tgt, true, /*force_bbox=*/true))) { drop_kept(); return rc; }
   if ((rc = prepare_cloud(c, c->src, false, /*force_bbox=*/true))) { drop_kept(); return rc; }
   if (kept[0].on || kept[1].on) {
@@ -3533,7 +3543,7 @@ int rgc_map_reset(rgc_ctx* c, const double origin[3]) {
   c->map_n = 0;
   c->map_dirty = true;
   c->map_ntarget = 0;
-  if (c->map_bound) { c->tgt.ready = false; c->tgt.n = 0; c->corr_valid = false; c->map_bound = false; }
+  if (c->map_bound) { c->tgt.ready = false; c->tgt.n = 0; c->corr_valid = c->gicp_valid = false; c->map_bound = false; }
   for (int a = 0; a < 3; a++) c->map_origin[a] = origin ? origin[a] : 0.0;
   c->map_rev++;
   return RGC_OK;
@@ -3623,7 +3633,7 @@ int rgc_map_rebase(rgc_ctx* c, const double new_origin[3]) {
   c->map_rev++;
   if (c->map_bound) {  // the committed target is in the OLD origin's coordinates: an align before the next rgc_map_commit must fail, not drift
     c->tgt.ready = false;
-    c->corr_valid = false;
+    c->corr_valid = c->gicp_valid = false;
   }
   return RGC_OK;
 }
@@ -3644,7 +3654,7 @@ int rgc_map_commit(rgc_ctx* c, float leaf, int* n_target) {
   // downSizeFilter2.setInputCloud(laserCloudsubmap); filter (:985-991) -- on the resident store, nothing crosses PCIe
   if (c->map_bound) {  // from here on the buffer no longer holds the cloud the bound target was set from: whatever fails below, that target goes
     c->map_bound = false;
-    c->tgt.ready = false; c->tgt.n = 0; c->corr_valid = false;
+    c->tgt.ready = false; c->tgt.n = 0; c->corr_valid = c->gicp_valid = false;
   }
   if ((rc = rgc_voxelgrid(c, (const float*)c->map_store[c->map_cur].p, (int)c->map_n, 16, leaf, (float*)c->map_target.p, &nt, 1))) return rc;
   // setInputTarget (:1007): grid, exact-kNN covariances, Gaussian voxel map
@@ -4513,6 +4523,209 @@ int rgc_ndt_get_raw_covariances(rgc_ctx* c, int which, int cap, double* cov9, in
   *count = total;
   if (cov9)
     for (size_t v = 0; v < cell.size(); v++) ndt_cov9(&rec[v * rgck::kNdtRec] + 16, cov9 + v * 9);
+  return RGC_OK;
+}
+
+// ---- FastGICP: GICP on exact nearest-neighbour correspondences (include/fast_gicp/gicp/impl/fast_gicp_impl.hpp:103-237) on the context's own clouds ----
+int rgc_gicp_set_max_correspondence_distance(rgc_ctx* c, double d_max) {
+  if (!c) return RGC_ERR_INVALID;
+  if (std::isnan(d_max) || d_max < 0.0) return fail(c, RGC_ERR_INVALID, "rgc_gicp_set_max_correspondence_distance: the distance must be >= 0");
+  c->gicp_dmax = d_max;
+  return RGC_OK;
+}
+
+int rgc_gicp_get_max_correspondence_distance(const rgc_ctx* c, double* d_max) {
+  if (!c || !d_max) return RGC_ERR_INVALID;
+  *d_max = c->gicp_dmax;
+  return RGC_OK;
+}
+
+// a pose the GICP calls accept: finite in fp64 and after the cast to fp32 the search transforms with (fast_gicp_impl.hpp:119)
+static bool gicp_pose_ok(const double T[16]) {
+  for (int i = 0; i < 12; i++)
+    if (!std::isfinite(T[i]) || !std::isfinite((float)T[i])) return false;
+  return true;
+}
+
+// both clouds there, no solve in flight, the speculative grids' guards read, a lazy target completed, the source's preparation joined
+static int gicp_need_inputs(rgc_ctx* c) {
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  if (!c->src.ready || !c->tgt.ready) return fail(c, RGC_ERR_INVALID, "rgc_gicp_*: source and target must be set first");
+  int rc = need_inputs(c);
+  if (rc == RGC_ERR_NO_INPUT) return fail(c, RGC_ERR_INVALID, "rgc_gicp_*: source and target must be set first");
+  if (rc) return rc;
+  if (!c->gicp_h_out) HIPCHK(c, hipHostMalloc((void**)&c->gicp_h_out, sizeof(double) * 32, hipHostMallocDefault));
+  return ensure(c, c->gicp_out, sizeof(double) * 32);
+}
+
+static rgck::GicpCov gicp_cov_of(const Cloud& cl) {
+  if (cl.general) return rgck::GicpCov{(const double*)cl.c6.p, nullptr, nullptr, nullptr};
+  return rgck::GicpCov{nullptr, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p};
+}
+
+// update_correspondences + linearize (fast_gicp_impl.hpp:115-211); the inputs have been checked (gicp_need_inputs)
+static int gicp_do_linearize(rgc_ctx* c, const double T[16], double* H, double* b, double* cost) {
+  const Cloud& sc = c->src;
+  const Cloud& tg = c->tgt;
+  const int n = sc.n, nb = rgck::gicp_blocks(n);
+  int rc;
+  c->gicp_valid = false;
+  if ((rc = ensure(c, c->gicp_corr, sizeof(int) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_key, sizeof(float) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_M, sizeof(double) * 6 * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_partials, sizeof(double) * (rgck::kAccum + 1) * (size_t)nb))) return rc;
+  float T32[16];
+  for (int i = 0; i < 16; i++) T32[i] = (float)T[i];  // trans.cast<float>(), :119
+  const int want = (H && b) ? 1 : 0;
+  rgck::gicp_correspond(c->stream, (const float4*)sc.P.p, n, posef_from(T32), (const float4*)tg.P.p, (const int*)tg.start.p, tg.grid,
+                        c->gicp_dmax * c->gicp_dmax, (int*)c->gicp_corr.p, (float*)c->gicp_key.p);
+  rgck::gicp_terms(c->stream, (const float4*)sc.P.p, n, (const float4*)tg.P.p, tg.n, (const int*)c->gicp_corr.p, gicp_cov_of(sc), gicp_cov_of(tg), pose_from(T),
+                   want, (double*)c->gicp_M.p, (double*)c->gicp_partials.p, (double*)c->gicp_out.p);
+  HIPCHK(c, hipMemcpyAsync(c->gicp_h_out, c->gicp_out.p, sizeof(double) * (rgck::kAccum + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  const double* o = c->gicp_h_out;
+  c->gicp_valid = true;
+  c->gicp_n = n;
+  c->gicp_kept = (int)o[28];
+  if (want) {
+    int u = 0;
+    for (int a = 0; a < 6; a++)
+      for (int d = a; d < 6; d++) { H[a * 6 + d] = o[u]; H[d * 6 + a] = o[u]; u++; }
+    for (int a = 0; a < 6; a++) b[a] = o[21 + a];
+  }
+  if (cost) *cost = o[27];
+  return RGC_OK;
+}
+
+// compute_error (fast_gicp_impl.hpp:214-237) over the frozen pairs and matrices
+static int gicp_do_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c->gicp_valid || c->gicp_n != c->src.n) return fail(c, RGC_ERR_INVALID, "rgc_gicp_compute_error needs a preceding rgc_gicp_linearize on the present clouds");
+  const Cloud& sc = c->src;
+  const Cloud& tg = c->tgt;
+  rgck::gicp_error(c->stream, (const float4*)sc.P.p, sc.n, (const float4*)tg.P.p, tg.n, (const int*)c->gicp_corr.p, (const double*)c->gicp_M.p, pose_from(T),
+                   (double*)c->gicp_partials.p, (double*)c->gicp_out.p);
+  HIPCHK(c, hipMemcpyAsync(c->gicp_h_out, c->gicp_out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  *cost = c->gicp_h_out[0];
+  return RGC_OK;
+}
+
+int rgc_gicp_linearize(rgc_ctx* c, const double T[16], double H[36], double b[6], double* cost) {
+  if (!c || !T) return RGC_ERR_INVALID;
+  if (!gicp_pose_ok(T)) return fail(c, RGC_ERR_INVALID, "rgc_gicp_linearize: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = gicp_need_inputs(c);
+  return rc ? rc : gicp_do_linearize(c, T, H, b, cost);
+}
+
+int rgc_gicp_compute_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c || !T || !cost) return RGC_ERR_INVALID;
+  if (!gicp_pose_ok(T)) return fail(c, RGC_ERR_INVALID, "rgc_gicp_compute_error: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = gicp_need_inputs(c);
+  return rc ? rc : gicp_do_error(c, T, cost);
+}
+
+int rgc_gicp_num_correspondences(rgc_ctx* c, int* n) {
+  if (!c || !n) return RGC_ERR_INVALID;
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  if (!c->gicp_valid) return fail(c, RGC_ERR_INVALID, "rgc_gicp_num_correspondences needs a preceding rgc_gicp_linearize on the present clouds");
+  *n = c->gicp_kept;
+  return RGC_OK;
+}
+
+int rgc_gicp_get_correspondences(rgc_ctx* c, int* idx, float* sq_dist) {
+  if (!c) return RGC_ERR_INVALID;
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  if (!c->gicp_valid || !c->src.ready || !c->tgt.ready || c->gicp_n != c->src.n)
+    return fail(c, RGC_ERR_INVALID, "rgc_gicp_get_correspondences needs a preceding rgc_gicp_linearize on the present clouds");
+  if (!idx && !sq_dist) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int n = c->src.n;
+  int rc = check_target_owner(c);
+  if (rc) return rc;
+  if ((rc = ensure(c, c->scratch, (sizeof(int) + sizeof(float)) * (size_t)n))) return rc;
+  int* d_idx = (int*)c->scratch.p;
+  float* d_sq = (float*)(d_idx + n);
+  HIPCHK(c, hipMemsetAsync(d_idx, 0xff, sizeof(int) * (size_t)n, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_sq, 0, sizeof(float) * (size_t)n, c->stream));
+  rgck::gicp_export(c->stream, (const float4*)c->src.P.p, n, (const float4*)c->tgt.P.p, c->tgt.n, (const int*)c->gicp_corr.p, (const float*)c->gicp_key.p, d_idx, d_sq);
+  if (idx) HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (sq_dist) HIPCHK(c, hipMemcpyAsync(sq_dist, d_sq, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+
+// computeTransformation: LsqRegistration's driver and LM step (lsq_registration_impl.hpp:53-79, 125-172) over the two calls above, host-driven
+// like rgc_ndt_align; the fitness score of the final pose as rgc_align gives it
+int rgc_gicp_align(rgc_ctx* c, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged, int* lm_failed) {
+  if (!c || !guess) return RGC_ERR_INVALID;
+  for (int i = 0; i < 12; i++)
+    if (!std::isfinite(guess[i])) return fail(c, RGC_ERR_INVALID, "rgc_gicp_align: the guess is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = gicp_need_inputs(c);
+  if (rc) return rc;
+  const rgc_params& P = c->prm;
+  double x0[16];
+  for (int i = 0; i < 12; i++) x0[i] = (double)guess[i];
+  x0[12] = x0[13] = x0[14] = 0.0;
+  x0[15] = 1.0;
+  double lambda = -1.0;  // :56
+  bool conv = false, failed = false;
+  int iters = 0;
+  double Hfin[36];
+  memset(Hfin, 0, sizeof(Hfin));
+  for (int i = 0; i < 6; i++) Hfin[i * 7] = 1.0;  // final_hessian_.setIdentity(), :21
+  for (int it = 0; it < P.max_iterations && !conv; it++) {  // :65
+    iters = it + 1;
+    double H[36], b[6], y0, delta[16], d[6], xi[16], yi;
+    if (!gicp_pose_ok(x0)) { failed = true; break; }          // (a step of an empty or singular system: nothing to search at)
+    if ((rc = gicp_do_linearize(c, x0, H, b, &y0))) return rc;  // :128
+    if (lambda < 0.0) {  // :130-132
+      double m = 0;
+      for (int a = 0; a < 6; a++) m = std::fmax(m, std::fabs(H[a * 7]));
+      lambda = P.lm_init_lambda_factor * m;
+    }
+    double nu = 2.0;
+    bool ok = false;
+    memset(delta, 0, sizeof(delta));
+    for (int k = 0; k < P.lm_max_iterations; k++) {  // :135
+      rgclm::lm_try(H, b, lambda, x0, d, delta, xi);  // :136-143
+      if ((rc = gicp_do_error(c, xi, &yi))) return rc;  // :144
+      double den = 0;
+      for (int i = 0; i < 6; i++) den += d[i] * (lambda * d[i] - b[i]);
+      const double rho = (y0 - yi) / den;  // :145
+      if (rho < 0) {  // :155-163
+        if (is_converged(delta, P.rotation_eps, P.translation_eps)) { ok = true; break; }
+        lambda = nu * lambda;
+        nu = 2 * nu;
+        continue;
+      }
+      memcpy(x0, xi, sizeof(xi));  // :165
+      lambda = lambda * std::fmax(1.0 / 3.0, 1 - std::pow(2 * rho - 1, 3));  // :166
+      memcpy(Hfin, H, sizeof(Hfin));  // :167
+      ok = true;
+      break;
+    }
+    if (!ok) { failed = true; break; }  // :69-72 "lm not converged!!"
+    conv = is_converged(delta, P.rotation_eps, P.translation_eps);  // :74
+  }
+  float fin[16];
+  for (int i = 0; i < 16; i++) fin[i] = (float)x0[i];  // :77
+  if (final_T) memcpy(final_T, fin, sizeof(fin));
+  if (final_H) memcpy(final_H, Hfin, sizeof(Hfin));
+  if (iterations) *iterations = iters;
+  if (converged) *converged = conv ? 1 : 0;
+  if (lm_failed) *lm_failed = failed ? 1 : 0;
+  if (fitness) {
+    bool fin_ok = true;
+    for (int i = 0; i < 12; i++) fin_ok = fin_ok && std::isfinite(fin[i]);
+    if (!fin_ok) *fitness = (double)NAN;
+    else if ((rc = do_fitness(c, fin, fitness))) return rc;
+  }
   return RGC_OK;
 }
 

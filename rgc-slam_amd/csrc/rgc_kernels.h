@@ -255,6 +255,21 @@ int  ndt_blocks(int n);
 // ipartials: as many ints; out29: the 28 sums and the number of terms.
 void ndt_terms(hipStream_t s, int d2d, int find, const float* in, int stride_f, const double* svox, int n, Pose T, Pose Tlin, Grid g, const int* cell_voxel,
                const double* vox, const int* offs, int noff, int* corr_v, int want_H, double* partials, int* ipartials, double* out29);
+// ---- FastGICP: GICP on exact nearest-neighbour correspondences (rgc_gicp.hip; fast_gicp::FastGICP, include/fast_gicp/gicp/impl/fast_gicp_impl.hpp:103-237) ----
+// the covariances of a prepared cloud, in its sorted order: c6 (the general route: six doubles per point, SoA) or, c6 == nullptr, its unit normal
+struct GicpCov { const double* c6; const double* nx; const double* ny; const double* nz; };
+int  gicp_blocks(int n);
+// the exact nearest target point of every source point at T (fp32, nn_search): corr[s] = its sorted position or -1 (key >= dmax2), key[s] =
+// the squared distance; s = the source's sorted order
+void gicp_correspond(hipStream_t s, const float4* SP, int ns, PoseF T, const float4* TP, const int* tstart, Grid g, double dmax2, int* corr, float* key);
+// the terms of that pair list at T: M (6 * ns doubles, SoA) <- the Mahalanobis matrices; partials: gicp_blocks(ns) rows of kAccum + 1 doubles;
+// out29: the 28 sums and the number of pairs
+void gicp_terms(hipStream_t s, const float4* SP, int ns, const float4* TP, int nt, const int* corr, const GicpCov& A, const GicpCov& B, Pose T, int want_H,
+                double* M, double* partials, double* out29);
+// the cost of the same pairs under the same matrices at another pose
+void gicp_error(hipStream_t s, const float4* SP, int ns, const float4* TP, int nt, const int* corr, const double* M, Pose T, double* partials, double* out1);
+// the pair list in caller order: idx[i] = the neighbour's original index or -1, sq[i] = the key
+void gicp_export(hipStream_t s, const float4* SP, int ns, const float4* TP, int nt, const int* corr, const float* key, int* idx, float* sq);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,
