@@ -1,0 +1,540 @@
+// rgc_api_lsq.hip -- the host LM driver every registration method shares (LsqRegistration::computeTransformation and step_lm,
+// lsq_registration_impl.hpp:53-79, 125-172) and the two methods that are nothing else on the host: NDT (rgc_ndt_*) and FastGICP (rgc_gicp_*).
+// rgc_align's host-driven route (rgc_api.hip) runs on the same driver.  The kernels are in rgc_ndt.hip and rgc_gicp.hip.
+#include "rgc_ctx.h"
+#include "rgc_lm.h"
+
+using namespace rgcapi;
+
+// lsq_registration_impl.hpp:82-91
+static bool is_converged(const double d[16], double rot_eps, double trans_eps) {
+  double m = 0;
+  for (int a = 0; a < 3; a++) {
+    for (int b = 0; b < 3; b++) m = std::fmax(m, std::fabs(d[a * 4 + b] - (a == b ? 1.0 : 0.0)) / rot_eps);
+    m = std::fmax(m, std::fabs(d[a * 4 + 3]) / trans_eps);
+  }
+  return m < 1;
+}
+
+// LsqRegistration::computeTransformation (lsq_registration_impl.hpp:53-79) + step_lm (:125-172); SURVEY A.5.  The scalar pieces (so3_exp, the
+// LDLT solve, the 4x4 product) are rgc_lm.h's, shared with the device.
+int rgcapi::lm_solve(rgc_ctx* c, const LmSystem& sys, const float guess[16], LmResult* r) {
+  const rgc_params& P = c->prm;
+  double* x0 = r->x0;
+  for (int i = 0; i < 12; i++) x0[i] = (double)guess[i];
+  x0[12] = x0[13] = x0[14] = 0.0;
+  x0[15] = 1.0;
+  double lambda = -1.0;  // :56
+  r->conv = r->failed = false;
+  r->iters = 0;
+  memset(r->Hfin, 0, sizeof(r->Hfin));
+  for (int i = 0; i < 6; i++) r->Hfin[i * 7] = 1.0;  // final_hessian_.setIdentity(), :21
+  for (int it = 0; it < P.max_iterations && !r->conv; it++) {  // :65
+    r->iters = it + 1;
+    double H[36], b[6], y0, delta[16], d[6], xi[16], yi;
+    int rc;
+    if (sys.may_linearize && !sys.may_linearize(x0)) { r->failed = true; break; }  // (FastGICP: a step of an empty or singular system)
+    if (sys.linearize_try) {  // :128 and the first try of :135-144 in one call; :130-132 with it (lambda0 = factor * max|H_ii|)
+      if ((rc = sys.linearize_try(c, x0, lambda, H, b, &y0, d, xi, &lambda, &yi))) return rc;
+      double R[9];  // that try's delta = [so3_exp(d[0:3]) | d[3:6]] (:136-143)
+      rgclm::so3_exp_R(d, R);
+      memset(delta, 0, sizeof(delta));
+      for (int a = 0; a < 3; a++) { for (int e = 0; e < 3; e++) delta[a * 4 + e] = R[a * 3 + e]; delta[a * 4 + 3] = d[3 + a]; }
+      delta[15] = 1.0;
+    } else {
+      if ((rc = sys.linearize(c, x0, H, b, &y0))) return rc;  // :128
+      if (lambda < 0.0) {  // :130-132
+        double m = 0;
+        for (int a = 0; a < 6; a++) m = std::fmax(m, std::fabs(H[a * 7]));
+        lambda = P.lm_init_lambda_factor * m;
+      }
+    }
+    double nu = 2.0;
+    bool ok = false;
+    for (int k = 0; k < P.lm_max_iterations; k++) {  // :135
+      if (k > 0 || !sys.linearize_try) {  // (every try but one that linearize_try has made)
+        rgclm::lm_try(H, b, lambda, x0, d, delta, xi);  // :136-143
+        if ((rc = sys.error(c, xi, &yi))) return rc;    // :144
+      }
+      double den = 0;
+      for (int i = 0; i < 6; i++) den += d[i] * (lambda * d[i] - b[i]);
+      const double rho = (y0 - yi) / den;  // :145
+      if (rho < 0) {  // :155-163
+        if (is_converged(delta, P.rotation_eps, P.translation_eps)) { ok = true; break; }
+        lambda = nu * lambda;
+        nu = 2 * nu;
+        continue;
+      }
+      memcpy(x0, xi, sizeof(xi));  // :165
+      lambda = lambda * std::fmax(1.0 / 3.0, 1 - std::pow(2 * rho - 1, 3));  // :166
+      memcpy(r->Hfin, H, sizeof(r->Hfin));  // :167
+      ok = true;
+      break;
+    }
+    if (!ok) { r->failed = true; break; }  // :69-72 "lm not converged!!"
+    r->conv = is_converged(delta, P.rotation_eps, P.translation_eps);  // :74
+  }
+  for (int i = 0; i < 16; i++) r->fin[i] = (float)x0[i];  // :77
+  return RGC_OK;
+}
+
+extern "C" {
+
+// ---- NDT registration (P2D / D2D) on a Gaussian voxel map: fast_gicp::NDTCuda (src/fast_gicp/cuda/ndt_cuda.cu, ndt_compute_derivatives.cu) ----
+void rgc_default_ndt_params(rgc_ndt_params* p) {
+  if (!p) return;
+  p->resolution = 1.0;                     // src/fast_gicp/cuda/ndt_cuda.cu:15
+  p->distance_mode = RGC_NDT_D2D;          // :21
+  p->neighbor_method = RGC_NDT_DIRECT7;    // :22
+  p->neighbor_radius = 0.0;
+}
+
+// the offsets of a neighbour method in the reference's order (src/fast_gicp/cuda/ndt_cuda.cu:35-88); false: more than RGC_NDT_MAX_OFFSETS
+static bool ndt_offsets_of(int method, double radius, std::vector<int>& o) {
+  o.clear();
+  if (method == RGC_NDT_DIRECT1) { o = {0, 0, 0}; return true; }
+  if (method == RGC_NDT_DIRECT7) { o = {0, 0, 0, 1, 0, 0, -1, 0, 0, 0, 1, 0, 0, -1, 0, 0, 0, 1, 0, 0, -1}; return true; }
+  if (method == RGC_NDT_DIRECT27) {
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++)
+        for (int k = 0; k < 3; k++) { o.push_back(i - 1); o.push_back(j - 1); o.push_back(k - 1); }
+    return true;
+  }
+  if (radius > 16.0) return false;
+  const int range = (int)std::ceil(radius);
+  for (int i = -range; i <= range; i++)
+    for (int j = -range; j <= range; j++)
+      for (int k = -range; k <= range; k++)
+        if (std::sqrt((double)(i * i + j * j + k * k)) <= radius + 1e-3) {
+          if ((int)o.size() / 3 >= RGC_NDT_MAX_OFFSETS) return false;
+          o.push_back(i); o.push_back(j); o.push_back(k);
+        }
+  return true;
+}
+
+static void ndt_drop_terms(rgc_ctx* c) { c->ndt_corr_valid = false; c->ndt_terms = 0; }
+
+int rgc_ndt_set_params(rgc_ctx* c, const rgc_ndt_params* p) {
+  if (!c || !p) return RGC_ERR_INVALID;
+  if (!std::isfinite(p->resolution) || !(p->resolution > 0.0)) return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: resolution must be finite and > 0");
+  if (p->distance_mode != RGC_NDT_P2D && p->distance_mode != RGC_NDT_D2D) return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: no distance mode %d", p->distance_mode);
+  if (p->neighbor_method < RGC_NDT_DIRECT27 || p->neighbor_method > RGC_NDT_DIRECT_RADIUS) return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: no neighbour method %d", p->neighbor_method);
+  std::vector<int> offs;
+  if (p->neighbor_method == RGC_NDT_DIRECT_RADIUS) {
+    if (!std::isfinite(p->neighbor_radius) || p->neighbor_radius < 0.0) return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: DIRECT_RADIUS needs a finite radius >= 0");
+  }
+  if (!ndt_offsets_of(p->neighbor_method, p->neighbor_radius, offs))
+    return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: radius %g has more than %d offsets", p->neighbor_radius, RGC_NDT_MAX_OFFSETS);
+  if (p->resolution != c->ndt_prm.resolution || p->distance_mode != c->ndt_prm.distance_mode) ndt_drop_terms(c);
+  c->ndt_prm = *p;
+  c->ndt_offs_h.swap(offs);
+  c->ndt_offs_dirty = true;
+  return RGC_OK;
+}
+
+int rgc_ndt_get_params(const rgc_ctx* c, rgc_ndt_params* p) {
+  if (!c || !p) return RGC_ERR_INVALID;
+  *p = c->ndt_prm;
+  return RGC_OK;
+}
+
+// one body of the four setters: the points packed to 12 bytes each in the cloud's own buffer, in stream order on the context's stream
+static int ndt_set_cloud(rgc_ctx* c, int which, const float* xyz, int n, int stride_bytes, bool on_device) {
+  if (!c || !xyz) return RGC_ERR_INVALID;
+  if (!stride_ok(stride_bytes)) return fail(c, RGC_ERR_INVALID, "stride_bytes must be a multiple of 4 between 12 and 4096");
+  if (n < 1) return fail(c, n < 0 ? RGC_ERR_INVALID : RGC_ERR_TOO_FEW_POINTS, "rgc_ndt_set_*: a cloud needs at least one point");
+  if (n > (1 << 27)) return fail(c, RGC_ERR_INVALID, "cloud has %d points, the limit is 2^27", n);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if (on_device && (rc = check_device_range(c, xyz, (size_t)n * stride_bytes - (stride_bytes - 12), which ? "rgc_ndt_set_source_device" : "rgc_ndt_set_target_device"))) return rc;
+  Cloud& cl = c->ndt_cl[which];
+  if ((rc = ensure(c, cl.in_copy, (size_t)n * 12))) return rc;
+  HIPCHK(c, hipMemcpy2DAsync(cl.in_copy.p, 12, xyz, (size_t)stride_bytes, 12, (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  if (!on_device) HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller owns a host buffer for the duration of the call only
+  cl.in = (const float*)cl.in_copy.p;
+  cl.stride_f = 3;
+  cl.n = n;
+  cl.ready = false;
+  c->ndt_set[which] = true;
+  c->ndt_built[which] = false;
+  ndt_drop_terms(c);
+  return RGC_OK;
+}
+int rgc_ndt_set_target(rgc_ctx* c, const float* xyz, int n, int stride_bytes) { return ndt_set_cloud(c, 0, xyz, n, stride_bytes, false); }
+int rgc_ndt_set_source(rgc_ctx* c, const float* xyz, int n, int stride_bytes) { return ndt_set_cloud(c, 1, xyz, n, stride_bytes, false); }
+int rgc_ndt_set_target_device(rgc_ctx* c, const float* d_xyz, int n, int stride_bytes) { return ndt_set_cloud(c, 0, d_xyz, n, stride_bytes, true); }
+int rgc_ndt_set_source_device(rgc_ctx* c, const float* d_xyz, int n, int stride_bytes) { return ndt_set_cloud(c, 1, d_xyz, n, stride_bytes, true); }
+
+int rgc_ndt_clear_source(rgc_ctx* c) {
+  if (!c) return RGC_ERR_INVALID;
+  c->ndt_set[1] = c->ndt_built[1] = false;
+  ndt_drop_terms(c);
+  return RGC_OK;
+}
+int rgc_ndt_clear_target(rgc_ctx* c) {
+  if (!c) return RGC_ERR_INVALID;
+  c->ndt_set[0] = c->ndt_built[0] = false;
+  ndt_drop_terms(c);
+  return RGC_OK;
+}
+int rgc_ndt_swap_source_and_target(rgc_ctx* c) {
+  if (!c) return RGC_ERR_INVALID;
+  std::swap(c->ndt_cl[0], c->ndt_cl[1]);
+  std::swap(c->ndt_set[0], c->ndt_set[1]);
+  std::swap(c->ndt_built[0], c->ndt_built[1]);
+  std::swap(c->ndt_built_res[0], c->ndt_built_res[1]);
+  ndt_drop_terms(c);
+  return RGC_OK;
+}
+
+static int ndt_scratch(rgc_ctx* c) {
+  int rc;
+  if ((rc = ensure(c, c->ndt_small, 64))) return rc;
+  if ((rc = ensure(c, c->ndt_out, sizeof(double) * 32))) return rc;
+  if (!c->ndt_h_out) HIPCHK(c, hipHostMalloc((void**)&c->ndt_h_out, sizeof(double) * 32, hipHostMallocDefault));
+  if (!c->ndt_h_small) HIPCHK(c, hipHostMalloc((void**)&c->ndt_h_small, sizeof(int) * 8, hipHostMallocDefault));
+  return RGC_OK;
+}
+
+// the voxel map of NDT cloud `which` at the current resolution, if it is not there yet: the VGICP target's table construction (bounding box,
+// counting sort by voxel, points of a voxel in ascending index) and one segmented pass (rgck::ndt_voxels)
+static int ndt_build(rgc_ctx* c, int which) {
+  Cloud& cl = c->ndt_cl[which];
+  const double res = c->ndt_prm.resolution;
+  if (c->ndt_built[which] && c->ndt_built_res[which] == res) return RGC_OK;
+  c->ndt_built[which] = false;
+  int rc;
+  if ((rc = ndt_scratch(c))) return rc;
+  hipStream_t s = c->stream;
+  int* dsm = (int*)c->ndt_small.p;
+  int* hsm = c->ndt_h_small;
+  if ((rc = build_measured_grid(c, cl, res, dsm, hsm, true, which ? "NDT source" : "NDT target", which ? "NDT source: voxel grid" : "NDT target: voxel grid"))) return rc;
+  HIPCHK(c, hipMemcpyAsync(hsm + 7, dsm + 7, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  const int nvox = hsm[7];
+  if (nvox < 1 || nvox > cl.n) return fail(c, RGC_ERR_HIP, "NDT voxel count %d out of range", nvox);
+  if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kNdtRec * (size_t)nvox))) return rc;
+  if ((rc = ensure(c, cl.vox_cell, sizeof(int) * (size_t)nvox))) return rc;
+  rgck::ndt_voxels(s, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p);
+  HIPCHK(c, hipGetLastError());
+  cl.nvox = nvox;
+  cl.ready = true;
+  c->ndt_built[which] = true;
+  c->ndt_built_res[which] = res;
+  return RGC_OK;
+}
+
+static int ndt_need_inputs(rgc_ctx* c) {
+  if (!c->ndt_set[0]) return fail(c, RGC_ERR_NO_INPUT, "NDT target not set");
+  if (!c->ndt_set[1]) return fail(c, RGC_ERR_NO_INPUT, "NDT source not set");
+  int rc;
+  if ((rc = ndt_build(c, 0))) return rc;
+  if (c->ndt_prm.distance_mode == RGC_NDT_D2D && (rc = ndt_build(c, 1))) return rc;
+  return RGC_OK;
+}
+
+// find != 0: linearize at T (the term list and R_lin are made); else the cost at T over the frozen list.  out: 28 sums + the number of terms.
+static int ndt_run_terms(rgc_ctx* c, const double T[16], bool find, bool want_H, double out[29]) {
+  int rc;
+  if ((rc = ndt_scratch(c))) return rc;
+  const int d2d = find ? (c->ndt_prm.distance_mode == RGC_NDT_D2D) : c->ndt_corr_mode;
+  const Cloud& tg = c->ndt_cl[0];
+  const Cloud& sc = c->ndt_cl[1];
+  const int n = find ? (d2d ? sc.nvox : sc.n) : c->ndt_corr_n;
+  if (find) {
+    if (c->ndt_offs_h.empty()) ndt_offsets_of(c->ndt_prm.neighbor_method, c->ndt_prm.neighbor_radius, c->ndt_offs_h);
+    if (c->ndt_offs_dirty) {
+      if ((rc = ensure(c, c->ndt_offs, sizeof(int) * 3 * RGC_NDT_MAX_OFFSETS))) return rc;
+      HIPCHK(c, hipStreamSynchronize(c->stream));  // (a launch that reads the former list may still run)
+      HIPCHK(c, hipMemcpy(c->ndt_offs.p, c->ndt_offs_h.data(), sizeof(int) * c->ndt_offs_h.size(), hipMemcpyHostToDevice));
+      c->ndt_offs_dirty = false;
+    }
+    c->ndt_corr_valid = false;
+    c->ndt_corr_noff = (int)c->ndt_offs_h.size() / 3;
+    c->ndt_corr_n = n;
+    c->ndt_corr_mode = d2d;
+    memcpy(c->ndt_Tlin, T, sizeof(double) * 16);
+    if ((rc = ensure(c, c->ndt_corr, sizeof(int) * (size_t)n * c->ndt_corr_noff))) return rc;
+  }
+  const int noff = c->ndt_corr_noff;
+  const int nb = rgck::ndt_blocks(n);
+  if ((rc = ensure(c, c->ndt_partials, sizeof(double) * rgck::kAccum * (size_t)nb))) return rc;
+  if ((rc = ensure(c, c->ndt_ipartials, sizeof(int) * (size_t)nb))) return rc;
+  rgck::ndt_terms(c->stream, d2d, find ? 1 : 0, sc.in, sc.stride_f, (const double*)sc.vox.p, n, pose_from(T), pose_from(c->ndt_Tlin), tg.grid,
+                  (const int*)tg.cell_voxel.p, (const double*)tg.vox.p, (const int*)c->ndt_offs.p, noff, (int*)c->ndt_corr.p, want_H ? 1 : 0,
+                  (double*)c->ndt_partials.p, (int*)c->ndt_ipartials.p, (double*)c->ndt_out.p);
+  HIPCHK(c, hipMemcpyAsync(c->ndt_h_out, c->ndt_out.p, sizeof(double) * 29, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  memcpy(out, c->ndt_h_out, sizeof(double) * 29);
+  if (find) {
+    c->ndt_corr_valid = true;
+    c->ndt_terms = (int)out[28];
+  }
+  return RGC_OK;
+}
+
+static int ndt_do_linearize(rgc_ctx* c, const double T[16], double* H, double* b, double* cost) {
+  int rc = ndt_need_inputs(c);
+  if (rc) return rc;
+  double out[29];
+  const bool want = H && b;
+  if ((rc = ndt_run_terms(c, T, true, want, out))) return rc;
+  if (want) unpack_system(out, H, b);
+  if (cost) *cost = out[27];
+  return RGC_OK;
+}
+
+static int ndt_do_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c->ndt_set[0] || !c->ndt_set[1]) return fail(c, RGC_ERR_NO_INPUT, "NDT source or target not set");
+  if (!c->ndt_corr_valid) return fail(c, RGC_ERR_INVALID, "rgc_ndt_compute_error needs a preceding rgc_ndt_linearize");
+  double out[29];
+  const int rc = ndt_run_terms(c, T, false, false, out);
+  if (rc) return rc;
+  *cost = out[27];
+  return RGC_OK;
+}
+
+int rgc_ndt_linearize(rgc_ctx* c, const double T[16], double H[36], double b[6], double* cost) {
+  if (!c || !T) return RGC_ERR_INVALID;
+  if (!pose12_finite(T)) return fail(c, RGC_ERR_NONFINITE, "rgc_ndt_linearize: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  return ndt_do_linearize(c, T, H, b, cost);
+}
+
+int rgc_ndt_compute_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c || !T || !cost) return RGC_ERR_INVALID;
+  if (!pose12_finite(T)) return fail(c, RGC_ERR_NONFINITE, "rgc_ndt_compute_error: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  return ndt_do_error(c, T, cost);
+}
+
+int rgc_ndt_num_correspondences(rgc_ctx* c, int* n) {
+  if (!c || !n) return RGC_ERR_INVALID;
+  if (!c->ndt_corr_valid) return fail(c, RGC_ERR_INVALID, "rgc_ndt_num_correspondences needs a preceding rgc_ndt_linearize");
+  *n = c->ndt_terms;
+  return RGC_OK;
+}
+
+// computeTransformation (lm_solve) over the two calls above
+int rgc_ndt_align(rgc_ctx* c, const float guess[16], float final_T[16], double final_H[36], int* iterations, int* converged, int* lm_failed) {
+  if (!c || !guess) return RGC_ERR_INVALID;
+  if (!pose12_finite(guess)) return fail(c, RGC_ERR_NONFINITE, "rgc_ndt_align: the guess is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = ndt_need_inputs(c);  // create_voxelmaps() (include/fast_gicp/ndt/impl/ndt_cuda_impl.hpp:77)
+  if (rc) return rc;
+  static const LmSystem sys = {ndt_do_linearize, ndt_do_error, nullptr, nullptr};
+  LmResult r;
+  if ((rc = lm_solve(c, sys, guess, &r))) return rc;
+  r.write(final_T, final_H, iterations, converged, lm_failed);
+  return RGC_OK;
+}
+
+// the records of map `which` on the host (m of them); cells: their grid cells
+static int ndt_fetch_voxels(rgc_ctx* c, int which, int cap, std::vector<double>& rec, std::vector<int>& cell, int* count) {
+  if (which != 0 && which != 1) return fail(c, RGC_ERR_INVALID, "which: 0 target, 1 source");
+  if (cap < 0) return fail(c, RGC_ERR_INVALID, "negative capacity");
+  if (!c->ndt_set[which]) return fail(c, RGC_ERR_NO_INPUT, "NDT %s not set", which ? "source" : "target");
+  int rc = ndt_build(c, which);
+  if (rc) return rc;
+  const Cloud& cl = c->ndt_cl[which];
+  *count = cl.nvox;
+  const int m = cl.nvox < cap ? cl.nvox : cap;
+  rec.resize((size_t)m * rgck::kNdtRec);
+  cell.resize((size_t)m);
+  if (m <= 0) return RGC_OK;
+  HIPCHK(c, hipMemcpyAsync(rec.data(), cl.vox.p, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(cell.data(), cl.vox_cell.p, sizeof(int) * cell.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RGC_OK;
+}
+
+static void ndt_cov9(const double* r6, double* C) {
+  C[0] = r6[0]; C[1] = r6[1]; C[2] = r6[2];
+  C[3] = r6[1]; C[4] = r6[3]; C[5] = r6[4];
+  C[6] = r6[2]; C[7] = r6[4]; C[8] = r6[5];
+}
+
+int rgc_ndt_get_voxels(rgc_ctx* c, int which, int cap, int* coords, int* num, double* mean, double* cov9, int* count) {
+  if (!c || !count) return RGC_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<double> rec;
+  std::vector<int> cell;
+  int total = 0;
+  const int rc = ndt_fetch_voxels(c, which, cap, rec, cell, &total);
+  if (rc) return rc;
+  *count = total;
+  const rgck::Grid& g = c->ndt_cl[which].grid;
+  for (size_t v = 0; v < cell.size(); v++) {
+    const double* r = &rec[v * rgck::kNdtRec];
+    const int ci = cell[v];
+    if (coords) rgck::cell_coords(g, ci, coords + v * 3);
+    if (num) num[v] = (int)r[9];
+    if (mean) { mean[v * 3] = r[0]; mean[v * 3 + 1] = r[1]; mean[v * 3 + 2] = r[2]; }
+    if (cov9) ndt_cov9(r + 3, cov9 + v * 9);
+  }
+  return RGC_OK;
+}
+
+int rgc_ndt_get_raw_covariances(rgc_ctx* c, int which, int cap, double* cov9, int* count) {
+  if (!c || !count) return RGC_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<double> rec;
+  std::vector<int> cell;
+  int total = 0;
+  const int rc = ndt_fetch_voxels(c, which, cap, rec, cell, &total);
+  if (rc) return rc;
+  *count = total;
+  if (cov9)
+    for (size_t v = 0; v < cell.size(); v++) ndt_cov9(&rec[v * rgck::kNdtRec] + 16, cov9 + v * 9);
+  return RGC_OK;
+}
+
+// ---- FastGICP: GICP on exact nearest-neighbour correspondences (include/fast_gicp/gicp/impl/fast_gicp_impl.hpp:103-237) on the context's own clouds ----
+int rgc_gicp_set_max_correspondence_distance(rgc_ctx* c, double d_max) {
+  if (!c) return RGC_ERR_INVALID;
+  if (std::isnan(d_max) || d_max < 0.0) return fail(c, RGC_ERR_INVALID, "rgc_gicp_set_max_correspondence_distance: the distance must be >= 0");
+  c->gicp_dmax = d_max;
+  return RGC_OK;
+}
+
+int rgc_gicp_get_max_correspondence_distance(const rgc_ctx* c, double* d_max) {
+  if (!c || !d_max) return RGC_ERR_INVALID;
+  *d_max = c->gicp_dmax;
+  return RGC_OK;
+}
+
+// a pose the GICP calls accept: finite in fp64 and after the cast to fp32 the search transforms with (fast_gicp_impl.hpp:119)
+static bool gicp_pose_ok(const double T[16]) {
+  for (int i = 0; i < 12; i++)
+    if (!std::isfinite(T[i]) || !std::isfinite((float)T[i])) return false;
+  return true;
+}
+
+// both clouds there, no solve in flight, the speculative grids' guards read, a lazy target completed, the source's preparation joined
+static int gicp_need_inputs(rgc_ctx* c) {
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  if (!c->src.ready || !c->tgt.ready) return fail(c, RGC_ERR_INVALID, "rgc_gicp_*: source and target must be set first");
+  int rc = need_inputs(c);
+  if (rc == RGC_ERR_NO_INPUT) return fail(c, RGC_ERR_INVALID, "rgc_gicp_*: source and target must be set first");
+  if (rc) return rc;
+  if (!c->gicp_h_out) HIPCHK(c, hipHostMalloc((void**)&c->gicp_h_out, sizeof(double) * 32, hipHostMallocDefault));
+  return ensure(c, c->gicp_out, sizeof(double) * 32);
+}
+
+static rgck::GicpCov gicp_cov_of(const Cloud& cl) {
+  if (cl.general) return rgck::GicpCov{(const double*)cl.c6.p, nullptr, nullptr, nullptr};
+  return rgck::GicpCov{nullptr, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p};
+}
+
+// update_correspondences + linearize (fast_gicp_impl.hpp:115-211); the inputs have been checked (gicp_need_inputs)
+static int gicp_do_linearize(rgc_ctx* c, const double T[16], double* H, double* b, double* cost) {
+  const Cloud& sc = c->src;
+  const Cloud& tg = c->tgt;
+  const int n = sc.n, nb = rgck::gicp_blocks(n);
+  int rc;
+  c->gicp_valid = false;
+  if ((rc = ensure(c, c->gicp_corr, sizeof(int) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_key, sizeof(float) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_M, sizeof(double) * 6 * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_partials, sizeof(double) * (rgck::kAccum + 1) * (size_t)nb))) return rc;
+  float T32[16];
+  for (int i = 0; i < 16; i++) T32[i] = (float)T[i];  // trans.cast<float>(), :119
+  const int want = (H && b) ? 1 : 0;
+  rgck::gicp_correspond(c->stream, (const float4*)sc.P.p, n, posef_from(T32), (const float4*)tg.P.p, (const int*)tg.start.p, tg.grid,
+                        c->gicp_dmax * c->gicp_dmax, (int*)c->gicp_corr.p, (float*)c->gicp_key.p);
+  rgck::gicp_terms(c->stream, (const float4*)sc.P.p, n, (const float4*)tg.P.p, tg.n, (const int*)c->gicp_corr.p, gicp_cov_of(sc), gicp_cov_of(tg), pose_from(T),
+                   want, (double*)c->gicp_M.p, (double*)c->gicp_partials.p, (double*)c->gicp_out.p);
+  HIPCHK(c, hipMemcpyAsync(c->gicp_h_out, c->gicp_out.p, sizeof(double) * (rgck::kAccum + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  const double* o = c->gicp_h_out;
+  c->gicp_valid = true;
+  c->gicp_n = n;
+  c->gicp_kept = (int)o[28];
+  if (want) unpack_system(o, H, b);
+  if (cost) *cost = o[27];
+  return RGC_OK;
+}
+
+// compute_error (fast_gicp_impl.hpp:214-237) over the frozen pairs and matrices
+static int gicp_do_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c->gicp_valid || c->gicp_n != c->src.n) return fail(c, RGC_ERR_INVALID, "rgc_gicp_compute_error needs a preceding rgc_gicp_linearize on the present clouds");
+  const Cloud& sc = c->src;
+  const Cloud& tg = c->tgt;
+  rgck::gicp_error(c->stream, (const float4*)sc.P.p, sc.n, (const float4*)tg.P.p, tg.n, (const int*)c->gicp_corr.p, (const double*)c->gicp_M.p, pose_from(T),
+                   (double*)c->gicp_partials.p, (double*)c->gicp_out.p);
+  HIPCHK(c, hipMemcpyAsync(c->gicp_h_out, c->gicp_out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  *cost = c->gicp_h_out[0];
+  return RGC_OK;
+}
+
+int rgc_gicp_linearize(rgc_ctx* c, const double T[16], double H[36], double b[6], double* cost) {
+  if (!c || !T) return RGC_ERR_INVALID;
+  if (!gicp_pose_ok(T)) return fail(c, RGC_ERR_INVALID, "rgc_gicp_linearize: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = gicp_need_inputs(c);
+  return rc ? rc : gicp_do_linearize(c, T, H, b, cost);
+}
+
+int rgc_gicp_compute_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c || !T || !cost) return RGC_ERR_INVALID;
+  if (!gicp_pose_ok(T)) return fail(c, RGC_ERR_INVALID, "rgc_gicp_compute_error: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = gicp_need_inputs(c);
+  return rc ? rc : gicp_do_error(c, T, cost);
+}
+
+int rgc_gicp_num_correspondences(rgc_ctx* c, int* n) {
+  if (!c || !n) return RGC_ERR_INVALID;
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  if (!c->gicp_valid) return fail(c, RGC_ERR_INVALID, "rgc_gicp_num_correspondences needs a preceding rgc_gicp_linearize on the present clouds");
+  *n = c->gicp_kept;
+  return RGC_OK;
+}
+
+int rgc_gicp_get_correspondences(rgc_ctx* c, int* idx, float* sq_dist) {
+  if (!c) return RGC_ERR_INVALID;
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  if (!c->gicp_valid || !c->src.ready || !c->tgt.ready || c->gicp_n != c->src.n)
+    return fail(c, RGC_ERR_INVALID, "rgc_gicp_get_correspondences needs a preceding rgc_gicp_linearize on the present clouds");
+  if (!idx && !sq_dist) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int n = c->src.n;
+  int rc = check_target_owner(c);
+  if (rc) return rc;
+  if ((rc = ensure(c, c->scratch, (sizeof(int) + sizeof(float)) * (size_t)n))) return rc;
+  int* d_idx = (int*)c->scratch.p;
+  float* d_sq = (float*)(d_idx + n);
+  HIPCHK(c, hipMemsetAsync(d_idx, 0xff, sizeof(int) * (size_t)n, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_sq, 0, sizeof(float) * (size_t)n, c->stream));
+  rgck::gicp_export(c->stream, (const float4*)c->src.P.p, n, (const float4*)c->tgt.P.p, c->tgt.n, (const int*)c->gicp_corr.p, (const float*)c->gicp_key.p, d_idx, d_sq);
+  if (idx) HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  if (sq_dist) HIPCHK(c, hipMemcpyAsync(sq_dist, d_sq, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+
+// computeTransformation (lm_solve) over the two calls above; the fitness score of the final pose as rgc_align gives it
+int rgc_gicp_align(rgc_ctx* c, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged, int* lm_failed) {
+  if (!c || !guess) return RGC_ERR_INVALID;
+  if (!pose12_finite(guess)) return fail(c, RGC_ERR_INVALID, "rgc_gicp_align: the guess is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = gicp_need_inputs(c);
+  if (rc) return rc;
+  static const LmSystem sys = {gicp_do_linearize, gicp_do_error, nullptr, gicp_pose_ok};
+  LmResult r;
+  if ((rc = lm_solve(c, sys, guess, &r))) return rc;
+  r.write(final_T, final_H, iterations, converged, lm_failed);
+  if (fitness) {
+    if (!pose12_finite(r.fin)) *fitness = (double)NAN;
+    else if ((rc = do_fitness(c, r.fin, fitness))) return rc;
+  }
+  return RGC_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,712 @@
+// rgc_api_pre.hip -- host side of the stages around the registration: B2 de-skew, B3 leaf filter, B9 re-framing (rgc_deskew,
+// rgc_transform_cloud, rgc_set_target_reframed, rgc_align_end_reframe, rgc_voxelgrid*) and the A1-A8 front end (rgc_frontend*).
+// The kernels are in rgc_pre.hip and rgc_frontend.hip.
+#include "rgc_ctx.h"
+
+using namespace rgcapi;
+
+// ---- B2 / B3 / B9: the stages either side of the operator in the odometer's frame body ----
+int rgcapi::stage_in(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, const float** d_in) {
+  if (n > (1 << 27)) return fail(c, RGC_ERR_INVALID, "cloud has %d points, the limit is 2^27", n);  // (every entry point that takes a cloud: one limit)
+  if (on_device) {
+    if (n > 0) { const int rk = check_device_range(c, p, (size_t)n * stride_bytes - (stride_bytes - 12), "input cloud"); if (rk) return rk; }
+    *d_in = p;
+    return RGC_OK;
+  }
+  const size_t bytes = (size_t)n * stride_bytes;
+  int rc = ensure(c, c->pre_in, bytes);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->pre_in.p, p, bytes, hipMemcpyHostToDevice, c->stream));
+  *d_in = (const float*)c->pre_in.p;
+  return RGC_OK;
+}
+
+extern "C" {
+
+int rgc_deskew(rgc_ctx* c, float* xyzi, int n, int stride_bytes, const double q[4], const double t[3], int on_device) {
+  if (!c || !xyzi || !q || !t || n < 0) return RGC_ERR_INVALID;
+  if (stride_bytes < 16 || (stride_bytes & 3) || stride_bytes > 4096) return fail(c, RGC_ERR_INVALID, "de-skew needs x,y,z,intensity: stride_bytes >= 16");
+  if (n == 0) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const float* d_in;
+  int rc = stage_in(c, xyzi, n, stride_bytes, on_device, &d_in);
+  if (rc) return rc;
+  // q_last_curr.inverse() = conjugate / squaredNorm (Eigen), RGC_odometer.cpp:1444
+  const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+  if (!(n2 > 0)) return fail(c, RGC_ERR_INVALID, "zero quaternion");
+  rgck::Quat qi{-q[0] / n2, -q[1] / n2, -q[2] / n2, q[3] / n2};
+  if (c->main_has_target_prep && map_prep_finished(c)) c->main_has_target_prep = false;  // it has drained
+  rgck::deskew(c->stream, (float*)d_in, stride_bytes / 4, n, qi, t);
+  if (!on_device) HIPCHK(c, hipMemcpyAsync(xyzi, d_in, (size_t)n * stride_bytes, hipMemcpyDeviceToHost, c->stream));
+  // device memory: in place and stream-ordered, whatever reads the sweep next on the main stream is enqueued behind it -- unless a map
+  // preparation is still pending there: rgc_set_source_device orders the scan's stream after a mark recorded BEFORE that preparation
+  // (see prepare_cloud), which this kernel would then lie behind
+  if (!on_device || c->main_has_target_prep) HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+
+int rgc_transform_cloud(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, const double q[4], const double t[3], float* out_xyzi,
+                        int on_device) {
+  if (!c || !xyzi || !q || !t || !out_xyzi || n < 0) return RGC_ERR_INVALID;
+  if (!stride_ok(stride_bytes)) return fail(c, RGC_ERR_INVALID, "bad stride");
+  if (n == 0) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const float* d_in;
+  int rc = stage_in(c, xyzi, n, stride_bytes, on_device, &d_in);
+  if (rc) return rc;
+  float* d_out = out_xyzi;
+  if (!on_device) {
+    if ((rc = ensure(c, c->pre_out, sizeof(float) * 4 * (size_t)n))) return rc;
+    d_out = (float*)c->pre_out.p;
+  }
+  rgck::transform_q(c->stream, d_in, stride_bytes / 4, n, rgck::Quat{q[0], q[1], q[2], q[3]}, t, d_out, 4);
+  if (!on_device) HIPCHK(c, hipMemcpyAsync(out_xyzi, d_out, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  // device memory: stream-ordered like rgc_deskew; the one exception is the same as there (a pending map preparation, see rgc_deskew)
+  if (!on_device || c->main_has_target_prep) HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+
+// B9 followed by setInputTarget, in one call and without a host round trip: the sub-map (device memory, fixed between calls) re-expressed
+// by (q, t) into d_scratch and handed to the registration as its new target (RGC_odometer.cpp:1248-1256, 998, 1007).  The output's
+// bounding box follows from the input's -- measured once per input buffer (whole 1 m cells, k_bbox) -- and the transform: its eight
+// corners through q * p + t in fp64, a millimetre added for the fp32 rounding of the stored points.  rgc_set_target_device takes its grid
+// from that box: no bounding-box kernel, no read-back, and no speculative-grid miss when the re-framed map's box swings with the yaw.
+// the argument checks of rgc_set_target_reframed (also made by rgc_align_end_reframe BEFORE it consumes the solve)
+static int reframe_args_ok(rgc_ctx* c, const float* d_xyzi, int n, int stride_bytes, const float* d_scratch) {
+  if (!d_xyzi || !d_scratch || n <= 0) return fail(c, RGC_ERR_INVALID, "rgc_set_target_reframed: null buffer or no points");
+  if (!stride_ok(stride_bytes)) return fail(c, RGC_ERR_INVALID, "bad stride");
+  if (n > (1 << 27)) return fail(c, RGC_ERR_INVALID, "cloud has %d points, the limit is 2^27 (32-bit byte offsets into the sorted array)", n);
+  if (n < c->prm.k_correspondences) return fail(c, RGC_ERR_TOO_FEW_POINTS, "target cloud has %d points, need >= k = %d", n, c->prm.k_correspondences);
+  // the re-framed cloud is WRITTEN to d_scratch while d_xyzi is read: they must not overlap (and one buffer has one bounding-box hint)
+  const char* a0 = (const char*)d_xyzi; const char* a1 = a0 + (size_t)n * stride_bytes;
+  const char* b0 = (const char*)d_scratch; const char* b1 = b0 + (size_t)n * 16;
+  if (a0 < b1 && b0 < a1) return fail(c, RGC_ERR_INVALID, "rgc_set_target_reframed: d_scratch overlaps d_xyzi");
+  { int rk = check_device_range(c, d_xyzi, (size_t)n * stride_bytes - (stride_bytes - 12), "rgc_set_target_reframed: d_xyzi"); if (rk) return rk; }
+  { int rk = check_device_range(c, d_scratch, (size_t)n * 16, "rgc_set_target_reframed: d_scratch"); if (rk) return rk; }
+  return RGC_OK;
+}
+
+int rgc_set_target_reframed(rgc_ctx* c, const float* d_xyzi, int n, int stride_bytes, const double q[4], const double t[3], float* d_scratch) {
+  if (!c || !q || !t) return RGC_ERR_INVALID;
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  {
+    const int rc = reframe_args_ok(c, d_xyzi, n, stride_bytes, d_scratch);
+    if (rc) return rc;
+  }
+  // a pose that is not a pose -- the NaN a diverged solve hands on through rgc_align_end_reframe, a zero quaternion -- has no box to derive a
+  // grid from (the float -> int conversions behind it are undefined: tests/fuzz/fuzz_api.py saw a 40-petabyte allocation request)
+  {
+    const double qq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    if (!(std::isfinite(qq) && qq > 1.0e-12 && qq < 1.0e12 && std::isfinite(t[0]) && std::isfinite(t[1]) && std::isfinite(t[2]) &&
+          std::fabs(t[0]) <= 1.0e8 && std::fabs(t[1]) <= 1.0e8 && std::fabs(t[2]) <= 1.0e8))
+      return fail(c, RGC_ERR_NONFINITE, "rgc_set_target_reframed: the pose (q, t) is not finite");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const float* xyzi = d_xyzi;
+  const float* d_in = d_xyzi;
+  float* out_xyzi = d_scratch;
+  const int on_device = 1;
+  if (on_device && c->spec_on) {
+    // the output's bounding box from the input's: measured once per input buffer (whole cells of 1 m, k_bbox), then the eight
+    // corners through q * p + t in fp64, a millimetre added for the fp32 rounding of the stored points
+    const rgc_ctx::BoxHint* hin = find_hint(c, xyzi, n);
+    if (!hin) {
+      int* dsm = c->d_small + 32;
+      int* hsm = c->h_small + 32;
+      const int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
+      memcpy(hsm, init, sizeof(init));
+      HIPCHK(c, hipMemcpyAsync(dsm, hsm, sizeof(init), hipMemcpyHostToDevice, c->stream));
+      rgck::bbox(c->stream, d_in, stride_bytes / 4, n, 1.0, dsm, dsm + 6);
+      HIPCHK(c, hipMemcpyAsync(hsm, dsm, 7 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      if (!hsm[6]) {
+        const double lo[3] = {hsm[0] + 0.5, hsm[1] + 0.5, hsm[2] + 0.5}, hi[3] = {hsm[3] + 1.5, hsm[4] + 1.5, hsm[5] + 1.5};
+        put_hint(c, xyzi, n, lo, hi);
+        hin = find_hint(c, xyzi, n);
+      }
+    }
+    if (hin) {
+      const double x = q[0], y = q[1], z = q[2], w = q[3];
+      const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z),
+                           2 * (y * z - x * w), 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+      double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+      for (int k = 0; k < 8; k++) {
+        const double p[3] = {(k & 1) ? hin->hi[0] : hin->lo[0], (k & 2) ? hin->hi[1] : hin->lo[1], (k & 4) ? hin->hi[2] : hin->lo[2]};
+        for (int a = 0; a < 3; a++) {
+          const double v = R[3 * a] * p[0] + R[3 * a + 1] * p[1] + R[3 * a + 2] * p[2] + t[a];
+          lo[a] = std::min(lo[a], v - 1.0e-3);
+          hi[a] = std::max(hi[a], v + 1.0e-3);
+        }
+      }
+      // how large the re-framed box can get as the vehicle turns: under any yaw its x / y extents stay within the horizontal diagonal of
+      // the map's own box; pitch and roll of a ground vehicle tilt it by a few cells.  The cell arrays are sized for that ONCE.
+      const double dxy = std::hypot(hin->hi[0] - hin->lo[0], hin->hi[1] - hin->lo[1]);
+      put_hint(c, out_xyzi, n, lo, hi, dxy, (hi[2] - lo[2]) + 0.08 * dxy);
+    }
+  }
+  // (the re-framing itself is left to the preparation: its counting pass writes d_scratch on the way, prepare_cloud)
+  const rgck::Reframe rf{d_in, stride_bytes / 4, rgck::Quat{q[0], q[1], q[2], q[3]}, {t[0], t[1], t[2]}};
+  HIPCHK(c, hipGetLastError());
+  return set_cloud(c, c->tgt, true, d_scratch, n, 16, true, &rf);
+}
+
+int rgc_align_end_reframe(rgc_ctx* c, rgc_ctx* next, double Tw[16], const float* d_map, int n, int stride_bytes, float* d_scratch,
+                          float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged, int* lm_failed) {
+  if (!c || !next || !Tw) return RGC_ERR_INVALID;
+  // Everything that could make the second half (the next frame's target) fail for the caller's arguments is checked BEFORE the solve is
+  // consumed: a non-OK return then means "nothing happened" (the solve is still pending, Tw untouched) -- or, past this point, a HIP /
+  // allocation failure inside the preparation, with the solve's outputs and Tw already valid (the message says which call failed).
+  if (next != c) {
+    if (!ctx_alive(next)) return fail(c, RGC_ERR_INVALID, "rgc_align_end_reframe: the next context is not alive");
+    if (solve_in_flight(next)) return fail(c, RGC_ERR_INVALID, "rgc_align_end_reframe: a solve is in flight on the next context");
+  }
+  if (!c->pend.active && !c->gen_res.on) return fail(c, RGC_ERR_INVALID, "rgc_align_end without rgc_align_begin");
+  {
+    const int rc0 = reframe_args_ok(next, d_map, n, stride_bytes, d_scratch);
+    if (rc0) { if (next != c) fail(c, rc0, "rgc_align_end_reframe: %s", next->err); return rc0; }
+  }
+  // world_T * T in fp64, rows in ascending k (the composition of :1201-1203 on matrices), and world -> body of the new pose: R^T and
+  // -R^T t; the unit quaternion of R^T by Shepperd's branches (:1250-1255)
+  auto compose = [](const double* Tw_in, const float* T, double* W, double* q, double* t) {
+    for (int a = 0; a < 4; a++)
+      for (int b = 0; b < 4; b++) {
+        double v = 0.0;
+        for (int k = 0; k < 4; k++) v += Tw_in[a * 4 + k] * (double)T[k * 4 + b];
+        W[a * 4 + b] = v;
+      }
+    const double Rt[3][3] = {{W[0], W[4], W[8]}, {W[1], W[5], W[9]}, {W[2], W[6], W[10]}};
+    const double tr = Rt[0][0] + Rt[1][1] + Rt[2][2];
+    if (tr > 0) {
+      const double s4 = 2.0 * std::sqrt(tr + 1.0);
+      q[0] = (Rt[2][1] - Rt[1][2]) / s4; q[1] = (Rt[0][2] - Rt[2][0]) / s4; q[2] = (Rt[1][0] - Rt[0][1]) / s4; q[3] = 0.25 * s4;
+    } else {
+      const int i = (Rt[0][0] >= Rt[1][1] && Rt[0][0] >= Rt[2][2]) ? 0 : (Rt[1][1] >= Rt[2][2] ? 1 : 2);
+      const int j = (i + 1) % 3, k = (i + 2) % 3;
+      const double s4 = 2.0 * std::sqrt(1.0 + Rt[i][i] - Rt[j][j] - Rt[k][k]);
+      q[3] = (Rt[k][j] - Rt[j][k]) / s4;
+      q[i] = 0.25 * s4;
+      q[j] = (Rt[j][i] + Rt[i][j]) / s4;
+      q[k] = (Rt[k][i] + Rt[i][k]) / s4;
+    }
+    const double nrm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    for (int a = 0; a < 4; a++) q[a] /= nrm;
+    const double tx = W[3], ty = W[7], tz = W[11];
+    t[0] = -(Rt[0][0] * tx + Rt[0][1] * ty + Rt[0][2] * tz);
+    t[1] = -(Rt[1][0] * tx + Rt[1][1] * ty + Rt[1][2] * tz);
+    t[2] = -(Rt[2][0] * tx + Rt[2][1] * ty + Rt[2][2] * tz);
+  };
+  // The POSE of a solve whose score is chained to it arrives before the score does (LmEarly: the deciding launch posts it, then scores it,
+  // ~25 us at the headline size).  On two contexts taking turns the next frame's target needs nothing else: it is enqueued on `next` while
+  // this context's last launch still computes the score, whose arrival the call then waits for like rgc_align_end.  Not on one context
+  // (the score reads the buffers the next preparation writes), not when a guard tripped or a lazy target missed (the solve is repeated).
+  float Te[16];
+  double We[16], qe[4], te[3];
+  bool early_done = false;
+  int rc_next = RGC_OK;
+  if (next != c && RGC_EARLY_POSE && c->post_on && c->d_post && c->d_early && c->pend.active && c->pend.want_fitness && !c->lm_host && !c->gen_res.on) {
+    volatile int* eg = &c->h_early->gen;
+    volatile int* fg = &c->h_post->gen;
+    bool early = false;
+    for (unsigned spin = 0;; spin++) {
+      if (*eg == c->lm_seq) { early = true; break; }
+      if (*fg == c->lm_seq) break;
+      if (spin & 31u) continue;
+      const hipError_t qy = hipEventQuery(c->lm_tail);
+      if (qy == hipSuccess) { early = *eg == c->lm_seq; break; }
+      if (qy != hipErrorNotReady) break;   // (rgc_align_end below reports it)
+      (void)hipGetLastError();
+    }
+    if (early) {
+      std::atomic_thread_fence(std::memory_order_acquire);
+      rgck::LmEarly E;
+      memcpy(&E, c->h_early, sizeof(E));
+      if (E.pad == 0 && E.pad2 == 0) {
+        for (int i = 0; i < 16; i++) Te[i] = (float)E.x0[i];  // final_transformation_ = x0.cast<float>(), :77
+        compose(Tw, Te, We, qe, te);
+        rc_next = rgc_set_target_reframed(next, d_map, n, stride_bytes, qe, te, d_scratch);
+        if (rc_next) fail(c, rc_next, "rgc_align_end_reframe: %s", next->err);
+        early_done = true;
+      }
+    }
+  }
+  float T[16];
+  char next_err[sizeof(c->err)];
+  if (rc_next) memcpy(next_err, c->err, sizeof(next_err));
+  int rc = rgc_align_end(c, T, final_H, fitness, iterations, converged, lm_failed);
+  if (rc) return rc;
+  if (final_T) memcpy(final_T, T, sizeof(T));
+  if (early_done && memcmp(T, Te, sizeof(T)) == 0) {  // (always, unless the solve had to be repeated behind the early pose's back)
+    memcpy(Tw, We, sizeof(We));
+    if (rc_next) memcpy(c->err, next_err, sizeof(next_err));
+    return rc_next;
+  }
+  double W[16], q[4], t[3];
+  compose(Tw, T, W, q, t);
+  memcpy(Tw, W, sizeof(W));
+  rc = rgc_set_target_reframed(next, d_map, n, stride_bytes, q, t, d_scratch);
+  if (rc && next != c) fail(c, rc, "rgc_align_end_reframe: %s", next->err);
+  return rc;
+}
+
+}  // extern "C"
+
+// The rows chain of the leaf filter on box g (rgc_pre.hip); one read-back: *flags (bits as rgck::vg_rows documents) and *n_out.
+// h_result (nullable): the chain is only ENQUEUED -- its three result ints go to h_result (pinned), c->vg_done is recorded behind the
+// copy, and the caller picks them up later (rgc_voxelgrid_begin / _end); flags / n_out are not written then.
+static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, float inv, const rgck::LeafGrid& g, int edge, bool dense, float* d_out,
+                          int* flags, int* n_out, rgc_vg_route* rt, int* h_result = nullptr) {
+  hipStream_t s = c->stream;
+  int* dsm = c->d_small + 24;
+  int* hsm = c->h_small + 24;
+  Cloud& cl = c->aux;
+  int rc;
+  // the sort's buckets: leaves for a dense cloud, whole grid rows for a sweep, and for a LARGE cloud in a box too big for leaf buckets
+  // segments of a row, as many as keep the table near 4 n entries (the ranking pass is quadratic in a bucket's population: a ground-level
+  // row of a 1.3 M-point keyframe store holds thousands of points)
+  int seg_shift = dense ? 0 : 31;
+  if (!dense) {
+    const double rows = (double)g.div[1] * (double)g.div[2], nseg_max = 4.0 * (double)n / rows;
+    if (nseg_max >= 2.0) {
+      seg_shift = 3;
+      while (seg_shift < 30 && (double)(((long long)g.div[0] + (1ll << seg_shift) - 1) >> seg_shift) > nseg_max) seg_shift++;
+    }
+  }
+  const size_t nr1 = (size_t)g.div[1] * (size_t)g.div[2] * (size_t)rgck::vg_segments(g, seg_shift) + 1;   // buckets
+  if ((rc = ensure(c, cl.cell_of, sizeof(int) * n))) return rc;                                                    // row of every point
+  if ((rc = ensure(c, cl.slot_of, sizeof(int) * n))) return rc;                                                    // leaf x of every point
+  if ((rc = ensure(c, c->vg_pos, sizeof(int) * n))) return rc;                                                     // arrival slot, then output number
+  if ((rc = ensure(c, c->vg_order, sizeof(int) * n))) return rc;
+  if ((rc = ensure(c, c->vg_tmp, sizeof(long long) * n))) return rc;
+  if ((rc = ensure(c, c->vg_leaf, sizeof(long long) * n))) return rc;
+  if ((rc = ensure(c, cl.cnt, sizeof(int) * nr1))) return rc;
+  if ((rc = ensure(c, cl.start, sizeof(int) * nr1))) return rc;
+  const size_t row_bs = sizeof(long long) * (nr1 / 2048 + 2);
+  if ((rc = ensure(c, cl.block_sums, row_bs + sizeof(int) * ((size_t)n / 2048 + 2)))) return rc;
+  if (cl.cnt.p != cl.cnt_seen) { cl.cnt_clean = 0; cl.cnt_seen = cl.cnt.p; }
+  if (cl.cnt_clean < nr1) {  // afterwards the scan leaves the counters it consumed at zero: no fill per call
+    const size_t fill = std::min(cl.cnt.cap, (sizeof(int) * nr1 + 255) & ~(size_t)255);
+    HIPCHK(c, hipMemsetAsync(cl.cnt.p, 0, fill, s));
+  }
+  cl.cnt_clean = std::max(cl.cnt_clean, nr1);  // (what lies beyond this call's rows was not touched: the scan's and the map's filter take turns)
+  if (!c->vg_flags_clean) HIPCHK(c, hipMemsetAsync(dsm + 6, 0, sizeof(int), s));
+  c->vg_flags_clean = false;
+  const bool packed = rgck::vg_rows(s, d_in, stride_f, n, inv, g, edge, seg_shift, (int*)cl.cell_of.p, (int*)cl.slot_of.p, (int*)c->vg_pos.p, (int*)cl.cnt.p,
+                                    (int*)cl.start.p, cl.block_sums.p, (unsigned long long*)c->vg_tmp.p, (int*)c->vg_order.p, (unsigned long long*)c->vg_leaf.p,
+                                    (int*)((char*)cl.block_sums.p + row_bs), d_out, dsm + 5);
+  rt->chain = 1; rt->leaf_buckets = dense ? 1 : 0; rt->seg_shift = seg_shift; rt->nseg = rgck::vg_segments(g, seg_shift); rt->packed = packed ? 1 : 0;
+  rt->edge = edge; rt->flags = 0;
+  for (int a = 0; a < 3; a++) { rt->minb[a] = g.minb[a]; rt->div[a] = g.div[a]; }
+  if (h_result) {  // (the finished chain leaves the flag word zeroed: the next chain on this stream finds it so)
+    HIPCHK(c, hipMemcpyAsync(h_result, dsm + 5, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->vg_done, s));
+    c->vg_flags_clean = true;
+    return RGC_OK;
+  }
+  HIPCHK(c, hipMemcpyAsync(hsm + 5, dsm + 5, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  c->vg_flags_clean = true;
+  *flags = hsm[5];
+  *n_out = hsm[7];
+  rt->flags = hsm[5];
+  return RGC_OK;
+}
+static bool vg_rows_fit(const rgck::LeafGrid& g, int n) {  // sparse enough for the sort over rows (else: over the leaves)
+  const double ncell = (double)g.div[0] * (double)g.div[1] * (double)g.div[2], nrows = (double)g.div[1] * (double)g.div[2];
+  return ncell <= 2147483647.0 && ncell > 64.0 * (double)n && nrows <= 64.0e6;
+}
+
+int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt) {
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const float* d_in;
+  int rc = stage_in(c, xyzi, n, stride_bytes, on_device, &d_in);
+  if (rc) return rc;
+  const int stride_f = stride_bytes / 4;
+  const float inv = 1.0f / leaf;  // inverse_leaf_size_
+  int* dsm = c->d_small + 24;
+  int* hsm = c->h_small + 24;
+  float* d_out = out_xyzi;
+  if (!on_device) {
+    if ((rc = ensure(c, c->pre_out, sizeof(float) * 4 * (size_t)n))) return rc;
+    d_out = (float*)c->pre_out.p;
+  }
+  // leaves added on every side of a measured box when the next cloud of this leaf size is filtered on it: 32 for a sweep (its rows are
+  // what is counted and scanned), 8 for a dense cloud (its leaves are: a wider box is a longer scan)
+  constexpr int kPadSparse = 32, kPadDense = 8;
+  auto padded = [](const rgck::LeafGrid& g, int pad) {
+    rgck::LeafGrid p = g;
+    for (int a = 0; a < 3; a++) { p.minb[a] -= pad; p.div[a] += 2 * pad; }
+    return p;
+  };
+  rgc_ctx::VgBox* box = nullptr;
+  for (auto& b : c->vg_box) if (b.leaf == leaf) box = &b;
+  bool done = false;
+  rt.kept_box = !box ? 0 : box->valid ? 2 : 3;
+  if (box && box->valid) {
+    // the box of an earlier cloud: no bounding-box pass, no read-back before the filter (the frames of a sequence span the same volume)
+    const rgck::LeafGrid ps = padded(box->g, kPadSparse), pd = padded(box->g, kPadDense);
+    const bool sparse = vg_rows_fit(ps, n);
+    const double dcell = (double)pd.div[0] * (double)pd.div[1] * (double)pd.div[2];
+    if (sparse || dcell <= (double)c->prm.max_cells) {
+      int flags = 0, no = 0;
+      rt.kept_box = 1;
+      rt.path = RGC_VG_PATH_KEPT;
+      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, sparse ? ps : pd, (sparse ? kPadSparse : kPadDense) / 2, !sparse, d_out, &flags, &no, &rt))) return rc;
+      rt.kept_flags = flags;
+      if (flags & 1) return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)");
+      if (flags & 6) { box->valid = false; rt.box_invalidated = 1; }  // outside: measure and repeat now; near a face: measure at the next call
+      if (!(flags & 2)) { *n_out = no; done = true; hint_from_leaf_grid(c, out_xyzi, no, sparse ? ps : pd, leaf); }
+    }
+  }
+  if (!done) {
+    rt.repeated = rt.path == RGC_VG_PATH_KEPT ? 1 : 0;
+    rt.path = RGC_VG_PATH_MEASURED;
+    rt.chain = rt.leaf_buckets = rt.seg_shift = rt.nseg = rt.packed = rt.edge = rt.flags = 0;  // (of the chain on the kept box)
+    int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
+    memcpy(hsm, init, sizeof(init));
+    c->vg_flags_clean = false;
+    HIPCHK(c, hipMemcpyAsync(dsm, hsm, sizeof(init), hipMemcpyHostToDevice, s));
+    rgck::vg_bbox(s, d_in, stride_f, n, inv, dsm, dsm + 6);
+    HIPCHK(c, hipMemcpyAsync(hsm, dsm, 7 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (hsm[6]) return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)");
+    c->vg_flags_clean = true;
+    rgck::LeafGrid g{};
+    double ncell = 1.0;
+    for (int a = 0; a < 3; a++) { g.minb[a] = hsm[a]; g.div[a] = hsm[3 + a] - hsm[a] + 1; ncell *= (double)g.div[a]; }
+    for (int a = 0; a < 3; a++) { rt.minb[a] = g.minb[a]; rt.div[a] = g.div[a]; }
+    {  // keep the measured box for the next cloud of this leaf size
+      if (!box) { box = &c->vg_box[c->vg_box_next]; c->vg_box_next = (c->vg_box_next + 1) % 4; box->leaf = leaf; }
+      bool ok = ncell <= 2.0e9;
+      for (int a = 0; a < 3; a++) if (g.minb[a] < -1000000000 || g.div[a] > 1000000000) ok = false;
+      box->g = g;
+      box->valid = ok;
+    }
+    if (ncell > 2147483647.0) {
+      // PCL: "Leaf size is too small for the input dataset. Integer indices would overflow." -> output = input
+      rt.path = RGC_VG_PATH_UNFILTERED;
+      rgck::transform_q(s, d_in, stride_f, n, rgck::Quat{0, 0, 0, 1}, (const double[3]){0, 0, 0}, d_out, 4);
+      *n_out = n;
+      HIPCHK(c, hipStreamSynchronize(s));
+    } else if (vg_rows_fit(g, n)) {
+      int flags = 0;
+      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, false, d_out, &flags, n_out, &rt))) return rc;
+      hint_from_leaf_grid(c, out_xyzi, *n_out, g, leaf);
+    } else {
+      // a dense cloud: the same chain with the leaves themselves as the sort's buckets
+      if (ncell > (double)c->prm.max_cells) return fail(c, RGC_ERR_GRID_TOO_LARGE, "leaf grid %d x %d x %d exceeds max_cells", g.div[0], g.div[1], g.div[2]);
+      int flags = 0;
+      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, true, d_out, &flags, n_out, &rt))) return rc;
+      hint_from_leaf_grid(c, out_xyzi, *n_out, g, leaf);
+    }
+  }
+  if (!on_device) {
+    HIPCHK(c, hipMemcpyAsync(out_xyzi, d_out, sizeof(float) * 4 * (size_t)*n_out, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+
+extern "C" {
+
+int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device) {
+  if (!c || !xyzi || !out_xyzi || !n_out || n < 0) return RGC_ERR_INVALID;
+  if (!stride_ok(stride_bytes) || !(leaf > 0.f) || !std::isfinite(leaf)) return fail(c, RGC_ERR_INVALID, "bad stride or leaf size");
+  *n_out = 0;
+  rgc_vg_route rt{};
+  rt.n = n;
+  const int rc = n == 0 ? RGC_OK : voxelgrid_run(c, xyzi, n, stride_bytes, leaf, out_xyzi, n_out, on_device, rt);
+  rt.status = rc;
+  rt.n_out = *n_out;
+  c->vg_route = rt;
+  return rc;
+}
+
+int rgc_voxelgrid_route(rgc_ctx* c, rgc_vg_route* out) {
+  if (!c || !out) return RGC_ERR_INVALID;
+  *out = c->vg_route;
+  return RGC_OK;
+}
+
+// rgc_voxelgrid for a DEVICE cloud in two halves.  begin enqueues the filter on the box kept from the previous cloud of this leaf size and
+// returns; end waits for it, looks at its flags and returns the point count -- repeating the filter through rgc_voxelgrid when the kept box
+// did not hold the cloud (the input must therefore stay untouched in between).  Without a kept box begin is the whole rgc_voxelgrid.
+// What it is for: the odometer's sub-map filter (RGC_odometer.cpp:985-991) depends on the pose of the PREVIOUS frame only, so a caller
+// can start it when that frame ends and collect the result after the next sweep's own filter -- its 55 us of kernels and the read-back
+// of its count are off the frame's critical path.  Other rgc_voxelgrid calls may run in between (they come later in stream order and
+// use other result words); only ONE begin may be open per context.
+int rgc_voxelgrid_begin(rgc_ctx* c, const float* d_xyzi, int n, int stride_bytes, float leaf, float* d_out) {
+  if (!c || !d_xyzi || !d_out || n < 0 || n > (1 << 27)) return RGC_ERR_INVALID;
+  if (!stride_ok(stride_bytes) || !(leaf > 0.f) || !std::isfinite(leaf)) return fail(c, RGC_ERR_INVALID, "bad stride or leaf size");
+  if (c->vg_pend.active) return fail(c, RGC_ERR_INVALID, "rgc_voxelgrid_begin: the previous one has not been ended");
+  if (n > 0) { int rk = check_device_range(c, d_xyzi, (size_t)n * stride_bytes - (stride_bytes - 12), "rgc_voxelgrid_begin: d_xyzi"); if (rk) return rk; rk = check_device_range(c, d_out, (size_t)n * 16, "rgc_voxelgrid_begin: d_out"); if (rk) return rk; }
+  HIPCHK(c, hipSetDevice(c->device));
+  rgc_ctx::VgPending& pd_ = c->vg_pend;
+  pd_ = rgc_ctx::VgPending{};
+  pd_.d_in = d_xyzi; pd_.n = n; pd_.stride_bytes = stride_bytes; pd_.leaf = leaf; pd_.d_out = d_out;
+  rgc_ctx::VgBox* box = nullptr;
+  for (auto& b : c->vg_box) if (b.leaf == leaf) box = &b;
+  bool enqueued = false;
+  if (n > 0 && box && box->valid) {
+    constexpr int kPadSparse = 32, kPadDense = 8;   // as in rgc_voxelgrid
+    rgck::LeafGrid ps = box->g, pdg = box->g;
+    for (int a = 0; a < 3; a++) { ps.minb[a] -= kPadSparse; ps.div[a] += 2 * kPadSparse; pdg.minb[a] -= kPadDense; pdg.div[a] += 2 * kPadDense; }
+    const bool sparse = vg_rows_fit(ps, n);
+    const double dcell = (double)pdg.div[0] * (double)pdg.div[1] * (double)pdg.div[2];
+    if (sparse || dcell <= (double)c->prm.max_cells) {
+      pd_.route.n = n;
+      pd_.route.kept_box = 1;
+      pd_.route.path = RGC_VG_PATH_KEPT;
+      int rc = voxelgrid_rows(c, d_xyzi, stride_bytes / 4, n, 1.0f / leaf, sparse ? ps : pdg, (sparse ? kPadSparse : kPadDense) / 2, !sparse, d_out, nullptr,
+                              nullptr, &pd_.route, c->h_vg);
+      if (rc) return rc;
+      pd_.g = sparse ? ps : pdg;
+      enqueued = true;
+    }
+  }
+  if (!enqueued) {  // no box to trust yet: the whole filter now
+    const rgc_vg_route last = c->vg_route;
+    int rc = rgc_voxelgrid(c, d_xyzi, n, stride_bytes, leaf, d_out, &pd_.n_out, 1);
+    if (rc) return rc;
+    pd_.route = c->vg_route;  // reported when this filter is ended; until then the context shows the filter before it
+    c->vg_route = last;
+    pd_.ready = true;
+  }
+  pd_.active = true;
+  return RGC_OK;
+}
+
+int rgc_voxelgrid_end(rgc_ctx* c, int* n_out) {
+  if (!c || !n_out) return RGC_ERR_INVALID;
+  rgc_ctx::VgPending& pd_ = c->vg_pend;
+  if (!pd_.active) return fail(c, RGC_ERR_INVALID, "rgc_voxelgrid_end without rgc_voxelgrid_begin");
+  pd_.active = false;
+  if (pd_.ready) { *n_out = pd_.n_out; c->vg_route = pd_.route; return RGC_OK; }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->vg_done));
+  const int flags = c->h_vg[0], no = c->h_vg[2];
+  rgc_vg_route& rt = pd_.route;
+  rt.flags = rt.kept_flags = flags;
+  if (flags & 1) { rt.status = RGC_ERR_NONFINITE; c->vg_route = rt; return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)"); }
+  rgc_ctx::VgBox* box = nullptr;
+  for (auto& b : c->vg_box) if (b.leaf == pd_.leaf) box = &b;
+  if (box && (flags & 6)) { box->valid = false; rt.box_invalidated = 1; }  // outside: measure and repeat now; near a face: measure at the next call
+  if (!(flags & 2)) { *n_out = no; rt.n_out = no; c->vg_route = rt; hint_from_leaf_grid(c, pd_.d_out, no, pd_.g, pd_.leaf); return RGC_OK; }
+  const int rc = rgc_voxelgrid(c, pd_.d_in, pd_.n, pd_.stride_bytes, pd_.leaf, pd_.d_out, n_out, 1);  // (the kept box is invalid now: measured)
+  c->vg_route.repeated = 1;
+  c->vg_route.kept_box = 1;
+  c->vg_route.kept_flags = flags;
+  c->vg_route.box_invalidated = rt.box_invalidated;
+  return rc;
+}
+
+}  // extern "C"
+
+
+// ---- A1-A8: ScanRegistration::laserCloudHandler on the device (src/scanRegistration.cpp:89-730) ----
+void rgcapi::host_eig3_sym(const double S[6], double ev[3], double V[9]) {  // Jacobi; eigenvalues ASCENDING, columns of V
+  double A[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}}, U[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  for (int sweep = 0; sweep < 60; sweep++) {
+    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+    const double dg = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+    if (off <= 1e-40 * dg || off == 0.0) break;
+    for (int p = 0; p < 2; p++)
+      for (int q = p + 1; q < 3; q++) {
+        if (A[p][q] == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double cc = 1.0 / std::sqrt(t * t + 1.0), ss = t * cc;
+        for (int k = 0; k < 3; k++) { const double a = A[k][p], b = A[k][q]; A[k][p] = cc * a - ss * b; A[k][q] = ss * a + cc * b; }
+        for (int k = 0; k < 3; k++) { const double a = A[p][k], b = A[q][k]; A[p][k] = cc * a - ss * b; A[q][k] = ss * a + cc * b; }
+        for (int k = 0; k < 3; k++) { const double a = U[k][p], b = U[k][q]; U[k][p] = cc * a - ss * b; U[k][q] = ss * a + cc * b; }
+      }
+  }
+  int o[3] = {0, 1, 2};
+  const double e[3] = {A[0][0], A[1][1], A[2][2]};
+  for (int i = 0; i < 2; i++) for (int j = i + 1; j < 3; j++) if (e[o[j]] < e[o[i]]) std::swap(o[i], o[j]);
+  for (int j = 0; j < 3; j++) { ev[j] = e[o[j]]; for (int i = 0; i < 3; i++) V[i * 3 + j] = U[i][o[j]]; }
+}
+
+extern "C" {
+
+void rgc_default_fe_params(rgc_fe_params* p) {
+  if (!p) return;
+  p->n_scans = 16; p->min_range = 0.5; p->max_range = 80.0; p->use_intensity = 1;  // launch/run.launch:6,12-13,18
+}
+
+static int frontend_impl(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, const rgc_fe_params* prm, rgc_fe_out* out, int on_device, bool allow_spec = true);
+int rgc_frontend(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, const rgc_fe_params* prm, rgc_fe_out* out) {
+  return frontend_impl(c, xyzi, n, stride_bytes, prm, out, 0);
+}
+// the same with the sweep already on the device (e.g. rgc_pc2_unpack(..., out_on_device = 1)): no host copy of the input
+int rgc_frontend_device(rgc_ctx* c, const float* d_xyzi, int n, int stride_bytes, const rgc_fe_params* prm, rgc_fe_out* out) {
+  return frontend_impl(c, d_xyzi, n, stride_bytes, prm, out, 1);
+}
+static int frontend_impl(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, const rgc_fe_params* prm, rgc_fe_out* out, int on_device, bool allow_spec) {
+  if (!c || !xyzi || !prm || !out || n < 0 || n > (1 << 27)) return RGC_ERR_INVALID;
+  if (n > (1 << 24)) return fail(c, RGC_ERR_INVALID, "sweep has %d points, the front-end's limit is 2^24", n);  // 32-bit sizes and candidate lists below
+  if (stride_bytes < 16 || (stride_bytes & 3) || stride_bytes > 4096) return fail(c, RGC_ERR_INVALID, "front-end needs x,y,z,intensity: stride_bytes >= 16");
+  const int NS = prm->n_scans;
+  if (NS != 16 && NS != 32 && NS != 64) return fail(c, RGC_ERR_INVALID, "only 16, 32 or 64 scan lines (scanRegistration.cpp:69-72)");
+  out->n_cloud = out->n_sharp = out->n_sharp_own = out->n_flat = out->n_inten = out->n_ground = 0;
+  out->ground_valid = 0;
+  c->fe_n_cloud = 0;
+  memset(out->ring_count, 0, sizeof(out->ring_count));
+  if (n == 0) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int stride_f = stride_bytes / 4;
+  const float* d_in;
+  int rc = stage_in(c, xyzi, n, stride_bytes, on_device, &d_in);
+  if (rc) return rc;
+  const int nb = rgck::fe_blocks(n);
+  enum { RING, RANK, HIST, META, ST, CL, INUM2, INUM, RANGE, ANGLE, CURV, CURV2, ICURV, DSRC, OSRC, PICK, IPICK, LAB, ILAB, GMARK, MULT, SCNT,
+         SPOS, PART, OUTD, SLOTS, FLAGS, SHARP, FLAT, INTEN, GLIST, BSUM, SORTC, SORTI };
+  const int nu = NS * 6, fcap = nu * 41;
+  constexpr size_t kTailFlags = 304, kTailSt = 336, kTailFeat = 496;  // see OUTD below
+  const size_t n4 = (size_t)4 * n;
+  const size_t sizes[34] = {n4, n4, (size_t)4 * 64 * nb, 4u * 132, 4u * 8, 4 * n4, n4, n4, n4, n4, n4, n4, n4, n4,
+                            n4, n4, n4, n4, n4, n4, n4, n4, n4, (size_t)8 * 11 * nb, kTailFeat + 60u * (size_t)fcap,
+                            4u * (size_t)nu * rgck::fe_slot_ints(), 4u * 8, 64u, 64u, 64u, 16u * 10 * (size_t)n, 4u * ((size_t)n / 2048 + 4), n4, n4};
+  // OUTD is the sweep's "tail": ground sums / fit / distance sums (doubles 0..33), the flags, the filter's start-end state and the three
+  // feature clouds in ONE buffer laid out like the pinned staging area behind the meta block, so that everything the host needs at the
+  // end of the sweep comes down in ONE copy and the two small blocks are initialised by ONE
+  for (int b = 0; b < 34; b++) if ((rc = ensure(c, c->fe[b], sizes[b] + 64))) return rc;
+#define FE(i, T) ((T*)c->fe[i].p)
+  unsigned char* const tail = (unsigned char*)c->fe[OUTD].p;
+  int* const d_flags = (int*)(tail + kTailFlags);
+  int* const d_st = (int*)(tail + kTailSt);
+  float* const d_sharp = (float*)(tail + kTailFeat);
+  float* const d_flat = d_sharp + 5 * (size_t)fcap;
+  float* const d_inten = d_flat + 5 * (size_t)fcap;
+  const int init16[16] = {0, 0, 0, 0, 0, 0, 0, 0, INT_MAX, -1, INT_MAX, 0, 0, 0, 0, 0};  // flags (zero) + the filter's state
+  memcpy(c->h_small + 32, init16, sizeof(init16));
+  HIPCHK(c, hipMemcpyAsync(d_flags, c->h_small + 32, sizeof(init16), hipMemcpyHostToDevice, s));
+  rgck::FeParams fp{NS, prm->min_range, prm->max_range};
+  rgck::fe_filter(s, d_in, stride_f, n, fp, FE(RING, int), d_st, FE(RANK, int), FE(HIST, int));
+  rgck::fe_half(s, d_in, stride_f, n, FE(RING, int), d_st);
+  rgck::fe_bucket(s, d_in, stride_f, n, NS, FE(RING, int), FE(RANK, int), FE(HIST, int), FE(META, int), d_st, FE(CL, float4), FE(INUM2, int),
+                  FE(PICK, int), FE(IPICK, int), FE(LAB, int), FE(ILAB, int));
+  // pinned staging: [0, 1024) meta + ground sums + flags, then the three feature clouds
+  const size_t stage_need = 1024 + 3 * 20u * (size_t)fcap;
+  if (c->h_stage_cap < stage_need) {
+    if (c->h_stage) (void)hipHostFree(c->h_stage);
+    c->h_stage = nullptr; c->h_stage_cap = 0;
+    HIPCHK(c, hipHostMalloc((void**)&c->h_stage, stage_need, hipHostMallocDefault));
+    c->h_stage_cap = stage_need;
+  }
+  int* meta = (int*)c->h_stage;                       // 129 ints
+  int* fl = (int*)(c->h_stage + 832);                 // 8 ints ([528, 800): the ground sums, fit and distance sums)
+  unsigned char* h_feat = c->h_stage + 1024;
+  // The sweep's size after the range filter and its ring sizes are known on the device (k_fe_hist_scan); the host needs them only to
+  // size launches and the selection kernel's LDS.  From the second sweep of a sequence on it does not wait for them: launches are sized
+  // by the raw point count, the kernels read the size themselves (csp), the selection kernel's window by the largest ring of the
+  // PREVIOUS sweep plus a quarter -- if a ring outgrows that (flag bit 1), the sweep is done again the slow way.
+  const bool spec = allow_spec && c->fe_spec_on && c->fe_last_ns == NS && c->fe_last_max_ring > 0 && !out->cloud;
+  int cs = n, max_ring = 0;
+  const int* csp = nullptr;
+  if (spec) {
+    csp = FE(META, int) + 128;
+    max_ring = std::min(n, c->fe_last_max_ring + c->fe_last_max_ring / 4 + 64);
+  } else {
+    HIPCHK(c, hipMemcpyAsync(meta, FE(META, int), sizeof(int) * 129, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    cs = meta[128];
+    out->n_cloud = cs;
+    for (int r = 0; r < NS; r++) { out->ring_count[r] = meta[r]; max_ring = std::max(max_ring, meta[r]); }
+    if (cs == 0) return RGC_OK;
+    if (out->cloud && out->cloud_cap < cs) return fail(c, RGC_ERR_INVALID, "cloud_cap %d < %d points", out->cloud_cap, cs);
+  }
+  rgck::fe_stencils(s, FE(CL, float4), cs, csp, FE(RANGE, float), FE(ANGLE, float), FE(INUM2, int), FE(INUM, int), FE(CURV, float), FE(CURV2, float),
+                    FE(ICURV, float), FE(DSRC, float), FE(OSRC, float), FE(PICK, int));
+  // A5: ground set (with multiplicities) -> weighted centroid / covariance -> plane (scanRegistration.cpp:308-431)
+  rgck::fe_ground(s, FE(CL, float4), cs, csp, NS, FE(RANGE, float), FE(META, int), FE(GMARK, int), FE(MULT, int), FE(SCNT, int), FE(PART, double), FE(OUTD, double),
+                  FE(OUTD, double) + 16);
+  // OUTD: [0..10] the ground sums, [16..31] the plane fit, [32..33] the distance sums -- fitted on the device, read back with the features
+  rgck::fe_ground_dist(s, FE(CL, float4), cs, csp, FE(MULT, int), FE(OUTD, double) + 16, FE(PART, double), FE(OUTD, double) + 32);
+  // /laser_cloud_ground: pushes in reference order (with duplicates); empty when no ground seed was found
+  // (only when the caller takes the list: the chained frame body does not, and these are four launches)
+  if (out->ground_pts && out->ground_cap > 0) {
+    rgck::exclusive_scan(s, FE(SCNT, int), FE(SPOS, int), cs, FE(BSUM, int));
+    const int gcap_dev = 10 * n;
+    rgck::fe_ground_list(s, FE(CL, float4), cs, csp, NS, FE(RANGE, float), FE(META, int), FE(SCNT, int), FE(SPOS, int), FE(GLIST, float4), gcap_dev);
+  }
+  // A7 + A8
+  rgck::fe_select(s, FE(CL, float4), NS, FE(META, int), FE(CURV, float), FE(CURV2, float), FE(ICURV, float), FE(INUM, int), FE(GMARK, int),
+                  FE(PICK, int), FE(IPICK, int), FE(LAB, int), FE(ILAB, int), FE(SLOTS, int), d_flags, max_ring, FE(SORTC, int), FE(SORTI, int));
+  rgck::fe_emit(s, FE(CL, float4), NS, FE(SLOTS, int), FE(DSRC, float), FE(OSRC, float), d_sharp, d_flat, d_inten, fcap,
+                d_flags + 4);
+  // flags and the three feature clouds (at their capacity: ~80 kB each for 16 rings) come down together into pinned memory, one
+  // synchronisation; the counts decide how much of each is handed to the caller
+  double* gd = (double*)(c->h_stage + 528);            // 34 doubles behind the 129 meta ints
+  static_assert(528 + kTailFlags == 832 && 528 + kTailFeat == 1024, "the device tail mirrors the staging area from gd on");
+  HIPCHK(c, hipMemcpyAsync(gd, tail, kTailFeat + 60u * (size_t)fcap, hipMemcpyDeviceToHost, s));
+  if (spec) HIPCHK(c, hipMemcpyAsync(meta, FE(META, int), sizeof(int) * 129, hipMemcpyDeviceToHost, s));
+  if (out->cloud) HIPCHK(c, hipMemcpyAsync(out->cloud, FE(CL, float4), sizeof(float) * 4 * (size_t)cs, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (spec) {
+    if (fl[0] & 2) {  // a ring outgrew the window sized from the previous sweep (or really holds an oversize sector): the slow way decides
+      c->fe_last_max_ring = 0;
+      return frontend_impl(c, xyzi, n, stride_bytes, prm, out, on_device, false);
+    }
+    cs = meta[128];
+    out->n_cloud = cs;
+    max_ring = 0;
+    for (int r = 0; r < NS; r++) { out->ring_count[r] = meta[r]; max_ring = std::max(max_ring, meta[r]); }
+    if (cs == 0) return RGC_OK;
+  }
+  if (fl[0] & 2) return fail(c, RGC_ERR_INVALID, "a ring sector holds more than 2048 points");
+  c->fe_n_cloud = cs;
+  c->fe_last_ns = NS; c->fe_last_max_ring = max_ring;
+  {  // ground message (:403-430) from the sums, the fit and the distance sums that just came down
+    const long long gsize = (long long)(gd[10] + 0.5);
+    if (gsize > 0) {
+      const double* nrm = gd + 19;
+      const double* V = gd + 22;
+      const double* d2 = gd + 32;
+      const double laderH = 0.56;  // :39
+      double distance = d2[1] / d2[0], src1 = d2[0] / (double)gsize;  // :403-404
+      if ((distance / laderH) > 1.1 || (distance / laderH) < 0.9) distance = laderH;  // :405-409
+      if (src1 < 0.9) distance = 0.9 * laderH + 0.1 * distance;                       // :410-413
+      double* g = out->groundparam;  // groundparam.msg order, :420-430
+      g[0] = nrm[0]; g[1] = nrm[1]; g[2] = nrm[2];
+      g[3] = V[1]; g[4] = V[4]; g[5] = V[7];
+      g[6] = V[2]; g[7] = V[5]; g[8] = V[8];
+      g[9] = distance; g[10] = 1 - src1;
+      out->ground_valid = 1;
+      out->n_ground = (int)gsize;
+      if (out->ground_pts && out->ground_cap > 0) {
+        const long long m = gsize < out->ground_cap ? gsize : out->ground_cap;
+        HIPCHK(c, hipMemcpyAsync(out->ground_pts, FE(GLIST, float4), sizeof(float) * 4 * (size_t)m, hipMemcpyDeviceToHost, s));
+      }
+    }
+  }
+  const int ns = fl[4], nf = fl[5], ni = fl[6];
+  out->n_sharp_own = ns; out->n_flat = nf; out->n_inten = ni;
+  const bool add_inten = prm->use_intensity && ((double)ns / (double)nf < 0.3);  // :645-656
+  out->n_sharp = ns + (add_inten ? ni : 0);
+  if (out->feat_cap < out->n_sharp || out->feat_cap < nf || out->feat_cap < ni) return fail(c, RGC_ERR_INVALID, "feat_cap too small");
+  if (ns) memcpy(out->sharp, h_feat, 20u * (size_t)ns);
+  if (nf) memcpy(out->flat, h_feat + 20u * (size_t)fcap, 20u * (size_t)nf);
+  if (ni) memcpy(out->inten, h_feat + 40u * (size_t)fcap, 20u * (size_t)ni);
+  if (add_inten && ni) memcpy(out->sharp + 5 * (size_t)ns, h_feat + 40u * (size_t)fcap, 20u * (size_t)ni);
+  const struct { void* dst; int src; } diag[7] = {{out->curvature, CURV}, {out->curvature2, CURV2}, {out->inten_curvature, ICURV}, {out->label, LAB},
+                                                   {out->inten_label, ILAB}, {out->picked, PICK}, {out->ground_marked, GMARK}};
+  for (auto& d : diag) if (d.dst) HIPCHK(c, hipMemcpyAsync(d.dst, c->fe[d.src].p, 4u * (size_t)cs, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+#undef FE
+  return RGC_OK;
+}
+
+int rgc_frontend_cloud_device(rgc_ctx* c, float** d_cloud, int* n) {
+  if (!c || !d_cloud || !n) return RGC_ERR_INVALID;
+  *d_cloud = c->fe_n_cloud > 0 ? (float*)c->fe[5].p : nullptr;  // CL: float4 {x, y, z, ring + 0.1 relTime}, ring-major
+  *n = c->fe_n_cloud;
+  return RGC_OK;
+}
+
+}  // extern "C"

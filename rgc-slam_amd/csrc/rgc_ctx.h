@@ -1,0 +1,391 @@
+// rgc_ctx.h -- internal to librgc_hip.so: what the host files of the C-ABI (rgc_api*.hip) share.  The build-flag defaults, the context
+// (struct rgc_ctx: opaque to callers, include/rgc_hip.h) with its buffer and cloud records, and the helpers more than one of those files
+// calls, in namespace rgcapi (-fvisibility=hidden keeps them out of the dynamic symbol table).  DESIGN.md says which file holds what.
+#pragma once
+#include "../../include/rgc_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <climits>
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <atomic>
+#include <chrono>
+#include <mutex>
+#include <new>
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+#include "rgc_kernels.h"
+
+namespace rgcapi {
+
+// Build-time switches (RGC_EXTRA_FLAGS=-D...): alternative routes to the SAME results, kept for A/B measurements.  A caller's
+// process reads RGC_LM_IMPL, RGC_SPEC_GRID, RGC_KNN_SEEDS, RGC_KNN_CACHE (a context's initial rgc_set_knn_reuse mode), RGC_TRACE_ALLOC, RGC_TRACE_CACHE, RGC_CHECK_POINTERS,
+// RGC_FORCE_GENERAL (the odometer's settings on the general covariance route: a cross-check) and the
+// three scheduling switches RGC_JOIN_SPIN_US / RGC_PREP_EVENT_EXT / RGC_COOP_STREAM from the environment, once, in rgc_create.
+#ifndef RGC_LM_POST
+#define RGC_LM_POST 1          // 0: rgc_align_end always waits for the stream and its copy of the state (round 2)
+#endif
+#ifndef RGC_FE_SPEC
+#define RGC_FE_SPEC 1          // 0: the front-end reads every sweep's size back before its stencil kernels
+#endif
+#ifndef RGC_SOLVE_BEHIND_MAP
+#define RGC_SOLVE_BEHIND_MAP 1 // 0: the solve always on the scan's (high-priority) stream (round 2)
+#endif
+#ifndef RGC_KNN_SEEDS
+#define RGC_KNN_SEEDS 1        // 0: the map's exact search never starts from the previous search's k-th distances (round 4)
+#endif
+#ifndef RGC_COOP_STREAM
+#define RGC_COOP_STREAM 0      // 1: the scan's deferred queries are resolved by waiting waves at the end of its bulk kNN launch (coop_stream): a frame at a time
+                               // 3 % faster, a sequence on two contexts 9 % slower (the waiting waves hold slots the other context's map wants); measured, off
+#endif
+#ifndef RGC_PREP_EVENT_EXT
+#define RGC_PREP_EVENT_EXT 1
+#endif
+#ifndef RGC_JOIN_SPIN_US
+#define RGC_JOIN_SPIN_US 300
+#endif
+#ifndef RGC_EARLY_POSE
+#define RGC_EARLY_POSE 1       // 0: rgc_align_end_reframe waits for a solve's score before it enqueues the next frame's target (round 5)
+#endif
+#ifndef RGC_KNN_CACHE
+#define RGC_KNN_CACHE 1        // 0: no neighbour lists (rgck::KnnCache): every frame searches the whole map, seeded
+#endif
+#ifndef RGC_MAP_WIDE_R
+#define RGC_MAP_WIDE_R 2       // block radius of the bulk kNN launch for a sparse map (0 = off, 2)
+#endif
+#ifndef RGC_MAP_WIDE
+#define RGC_MAP_WIDE 0.25      // ... taken when the map has fewer points per grid cell than this
+#endif
+#ifndef RGC_SRC_RES
+#define RGC_SRC_RES 0.0        // fixed cell size of the scan's kNN grid (0 = adaptive)
+#endif
+static_assert(RGC_MAP_WIDE_R == 0 || RGC_MAP_WIDE_R == 2, "RGC_MAP_WIDE_R: 0 or 2");
+constexpr int kProfKinds = RGC_K_COUNT;
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool borrowed = false;  // p belongs to another context (rgc_share_target): never freed, never grown here
+};
+
+struct Cloud {
+  // input (device copy owned by ctx, or caller's device pointer)
+  const float* in = nullptr;
+  int stride_f = 0;
+  int n = 0;
+  bool ready = false;  // grid + normals (+ voxels for the target) enqueued
+  bool covs_user = false;  // the normals were given by the caller (rgc_set_source/target_covariances), not computed from the neighbours
+  DevBuf in_copy, cell_of, slot_of, cnt, start, block_sums, order_tmp, P, nx, ny, nz;  // P: sorted float4 {x,y,z,orig idx}
+  DevBuf c6;            // the general covariance route only (general_route()): six doubles per point, SoA, instead of the normal
+  bool general = false; // this cloud was prepared on the general route (its covariances are in c6, nx / ny / nz hold nothing)
+  DevBuf segs;  // deferred-query list of the bulk kNN kernel: [count, pad x15][query n][bound n]
+  int deferred_seen = -1;  // deferred count of the last cloud whose count came home (sizes the next cooperative launch)
+  rgck::Grid grid{};   // the search grid: sorted array P, start[]; for the target also the voxel grid cell_voxel[] is laid out on
+  // speculative grid (voxel level): the previous cloud's grid, widened, re-used without the bounding-box round trip; k_count guards it
+  rgck::Grid spec_grid{};
+  bool spec_ok = false;    // spec_grid is usable
+  bool spec_used = false;  // this cloud was prepared on spec_grid and its guard has not been read yet
+  bool reframe_pending = false;  // in[] has not been written yet: the next preparation produces it from rf (rgc_set_target_reframed)
+  rgck::Reframe rf{};
+  size_t cnt_clean = 0;    // cnt[0 .. cnt_clean) is known to be zero (the cell scan leaves the counters it consumed at zero)
+  const void* cnt_seen = nullptr;  // the allocation cnt_clean refers to
+  // target only
+  DevBuf cell_voxel, vox, vox_cell;
+  int nvox = -1;
+  // lazy target (rgc_set_target_lazy): 0 = covariances and voxel map complete; 1 = the grid is built, nothing else (the solve's guess
+  // decides which part is needed); 2 = built for the cells stamped need_stamp in `need` only
+  int lazy = 0;
+  DevBuf need, qlist, cell_list;  // one stamp per grid cell; the listed queries (points) and cells of this frame (k_footprint)
+  int need_stamp = 0;
+  const void* need_seen = nullptr;  // the allocation the stamps refer to
+  int lazy_nq_seen = -1, lazy_ncell_seen = -1;  // the previous frame's list sizes (they size this frame's launches)
+  // seeds of the exact search (rgck::KnnSeeds): kept while the target is a re-expression of the SAME buffer (rgc_set_target_reframed: the
+  // key is the buffer it re-frames), one float per original point
+  DevBuf seed;
+  const void* seed_key = nullptr;
+  int seed_n = 0;
+  bool seed_on = false;    // this cloud's searches read and write them
+  bool seed_warm = false;  // ... and some search has written them
+  float seed_slack = 0.f;
+  // the neighbour-list cache on top of the seeds (rgck::KnnCache): the same key, the same life
+  DevBuf nbr, rank_of, pos_of, qrank, map_copy, todo, cache_small;  // cache_small: kTodoLists list lengths, the epoch word, the overflow word
+  bool cache_on = false;    // this preparation compares the map with map_copy and its searches read / write the lists
+  bool cache_live = false;  // the LAST preparation's searches ran with the lists attached (otherwise they are stale: the next frame starts over)
+  int cache_frame = 0;
+  int cache_e2 = 0;         // binary exponent of the largest coordinate the certificates were issued for
+  int cache_e2_low = 0;     // frames in a row whose coordinates stayed below it
+  int cache_e2_low_max = 0; // ... and the largest exponent among them
+  int todo_cap = 0;
+  bool slots_clean = false;        // segs' entry words hold the "empty slot" pattern (the scan's deferred queries resolved inside its bulk launch)
+  const void* slots_seen = nullptr;  // ... of this allocation
+  bool prepared_recorded = false;  // the preparation's last launch carried the context's tgt_prepared event (no record packet behind it)
+  bool cache_searched_lists = false;  // the last preparation's search was the seeded launch that reads the lists (rgc_stats::searched_target)
+  int searched_known = -1;            // rgc_stats::searched_target of this preparation once it has been fetched (-1: not yet)
+};
+
+struct ProfRegion {
+  hipEvent_t a, b;
+  int kind;
+  long long points;
+};
+
+}  // namespace rgcapi
+
+using rgcapi::Cloud;
+using rgcapi::DevBuf;
+using rgcapi::kProfKinds;
+using rgcapi::ProfRegion;
+
+struct rgc_ctx {
+  int device = 0;
+  rgc_params prm{};
+  hipStream_t stream = nullptr;   // main stream: target preprocessing, LM loop, fitness, getters
+  hipStream_t stream2 = nullptr;  // source preprocessing runs here, concurrently with the (much larger) target's
+  hipEvent_t src_ready = nullptr; // recorded on stream2 after the source is prepared
+  hipEvent_t tgt_ready = nullptr; // recorded on the main stream at rgc_align_begin: the solve (on stream2) waits for the map's preparation
+  hipEvent_t main_mark = nullptr; // recorded on the main stream before a source is prepared: stream2 waits for it (producers on rgc_stream())
+  bool src_pending = false;       // main stream has not yet been ordered after src_ready
+  bool mark_valid = false, main_has_target_prep = false;  // main_mark recorded; a map preparation was enqueued after it and may still run
+  bool main_late_producer = false;  // ... and something that may WRITE a scan buffer (rgc_upload) was enqueued on the main stream behind it
+  char err[512] = {0};
+  Cloud src, tgt;
+  // per-correspondence state frozen by linearize (fast_vgicp_impl.hpp:104-115)
+  DevBuf corr_v, corr_M, partials, ipartials;
+  DevBuf corr_v2, corr_M2;    // second correspondence buffer of the chained LM (speculative linearisation); corr_v / corr_M
+                              // always name the VALID one after a solve
+  int corr_noff = 0, corr_n = 0;
+  bool corr_valid = false;
+  // small device scratch + pinned host mirrors
+  int* d_small = nullptr;     // [0..5] target bbox, [6] flags, [7] nvox, [8] ncorr, [16..22] source bbox + flags
+  double* d_out = nullptr;    // 28 doubles
+  int* h_small = nullptr;     // pinned, same layout
+  double* h_out = nullptr;    // pinned
+  DevBuf scratch;             // getters
+  DevBuf lm_state;            // device-chained LM state (rgck::LmState)
+  // f1: mapping-node feature registration (corner / surf feature maps: grid only, 1.5 m cells)
+  Cloud mr_map[2];
+  DevBuf mr_feat[4], mr_fac[4], mr_partials, mr_small;
+  bool deferred_known = false;  // stats.deferred_* are those of the current clouds (carried home by the last align)
+  DevBuf fit_partials;        // fitness rows when it is chained behind the LM slots
+  rgck::LmState* h_lm = nullptr;  // pinned mirror (the stream-ordered copy behind every batch of LM launches)
+  rgck::LmState* h_post = nullptr; // mapped host memory the DEVICE writes a finished solve's state into, then the solve's number into its `gen`
+  rgck::LmState* d_post = nullptr; // ... its device address
+  rgck::LmEarly* h_early = nullptr, *d_early = nullptr;  // mapped host memory / its device address: a solve's final pose, posted before its score (rgc_align_end_reframe)
+  int lazy_margin = 0;             // rgc_set_target_lazy: > 0 = the target's covariances / voxels are built only where the solve can look (cells of margin)
+  hipEvent_t src_in_ready = nullptr;  // recorded on stream2 behind a HOST scan's upload: the lazy target's footprint pass (main stream) reads the scan's input
+  bool src_in_pending = false;
+  int lm_seq = 0;                  // number of the pending solve (1, 2, ...)
+  int lm_j = 0;                    // launches enqueued for it so far (rgck::lm_step's launch number: the state image alternates with it)
+  rgck::LmState lm_res{};          // the finished solve's state as rgc_align_end took it (from h_post or h_lm): nothing writes it asynchronously
+  hipEvent_t lm_mid = nullptr;     // recorded on the solve's stream behind its expected launches: the spare ones, on the context's other stream, wait for it
+  hipEvent_t lm_tail = nullptr;    // recorded behind every batch of LM launches (and its copy into h_lm) on the stream they went to
+  hipStream_t lm_tail_stream = nullptr;  // ... that stream: a solve enqueued on the OTHER stream waits for lm_tail first
+  bool post_on = RGC_LM_POST != 0; // (build flag) 0: always wait for the stream and its copy, as in round 2
+  struct { bool active = false; bool want_fitness = false; float guess[16]; } pend;  // rgc_align_begin .. rgc_align_end
+  struct { bool on = false; int rc = 0; float T[16]; double H[36]; double fitness = 0; int iterations = 0, converged = 0, lm_failed = 0; bool has_fit = false; } gen_res;  // general route: rgc_align_begin solves at once, rgc_align_end hands this over
+  int lm_last_outer = 0;      // outer iterations of the previous solve: sizes the next blind batch
+  bool small_clean[2] = {false, false};  // d_small block of the map / the scan holds its initial image (the last solve's first step restored it)
+  hipStream_t solve_stream = nullptr;  // where the pending solve was enqueued (rgc_align_begin)
+  bool solve_behind_map = RGC_SOLVE_BEHIND_MAP != 0;  // (build flag) 0: the solve always on the scan's (high-priority) stream, as in round 2
+  bool lm_host = false;       // RGC_LM_IMPL=host: host-driven LM loop over the public fine-seam kernels (cross-check of the device-chained one)
+  bool spec_on = true;        // RGC_SPEC_GRID=0 turns the speculative grid off
+  bool coop_stream_on = RGC_COOP_STREAM != 0;  // (build flag; RGC_COOP_STREAM in the environment) the scan's deferred queries inside its bulk kNN launch
+  bool prep_event_ext = RGC_PREP_EVENT_EXT != 0;  // (build flag; RGC_PREP_EVENT_EXT in the environment) the map's last launch signals tgt_prepared itself
+  int join_spin_us = RGC_JOIN_SPIN_US;  // (build flag; RGC_JOIN_SPIN_US in the environment) how long the host waits for an almost-ready scan instead of putting a barrier into the map's stream (join_source)
+  bool cache_on = RGC_KNN_CACHE != 0;  // (build flag; RGC_KNN_CACHE=0 in the environment) the neighbour lists of an unchanged map on top of the seeds
+  bool seeds_on = RGC_KNN_SEEDS != 0;  // (build flag; RGC_KNN_SEEDS=0 in the environment) 0: every search of a re-framed map starts without a bound, as before round 5
+  int reg_method = RGC_REG_PLANE, voxel_mode = RGC_VOXEL_ADDITIVE;  // as selected by the caller, implemented or not (rgc_set_regularization_method)
+  bool test_fail_cache_alloc = false;  // RGC_TEST_FAIL_CACHE_ALLOC in the environment (rgc_create)
+  bool force_general = false;          // RGC_FORCE_GENERAL=1 in the environment (rgc_create): PLANE / ADDITIVE on the general route too (a test's cross-check of the two routes)
+  bool cache_dropped = false;          // the lists' buffers did not fit on the device: the context went down to the seeds by itself (rgc_get_knn_reuse)
+  bool check_ptrs = false;             // RGC_CHECK_POINTERS in the environment (rgc_create): every pointer a caller calls "device" is looked up before it is used (check_device_range)
+  bool trace_cache = false;            // RGC_TRACE_CACHE in the environment (rgc_create): rgc_get_stats reports the lists' state on stderr
+  double src_res = RGC_SRC_RES;  // (build flag) fixed cell size of the SCAN's kNN grid (only the map's grid must be the voxel grid); 0 = adaptive
+  int map_wide_r = RGC_MAP_WIDE_R;          // (build flag; 0 = off, 2) block radius of the bulk kNN launch for a sparse map
+  double map_wide_density = RGC_MAP_WIDE;   // (build flag) ... when the map has fewer points per grid cell than this
+  double src_res_auto = 0.0;  // adaptive cell size of the scan's kNN grid, steered by how crowded its cells were in the previous frame (0 = voxel_res)
+  Cloud aux;                  // grid scratch of rgc_voxelgrid
+  DevBuf pre_in, pre_out, vg_order, vg_pos, vg_tmp, vg_leaf;  // B2/B3/B9 staging
+  struct VgBox { float leaf = 0.f; bool valid = false; rgck::LeafGrid g{}; } vg_box[4];  // measured leaf boxes of earlier clouds, by leaf size
+  int vg_box_next = 0;
+  // Bounding boxes the library knows WITHOUT measuring: rgc_set_target_reframed maps the input's box (measured once per input buffer)
+  // through the transform it applies -- the box of a sub-map re-framed by a new pose (RGC_odometer.cpp:1248-1256) follows from the
+  // pose.  The target's preparation takes its grid from the hint: no bounding-box kernel, no host round trip, and no speculative-grid
+  // miss when the re-framed map's box swings with the vehicle's yaw.  k_count's guard still checks it.
+  struct BoxHint { const void* p = nullptr; int n = 0; double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}; double reach_xy = 0, reach_z = 0; } box_hint[4];
+  int box_hint_next = 0;
+  bool vg_flags_clean = false;  // d_small[24 + 6] is known to be zero (a finished rows chain leaves it so)
+  // rgc_voxelgrid_begin / _end: one filter of a device cloud in flight (enqueued on its kept box, result not yet looked at)
+  struct VgPending { bool active = false, ready = false; const float* d_in = nullptr; int n = 0, stride_bytes = 0; float leaf = 0.f; float* d_out = nullptr;
+                     rgck::LeafGrid g{};  // the leaf grid the pending filter was enqueued on
+                     int n_out = 0;
+                     rgc_vg_route route{};  // what rgc_voxelgrid_route reports once the pending filter is ended
+                     } vg_pend;
+  rgc_vg_route vg_route{};  // the last finished leaf filter (rgc_voxelgrid_route)
+  hipEvent_t vg_done = nullptr;
+  int* h_vg = nullptr;  // pinned: the pending filter's three result ints (h_small's words are all taken: the front-end stages 16 ints at +32)
+  DevBuf fe[34];              // front-end buffers
+  unsigned char* h_stage = nullptr;  // pinned staging of the front-end's small read-backs and feature clouds (a copy into pageable
+  size_t h_stage_cap = 0;            // memory is staged by the runtime anyway, one blocking hop per call)
+  bool fe_spec_on = RGC_FE_SPEC != 0;  // (build flag) 0: read every sweep's size back before its stencil kernels
+  int fe_last_ns = 0, fe_last_max_ring = 0;  // the previous sweep's scan lines and largest ring: sizes the next sweep's launches without a read-back
+  int fe_n_cloud = 0;         // points of the last front-end's ring-major cloud (fe[5]), for rgc_frontend_cloud_device
+  // f2: rolling local map.  World-frame points (relative to map_origin, x,y,z,intensity, 16 B) of the live keyframes as
+  // contiguous segments in insertion order in map_store[map_cur]; the other buffer is the compaction / re-basing target.
+  struct MapKf { int id; size_t off; int n; double t[3]; };
+  DevBuf map_store[2], map_target;
+  int map_cur = 0;
+  size_t map_n = 0;
+  std::vector<MapKf> map_kf;
+  int map_next_id = 0;
+  double map_origin[3] = {0, 0, 0};
+  bool map_dirty = false;     // keyframes changed since the last commit
+  bool map_bound = false;     // the context's target IS the committed map (rgc_set_target* unbinds it)
+  unsigned long long tgt_generation = 0;   // bumped whenever this context prepares a target (what borrowers check)
+  const rgc_ctx* tgt_owner = nullptr;      // rgc_share_target: whose target this context aliases, and at which generation
+  unsigned long long tgt_owner_gen = 0, tgt_owner_uid = 0;
+  unsigned long long uid = 0;              // process-wide, never re-used
+  hipEvent_t tgt_prepared = nullptr;       // recorded on the main stream behind every target preparation (rgc_hold_source_until_target_of of another context waits for it)
+  hipEvent_t src_read_done = nullptr;      // recorded on the main stream behind a kernel that reads the source's INPUT buffer (rgc_get_aligned*)
+  bool src_read_pending = false;           // ... and not yet waited for by the stream a host source is copied on
+  float map_leaf = 0.f;
+  int map_ntarget = 0;
+  unsigned long long map_rev = 0;
+  // f5: the mapping node's keyframe store.  Body-frame points (x,y,z,c, 16 B) per kind in kf_store[kind], a keyframe's clouds as one
+  // contiguous run each; the key poses (and the quaternions the reference's chain makes of them) stay on the host and travel with every
+  // assembly's segment table.
+  struct KfRec { int id; size_t off[RGC_KF_KINDS]; int n[RGC_KF_KINDS]; rgc_kf_pose pose; double q[4]; };
+  DevBuf kf_store[RGC_KF_KINDS];
+  size_t kf_n[RGC_KF_KINDS] = {0, 0, 0};
+  std::vector<KfRec> kf;
+  std::unordered_map<int, int> kf_index;   // id -> position in kf
+  unsigned long long kf_rev = 0;
+  DevBuf kf_table, kf_raw, kf_filt;        // the segment table on the device; the unfiltered / filtered assembly when it is not written to the caller's buffer
+  unsigned char* kf_h_table = nullptr;     // pinned staging of the segment table
+  size_t kf_h_cap = 0;
+  hipEvent_t kf_uploaded = nullptr;        // recorded behind the table's copy: the staging is rewritten only after it
+  bool kf_upload_pending = false;
+  // NDT registration (rgc_ndt_*): two clouds of its own (0 target, 1 source) with their grids and voxel maps (Cloud::cell_voxel / vox / vox_cell,
+  // records of rgck::kNdtRec doubles), the offsets of the neighbour method, the frozen term list of the last linearisation
+  rgc_ndt_params ndt_prm{1.0, RGC_NDT_D2D, RGC_NDT_DIRECT7, 0.0};
+  Cloud ndt_cl[2];
+  bool ndt_set[2] = {false, false};       // a cloud has been handed over (its points are in Cloud::in_copy, 12-byte stride)
+  bool ndt_built[2] = {false, false};     // ... and its voxel map is built, at resolution ndt_built_res
+  double ndt_built_res[2] = {0.0, 0.0};
+  std::vector<int> ndt_offs_h;            // 3 ints per offset, the order of the reference's list
+  DevBuf ndt_offs, ndt_corr, ndt_partials, ndt_ipartials, ndt_small, ndt_out;
+  bool ndt_offs_dirty = true;
+  double* ndt_h_out = nullptr;            // pinned: 32 doubles
+  int* ndt_h_small = nullptr;             // pinned: 8 ints
+  bool ndt_corr_valid = false;            // ndt_corr holds the list of ndt_corr_n elements x ndt_corr_noff offsets made under ndt_corr_mode at ndt_Tlin
+  int ndt_corr_n = 0, ndt_corr_noff = 0, ndt_corr_mode = 0, ndt_terms = 0;
+  double ndt_Tlin[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  // FastGICP (rgc_gicp_*) on the context's own source and target: the pair list of the last rgc_gicp_linearize (per sorted source point the
+  // neighbour's position in the target's sorted array or -1, and the fp32 key), its Mahalanobis matrices, scratch of its own.  gicp_valid
+  // falls wherever corr_valid falls: a cloud set, cleared, swapped, given covariances or prepared again
+  double gicp_dmax = (double)FLT_MAX;     // corr_dist_threshold_ (fast_gicp_impl.hpp:18: std::numeric_limits<float>::max())
+  DevBuf gicp_corr, gicp_key, gicp_M, gicp_partials, gicp_out;
+  double* gicp_h_out = nullptr;           // pinned: 32 doubles
+  bool gicp_valid = false;
+  int gicp_n = 0, gicp_kept = 0;
+  rgc_stats stats{};
+  // profiling
+  bool prof_on = false;
+  unsigned prof_mask = ~0u;
+  std::vector<ProfRegion> prof_open;
+  std::vector<hipEvent_t> ev_pool;
+  long long prof_launches[kProfKinds] = {0};
+  double prof_ms[kProfKinds] = {0};
+  long long prof_points[kProfKinds] = {0};
+};
+
+namespace rgcapi {
+
+#define HIPCHK(c, expr)                                                                                    \
+  do {                                                                                                     \
+    hipError_t _e = (expr);                                                                                \
+    if (_e != hipSuccess) {                                                                                \
+      (void)hipGetLastError(); /* the runtime keeps a failed call's error until it is read: reported HERE, it must not surface again   \
+                                  from the hipGetLastError() of the next, unrelated call (tests/fuzz/fuzz_bad_args.py) */             \
+      return rgcapi::fail((c), RGC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);               \
+    }                                                                                                      \
+  } while (0)
+
+// ---- rgc_api.hip: errors, buffers, the clouds' preparation, the registration core ----
+int fail(rgc_ctx* c, int code, const char* fmt, ...);
+int ensure(rgc_ctx* c, DevBuf& b, size_t bytes);
+int check_device_range(rgc_ctx* c, const void* p, size_t bytes, const char* what);
+bool ctx_alive(const rgc_ctx* c);
+const rgc_ctx::BoxHint* find_hint(const rgc_ctx* c, const void* p, int n);
+void put_hint(rgc_ctx* c, const void* p, int n, const double lo[3], const double hi[3], double reach_xy = 0, double reach_z = 0);
+void hint_from_leaf_grid(rgc_ctx* c, const float* out /* device, or the caller's host buffer */, int n_out, const rgck::LeafGrid& g, float leaf);
+bool map_prep_finished(rgc_ctx* c);
+// rf (nullable, device clouds only): xyz has not been written yet -- the preparation produces it from rf (rgc_set_target_reframed)
+int set_cloud(rgc_ctx* c, Cloud& cl, bool is_target, const float* xyz, int n, int stride_bytes, bool on_device, const rgck::Reframe* rf = nullptr);
+// The grid of a cloud that is no VGICP target (a feature map, the ICP target, an NDT voxel map): its bounding box measured (one round
+// trip), the points counting-sorted into that box's cells of size `cell`.  dsm / hsm: eight scratch ints on the device / the host;
+// with_voxels: cell_voxel[] too, and the voxel count in dsm[7] (not read back here); name / grid_name: the cloud in the two error messages
+int build_measured_grid(rgc_ctx* c, Cloud& cl, double cell, int* dsm, int* hsm, bool with_voxels, const char* name, const char* grid_name);
+rgck::Pose pose_from(const double T[16]);
+rgck::PoseF posef_from(const float T[16]);
+int check_target_owner(rgc_ctx* c);
+int need_inputs(rgc_ctx* c, bool validate = true);
+int do_fitness(rgc_ctx* c, const float T[16], double* out);
+// the 28 sums a linearisation folds to (21 of H's upper triangle by rows, 6 of b, the cost) -> the full symmetric H and b
+void unpack_system(const double sums[28], double H[36], double b[6]);
+
+// between rgc_align_begin and rgc_align_end -- on the general route too, where the solve has already run and its result waits to be handed over:
+// the same calls are refused on both routes
+inline bool solve_in_flight(const rgc_ctx* c) { return c->pend.active || c->gen_res.on; }
+// what every entry point that takes a strided cloud accepts: x, y, z as floats at the head of each record
+inline bool stride_ok(int stride_bytes) { return stride_bytes >= 12 && !(stride_bytes & 3) && stride_bytes <= 4096; }
+// the rotation and translation rows of a row-major 4x4 (or 3x4) pose
+template <class T>
+inline bool pose12_finite(const T* m) {
+  for (int i = 0; i < 12; i++)
+    if (!std::isfinite(m[i])) return false;
+  return true;
+}
+
+// ---- rgc_api_pre.hip ----
+int stage_in(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, const float** d_in);
+// rgc_voxelgrid after its argument checks; rt: what rgc_voxelgrid_route reports, filled as the call goes (the caller adds status and n_out)
+int voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt);
+void host_eig3_sym(const double S[6], double ev[3], double V[9]);  // Jacobi; eigenvalues ASCENDING, columns of V
+
+// ---- rgc_api_lsq.hip: the LM driver of every registration method ----
+// A registration problem as the driver sees it.  Either linearize + error (the driver makes the first try of an outer iteration itself, on
+// the host), or linearize_try + error: the linearisation at x0 AND that first try in one call (rgc_align: one enqueue, the try on the
+// device; lambda < 0 on entry = not initialised yet, *lambda_used = the one the try used).
+struct LmSystem {
+  int (*linearize)(rgc_ctx* c, const double T[16], double* H, double* b, double* cost);
+  int (*error)(rgc_ctx* c, const double T[16], double* cost);
+  int (*linearize_try)(rgc_ctx* c, const double x0[16], double lambda, double H[36], double b[6], double* y0, double d[6], double xi[16],
+                       double* lambda_used, double* yi);
+  bool (*may_linearize)(const double x0[16]);  // nullable; false: nothing can be linearised at this pose -- the solve ends as failed
+};
+struct LmResult {
+  double x0[16], Hfin[36];  // the final pose and final_hessian_
+  float fin[16];            // ... the pose as the caller gets it (lsq_registration_impl.hpp:77)
+  int iters;                // outer iterations started
+  bool conv, failed;
+  void write(float final_T[16], double final_H[36], int* iterations, int* converged, int* lm_failed) const {  // (each nullable)
+    if (final_T) memcpy(final_T, fin, sizeof(fin));
+    if (final_H) memcpy(final_H, Hfin, sizeof(Hfin));
+    if (iterations) *iterations = iters;
+    if (converged) *converged = conv ? 1 : 0;
+    if (lm_failed) *lm_failed = failed ? 1 : 0;
+  }
+};
+// computeTransformation from `guess` under c->prm's limits; an error of a system call ends it with that code (r is not complete then)
+int lm_solve(rgc_ctx* c, const LmSystem& sys, const float guess[16], LmResult* r);
+
+}  // namespace rgcapi

@@ -1141,7 +1141,7 @@ __device__ __forceinline__ bool list_certified(float a_up, float b_lo, double bo
 // the lists outlive the frame's order).  ~1 % of the queries, an atomic each on one of kTodoLists words.
 constexpr int kListCertified = (int)0x80000000;
 #ifndef RGC_KNN_CACHE
-#define RGC_KNN_CACHE 1  // 0: the neighbour-list workgroups are not compiled into k_knn_sp (rgc_api.hip's flag of the same name keeps the host from asking for them)
+#define RGC_KNN_CACHE 1  // 0: the neighbour-list workgroups are not compiled into k_knn_sp (rgc_ctx.h's flag of the same name keeps the host from asking for them)
 #endif
 template <int KC>
 __device__ __forceinline__ void cache_uncertified(const Deferred& df, int rank) {
@@ -3223,7 +3223,7 @@ __device__ __forceinline__ void step_fitness_rows(const float4* __restrict__ SP,
   if (((int)threadIdx.x & (WAVE - 1)) == 0) __hip_atomic_store(&fa.partials[w], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The words of the LM area that are NOT part of either state image (rgc_api.hip allocates 4096 bytes and zeroes them once):
+// The words of the LM area that are NOT part of either state image (rgc_align_begin, rgc_api.hip, allocates 4096 bytes and zeroes them once):
 //   +3072  the lazy target's miss flag ("a look-up hit an occupied voxel outside the part that was built"), set by any workgroup of any
 //          launch of a solve, taken into the finished state (pad2) and cleared by whoever finishes it
 //   +3076  the ticket of the score's fold (the one launch of a solve whose workgroups hand rows to each other)

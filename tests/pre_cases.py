@@ -15,7 +15,7 @@ def drawn_leaves(k=4, seed=20260):
     return tuple(float(np.float32(x)) for x in np.random.default_rng(seed).uniform(0.06, 2.5, k))
 
 
-# ---- the route rule as csrc/rgc_api.hip has it (voxelgrid_rows, vg_rows_fit), restated -----------------------------------------------
+# ---- the route rule as csrc/rgc_api_pre.hip has it (voxelgrid_rows, vg_rows_fit), restated -----------------------------------------------
 def rows_fit(div, n):
     ncell, nrows = float(div[0]) * div[1] * div[2], float(div[1]) * div[2]
     return ncell <= 2147483647.0 and ncell > 64.0 * n and nrows <= 64.0e6

@@ -92,11 +92,12 @@ def test_knob_inventory_is_current():
 
 def test_every_entry_point_selects_its_device():
     """One process may hold contexts on several GPUs and call them from threads whose current device is another one (a new thread starts on device 0).
-    A static audit of csrc/rgc_api.hip, where every entry point lives: each exported rgc_* function from which a HIP runtime call or a kernel launch can
+    A static audit of csrc/rgc_api*.hip, where every entry point lives (non-static helpers have one name across them): each exported rgc_* function from which a HIP runtime call or a kernel launch can
     be reached calls hipSetDevice(c->device) itself or in a function it calls directly.  (A one-GPU box cannot show the difference; round 6 found
     rgc_set_params and rgc_get_stats re-preparing clouds -- kernel launches -- on whatever device the caller's thread had current.)"""
     import re
-    src = open(os.path.join(ROOT, "rgc-slam_amd", "csrc", "rgc_api.hip")).read()
+    csrc = os.path.join(ROOT, "rgc-slam_amd", "csrc")
+    src = "\n".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if re.fullmatch(r"rgc_api\w*\.hip", f))
     funcs = {}
     for m in re.finditer(r'^(?:extern "C" )?(?:RGC_API |static |inline )*[\w:<>\*& ]+?\b(\w+)\s*\(([^;{}]*?)\)\s*(?:const\s*)?\{', src, re.M):
         if m.group(1) in ("for", "if", "while", "switch", "catch"):
