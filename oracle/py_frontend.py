@@ -87,8 +87,11 @@ def occlusion(rng):
     return picked[:n]
 
 
-def select(cloud, st, picked_in, ground_marked, scan_start, scan_end, use_intensity=1):
-    """:458-656.  cloud: (n,4) ring-major with encoded intensity; st: stencils() output; scan_start / scan_end = scanStartInd / scanEndInd."""
+def select(cloud, st, picked_in, ground_marked, scan_start, scan_end, use_intensity=1, tie=1, only=None, trace=None):
+    """:458-656.  cloud: (n,4) ring-major with encoded intensity; st: stencils() output; scan_start / scan_end = scanStartInd / scanEndInd.
+    For the census of tests/fe_reference.py (defaults = the restatement): tie = -1 sorts equal keys by DESCENDING index (the other order
+    std::sort may leave them in); only = (ring, sector) runs that one sector alone; trace: a list that receives, per sector,
+    (ring, sector, [k_sharp, k_flat, k_inten]) -- the list is filled in as the three loops end, with their counters as they leave them (22 / 41 / 22: the quota's `break` was taken)."""
     P = np.asarray(cloud, np.float32)
     n = len(P)
     curv, curv2, icurv, num = st["curvature"], st["curvature2"], st["inten_curvature"], st["intensity_num"]
@@ -117,10 +120,15 @@ def select(cloud, st, picked_in, ground_marked, scan_start, scan_end, use_intens
         if E - S < 10:
             continue
         for j in range(6):
+            if only is not None and only != (i, j):
+                continue
             sp = S + (E - S) * j // 6
             ep = S + (E - S) * (j + 1) // 6 - 1
-            by_curv = sorted(range(sp, ep + 1), key=lambda t: (curv[t], t))
-            by_int = sorted(range(sp, ep + 1), key=lambda t: (icurv[t], t))
+            by_curv = sorted(range(sp, ep + 1), key=lambda t: (curv[t], tie * t))
+            by_int = sorted(range(sp, ep + 1), key=lambda t: (icurv[t], tie * t))
+            ks = [0, 0, 0]
+            if trace is not None:
+                trace.append((i, j, ks))
             k = 0
             for ind in reversed(by_curv):
                 if picked[ind] == 0 and ground_marked[ind] != 1 and curv[ind] > 0.1 and curv2[ind] > 0.3:
@@ -134,6 +142,7 @@ def select(cloud, st, picked_in, ground_marked, scan_start, scan_end, use_intens
                         break
                     picked[ind] = 1
                     suppress(ind, picked, far_pts)
+            ks[0] = k
             k = 0
             for ind in by_curv:
                 if picked[ind] == 0 and curv[ind] < 0.3 and curv2[ind] < 0.4:
@@ -145,6 +154,7 @@ def select(cloud, st, picked_in, ground_marked, scan_start, scan_end, use_intens
                         break
                     picked[ind] = 1
                     suppress(ind, picked, far_pts)
+            ks[1] = k
             k = 0
             for ind in reversed(by_int):
                 if ipicked[ind] == 0 and ground_marked[ind] != 1 and icurv[ind] > 65 and label[ind] != 2 and label[ind] != 1:
@@ -158,6 +168,7 @@ def select(cloud, st, picked_in, ground_marked, scan_start, scan_end, use_intens
                         break
                     ipicked[ind] = 1
                     suppress(ind, ipicked, far_int)
+            ks[2] = k
     n_sharp_own = len(sharp)
     if use_intensity and len(flat) and n_sharp_own / len(flat) < 0.3:   # :645-656
         sharp = sharp + inten
