@@ -569,6 +569,17 @@ RGC_API int rgc_mapreg_optimize(rgc_ctx* ctx, const float* corner_cur, int n_ccu
                                 const float* corner_last, int n_clast, const float* surf_last, int n_slast,
                                 const rgc_mapreg_ground* ground_cur, const rgc_mapreg_ground* ground_last,
                                 const rgc_mapreg_imu* imu, double poses[14], rgc_mapreg_report report[2], int* gate_failed);
+/* the normal equations one LM iteration of rgc_mapreg_optimize starts from, read out (the counterpart of rgc_linearize): the four
+ * association loops at poses_assoc, then H (12 x 12 row-major, full and symmetric; rows 0-2 / 3-5 the rotation / translation of the
+ * current pose on the local parameterisation, 6-11 the last pose's), g (12) and the robust cost of those frozen factors at
+ * poses_eval (NULL: at poses_assoc).  n_factors: n_edge_cur, n_plane_cur, n_edge_last, n_plane_last.  factors8 (nullable, each entry
+ * nullable): the factors of {corner_cur, surf_cur, corner_last, surf_last}, n x 8 doubles each in rgc_mapreg_associate's layout.
+ * Needs rgc_mapreg_set_maps; does NOT apply the size gate of :1069, and any feature set may be empty. */
+RGC_API int rgc_mapreg_linearize(rgc_ctx* ctx, const float* corner_cur, int n_ccur, const float* surf_cur, int n_scur,
+                                 const float* corner_last, int n_clast, const float* surf_last, int n_slast,
+                                 const rgc_mapreg_ground* ground_cur, const rgc_mapreg_ground* ground_last,
+                                 const rgc_mapreg_imu* imu, const double poses_assoc[14], const double poses_eval[14],
+                                 double H[144], double g[12], double* cost, int n_factors[4], double* const factors8[4]);
 
 
 /* ---- f2: rolling local map resident on the device ----

@@ -179,6 +179,7 @@ def lib():
         gp = C.POINTER(MapregGround)
         mi = C.POINTER(MapregImu)
         L.orc_mapreg_solve.argtypes = [fp, ef, C.c_int, fp, pf, C.c_int, fp, ef, C.c_int, fp, pf, C.c_int, gp, gp, mi, dp, C.c_int, tr]
+        L.orc_mapreg_evaluate.argtypes = [fp, ef, C.c_int, fp, pf, C.c_int, fp, ef, C.c_int, fp, pf, C.c_int, gp, gp, mi, dp, dp, dp, dp]
         L.orc_mapreg_optimize.argtypes = [fp, C.c_int, fp, C.c_int, fp, C.c_int, fp, C.c_int, fp, C.c_int, fp, C.c_int, C.c_int, gp, gp, mi, dp, tr, C.c_int]
         _lib = L
     return _lib
@@ -401,6 +402,38 @@ def mapreg_solve(corner_cur, e_cur, surf_cur, p_cur, corner_last, e_last, surf_l
                            C.byref(gc) if gc else None, C.byref(gl) if gl else None, C.byref(im) if im else None,
                            x.ctypes.data_as(C.POINTER(C.c_double)), max_iterations, C.byref(tr))
     return x, {k: getattr(tr, k) for k, _ in MapregTrace._fields_ if k != "pad"}
+
+
+def make_factors(f, kind):
+    """a raw ctypes factor array from a dict of numpy arrays (valid, a, b, var / valid, n, d, var): the inverse of mapreg_associate(raw=False)"""
+    n = len(f["valid"])
+    arr = ((EdgeFactor if kind == "edge" else PlaneFactor) * max(n, 1))()
+    for i in range(n):
+        arr[i].valid = int(bool(f["valid"][i]))
+        arr[i].var = float(f["var"][i])
+        if kind == "edge":
+            arr[i].a[:] = [float(v) for v in f["a"][i]]
+            arr[i].b[:] = [float(v) for v in f["b"][i]]
+        else:
+            arr[i].n[:] = [float(v) for v in f["n"][i]]
+            arr[i].d = float(f["d"][i])
+    return arr
+
+
+def mapreg_evaluate(corner_cur, e_cur, surf_cur, p_cur, corner_last, e_last, surf_last, p_last, poses14, ground_cur=None, ground_last=None, imu=None,
+                    want_H=True):
+    """H (12,12), g (12), cost of the frozen factors at poses14 (orc_mapreg_evaluate); e_*/p_* are RAW ctypes factor arrays."""
+    cc, ccp = _f32(corner_cur); sc, scp = _f32(surf_cur); cl, clp = _f32(corner_last); sl, slp = _f32(surf_last)
+    x = np.ascontiguousarray(poses14, dtype=np.float64)
+    H, g, cost = np.zeros((12, 12)), np.zeros(12), C.c_double(0)
+    gc, gl, im = make_ground(ground_cur), make_ground(ground_last), make_imu(imu)
+    dp = C.POINTER(C.c_double)
+    rc = lib().orc_mapreg_evaluate(ccp, e_cur, cc.shape[0], scp, p_cur, sc.shape[0], clp, e_last, cl.shape[0], slp, p_last, sl.shape[0],
+                                   C.byref(gc) if gc else None, C.byref(gl) if gl else None, C.byref(im) if im else None, x.ctypes.data_as(dp),
+                                   H.ctypes.data_as(dp) if want_H else None, g.ctypes.data_as(dp) if want_H else None, C.byref(cost))
+    if rc:
+        raise RuntimeError(f"orc_mapreg_evaluate rc={rc}")
+    return H, g, cost.value
 
 
 def mapreg_optimize(corner_cur, surf_cur, corner_last, surf_last, corner_map, surf_map, poses14, threads=0, ground_cur=None, ground_last=None,

@@ -166,6 +166,13 @@ int orc_mapreg_solve(const float* corner_cur, const orc_edge_factor* e_cur, int 
                      const orc_plane_factor* p_last, int n_slast, const orc_mapreg_ground* ground_cur /* nullable */,
                      const orc_mapreg_ground* ground_last /* nullable */, const orc_mapreg_imu* imu /* nullable */, double poses[14],
                      int max_iterations, orc_mapreg_trace* trace);
+/* what one LM iteration of orc_mapreg_solve starts from: the robust cost of the frozen factors at poses and, unless H144 and g12 are
+ * both NULL, their normal equations (H 12 x 12 row-major, full and symmetric; g 12) */
+int orc_mapreg_evaluate(const float* corner_cur, const orc_edge_factor* e_cur, int n_ccur, const float* surf_cur, const orc_plane_factor* p_cur,
+                        int n_scur, const float* corner_last, const orc_edge_factor* e_last, int n_clast, const float* surf_last,
+                        const orc_plane_factor* p_last, int n_slast, const orc_mapreg_ground* ground_cur /* nullable */,
+                        const orc_mapreg_ground* ground_last /* nullable */, const orc_mapreg_imu* imu /* nullable */, const double poses[14],
+                        double* H144, double* g12, double* cost);
 /* returns 1 if the gate of RGC_mapping.cpp:1069 is not met (poses untouched), 0 on success */
 int orc_mapreg_optimize(const float* corner_cur, int n_ccur, const float* surf_cur, int n_scur, const float* corner_last, int n_clast,
                         const float* surf_last, int n_slast, const float* corner_map, int n_cmap, const float* surf_map, int n_smap,

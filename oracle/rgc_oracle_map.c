@@ -435,6 +435,19 @@ static double mapreg_evaluate(const mapreg_problem* P, const double x[14], doubl
   return cost;
 }
 
+/* mapreg_evaluate for callers outside this file: H144 (full, symmetric) and g12 nullable together -> the cost only */
+int orc_mapreg_evaluate(const float* corner_cur, const orc_edge_factor* e_cur, int n_ccur, const float* surf_cur, const orc_plane_factor* p_cur,
+                        int n_scur, const float* corner_last, const orc_edge_factor* e_last, int n_clast, const float* surf_last,
+                        const orc_plane_factor* p_last, int n_slast, const orc_mapreg_ground* ground_cur, const orc_mapreg_ground* ground_last,
+                        const orc_mapreg_imu* imu, const double poses[14], double* H144, double* g12, double* cost) {
+  if (!poses || !cost || (H144 == NULL) != (g12 == NULL)) return -1;
+  const mapreg_problem P = {corner_cur, surf_cur, corner_last, surf_last, e_cur, e_last, p_cur, p_last, n_ccur, n_scur, n_clast, n_slast,
+                            ground_cur, ground_last, imu};
+  if (g12) memset(g12, 0, sizeof(double) * 12);
+  *cost = mapreg_evaluate(&P, poses, H144, g12);
+  return 0;
+}
+
 /* ceres::Solve restated (see the header of this file).  poses: q_cur[4] t_cur[3] q_last[4] t_last[3] in/out. */
 int orc_mapreg_solve(const float* corner_cur, const orc_edge_factor* e_cur, int n_ccur, const float* surf_cur, const orc_plane_factor* p_cur,
                      int n_scur, const float* corner_last, const orc_edge_factor* e_last, int n_clast, const float* surf_last,

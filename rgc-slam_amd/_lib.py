@@ -148,7 +148,7 @@ SYMBOLS = [
     "rgc_clear_source", "rgc_clear_target", "rgc_swap_source_and_target", "rgc_get_voxels",
     "rgc_get_stats", "rgc_device_alloc", "rgc_device_free", "rgc_host_alloc", "rgc_host_free", "rgc_upload", "rgc_download", "rgc_synchronize",
     "rgc_stream", "rgc_default_fe_params", "rgc_frontend", "rgc_extract_pose", "rgc_imu_preintegrate", "rgc_imu_filter_init", "rgc_imu_filter_push", "rgc_ground_gate_init", "rgc_ground_gate_remember", "rgc_ground_gate_step", "rgc_default_fuse_in", "rgc_fuse_pose", "rgc_compose_pose",
-    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_kf_reset", "rgc_kf_push", "rgc_kf_set_poses", "rgc_kf_get_info", "rgc_kf_assemble", "rgc_mapreg_set_maps_device", "rgc_icp_align_device",
+    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_mapreg_linearize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_kf_reset", "rgc_kf_push", "rgc_kf_set_poses", "rgc_kf_get_info", "rgc_kf_assemble", "rgc_mapreg_set_maps_device", "rgc_icp_align_device",
     "rgc_default_ndt_params", "rgc_ndt_set_params", "rgc_ndt_get_params", "rgc_ndt_set_target", "rgc_ndt_set_source", "rgc_ndt_set_target_device", "rgc_ndt_set_source_device", "rgc_ndt_clear_source", "rgc_ndt_clear_target", "rgc_ndt_swap_source_and_target", "rgc_ndt_linearize", "rgc_ndt_compute_error", "rgc_ndt_num_correspondences", "rgc_ndt_align", "rgc_ndt_get_voxels", "rgc_ndt_get_raw_covariances",
     "rgc_gicp_set_max_correspondence_distance", "rgc_gicp_get_max_correspondence_distance", "rgc_gicp_linearize", "rgc_gicp_compute_error", "rgc_gicp_num_correspondences", "rgc_gicp_get_correspondences", "rgc_gicp_align",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
@@ -308,6 +308,8 @@ def load():
     L.rgc_mapreg_associate.argtypes = [vp, C.c_int, fp, C.c_int, dp, dp, dp, ip]
     L.rgc_mapreg_optimize.argtypes = [vp, fp, C.c_int, fp, C.c_int, fp, C.c_int, fp, C.c_int, C.POINTER(MapregGround), C.POINTER(MapregGround),
                                       C.POINTER(MapregImu), dp, C.POINTER(MapregReport), ip]
+    L.rgc_mapreg_linearize.argtypes = [vp, fp, C.c_int, fp, C.c_int, fp, C.c_int, fp, C.c_int, C.POINTER(MapregGround), C.POINTER(MapregGround),
+                                       C.POINTER(MapregImu), dp, dp, dp, dp, dp, ip, C.POINTER(dp)]
     L.rgc_frontend_cloud_device.argtypes = [vp, C.POINTER(C.c_void_p), ip]
     L.rgc_map_reset.argtypes = [vp, dp]
     L.rgc_map_insert.argtypes = [vp, vp, C.c_int, C.c_int, dp, dp, C.c_int, ip]

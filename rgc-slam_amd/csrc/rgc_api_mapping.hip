@@ -369,6 +369,49 @@ int rgc_mapreg_optimize(rgc_ctx* c, const float* corner_cur, int n_ccur, const f
   return RGC_OK;
 }
 
+// a read-out of what one LM iteration of rgc_mapreg_optimize sees: the association at poses_assoc (the four loops in one launch, as
+// there), then the normal equations of the frozen factors at poses_eval (NULL: at poses_assoc).  No gate of :1069 -- it reports, it
+// does not decide -- and any feature set may be empty.
+int rgc_mapreg_linearize(rgc_ctx* c, const float* corner_cur, int n_ccur, const float* surf_cur, int n_scur, const float* corner_last,
+                         int n_clast, const float* surf_last, int n_slast, const rgc_mapreg_ground* ground_cur, const rgc_mapreg_ground* ground_last,
+                         const rgc_mapreg_imu* imu, const double poses_assoc[14], const double poses_eval[14], double H[144], double g[12],
+                         double* cost, int n_factors[4], double* const factors8[4]) {
+  if (!c || !poses_assoc || !H || !g || !cost || !n_factors || n_ccur < 0 || n_scur < 0 || n_clast < 0 || n_slast < 0) return RGC_ERR_INVALID;
+  if (n_ccur > (1 << 27) || n_scur > (1 << 27) || n_clast > (1 << 27) || n_slast > (1 << 27)) return fail(c, RGC_ERR_INVALID, "feature cloud larger than 2^27 points");
+  if ((n_ccur && !corner_cur) || (n_scur && !surf_cur) || (n_clast && !corner_last) || (n_slast && !surf_last)) return RGC_ERR_INVALID;
+  if (!c->mr_map[0].ready || !c->mr_map[1].ready) return fail(c, RGC_ERR_NO_INPUT, "rgc_mapreg_set_maps first");
+  HIPCHK(c, hipSetDevice(c->device));
+  const float* feat[4] = {corner_cur, surf_cur, corner_last, surf_last};
+  const int nfeat[4] = {n_ccur, n_scur, n_clast, n_slast};
+  const rgc_mapreg_ground* const ground[2] = {ground_cur, ground_last};
+  int rc;
+  for (int s = 0; s < 4; s++)
+    if ((rc = mapreg_upload_features(c, s, feat[s], nfeat[s]))) return rc;
+  const int nb = std::max(rgck::mapreg_blocks(n_ccur, n_scur), rgck::mapreg_blocks(n_clast, n_slast));
+  if ((rc = ensure(c, c->mr_partials, sizeof(double) * 2 * rgck::kAccum * (size_t)(nb > 0 ? nb : 1)))) return rc;
+  int* dcnt = (int*)c->mr_small.p + 8;
+  HIPCHK(c, hipMemsetAsync(dcnt, 0, 4 * sizeof(int), c->stream));
+  rgck::MapregAssoc sets[4];
+  for (int s = 0; s < 4; s++) {
+    const double* q = poses_assoc + 7 * (s / 2);
+    const Cloud& m = c->mr_map[s & 1];
+    sets[s] = rgck::MapregAssoc{(const float*)c->mr_feat[s].p, nfeat[s], (s & 1) == 0 ? 1 : 0, rgck::Quat{q[0], q[1], q[2], q[3]}, {q[4], q[5], q[6]},
+                                (const float4*)m.P.p, (const int*)m.start.p, m.grid, (double*)c->mr_fac[s].p, dcnt + s};
+  }
+  rgck::mapreg_associate(c->stream, sets, 4);
+  HIPCHK(c, hipMemcpyAsync(c->h_small + 40, dcnt, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  for (int s = 0; s < 4 && factors8; s++)
+    if (factors8[s] && nfeat[s] > 0)
+      HIPCHK(c, hipMemcpyAsync(factors8[s], c->mr_fac[s].p, sizeof(double) * 8 * (size_t)nfeat[s], hipMemcpyDeviceToHost, c->stream));
+  MapregSystem S;
+  if ((rc = mapreg_eval(c, nfeat, poses_eval ? poses_eval : poses_assoc, true, ground, imu, &S))) return rc;
+  memcpy(H, S.H, sizeof(S.H));
+  memcpy(g, S.g, sizeof(S.g));
+  *cost = S.cost;
+  for (int s = 0; s < 4; s++) n_factors[s] = c->h_small[40 + s];
+  return RGC_OK;
+}
+
 // ---- f2: rolling local map resident on the device (replaces the keyframe deque + per-frame re-framing + re-upload of
 // src/RGC_odometer.cpp:1218-1256, 985-991, 1007) ----------------------------------------------------------------------------
 static int map_reserve(rgc_ctx* c, int which, size_t points, bool preserve) {

@@ -121,3 +121,28 @@ class MapFeatureRegistration:
                                               C.byref(im) if im else None, x.ctypes.data_as(C.POINTER(C.c_double)), rep, C.byref(gate)))
         report = None if gate.value else [{k: getattr(r, k) for k, _ in _lib.MapregReport._fields_} for r in rep]
         return x[0:4].copy(), x[4:7].copy(), x[7:11].copy(), x[11:14].copy(), report
+
+    def linearize(self, corner_cur, surf_cur, corner_last, surf_last, poses_assoc, poses_eval=None, ground_cur=None, ground_last=None, imu=None,
+                  want_factors=False):
+        """rgc_mapreg_linearize: what one LM iteration of optimize() starts from, read out.  The four association loops at poses_assoc (14: q_w_curr
+        t_w_curr q_w_last t_w_last), then H (12,12), g (12) and the robust cost of those frozen factors at poses_eval (None: at poses_assoc).
+        Returns dict(H, g, cost, n_factors=(n_edge_cur, n_plane_cur, n_edge_last, n_plane_last)[, factors=[four (n,8) arrays]]).  No size gate;
+        any feature set may be empty."""
+        sets = [_f32(np.asarray(a, np.float32).reshape(-1, 4), 4) for a in (corner_cur, surf_cur, corner_last, surf_last)]
+        dp = C.POINTER(C.c_double)
+        xa = np.ascontiguousarray(poses_assoc, np.float64)
+        xe = None if poses_eval is None else np.ascontiguousarray(poses_eval, np.float64)
+        H, g, cost, nf = np.zeros((12, 12)), np.zeros(12), C.c_double(0), (C.c_int * 4)()
+        fac = [np.zeros((a.shape[0], 8)) for a, _ in sets] if want_factors else None
+        fp = (dp * 4)(*[f.ctypes.data_as(dp) for f in fac]) if want_factors else None
+        gc, gl, im = self._ground(ground_cur), self._ground(ground_last), self._imu(imu)
+        args = []
+        for a, p in sets:
+            args += [p if a.shape[0] else None, a.shape[0]]
+        self._chk(self._L.rgc_mapreg_linearize(self._h, *args, C.byref(gc) if gc else None, C.byref(gl) if gl else None, C.byref(im) if im else None,
+                                               xa.ctypes.data_as(dp), xe.ctypes.data_as(dp) if xe is not None else None, H.ctypes.data_as(dp),
+                                               g.ctypes.data_as(dp), C.byref(cost), nf, fp))
+        out = dict(H=H, g=g, cost=cost.value, n_factors=tuple(nf))
+        if want_factors:
+            out["factors"] = fac
+        return out

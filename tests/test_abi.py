@@ -68,6 +68,7 @@ def test_null_arguments_are_rejected_without_a_gpu(lib):
     assert L.rgc_share_target(None, None) == -1
     assert L.rgc_align(None, g, None, None, None, None, None, None) == -1
     assert L.rgc_voxelgrid_route(None, C.byref(lib.VgRoute())) == -1
+    assert L.rgc_mapreg_linearize(None, None, 0, None, 0, None, 0, None, 0, None, None, None, None, None, None, None, None, None, None) == -1
 
 
 def test_knob_inventory_is_current():
@@ -116,7 +117,7 @@ def test_every_entry_point_selects_its_device():
         return bool(hip_call.search(body)) or any(reaches_hip(c, seen | {name}) for c in set(re.findall(r"\b(\w+)\s*\(", body)) if c in funcs and c != name)
 
     exported = [n for n in funcs if n.startswith("rgc_")]
-    assert len(exported) >= 75
+    assert len(exported) >= 76 and "rgc_mapreg_linearize" in exported and reaches_hip("rgc_mapreg_linearize") and "hipSetDevice" in funcs["rgc_mapreg_linearize"]
     no_context = {"rgc_host_alloc", "rgc_host_free"}                    # pinned host memory, hipHostMallocPortable: no context in the signature
     bad = []
     for n in exported:
@@ -162,7 +163,7 @@ def test_integration_names_every_entry_point():
     assert r.returncode == 0, r.stderr or r.stdout
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     syms = set(re.findall(r"\b(rgc_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", "rgc_hip.h")).read()))
-    assert len(syms) >= 85 and [s for s in sorted(syms) if "`" + s + "`" not in doc] == []
+    assert len(syms) >= 86 and "rgc_mapreg_linearize" in syms and [s for s in sorted(syms) if "`" + s + "`" not in doc] == []
 
 
 def test_python_mirror_prototypes_match_the_header(lib):
@@ -186,7 +187,7 @@ def test_python_mirror_prototypes_match_the_header(lib):
             if not is_ptr and re.match(r"(const\s+)?(double|float)\b", p):
                 assert t in (C.c_double, C.c_float) and (t is C.c_double) == ("double" in p), (name, p, t)
         checked += 1
-    assert checked >= 80
+    assert checked >= 81 and len(L.rgc_mapreg_linearize.argtypes) == 19
 
 
 def test_python_mirror_struct_layouts_match_the_header(lib, tmp_path):

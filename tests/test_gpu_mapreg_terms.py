@@ -1,0 +1,156 @@
+"""f1, everything behind the association, term by term on the GPU.  -m gpu.
+
+rgc_mapreg_linearize (k_mapreg_terms, k_mapreg_fold, the host's ground and IMU blocks) against the longdouble reference of
+tests/mapreg_reference.py at the GPU's OWN factors, on the designed cases of tests/mapreg_cases.py: every entry of H and g and the cost in the
+unit |difference| / sum |terms of that entry|, at the association pose and at a second pose with the factors frozen.  The bar is 8 x the
+largest deviation of the C oracle (the same formulas in sequential fp64) from the reference, measured without a GPU by
+tests/test_mapreg_reference.py -- which also shows that one dropped factor, one wrong rho', one negated Jacobian column or a wrong edge
+baseline moves some entry by 100 bars in every case.  Then the routes (bit for bit) and rgc_mapreg_optimize against the C oracle on every
+LM-path and shape case: iterations, accepted steps and factor counts equal, costs 1e-9 relative, poses 1e-7."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import mapreg_cases as mc
+import mapreg_reference as ref
+
+pytestmark = pytest.mark.gpu
+CASES = list(mc.SPECS)
+
+
+@pytest.fixture(scope="module")
+def reg():
+    from rgc_slam_amd import mapping
+    r = mapping.MapFeatureRegistration(0)
+    r.setInputMaps(*mc.maps())
+    yield r
+    r.close()
+
+
+def _linearize(r, c, x_eval=None, want_factors=True):
+    f = c["feat"]
+    return r.linearize(f[0], f[1], f[2], f[3], c["x0"], x_eval, ground_cur=c["ground"][0], ground_last=c["ground"][1], imu=c["imu"], want_factors=want_factors)
+
+
+def _same(a, b):
+    return np.array_equal(a["H"], b["H"]) and np.array_equal(a["g"], b["g"]) and a["cost"] == b["cost"] and a["n_factors"] == b["n_factors"]
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_readout_vs_reference(reg, name):
+    c = mc.build(name)
+    bar = mc.bar_of(c)
+    out = _linearize(reg, c)
+    fac = out["factors"]
+    # the factors it reports are those of rgc_mapreg_associate at the same pose, and the counts are theirs
+    for s in range(4):
+        b = s // 2
+        if not len(c["feat"][s]):
+            assert fac[s].shape == (0, 8) and out["n_factors"][s] == 0
+            continue
+        a = reg.associate(c["feat"][s], c["x0"][7 * b: 7 * b + 4], c["x0"][7 * b + 4: 7 * b + 7], "edge" if s % 2 == 0 else "plane")
+        F = mc.factors8(a, "edge" if s % 2 == 0 else "plane")
+        assert np.array_equal(F, fac[s]) and out["n_factors"][s] == int((fac[s][:, 7] != 0).sum()) == a["n_valid"]
+    assert out["n_factors"] == tuple(int((f[:, 7] != 0).sum()) for f in mc.associate(c, c["x0"]))      # the C oracle finds as many
+    for x_eval in (None, c["x_eval"]):
+        o = out if x_eval is None else _linearize(reg, c, x_eval)
+        if x_eval is not None:
+            assert all(np.array_equal(a, b) for a, b in zip(o["factors"], fac))                        # frozen: associated at x0 again
+        e = ref.evaluate(mc.problem(c, fac), c["x0"] if x_eval is None else x_eval)
+        dev, zeros_ok = ref.deviation(e, o["H"], o["g"], o["cost"])
+        print(f"{name} {'x0' if x_eval is None else 'x_eval'}: |gpu - reference| / sum |terms| = {dev:.3e} (bar {bar:.2e}), cost {o['cost']:.6g}")
+        assert np.array_equal(o["H"], o["H"].T)
+        assert zeros_ok, "an entry whose terms are all exactly zero is not exactly zero"
+        assert dev <= bar
+    if c["minima"].get("no_factors"):
+        assert not out["H"].any() and not out["g"].any() and out["cost"] == 0 and out["n_factors"] == (0, 0, 0, 0)
+    if c["minima"].get("planes_ez"):
+        for a in (2, 3, 4, 8, 9, 10):    # yaw, x, y: the plane fit leaves 1e-15 in n_x, n_y (see test_mapreg_reference.py), nothing more
+            assert np.abs(out["H"][a]).max() < 1e-12 * out["H"].max() and np.abs(out["H"][:, a]).max() < 1e-12 * out["H"].max()
+            assert abs(out["g"][a]) < 1e-12 * np.abs(out["g"]).max()
+
+
+def test_routes_give_the_same_bits(reg):
+    """host maps / device maps, strides 12, 16 and 32, a fresh context / one that has just solved the largest case, a repeated call"""
+    from rgc_slam_amd import mapping
+    corner, surf = mc.maps()
+    big = mc.build("huber")
+    for name in ("n257", "blocks_1_3", "ground_imu", "all_invalid"):
+        c = mc.build(name)
+        base = _linearize(reg, c)
+        assert _same(base, _linearize(reg, c, want_factors=False))                                  # repeated, without the optional output
+        _linearize(reg, big)
+        bf = big["feat"]
+        reg.optimize(bf[0], bf[1], bf[2], bf[3], big["x0"][0:4], big["x0"][4:7], big["x0"][7:11], big["x0"][11:14])
+        after = _linearize(reg, c)                                                                  # stale factors, partials and counts behind it
+        assert _same(base, after) and all(np.array_equal(a, b) for a, b in zip(base["factors"], after["factors"]))
+        for stride in (12, 16, 32):
+            r = mapping.MapFeatureRegistration(0)
+            cm, sm = np.zeros((len(corner), stride // 4), np.float32), np.zeros((len(surf), stride // 4), np.float32)
+            cm[:, :3], sm[:, :3] = corner, surf
+            cm[:, 3:], sm[:, 3:] = 7.5, -3.25                                                       # what lies between the points is not read
+            r.setInputMaps(cm, sm)
+            assert _same(base, _linearize(r, c)), ("host", stride)
+            L = r._L
+            dc, ds = C.c_void_p(), C.c_void_p()
+            assert L.rgc_device_alloc(r._h, cm.nbytes, C.byref(dc)) == 0 and L.rgc_device_alloc(r._h, sm.nbytes, C.byref(ds)) == 0
+            assert L.rgc_upload(r._h, dc, cm.ctypes.data_as(C.c_void_p), cm.nbytes) == 0 and L.rgc_upload(r._h, ds, sm.ctypes.data_as(C.c_void_p), sm.nbytes) == 0
+            r._chk(L.rgc_mapreg_set_maps_device(r._h, dc, len(cm), ds, len(sm), stride))
+            assert _same(base, _linearize(r, c)), ("device", stride)
+            L.rgc_device_free(r._h, dc); L.rgc_device_free(r._h, ds)
+            r.close()
+
+
+def test_readout_needs_maps_and_leaves_optimize_alone(reg):
+    from rgc_slam_amd import mapping, _lib
+    c = mc.build("smallest")
+    r = mapping.MapFeatureRegistration(0)
+    with pytest.raises(_lib.RgcError):
+        _linearize(r, c)
+    r.close()
+    f, x0 = c["feat"], c["x0"]
+    a = reg.optimize(f[0], f[1], f[2], f[3], x0[0:4], x0[4:7], x0[7:11], x0[11:14])
+    _linearize(reg, c, c["x_eval"])
+    b = reg.optimize(f[0], f[1], f[2], f[3], x0[0:4], x0[4:7], x0[7:11], x0[11:14])
+    assert all(np.array_equal(u, v) for u, v in zip(a[:4], b[:4])) and a[4] == b[4]
+
+
+def test_readout_of_four_empty_sets(reg):
+    """no feature at all: no association launch, one block of zeros per pose.  H, g, cost and counts are exactly zero; with the IMU block what
+    is left is that block alone (the host's), the same bits as on a fresh context, the translations' rows exactly zero.  (No comparison in
+    |difference| / sum |terms| here: with seven terms per entry the rounding of a central-difference Jacobian is not small against an entry
+    whose own terms are small; the blocks are held to the reference inside the designed cases.)"""
+    from rgc_slam_amd import mapping
+    empty = np.zeros((0, 4), np.float32)
+    c = mc.build("imu_0.4")
+    _linearize(reg, mc.build("huber"))                          # stale factors and partials of five blocks behind it
+    o = reg.linearize(empty, empty, empty, empty, c["x0"], want_factors=True)
+    assert not o["H"].any() and not o["g"].any() and o["cost"] == 0 and o["n_factors"] == (0, 0, 0, 0) and all(f.shape == (0, 8) for f in o["factors"])
+    o = reg.linearize(empty, empty, empty, empty, c["x0"], c["x_eval"], imu=c["imu"])
+    r = mapping.MapFeatureRegistration(0)
+    r.setInputMaps(*mc.maps())
+    assert _same(o, r.linearize(empty, empty, empty, empty, c["x0"], c["x_eval"], imu=c["imu"]))
+    r.close()
+    assert np.array_equal(o["H"], o["H"].T) and o["H"][0, 0] > 0 and o["cost"] > 0 and not o["H"][3:6].any() and not o["H"][9:12].any()
+    assert not o["g"][3:6].any() and not o["g"][9:12].any()
+
+
+@pytest.mark.parametrize("name", mc.LM_CASES)
+def test_optimize_vs_oracle(reg, name):
+    c = mc.build(name)
+    f, x0 = c["feat"], c["x0"]
+    qc, tc, ql, tl, rep = reg.optimize(f[0], f[1], f[2], f[3], x0[0:4], x0[4:7], x0[7:11], x0[11:14], ground_cur=c["ground"][0], ground_last=c["ground"][1],
+                                       imu=c["imu"])
+    xo, rc, tr = mc.oracle_optimize(c)
+    assert rc == 0 and rep is not None
+    x = np.concatenate([qc, tc, ql, tl])
+    for i in range(2):
+        print(name, i, {k: rep[i][k] for k in ("iterations", "successful", "initial_cost", "final_cost")}, tr[i]["final_cost"])
+        assert (rep[i]["iterations"], rep[i]["successful"]) == (tr[i]["iterations"], tr[i]["successful"])
+        assert (rep[i]["n_edge_cur"], rep[i]["n_edge_last"], rep[i]["n_plane_cur"], rep[i]["n_plane_last"]) == \
+               (tr[i]["n_edge_cur"], tr[i]["n_edge_last"], tr[i]["n_plane_cur"], tr[i]["n_plane_last"])
+        assert abs(rep[i]["initial_cost"] - tr[i]["initial_cost"]) <= 1e-9 * tr[i]["initial_cost"]
+        assert abs(rep[i]["final_cost"] - tr[i]["final_cost"]) <= 1e-9 * tr[i]["final_cost"]
+    assert np.abs(x - xo).max() < 1e-7
+    assert abs(np.linalg.norm(x[0:4]) - 1) < 1e-15 and abs(np.linalg.norm(x[7:11]) - 1) < 1e-15       # returned normalised (all_invalid starts at |q| = 1.5, 0.5)
