@@ -99,6 +99,32 @@ typedef enum rgc_voxel_accumulation_mode { RGC_VOXEL_ADDITIVE = 0, RGC_VOXEL_ADD
 RGC_API int rgc_set_regularization_method(rgc_ctx* ctx, int method);
 RGC_API int rgc_set_voxel_accumulation_mode(rgc_ctx* ctx, int mode);
 
+/* FastVGICPCuda::setNearestNeighborSearchMethod / setKernelWidth (include/fast_gicp/gicp/fast_vgicp_cuda.hpp:21,58,61,
+ * impl/fast_vgicp_cuda_impl.hpp:46-51,64-66,107-109,136-138): how a point's covariance is estimated.  RGC_COV_KNN (default; the reference's
+ * CPU_PARALLEL_KDTREE and GPU_BRUTEFORCE): the moment of its k exact nearest neighbours.  RGC_COV_RBF (GPU_RBF_KERNEL,
+ * src/fast_gicp/cuda/covariance_estimation_rbf.cu:59-151): the Gaussian-weighted moment of EVERY point of its cloud within max_dist.
+ *   ball     B(i) = { j : key(i, j) <= max_dist_sq }, key = the fp32 ((dx*dx + dy*dy) + dz*dz) without FMA (the key of the exact kNN),
+ *            max_dist_sq = (float)max_dist * (float)max_dist in fp32 (:70,75-78); the point itself is always a member
+ *   moment   in fp64: w_j = exp(-(double)(float)kernel_width * (double)key) -- "kernel_width" is the exponent's FACTOR (:80,120) --,
+ *            d_j = P_j - P_i, S0 = sum w_j, S1 = sum w_j d_j, S2 = sum w_j d_j d_j^T, m = S1 / S0, cov = S2 / S0 - m m^T
+ *            (NormalDistribution::finalize, :46-52, with the origin at P_i: the same matrix without the reference's fp32 cancellation),
+ *            summed over the ball in ascending position of the cloud's cell-sorted order, one chain per point: bit-reproducible
+ *   then     the selected RegularizationMethod, as after the kNN moment (fast_vgicp_cuda.cu:210,218)
+ * The reference pads the cloud to a multiple of 512 with points at the origin and does not mask them (:74,127-129): points within max_dist of
+ * (0,0,0) gain phantom neighbours there.  That defect is not reproduced.
+ * rgc_set_rbf_kernel: defaults 0.5, 3.0 (fast_vgicp_cuda_impl.hpp:31); max_dist <= 0 means 5 * kernel_width (:46-51) and is what the getter
+ * returns; kernel_width must be finite and > 0 (as a float too), max_dist not NaN: otherwise RGC_ERR_INVALID and nothing changes.  It may be
+ * called under either method; it takes effect under RGC_COV_RBF.
+ * RGC_COV_RBF runs on the GENERAL route whatever the regularisation (a 3x3 per point, see above: the same entry points, the host-driven LM,
+ * rgc_set_target_lazy / rgc_set_knn_reuse without effect).  k_correspondences plays no part and RGC_ERR_TOO_FEW_POINTS does not apply: a
+ * cloud of one point is legal.  Changing the method, or the kernel while RBF is selected, DROPS the clouds (the rule of
+ * rgc_set_regularization_method); setting the current value again drops nothing.  An out-of-range method is RGC_ERR_INVALID. */
+typedef enum rgc_covariance_estimation { RGC_COV_KNN = 0, RGC_COV_RBF = 1 } rgc_covariance_estimation;
+RGC_API int rgc_set_covariance_estimation(rgc_ctx* ctx, int method);
+RGC_API int rgc_get_covariance_estimation(const rgc_ctx* ctx, int* method);
+RGC_API int rgc_set_rbf_kernel(rgc_ctx* ctx, double kernel_width, double max_dist);
+RGC_API int rgc_get_rbf_kernel(const rgc_ctx* ctx, double* kernel_width, double* max_dist);
+
 /* FastVGICP construction / destruction (a stack local re-created per frame at RGC_odometer.cpp:998;
  * here the context is long-lived and re-used, device buffers grow on demand). */
 RGC_API int  rgc_create(int hip_device, const rgc_params* params /* NULL = defaults */, rgc_ctx** out);

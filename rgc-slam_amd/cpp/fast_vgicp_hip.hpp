@@ -32,6 +32,7 @@ namespace rgc {
 enum class NeighborSearchMethod { DIRECT27 = RGC_DIRECT27, DIRECT7 = RGC_DIRECT7, DIRECT1 = RGC_DIRECT1 };  // gicp_settings.hpp:8
 enum class RegularizationMethod { NONE, MIN_EIG, NORMALIZED_MIN_EIG, PLANE, FROBENIUS };                    // gicp_settings.hpp:6
 enum class VoxelAccumulationMode { ADDITIVE, ADDITIVE_WEIGHTED, MULTIPLICATIVE };                            // gicp_settings.hpp:10
+enum class NearestNeighborMethod { CPU_PARALLEL_KDTREE, GPU_BRUTEFORCE, GPU_RBF_KERNEL };                    // fast_vgicp_cuda.hpp:21
 
 class FastVGICPHip {
 public:
@@ -60,6 +61,12 @@ public:
   // point, unoptimised).  Select before setInputTarget / setInputSource: a change drops the clouds that were set under the other setting.
   void setRegularizationMethod(RegularizationMethod m) { note(rgc_set_regularization_method(ctx_, (int)m)); }
   void setVoxelAccumulationMode(VoxelAccumulationMode m) { note(rgc_set_voxel_accumulation_mode(ctx_, (int)m)); }
+  // FastVGICPCuda's pair (fast_vgicp_cuda.hpp:58,61): GPU_RBF_KERNEL takes a point's covariance from the Gaussian-weighted moment of every point
+  // within max_dist (rgc_set_covariance_estimation in rgc_hip.h, the general route); the other two methods both mean the exact kNN
+  void setNearestNeighborSearchMethod(NearestNeighborMethod method) {
+    note(rgc_set_covariance_estimation(ctx_, method == NearestNeighborMethod::GPU_RBF_KERNEL ? RGC_COV_RBF : RGC_COV_KNN));
+  }
+  void setKernelWidth(double kernel_width, double max_dist = -1.0) { note(rgc_set_rbf_kernel(ctx_, kernel_width, max_dist)); }
   int lastSetterStatus() const { return setter_status_; }                 // RGC_OK, or why the last refused setter was refused
   const std::string& lastSetterError() const { return setter_error_; }
   void setMaxCorrespondenceDistance(double) {}   // unused by FastVGICP

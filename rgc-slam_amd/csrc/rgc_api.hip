@@ -40,7 +40,10 @@ int fail(rgc_ctx* c, int code, const char* fmt, ...) {
 // the GENERAL route: every point through the cooperative search with a regularised 3x3 per point (rgck::knn_cov6), a plain voxel pass, and
 // the host-driven LM loop over a linearisation that takes the full source covariance.  Unoptimised; the same entry points, the same results
 // as the reference's arithmetic for those settings (fast_gicp_impl.hpp:262-293, fast_vgicp_voxel.hpp:76-99).
-static bool general_route(const rgc_ctx* c) { return c->force_general || c->reg_method != RGC_REG_PLANE || c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE; }
+// RBF covariance estimation (rgc_set_covariance_estimation) hands out a 3x3 per point too, whatever the regularisation.
+static bool general_route(const rgc_ctx* c) {
+  return c->force_general || c->reg_method != RGC_REG_PLANE || c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE || c->cov_method == RGC_COV_RBF;
+}
 
 int ensure(rgc_ctx* c, DevBuf& b, size_t bytes) {
   if (b.borrowed) { b.p = nullptr; b.cap = 0; b.borrowed = false; }  // an alias is dropped, never resized: this context gets its own buffer
@@ -509,6 +512,19 @@ static rgck::KnnSeeds cloud_seeds(const Cloud& cl, bool is_target) {
   return sd;
 }
 
+// How many cells of grid g (per axis) a ball of max_dist can span beyond its centre's cell.  The fp32 key of a pair can ROUND DOWN onto
+// max_dist_sq: res = 1, max_dist = 3, x = nextafter(1, 0) in cell 0 and a neighbour at x = 4 in cell 4 have dx = 3.0f and key 9 -- a member
+// four cells away.  A member lies within max_dist (1 + 2^-20) of its centre (*reach_dist; the key's three roundings are 2^-22 of it), and a
+// cell offset of d needs a distance above (d - 1) res: d <= floor(reach_dist / res) + 1.  Clamped to the grid's largest dimension.
+static int rbf_reach(const rgck::Grid& g, double max_dist, double* reach_dist) {
+  const double R = max_dist * (1.0 + 0x1p-20);
+  *reach_dist = R;
+  int dmax = 1;
+  for (int a = 0; a < 3; a++) dmax = g.dim[a] > dmax ? g.dim[a] : dmax;
+  const double r = std::floor(R / g.res) + 1.0;
+  return r < (double)dmax ? (int)r : dmax;  // (also when r is infinite)
+}
+
 // C2 / C3 of a cloud whose grid is built: exact-kNN covariances (+ the Gaussian voxel map for the target), enqueued on the cloud's stream.
 static int cloud_covariances(rgc_ctx* c, Cloud& cl, bool is_target) {
   const int n = cl.n, k = c->prm.k_correspondences;
@@ -521,7 +537,15 @@ static int cloud_covariances(rgc_ctx* c, Cloud& cl, bool is_target) {
     const int* guard = cl.spec_used ? dsm + 6 : nullptr;
     {
       ProfScope ps(c, is_target ? RGC_K_KNN_COV : RGC_K_KNN_COV_SRC, n, s);
-      rgck::knn_cov6(s, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, c->reg_method, (double*)cl.c6.p, guard);
+      if (c->cov_method == RGC_COV_RBF) {
+        const float md = (float)c->rbf_max_dist;
+        double reach_dist;
+        const int reach = rbf_reach(cl.grid, c->rbf_max_dist, &reach_dist);
+        rgck::rbf_cov6(s, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, (float)c->rbf_width, md * md, reach, reach_dist, c->reg_method,
+                       (double*)cl.c6.p, guard);
+      } else {
+        rgck::knn_cov6(s, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, c->reg_method, (double*)cl.c6.p, guard);
+      }
     }
     if (is_target) {
       const size_t vmax = (size_t)(n < cl.grid.ncell ? n : cl.grid.ncell);
@@ -695,7 +719,7 @@ int set_cloud(rgc_ctx* c, Cloud& cl, bool is_target, const float* xyz, int n, in
   if (!xyz || n < 0) return fail(c, RGC_ERR_INVALID, "null cloud");
   if (!stride_ok(stride_bytes)) return fail(c, RGC_ERR_INVALID, "stride_bytes must be a multiple of 4 and >= 12");
   if (n > (1 << 27)) return fail(c, RGC_ERR_INVALID, "cloud has %d points, the limit is 2^27 (32-bit byte offsets into the sorted array)", n);
-  if (n < c->prm.k_correspondences)
+  if (n < min_cloud_points(c))
     return fail(c, RGC_ERR_TOO_FEW_POINTS, "%s cloud has %d points, need >= k = %d", is_target ? "target" : "source", n, c->prm.k_correspondences);
   HIPCHK(c, hipSetDevice(c->device));
   const int stride_f = stride_bytes / 4;
@@ -1292,6 +1316,46 @@ int rgc_set_regularization_method(rgc_ctx* c, int method) {
     c->src.ready = c->tgt.ready = false; c->corr_valid = c->gicp_valid = false; c->deferred_known = false; c->map_bound = false;
   }
   c->reg_method = method;
+  return RGC_OK;
+}
+
+int rgc_set_covariance_estimation(rgc_ctx* c, int method) {
+  if (!c) return RGC_ERR_INVALID;
+  if (method != RGC_COV_KNN && method != RGC_COV_RBF) return fail(c, RGC_ERR_INVALID, "rgc_set_covariance_estimation: %d is neither RGC_COV_KNN nor RGC_COV_RBF", method);
+  if (method != c->cov_method) {  // the clouds' covariances were estimated the other way: the rule of rgc_set_regularization_method
+    if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+    c->src.ready = c->tgt.ready = false; c->corr_valid = c->gicp_valid = false; c->deferred_known = false; c->map_bound = false;
+  }
+  c->cov_method = method;
+  return RGC_OK;
+}
+
+int rgc_get_covariance_estimation(const rgc_ctx* c, int* method) {
+  if (!c || !method) return RGC_ERR_INVALID;
+  *method = c->cov_method;
+  return RGC_OK;
+}
+
+int rgc_set_rbf_kernel(rgc_ctx* c, double kernel_width, double max_dist) {
+  if (!c) return RGC_ERR_INVALID;
+  // the kernel computes with (float)kernel_width (covariance_estimation_rbf.cu:80): it must be a positive finite float as well
+  if (!std::isfinite(kernel_width) || !(kernel_width > 0.0) || kernel_width > (double)FLT_MAX || !((float)kernel_width > 0.f))
+    return fail(c, RGC_ERR_INVALID, "rgc_set_rbf_kernel: kernel_width must be finite and > 0");
+  if (std::isnan(max_dist)) return fail(c, RGC_ERR_INVALID, "rgc_set_rbf_kernel: max_dist is not a number");
+  if (max_dist <= 0.0) max_dist = 5.0 * kernel_width;  // fast_vgicp_cuda_impl.hpp:46-51
+  if (c->cov_method == RGC_COV_RBF && (kernel_width != c->rbf_width || max_dist != c->rbf_max_dist)) {
+    if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+    c->src.ready = c->tgt.ready = false; c->corr_valid = c->gicp_valid = false; c->deferred_known = false; c->map_bound = false;
+  }
+  c->rbf_width = kernel_width;
+  c->rbf_max_dist = max_dist;
+  return RGC_OK;
+}
+
+int rgc_get_rbf_kernel(const rgc_ctx* c, double* kernel_width, double* max_dist) {
+  if (!c || !kernel_width || !max_dist) return RGC_ERR_INVALID;
+  *kernel_width = c->rbf_width;
+  *max_dist = c->rbf_max_dist;
   return RGC_OK;
 }
 

@@ -78,7 +78,7 @@ static int reframe_args_ok(rgc_ctx* c, const float* d_xyzi, int n, int stride_by
   if (!d_xyzi || !d_scratch || n <= 0) return fail(c, RGC_ERR_INVALID, "rgc_set_target_reframed: null buffer or no points");
   if (!stride_ok(stride_bytes)) return fail(c, RGC_ERR_INVALID, "bad stride");
   if (n > (1 << 27)) return fail(c, RGC_ERR_INVALID, "cloud has %d points, the limit is 2^27 (32-bit byte offsets into the sorted array)", n);
-  if (n < c->prm.k_correspondences) return fail(c, RGC_ERR_TOO_FEW_POINTS, "target cloud has %d points, need >= k = %d", n, c->prm.k_correspondences);
+  if (n < min_cloud_points(c)) return fail(c, RGC_ERR_TOO_FEW_POINTS, "target cloud has %d points, need >= k = %d", n, c->prm.k_correspondences);
   // the re-framed cloud is WRITTEN to d_scratch while d_xyzi is read: they must not overlap (and one buffer has one bounding-box hint)
   const char* a0 = (const char*)d_xyzi; const char* a1 = a0 + (size_t)n * stride_bytes;
   const char* b0 = (const char*)d_scratch; const char* b1 = b0 + (size_t)n * 16;

@@ -203,6 +203,10 @@ struct rgc_ctx {
   bool cache_on = RGC_KNN_CACHE != 0;  // (build flag; RGC_KNN_CACHE=0 in the environment) the neighbour lists of an unchanged map on top of the seeds
   bool seeds_on = RGC_KNN_SEEDS != 0;  // (build flag; RGC_KNN_SEEDS=0 in the environment) 0: every search of a re-framed map starts without a bound, as before round 5
   int reg_method = RGC_REG_PLANE, voxel_mode = RGC_VOXEL_ADDITIVE;  // as selected by the caller, implemented or not (rgc_set_regularization_method)
+  // rgc_set_covariance_estimation / rgc_set_rbf_kernel: RGC_COV_RBF takes a point's covariance from the Gaussian-weighted moment of its ball
+  // (rgc_rbf.hip) on the general route; the kernel as the caller gave it, max_dist already resolved (<= 0 -> 5 kernel_width)
+  int cov_method = RGC_COV_KNN;
+  double rbf_width = 0.5, rbf_max_dist = 3.0;  // fast_vgicp_cuda_impl.hpp:31
   bool test_fail_cache_alloc = false;  // RGC_TEST_FAIL_CACHE_ALLOC in the environment (rgc_create)
   bool force_general = false;          // RGC_FORCE_GENERAL=1 in the environment (rgc_create): PLANE / ADDITIVE on the general route too (a test's cross-check of the two routes)
   bool cache_dropped = false;          // the lists' buffers did not fit on the device: the context went down to the seeds by itself (rgc_get_knn_reuse)
@@ -345,6 +349,8 @@ void unpack_system(const double sums[28], double H[36], double b[6]);
 // between rgc_align_begin and rgc_align_end -- on the general route too, where the solve has already run and its result waits to be handed over:
 // the same calls are refused on both routes
 inline bool solve_in_flight(const rgc_ctx* c) { return c->pend.active || c->gen_res.on; }
+// the fewest points a cloud may have: k for the k nearest neighbours, one under RBF (a point is a member of its own ball)
+inline int min_cloud_points(const rgc_ctx* c) { return c->cov_method == RGC_COV_RBF ? 1 : c->prm.k_correspondences; }
 // what every entry point that takes a strided cloud accepts: x, y, z as floats at the head of each record
 inline bool stride_ok(int stride_bytes) { return stride_bytes >= 12 && !(stride_bytes & 3) && stride_bytes <= 4096; }
 // the rotation and translation rows of a row-major 4x4 (or 3x4) pose

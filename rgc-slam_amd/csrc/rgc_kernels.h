@@ -173,6 +173,10 @@ void linearize(hipStream_t s, const float4* P, const double* nx, const double* n
 // through the cooperative search, a regularised 3x3 per point (c6: six doubles, SoA c6[a * n + i], sorted order) instead of a unit normal;
 // unoptimised by design.  method = rgc_regularization_method; guard (nullable): a tripped speculative-grid guard makes the kernels stand still
 void knn_cov6(hipStream_t s, const float4* P, const int* start, Grid g, int n, int k, int method, double* c6, const int* guard);
+// ... or, rgc_set_covariance_estimation(RGC_COV_RBF), the Gaussian-weighted moment of every point within max_dist (rgc_rbf.hip: semantics there).
+// reach: cells per axis a ball can span, reach_dist: the distance that bound was made for (rgcapi::rbf_reach)
+void rbf_cov6(hipStream_t s, const float4* P, const int* start, Grid g, int n, float kernel_width, float max_dist_sq, int reach, double reach_dist,
+              int method, double* c6, const int* guard);
 void voxel_build_general(hipStream_t s, const float4* P, const double* c6, const int* start, Grid g, int n, const int* cell_voxel, double* vox,
                          int* vox_cell, int multiplicative, const int* guard);
 void linearize_general(hipStream_t s, const float4* P, const double* c6, int n, Pose T, Grid g, const int* cell_voxel, const double* vox, int noff,

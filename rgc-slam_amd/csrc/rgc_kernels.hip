@@ -24,6 +24,7 @@
 #include "rgc_kernels.h"
 #include "rgc_nn.h"
 #include "rgc_lm.h"
+#include "rgc_cov.h"
 #include <hip/hip_ext.h>
 
 #include <limits.h>
@@ -621,36 +622,6 @@ __global__ void k_rank_gather(const float* __restrict__ in, int stride_f, int n,
 // Stands in for Eigen::JacobiSVD on the symmetric PSD neighbourhood covariance (fast_gicp_impl.hpp:273):
 // U diag(1,1,1e-3) V^T = I - 0.999 n n^T with n that eigenvector.
 // ------------------------------------------------------------------------------------------------
-// One Jacobi rotation in the (P,Q) plane, R = the third index.  Same rotation as the textbook two-sided product
-// A <- G^T A G (t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), theta = (a_qq - a_pp) / (2 a_pq)) written in its closed
-// form: only the five entries that change are touched, and t comes from ONE division and ONE square root
-// (t = 2 |a_pq| sgn(theta) / (|d| + sqrt(d^2 + 4 a_pq^2)), d = a_qq - a_pp) -- fp64 divisions and roots are ~15 VALU ops each
-// and this routine runs once per point of the map.
-template <int P, int Q, int R>
-__device__ __forceinline__ void jacobi_rot(double (&A)[3][3], double (&V)[3][3]) {
-  const double apq = A[P][Q];
-  if (apq == 0.0) return;
-  const double d = A[Q][Q] - A[P][P];
-  const bool pos = (d == 0.0) || ((d > 0.0) == (apq > 0.0));  // sign of theta, with theta = 0 counted positive
-  const double t = (pos ? 2.0 : -2.0) * fabs(apq) / (fabs(d) + sqrt(d * d + 4.0 * apq * apq));
-  const double c = rsqrt(t * t + 1.0), s = t * c;
-  const double tap = t * apq;
-  A[P][P] -= tap;
-  A[Q][Q] += tap;
-  A[P][Q] = 0.0;
-  A[Q][P] = 0.0;
-  const double arp = A[R][P], arq = A[R][Q];
-  const double nrp = c * arp - s * arq, nrq = s * arp + c * arq;
-  A[R][P] = nrp; A[P][R] = nrp;
-  A[R][Q] = nrq; A[Q][R] = nrq;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const double vkp = V[k][P], vkq = V[k][Q];
-    V[k][P] = c * vkp - s * vkq;
-    V[k][Q] = s * vkp + c * vkq;
-  }
-}
-
 __device__ __forceinline__ void min_eigenvector(const double S[6], double n[3]) {
   double A[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}};
   double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
@@ -2708,17 +2679,6 @@ k_voxel_cells_coop(const float4* __restrict__ P, double* __restrict__ nx, double
 constexpr int LIN_T = 256;
 int linearize_blocks(int n) { return (n + LIN_T - 1) / LIN_T; }
 
-__device__ __forceinline__ bool inv_sym3(const double S[6], double M[6]) {
-  const double a = S[0], b = S[1], c = S[2], d = S[3], e = S[4], f = S[5];
-  const double c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
-  const double det = a * c00 + b * c01 + c * c02;
-  if (det == 0.0) return false;
-  const double id = 1.0 / det;
-  M[0] = c00 * id; M[1] = c01 * id; M[2] = c02 * id;
-  M[3] = (a * f - c * c) * id; M[4] = (b * c - a * e) * id; M[5] = (a * d - b * b) * id;
-  return true;
-}
-
 __device__ __forceinline__ void neighbor_offset(int noff, int o, int& ox, int& oy, int& oz) {
   // fast_vgicp_voxel.hpp:10-44
   if (noff == 1) { ox = oy = oz = 0; return; }
@@ -3691,28 +3651,6 @@ __device__ __forceinline__ void quat_rot_d(const Quat& q, const double p[3], dou
   out[2] = p[2] + q.w * tz + (q.x * ty - q.y * tx);
 }
 
-// all three eigenpairs of a symmetric 3x3 (same cyclic Jacobi as min_eigenvector); ord[] = indices by DESCENDING eigenvalue
-__device__ __forceinline__ void eig3_sym(const double S[6], double ev[3], double (&V)[3][3], int ord[3]) {
-  double A[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}};
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-#pragma unroll
-    for (int b = 0; b < 3; b++) V[a][b] = a == b ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 60; sweep++) {
-    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-    const double diag = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-    if (off <= 1e-40 * diag || off == 0.0) break;
-    jacobi_rot<0, 1, 2>(A, V);
-    jacobi_rot<0, 2, 1>(A, V);
-    jacobi_rot<1, 2, 0>(A, V);
-  }
-  ev[0] = A[0][0]; ev[1] = A[1][1]; ev[2] = A[2][2];
-  ord[0] = 0; ord[1] = 1; ord[2] = 2;
-  for (int i = 0; i < 2; i++)
-    for (int j = i + 1; j < 3; j++)
-      if (ev[ord[j]] > ev[ord[i]]) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
-}
-
 // ---- the general covariance route (see GenOut above) ----
 // fast_gicp_impl.hpp:256-293 for one point: mean and covariance of its k neighbours (fp64; neighbours in ascending position, the order every
 // route of this file sums in), then the selected regularisation.  JacobiSVD of a symmetric positive semi-definite matrix is its
@@ -3731,33 +3669,7 @@ __device__ __forceinline__ void cov6_of(const float4* __restrict__ P, const int 
   }
   for (int a = 0; a < 6; a++) S[a] /= (double)k;                             // :262
   double C[6];
-  if (go.method == 0) {                                                       // NONE, :264-265
-    for (int a = 0; a < 6; a++) C[a] = S[a];
-  } else if (go.method == 4) {                                                // FROBENIUS, :266-271: (C_inv / |C_inv|_F)^-1 = |C_inv|_F (S + lambda I)
-    const double R[6] = {S[0] + 1e-3, S[1], S[2], S[3] + 1e-3, S[4], S[5] + 1e-3};
-    double Ci[6];
-    if (!inv_sym3(R, Ci)) { for (int a = 0; a < 6; a++) Ci[a] = 0.0; }
-    const double nrm = sqrt(Ci[0] * Ci[0] + Ci[3] * Ci[3] + Ci[5] * Ci[5] + 2.0 * (Ci[1] * Ci[1] + Ci[2] * Ci[2] + Ci[4] * Ci[4]));
-    for (int a = 0; a < 6; a++) C[a] = nrm * R[a];
-  } else {
-    double ev[3], V[3][3];
-    int ord[3];
-    eig3_sym(S, ev, V, ord);                                                  // :273, singular values in descending order
-    double val[3];
-    const double smax = ev[ord[0]];
-    for (int r = 0; r < 3; r++) {
-      const double sv = ev[ord[r]];
-      if (go.method == 3) val[r] = r < 2 ? 1.0 : 1e-3;                        // PLANE, :280-282
-      else if (go.method == 1) val[r] = sv > 1e-3 ? sv : 1e-3;                // MIN_EIG, :283-285
-      else { const double t = sv / smax; val[r] = t > 1e-3 ? t : 1e-3; }      // NORMALIZED_MIN_EIG, :286-289
-    }
-    for (int a = 0; a < 6; a++) C[a] = 0.0;
-    for (int r = 0; r < 3; r++) {                                             // U diag(values) V^T, :293
-      const int c = ord[r];
-      const double v0 = V[0][c], v1 = V[1][c], v2 = V[2][c], w = val[r];
-      C[0] += w * v0 * v0; C[1] += w * v0 * v1; C[2] += w * v0 * v2; C[3] += w * v1 * v1; C[4] += w * v1 * v2; C[5] += w * v2 * v2;
-    }
-  }
+  regularize6(S, go.method, C);
   for (int a = 0; a < 6; a++) go.c6[(size_t)a * go.n + i] = C[a];
 }
 

@@ -179,6 +179,24 @@ class FastVGICP:
         """FastVGICP::setVoxelAccumulationMode (fast_vgicp_impl.hpp:41-43); MULTIPLICATIVE runs on the general route"""
         self._chk(self._L.rgc_set_voxel_accumulation_mode(self._h, int(mode)))
 
+    class NearestNeighborMethod:
+        """fast_gicp::NearestNeighborMethod (fast_vgicp_cuda.hpp:21).  The first two both mean the exact kNN here."""
+        CPU_PARALLEL_KDTREE, GPU_BRUTEFORCE, GPU_RBF_KERNEL = range(3)
+
+    def setNearestNeighborSearchMethod(self, method: int):
+        """FastVGICPCuda::setNearestNeighborSearchMethod (fast_vgicp_cuda_impl.hpp:64-66).  GPU_RBF_KERNEL: a point's covariance is the
+        Gaussian-weighted moment of every point within setKernelWidth's max_dist (rgc_set_covariance_estimation in rgc_hip.h; the general
+        route); the other two: its k exact nearest neighbours.  Select BEFORE setting the clouds: a change drops them."""
+        m = int(method)
+        if m not in (0, 1, 2):
+            raise ValueError(f"setNearestNeighborSearchMethod: {method!r} is not a NearestNeighborMethod")
+        self._chk(self._L.rgc_set_covariance_estimation(self._h, 1 if m == self.NearestNeighborMethod.GPU_RBF_KERNEL else 0))
+
+    def setKernelWidth(self, kernel_width: float, max_dist: float = -1.0):
+        """FastVGICPCuda::setKernelWidth (fast_vgicp_cuda_impl.hpp:46-51): the factor of the RBF weight's exponent and the ball's radius;
+        max_dist <= 0 means 5 * kernel_width"""
+        self._chk(self._L.rgc_set_rbf_kernel(self._h, float(kernel_width), float(max_dist)))
+
     def setNeighbourReuse(self, mode: int):
         """rgc_set_knn_reuse: what the context keeps between the targets setInputTargetReframed prepares -- REUSE_NONE (every target is
         searched like a map the library has not seen: what a caller whose map's point set changes every frame pays anyway), REUSE_SEEDS
