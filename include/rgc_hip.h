@@ -482,6 +482,8 @@ typedef struct rgc_stats {
   int lazy_misses;                      /* lazy target: solves repeated on the completed map since the context was created */
   int searched_target;                  /* queries of the target's last preparation whose k neighbours were SEARCHED: n_target, or -- a map handed
                                          * over again by rgc_set_target_reframed, unchanged -- the few whose neighbour list carries no certificate */
+  int lm_fallbacks;                     /* solves whose one-launch (resident) LM gave up and that were solved again by the chained launches (same
+                                         * result) since the context was created: 0 unless the device was badly oversubscribed */
 } rgc_stats;
 RGC_API int rgc_get_stats(rgc_ctx* ctx, rgc_stats* out);
 

@@ -183,7 +183,7 @@ public:
   std::vector<double> getSourceCovariances() { std::vector<double> c((size_t)n_src_ * 9); chk(rgc_get_source_covariances(ctx_, c.data(), nullptr)); return c; }
   std::vector<double> getTargetCovariances() { std::vector<double> c((size_t)n_tgt_ * 9); chk(rgc_get_target_covariances(ctx_, c.data(), nullptr)); return c; }
   rgc_ctx* context() { return ctx_; }
-  rgc_stats stats() { rgc_stats st; chk(rgc_get_stats(ctx_, &st)); return st; }   // (lazy_misses: solves repeated on the completed map)
+  rgc_stats stats() { rgc_stats st{}; chk(rgc_get_stats(ctx_, &st)); return st; }   // (lazy_misses: solves repeated on the completed map)
 
 private:
   static void set_identity(float m[16]) { std::memset(m, 0, 16 * sizeof(float)); m[0] = m[5] = m[10] = m[15] = 1.f; }

@@ -114,7 +114,13 @@ int main(int argc, char** argv) {
     printf("{\"frames_per_pass\": %d, \"passes\": %d, \"knn_reuse\": %d, \"n_target\": %d, \"n_source\": %d, \"host_threads_available\": %u, \"runs\": [", frames, reps, reuse,
            seqs[0]->map.n, seqs[0]->scans[0].n, std::thread::hardware_concurrency());
     bool first = true;
+    auto fallbacks = [&] {   // solves whose resident LM launch gave up and that were repeated by the chained launches, all contexts, so far
+      long long f = 0;
+      for (auto& q : seqs) f += q->a->stats().lm_fallbacks + q->b->stats().lm_fallbacks;
+      return f;
+    };
     for (int S : S_list) {
+      const long long fb0 = fallbacks();
       Gate gate(S + 1);
       std::vector<std::thread> th;
       std::vector<double> per_seq_ms((size_t)S, 0.0);
@@ -139,7 +145,8 @@ int main(int argc, char** argv) {
         best = per_seq_ms[(size_t)s] < best ? per_seq_ms[(size_t)s] : best;
       }
       printf("%s{\"S\": %d, \"aggregate_scans_per_s\": %.3f, \"ms_per_frame_per_sequence_min\": %.4f, \"ms_per_frame_per_sequence_max\": %.4f, "
-             "\"poses_equal_each_sequence_alone\": %s}", first ? "" : ", ", S, (double)S * reps * frames / wall, best, worst, same ? "true" : "false");
+             "\"poses_equal_each_sequence_alone\": %s, \"lm_fallbacks\": %lld}", first ? "" : ", ", S, (double)S * reps * frames / wall, best, worst,
+             same ? "true" : "false", fallbacks() - fb0);
       first = false;
     }
     printf("]}\n");

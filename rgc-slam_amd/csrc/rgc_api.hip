@@ -1149,7 +1149,9 @@ int rgc_create(int hip_device, const rgc_params* params, rgc_ctx** out) {
   if (const char* e = getenv("RGC_JOIN_SPIN_US")) c->join_spin_us = atoi(e);
   if (const char* e = getenv("RGC_PREP_EVENT_EXT")) c->prep_event_ext = atoi(e) != 0;
   if (const char* e = getenv("RGC_COOP_STREAM")) c->coop_stream_on = atoi(e) != 0;
-  if (const char* e = getenv("RGC_LM_IMPL")) c->lm_host = strcmp(e, "host") == 0;
+  if (const char* e = getenv("RGC_LM_IMPL")) { c->lm_host = strcmp(e, "host") == 0; c->lm_chained = strcmp(e, "chained") == 0; }
+  if (const char* e = getenv("RGC_LM_GIVE_UP_AT")) c->lm_give_up_at = atoi(e);
+  if (hipDeviceGetAttribute(&c->cu_count, hipDeviceAttributeMultiprocessorCount, hip_device) != hipSuccess) c->cu_count = 0;
   if (!ok) { rgc_destroy(c); return RGC_ERR_HIP; }
   { std::lock_guard<std::mutex> lk(g_live_mutex); g_live.insert(c); }
   *out = c;
@@ -1435,10 +1437,11 @@ int rgc_num_correspondences(rgc_ctx* c, int* n) {
   return RGC_OK;
 }
 
-// One batch of blind LM steps (the first launch of a solve opens it), the fitness kernel behind them and the state's read-back:
-// enqueued, not waited for.
+// The solve's launches, enqueued and not waited for: the one resident launch (k_lm_solve) where that route is taken (`open` only: it runs a
+// solve from its opening to its posted result), otherwise one batch of blind LM steps (the first launch of a solve opens it), the fitness
+// kernel behind them and the state's read-back.
 static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, bool want_fitness) {
-  const int n = c->src.n, noff = noff_of(c->prm.neighbor_method);
+  const int n = c->src.n, noff = noff_of(c->prm.neighbor_method), nb_lm = rgck::linearize_blocks(n);
   hipStream_t s = c->solve_stream;  // see rgc_align_begin
   rgck::LmState* post = (c->post_on && c->d_post) ? c->d_post : nullptr;
   const int seq = want_fitness ? -c->lm_seq : c->lm_seq;  // what is posted: a finished state (> 0), or a finished state with its score (< 0)
@@ -1449,6 +1452,23 @@ static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, boo
   // No separate score launches, no blind steps between the deciding launch and the score.
   const bool fit_in_steps = want_fitness && !staged;
   if (open) c->lm_j = 0;
+  // The whole solve as ONE resident launch (k_lm_solve) wherever it has no more workgroups than the device has CUs and the result is posted; the
+  // chained launches otherwise: the stage-by-stage profiling pass, a scan of more rows than CUs, a context without mapped host memory, and
+  // RGC_LM_IMPL=chained -- and for any solve whose resident launch gave up (rgc_align_end).
+  c->lm_resident = open && !staged && !c->lm_chained && post && nb_lm <= c->cu_count && nb_lm <= rgck::kLmSolveMaxGroups;
+  if (c->lm_resident) {
+    rgck::lm_solve_resident(s, (const float4*)c->src.P.p, (const double*)c->src.nx.p, (const double*)c->src.ny.p, (const double*)c->src.nz.p, n,
+                            c->tgt.grid, (const int*)c->tgt.cell_voxel.p, (const double*)c->tgt.vox.p, noff, (int*)c->corr_v.p, (double*)c->corr_M.p,
+                            (int*)c->corr_v2.p, (double*)c->corr_M2.p, (double*)c->partials.p, (rgck::LmState*)c->lm_state.p, *open, c->d_small + 7,
+                            c->tgt.segs.p, c->src.segs.p, post, seq, fit_in_steps ? (const float4*)c->tgt.P.p : nullptr,
+                            fit_in_steps ? (const int*)c->tgt.start.p : nullptr, fit_in_steps ? (double*)c->fit_partials.p : nullptr, c->tgt.n,
+                            c->tgt.lazy == 2 ? (const int*)c->tgt.need.p : nullptr, c->tgt.need_stamp, c->tgt.lazy == 2 ? (const int*)c->tgt.segs.p + 1 : nullptr,
+                            fit_in_steps ? c->d_early : nullptr, c->lm_give_up_at);
+    c->lm_j = 1;  // the finished state is image 0
+    HIPCHK(c, hipEventRecord(c->lm_tail, s));
+    c->lm_tail_stream = s;
+    return RGC_OK;
+  }
   auto step = [&](const rgck::LmInit* op, hipStream_t on) {
     rgck::lm_step(on, (const float4*)c->src.P.p, (const double*)c->src.nx.p, (const double*)c->src.ny.p, (const double*)c->src.nz.p, n,
                   c->tgt.grid, (const int*)c->tgt.cell_voxel.p, (const double*)c->tgt.vox.p, noff, (int*)c->corr_v.p, (double*)c->corr_M.p,
@@ -1555,8 +1575,9 @@ int rgc_align_begin(rgc_ctx* c, const float guess[16], int want_fitness) {
   if ((rc = ensure(c, c->partials, sizeof(double) * (rgck::kAccum + 2) * (size_t)nb * 2))) return rc;  // (two halves: rgck::lm_step)
   if ((rc = ensure(c, c->ipartials, sizeof(int) * (size_t)nb))) return rc;
   if (!c->lm_state.p) {
-    if ((rc = ensure(c, c->lm_state, 4096))) return rc;
-    HIPCHK(c, hipMemsetAsync(c->lm_state.p, 0, 4096, c->solve_stream));  // the score's ticket and the lazy target's miss flag start at 0
+    if ((rc = ensure(c, c->lm_state, rgck::kLmAreaBytes))) return rc;
+    // the score's ticket, the lazy target's miss flag and the resident solve's flags and give-up word start at 0
+    HIPCHK(c, hipMemsetAsync(c->lm_state.p, 0, rgck::kLmAreaBytes, c->solve_stream));
   }
   if ((rc = ensure(c, c->fit_partials, sizeof(double) * (size_t)rgck::fitness_blocks(n) + 64))) return rc;
   rgck::LmInit in;
@@ -1576,9 +1597,15 @@ int rgc_align_begin(rgc_ctx* c, const float guess[16], int want_fitness) {
   if (c->lm_last_outer + 6 > batch) batch = c->lm_last_outer + 6;
   if (batch > P.max_iterations + 2) batch = P.max_iterations + 2;
   if (batch < 2) batch = 2;
-  c->lm_seq = c->lm_seq >= 0x3fffffff ? 1 : c->lm_seq + 1;
+  if (c->lm_seq >= 0x3fffffff) {  // the solve numbers start over: neither a flag of the resident solve nor its give-up word may carry an old one (rgck::k_lm_solve)
+    c->lm_seq = 0;
+    HIPCHK(c, hipMemsetAsync((char*)c->lm_state.p + 3080, 0, rgck::kLmAreaBytes - 3080, c->solve_stream));
+  }
+  c->lm_seq++;
   if (join_late && (rc = join_source(c))) return rc;
   if ((rc = lm_enqueue_batch(c, batch, &in, want_fitness != 0))) return rc;
+  c->pend.in = in;
+  c->pend.batch = batch;
   memcpy(c->pend.guess, guess, sizeof(c->pend.guess));
   c->pend.want_fitness = want_fitness != 0;
   c->pend.active = true;
@@ -1624,6 +1651,22 @@ int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fit
         memcpy(&S, c->h_post, sizeof(S));
       }
     }
+    if (!posted && c->lm_resident) {
+      // The resident launch has left without a result: a wait of one of its workgroups ran out (or RGC_LM_GIVE_UP_AT).  It touched nothing
+      // but its own rows, flags and correspondence buffers -- the frame's counters are put back by the workgroup that FINISHES a solve -- so
+      // the same solve, from its opening and with the same LmInit, goes out as chained launches: the same result, one frame's time later.
+      HIPCHK(c, hipStreamSynchronize(c->lm_tail_stream));
+      c->stats.lm_fallbacks++;
+      c->lm_resident = false;
+      const bool keep = c->lm_chained;
+      c->lm_chained = true;
+      // (workgroups that had reached the score before the others gave up have taken tickets nobody collected)
+      HIPCHK(c, hipMemsetAsync((char*)c->lm_state.p + 3076, 0, 4, c->solve_stream));
+      rc = lm_enqueue_batch(c, c->pend.batch, &c->pend.in, want_fitness);
+      c->lm_chained = keep;
+      if (rc) return rc;
+      continue;
+    }
     if (!posted) {
       HIPCHK(c, hipStreamSynchronize(c->lm_tail_stream));
       if (c->post_on && c->d_post) {  // (no copy was chained)
@@ -1643,7 +1686,7 @@ int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fit
   }
   c->src_pending = false;  // the solve came after the scan's preparation and has finished (its spare launches may still drain: lm_tail)
   c->main_has_target_prep = false;  // (the solve came after the map's preparation)
-  c->small_clean[0] = c->small_clean[1] = true;  // the solve's first step re-initialised both blocks after capturing them
+  c->small_clean[0] = c->small_clean[1] = true;  // the solve re-initialised both blocks after capturing them (chained: its first step; resident: the workgroup that finished it)
   {  // a cloud that did not fit its speculative grid: everything above ran on a parked cloud -- prepare it properly, solve again
     const int r = resolve_guards(c, S.pad & 0xff, (S.pad >> 8) & 0xff);
     if (r < 0) return r;

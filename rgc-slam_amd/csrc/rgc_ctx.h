@@ -27,7 +27,7 @@
 namespace rgcapi {
 
 // Build-time switches (RGC_EXTRA_FLAGS=-D...): alternative routes to the SAME results, kept for A/B measurements.  A caller's
-// process reads RGC_LM_IMPL, RGC_SPEC_GRID, RGC_KNN_SEEDS, RGC_KNN_CACHE (a context's initial rgc_set_knn_reuse mode), RGC_TRACE_ALLOC, RGC_TRACE_CACHE, RGC_CHECK_POINTERS,
+// process reads RGC_LM_IMPL, RGC_LM_GIVE_UP_AT, RGC_SPEC_GRID, RGC_KNN_SEEDS, RGC_KNN_CACHE (a context's initial rgc_set_knn_reuse mode), RGC_TRACE_ALLOC, RGC_TRACE_CACHE, RGC_CHECK_POINTERS,
 // RGC_FORCE_GENERAL (the odometer's settings on the general covariance route: a cross-check) and the
 // three scheduling switches RGC_JOIN_SPIN_US / RGC_PREP_EVENT_EXT / RGC_COOP_STREAM from the environment, once, in rgc_create.
 #ifndef RGC_LM_POST
@@ -189,12 +189,16 @@ struct rgc_ctx {
   hipEvent_t lm_tail = nullptr;    // recorded behind every batch of LM launches (and its copy into h_lm) on the stream they went to
   hipStream_t lm_tail_stream = nullptr;  // ... that stream: a solve enqueued on the OTHER stream waits for lm_tail first
   bool post_on = RGC_LM_POST != 0; // (build flag) 0: always wait for the stream and its copy, as in round 2
-  struct { bool active = false; bool want_fitness = false; float guess[16]; } pend;  // rgc_align_begin .. rgc_align_end
+  struct { bool active = false; bool want_fitness = false; float guess[16]; rgck::LmInit in; int batch = 0; } pend;  // rgc_align_begin .. rgc_align_end (in, batch: what a chained solve of the same problem opens with)
   struct { bool on = false; int rc = 0; float T[16]; double H[36]; double fitness = 0; int iterations = 0, converged = 0, lm_failed = 0; bool has_fit = false; } gen_res;  // general route: rgc_align_begin solves at once, rgc_align_end hands this over
   int lm_last_outer = 0;      // outer iterations of the previous solve: sizes the next blind batch
   bool small_clean[2] = {false, false};  // d_small block of the map / the scan holds its initial image (the last solve's first step restored it)
   hipStream_t solve_stream = nullptr;  // where the pending solve was enqueued (rgc_align_begin)
   bool solve_behind_map = RGC_SOLVE_BEHIND_MAP != 0;  // (build flag) 0: the solve always on the scan's (high-priority) stream, as in round 2
+  bool lm_chained = false;    // RGC_LM_IMPL=chained: the solve as a chain of step launches (k_lm_step), never as one resident launch (k_lm_solve)
+  int lm_give_up_at = -1;     // RGC_LM_GIVE_UP_AT=<try> (a test hook): the resident solve's workgroup 0 gives up at that try, without waiting
+  int cu_count = 0;           // the device's compute units: the resident solve runs with at most one workgroup per CU
+  bool lm_resident = false;   // the solve in flight went out as one resident launch
   bool lm_host = false;       // RGC_LM_IMPL=host: host-driven LM loop over the public fine-seam kernels (cross-check of the device-chained one)
   bool spec_on = true;        // RGC_SPEC_GRID=0 turns the speculative grid off
   bool coop_stream_on = RGC_COOP_STREAM != 0;  // (build flag; RGC_COOP_STREAM in the environment) the scan's deferred queries inside its bulk kNN launch

@@ -205,6 +205,20 @@ void lm_step(hipStream_t s, const float4* P, const double* nx, const double* ny,
              // raises LmState::pad2; lazy_counts: the lists' sizes, carried home in LmState::lazy_nq / lazy_ncell
              const int* lazy_need = nullptr, int lazy_stamp = 0, const int* lazy_counts = nullptr,
              LmEarly* h_early = nullptr /* mapped host memory (nullable): the deciding launch posts the final pose there before it scores it */);
+// The whole solve in ONE resident launch (see k_lm_solve): lm_step's arguments without a launch number; the finished state is left in image 0
+// (lm_image(st, 0)).  st is kLmAreaBytes long, zeroed once; the caller keeps linearize_blocks(n) <= min(the device's CU count,
+// kLmSolveMaxGroups) -- all of them resident at once -- and finds a solve that gave up (a bounded wait ran out; give_up_at >= 0: workgroup 0
+// at that try, without waiting) as a stream that drained with nothing posted.  seq != 0 always: its magnitude tags the hand-over's words.
+constexpr int kLmAreaBytes = 8192, kLmSolveMaxGroups = 512;
+// The longest a workgroup waits for the others' rows, in ticks of the 100 MHz wall clock: 2 ms.  The workgroups of a solve are placed as
+// CU slots free up, so a wait can last as long as the longest kernel that may hold the slots: the map's kNN launch of a c-main frame, ~165 us.
+// Twelve times that, and still a bound on what a lost frame costs (the chained solve that follows takes ~0.15 ms).
+constexpr unsigned long long kLmSolveWaitTicks = 200000;
+void lm_solve_resident(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Grid g, const int* cell_voxel,
+              const double* vox, int noff, int* corr_v0, double* corr_M0, int* corr_v1, double* corr_M1, double* partials, LmState* st,
+              const LmInit& open, const int* nvox, const void* segs_t, const void* segs_s, LmState* h_post, int seq, const float4* TP,
+              const int* tstart, double* fit_partials, int nt, const int* lazy_need, int lazy_stamp, const int* lazy_counts, LmEarly* h_early,
+              int give_up_at);
 // nt: the target's point count (a small map is scanned whole by the wave for a query its first cube does not settle; 0: never)
 void fitness_lm(hipStream_t s, const float4* SP, int ns, LmState* st, const float4* TP, const int* tstart, Grid g, double* partials,
                 LmState* h_post = nullptr, int seq = 0, int nt = 0);

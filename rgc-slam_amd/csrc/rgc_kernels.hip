@@ -2920,14 +2920,21 @@ __device__ __forceinline__ bool last_block_arrive(int* ticket) {
 // are fetched by block_fold_rows_load16 -- k_lm_step issues those loads together with its other loads at the top of the launch: one round
 // trip instead of one for the state and two for the rows -- any further ones eight at a time (a missing row is +0.0: no effect on a sum
 // that starts at +0.0).
-template <int NACC>
-__device__ __forceinline__ void block_fold_rows_load16(const double* __restrict__ partials, int nrows, double (&v)[16]) {
+// kWriteThrough: the rows were handed over INSIDE this launch (k_lm_solve): every load of them is an agent-scope relaxed atomic load
+// (sc1: past this CU's L1), which is what lets the hand-over do without an acquire; the order of the sums is the same.
+template <bool kWriteThrough>
+__device__ __forceinline__ double fold_row_load(const double* p) {
+  if constexpr (kWriteThrough) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else return *p;
+}
+template <int NACC, bool kWriteThrough = false>
+__device__ __forceinline__ void block_fold_rows_load16(const double* partials, int nrows, double (&v)[16]) {
   const int a = threadIdx.x & 31, gq = threadIdx.x >> 5;
 #pragma unroll
-  for (int u = 0; u < 16; u++) v[u] = (a < NACC && gq + 8 * u < nrows) ? partials[(size_t)(gq + 8 * u) * NACC + a] : 0.0;
+  for (int u = 0; u < 16; u++) v[u] = (a < NACC && gq + 8 * u < nrows) ? fold_row_load<kWriteThrough>(&partials[(size_t)(gq + 8 * u) * NACC + a]) : 0.0;
 }
-template <int NACC>
-__device__ __forceinline__ void block_fold_rows_pre(const double* __restrict__ partials, int nrows, const double (&v)[16], double* sh_out) {
+template <int NACC, bool kWriteThrough = false>
+__device__ __forceinline__ void block_fold_rows_pre(const double* partials, int nrows, const double (&v)[16], double* sh_out) {
   static_assert(NACC <= 32 && LIN_T == 256, "thread -> (accumulator, row group) mapping");
   __shared__ double grp[LIN_T / 32][32];
   const int a = threadIdx.x & 31, gq = threadIdx.x >> 5;
@@ -2938,7 +2945,7 @@ __device__ __forceinline__ void block_fold_rows_pre(const double* __restrict__ p
     for (int r0 = gq + 128; r0 < nrows; r0 += 64) {
       double w[8];
 #pragma unroll
-      for (int u = 0; u < 8; u++) w[u] = (r0 + 8 * u < nrows) ? partials[(size_t)(r0 + 8 * u) * NACC + a] : 0.0;
+      for (int u = 0; u < 8; u++) w[u] = (r0 + 8 * u < nrows) ? fold_row_load<kWriteThrough>(&partials[(size_t)(r0 + 8 * u) * NACC + a]) : 0.0;
 #pragma unroll
       for (int u = 0; u < 8; u++) s += w[u];
     }
@@ -3011,8 +3018,9 @@ __device__ __forceinline__ void reinit_small_blocks(const int* nvox) {
 }
 
 // The fresh state of a solve (:53-63) plus the frame's counters, on a zeroed image (k_lm_step's opening launch, lane 0 of workgroup 0).
-__device__ __forceinline__ void lm_state_open(LmState& ls, const LmInit& in, const int* __restrict__ nvox, const int* __restrict__ def_t,
-                                              const int* __restrict__ def_s) {
+// reinit: put the counters' blocks back at once (k_lm_solve does it itself when the solve has finished)
+__device__ __forceinline__ void lm_state_open(LmState& ls, const LmInit& in, const int* nvox, const int* __restrict__ def_t,
+                                              const int* __restrict__ def_s, bool reinit = true) {
 #pragma unroll
   for (int a = 0; a < 16; a++) ls.x0[a] = in.x0[a];
   ls.lambda = -1.0;  // :56
@@ -3029,7 +3037,7 @@ __device__ __forceinline__ void lm_state_open(LmState& ls, const LmInit& in, con
   ls.def_t = def_t ? *def_t : 0;
   ls.def_s = def_s ? *def_s : 0;
   ls.src_sq = nvox ? __int_as_float(nvox[16]) : 0.f;  // d_small[23]
-  if (nvox) reinit_small_blocks(nvox);
+  if (nvox && reinit) reinit_small_blocks(nvox);
 }
 
 // The decision the sums of one launch call for, taken by lane 0 of a workgroup on its LDS copy `ls` of the state the launch ran from:
@@ -3190,6 +3198,25 @@ __device__ __forceinline__ void step_fitness_rows(const float4* __restrict__ SP,
 static_assert(2 * sizeof(LmState) <= 3072, "two state images in front of the area's loose words");
 __device__ __forceinline__ int* lm_area_miss(LmState* st) { return reinterpret_cast<int*>(reinterpret_cast<char*>(st) + 3072); }
 __device__ __forceinline__ int* lm_area_ticket(LmState* st) { return reinterpret_cast<int*>(reinterpret_cast<char*>(st) + 3076); }
+// ... and, behind the first 4096 bytes (kLmAreaBytes in all, zeroed once with them), what the resident solve (k_lm_solve) hands over with:
+//   +3080  its give-up word: the number of the solve a workgroup gave up on (a wait ran out, or RGC_LM_GIVE_UP_AT)
+//   +4096  one 64-bit flag per workgroup, {solve number, try number}: written by that workgroup alone
+__device__ __forceinline__ unsigned* lm_area_give_up(LmState* st) { return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(st) + 3080); }
+__device__ __forceinline__ unsigned long long* lm_area_flags(LmState* st) { return reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(st) + 4096); }
+static_assert(kLmAreaBytes >= 4096 + 8 * kLmSolveMaxGroups, "a flag per workgroup of the resident solve");
+
+// The final pose of a finished solve (LDS state `ls`) into mapped host memory, then the solve's number: the whole workgroup takes part.
+__device__ __forceinline__ void post_early_pose(const LmState& ls, LmEarly* early, int* miss, int gen) {
+  int* hw = reinterpret_cast<int*>(early);
+  const int* sw = reinterpret_cast<const int*>(ls.x0);
+  if (threadIdx.x < 32) __hip_atomic_store(&hw[threadIdx.x], sw[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (threadIdx.x == 32) __hip_atomic_store(&early->pad, ls.pad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (threadIdx.x == 33) __hip_atomic_store(&early->pad2, __hip_atomic_load(miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (threadIdx.x == 34) __hip_atomic_store(&early->outer, ls.outer, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  __syncthreads();
+  if (threadIdx.x == 0) __hip_atomic_store(&early->gen, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // One launch of the device-chained LM, launch number j of its solve (the host counts; 0 opens the solve).
 //
@@ -3297,15 +3324,7 @@ k_lm_step(const float4* __restrict__ P, const double* __restrict__ nx, const dou
         if (fa.early && blockIdx.x == 0 && !was_done) {
           // ... the final POSE first (every linearisation of this solve ran in an earlier launch: the guards and the lazy target's miss flag
           // are final too): whoever needs only the pose to go on does not wait for the score
-          int* hw = reinterpret_cast<int*>(fa.early);
-          const int* sw = reinterpret_cast<const int*>(ls.x0);
-          if (threadIdx.x < 32) __hip_atomic_store(&hw[threadIdx.x], sw[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          if (threadIdx.x == 32) __hip_atomic_store(&fa.early->pad, ls.pad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          if (threadIdx.x == 33) __hip_atomic_store(&fa.early->pad2, __hip_atomic_load(miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          if (threadIdx.x == 34) __hip_atomic_store(&fa.early->outer, ls.outer, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-          __syncthreads();
-          if (threadIdx.x == 0) __hip_atomic_store(&fa.early->gen, seq < 0 ? -seq : seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+          post_early_pose(ls, fa.early, miss, seq < 0 ? -seq : seq);
 #ifdef RGC_LAB_TURN
           if (threadIdx.x == 0) { const unsigned long long now = wall_clock64(); atomicExch(&g_lab_turn[3], now); atomicAdd(&g_lab_turn[5], now - lab_turn_t0); }
 #endif
@@ -3360,6 +3379,167 @@ k_lm_step(const float4* __restrict__ P, const double* __restrict__ nx, const dou
   block_reduce_store<kStepAcc>(acc, rows_out + (size_t)blockIdx.x * kStepAcc);  // (read by the NEXT launch: plain stores)
   LAB_TS_MIN(2);
   if (j > 0 && blockIdx.x == 0) store_image(sn);
+}
+
+
+// ---- the same state machine in ONE launch: k_lm_solve ----
+// The workgroups of a k_lm_step launch, their points, rows, fold and decision, but resident for the whole solve: the state stays in LDS,
+// and the only thing that crosses workgroups between two tries are the rows.  Workgroup b stores its row write-through (sc1), every
+// storing wave drains vmcnt, a workgroup barrier, then one lane stores the workgroup's OWN flag word {solve, try}; one wave per workgroup
+// polls everybody's flags (lane g: workgroup g, g + 64, ...) with relaxed agent-scope loads and s_sleep until all show this try, and
+// every load of a row after that is an sc1 load as well (block_fold_rows_*<.., true>): no fence in the loop, no word with two writers
+// (cdna_hip_programming.md G16, the write-through form).  Rows alternate between the two halves by try parity: a workgroup writes try
+// t + 2's row only after it has seen every flag at t + 1, when every workgroup has folded try t's rows.  Flags carry the solve's number,
+// so nothing is reset between solves.
+//
+// Every wait is bounded by wall clock (kLmSolveWaitTicks).  A workgroup whose wait runs out writes the solve's number into the give-up
+// word, marks image 0 (cmd = -1) and leaves; every waiting loop watches that word and leaves likewise.  Nothing is posted then and the
+// frame's counters are untouched (they are put back by the workgroup that finishes the solve, not by the one that opens it): the host
+// finds a drained stream without a result and solves again through the chained launches.  give_up_at >= 0 (RGC_LM_GIVE_UP_AT, a test
+// hook): workgroup 0 takes that way out at that try without waiting.
+//
+// false: this workgroup leaves the solve.
+__device__ __forceinline__ bool lm_solve_hand_over(LmState* st, unsigned solve, unsigned t, bool give_up_now) {
+  __shared__ int go_s;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's row stores (sc1) have reached memory
+  __syncthreads();
+  if (threadIdx.x < WAVE) {
+    unsigned long long* const flags = lm_area_flags(st);
+    unsigned* const give_up = lm_area_give_up(st);
+    const int lane = threadIdx.x, G = (int)gridDim.x;
+    bool go = false, expired = give_up_now;
+    if (!give_up_now) {
+      if (lane == 0) __hip_atomic_store(&flags[blockIdx.x], ((unsigned long long)solve << 32) | t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long t0 = wall_clock64();
+      for (;;) {
+        bool here = true;
+        for (int b = lane; b < G; b += WAVE) {
+          const unsigned long long f = __hip_atomic_load(&flags[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          here = here && (unsigned)(f >> 32) == solve && (unsigned)f >= t;  // (a faster workgroup may already show t + 1)
+        }
+        const unsigned gu = lane == WAVE - 1 ? __hip_atomic_load(give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~solve;
+        if (__any(gu == solve)) break;
+        if (__all(here)) { go = true; break; }
+        if (wall_clock64() - t0 > kLmSolveWaitTicks) { expired = true; break; }
+        __builtin_amdgcn_s_sleep(2);
+      }
+    }
+    if (expired && lane == 0) {
+      __hip_atomic_store(give_up, solve, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&st[0].cmd, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (lane == 0) go_s = go ? 1 : 0;
+  }
+  __syncthreads();  // (also keeps the row loads behind the poll: a barrier is not crossed by memory operations)
+  return go_s != 0;
+}
+
+__global__ void __launch_bounds__(LIN_T)
+k_lm_solve(const float4* __restrict__ P, const double* __restrict__ nx, const double* __restrict__ ny, const double* __restrict__ nz, int n, Grid g,
+           const int* __restrict__ cell_voxel, const double* __restrict__ vox, int noff, int* corr_v0, double* corr_M0, int* corr_v1, double* corr_M1,
+           double* partials, LmState* st, LmInit in, const int* nvox, const int* __restrict__ def_t, const int* __restrict__ def_s,
+           LmState* __restrict__ h_post, int seq, FitArgs fa, int give_up_at) {
+  wave_prio(2);
+  constexpr int kStateWords = (int)(sizeof(LmState) / sizeof(int));
+  __shared__ LmState ls;
+  __shared__ double folded[kStepAcc];
+  const unsigned solve = (unsigned)(seq < 0 ? -seq : seq);
+  int* const miss = lm_area_miss(st);
+  const int i = blockIdx.x * LIN_T + threadIdx.x;
+  float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
+  double pn0 = 0.0, pn1 = 0.0, pn2 = 0.0;
+  if (i < n) { pp = P[i]; pn0 = nx[i]; pn1 = ny[i]; pn2 = nz[i]; }
+  {  // the fresh state (:53-63), in every workgroup
+    int* lw = reinterpret_cast<int*>(&ls);
+    for (int u = threadIdx.x; u < kStateWords; u += LIN_T) lw[u] = 0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      lm_state_open(ls, in, nvox, def_t, def_s, /*reinit=*/false);
+      ls.lazy_nq = fa.counts ? fa.counts[0] : 0;
+      ls.lazy_ncell = fa.counts ? fa.counts[1] : 0;
+      ls.mode = LM_MODE_LIN;
+      if (in.max_outer <= 0) ls.done = 1;  // max_iterations <= 0: the guess is the answer
+    }
+    __syncthreads();
+  }
+  const bool was_done = in.max_outer <= 0;
+  if (!was_done) {
+    // every decision but the opening one consumes a cost evaluation (at most max_outer * max_inner of them) and an outer iteration has at
+    // most one linearisation of its own: the control flow ends the loop long before this count does
+    const long long max_tries = (long long)in.max_outer * ((in.max_inner > 0 ? in.max_inner : 1) + 1) + 2;
+    long long t = 0;
+    for (; t < max_tries; t++) {
+#ifdef RGC_LAB
+      // (developer build: workgroup 0's clock at the top of its first 13 tries, in the slots lm_step_decide's own stamps -- 5, 6, 7 -- leave)
+      if (blockIdx.x == 0 && threadIdx.x == 0 && t < 13) g_lab_ts[t < 5 ? t : t + 3] = wall_clock64();
+#endif
+      // ---- this try's per-point work (k_lm_step's, at the pose the last decision arrived at) ----
+      const int mode = ls.mode, cur = ls.cur;
+      const bool final_try = mode != LM_MODE_LIN && lm_is_converged(ls.delta, ls.rot_eps, ls.trans_eps);
+      int* cv_cur = cur ? corr_v1 : corr_v0;
+      double* cm_cur = cur ? corr_M1 : corr_M0;
+      int* cv_nxt = cur ? corr_v0 : corr_v1;
+      double* cm_nxt = cur ? corr_M0 : corr_M1;
+      double acc[kStepAcc];
+#pragma unroll
+      for (int a = 0; a < kStepAcc; a++) acc[a] = 0.0;
+      if (mode != LM_MODE_LIN && i < n) acc[kAccum + 1] = error_point_pre(pp, i, n, ls.xi, vox, noff, cv_cur, cm_cur);
+      if (mode != LM_MODE_B && !final_try) {
+        Pose T;
+        lm_load_pose(mode == LM_MODE_LIN ? ls.x0 : ls.xi, T);
+        double lin[kAccum];
+#pragma unroll
+        for (int a = 0; a < kAccum; a++) lin[a] = 0.0;
+        int ncorr = 0;
+        if (i < n) linearize_point_pre(pp, pn0, pn1, pn2, i, n, T, g, cell_voxel, vox, noff, mode == LM_MODE_LIN ? cv_cur : cv_nxt,
+                                       mode == LM_MODE_LIN ? cm_cur : cm_nxt, 1, lin, ncorr, fa.need ? miss : nullptr, fa.need, fa.stamp);
+#pragma unroll
+        for (int a = 0; a < kAccum; a++) acc[a] = lin[a];
+        acc[kAccum] = (double)ncorr;
+      }
+      double* const rows = partials + (size_t)(t & 1) * gridDim.x * kStepAcc;
+      block_reduce_store<kStepAcc, true>(acc, rows + (size_t)blockIdx.x * kStepAcc);
+      if (!lm_solve_hand_over(st, solve, (unsigned)t, blockIdx.x == 0 && t == give_up_at)) return;
+      // ---- everybody's rows, the fixed-order fold and the decision, in every workgroup ----
+      double rv[16];
+      block_fold_rows_load16<kStepAcc, true>(rows, gridDim.x, rv);
+      block_fold_rows_pre<kStepAcc, true>(rows, gridDim.x, rv, folded);
+      if (threadIdx.x == 0) {
+        bool took_xi = false;
+        lm_step_decide(ls, folded, ls.mode, ls.cur, &took_xi);
+      }
+      __syncthreads();
+      if (ls.done) break;
+    }
+    if (t >= max_tries) return;  // (never: nothing is posted, the host solves again)
+  }
+  // ---- the solve is over: the early pose, the score, the state (k_lm_step's closing launch) ----
+  const bool score = fa.on != 0;
+  if (score) {
+    if (fa.early && blockIdx.x == 0 && !was_done) post_early_pose(ls, fa.early, miss, (int)solve);
+    step_fitness_rows(P, n, ls.x0, g, fa);
+    if (!last_block_arrive(lm_area_ticket(st))) return;
+    if (threadIdx.x < WAVE) {
+      const double f = fitness_fold(fa.partials, fitness_blocks_dev(n));
+      if (threadIdx.x == 0) { ls.fit_sum = f; ls.has_fit = 1; }
+    }
+  } else if (blockIdx.x != 0) {
+    return;
+  }
+  if (threadIdx.x == 0) {
+    if (!was_done) {
+      ls.pad2 = __hip_atomic_load(miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(miss, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (nvox) reinit_small_blocks(nvox);  // every workgroup has captured the counters (each passed a hand-over or the score's ticket since)
+  }
+  __syncthreads();
+  {
+    const int* lw = reinterpret_cast<const int*>(&ls);
+    int* gw = reinterpret_cast<int*>(st);  // image 0: lm_image(st, 0)
+    for (int u = threadIdx.x; u < kStateWords; u += LIN_T) gw[u] = lw[u];
+  }
+  if (h_post && (seq > 0 || ls.has_fit)) post_state_to_host(&ls, h_post, (int)solve, LIN_T, false);
 }
 
 // fold per-block rows in a fixed order: block a (one wave) owns accumulator a; lane l sums rows l, l+64, ...
@@ -4312,6 +4492,15 @@ void lm_step(hipStream_t s, const float4* P, const double* nx, const double* ny,
   const FitArgs fa{TP, tstart, fit_partials, fitness_scan_all(nt), (TP && tstart && fit_partials) ? 1 : 0, lazy_need, lazy_stamp, lazy_counts, h_early};
   hipLaunchKernelGGL(k_lm_step, dim3(linearize_blocks(n)), dim3(LIN_T), 0, s, P, nx, ny, nz, n, g, cell_voxel, vox, noff, corr_v0, corr_M0, corr_v1,
                      corr_M1, partials, st, j, (j == 0 && open) ? *open : LmInit{}, nvox, (const int*)segs_t, (const int*)segs_s, h_post, seq, fa);
+}
+void lm_solve_resident(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Grid g, const int* cell_voxel,
+              const double* vox, int noff, int* corr_v0, double* corr_M0, int* corr_v1, double* corr_M1, double* partials, LmState* st,
+              const LmInit& open, const int* nvox, const void* segs_t, const void* segs_s, LmState* h_post, int seq, const float4* TP,
+              const int* tstart, double* fit_partials, int nt, const int* lazy_need, int lazy_stamp, const int* lazy_counts, LmEarly* h_early,
+              int give_up_at) {
+  const FitArgs fa{TP, tstart, fit_partials, fitness_scan_all(nt), (TP && tstart && fit_partials) ? 1 : 0, lazy_need, lazy_stamp, lazy_counts, h_early};
+  hipLaunchKernelGGL(k_lm_solve, dim3(linearize_blocks(n)), dim3(LIN_T), 0, s, P, nx, ny, nz, n, g, cell_voxel, vox, noff, corr_v0, corr_M0, corr_v1,
+                     corr_M1, partials, st, open, nvox, (const int*)segs_t, (const int*)segs_s, h_post, seq, fa, give_up_at);
 }
 void fitness_lm(hipStream_t s, const float4* SP, int ns, LmState* st, const float4* TP, const int* tstart, Grid g, double* partials, LmState* h_post,
                 int seq, int nt) {
