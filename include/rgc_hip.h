@@ -708,6 +708,84 @@ RGC_API int rgc_mapreg_set_maps_device(rgc_ctx* ctx, const float* d_corner, int 
 RGC_API int rgc_icp_align_device(rgc_ctx* ctx, const float* d_source, int n_source, const float* d_target, int n_target, int stride_bytes,
                                  const rgc_icp_params* params, float final_T[16], rgc_icp_result* result);
 
+/* ---- 4-DoF pose-graph optimisation over the keyframe store's key poses: PoseGraphOptimize4DoF (src/RGC_mapping.cpp:2303-2466) with
+ * FourDOFError / AngleLocalParameterization (src/lidarFactor.hpp:490-595), the link between f4's drift matrix and f5's poses ----
+ * For the selected keyframes IN THE CALLER'S ORDER (positions 0 .. N-1: copy_cloudKeyPoses6D's order, ids = its intensity):
+ *   State (:2352-2358), fp64 from the store's float pose, rad2deg = 180.0 / M_PI (:197): yaw_k = (double)yaw * rad2deg in DEGREES and
+ * t_k = (double)(x, y, z) are the 4 unknowns of position k; pitch_k, roll_k (likewise) are constants (the yaw block has size 1, :2361).
+ *   Odometry edge (:2367-2373), one per position i >= 1, from i - 1: m = q_from^-1 (t_i - t_from) with q_from of the reference's chain (as
+ * rgc_kf_assemble uses it), rel_yaw = yaw_i - yaw_from NOT normalised, pitch_from, roll_from -- built from the store's poses themselves.
+ *   Loop edge (:2376-2392) from key_loop to key_curr: m = t_loop_curr, rel_yaw = yaw_loop_curr_deg (R2ypr(q_loop_curr).x), pitch / roll those
+ * of keyPose6DLoop as recorded at detection.  A loop is USED when both its ids are selected and key_curr is not at position 0 (the `continue`
+ * at :2364 precedes :2376); every other loop is ignored and counted.  "Both ids are selected" REPLACES the reference's membership test in
+ * correctedKeyPose6DByLoop (:2338, 2386: the poses of the previous optimisation, which this library does not keep).  Unlike the reference's
+ * loopInfoContainer (a map keyed by key_curr) several loops may end at one keyframe; at most RGC_PGO_MAX_LOOPS used loops (the reference
+ * holds 100, :2110-2113).
+ *   Residual of an edge i -> j (src/lidarFactor.hpp:557-595), NULL loss, cost = 1/2 sum |r|^2:  r[0..2] = R(yaw_i, pitch, roll)^T (t_j - t_i) - m
+ * with YawPitchRollToRotationMatrix (:517-533, degrees in), r[3] = NormalizeAngle(yaw_j - yaw_i - rel_yaw) (:490-499: one wrap at +-180,
+ * derivative 1).  Jacobians analytic: d r[0..2] / d yaw_i = (pi / 180) (dR/dyaw)^T (t_j - t_i), d r[3] / d yaw_i = -1, d r[0..2] / d t_i = -R^T,
+ * d r[3] / d yaw_j = +1, d r[0..2] / d t_j = R^T.
+ *   Gauge (:2325-2344, 2404-2414): the keyframe with the smallest key_loop id among the used loops is constant, all four parameters.  With no
+ * used loop nothing is optimised and no pose changes (RGC_PGO_NO_LOOP; :2308, 2415-2419).
+ *   Solve (:2423-2427): Ceres' trust-region LM as rgc_mapreg_optimize restates it, in dimension 4 (N - 1): damping clamp(diag H, 1e-6, 1e32) /
+ * radius, a step is accepted above rho = 1e-3, the same radius update and the same four stops (gradient 1e-10, function 1e-6, parameter 1e-8
+ * over the free parameters, radius 1e-32); a damped system that is not positive definite counts as a rejected step.  Plus is
+ * NormalizeAngle(yaw + delta) on the yaw (:501-515), additive on t.  Ceres' Jacobi scaling is not restated (as in rgc_mapreg_optimize: parity
+ * unpinned).  Every iteration linearises and solves the sparse system on the device, directly (nested dissection of the chain), in
+ * fp64 with every sum in a fixed order: results are bit-identical from run to run.  The LM decisions are taken on the host.
+ *   Write-back (:2450-2462): x, y, z = (float)t, yaw = (float)(yaw_deg * deg2rad); pitch and roll stay as stored, bit for bit.  The
+ * reference's "loop pose changed by > 0.01" bail-out (:2441-2447) guards a Ceres defect; the constant node cannot move here, it is not reproduced.
+ *   State machine: like the other rgc_kf_* calls these touch the store's poses and buffers of their own; with a solve in flight
+ * (rgc_align_begin .. rgc_align_end) they RUN and the solve's result is what it would have been. */
+enum { RGC_PGO_OPTIMIZED = 0, RGC_PGO_NO_LOOP = 1 };
+enum { RGC_PGO_STOP_CAP = 0, RGC_PGO_STOP_GRADIENT = 1, RGC_PGO_STOP_FUNCTION = 2, RGC_PGO_STOP_PARAMETER = 3, RGC_PGO_STOP_RADIUS = 4 };
+#define RGC_PGO_MAX_LOOPS 128
+typedef struct rgc_pgo_loop {
+  int key_curr, key_loop;          /* loopInfo::key_curr, key_loop (:2101-2102) */
+  double t_loop_curr[3];           /* loopInfo::t_loop_curr (:2105) */
+  double yaw_loop_curr_deg;        /* Utility::R2ypr(q_loop_curr.toRotationMatrix()).x() (:2389-2390) */
+  double pitch_loop_deg, roll_loop_deg; /* keyPose6DLoop.pitch / roll * rad2deg (:2391) */
+} rgc_pgo_loop;
+typedef struct rgc_pgo_params {
+  int max_iterations;              /* options.max_num_iterations (10, :2425) */
+  double initial_radius;           /* ceres::Solver::Options::initial_trust_region_radius (1e4) */
+} rgc_pgo_params;
+typedef struct rgc_pgo_report {
+  int status;                      /* RGC_PGO_OPTIMIZED | RGC_PGO_NO_LOOP */
+  int n_nodes, n_odom, n_loops_used, n_loops_ignored;
+  int fixed_id;                    /* oldestLoopKey (:2322-2344), -1 under RGC_PGO_NO_LOOP */
+  int iterations, successful;      /* LM iterations run, accepted steps */
+  int stop;                        /* RGC_PGO_STOP_* */
+  unsigned accepted_mask;          /* bit k: the step of iteration k was accepted */
+  double initial_cost, final_cost; /* 1/2 sum |r|^2 before / after */
+} rgc_pgo_report;
+RGC_API void rgc_default_pgo_params(rgc_pgo_params* p);
+/* host only: the edge a loop-closure ICP gives (:2086-2107).  T_loop_correct = T_w_loop^-1 * T_drift * T_w_latest in fp32 with
+ * pclPointToAffine3f (:2614-2617: pcl::getTransformation) of the two key poses and T_drift = rgc_icp_align's final_T (row-major 4x4);
+ * t_loop_curr = its translation, yaw_loop_curr_deg = R2ypr of its linear part (widened to fp64), pitch / roll = the loop pose's * rad2deg.
+ * (T_w_loop^-1 is formed as [R^T | -R^T t]; the reference's Eigen general inverse and its rotation() differ from that by fp32 rounding.) */
+RGC_API int rgc_pgo_make_loop(const rgc_kf_pose* latest_pose, const rgc_kf_pose* loop_pose, const float T_drift[16], int key_curr, int key_loop,
+                              rgc_pgo_loop* out);
+/* reads the poses of ids[0 .. n_ids) from the keyframe store and optimises them.  params: NULL = defaults.  out_poses (nullable): the n_ids
+ * corrected poses (the stored ones under RGC_PGO_NO_LOOP).  apply != 0 and RGC_PGO_OPTIMIZED: they are written back as rgc_kf_set_poses does,
+ * all or nothing, the revision bumped once.  RGC_ERR_INVALID, nothing changed: an unknown or repeated id, n_ids < 1, a loop from a keyframe to
+ * itself, more than RGC_PGO_MAX_LOOPS used loops, non-finite loop data, max_iterations outside 0..32 (accepted_mask has one bit per iteration: its
+ * 32 bits are the only reason for that limit), a radius that is not positive. */
+RGC_API int rgc_pgo_optimize(rgc_ctx* ctx, const int* ids, int n_ids, const rgc_pgo_loop* loops, int n_loops, const rgc_pgo_params* params,
+                             int apply, rgc_kf_pose* out_poses, rgc_pgo_report* report);
+/* what one LM iteration of rgc_pgo_optimize sees, read out (the counterpart of rgc_mapreg_linearize); every output is nullable.  The same
+ * selection and loops; x_eval (nullable: the store's state): 4 n_ids doubles {yaw_deg, t} per position -- the edges are always built from the
+ * store's poses.  Edges: the n_ids - 1 odometry edges first, then the used loops in the order given; edge_ij 2 ints (positions i, j),
+ * edge_meas 6 doubles {m[3], rel_yaw, pitch, roll}, residuals 4 doubles per edge.  g: 4 n_ids (the constant node's rows zero).  H as 4x4
+ * row-major blocks: H_diag n_ids of them, H_chain n_ids - 1 (block k: rows of position k, columns of k + 1, the odometry edge's term),
+ * H_loop one per used loop (rows of key_loop's position, columns of key_curr's; that loop's term alone, also where two loops join the same
+ * pair or the pair are neighbours -- the solve adds them onto the chain's block).  d (4 n_ids): the LM step of the system damped at radius,
+ * written when radius > 0 and a loop is used.  report: status, counts and fixed_id; initial_cost = final_cost = the cost.  A damped system that is not
+ * positive definite (a numerical condition, reported with the argument errors' code) is RGC_ERR_INVALID; on any error no output is written. */
+RGC_API int rgc_pgo_linearize(rgc_ctx* ctx, const int* ids, int n_ids, const rgc_pgo_loop* loops, int n_loops, const double* x_eval, double radius,
+                              int* edge_ij, double* edge_meas, double* residuals, double* g, double* cost, double* H_diag, double* H_chain,
+                              double* H_loop, double* d, rgc_pgo_report* report);
+
 /* ---- NDT registration (P2D / D2D) on a Gaussian voxel map: fast_gicp::NDTCuda (include/fast_gicp/ndt/ndt_cuda.hpp:27-60,
  * include/fast_gicp/ndt/impl/ndt_cuda_impl.hpp:10-90, src/fast_gicp/cuda/ndt_cuda.cu:13-177, src/fast_gicp/cuda/ndt_compute_derivatives.cu:33-231), the one
  * registration of the vendored tree whose only body is CUDA ----

@@ -114,6 +114,27 @@ class KfInfo(C.Structure):
 KF_CORNER, KF_SURF, KF_SCAN, KF_KINDS = 0, 1, 2, 3
 
 
+class PgoLoop(C.Structure):
+    """rgc_pgo_loop: one loop edge of the 4-DoF pose graph (key_loop -> key_curr)"""
+    _fields_ = [("key_curr", C.c_int), ("key_loop", C.c_int), ("t_loop_curr", C.c_double * 3), ("yaw_loop_curr_deg", C.c_double),
+                ("pitch_loop_deg", C.c_double), ("roll_loop_deg", C.c_double)]
+
+
+class PgoParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("initial_radius", C.c_double)]
+
+
+class PgoReport(C.Structure):
+    _fields_ = [("status", C.c_int), ("n_nodes", C.c_int), ("n_odom", C.c_int), ("n_loops_used", C.c_int), ("n_loops_ignored", C.c_int),
+                ("fixed_id", C.c_int), ("iterations", C.c_int), ("successful", C.c_int), ("stop", C.c_int), ("accepted_mask", C.c_uint),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+
+PGO_OPTIMIZED, PGO_NO_LOOP = 0, 1
+PGO_STOP_CAP, PGO_STOP_GRADIENT, PGO_STOP_FUNCTION, PGO_STOP_PARAMETER, PGO_STOP_RADIUS = range(5)
+PGO_MAX_LOOPS = 128
+
+
 class VgRoute(C.Structure):
     """rgc_vg_route: what the last leaf filter on a context did (rgc_voxelgrid_route)"""
     _fields_ = [("path", C.c_int), ("status", C.c_int), ("repeated", C.c_int), ("kept_box", C.c_int), ("kept_flags", C.c_int), ("box_invalidated", C.c_int),
@@ -150,6 +171,7 @@ SYMBOLS = [
     "rgc_get_stats", "rgc_device_alloc", "rgc_device_free", "rgc_host_alloc", "rgc_host_free", "rgc_upload", "rgc_download", "rgc_synchronize",
     "rgc_stream", "rgc_default_fe_params", "rgc_frontend", "rgc_extract_pose", "rgc_imu_preintegrate", "rgc_imu_filter_init", "rgc_imu_filter_push", "rgc_ground_gate_init", "rgc_ground_gate_remember", "rgc_ground_gate_step", "rgc_default_fuse_in", "rgc_fuse_pose", "rgc_compose_pose",
     "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_mapreg_linearize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_kf_reset", "rgc_kf_push", "rgc_kf_set_poses", "rgc_kf_get_info", "rgc_kf_assemble", "rgc_mapreg_set_maps_device", "rgc_icp_align_device",
+    "rgc_default_pgo_params", "rgc_pgo_make_loop", "rgc_pgo_optimize", "rgc_pgo_linearize",
     "rgc_default_ndt_params", "rgc_ndt_set_params", "rgc_ndt_get_params", "rgc_ndt_set_target", "rgc_ndt_set_source", "rgc_ndt_set_target_device", "rgc_ndt_set_source_device", "rgc_ndt_clear_source", "rgc_ndt_clear_target", "rgc_ndt_swap_source_and_target", "rgc_ndt_linearize", "rgc_ndt_compute_error", "rgc_ndt_num_correspondences", "rgc_ndt_align", "rgc_ndt_get_voxels", "rgc_ndt_get_raw_covariances",
     "rgc_gicp_set_max_correspondence_distance", "rgc_gicp_get_max_correspondence_distance", "rgc_gicp_linearize", "rgc_gicp_compute_error", "rgc_gicp_num_correspondences", "rgc_gicp_get_correspondences", "rgc_gicp_align",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
@@ -330,6 +352,11 @@ def load():
     L.rgc_kf_assemble.argtypes = [vp, ip, C.c_int, C.c_uint, C.c_float, vp, C.c_int, C.c_int, ip, ip]
     L.rgc_mapreg_set_maps_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int]
     L.rgc_icp_align_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(IcpParams), fp, C.POINTER(IcpResult)]
+    L.rgc_default_pgo_params.argtypes = [C.POINTER(PgoParams)]
+    L.rgc_default_pgo_params.restype = None
+    L.rgc_pgo_make_loop.argtypes = [C.POINTER(KfPose), C.POINTER(KfPose), fp, C.c_int, C.c_int, C.POINTER(PgoLoop)]
+    L.rgc_pgo_optimize.argtypes = [vp, ip, C.c_int, C.POINTER(PgoLoop), C.c_int, C.POINTER(PgoParams), C.c_int, C.POINTER(KfPose), C.POINTER(PgoReport)]
+    L.rgc_pgo_linearize.argtypes = [vp, ip, C.c_int, C.POINTER(PgoLoop), C.c_int, dp, C.c_double, ip, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(PgoReport)]
     L.rgc_default_ndt_params.argtypes = [C.POINTER(NdtParams)]
     L.rgc_default_ndt_params.restype = None
     L.rgc_ndt_set_params.argtypes = [vp, C.POINTER(NdtParams)]

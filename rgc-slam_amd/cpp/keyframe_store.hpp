@@ -8,6 +8,8 @@
 //   store.setPoses(ids, poses);                            // correctKeyFramePoseGraph (:1618-1686)
 //   rgc::DeviceCloud target = store.assembleDevice(ids, rgc::KeyframeStore::CORNER | rgc::KeyframeStore::SURF, 0.4f);
 //   rgc_icp_align_device(ctx, source.data(), source.size(), target.data(), target.size(), 16, &icp_params, T, &result);
+//   loops.push_back(rgc::makeLoop(latestPose, loopPose, T, latestId, loopId));            // the loop edge of :2086-2107
+//   rgc_pgo_report rep = store.optimizePoseGraph(ids, loops);                             // PoseGraphOptimize4DoF (:2303-2466): the poses are corrected
 //
 // Errors throw std::runtime_error carrying rgc_last_error().  No CPU fallback.
 #pragma once
@@ -50,6 +52,13 @@ private:
   int n_ = 0, n_raw_ = 0;
 };
 
+// the loop edge a loop-closure ICP gives (rgc_pgo_make_loop): the two key poses as they were when it ran, its final transformation (row-major 4x4)
+inline rgc_pgo_loop makeLoop(const rgc_kf_pose& latest_pose, const rgc_kf_pose& loop_pose, const float T_drift[16], int key_curr, int key_loop) {
+  rgc_pgo_loop l;
+  if (rgc_pgo_make_loop(&latest_pose, &loop_pose, T_drift, key_curr, key_loop, &l) != RGC_OK) throw std::runtime_error("rgc::makeLoop: a pose or the drift is not finite");
+  return l;
+}
+
 class KeyframeStore {
 public:
   enum Kind : unsigned { CORNER = 1u << RGC_KF_CORNER, SURF = 1u << RGC_KF_SURF, SCAN = 1u << RGC_KF_SCAN };
@@ -89,6 +98,17 @@ public:
     chk(rgc_kf_set_poses(ctx_, ids.data(), poses.data(), (int)ids.size()));
   }
   rgc_kf_info info() { rgc_kf_info i; chk(rgc_kf_get_info(ctx_, &i)); return i; }
+
+  // PoseGraphOptimize4DoF (:2303-2466) over the keyframes `ids` in that order; apply: the store's poses are corrected (all or nothing);
+  // corrected (nullable): the ids.size() corrected poses either way; params (nullable): Ceres' iteration cap and initial radius
+  rgc_pgo_report optimizePoseGraph(const std::vector<int>& ids, const std::vector<rgc_pgo_loop>& loops, bool apply = true,
+                                   std::vector<rgc_kf_pose>* corrected = nullptr, const rgc_pgo_params* params = nullptr) {
+    rgc_pgo_report rep;
+    if (corrected) corrected->resize(ids.size());
+    chk(rgc_pgo_optimize(ctx_, ids.data(), (int)ids.size(), loops.empty() ? nullptr : loops.data(), (int)loops.size(), params, apply ? 1 : 0,
+                         corrected && !ids.empty() ? corrected->data() : nullptr, &rep));
+    return rep;
+  }
 
   // the selection's point count before the filter (nothing runs on the device)
   int rawSize(const std::vector<int>& ids, unsigned kind_mask) {

@@ -1192,6 +1192,7 @@ void rgc_destroy(rgc_ctx* c) {
   if (c->h_vg) (void)hipHostFree(c->h_vg);
   for (DevBuf* b : {&c->kf_store[0], &c->kf_store[1], &c->kf_store[2], &c->kf_table, &c->kf_raw, &c->kf_filt}) release(*b);
   if (c->kf_h_table) (void)hipHostFree(c->kf_h_table);
+  for (DevBuf* b : {&c->pgo_i, &c->pgo_d, &c->pgo_M}) release(*b);
   release_cloud(c->ndt_cl[0]);
   release_cloud(c->ndt_cl[1]);
   for (DevBuf* b : {&c->ndt_offs, &c->ndt_corr, &c->ndt_partials, &c->ndt_ipartials, &c->ndt_small, &c->ndt_out}) release(*b);

@@ -281,6 +281,9 @@ struct rgc_ctx {
   size_t kf_h_cap = 0;
   hipEvent_t kf_uploaded = nullptr;        // recorded behind the table's copy: the staging is rewritten only after it
   bool kf_upload_pending = false;
+  // the 4-DoF pose graph over the store's key poses (rgc_pgo_*): buffers of its own -- the graph's index tables, every double array of a solve
+  // (two evaluations: the accepted state and the candidate), the separators' dense system
+  DevBuf pgo_i, pgo_d, pgo_M;
   // NDT registration (rgc_ndt_*): two clouds of its own (0 target, 1 source) with their grids and voxel maps (Cloud::cell_voxel / vox / vox_cell,
   // records of rgck::kNdtRec doubles), the offsets of the neighbour method, the frozen term list of the last linearisation
   rgc_ndt_params ndt_prm{1.0, RGC_NDT_D2D, RGC_NDT_DIRECT7, 0.0};

@@ -168,6 +168,52 @@ extern "C" {
 void rgc_R2ypr(const double R[9], double ypr_deg[3]) { if (R && ypr_deg) R2ypr(R, ypr_deg); }
 void rgc_ypr2R(const double ypr_deg[3], double R[9]) { if (ypr_deg && R) ypr2R(ypr_deg, R); }
 
+// the loop edge of the 4-DoF pose graph from a loop-closure ICP's drift (src/RGC_mapping.cpp:2086-2107), fp32 as the reference's Affine3f
+int rgc_pgo_make_loop(const rgc_kf_pose* latest_pose, const rgc_kf_pose* loop_pose, const float T_drift[16], int key_curr, int key_loop, rgc_pgo_loop* out) {
+  if (!latest_pose || !loop_pose || !T_drift || !out) return RGC_ERR_INVALID;
+  for (int i = 0; i < 16; i++)
+    if (!std::isfinite(T_drift[i])) return RGC_ERR_INVALID;
+  auto affine = [](const rgc_kf_pose& p, float T[12]) -> bool {  // pcl::getTransformation(x, y, z, roll, pitch, yaw), :2614-2617
+    const float v[6] = {p.x, p.y, p.z, p.roll, p.pitch, p.yaw};
+    for (float a : v)
+      if (!std::isfinite(a)) return false;
+    const float A = std::cos(p.yaw), B = std::sin(p.yaw), C = std::cos(p.pitch), D = std::sin(p.pitch), E = std::cos(p.roll), F = std::sin(p.roll);
+    const float DE = D * E, DF = D * F;
+    T[0] = A * C; T[1] = A * DF - B * E; T[2] = B * F + A * DE; T[3] = p.x;
+    T[4] = B * C; T[5] = A * E + B * DF; T[6] = B * DE - A * F; T[7] = p.y;
+    T[8] = -D;    T[9] = C * F;          T[10] = C * E;         T[11] = p.z;
+    return true;
+  };
+  auto mul = [](const float X[12], const float Y[12], float Z[12]) {  // affine product, rows of 4
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) {
+        float s = X[r * 4] * Y[c] + X[r * 4 + 1] * Y[4 + c] + X[r * 4 + 2] * Y[8 + c];
+        if (c == 3) s += X[r * 4 + 3];
+        Z[r * 4 + c] = s;
+      }
+  };
+  float Tl[12], Tw[12], Td[12], Tc[12], Ti[12], Tlc[12];
+  if (!affine(*latest_pose, Tl) || !affine(*loop_pose, Tw)) return RGC_ERR_INVALID;
+  for (int i = 0; i < 12; i++) Td[i] = T_drift[i];
+  mul(Td, Tl, Tc);                                     // T_w_correct = T_Drift * T_w_latest, :2094
+  for (int r = 0; r < 3; r++) {                        // T_w_loop.inverse(), :2098
+    for (int c = 0; c < 3; c++) Ti[r * 4 + c] = Tw[c * 4 + r];
+    Ti[r * 4 + 3] = -(Tw[r] * Tw[3] + Tw[4 + r] * Tw[7] + Tw[8 + r] * Tw[11]);
+  }
+  mul(Ti, Tc, Tlc);                                    // T_loop_correct
+  double R[9], ypr[3];
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) R[r * 3 + c] = (double)Tlc[r * 4 + c];
+  R2ypr(R, ypr);
+  const double rad2deg = 180.0 / M_PI;
+  out->key_curr = key_curr; out->key_loop = key_loop;
+  for (int a = 0; a < 3; a++) out->t_loop_curr[a] = (double)Tlc[a * 4 + 3];
+  out->yaw_loop_curr_deg = ypr[0];
+  out->pitch_loop_deg = loop_pose->pitch * rad2deg;    // keyPose6DLoop.pitch * rad2deg, :2391
+  out->roll_loop_deg = loop_pose->roll * rad2deg;
+  return RGC_OK;
+}
+
 // B1  vg_ICP::IMU_preintegration / IMU_preintegration2 over the samples of one sweep
 // (src/RGC_odometer.cpp:883-931, 1418-1438).  stamps/gyr/acc: the vectors getIMUInterval returns (:1376-1416).
 int rgc_imu_preintegrate(const double* stamps, const double* gyr3, const double* acc3, int n, double prev_time, double cur_time,

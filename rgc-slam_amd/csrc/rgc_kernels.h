@@ -261,6 +261,26 @@ void transform_q(hipStream_t s, const float* in, int stride_f, int n, Quat q, co
 constexpr int kKfBlock = 256;
 struct KfSegment { const float4* src; int n; int out0; Quat q; double t[3]; };
 void kf_assemble(hipStream_t s, const KfSegment* seg, const int* blk0, int nseg, int nblocks, float4* out);
+// ---- 4-DoF pose graph over the key poses (rgc_pgo.hip; PoseGraphOptimize4DoF, src/RGC_mapping.cpp:2303-2466) ----
+// The graph on the device.  Positions 0 .. n_nodes - 1, 4 unknowns each {yaw in degrees, t}; edges: the n_nodes - 1 odometry edges e = n
+// (n -> n + 1), then the used loops; ij: 2 ints per edge, meas: 6 doubles per edge {m[3], rel_yaw, pitch, roll}; fixed: the constant
+// position or -1.  inc_start[n_nodes + 1] / inc: per node its loops in ascending order (loop * 2 + side, side 1 = the node is the edge's j).
+// sep[n_sep]: the separators in ascending order (sep[0] = 0), sep_of[n_nodes]: a position's index in sep or -1.
+constexpr int kPgoBlock = 256, kPgoDenseBlock = 1024;
+constexpr int kPgoTerm = 64;     // doubles per edge record (k_pgo_edges)
+constexpr int kPgoWs = 52;       // doubles per position kept between k_pgo_segments and k_pgo_backsub
+constexpr int kPgoSlot = 56;     // doubles per segment handed to k_pgo_dense
+constexpr int kPgoMaxSep = 384;  // separators the dense stage takes (its two LDS vectors: 2 x 4 x kPgoMaxSep doubles)
+struct PgoGraph { int n_nodes, n_edges, fixed, n_sep; const int *ij, *inc_start, *inc, *sep, *sep_of; const double* meas; };
+// residuals, Jacobian products (terms: kPgoTerm doubles per edge), the diagonal blocks D (16 per node) and g (4 per node), out2 = {cost, max |g|}
+void pgo_evaluate(hipStream_t s, const PgoGraph& G, const double* x, double* terms, double* D, double* g, double* out2);
+// d (4 per node) of (H + clamp(diag H, 1e-6, 1e32) / radius) d = -g; ws: kPgoWs doubles per node, slots: kPgoSlot per separator, M: (4 n_sep)^2
+// doubles; flag[0] is raised (never cleared) where the system is not positive definite
+void pgo_solve(hipStream_t s, const PgoGraph& G, const double* terms, const double* D, const double* g, double radius, double* ws, double* slots, double* M, double* d,
+               int* flag);
+// x_new = Plus(x, d); out3 = {model decrease, |d|^2, |x_new|^2 over the free parameters}; part: 4 doubles per node
+void pgo_step(hipStream_t s, const PgoGraph& G, const double* terms, const double* D, const double* g, const double* x, const double* d, double* x_new, double* part,
+              double* out3);
 // ---- NDT registration on a Gaussian voxel map (rgc_ndt.hip; fast_gicp::NDTCuda, src/fast_gicp/cuda/ndt_cuda.cu) ----
 // voxel record = kNdtRec doubles: mean(3), covariance after MIN_EIG (6: xx xy xz yy yz zz), number of points, its inverse (6), the covariance
 // before MIN_EIG (6), two unused.  The voxels are those of the grid's occupied cells (cell_voxel / vox_cell as for the VGICP map).

@@ -132,6 +132,15 @@ class KeyframeStore:
         self._chk(self._L.rgc_kf_get_info(self._h, C.byref(i)))
         return dict(n_keyframes=i.n_keyframes, n_points=list(i.n_points), revision=i.revision)
 
+    def optimize_pose_graph(self, ids, loops, apply=True, max_iterations=None, initial_radius=None):
+        """PoseGraphOptimize4DoF (src/RGC_mapping.cpp:2303-2466) over the keyframes ``ids`` in one call: ``loops`` are ``_lib.PgoLoop`` records
+        (``pose_graph.make_loop`` turns a loop-closure ICP's drift into one).  Returns (report dict, corrected poses (n, 6) float32); with
+        ``apply`` the store's poses are corrected."""
+        from .pose_graph import PoseGraph4DoF
+        graph = PoseGraph4DoF(self)
+        graph.loops = list(loops)
+        return graph.optimize(ids, apply=apply, max_iterations=max_iterations, initial_radius=initial_radius)
+
     @staticmethod
     def kind_mask(kinds) -> int:
         if isinstance(kinds, (int, np.integer)):
