@@ -206,6 +206,7 @@ static int map_wide_r_of(const rgc_ctx* c, const Cloud& cl) {
 static rgck::KnnSeeds cloud_seeds(const Cloud& cl, bool is_target);
 
 static int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox = false) {
+  if (!is_target && &cl == &c->src) { c->src_held = c->src_hold_pending; c->src_hold_pending = false; }  // was THIS scan held? (the same contexts may run a frame at a time later)
   const int n = cl.n;
   cl.covs_user = false;
   if (is_target && &cl == &c->tgt) {
@@ -525,6 +526,19 @@ static int rbf_reach(const rgck::Grid& g, double max_dist, double* reach_dist) {
   return r < (double)dmax ? (int)r : dmax;  // (also when r is infinite)
 }
 
+// The deferred list's entry words as the launches that resolve the deferred queries themselves need them on entry (coop_stream): "empty".
+// The WHOLE allocation is filled, once: the buffer keeps its head-room from cloud to cloud, and a larger cloud that still fits it has its
+// entries where a smaller one's launches never wrote.  The readers put "empty" back, so the words stay clean until a plain list is
+// written over them (slots_clean = false).
+static int slots_make_clean(rgc_ctx* c, Cloud& cl, hipStream_t s) {
+  if (cl.slots_clean && cl.slots_seen == cl.segs.p && cl.slots_cap == cl.segs.cap) return RGC_OK;  // (a new allocation may come back at the old address)
+  HIPCHK(c, hipMemsetAsync((int*)cl.segs.p + 16, rgck::kDeferredSlotEmptyByte, cl.segs.cap - 16 * sizeof(int), s));
+  cl.slots_clean = true;
+  cl.slots_seen = cl.segs.p;
+  cl.slots_cap = cl.segs.cap;
+  return RGC_OK;
+}
+
 // C2 / C3 of a cloud whose grid is built: exact-kNN covariances (+ the Gaussian voxel map for the target), enqueued on the cloud's stream.
 static int cloud_covariances(rgc_ctx* c, Cloud& cl, bool is_target) {
   const int n = cl.n, k = c->prm.k_correspondences;
@@ -560,7 +574,7 @@ static int cloud_covariances(rgc_ctx* c, Cloud& cl, bool is_target) {
     // (the deferred-list counter is zeroed by the grid build and stays zero: no query is deferred on this route)
     return RGC_OK;
   }
-  bool stream_coop = false;
+  bool stream_coop = false, fused = false;
   {
     // a sparse map (points per cell of its grid below map_wide_density): the wider block, see k_knn_sp_wide
     const int wide_r = is_target ? map_wide_r_of(c, cl) : 0;
@@ -580,25 +594,48 @@ static int cloud_covariances(rgc_ctx* c, Cloud& cl, bool is_target) {
       own.points = n;
     }
     const rgck::KnnSeeds seeds = cloud_seeds(cl, is_target);
-    if (is_target) cl.slots_clean = false;
+    // The dense map's launch over the whole map also builds the voxel records of its workgroups' own cells and resolves its deferred
+    // queries in-launch (rgck::VoxFuse; voxel_seams behind it) -- unless the stage-by-stage profile wants the voxel or the cooperative
+    // stage apart, or RGC_VOXEL_IMPL=separate.  A target shared or bound to the rolling map keeps the stages apart as well.
+    rgck::VoxFuse vf{};
+    const bool stage_prof = c->prof_on && (((c->prof_mask >> RGC_K_VOXEL) & 1u) || ((c->prof_mask >> RGC_K_KNN_COOP) & 1u));
+    // Nor, unless RGC_VOXEL_IMPL=fused, a context whose last scan was not held behind another context's target (rgc_hold_source_until_target_of:
+    // a pipelined sequence).  There the scan is prepared on the second stream BESIDE this launch, and its one-wave search (154 VGPRs: 160
+    // allocated) gets onto a SIMD when ONE of the map's five 88-register waves retires (72 + 88 free) -- with the cooperative waves inlined
+    // the map's kernel allocates 96, two must retire, and the scan's search took 160 us instead of 91: a frame one at a time 11 % slower
+    // (EXPERIMENTS.md round 16).  A pipelined context prepares its scan under the other context's solve, not beside its own map's search.
+    const bool want = c->voxel_impl == 2 || (c->voxel_impl == 0 && c->src_held);
+    fused = is_target && &cl == &c->tgt && !c->tgt_owner && !c->map_bound && want && !stage_prof && k <= 32 &&
+            rgck::knn_bulk_fuses_voxels(true, n, k, wide_r, nullptr, seeds);
+    if (fused) {
+      int rc;
+      const size_t vmax = (size_t)(n < cl.grid.ncell ? n : cl.grid.ncell);  // (the launch writes the voxel records: allocated here, not below)
+      if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kVoxRec * vmax))) return rc;
+      if ((rc = ensure(c, cl.vox_cell, sizeof(int) * vmax))) return rc;
+      if ((rc = slots_make_clean(c, cl, s))) return rc;  // the entry words "empty" on entry: filled once per allocation, the last reader puts it back
+      vf = rgck::VoxFuse{(const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p,
+                         cl.deferred_seen >= 0 ? cl.deferred_seen + cl.deferred_seen / 4 + 32 : n / 64 + 32};
+    } else if (is_target) {
+      cl.slots_clean = false;
+    }
     if (self_timed) {
       rgck::knn_bulk(s, is_target, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, cl.segs.p, (double*)cl.nx.p, (double*)cl.ny.p,
-                     (double*)cl.nz.p, cl.spec_used ? dsm + 6 : nullptr, wide_r, own.a, own.b, nullptr, nullptr, 0, seeds);
+                     (double*)cl.nz.p, cl.spec_used ? dsm + 6 : nullptr, wide_r, own.a, own.b, nullptr, nullptr, 0, seeds, 0, fused ? &vf : nullptr);
       c->prof_open.push_back(own);
     } else {
       // the scan: its deferred queries are resolved by the last workgroups of the same launch (coop_stream) -- unless the stage-by-stage
       // profile wants the two apart.  The entry words must be "empty" on entry: filled once per allocation, the readers put it back.
       const int coop_waves_s = cl.deferred_seen >= 0 ? cl.deferred_seen + cl.deferred_seen / 4 + 32 : n / 64 + 32;
       stream_coop = !is_target && c->coop_stream_on && k <= 32 && !(c->prof_on && ((c->prof_mask >> RGC_K_KNN_COOP_SRC) & 1u));
-      if (stream_coop && (!cl.slots_clean || cl.slots_seen != cl.segs.p)) {
-        HIPCHK(c, hipMemsetAsync((int*)cl.segs.p + 16, rgck::kDeferredSlotEmptyByte, sizeof(int) * 2 * (size_t)n, s));
-        cl.slots_clean = true;
-        cl.slots_seen = cl.segs.p;
+      if (stream_coop) {
+        int rc = slots_make_clean(c, cl, s);
+        if (rc) return rc;
       }
-      if (!stream_coop) cl.slots_clean = false;  // (the plain list will be written over the slots; a cloud can change roles: rgc_swap_source_and_target)
+      if (!stream_coop && !fused) cl.slots_clean = false;  // (the plain list will be written over the slots; a cloud can change roles: rgc_swap_source_and_target)
       ProfScope ps(c, kind, n, s);
       rgck::knn_bulk(s, is_target, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, cl.segs.p, (double*)cl.nx.p, (double*)cl.ny.p,
-                     (double*)cl.nz.p, cl.spec_used ? dsm + 6 : nullptr, wide_r, nullptr, nullptr, nullptr, nullptr, 0, seeds, stream_coop ? coop_waves_s : 0);
+                     (double*)cl.nz.p, cl.spec_used ? dsm + 6 : nullptr, wide_r, nullptr, nullptr, nullptr, nullptr, 0, seeds, stream_coop ? coop_waves_s : 0,
+                     fused ? &vf : nullptr);
     }
     if (is_target) cl.cache_searched_lists = seeds.cache.nbr && seeds.warm && wide_r == 0;
     if (seeds.seed && wide_r == 0) {
@@ -609,7 +646,7 @@ static int cloud_covariances(rgc_ctx* c, Cloud& cl, bool is_target) {
   // The map's deferred queries (~100 of a million, one wave each: 20 us of latency) are resolved in the SAME launch as the voxel map's
   // build (k_voxel_build_coop); the few voxels that hold one are recomputed behind it (k_voxel_patch).  The scan has no voxel map:
   // its chain stays serial.
-  const bool coop_beside = is_target;
+  const bool coop_beside = is_target;  // (`fused`: inside the bulk launch itself, and the voxel map with them; k_voxel_seams below finishes it)
   // grid of the cooperative launch: twice the deferred count of the previous cloud prepared here (consecutive clouds of a sequence
   // defer about the same queries), n / 64 for the first one
   const int coop_waves = cl.deferred_seen >= 0 ? cl.deferred_seen + cl.deferred_seen / 4 + 32 : n / 64 + 32;
@@ -624,7 +661,12 @@ static int cloud_covariances(rgc_ctx* c, Cloud& cl, bool is_target) {
     if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kVoxRec * vmax))) return rc;
     if ((rc = ensure(c, cl.vox_cell, sizeof(int) * vmax))) return rc;
     ProfScope ps(c, RGC_K_VOXEL, n);
-    {
+    if (fused) {
+      rgck::voxel_seams(s, (const float4*)cl.P.p, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p, (const int*)cl.start.p, cl.grid, n,
+                        cl.segs.p, (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p, cl.spec_used ? dsm + 6 : nullptr,
+                        cl.deferred_seen >= 0 ? 2 * cl.deferred_seen + 64 : n, c->prep_event_ext ? c->tgt_prepared : nullptr);
+      cl.prepared_recorded = c->prep_event_ext;
+    } else {
       rgck::voxel_build_coop(s, (const float4*)cl.P.p, (double*)cl.nx.p, (double*)cl.ny.p, (double*)cl.nz.p, (const int*)cl.start.p, cl.grid, n,
                              (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p, k, cl.segs.p, cl.spec_used ? dsm + 6 : nullptr, coop_waves,
                              cloud_seeds(cl, true));
@@ -669,6 +711,7 @@ static int lazy_build(rgc_ctx* c, const float guess[16]) {
                   (const int*)cl.start.p, (int*)cl.qlist.p, (int*)cl.cell_list.p, counts, guard);
   const int q_est = cl.lazy_nq_seen >= 0 ? cl.lazy_nq_seen + cl.lazy_nq_seen / 4 + 4096 : n;
   const int c_est = cl.lazy_ncell_seen >= 0 ? cl.lazy_ncell_seen + cl.lazy_ncell_seen / 4 + 1024 : n / 8 + 1024;
+  cl.slots_clean = false;  // (the plain deferred list is written over the entry words)
   {
     ProfScope ps(c, RGC_K_KNN_COV, n, s);
     rgck::knn_bulk(s, true, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, cl.segs.p, (double*)cl.nx.p, (double*)cl.ny.p, (double*)cl.nz.p,
@@ -694,7 +737,7 @@ static int lazy_build(rgc_ctx* c, const float guess[16]) {
 static int complete_target(rgc_ctx* c) {
   Cloud& cl = c->tgt;
   if (!cl.ready || cl.lazy == 0 || c->tgt_owner) return RGC_OK;
-  HIPCHK(c, hipMemsetAsync(cl.segs.p, 0, sizeof(int), c->stream));  // the deferred-query counter of the bulk launch
+  HIPCHK(c, hipMemsetAsync(cl.segs.p, 0, 3 * sizeof(int), c->stream));  // the deferred-query counter of the bulk launch, and the lazy lists' sizes behind it (the launch's count-out word)
   int rc = cloud_covariances(c, cl, true);
   if (rc) return rc;
   HIPCHK(c, hipGetLastError());
@@ -1149,6 +1192,7 @@ int rgc_create(int hip_device, const rgc_params* params, rgc_ctx** out) {
   if (const char* e = getenv("RGC_JOIN_SPIN_US")) c->join_spin_us = atoi(e);
   if (const char* e = getenv("RGC_PREP_EVENT_EXT")) c->prep_event_ext = atoi(e) != 0;
   if (const char* e = getenv("RGC_COOP_STREAM")) c->coop_stream_on = atoi(e) != 0;
+  if (const char* e = getenv("RGC_VOXEL_IMPL")) c->voxel_impl = strcmp(e, "separate") == 0 ? 1 : (strcmp(e, "fused") == 0 ? 2 : 0);
   if (const char* e = getenv("RGC_LM_IMPL")) { c->lm_host = strcmp(e, "host") == 0; c->lm_chained = strcmp(e, "chained") == 0; }
   if (const char* e = getenv("RGC_LM_GIVE_UP_AT")) c->lm_give_up_at = atoi(e);
   if (hipDeviceGetAttribute(&c->cu_count, hipDeviceAttributeMultiprocessorCount, hip_device) != hipSuccess) c->cu_count = 0;
@@ -1416,6 +1460,7 @@ int rgc_hold_source_until_target_of(rgc_ctx* c, rgc_ctx* other) {
   HIPCHK(c, hipSetDevice(c->device));
   // the scan's stream waits for the end of other's latest target preparation (a wait on an event nobody recorded yet is no wait)
   HIPCHK(c, hipStreamWaitEvent(c->stream2, other->tgt_prepared, 0));
+  c->src_hold_pending = true;  // (a pipelined sequence: the scan set next is not prepared beside this context's own map's search, cloud_covariances)
   return RGC_OK;
 }
 
@@ -2106,6 +2151,8 @@ RGC_API int rgc_lab_declines(rgc_ctx*, int* out16) { rgck::lab_declines(out16); 
 RGC_API int rgc_lab_iters(rgc_ctx*, unsigned long long* out8) { rgck::lab_iters(out8); return RGC_OK; }
 RGC_API int rgc_lab_wave_ts(rgc_ctx* c, long long* out16384) { (void)hipStreamSynchronize(c->stream); rgck::lab_wave_ts(out16384, c->stream2); return RGC_OK; }
 // developer build only (-DRGC_LAB): the deferred-query list of a cloud as the bulk kNN kernel left it
+// (a plain list only: a launch that resolved its deferred queries itself -- the scan's coop_stream, the map's k_knn_sp_vox -- leaves "empty"
+// words where idx / thr would be; the count is right either way.  RGC_COOP_STREAM=0 / RGC_VOXEL_IMPL=separate give the lists.)
 RGC_API int rgc_lab_deferred(rgc_ctx* c, int is_target, int* idx, float* thr, int cap, int* count) {
   Cloud& cl = is_target ? c->tgt : c->src;
   HIPCHK(c, hipStreamSynchronize(c->stream2));

@@ -27,7 +27,7 @@
 namespace rgcapi {
 
 // Build-time switches (RGC_EXTRA_FLAGS=-D...): alternative routes to the SAME results, kept for A/B measurements.  A caller's
-// process reads RGC_LM_IMPL, RGC_LM_GIVE_UP_AT, RGC_SPEC_GRID, RGC_KNN_SEEDS, RGC_KNN_CACHE (a context's initial rgc_set_knn_reuse mode), RGC_TRACE_ALLOC, RGC_TRACE_CACHE, RGC_CHECK_POINTERS,
+// process reads RGC_LM_IMPL, RGC_VOXEL_IMPL, RGC_LM_GIVE_UP_AT, RGC_SPEC_GRID, RGC_KNN_SEEDS, RGC_KNN_CACHE (a context's initial rgc_set_knn_reuse mode), RGC_TRACE_ALLOC, RGC_TRACE_CACHE, RGC_CHECK_POINTERS,
 // RGC_FORCE_GENERAL (the odometer's settings on the general covariance route: a cross-check) and the
 // three scheduling switches RGC_JOIN_SPIN_US / RGC_PREP_EVENT_EXT / RGC_COOP_STREAM from the environment, once, in rgc_create.
 #ifndef RGC_LM_POST
@@ -124,8 +124,9 @@ struct Cloud {
   int cache_e2_low = 0;     // frames in a row whose coordinates stayed below it
   int cache_e2_low_max = 0; // ... and the largest exponent among them
   int todo_cap = 0;
-  bool slots_clean = false;        // segs' entry words hold the "empty slot" pattern (the scan's deferred queries resolved inside its bulk launch)
+  bool slots_clean = false;        // segs' entry words hold the "empty slot" pattern (the scan's deferred queries resolved inside its bulk launch, and the dense map's)
   const void* slots_seen = nullptr;  // ... of this allocation
+  size_t slots_cap = 0;              // ... at this capacity
   bool prepared_recorded = false;  // the preparation's last launch carried the context's tgt_prepared event (no record packet behind it)
   bool cache_searched_lists = false;  // the last preparation's search was the seeded launch that reads the lists (rgc_stats::searched_target)
   int searched_known = -1;            // rgc_stats::searched_target of this preparation once it has been fetched (-1: not yet)
@@ -199,6 +200,11 @@ struct rgc_ctx {
   int lm_give_up_at = -1;     // RGC_LM_GIVE_UP_AT=<try> (a test hook): the resident solve's workgroup 0 gives up at that try, without waiting
   int cu_count = 0;           // the device's compute units: the resident solve runs with at most one workgroup per CU
   bool lm_resident = false;   // the solve in flight went out as one resident launch
+  int voxel_impl = 0;         // RGC_VOXEL_IMPL: 1 "separate", the voxel stage and the map's cooperative search always in launches of their own (k_voxel_build_coop,
+                              // k_voxel_patch); 2 "fused", inside the dense map's kNN launch (rgck::VoxFuse) wherever that launch runs; 0 (unset): fused on a
+                              // context whose scans are held behind another context's target (src_held: a pipelined sequence), separate elsewhere
+  bool src_held = false;      // the scan prepared last on this context was held by rgc_hold_source_until_target_of (src_hold_pending: the call came, the scan has not yet)
+  bool src_hold_pending = false;
   bool lm_host = false;       // RGC_LM_IMPL=host: host-driven LM loop over the public fine-seam kernels (cross-check of the device-chained one)
   bool spec_on = true;        // RGC_SPEC_GRID=0 turns the speculative grid off
   bool coop_stream_on = RGC_COOP_STREAM != 0;  // (build flag; RGC_COOP_STREAM in the environment) the scan's deferred queries inside its bulk kNN launch

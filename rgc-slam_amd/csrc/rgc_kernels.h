@@ -132,6 +132,18 @@ struct KnnSeeds {
   KnnCache cache;  // (nbr == nullptr: no lists)
 };
 bool knn_seeds_apply(int n, int k);  // the seeded search exists for this cloud size and k
+// The dense map's launch over the whole map (target, wide_r == 0, no query list, not the seeded kernel) can do the voxel stage's work itself:
+// every workgroup builds the voxel records of the cells that start and end among its 256 sorted points, from the normals it has in
+// registers, and the launch's last workgroups resolve the deferred queries as they are published (coop_waves of them, sized like
+// knn_coop's).  voxel_seams then finishes the map: the cells that cross a workgroup boundary and the voxels of the deferred queries.
+// The deferred buffer's entry words must hold kDeferredSlotEmptyByte bytes on entry; voxel_seams leaves them so.
+struct VoxFuse {
+  const int* cell_voxel;
+  double* vox;
+  int* vox_cell;
+  int coop_waves;
+};
+bool knn_bulk_fuses_voxels(bool is_target, int n, int k, int wide_r, const int* qlist, const KnnSeeds& seeds);  // knn_bulk would honour `fuse`
 // wide_r = 2: the four-lanes-per-query search on the 5^3 block whatever the cloud (a sparse map)
 void knn_bulk(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* deferred, double* nx,
               double* ny, double* nz, const int* guard = nullptr, int wide_r = 0,
@@ -140,7 +152,9 @@ void knn_bulk(hipStream_t s, bool is_target, const float4* P, const int* start, 
               const int* qlist = nullptr, const int* nq = nullptr, int q_est = 0, const KnnSeeds& seeds = KnnSeeds{},
               // the scan's launch only: > 0 = that many waves at the end of the launch resolve the deferred queries as they are published
               // (no knn_coop launch behind it); the deferred buffer's entry words must hold kDeferredSlotEmptyByte bytes on entry
-              int stream_coop_waves = 0);
+              int stream_coop_waves = 0,
+              // the dense map's launch only, where knn_bulk_fuses_voxels says so (ignored elsewhere): see VoxFuse; voxel_seams must follow
+              const VoxFuse* fuse = nullptr);
 constexpr int kDeferredSlotEmptyByte = 0x80;
 // lazy target: stamp the cells of grid g within `margin` cells of the cell each point of the cloud falls into under T and list the occupied
 // ones (cell_list: their first sorted point; qlist: all their points; counts[0] / [1]: the lists' sizes, zeroed by rank_gather)
@@ -165,6 +179,10 @@ void voxel_build_coop(hipStream_t s, const float4* P, double* nx, double* ny, do
 // the number of deferred queries (grid-stride loop)
 void voxel_patch(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, const int* start, Grid g, const void* deferred,
                  const int* cell_voxel, double* vox, int lanes, hipEvent_t done = nullptr /* signalled by the launch's own completion */);
+// behind a knn_bulk that fused the voxel stage (VoxFuse): the cells that cross a boundary between two of its workgroups and the voxels of the
+// deferred queries (k_voxel_seams); patch_waves: about the number of deferred queries (they stride over the list)
+void voxel_seams(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, const int* start, Grid g, int n, void* deferred,
+                 const int* cell_voxel, double* vox, int* vox_cell, const int* guard, int patch_waves, hipEvent_t done = nullptr);
 // ---- C4/C5/C6 ----
 void linearize(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Pose T, Grid g,
                const int* cell_voxel, const double* vox, int noff, int* corr_v, double* corr_M, int want_H, double* partials,

@@ -784,6 +784,7 @@ struct Deferred {
 };
 constexpr unsigned long long kSlotEnd = 0x8080808080808081ull;    // "no entry will ever appear here": written behind the list by the last bulk workgroup
 constexpr unsigned long long kSlotEmpty = 0x8080808080808080ull;  // (what hipMemset can write; its low word is no valid entry: |enc| <= 2^27)
+constexpr unsigned long long kSlotResolvedTag = 0x4000000000000000ull;  // the map's launch: {query | tag} left by the wave that resolved the entry (coop_stream)
 
 // ------------------------------------------------------------------------------------------------
 // C2  exact k-nearest neighbours + covariance + normal (fast_gicp_impl.hpp:241-298), the bulk kernel: one lane per query, queries
@@ -1043,8 +1044,9 @@ __device__ __forceinline__ int sp_piece_table(const int* __restrict__ start, con
 }
 
 // sums -> mean / covariance (fast_gicp_impl.hpp:256-262) -> unit normal of the smallest eigenvalue, stored: the tail every route shares
+// (nrm_out, nullable: the three values also handed back in registers -- the map's search builds its workgroup's voxel records from them)
 __device__ __forceinline__ void normal_from_moments(double (&S)[6], double mx, double my, double mz, int k, int i, double* __restrict__ nx,
-                                                    double* __restrict__ ny, double* __restrict__ nz) {
+                                                    double* __restrict__ ny, double* __restrict__ nz, double* nrm_out = nullptr) {
   const double inv_k = 1.0 / (double)k;
   mx *= inv_k; my *= inv_k; mz *= inv_k;
   S[0] = S[0] * inv_k - mx * mx; S[1] = S[1] * inv_k - mx * my; S[2] = S[2] * inv_k - mx * mz;
@@ -1057,6 +1059,7 @@ __device__ __forceinline__ void normal_from_moments(double (&S)[6], double mx, d
   nx[i] = nrm[0];
   ny[i] = nrm[1];
   nz[i] = nrm[2];
+  if (nrm_out) { nrm_out[0] = nrm[0]; nrm_out[1] = nrm[1]; nrm_out[2] = nrm[2]; }
 }
 
 // Mean / covariance (fast_gicp_impl.hpp:256-262) / normal of query (px, py, pz) from its neighbours' positions idx[0 .. k) in the sorted
@@ -1069,7 +1072,7 @@ __device__ __forceinline__ void normal_from_moments(double (&S)[6], double mx, d
 template <int KC, bool kFull>
 __device__ __forceinline__ void sp_normal_of(const float4* __restrict__ P, const int (&idx)[KC], float px, float py, float pz, int k, int i,
                                              double* __restrict__ nx, double* __restrict__ ny, double* __restrict__ nz, int* __restrict__ nbr_out = nullptr,
-                                             int nbr_flag = 0) {
+                                             int nbr_flag = 0, double* nrm_out = nullptr) {
   double S[6] = {0, 0, 0, 0, 0, 0};
   if constexpr (kFull && KC % 4 == 0) {
     if (nbr_out) {
@@ -1090,7 +1093,7 @@ __device__ __forceinline__ void sp_normal_of(const float4* __restrict__ P, const
       S[3] = fma(dy, dy, S[3]); S[4] = fma(dy, dz, S[4]); S[5] = fma(dz, dz, S[5]);
     }
   }
-  normal_from_moments(S, mx, my, mz, k, i, nx, ny, nz);
+  normal_from_moments(S, mx, my, mz, k, i, nx, ny, nz, nrm_out);
 }
 
 
@@ -1132,7 +1135,7 @@ __device__ __forceinline__ void cache_uncertified(const Deferred& df, int rank) 
 template <int KC, int KB, int R, int T, bool kExact>  // T: threads per workgroup = stride of the per-lane LDS columns
 __device__ __forceinline__ void knn_point_sp(const float4* __restrict__ P, const int* __restrict__ start, const Grid& g, int n, int k,
                                              int i, int* lds, const Deferred& df, double* __restrict__ nx, double* __restrict__ ny,
-                                             double* __restrict__ nz) {
+                                             double* __restrict__ nz, double* nrm_out = nullptr) {
   constexpr bool kClip = false;
   using Shape = SpShape<R, kClip>;
   constexpr int L = KC + 2;
@@ -1151,8 +1154,14 @@ __device__ __forceinline__ void knn_point_sp(const float4* __restrict__ P, const
   const double q[3] = {(double)px, (double)py, (double)pz};
   auto defer = [&](int enc, float thr) {
     const int e = atomicAdd(df.cnt, 1);
-    df.idx[e] = enc;
-    df.thr[e] = thr;
+    if (df.coop_blocks > 0) {  // published to the waves that resolve the deferred queries inside this launch (coop_stream), as in knn_point_split
+      __hip_atomic_store(&df.slots[e], (unsigned long long)(unsigned)enc | ((unsigned long long)(unsigned)__float_as_int(thr) << 32),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the word has arrived before this wave goes on (and, at the launch's end, counts itself out)
+    } else {
+      df.idx[e] = enc;
+      df.thr[e] = thr;
+    }
     if constexpr (kExact && KC == 20) cache_uncertified<KC>(df, i);
   };
   bool heavy_piece = false;
@@ -1334,11 +1343,11 @@ __device__ __forceinline__ void knn_point_sp(const float4* __restrict__ P, const
     // (the (k+1)-th candidate is a_k; when the exact distances swapped the two the gap is a key bucket or two: no certificate)
     int* const nbr_out = df.cache.nbr ? df.cache.nbr + (size_t)i * KC : nullptr;
     const bool cert = nbr_out && !swap && list_certified(thr_up, __int_as_float(a_k & ~kKeyOrd), bound, df.cache.cert_slack);
-    sp_normal_of<KC, true>(P, idx, px, py, pz, k, i, nx, ny, nz, cert ? nbr_out : nullptr, kListCertified);
+    sp_normal_of<KC, true>(P, idx, px, py, pz, k, i, nx, ny, nz, cert ? nbr_out : nullptr, kListCertified, nrm_out);
     if (!cert) cache_uncertified<KC>(df, i);
   } else {
-    if (kExact || k == KC) sp_normal_of<KC, true>(P, idx, px, py, pz, k, i, nx, ny, nz);
-    else sp_normal_of<KC, false>(P, idx, px, py, pz, k, i, nx, ny, nz);
+    if (kExact || k == KC) sp_normal_of<KC, true>(P, idx, px, py, pz, k, i, nx, ny, nz, nullptr, 0, nrm_out);
+    else sp_normal_of<KC, false>(P, idx, px, py, pz, k, i, nx, ny, nz, nullptr, 0, nrm_out);
   }
   if (df.seed) df.seed[orig] = thr_up;
 }
@@ -2090,7 +2099,10 @@ __device__ __forceinline__ void cov6_of(const float4* __restrict__ P, const int 
 // still have to be dispatched: 2048 four-wave workgroups cost 0.25 ms of the scan's critical path when 200 queries were waiting).
 // (the body: wave `wave` of `nwaves` takes every nwaves-th entry of the deferred list; sh: this wave's LDS scratch)
 // one deferred entry (enc: the query, or ~query when radius 1 is known to be insufficient; thr: the k-th distance seen so far), one wave
-template <int KC, bool kTarget, bool kGeneral = false>
+// kLean (the map's queries resolved inside its bulk launch, coop_stream): the neighbours' coordinates are fetched a lane each and lane 0 adds
+// the moments from LDS in a loop -- sp_normal_of's operations in sp_normal_of's order, so the same bits -- instead of holding all KC
+// gathers in its registers: that unrolled form costs 118 VGPRs, which would take the whole bulk launch from five waves per SIMD to four.
+template <int KC, bool kTarget, bool kGeneral = false, bool kLean = false>
 __device__ __forceinline__ void coop_one(const float4* __restrict__ P, const int* __restrict__ start, const Grid& g, int k, const Deferred& df,
                                          double* __restrict__ nx, double* __restrict__ ny, double* __restrict__ nz, CoopRows* sh, int lane,
                                          int e, int enc, float thr, const GenOut& go = GenOut{nullptr, 0, 0}) {
@@ -2188,7 +2200,28 @@ __device__ __forceinline__ void coop_one(const float4* __restrict__ P, const int
     // pass, neighbours in ascending position) -- a query's covariance is then the same bits whichever kernel ends up computing it, so
     // WHICH queries a launch defers (that depends on the grid's extent, on stray candidates behind a row, on the seeds) cannot show in
     // the results.  (~600 instructions on one lane, 3 us of a deferred query's 15; the lanes' tree sums of rounds 1-4 were another order.)
-    if (lane == 0) {
+    if constexpr (kLean) {
+      static_assert(!kGeneral && KC <= 32, "coordinates of up to 32 neighbours in the rows' LDS");
+      if (lane < k) {  // (pref / rowa are dead behind the collection above)
+        const float4 cp = P[sh->nb[lane]];
+        sh->pref[lane] = __float_as_int(cp.x); sh->pref[32 + lane] = __float_as_int(cp.y); sh->rowa[lane] = __float_as_int(cp.z);
+      }
+      wave_lds_fence();
+      if (lane == 0) {
+        double S[6] = {0, 0, 0, 0, 0, 0};
+        const double qx = (double)px, qy = (double)py, qz = (double)pz;
+        double mx = 0, my = 0, mz = 0;
+#pragma unroll 1
+        for (int j = 0; j < k; j++) {
+          const double dx = (double)__int_as_float(sh->pref[j]) - qx, dy = (double)__int_as_float(sh->pref[32 + j]) - qy, dz = (double)__int_as_float(sh->rowa[j]) - qz;
+          mx += dx; my += dy; mz += dz;
+          S[0] = fma(dx, dx, S[0]); S[1] = fma(dx, dy, S[1]); S[2] = fma(dx, dz, S[2]);
+          S[3] = fma(dy, dy, S[3]); S[4] = fma(dy, dz, S[4]); S[5] = fma(dz, dz, S[5]);
+        }
+        normal_from_moments(S, mx, my, mz, k, i, nx, ny, nz);
+        if (kTarget && df.seed) df.seed[__float_as_int(pq.w)] = thr;
+      }
+    } else if (lane == 0) {
       int idx[KC];
 #pragma unroll
       for (int j = 0; j < KC; j++) idx[j] = j < k ? sh->nb[j] : 0;
@@ -2224,7 +2257,11 @@ __device__ __forceinline__ void coop_run(const float4* __restrict__ P, const int
 // the list for every waiting wave: a wave that reads it leaves.  Workgroups are dispatched in order, so every bulk workgroup is running
 // or finished when the first of these starts: the wait cannot deadlock.  (A launch of its own
 // behind the bulk one started 45 us of latency-bound work only when the last bulk wave had left.)
-template <int KC>
+// The MAP's launch (kTarget, round 16) runs the same protocol with one difference: the voxel records that hold a deferred query are redone
+// behind the launch (k_voxel_seams), which has to know the deferred queries -- and the slots ARE the list.  The reader therefore leaves
+// a "resolved" word {query | kSlotResolvedTag} in an entry's slot instead of kSlotEmpty; k_voxel_seams, the last reader, reads entries
+// [0, *cnt) and puts kSlotEmpty back.  (The end words are put back here, as for the scan: a wave reads exactly one.)
+template <int KC, bool kTarget = false>
 __device__ __forceinline__ void coop_stream(const float4* __restrict__ P, const int* __restrict__ start, const Grid& g, int k, const Deferred& df,
                             double* __restrict__ nx, double* __restrict__ ny, double* __restrict__ nz, CoopRows* sh, int lane, int wave, int nwaves,
                             int bulk_blocks, int nslots) {
@@ -2236,13 +2273,42 @@ __device__ __forceinline__ void coop_stream(const float4* __restrict__ P, const 
       if (v != kSlotEmpty) break;
       __builtin_amdgcn_s_sleep(20);
     }
-    if (lane == 0) __hip_atomic_store(&df.slots[e], kSlotEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (kTarget) {
+      const int enc0 = (int)(unsigned)v;
+      const unsigned long long left = v == kSlotEnd ? kSlotEmpty : (kSlotResolvedTag | (unsigned long long)(unsigned)(enc0 < 0 ? ~enc0 : enc0));
+      if (lane == 0) __hip_atomic_store(&df.slots[e], left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      if (lane == 0) __hip_atomic_store(&df.slots[e], kSlotEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (v == kSlotEnd) return;
     const int enc = __builtin_amdgcn_readfirstlane((int)(unsigned)v);
     const float thr = __int_as_float(__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32)));
-    coop_one<KC, false>(P, start, g, k, df, nx, ny, nz, sh, lane, e, enc, thr);
+    coop_one<KC, kTarget, false, kTarget>(P, start, g, k, df, nx, ny, nz, sh, lane, e, enc, thr);
   }
 }
+// A bulk workgroup counts itself out: everything it deferred has arrived (each publishing wave waited for its word).
+// No fence: an agent-scope release writes this XCD's whole L2 back and invalidates it -- under the searches still running on it.
+// The LAST workgroup to count itself out tells the waiting waves: an "end" word in the first slot behind the list for each of them
+// (they watch their own slots only -- hundreds of waves polling ONE word queue up at its memory channel, in front of the searches'
+// own atomics on the list's counter: the launch took 145 us instead of 55).  flag: one LDS word nobody else uses any more.
+__device__ __forceinline__ void coop_count_out(const Deferred& df, int bulk_blocks, int nwaves, int nslots, int* flag) {
+  __syncthreads();
+  if (threadIdx.x == 0) *flag = __hip_atomic_fetch_add(df.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == bulk_blocks - 1;
+  __syncthreads();
+  if (*flag) {
+    const int cnt = __hip_atomic_load(df.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int j = (int)threadIdx.x; j < nwaves; j += (int)blockDim.x)
+      if (cnt + j < nslots) __hip_atomic_store(&df.slots[cnt + j], kSlotEnd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// The map's search builds the voxel records of its workgroup's own cells at its end (voxel_block_from_search, with the voxel pass below).
+struct VoxOut {
+  double* vox;            // null: the search only
+  int* vox_cell;
+  const int* cell_voxel;
+};
+__device__ __forceinline__ void voxel_block_from_search(const float4* __restrict__ P, const int* __restrict__ start, const Grid& g, int n, int i,
+                                                        const double (&nrm)[3], const VoxOut& vo, int* lds);
 template <int KC, bool kTarget>
 __global__ void __launch_bounds__(WAVE)
 k_knn_coop(const float4* __restrict__ P, const int* __restrict__ start, Grid g, int k, Deferred df, double* __restrict__ nx,
@@ -2253,12 +2319,16 @@ k_knn_coop(const float4* __restrict__ P, const int* __restrict__ start, Grid g, 
   coop_run<KC, kTarget>(P, start, g, k, df, nx, ny, nz, &shm[0], (int)threadIdx.x, (int)blockIdx.x, (int)gridDim.x);
 }
 
-template <int KC, bool kTarget, bool kExact, bool kSeeded = false>
-__global__ void __launch_bounds__((SpLaunch<kTarget, kSeeded>::T), 1)  // (1 wave per SIMD: no cap on the registers -- the map's full search,
-                                                                        // 86 VGPRs and 30 KB of LDS per 256 threads, runs five waves per SIMD either way)
-k_knn_sp(const float4* __restrict__ P, const int* __restrict__ start, Grid g, int n, int k, Deferred df,
-         double* __restrict__ nx, double* __restrict__ ny, double* __restrict__ nz) {
-  extern __shared__ int slist_sp[];  // [SpShape::LDS][T]
+// The body of k_knn_sp and of k_knn_sp_vox (kVox: the dense map's launch that also builds its workgroups' voxel records and resolves its
+// deferred queries in-launch).  Two kernels, not one switched by an argument: with the cooperative waves inlined the allocator gives the
+// kernel 95 VGPRs (96 allocated) instead of 86 (88) -- "five waves per SIMD" either way, but the SCAN's one-wave search (154 VGPRs: 160
+// allocated), which a context by itself runs on its second stream BESIDE this launch, gets onto a SIMD when ONE of five 88-register waves
+// retires (72 + 88 free) and only when TWO of five 96-register ones do: its launch took 139 us instead of 87 beside the fused kernel
+// and still 101 beside the same kernel with the voxel work switched off (EXPERIMENTS.md round 16).  k_knn_sp is the parent's kernel.
+template <int KC, bool kTarget, bool kExact, bool kSeeded, bool kVox>
+__device__ __forceinline__ void knn_sp_body(const float4* __restrict__ P, const int* __restrict__ start, const Grid& g, int n, int k, const Deferred& df,
+                                            double* __restrict__ nx, double* __restrict__ ny, double* __restrict__ nz, const VoxOut& vo) {
+  extern __shared__ __align__(16) int slist_sp[];  // [SpShape::LDS][T]
   using Cfg = SpLaunch<kTarget, kSeeded>;
   static_assert(!kSeeded || (kTarget && kExact), "seeds: the map's search at k == KC");
   wave_prio(!kTarget);
@@ -2291,22 +2361,17 @@ k_knn_sp(const float4* __restrict__ P, const int* __restrict__ start, Grid g, in
 #ifdef RGC_LAB
     if (threadIdx.x == 0 && b < 8192) { g_lab_wave[2 * b] = lab_t0; g_lab_wave[2 * b + 1] = wall_clock64(); }
 #endif
-    if (df.coop_blocks > 0) {  // counted out: everything this workgroup deferred has arrived (each publishing wave waited for its word).
-      // No fence: an agent-scope release writes this XCD's whole L2 back and invalidates it -- under the searches still running on it
-      // The LAST workgroup to count itself out tells the waiting waves: an "end" word in the first slot behind the list for each of them
-      // (they watch their own slots only -- hundreds of waves polling ONE word queue up at its memory channel, in front of the searches'
-      // own atomics on the list's counter: the launch took 145 us instead of 55).
-      __syncthreads();
-      if (threadIdx.x == 0) slist_sp[0] = __hip_atomic_fetch_add(df.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - df.coop_blocks - 1;
-      __syncthreads();
-      if (slist_sp[0]) {
-        const int cnt = __hip_atomic_load(df.cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int nwaves = df.coop_blocks * (Cfg::T / WAVE);
-        for (int j = (int)threadIdx.x; j < nwaves; j += Cfg::T)
-          if (cnt + j < n) __hip_atomic_store(&df.slots[cnt + j], kSlotEnd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    if (df.coop_blocks > 0) coop_count_out(df, (int)gridDim.x - df.coop_blocks, df.coop_blocks * (Cfg::T / WAVE), n, slist_sp);
     return;
+  }
+  if constexpr (kVox) {
+    // the map's deferred queries, resolved by the launch's last workgroups as the searches in front publish them (as the scan's, above)
+    if (df.coop_blocks > 0 && b >= (int)gridDim.x - df.coop_blocks) {
+      const int bulk = (int)gridDim.x - df.coop_blocks;
+      coop_stream<KC, true>(P, start, g, k, df, nx, ny, nz, reinterpret_cast<CoopRows*>(slist_sp) + (threadIdx.x / WAVE), (int)threadIdx.x & (WAVE - 1),
+                            (b - bulk) * (Cfg::T / WAVE) + (int)threadIdx.x / WAVE, df.coop_blocks * (Cfg::T / WAVE), bulk, n);
+      return;
+    }
   }
   bool cached = false;
   if constexpr (kSeeded && RGC_KNN_CACHE != 0) {
@@ -2352,7 +2417,17 @@ k_knn_sp(const float4* __restrict__ P, const int* __restrict__ start, Grid g, in
       knn_point_sp<KC, Cfg::KB, Cfg::R, Cfg::T, kExact>(P, start, g, n, k, i, slist_sp + threadIdx.x, df, nx, ny, nz);
     }
   } else {
-    if (i < n) knn_point_sp<KC, Cfg::KB, Cfg::R, Cfg::T, kExact>(P, start, g, n, k, i, slist_sp + threadIdx.x, df, nx, ny, nz);
+    double nrm[3] = {0.0, 0.0, 0.0};  // (a deferred query's stay so: its voxel is redone behind the launch, k_voxel_seams)
+    if (i < n) knn_point_sp<KC, Cfg::KB, Cfg::R, Cfg::T, kExact>(P, start, g, n, k, i, slist_sp + threadIdx.x, df, nx, ny, nz, kVox ? nrm : nullptr);
+    if constexpr (kVox) {
+      // The voxel records of the cells that start AND end among this workgroup's 256 sorted points, from the registers and LDS the search
+      // leaves behind: no pass over the points and normals in a launch of its own.  The search's per-lane columns are dead behind the barrier.
+      if (vo.vox && i - (int)threadIdx.x < n) {
+        __syncthreads();
+        voxel_block_from_search(P, start, g, n, i, nrm, vo, slist_sp);
+      }
+      if (df.coop_blocks > 0) coop_count_out(df, (int)gridDim.x - df.coop_blocks, df.coop_blocks * (Cfg::T / WAVE), n, slist_sp);
+    }
   }
 #ifdef RGC_LAB_BLOCKS
   if (Cfg::T > WAVE) __syncthreads();
@@ -2366,6 +2441,20 @@ k_knn_sp(const float4* __restrict__ P, const int* __restrict__ start, Grid g, in
 #endif
   }
 #endif
+}
+template <int KC, bool kTarget, bool kExact, bool kSeeded = false>
+__global__ void __launch_bounds__((SpLaunch<kTarget, kSeeded>::T), 1)  // (1 wave per SIMD: no cap on the registers -- the map's full search,
+                                                                        // 86 VGPRs and 30 KB of LDS per 256 threads, runs five waves per SIMD either way)
+k_knn_sp(const float4* __restrict__ P, const int* __restrict__ start, Grid g, int n, int k, Deferred df,
+         double* __restrict__ nx, double* __restrict__ ny, double* __restrict__ nz) {
+  knn_sp_body<KC, kTarget, kExact, kSeeded, false>(P, start, g, n, k, df, nx, ny, nz, VoxOut{nullptr, nullptr, nullptr});
+}
+// the dense map's full launch with the voxel stage inside (95 VGPRs, no scratch, five waves per SIMD)
+template <int KC, bool kExact>
+__global__ void __launch_bounds__(KNN_T, 1)
+k_knn_sp_vox(const float4* __restrict__ P, const int* __restrict__ start, Grid g, int n, int k, Deferred df,
+             double* __restrict__ nx, double* __restrict__ ny, double* __restrict__ nz, VoxOut vo) {
+  knn_sp_body<KC, true, kExact, false, true>(P, start, g, n, k, df, nx, ny, nz, vo);
 }
 
 // Lazy target: the map's search for the LISTED queries only (df.qlist: whole cells, a cell's points are consecutive entries) instead of
@@ -2494,13 +2583,53 @@ __device__ __forceinline__ double voxel_term(const float4* __restrict__ P, const
 // the additions: the per-term lanes alone changed nothing, dropping the bounds look-up gave 36 -> 33 us.  Measured and dropped: workgroups
 // that walk several tiles with the next tile's loads in flight during the sums (36.7 us: the barrier at the end of a tile waits for
 // them anyway); dealing the terms to the cell's own lanes (round 4, earlier: it indexes the accumulators dynamically).)
+// The part behind the staging: the block's sorted points are [b0, bend), this lane's point lies in cell c and is (head) the first of it.
+// kSpill: a cell that runs past the block's end is finished from memory (the voxel pass).  Without it such a cell is left out -- the map's
+// search, whose workgroups build their own cells' records (voxel_block_from_search), leaves it to k_voxel_seams.
+template <bool kSpill>
+__device__ __forceinline__ void voxel_block_sums(const float4* __restrict__ P, const double* __restrict__ nx, const double* __restrict__ ny,
+                                                 const double* __restrict__ nz, const int* __restrict__ start, const int* __restrict__ cell_voxel,
+                                                 double* __restrict__ vox, int* __restrict__ vox_cell, VoxLds& sh, int b0, int bend, int c, bool head) {
+  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+  const unsigned long long mh = __ballot(head);
+  if (lane == 0) sh.wcnt[w] = __popcll(mh);
+  __syncthreads();
+  int base = 0, H = 0;
+#pragma unroll
+  for (int j = 0; j < VOX_T / WAVE; j++) { const int q = sh.wcnt[j]; base += j < w ? q : 0; H += q; }
+  if (head) {
+    const int h = base + __popcll(mh & ((1ull << lane) - 1ull));
+    sh.head_t[h] = threadIdx.x; sh.head_c[h] = c;
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < 9 * H; idx += VOX_T) {
+    const int h = idx / 9, k = idx - 9 * h;
+    const int t0 = sh.head_t[h], cc = sh.head_c[h];
+    const int vv = cell_voxel[cc];  // dense id from the cell scan: asked for now, needed behind the loop
+    // the cell ends where the next one starts; the block's last cell may run past the block: its end is the one look-up of the cell table
+    const bool last = h == H - 1;
+    const int e_in = last ? bend - b0 : sh.head_t[h + 1];
+    const int e1 = last ? start[cc + 1] : b0 + e_in;
+    if (!kSpill && e1 > bend) continue;
+    const double* __restrict__ row = sh.t[k];
+    double acc = 0.0;
+    for (int u = t0; u < e_in; u++) acc += row[u];
+    if constexpr (kSpill)
+      for (int u = b0 + e_in; u < e1; u++) acc += voxel_term(P, nx, ny, nz, k, u);  // the cell runs past this block
+    const double num = (double)(e1 - (b0 + t0));
+    vox[(size_t)vv * kVoxRec + k] = acc / num;
+    if (k == 0) {
+      vox[(size_t)vv * kVoxRec + 9] = num;
+      vox_cell[vv] = cc;
+    }
+  }
+}
 __device__ __forceinline__ void voxel_build_block(const float4* __restrict__ P, const double* __restrict__ nx, const double* __restrict__ ny,
                                                   const double* __restrict__ nz, const int* __restrict__ start, const Grid& g, int n,
                                                   const int* __restrict__ cell_voxel, double* __restrict__ vox, int* __restrict__ vox_cell,
                                                   VoxLds& sh, int block) {
   const int b0 = block * VOX_T, bend = min(b0 + VOX_T, n);
   const int s = b0 + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
   int c = 0;
   bool head = false;
   if (s < n) {
@@ -2521,36 +2650,37 @@ __device__ __forceinline__ void voxel_build_block(const float4* __restrict__ P, 
     sh.t[7][threadIdx.x] = -0.999 * b * d;
     sh.t[8][threadIdx.x] = 1.0 - 0.999 * d * d;
   }
-  const unsigned long long mh = __ballot(head);
-  if (lane == 0) sh.wcnt[w] = __popcll(mh);
-  __syncthreads();
-  int base = 0, H = 0;
-#pragma unroll
-  for (int j = 0; j < VOX_T / WAVE; j++) { const int q = sh.wcnt[j]; base += j < w ? q : 0; H += q; }
-  if (head) {
-    const int h = base + __popcll(mh & ((1ull << lane) - 1ull));
-    sh.head_t[h] = threadIdx.x; sh.head_c[h] = c;
+  voxel_block_sums<true>(P, nx, ny, nz, start, cell_voxel, vox, vox_cell, sh, b0, bend, c, head);
+}
+// The same records from the map's search (k_knn_sp): workgroup = 256 consecutive sorted points, as here; every lane stages the terms of
+// its own point from the normal it has just computed -- the staging expressions above, so the same bits -- and the cells that start and
+// end in the block are summed from LDS.  lds: the search's per-lane columns, dead by now (the caller's barrier).  Only the head flags
+// need memory: the point's coordinates and its predecessor's once more, both in the cache the search has just read them through.
+static_assert(KNN_T == VOX_T, "the search's workgroup is the voxel pass's block");
+static_assert(sizeof(VoxLds) <= sizeof(int) * SpShape<SpConfig<true>::R, SpConfig<true>::kClip>::LDS * KNN_T, "VoxLds fits the search's LDS columns");
+__device__ __forceinline__ void voxel_block_from_search(const float4* __restrict__ P, const int* __restrict__ start, const Grid& g, int n, int i,
+                                                        const double (&nrm)[3], const VoxOut& vo, int* lds) {
+  VoxLds& sh = *reinterpret_cast<VoxLds*>(lds);
+  const int b0 = i - (int)threadIdx.x, bend = min(b0 + VOX_T, n);
+  int c = 0;
+  bool head = false;
+  if (i < n) {
+    const float4 cp = P[i], pv = P[i > 0 ? i - 1 : 0];
+    const double a = nrm[0], b = nrm[1], d = nrm[2];
+    c = cell_index(g, cell_coord(cp.x, g) - g.minc[0], cell_coord(cp.y, g) - g.minc[1], cell_coord(cp.z, g) - g.minc[2]);
+    const int cprev = cell_index(g, cell_coord(pv.x, g) - g.minc[0], cell_coord(pv.y, g) - g.minc[1], cell_coord(pv.z, g) - g.minc[2]);
+    head = i == 0 || cprev != c;
+    sh.t[0][threadIdx.x] = (double)cp.x;
+    sh.t[1][threadIdx.x] = (double)cp.y;
+    sh.t[2][threadIdx.x] = (double)cp.z;
+    sh.t[3][threadIdx.x] = 1.0 - 0.999 * a * a;
+    sh.t[4][threadIdx.x] = -0.999 * a * b;
+    sh.t[5][threadIdx.x] = -0.999 * a * d;
+    sh.t[6][threadIdx.x] = 1.0 - 0.999 * b * b;
+    sh.t[7][threadIdx.x] = -0.999 * b * d;
+    sh.t[8][threadIdx.x] = 1.0 - 0.999 * d * d;
   }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < 9 * H; idx += VOX_T) {
-    const int h = idx / 9, k = idx - 9 * h;
-    const int t0 = sh.head_t[h], cc = sh.head_c[h];
-    const int vv = cell_voxel[cc];  // dense id from the cell scan: asked for now, needed behind the loop
-    // the cell ends where the next one starts; the block's last cell may run past the block: its end is the one look-up of the cell table
-    const bool last = h == H - 1;
-    const int e_in = last ? bend - b0 : sh.head_t[h + 1];
-    const int e1 = last ? start[cc + 1] : b0 + e_in;
-    const double* __restrict__ row = sh.t[k];
-    double acc = 0.0;
-    for (int u = t0; u < e_in; u++) acc += row[u];
-    for (int u = b0 + e_in; u < e1; u++) acc += voxel_term(P, nx, ny, nz, k, u);  // the cell runs past this block
-    const double num = (double)(e1 - (b0 + t0));
-    vox[(size_t)vv * kVoxRec + k] = acc / num;
-    if (k == 0) {
-      vox[(size_t)vv * kVoxRec + 9] = num;
-      vox_cell[vv] = cc;
-    }
-  }
+  voxel_block_sums<false>(P, nullptr, nullptr, nullptr, start, vo.cell_voxel, vo.vox, vo.vox_cell, sh, b0, bend, c, head);
 }
 __global__ void __launch_bounds__(VOX_T)
 k_voxel_build(const float4* __restrict__ P, const double* __restrict__ nx, const double* __restrict__ ny, const double* __restrict__ nz,
@@ -2642,6 +2772,44 @@ k_voxel_patch(const float4* __restrict__ P, const double* __restrict__ nx, const
     const float4 cp = P[i];
     const int c = cell_index(g, cell_coord(cp.x, g) - g.minc[0], cell_coord(cp.y, g) - g.minc[1], cell_coord(cp.z, g) - g.minc[2]);
     voxel_of_cell_wave(P, nx, ny, nz, start, c, cell_voxel, vox, nullptr, term, lane);
+  }
+}
+
+// Behind a map search that built its workgroups' own voxel records (k_knn_sp with VoxOut) and resolved its deferred queries in-launch:
+// what is left of the voxel map, one WAVE per item.
+//  * seam waves, one per block boundary s = 256 b (b = 1 ... nseam): the cell that holds both P[s - 1] and P[s] crosses the boundary and
+//    no workgroup of the search wrote it.  The wave computes it if the cell STARTS in block b - 1: a cell that spans several blocks is
+//    computed once, by the first boundary it crosses.
+//  * patch waves, one per deferred query (entries [0, *cnt) of the slots: the "resolved" words coop_stream left): the query's voxel
+//    once more, now from the normal the cooperative wave stored -- as k_voxel_patch does -- and kSlotEmpty put back: the last reader
+//    leaves the list clean for the next cloud.
+// Both kinds sum in ascending sorted position (voxel_of_cell_wave): the bits of the voxel pass.
+__global__ void __launch_bounds__(WAVE)
+k_voxel_seams(const float4* __restrict__ P, const double* __restrict__ nx, const double* __restrict__ ny, const double* __restrict__ nz,
+              const int* __restrict__ start, Grid g, int n, int* __restrict__ deferred, const int* __restrict__ cell_voxel, double* __restrict__ vox,
+              int* __restrict__ vox_cell, int nseam, const int* __restrict__ guard) {
+  __shared__ double term[9][WAVE];
+  if (guard && *guard) return;  // (nothing was searched, nothing published)
+  const int lane = (int)threadIdx.x;
+  if ((int)blockIdx.x < nseam) {
+    const int s = ((int)blockIdx.x + 1) * VOX_T;
+    if (s >= n) return;
+    const float4 cp = P[s], pv = P[s - 1];
+    const int c = cell_index(g, cell_coord(cp.x, g) - g.minc[0], cell_coord(cp.y, g) - g.minc[1], cell_coord(cp.z, g) - g.minc[2]);
+    const int cprev = cell_index(g, cell_coord(pv.x, g) - g.minc[0], cell_coord(pv.y, g) - g.minc[1], cell_coord(pv.z, g) - g.minc[2]);
+    if (c != cprev || start[c] < s - VOX_T) return;
+    voxel_of_cell_wave(P, nx, ny, nz, start, c, cell_voxel, vox, vox_cell, term, lane);
+    return;
+  }
+  const int cnt = deferred[0];
+  unsigned long long* slots = reinterpret_cast<unsigned long long*>(deferred + 16);
+  for (int e = (int)blockIdx.x - nseam; e < cnt; e += (int)gridDim.x - nseam) {
+    const int i = __builtin_amdgcn_readfirstlane((int)(unsigned)slots[e]);  // {query | kSlotResolvedTag} (the value is here before the store below leaves)
+    if (lane == 0) slots[e] = kSlotEmpty;
+    if ((unsigned)i >= (unsigned)n) continue;
+    const float4 cp = P[i];
+    const int c = cell_index(g, cell_coord(cp.x, g) - g.minc[0], cell_coord(cp.y, g) - g.minc[1], cell_coord(cp.z, g) - g.minc[2]);
+    voxel_of_cell_wave(P, nx, ny, nz, start, c, cell_voxel, vox, vox_cell, term, lane);
   }
 }
 
@@ -4314,10 +4482,14 @@ static Deferred deferred_of(const void* buf, int n) {
                   0, base + 1, reinterpret_cast<unsigned long long*>(base + 16), 0};
 }
 
+bool knn_bulk_fuses_voxels(bool is_target, int n, int k, int wide_r, const int* qlist, const KnnSeeds& seeds) {
+  const bool seeded = k == 20 && seeds.seed && n <= kSeedMaxPoints && seeds.warm;  // (knn_bulk_kc's choice of the seeded kernel)
+  return is_target && wide_r == 0 && !qlist && !seeded && n > 0;
+}
 template <int KC, bool kExact>
 static void knn_bulk_kc(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* deferred,
                         double* nx, double* ny, double* nz, const int* guard, int wide_r, hipEvent_t ev0, hipEvent_t ev1,
-                        const int* qlist, const int* nq, int q_est, const KnnSeeds& seeds, int stream_coop_waves) {
+                        const int* qlist, const int* nq, int q_est, const KnnSeeds& seeds, int stream_coop_waves, const VoxFuse* fuse) {
   Deferred df = deferred_of(deferred, n);  // df.cnt was zeroed by k_rank_gather
   df.guard = guard;
   df.split_sums = is_target ? 0 : 1;
@@ -4358,7 +4530,18 @@ static void knn_bulk_kc(hipStream_t s, bool is_target, const float4* P, const in
       return;
     }
   }
+  VoxOut vo{nullptr, nullptr, nullptr};
+  if (fuse && knn_bulk_fuses_voxels(is_target, n, k, wide_r, qlist, seeds)) {
+    // the workgroups build their own cells' voxel records, and the launch's last workgroups resolve the deferred queries (voxel_seams follows)
+    vo = VoxOut{fuse->vox, fuse->vox_cell, fuse->cell_voxel};
+    const int w = fuse->coop_waves;
+    df.coop_blocks = nblk(w < 32 ? 32 : (w > 8192 ? 8192 : w), T / WAVE);
+    static_assert(sizeof(CoopRows) * (CT::T / WAVE) <= (size_t)SpShape<CT::R, CT::kClip>::LDS * CT::T * sizeof(int), "the cooperative waves' scratch fits the bulk launch's LDS");
+    nb += df.coop_blocks;
+  }
   if (is_target && qlist) hipLaunchKernelGGL((k_knn_sp_listed<KC, kExact>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
+  else if (is_target && vo.vox && ev0 && ev1) hipExtLaunchKernelGGL((k_knn_sp_vox<KC, kExact>), dim3(nb), dim3(T), (std::uint32_t)lds, s, ev0, ev1, 0u, P, start, g, n, k, df, nx, ny, nz, vo);
+  else if (is_target && vo.vox) hipLaunchKernelGGL((k_knn_sp_vox<KC, kExact>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz, vo);
   else if (is_target && ev0 && ev1) hipExtLaunchKernelGGL((k_knn_sp<KC, true, kExact>), dim3(nb), dim3(T), (std::uint32_t)lds, s, ev0, ev1, 0u, P, start, g, n, k, df, nx, ny, nz);
   else if (is_target) hipLaunchKernelGGL((k_knn_sp<KC, true, kExact>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
   else {  // four lanes per query; the deferred queries resolved by the launch's last workgroups (coop_stream) when the caller asks for it
@@ -4388,12 +4571,12 @@ static void knn_coop_kc(hipStream_t s, bool is_target, const float4* P, const in
 bool knn_bulk_times_itself(bool is_target, int wide_r) { return is_target && wide_r != 2; }
 void knn_bulk(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* deferred, double* nx,
               double* ny, double* nz, const int* guard, int wide_r, hipEvent_t ev0, hipEvent_t ev1, const int* qlist, const int* nq, int q_est,
-              const KnnSeeds& seeds, int stream_coop_waves) {
+              const KnnSeeds& seeds, int stream_coop_waves, const VoxFuse* fuse) {
   if (is_target || wide_r == 2) stream_coop_waves = 0;  // (the scan's four-lane search only)
   // (k == 20, the reference's setting, gets an instance without the general-k branches)
-  if (k == 20) knn_bulk_kc<20, true>(s, is_target, P, start, g, n, k, deferred, nx, ny, nz, guard, wide_r, ev0, ev1, qlist, nq, q_est, seeds, stream_coop_waves);
-  else if (k < 20) knn_bulk_kc<20, false>(s, is_target, P, start, g, n, k, deferred, nx, ny, nz, guard, wide_r, ev0, ev1, qlist, nq, q_est, seeds, stream_coop_waves);
-  else knn_bulk_kc<32, false>(s, is_target, P, start, g, n, k, deferred, nx, ny, nz, guard, wide_r, ev0, ev1, qlist, nq, q_est, seeds, stream_coop_waves);
+  if (k == 20) knn_bulk_kc<20, true>(s, is_target, P, start, g, n, k, deferred, nx, ny, nz, guard, wide_r, ev0, ev1, qlist, nq, q_est, seeds, stream_coop_waves, fuse);
+  else if (k < 20) knn_bulk_kc<20, false>(s, is_target, P, start, g, n, k, deferred, nx, ny, nz, guard, wide_r, ev0, ev1, qlist, nq, q_est, seeds, stream_coop_waves, fuse);
+  else knn_bulk_kc<32, false>(s, is_target, P, start, g, n, k, deferred, nx, ny, nz, guard, wide_r, ev0, ev1, qlist, nq, q_est, seeds, stream_coop_waves, fuse);
 }
 
 void knn_coop(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* segs, double* nx,
@@ -4437,6 +4620,14 @@ void voxel_patch(hipStream_t s, const float4* P, const double* nx, const double*
   // (done: the launch's own completion is the event -- no record packet between the map's last kernel and the solve's first step)
   if (done) hipExtLaunchKernelGGL(k_voxel_patch, dim3(nb), dim3(WAVE), 0u, s, nullptr, done, 0u, P, nx, ny, nz, start, g, (const int*)deferred, cell_voxel, vox);
   else hipLaunchKernelGGL(k_voxel_patch, dim3(nb), dim3(WAVE), 0, s, P, nx, ny, nz, start, g, (const int*)deferred, cell_voxel, vox);
+}
+void voxel_seams(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, const int* start, Grid g, int n, void* deferred,
+                 const int* cell_voxel, double* vox, int* vox_cell, const int* guard, int patch_waves, hipEvent_t done) {
+  const int nseam = nblk(n, VOX_T) - 1;  // block boundaries inside the cloud
+  const int nb = nseam + (patch_waves < 64 ? 64 : (patch_waves > 4096 ? 4096 : patch_waves));  // one-wave workgroups; the patch waves stride over the list
+  // (done: the launch's own completion is the event, as voxel_patch's)
+  if (done) hipExtLaunchKernelGGL(k_voxel_seams, dim3(nb), dim3(WAVE), 0u, s, nullptr, done, 0u, P, nx, ny, nz, start, g, n, (int*)deferred, cell_voxel, vox, vox_cell, nseam, guard);
+  else hipLaunchKernelGGL(k_voxel_seams, dim3(nb), dim3(WAVE), 0, s, P, nx, ny, nz, start, g, n, (int*)deferred, cell_voxel, vox, vox_cell, nseam, guard);
 }
 void linearize(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Pose T, Grid g,
                const int* cell_voxel, const double* vox, int noff, int* corr_v, double* corr_M, int want_H, double* partials,
