@@ -45,6 +45,7 @@ static bool general_route(const rgc_ctx* c) {
   return c->force_general || c->reg_method != RGC_REG_PLANE || c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE || c->cov_method == RGC_COV_RBF;
 }
 
+static bool trace_alloc() { static const bool on = getenv("RGC_TRACE_ALLOC") != nullptr; return on; }  // developer aid: which buffer grew, and when
 int ensure(rgc_ctx* c, DevBuf& b, size_t bytes) {
   if (b.borrowed) { b.p = nullptr; b.cap = 0; b.borrowed = false; }  // an alias is dropped, never resized: this context gets its own buffer
   if (bytes <= b.cap && b.p) return RGC_OK;
@@ -61,8 +62,7 @@ int ensure(rgc_ctx* c, DevBuf& b, size_t bytes) {
   size_t want = bytes + (bytes < ((size_t)256 << 20) ? bytes / 2 : bytes / 8) + 256;
   HIPCHK(c, hipMalloc(&b.p, want));
   b.cap = want;
-  static const bool trace = getenv("RGC_TRACE_ALLOC") != nullptr;  // developer aid: which buffer grew, and when
-  if (trace) fprintf(stderr, "[rgc] buffer at ctx+%ld grew to %zu bytes (asked %zu)\n", (long)((char*)&b - (char*)c), want, bytes);
+  if (trace_alloc()) fprintf(stderr, "[rgc] buffer at ctx+%ld grew to %zu bytes (asked %zu)\n", (long)((char*)&b - (char*)c), want, bytes);
   return RGC_OK;
 }
 
@@ -94,21 +94,26 @@ static void release(DevBuf& b) {
   b.borrowed = false;
 }
 
+// the buffers of a target that a borrower aliases (rgc_share_target)
+static std::vector<DevBuf*> shared_bufs(Cloud& cl) {
+  return {&cl.in_copy, &cl.cell_of, &cl.slot_of, &cl.cnt, &cl.start, &cl.block_sums, &cl.order_tmp, &cl.P, &cl.nx, &cl.ny, &cl.nz, &cl.segs,
+          &cl.cell_voxel, &cl.vox, &cl.vox_cell, &cl.c6};
+}
 static void release_cloud(Cloud& cl) {
-  for (DevBuf* b : {&cl.in_copy, &cl.cell_of, &cl.slot_of, &cl.cnt, &cl.start, &cl.block_sums, &cl.order_tmp, &cl.P, &cl.nx, &cl.ny, &cl.nz, &cl.segs,
-                    &cl.cell_voxel, &cl.vox, &cl.vox_cell, &cl.need, &cl.qlist, &cl.cell_list, &cl.seed, &cl.nbr, &cl.rank_of, &cl.pos_of, &cl.qrank,
-                    &cl.map_copy, &cl.todo, &cl.cache_small, &cl.c6})
-    release(*b);
+  for (DevBuf* b : shared_bufs(cl)) release(*b);
+  for (DevBuf* b : {&cl.need, &cl.qlist, &cl.cell_list, &cl.seed, &cl.nbr, &cl.rank_of, &cl.pos_of, &cl.qrank, &cl.map_copy, &cl.todo, &cl.cache_small}) release(*b);
 }
 
 // ---- profiling regions (HIP events on the context's stream) ----
+static bool profiled(const rgc_ctx* c, int kind) { return c->prof_on && ((c->prof_mask >> kind) & 1u); }  // the profile is on and wants this kind of region
 namespace {
 struct ProfScope {
   rgc_ctx* c;
-  bool on;
+  bool on, records;  // records == false: the region's one launch fills r.a / r.b with its own start / stop times (hipExtLaunchKernelGGL)
   ProfRegion r{};
   hipStream_t st;
-  ProfScope(rgc_ctx* ctx, int kind, long long points, hipStream_t stream = nullptr) : c(ctx), on(ctx->prof_on && ((ctx->prof_mask >> kind) & 1u)), st(stream ? stream : ctx->stream) {
+  ProfScope(rgc_ctx* ctx, int kind, long long points, hipStream_t stream = nullptr, bool records_ = true)
+      : c(ctx), on(profiled(ctx, kind)), records(records_), st(stream ? stream : ctx->stream) {
     if (!on) return;
     auto get = [&](hipEvent_t* e) {
       if (!c->ev_pool.empty()) { *e = c->ev_pool.back(); c->ev_pool.pop_back(); return true; }
@@ -118,11 +123,11 @@ struct ProfScope {
     if (!get(&r.b)) { c->ev_pool.push_back(r.a); on = false; return; }
     r.kind = kind;
     r.points = points;
-    (void)hipEventRecord(r.a, st);
+    if (records) (void)hipEventRecord(r.a, st);
   }
   ~ProfScope() {
     if (!on) return;
-    (void)hipEventRecord(r.b, st);
+    if (records) (void)hipEventRecord(r.b, st);
     c->prof_open.push_back(r);
   }
 };
@@ -199,28 +204,43 @@ static int cloud_covariances(rgc_ctx* c, Cloud& cl, bool is_target);
 static int map_wide_r_of(const rgc_ctx* c, const Cloud& cl) {
   return (c->map_wide_r > 0 && (double)cl.n < c->map_wide_density * (double)cl.grid.ncell) ? c->map_wide_r : 0;
 }
-
-// C1-C3: grid + exact-kNN covariances (+ voxel map for the target), all enqueued on the stream.
-// The first cloud of a context costs one host<->device round trip -- the 6-int bounding box the dense grid is sized from; later
-// clouds re-use the previous (widened) grid speculatively and need none (see `spec` below).
 static rgck::KnnSeeds cloud_seeds(const Cloud& cl, bool is_target);
 
-static int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox = false) {
-  if (!is_target && &cl == &c->src) { c->src_held = c->src_hold_pending; c->src_hold_pending = false; }  // was THIS scan held? (the same contexts may run a frame at a time later)
-  const int n = cl.n;
-  cl.covs_user = false;
-  if (is_target && &cl == &c->tgt) {
-    c->tgt_generation++;       // borrowers of the previous target must share again
-    c->tgt_owner = nullptr;    // (a borrowed target's aliases are dropped buffer by buffer in ensure())
-  }
-  hipStream_t s = is_target ? c->stream : c->stream2;
-  int* dsm = c->d_small + (is_target ? 0 : 16);
-  int* hsm = c->h_small + (is_target ? 0 : 16);
-  const int hi = is_target ? 0 : 1;  // the scan's kernels share CUs with the map's kNN launch: raised wave priority
-  // The scan is prepared on stream2, concurrently with the map's preparation on the main stream.  Whatever produced the scan was
-  // enqueued on the main stream (rgc_upload, the front-end, a caller's own kernels on rgc_stream()): stream2 waits for a mark
-  // recorded on the main stream BEFORE this frame's map preparation was enqueued (waiting for the map's kNN launch would serialise
-  // the two) -- i.e. at rgc_set_target*, or here when no map preparation is pending.  See rgc_set_source_device in rgc_hip.h.
+// ---- one place per rule ----
+// a cloud's block of the context's small scratch (d_small / h_small): the map's at +0, the scan's at +16; [6] of it: the flags = its grid's guard
+static int small_off(bool is_target) { return is_target ? 0 : 16; }
+// ... as the cloud's kernels take it: while the cloud sits on a speculative (or hinted) grid whose guard has not been read yet
+static int* guard_of(rgc_ctx* c, const Cloud& cl, bool is_target) { return cl.spec_used ? c->d_small + small_off(is_target) + 6 : nullptr; }
+// Launch sizes from the deferred count of the previous cloud prepared here (consecutive clouds of a sequence defer about the same queries;
+// n / 64 for the first one): the waves of a cooperative search, and the waves that patch the voxels of the deferred queries
+static int coop_waves_est(const Cloud& cl) { return cl.deferred_seen >= 0 ? cl.deferred_seen + cl.deferred_seen / 4 + 32 : cl.n / 64 + 32; }
+static int patch_waves_est(const Cloud& cl) { return cl.deferred_seen >= 0 ? 2 * cl.deferred_seen + 64 : cl.n; }
+// the voxel records of a map of cl.n points on a grid of ncell cells: at most one voxel per point and per cell
+static int ensure_voxel_table(rgc_ctx* c, Cloud& cl, int ncell) {
+  const size_t vmax = (size_t)(cl.n < ncell ? cl.n : ncell);
+  int rc;
+  if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kVoxRec * vmax))) return rc;
+  return ensure(c, cl.vox_cell, sizeof(int) * vmax);
+}
+// what a linearisation of n source points freezes and folds: corr_v / corr_M for noff offsets, row_doubles per workgroup in partials
+static int ensure_corr(rgc_ctx* c, int n, int noff, size_t row_doubles) {
+  const size_t nb = (size_t)rgck::linearize_blocks(n);
+  int rc;
+  if ((rc = ensure(c, c->corr_v, sizeof(int) * (size_t)n * noff))) return rc;
+  if ((rc = ensure(c, c->corr_M, sizeof(double) * 6 * (size_t)n * noff))) return rc;
+  if ((rc = ensure(c, c->partials, sizeof(double) * row_doubles * nb))) return rc;
+  return ensure(c, c->ipartials, sizeof(int) * nb);
+}
+static rgck::Corr corr_of(const rgc_ctx* c) { return {c->corr_v.as<int>(), c->corr_M.as<double>()}; }
+
+// ---- C1-C3: grid + exact-kNN covariances (+ voxel map for the target), all enqueued on the stream: prepare_cloud and its stages ----
+// The first cloud of a context costs one host<->device round trip -- the 6-int bounding box the dense grid is sized from; later
+// clouds re-use the previous (widened) grid speculatively and need none (see prep_known_grid).
+// Stage 1, stream ordering.  The scan is prepared on stream2, concurrently with the map's preparation on the main stream.  Whatever
+// produced the scan was enqueued on the main stream (rgc_upload, the front-end, a caller's own kernels on rgc_stream()): stream2 waits for
+// a mark recorded on the main stream BEFORE this frame's map preparation was enqueued (waiting for the map's kNN launch would serialise
+// the two) -- i.e. at rgc_set_target*, or here when no map preparation is pending.  See rgc_set_source_device in rgc_hip.h.
+static int prep_order_streams(rgc_ctx* c, bool is_target) {
   if (!is_target && c->main_has_target_prep && map_prep_finished(c)) c->main_has_target_prep = false;  // it has drained
   // (The map's own mark sits in FRONT of its counting pass: an event record between two kernels of one stream holds the second one back
   // ~5.8 us; in front of the frame's first launch it is processed while the GPU waits for the host anyway.)
@@ -231,7 +251,253 @@ static int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox 
   }
   if (is_target) c->main_has_target_prep = true;
   else if (c->mark_valid) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->main_mark, 0));
+  return RGC_OK;
+}
 
+// Stage 2, grid choice: cl.grid <- the grid where one is to be had without measuring, guarded by k_count (returns true): that of a box the
+// library knows (*hint_out) or the speculative one; neither, the cloud's own box is measured (prep_measured_grid, behind the reuse set-up,
+// whose launches go first).
+// Speculative grid: consecutive clouds of a sequence cover (almost) the same cells, so the previous grid -- widened by two
+// cells in x and y, one in z -- is re-used WITHOUT the bounding-box kernel and its host round trip (the only synchronisation
+// between setInputTarget and the end of align).  A larger bounding grid changes nothing in the results: cells keep their
+// relative order (voxel ids come from the cell scan), neighbourhoods are the same.  k_count guards it; the guard comes home
+// with the LM state (or is read by the first other consumer) and a miss re-prepares the cloud on its own bounding box.
+static bool prep_known_grid(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox, double res, const rgc_ctx::BoxHint** hint_out) {
+  const rgc_ctx::BoxHint*& hint = *hint_out;
+  const bool spec = c->spec_on && !c->lm_host && cl.spec_ok && cl.spec_grid.res == res && !force_bbox;
+  hint = (is_target && c->spec_on && !c->lm_host && !force_bbox) ? find_hint(c, cl.in, cl.n) : nullptr;
+  if (hint)  // (a box that is not one -- it was derived from a pose that was not finite -- is no hint: the float -> int conversions below are undefined on it)
+    for (int a = 0; a < 3; a++)
+      if (!(std::isfinite(hint->lo[a]) && std::isfinite(hint->hi[a]) && hint->hi[a] >= hint->lo[a] && std::fabs(hint->lo[a]) <= 1.0e8 &&
+            std::fabs(hint->hi[a]) <= 1.0e8)) { hint = nullptr; break; }
+  if (hint) {  // the box is known (rgc_set_target_reframed / rgc_transform_cloud): its cells plus one on every side, guarded like a speculative grid
+    int lo[3], dm[3];
+    double ncell = 1.0;
+    for (int a = 0; a < 3; a++) {
+      lo[a] = (int)std::floor(hint->lo[a] / res - 0.5) - 1;
+      dm[a] = (int)std::floor(hint->hi[a] / res - 0.5) + 1 - lo[a] + 1;
+      ncell *= (double)dm[a];
+    }
+    if (ncell <= (double)c->prm.max_cells && ncell <= 2.0e9) cl.grid = rgck::make_grid(lo, dm, res);
+    else hint = nullptr;
+  }
+  if (hint) {
+    cl.spec_ok = true;
+    cl.spec_grid = cl.grid;
+  } else if (spec) {
+    cl.grid = cl.spec_grid;
+  }
+  return hint || spec;
+}
+// ... the measured grid: the bounding-box kernel and its round trip, and the grid the NEXT cloud will try
+static int prep_measured_grid(rgc_ctx* c, Cloud& cl, bool is_target, double res, hipStream_t s) {
+  int* dsm = c->d_small + small_off(is_target);
+  int* hsm = c->h_small + small_off(is_target);
+  rgck::Grid g{};
+  rgck::bbox(s, cl.in, cl.stride_f, cl.n, res, dsm, dsm + 6, is_target ? 0 : 1);
+  HIPCHK(c, hipMemcpyAsync(hsm, dsm, 7 * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (hsm[6]) return fail(c, RGC_ERR_NONFINITE, "%s cloud contains non-finite or absurd coordinates", is_target ? "target" : "source");
+  double ncell = 1.0;
+  for (int a = 0; a < 3; a++) {
+    g.minc[a] = hsm[a];
+    g.dim[a] = hsm[3 + a] - hsm[a] + 1;
+    ncell *= (double)g.dim[a];
+  }
+  if (ncell > (double)c->prm.max_cells || ncell > 2.0e9)
+    return fail(c, RGC_ERR_GRID_TOO_LARGE, "%s grid %d x %d x %d exceeds max_cells", is_target ? "target" : "source", g.dim[0], g.dim[1], g.dim[2]);
+  g.res = res;
+  g.inv_res = rgck::grid_inv_res(res);
+  g.ncell = (int)ncell;
+  cl.grid = g;
+  // The grid the NEXT cloud will try.  The map's box is stable and its grid large: 2 / 2 / 1 cells of margin.  A raw scan's box
+  // jumps with every far return, but it stays inside the sensor's range envelope and its grid is small: 16 / 16 / 4 cells of
+  // margin, united with the box tried before (a miss costs the scan's whole preparation and a second solve, so the box only
+  // ever grows -- at most to four times the measured one).
+  rgck::Grid w = g;
+  double wcell = 1.0;
+  for (int a = 0; a < 3; a++) {
+    const int m = is_target ? (a < 2 ? 2 : 1) : (a < 2 ? 16 : 4);
+    int lo = g.minc[a] - m, hi = g.minc[a] + g.dim[a] - 1 + m;
+    if (!is_target && cl.spec_ok && cl.spec_grid.res == g.res) {
+      lo = std::min(lo, cl.spec_grid.minc[a]);
+      hi = std::max(hi, cl.spec_grid.minc[a] + cl.spec_grid.dim[a] - 1);
+    }
+    w.minc[a] = lo; w.dim[a] = hi - lo + 1;
+    wcell *= (double)w.dim[a];
+  }
+  if (!is_target && wcell > 4.0 * ncell + 1.0e6) {  // the union ran away (a sequence that really moves its box): start over from this cloud
+    wcell = 1.0;
+    for (int a = 0; a < 3; a++) { const int m = a < 2 ? 16 : 4; w.minc[a] = g.minc[a] - m; w.dim[a] = g.dim[a] + 2 * m; wcell *= (double)w.dim[a]; }
+  }
+  w.ncell = (int)wcell;
+  cl.spec_ok = wcell <= (double)c->prm.max_cells && wcell <= 2.0e9;
+  cl.spec_grid = w;
+  if (cl.spec_ok) {  // its cell arrays now, in the frame that is slow anyway, not in the next one
+    const size_t wc1 = (size_t)w.ncell + 1;
+    int rc;
+    if ((rc = ensure(c, cl.cnt, sizeof(int) * wc1 + 256))) return rc;
+    if ((rc = ensure(c, cl.start, sizeof(int) * wc1))) return rc;
+    if ((rc = ensure(c, cl.block_sums, sizeof(long long) * (wc1 / 2048 + 2)))) return rc;
+    if (is_target && (rc = ensure(c, cl.cell_voxel, sizeof(int) * (size_t)w.ncell))) return rc;
+    // ... and the voxel table (80 B per cell of a map denser than its grid: 1.3 GB at 16 M cells -- growing it in the next
+    // frame, when the widened grid is first used, was a 77 ms allocation inside c5's three timed frames on a fresh box)
+    if (is_target && (rc = ensure_voxel_table(c, cl, w.ncell))) return rc;
+  }
+  return RGC_OK;
+}
+// ... the neighbour lists on top of the seeds (rgck::KnnCache): their buffers, the certificates' exponent, the frame number, the copy of the map the
+// counting pass compares it with (cl.rf).  An optimisation: if the device cannot hold them (112 B per point) the context goes down to the seeds.
+static int prep_lists(rgc_ctx* c, Cloud& cl, hipStream_t s, double maxabs, double res) {
+  const int n = cl.n;
+  const size_t cap = (size_t)std::max(256, n / (4 * rgck::kTodoLists) + 1);
+  const size_t want[7] = {sizeof(int) * (size_t)n * 20, sizeof(int) * (size_t)n, sizeof(int) * (size_t)n, sizeof(int) * (size_t)n,
+                          sizeof(float4) * (size_t)n, sizeof(int) * cap * rgck::kTodoLists, sizeof(int) * (rgck::kTodoLists + 16)};
+  DevBuf* bufs[7] = {&cl.nbr, &cl.pos_of, &cl.rank_of, &cl.qrank, &cl.map_copy, &cl.todo, &cl.cache_small};
+  bool lists = true;
+  for (int b = 0; b < 7 && lists; b++)
+    if (ensure(c, *bufs[b], want[b]) != RGC_OK) lists = false;
+  if (c->test_fail_cache_alloc) lists = false;  // (RGC_TEST_FAIL_CACHE_ALLOC at rgc_create: a test's way to walk the path below, as if the device were full)
+  if (!lists) {
+    (void)hipGetLastError();
+    for (DevBuf* b : bufs) release(*b);
+    c->cache_on = false;
+    c->cache_dropped = true;
+    cl.cache_live = false;
+    if (trace_alloc()) fprintf(stderr, "[rgc] neighbour lists of %d points do not fit on the device: this context keeps seeds only from here on\n", n);
+    return RGC_OK;
+  }
+  bool fresh = !cl.seed_warm || !cl.cache_live || !cl.nbr.p;
+  cl.todo_cap = (int)cap;
+  int ce2;  // (a cell of margin around the box, as the grid has)
+  (void)std::frexp(1.5 * maxabs + 2.0 * res, &ce2);
+  // larger coordinates than the certificates allow for: issue them again.  Smaller ones for sixteen frames in a row: new certificates
+  // need the smaller gap only (the old ones, issued for a wider one, stand).
+  if (fresh || ce2 > cl.cache_e2) { cl.cache_e2 = ce2; fresh = true; }
+  if (ce2 < cl.cache_e2) {
+    cl.cache_e2_low_max = cl.cache_e2_low ? std::max(cl.cache_e2_low_max, ce2) : ce2;
+    if (++cl.cache_e2_low >= 16) { cl.cache_e2 = cl.cache_e2_low_max; cl.cache_e2_low = 0; }  // (the largest of those sixteen frames)
+  } else {
+    cl.cache_e2_low = 0;
+  }
+  if (cl.cache_frame >= (1 << 30)) { cl.cache_frame = 0; fresh = true; }
+  cl.cache_frame++;
+  if (fresh) HIPCHK(c, hipMemsetAsync(cl.cache_small.p, 0, sizeof(int) * (rgck::kTodoLists + 16), s));  // (list lengths, epoch, overflow)
+  cl.rf.copy = cl.map_copy.as<float4>();
+  cl.rf.epoch = cl.cache_small.as<int>() + rgck::kTodoLists;
+  cl.rf.frame = cl.cache_frame;
+  cl.rf.force = fresh ? 1 : 0;
+  cl.cache_on = true;
+  return RGC_OK;
+}
+
+// Stage 3, reuse set-up.  A re-framed map (rgc_set_target_reframed) has not been written yet: with its box known the counting pass
+// produces it on the way (fuse_reframe: one pass over the map and one launch less); any other route measures the cloud first and needs
+// it in memory.  Seeds of the exact search: a re-framed map is the point set of cl.rf.src moved rigidly, so what the last search of that
+// buffer found bounds this one (rgck::KnnSeeds; exactness does not depend on it).  Any other target: no seeds.
+static int prep_reuse(rgc_ctx* c, Cloud& cl, bool is_target, hipStream_t s, const rgc_ctx::BoxHint* hint, bool fuse_reframe, double res) {
+  const int n = cl.n;
+  const bool own_target = is_target && &cl == &c->tgt;
+  if (cl.reframe_pending && !fuse_reframe)
+    rgck::transform_q(s, cl.rf.src, cl.rf.src_stride_f, n, cl.rf.q, cl.rf.t, const_cast<float*>(cl.in), 4);
+  cl.seed_on = false;
+  if (own_target && cl.reframe_pending && c->seeds_on && !general_route(c) && rgck::knn_seeds_apply(n, c->prm.k_correspondences)) {
+    int rc;
+    if (cl.seed_key != (const void*)cl.rf.src || cl.seed_n != n || !cl.seed.p) {
+      if ((rc = ensure(c, cl.seed, sizeof(float) * (size_t)n))) return rc;
+      HIPCHK(c, hipMemsetAsync(cl.seed.p, 0x7f, sizeof(float) * (size_t)n, s));  // 3.4e38: "no seed"
+      cl.seed_key = cl.rf.src;
+      cl.seed_n = n;
+      cl.seed_warm = false;
+    }
+    cl.seed_on = true;
+    // the coordinates' fp32 rounding, twice (two frames), on either end of a distance: 4 ulp of the largest coordinate of the box
+    double maxabs = 1.0;
+    if (hint) for (int a = 0; a < 3; a++) maxabs = std::max(maxabs, std::max(std::fabs(hint->lo[a]), std::fabs(hint->hi[a])));
+    else maxabs = 1024.0;
+    int e2;
+    (void)std::frexp(1.5 * maxabs, &e2);
+    cl.seed_slack = (float)(4.0 * std::ldexp(1.0, e2 - 24));
+    // The neighbour lists on top: the counting pass that produces the map compares it with the library's copy on the way, so only that
+    // route has them; a lazy target searches a part of the map per frame and keeps none.
+    // (the certificate's error budget is that of a RIGID motion: reframe_point applies v + 2w(u x v) + 2u x (u x v) as Eigen does, without
+    // normalising q, so |q|^2 - 1 shows up as a relative error of that order on every distance.  1e-9 is far inside the 4e-6 the
+    // certificate allows for and is met by any quaternion normalised in fp64; one normalised in fp32 gets seeds, not lists.)
+    const double qn = cl.rf.q.x * cl.rf.q.x + cl.rf.q.y * cl.rf.q.y + cl.rf.q.z * cl.rf.q.z + cl.rf.q.w * cl.rf.q.w;
+    cl.cache_on = false;
+    if (c->cache_on && fuse_reframe && c->lazy_margin <= 0 && std::fabs(qn - 1.0) < 1.0e-9 && (rc = prep_lists(c, cl, s, maxabs, res))) return rc;
+  } else if (own_target) {
+    cl.seed_key = nullptr;
+    cl.cache_on = false;
+  }
+  if (own_target) {
+    cl.cache_live = false;  // (set again by the search that attaches the lists, cloud_covariances)
+    cl.searched_known = -1;
+    if (!cl.cache_on) { cl.rf.copy = nullptr; cl.rf.epoch = nullptr; }
+  }
+  cl.reframe_pending = false;
+  return RGC_OK;
+}
+
+// Stage 4, buffer sizing: everything the grid build and the search write, and the counters known to be zero
+static int prep_size_buffers(rgc_ctx* c, Cloud& cl, bool is_target, hipStream_t s, const rgc_ctx::BoxHint* hint) {
+  const int n = cl.n;
+  const rgck::Grid& g = cl.grid;
+  const size_t nc1 = (size_t)g.ncell + 1;  // counters (+ sentinel)
+  int rc;
+  for (DevBuf* b : {&cl.cell_of, &cl.slot_of})
+    if ((rc = ensure(c, *b, sizeof(int) * n))) return rc;
+  // (a hinted box is that of a map re-framed by the vehicle's pose: as the yaw changes it swings between the map's own box and one
+  // with twice the cells -- the cell arrays are sized for the largest it can get, once, not grown a few per cent per frame)
+  size_t want_cells = nc1;
+  if (hint && hint->reach_xy > 0) {
+    const double e = hint->reach_xy / g.res + 6.0, ez = hint->reach_z / g.res + 6.0;
+    const double cells = e * e * ez * 1.05;
+    if (cells < 2.0e9 && cells <= (double)c->prm.max_cells && (size_t)cells > want_cells) want_cells = (size_t)cells;
+  }
+  if ((rc = ensure(c, cl.cnt, sizeof(int) * want_cells + 256))) return rc;
+  if ((rc = ensure(c, cl.start, sizeof(int) * want_cells))) return rc;
+  if ((rc = ensure(c, cl.block_sums, sizeof(long long) * (want_cells / 2048 + 2)))) return rc;
+  if ((rc = ensure(c, cl.order_tmp, sizeof(long long) * n))) return rc;
+  if ((rc = ensure(c, cl.P, sizeof(float4) * ((size_t)n + 4)))) return rc;
+  if ((rc = ensure(c, cl.segs, rgck::deferred_bytes(n)))) return rc;
+  for (DevBuf* b : {&cl.nx, &cl.ny, &cl.nz})
+    if ((rc = ensure(c, *b, sizeof(double) * n))) return rc;
+  if (is_target && (rc = ensure(c, cl.cell_voxel, sizeof(int) * want_cells))) return rc;  // (want_cells > ncell)
+  if (cl.cnt.p != cl.cnt_seen) { cl.cnt_clean = 0; cl.cnt_seen = cl.cnt.p; }  // re-allocated: contents unknown
+  if (cl.cnt_clean < nc1) {  // first use or a larger grid; afterwards the scan leaves the counters clean: no fill kernel per frame
+    const size_t fill = std::min(cl.cnt.cap, (sizeof(int) * nc1 + 255) & ~(size_t)255);
+    HIPCHK(c, hipMemsetAsync(cl.cnt.p, 0, fill, s));
+    cl.cnt_clean = fill / sizeof(int);
+  }  // (a smaller grid leaves the counters beyond it as clean as they were: a re-framed map's box breathes with the yaw)
+  return RGC_OK;
+}
+
+// Stage 5, the grid-build chain: count (a re-framed map is produced on the way), scan, place, gather
+static void prep_build_grid(rgc_ctx* c, Cloud& cl, bool is_target, hipStream_t s, bool fuse_reframe) {
+  const int n = cl.n, hi = is_target ? 0 : 1;  // the scan's kernels share CUs with the map's kNN launch: raised wave priority
+  int *cell_of = cl.cell_of.as<int>(), *start = cl.start.as<int>();
+  rgck::count_cells(s, cl.in, cl.stride_f, n, cl.grid, cell_of, cl.slot_of.as<int>(), cl.cnt.as<int>(), hi, guard_of(c, cl, is_target), fuse_reframe ? &cl.rf : nullptr);
+  rgck::scan_cells(s, cl.cnt.as<int>(), start, cl.grid.ncell + 1, cl.block_sums.p, is_target ? cl.cell_voxel.as<int>() : nullptr,
+                   is_target ? c->d_small + 7 : nullptr, hi, is_target ? nullptr : reinterpret_cast<float*>(c->d_small + 23));
+  const bool with_cache = is_target && &cl == &c->tgt && cl.cache_on;
+  const rgck::KnnSeeds sd = cloud_seeds(cl, is_target);
+  rgck::place(s, n, cell_of, cl.slot_of.as<int>(), start, cl.order_tmp.as<unsigned long long>(), hi, with_cache ? &sd.cache : nullptr);
+  rgck::rank_gather(s, cl.in, cl.stride_f, n, cell_of, start, cl.order_tmp.as<unsigned long long>(), cl.P.as<float4>(), cl.segs.as<int>(), hi,
+                    with_cache ? &sd.cache : nullptr);
+}
+
+static int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox = false) {
+  if (!is_target && &cl == &c->src) { c->src_held = c->src_hold_pending; c->src_hold_pending = false; }  // was THIS scan held? (the same contexts may run a frame at a time later)
+  const int n = cl.n;
+  cl.covs_user = false;
+  if (is_target && &cl == &c->tgt) {
+    c->tgt_generation++;       // borrowers of the previous target must share again
+    c->tgt_owner = nullptr;    // (a borrowed target's aliases are dropped buffer by buffer in ensure())
+  }
+  hipStream_t s = is_target ? c->stream : c->stream2;
+  int rc;
+  if ((rc = prep_order_streams(c, is_target))) return rc;
   {
     ProfScope ps(c, RGC_K_GRID, n, s);
     // bbox accumulators + flag; the map's copy also zeroes [7], its voxel counter ([8] ncorr stays untouched; the scan's
@@ -240,233 +506,28 @@ static int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox 
     if (!c->small_clean[is_target ? 0 : 1]) {
       const int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
       const size_t init_bytes = 8 * sizeof(int);  // the scan's eighth int (d_small[23]) is its sum of count^2, a float accumulated by the cell scan
-      memcpy(hsm, init, init_bytes);
-      HIPCHK(c, hipMemcpyAsync(dsm, hsm, init_bytes, hipMemcpyHostToDevice, s));
+      memcpy(c->h_small + small_off(is_target), init, init_bytes);
+      HIPCHK(c, hipMemcpyAsync(c->d_small + small_off(is_target), c->h_small + small_off(is_target), init_bytes, hipMemcpyHostToDevice, s));
     }
     c->small_clean[is_target ? 0 : 1] = false;  // this preparation uses it
-    // Speculative grid: consecutive clouds of a sequence cover (almost) the same cells, so the previous grid -- widened by two
-    // cells in x and y, one in z -- is re-used WITHOUT the bounding-box kernel and its host round trip (the only synchronisation
-    // between setInputTarget and the end of align).  A larger bounding grid changes nothing in the results: cells keep their
-    // relative order (voxel ids come from the cell scan), neighbourhoods are the same.  k_count guards it; the guard comes home
-    // with the LM state (or is read by the first other consumer) and a miss re-prepares the cloud on its own bounding box.
     // The scan's kNN grid need not be the voxel grid (only the map's doubles as the voxel map), and the exact search returns the
     // same neighbours on any grid: a raw 64-beam sweep puts thousands of points into the 1 m cells near the sensor (every query
     // scans its whole cell: O(c^2)), so its cell size follows the crowding measured on the previous frame of the sequence.
     const double res = is_target ? c->prm.voxel_res : (c->src_res > 0.0 ? c->src_res : (c->src_res_auto > 0.0 ? c->src_res_auto : c->prm.voxel_res));
-    bool spec = c->spec_on && !c->lm_host && cl.spec_ok && cl.spec_grid.res == res && !force_bbox;
-    const rgc_ctx::BoxHint* hint = (is_target && c->spec_on && !c->lm_host && !force_bbox) ? find_hint(c, cl.in, n) : nullptr;
-    if (hint)  // (a box that is not one -- it was derived from a pose that was not finite -- is no hint: the float -> int conversions below are undefined on it)
-      for (int a = 0; a < 3; a++)
-        if (!(std::isfinite(hint->lo[a]) && std::isfinite(hint->hi[a]) && hint->hi[a] >= hint->lo[a] && std::fabs(hint->lo[a]) <= 1.0e8 && std::fabs(hint->hi[a]) <= 1.0e8)) { hint = nullptr; break; }
-    rgck::Grid g{};
-    if (hint) {  // the box is known (rgc_set_target_reframed / rgc_transform_cloud): its cells plus one on every side, guarded like a speculative grid
-      int lo[3], dm[3];
-      double ncell = 1.0;
-      for (int a = 0; a < 3; a++) {
-        lo[a] = (int)std::floor(hint->lo[a] / res - 0.5) - 1;
-        dm[a] = (int)std::floor(hint->hi[a] / res - 0.5) + 1 - lo[a] + 1;
-        ncell *= (double)dm[a];
-      }
-      if (ncell <= (double)c->prm.max_cells && ncell <= 2.0e9) g = rgck::make_grid(lo, dm, res);
-      else hint = nullptr;
-    }
-    // A re-framed map (rgc_set_target_reframed) has not been written yet.  With its box known the counting pass below produces it on
-    // the way (one pass over the map and one launch less); any other route measures the cloud first and needs it in memory.
+    const rgc_ctx::BoxHint* hint = nullptr;
+    const bool guarded = prep_known_grid(c, cl, is_target, force_bbox, res, &hint);
     const bool fuse_reframe = cl.reframe_pending && hint != nullptr && cl.stride_f == 4 && ((uintptr_t)cl.in & 15) == 0;  // (k_count<true> stores float4)
-    if (cl.reframe_pending && !fuse_reframe)
-      rgck::transform_q(s, cl.rf.src, cl.rf.src_stride_f, n, cl.rf.q, cl.rf.t, const_cast<float*>(cl.in), 4);
-    // Seeds of the exact search: a re-framed map is the point set of cl.rf.src moved rigidly, so what the last search of that buffer found
-    // bounds this one (rgck::KnnSeeds; exactness does not depend on it).  Any other target: no seeds.
-    cl.seed_on = false;
-    if (is_target && &cl == &c->tgt && cl.reframe_pending && c->seeds_on && !general_route(c) && rgck::knn_seeds_apply(n, c->prm.k_correspondences)) {
-      int rc;
-      if (cl.seed_key != (const void*)cl.rf.src || cl.seed_n != n || !cl.seed.p) {
-        if ((rc = ensure(c, cl.seed, sizeof(float) * (size_t)n))) return rc;
-        HIPCHK(c, hipMemsetAsync(cl.seed.p, 0x7f, sizeof(float) * (size_t)n, s));  // 3.4e38: "no seed"
-        cl.seed_key = cl.rf.src;
-        cl.seed_n = n;
-        cl.seed_warm = false;
-      }
-      cl.seed_on = true;
-      // the coordinates' fp32 rounding, twice (two frames), on either end of a distance: 4 ulp of the largest coordinate of the box
-      double maxabs = 1.0;
-      if (hint) for (int a = 0; a < 3; a++) maxabs = std::max(maxabs, std::max(std::fabs(hint->lo[a]), std::fabs(hint->hi[a])));
-      else maxabs = 1024.0;
-      int e2;
-      (void)std::frexp(1.5 * maxabs, &e2);
-      cl.seed_slack = (float)(4.0 * std::ldexp(1.0, e2 - 24));
-      // The neighbour lists on top (rgck::KnnCache): the counting pass that produces the map compares it with the library's copy on the
-      // way, so only that route has them; a lazy target searches a part of the map per frame and keeps none.
-      const double qn = cl.rf.q.x * cl.rf.q.x + cl.rf.q.y * cl.rf.q.y + cl.rf.q.z * cl.rf.q.z + cl.rf.q.w * cl.rf.q.w;
-      cl.cache_on = false;
-      // (the certificate's error budget is that of a RIGID motion: reframe_point applies v + 2w(u x v) + 2u x (u x v) as Eigen does, without
-      // normalising q, so |q|^2 - 1 shows up as a relative error of that order on every distance.  1e-9 is far inside the 4e-6 the
-      // certificate allows for and is met by any quaternion normalised in fp64; one normalised in fp32 gets seeds, not lists.)
-      bool lists = c->cache_on && fuse_reframe && c->lazy_margin <= 0 && std::fabs(qn - 1.0) < 1.0e-9;
-      const size_t cap = (size_t)std::max(256, n / (4 * rgck::kTodoLists) + 1);
-      if (lists) {
-        // The lists are an optimisation: if the device cannot hold them (112 B per point) the context goes down to the seeds and carries on.
-        const size_t want[7] = {sizeof(int) * (size_t)n * 20, sizeof(int) * (size_t)n, sizeof(int) * (size_t)n, sizeof(int) * (size_t)n,
-                                sizeof(float4) * (size_t)n, sizeof(int) * cap * rgck::kTodoLists, sizeof(int) * (rgck::kTodoLists + 16)};
-        DevBuf* bufs[7] = {&cl.nbr, &cl.pos_of, &cl.rank_of, &cl.qrank, &cl.map_copy, &cl.todo, &cl.cache_small};
-        for (int b = 0; b < 7 && lists; b++)
-          if (ensure(c, *bufs[b], want[b]) != RGC_OK) lists = false;
-        if (c->test_fail_cache_alloc) lists = false;  // (RGC_TEST_FAIL_CACHE_ALLOC at rgc_create: a test's way to walk the path below, as if the device were full)
-        if (!lists) {
-          (void)hipGetLastError();
-          for (DevBuf* b : bufs) release(*b);
-          c->cache_on = false;
-          c->cache_dropped = true;
-          cl.cache_live = false;
-          static const bool trace = getenv("RGC_TRACE_ALLOC") != nullptr;
-          if (trace) fprintf(stderr, "[rgc] neighbour lists of %d points do not fit on the device: this context keeps seeds only from here on\n", n);
-        }
-      }
-      if (lists) {
-        bool fresh = !cl.seed_warm || !cl.cache_live || !cl.nbr.p;
-        cl.todo_cap = (int)cap;
-        int ce2;  // (a cell of margin around the box, as the grid has)
-        (void)std::frexp(1.5 * maxabs + 2.0 * res, &ce2);
-        // larger coordinates than the certificates allow for: issue them again.  Smaller ones for sixteen frames in a row: new certificates
-        // need the smaller gap only (the old ones, issued for a wider one, stand).
-        if (fresh || ce2 > cl.cache_e2) { cl.cache_e2 = ce2; fresh = true; }
-        if (ce2 < cl.cache_e2) {
-          cl.cache_e2_low_max = cl.cache_e2_low ? std::max(cl.cache_e2_low_max, ce2) : ce2;
-          if (++cl.cache_e2_low >= 16) { cl.cache_e2 = cl.cache_e2_low_max; cl.cache_e2_low = 0; }  // (the largest of those sixteen frames)
-        } else {
-          cl.cache_e2_low = 0;
-        }
-        if (cl.cache_frame >= (1 << 30)) { cl.cache_frame = 0; fresh = true; }
-        cl.cache_frame++;
-        if (fresh) HIPCHK(c, hipMemsetAsync(cl.cache_small.p, 0, sizeof(int) * (rgck::kTodoLists + 16), s));  // (list lengths, epoch, overflow)
-        cl.rf.copy = (float4*)cl.map_copy.p;
-        cl.rf.epoch = (int*)cl.cache_small.p + rgck::kTodoLists;
-        cl.rf.frame = cl.cache_frame;
-        cl.rf.force = fresh ? 1 : 0;
-        cl.cache_on = true;
-      }
-    } else if (is_target && &cl == &c->tgt) {
-      cl.seed_key = nullptr;
-      cl.cache_on = false;
-    }
-    if (is_target && &cl == &c->tgt) {
-      cl.cache_live = false;  // (set again by the search that attaches the lists, cloud_covariances)
-      cl.searched_known = -1;
-      if (!cl.cache_on) { cl.rf.copy = nullptr; cl.rf.epoch = nullptr; }
-    }
-    cl.reframe_pending = false;
-    if (hint) {
-      spec = true;
-      cl.spec_used = true;
-      cl.spec_ok = true;
-      cl.spec_grid = g;
-    } else if (spec) {
-      g = cl.spec_grid;
-      cl.spec_used = true;
-    } else {
-      cl.spec_used = false;
-      rgck::bbox(s, cl.in, cl.stride_f, n, res, dsm, dsm + 6, hi);
-      HIPCHK(c, hipMemcpyAsync(hsm, dsm, 7 * sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHK(c, hipStreamSynchronize(s));
-      if (hsm[6]) return fail(c, RGC_ERR_NONFINITE, "%s cloud contains non-finite or absurd coordinates", is_target ? "target" : "source");
-      double ncell = 1.0;
-      for (int a = 0; a < 3; a++) {
-        g.minc[a] = hsm[a];
-        g.dim[a] = hsm[3 + a] - hsm[a] + 1;
-        ncell *= (double)g.dim[a];
-      }
-      if (ncell > (double)c->prm.max_cells || ncell > 2.0e9)
-        return fail(c, RGC_ERR_GRID_TOO_LARGE, "%s grid %d x %d x %d exceeds max_cells", is_target ? "target" : "source", g.dim[0], g.dim[1], g.dim[2]);
-      g.res = res;
-      g.inv_res = rgck::grid_inv_res(res);
-      g.ncell = (int)ncell;
-      // The grid the NEXT cloud will try.  The map's box is stable and its grid large: 2 / 2 / 1 cells of margin.  A raw scan's box
-      // jumps with every far return, but it stays inside the sensor's range envelope and its grid is small: 16 / 16 / 4 cells of
-      // margin, united with the box tried before (a miss costs the scan's whole preparation and a second solve, so the box only
-      // ever grows -- at most to four times the measured one).
-      rgck::Grid w = g;
-      double wcell = 1.0;
-      for (int a = 0; a < 3; a++) {
-        const int m = is_target ? (a < 2 ? 2 : 1) : (a < 2 ? 16 : 4);
-        int lo = g.minc[a] - m, hi = g.minc[a] + g.dim[a] - 1 + m;
-        if (!is_target && cl.spec_ok && cl.spec_grid.res == g.res) {
-          lo = std::min(lo, cl.spec_grid.minc[a]);
-          hi = std::max(hi, cl.spec_grid.minc[a] + cl.spec_grid.dim[a] - 1);
-        }
-        w.minc[a] = lo; w.dim[a] = hi - lo + 1;
-        wcell *= (double)w.dim[a];
-      }
-      if (!is_target && wcell > 4.0 * ncell + 1.0e6) {  // the union ran away (a sequence that really moves its box): start over from this cloud
-        wcell = 1.0;
-        for (int a = 0; a < 3; a++) { const int m = a < 2 ? 16 : 4; w.minc[a] = g.minc[a] - m; w.dim[a] = g.dim[a] + 2 * m; wcell *= (double)w.dim[a]; }
-      }
-      w.ncell = (int)wcell;
-      cl.spec_ok = wcell <= (double)c->prm.max_cells && wcell <= 2.0e9;
-      cl.spec_grid = w;
-      if (cl.spec_ok) {  // its cell arrays now, in the frame that is slow anyway, not in the next one
-        const size_t wc1 = (size_t)w.ncell + 1;
-        int rc;
-        if ((rc = ensure(c, cl.cnt, sizeof(int) * wc1 + 256))) return rc;
-        if ((rc = ensure(c, cl.start, sizeof(int) * wc1))) return rc;
-        if ((rc = ensure(c, cl.block_sums, sizeof(long long) * (wc1 / 2048 + 2)))) return rc;
-        if (is_target && (rc = ensure(c, cl.cell_voxel, sizeof(int) * (size_t)w.ncell))) return rc;
-        if (is_target) {  // ... and the voxel table (80 B per cell of a map denser than its grid: 1.3 GB at 16 M cells -- growing it in the next
-                          // frame, when the widened grid is first used, was a 77 ms allocation inside c5's three timed frames on a fresh box)
-          const size_t vw = (size_t)(n < w.ncell ? n : w.ncell);
-          if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kVoxRec * vw))) return rc;
-          if ((rc = ensure(c, cl.vox_cell, sizeof(int) * vw))) return rc;
-        }
-      }
-    }
-    cl.grid = g;
-    const size_t nc1 = (size_t)g.ncell + 1;  // counters (+ sentinel)
-    const size_t ntot = nc1;
-    int rc;
-    if ((rc = ensure(c, cl.cell_of, sizeof(int) * n))) return rc;
-    if ((rc = ensure(c, cl.slot_of, sizeof(int) * n))) return rc;
-    // (a hinted box is that of a map re-framed by the vehicle's pose: as the yaw changes it swings between the map's own box and one
-    // with twice the cells -- the cell arrays are sized for the largest it can get, once, not grown a few per cent per frame)
-    size_t want_cells = ntot;
-    if (hint && hint->reach_xy > 0) {
-      const double e = hint->reach_xy / res + 6.0, ez = hint->reach_z / res + 6.0;
-      const double cells = e * e * ez * 1.05;
-      if (cells < 2.0e9 && cells <= (double)c->prm.max_cells && (size_t)cells > want_cells) want_cells = (size_t)cells;
-    }
-    if ((rc = ensure(c, cl.cnt, sizeof(int) * std::max(ntot, want_cells) + 256))) return rc;
-    if ((rc = ensure(c, cl.start, sizeof(int) * std::max(nc1, want_cells)))) return rc;
-    if ((rc = ensure(c, cl.block_sums, sizeof(long long) * (std::max(ntot, want_cells) / 2048 + 2)))) return rc;
-    if ((rc = ensure(c, cl.order_tmp, sizeof(long long) * n))) return rc;
-    if ((rc = ensure(c, cl.P, sizeof(float4) * ((size_t)n + 4)))) return rc;
-    if ((rc = ensure(c, cl.segs, rgck::deferred_bytes(n)))) return rc;
-    if ((rc = ensure(c, cl.nx, sizeof(double) * n))) return rc;
-    if ((rc = ensure(c, cl.ny, sizeof(double) * n))) return rc;
-    if ((rc = ensure(c, cl.nz, sizeof(double) * n))) return rc;
-    if (is_target && (rc = ensure(c, cl.cell_voxel, sizeof(int) * std::max((size_t)g.ncell, want_cells)))) return rc;
-    if (cl.cnt.p != cl.cnt_seen) { cl.cnt_clean = 0; cl.cnt_seen = cl.cnt.p; }  // re-allocated: contents unknown
-    if (cl.cnt_clean < ntot) {  // first use or a larger grid; afterwards the scan leaves the counters clean: no fill kernel per frame
-      const size_t fill = std::min(cl.cnt.cap, (sizeof(int) * ntot + 255) & ~(size_t)255);
-      HIPCHK(c, hipMemsetAsync(cl.cnt.p, 0, fill, s));
-      cl.cnt_clean = fill / sizeof(int);
-    }  // (a smaller grid leaves the counters beyond it as clean as they were: a re-framed map's box breathes with the yaw)
-    rgck::count_cells(s, cl.in, cl.stride_f, n, g, (int*)cl.cell_of.p, (int*)cl.slot_of.p, (int*)cl.cnt.p, hi, spec ? dsm + 6 : nullptr,
-                      fuse_reframe ? &cl.rf : nullptr);
-    rgck::scan_cells(s, (int*)cl.cnt.p, (int*)cl.start.p, (int)ntot, cl.block_sums.p, is_target ? (int*)cl.cell_voxel.p : nullptr,
-                     is_target ? c->d_small + 7 : nullptr, hi, is_target ? nullptr : (float*)(c->d_small + 23));
-    const bool with_cache = is_target && &cl == &c->tgt && cl.cache_on;
-    const rgck::KnnSeeds sd = cloud_seeds(cl, is_target);
-    rgck::place(s, n, (const int*)cl.cell_of.p, (const int*)cl.slot_of.p, (const int*)cl.start.p, (unsigned long long*)cl.order_tmp.p, hi,
-                with_cache ? &sd.cache : nullptr);
-    rgck::rank_gather(s, cl.in, cl.stride_f, n, (const int*)cl.cell_of.p, (const int*)cl.start.p, (const unsigned long long*)cl.order_tmp.p,
-                      (float4*)cl.P.p, (int*)cl.segs.p, hi, with_cache ? &sd.cache : nullptr);
+    if ((rc = prep_reuse(c, cl, is_target, s, hint, fuse_reframe, res))) return rc;
+    cl.spec_used = guarded;
+    if (!guarded && (rc = prep_measured_grid(c, cl, is_target, res, s))) return rc;
+    if ((rc = prep_size_buffers(c, cl, is_target, s, hint))) return rc;
+    prep_build_grid(c, cl, is_target, s, fuse_reframe);
   }
   cl.lazy = 0;
   if (is_target && &cl == &c->tgt && c->lazy_margin > 0 && !c->lm_host && !general_route(c) && map_wide_r_of(c, cl) == 0) {
     // lazy target: which part of the map needs covariances and voxels is decided by the solve's guess (rgc_align_begin: lazy_build);
     // any other consumer completes the map first (validate_clouds)
-    int rc;
-    const size_t vmax = (size_t)(n < cl.grid.ncell ? n : cl.grid.ncell);
-    if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kVoxRec * vmax))) return rc;
-    if ((rc = ensure(c, cl.vox_cell, sizeof(int) * vmax))) return rc;
+    if ((rc = ensure_voxel_table(c, cl, cl.grid.ncell))) return rc;
     cl.lazy = 1;
     cl.nvox = -1;
     HIPCHK(c, hipGetLastError());
@@ -475,10 +536,7 @@ static int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox 
     return RGC_OK;
   }
   cl.prepared_recorded = false;
-  {
-    int rc = cloud_covariances(c, cl, is_target);
-    if (rc) return rc;
-  }
+  if ((rc = cloud_covariances(c, cl, is_target))) return rc;
   HIPCHK(c, hipGetLastError());
   if (!is_target) {
     HIPCHK(c, hipEventRecord(c->src_ready, s));
@@ -493,17 +551,17 @@ static int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox 
 static rgck::KnnSeeds cloud_seeds(const Cloud& cl, bool is_target) {
   rgck::KnnSeeds sd;
   if (is_target && cl.seed_on) {
-    sd.seed = (float*)cl.seed.p; sd.slack = cl.seed_slack; sd.warm = cl.seed_warm;
+    sd.seed = cl.seed.as<float>(); sd.slack = cl.seed_slack; sd.warm = cl.seed_warm;
     if (cl.cache_on) {
       rgck::KnnCache& kc = sd.cache;
-      kc.nbr = (int*)cl.nbr.p;
-      kc.pos_of = (int*)cl.pos_of.p;
-      kc.rank_of = (int*)cl.rank_of.p;
-      kc.qrank = (int*)cl.qrank.p;
-      kc.todo = (int*)cl.todo.p;
-      kc.todo_cnt = (int*)cl.cache_small.p;
-      kc.epoch = (int*)cl.cache_small.p + rgck::kTodoLists;
-      kc.overflow = (int*)cl.cache_small.p + rgck::kTodoLists + 1;
+      kc.nbr = cl.nbr.as<int>();
+      kc.pos_of = cl.pos_of.as<int>();
+      kc.rank_of = cl.rank_of.as<int>();
+      kc.qrank = cl.qrank.as<int>();
+      kc.todo = cl.todo.as<int>();
+      kc.todo_cnt = cl.cache_small.as<int>();
+      kc.epoch = cl.cache_small.as<int>() + rgck::kTodoLists;
+      kc.overflow = cl.cache_small.as<int>() + rgck::kTodoLists + 1;
       kc.frame = cl.cache_frame;
       kc.todo_cap = cl.todo_cap;
       // what the coordinates' fp32 rounding in two frames can move a distance by, twice: 4 sqrt(3) ulp of the largest coordinate, and a tenth
@@ -532,148 +590,126 @@ static int rbf_reach(const rgck::Grid& g, double max_dist, double* reach_dist) {
 // written over them (slots_clean = false).
 static int slots_make_clean(rgc_ctx* c, Cloud& cl, hipStream_t s) {
   if (cl.slots_clean && cl.slots_seen == cl.segs.p && cl.slots_cap == cl.segs.cap) return RGC_OK;  // (a new allocation may come back at the old address)
-  HIPCHK(c, hipMemsetAsync((int*)cl.segs.p + 16, rgck::kDeferredSlotEmptyByte, cl.segs.cap - 16 * sizeof(int), s));
+  HIPCHK(c, hipMemsetAsync(cl.segs.as<int>() + 16, rgck::kDeferredSlotEmptyByte, cl.segs.cap - 16 * sizeof(int), s));
   cl.slots_clean = true;
   cl.slots_seen = cl.segs.p;
   cl.slots_cap = cl.segs.cap;
   return RGC_OK;
 }
 
+// The general covariance route (general_route above): every point through the cooperative search (or its RBF ball), a 3x3 per point, a
+// plain voxel pass.  (The deferred-list counter is zeroed by the grid build and stays zero: no query is deferred on this route.)
+static int cloud_covariances_general(rgc_ctx* c, Cloud& cl, bool is_target, hipStream_t s) {
+  const int n = cl.n;
+  int rc;
+  if ((rc = ensure(c, cl.c6, sizeof(double) * 6 * (size_t)n))) return rc;
+  const int* guard = guard_of(c, cl, is_target);
+  {
+    ProfScope ps(c, is_target ? RGC_K_KNN_COV : RGC_K_KNN_COV_SRC, n, s);
+    if (c->cov_method == RGC_COV_RBF) {
+      const float md = (float)c->rbf_max_dist;
+      double reach_dist;
+      const int reach = rbf_reach(cl.grid, c->rbf_max_dist, &reach_dist);
+      rgck::rbf_cov6(s, cl.sorted(), (float)c->rbf_width, md * md, reach, reach_dist, c->reg_method, cl.c6.as<double>(), guard);
+    } else {
+      rgck::knn_cov6(s, cl.sorted(), c->prm.k_correspondences, c->reg_method, cl.c6.as<double>(), guard);
+    }
+  }
+  if (is_target) {
+    if ((rc = ensure_voxel_table(c, cl, cl.grid.ncell))) return rc;
+    ProfScope ps(c, RGC_K_VOXEL, n);
+    rgck::voxel_build_general(s, cl.sorted(), cl.c6.as<double>(), cl.voxels(), c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE ? 1 : 0, guard);
+    cl.nvox = -1;
+    cl.cache_searched_lists = false;
+  }
+  return RGC_OK;
+}
+
+// How a cloud's covariances (and the map's voxels) are enqueued, decided before anything is: what the bulk launch is asked for beyond the
+// search (`bulk`: the sparse map's wider block, the seeds) and which stages go inside it.
+struct CovRoute {
+  rgck::KnnBulkOpts bulk;
+  // The dense map's launch (the dominant kernel) is timed by ITS OWN start / stop times (hipExtLaunchKernelGGL fills the two events):
+  // two hipEventRecord packets around it cost ~3 % of a frame of a dependent sequence on two contexts (bench.py's timed region).
+  bool self_timed;
+  // The dense map's launch over the whole map also builds the voxel records of its workgroups' own cells and resolves its deferred
+  // queries in-launch (rgck::KnnBulkOpts::fuse; voxel_seams behind it) -- unless the stage-by-stage profile wants the voxel or the cooperative
+  // stage apart, or RGC_VOXEL_IMPL=separate.  A target shared or bound to the rolling map keeps the stages apart as well.
+  // Nor, unless RGC_VOXEL_IMPL=fused, a context whose last scan was not held behind another context's target (rgc_hold_source_until_target_of:
+  // a pipelined sequence).  There the scan is prepared on the second stream BESIDE this launch, and its one-wave search (154 VGPRs: 160
+  // allocated) gets onto a SIMD when ONE of the map's five 88-register waves retires (72 + 88 free) -- with the cooperative waves inlined
+  // the map's kernel allocates 96, two must retire, and the scan's search took 160 us instead of 91: a frame one at a time 11 % slower
+  // (EXPERIMENTS.md round 16).  A pipelined context prepares its scan under the other context's solve, not beside its own map's search.
+  bool fused;
+  // the scan: its deferred queries are resolved by the last workgroups of the same launch (coop_stream) -- unless the stage-by-stage
+  // profile wants the two apart
+  bool stream_coop;
+};
+static CovRoute cov_route(const rgc_ctx* c, const Cloud& cl, bool is_target) {
+  const int n = cl.n, k = c->prm.k_correspondences;
+  CovRoute r{};
+  r.bulk.wide_r = is_target ? map_wide_r_of(c, cl) : 0;
+  r.bulk.seeds = cloud_seeds(cl, is_target);
+  r.self_timed = profiled(c, is_target ? RGC_K_KNN_COV : RGC_K_KNN_COV_SRC) && rgck::knn_bulk_times_itself(is_target, n, k, r.bulk);
+  const bool stage_prof = profiled(c, RGC_K_VOXEL) || profiled(c, RGC_K_KNN_COOP);
+  const bool want = c->voxel_impl == 2 || (c->voxel_impl == 0 && c->src_held);
+  r.fused = is_target && &cl == &c->tgt && !c->tgt_owner && !c->map_bound && want && !stage_prof && k <= 32 && rgck::knn_bulk_fuses_voxels(true, n, k, r.bulk);
+  r.stream_coop = !is_target && c->coop_stream_on && k <= 32 && !profiled(c, RGC_K_KNN_COOP_SRC);
+  return r;
+}
+
 // C2 / C3 of a cloud whose grid is built: exact-kNN covariances (+ the Gaussian voxel map for the target), enqueued on the cloud's stream.
 static int cloud_covariances(rgc_ctx* c, Cloud& cl, bool is_target) {
   const int n = cl.n, k = c->prm.k_correspondences;
   hipStream_t s = is_target ? c->stream : c->stream2;
-  int* dsm = c->d_small + (is_target ? 0 : 16);
+  int rc;
   cl.general = general_route(c);
-  if (cl.general) {  // the general covariance route (general_route above): every point through the cooperative search, a 3x3 per point
-    int rc;
-    if ((rc = ensure(c, cl.c6, sizeof(double) * 6 * (size_t)n))) return rc;
-    const int* guard = cl.spec_used ? dsm + 6 : nullptr;
-    {
-      ProfScope ps(c, is_target ? RGC_K_KNN_COV : RGC_K_KNN_COV_SRC, n, s);
-      if (c->cov_method == RGC_COV_RBF) {
-        const float md = (float)c->rbf_max_dist;
-        double reach_dist;
-        const int reach = rbf_reach(cl.grid, c->rbf_max_dist, &reach_dist);
-        rgck::rbf_cov6(s, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, (float)c->rbf_width, md * md, reach, reach_dist, c->reg_method,
-                       (double*)cl.c6.p, guard);
-      } else {
-        rgck::knn_cov6(s, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, c->reg_method, (double*)cl.c6.p, guard);
-      }
-    }
-    if (is_target) {
-      const size_t vmax = (size_t)(n < cl.grid.ncell ? n : cl.grid.ncell);
-      if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kVoxRec * vmax))) return rc;
-      if ((rc = ensure(c, cl.vox_cell, sizeof(int) * vmax))) return rc;
-      ProfScope ps(c, RGC_K_VOXEL, n);
-      rgck::voxel_build_general(s, (const float4*)cl.P.p, (const double*)cl.c6.p, (const int*)cl.start.p, cl.grid, n, (const int*)cl.cell_voxel.p,
-                                (double*)cl.vox.p, (int*)cl.vox_cell.p, c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE ? 1 : 0, guard);
-      cl.nvox = -1;
-      cl.cache_searched_lists = false;
-    }
-    // (the deferred-list counter is zeroed by the grid build and stays zero: no query is deferred on this route)
-    return RGC_OK;
+  if (cl.general) return cloud_covariances_general(c, cl, is_target, s);
+  const CovRoute rt = cov_route(c, cl, is_target);
+  rgck::KnnBulkOpts o = rt.bulk;
+  if (rt.fused) {
+    if ((rc = ensure_voxel_table(c, cl, cl.grid.ncell))) return rc;  // (the launch writes the voxel records: allocated here, not below)
+    o.fuse = cl.voxels();
   }
-  bool stream_coop = false, fused = false;
+  // a launch that resolves its deferred queries itself needs the entry words "empty" on entry: filled once per allocation, the readers
+  // put it back.  Any other writes the plain list over the slots (a cloud can change roles: rgc_swap_source_and_target)
+  if (rt.fused || rt.stream_coop) {
+    if ((rc = slots_make_clean(c, cl, s))) return rc;
+    o.coop_waves = coop_waves_est(cl);
+  } else {
+    cl.slots_clean = false;
+  }
+  const rgck::SortedCloud sc = cl.sorted();
+  const rgck::Normals nrm = cl.normals();
+  const rgck::DeferredBuf df = cl.deferred(guard_of(c, cl, is_target));
   {
-    // a sparse map (points per cell of its grid below map_wide_density): the wider block, see k_knn_sp_wide
-    const int wide_r = is_target ? map_wide_r_of(c, cl) : 0;
-    const int kind = is_target ? RGC_K_KNN_COV : RGC_K_KNN_COV_SRC;
-    // The dense map's launch (the dominant kernel) is timed by ITS OWN start / stop times (hipExtLaunchKernelGGL fills the two events):
-    // two hipEventRecord packets around it cost ~3 % of a frame of a dependent sequence on two contexts (bench.py's timed region).
-    ProfRegion own{};
-    bool self_timed = false;
-    if (c->prof_on && ((c->prof_mask >> kind) & 1u) && rgck::knn_bulk_times_itself(is_target, wide_r)) {
-      auto get = [&](hipEvent_t* e) {
-        if (!c->ev_pool.empty()) { *e = c->ev_pool.back(); c->ev_pool.pop_back(); return true; }
-        return hipEventCreate(e) == hipSuccess;
-      };
-      self_timed = get(&own.a);
-      if (self_timed && !get(&own.b)) { c->ev_pool.push_back(own.a); self_timed = false; }
-      own.kind = kind;
-      own.points = n;
-    }
-    const rgck::KnnSeeds seeds = cloud_seeds(cl, is_target);
-    // The dense map's launch over the whole map also builds the voxel records of its workgroups' own cells and resolves its deferred
-    // queries in-launch (rgck::VoxFuse; voxel_seams behind it) -- unless the stage-by-stage profile wants the voxel or the cooperative
-    // stage apart, or RGC_VOXEL_IMPL=separate.  A target shared or bound to the rolling map keeps the stages apart as well.
-    rgck::VoxFuse vf{};
-    const bool stage_prof = c->prof_on && (((c->prof_mask >> RGC_K_VOXEL) & 1u) || ((c->prof_mask >> RGC_K_KNN_COOP) & 1u));
-    // Nor, unless RGC_VOXEL_IMPL=fused, a context whose last scan was not held behind another context's target (rgc_hold_source_until_target_of:
-    // a pipelined sequence).  There the scan is prepared on the second stream BESIDE this launch, and its one-wave search (154 VGPRs: 160
-    // allocated) gets onto a SIMD when ONE of the map's five 88-register waves retires (72 + 88 free) -- with the cooperative waves inlined
-    // the map's kernel allocates 96, two must retire, and the scan's search took 160 us instead of 91: a frame one at a time 11 % slower
-    // (EXPERIMENTS.md round 16).  A pipelined context prepares its scan under the other context's solve, not beside its own map's search.
-    const bool want = c->voxel_impl == 2 || (c->voxel_impl == 0 && c->src_held);
-    fused = is_target && &cl == &c->tgt && !c->tgt_owner && !c->map_bound && want && !stage_prof && k <= 32 &&
-            rgck::knn_bulk_fuses_voxels(true, n, k, wide_r, nullptr, seeds);
-    if (fused) {
-      int rc;
-      const size_t vmax = (size_t)(n < cl.grid.ncell ? n : cl.grid.ncell);  // (the launch writes the voxel records: allocated here, not below)
-      if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kVoxRec * vmax))) return rc;
-      if ((rc = ensure(c, cl.vox_cell, sizeof(int) * vmax))) return rc;
-      if ((rc = slots_make_clean(c, cl, s))) return rc;  // the entry words "empty" on entry: filled once per allocation, the last reader puts it back
-      vf = rgck::VoxFuse{(const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p,
-                         cl.deferred_seen >= 0 ? cl.deferred_seen + cl.deferred_seen / 4 + 32 : n / 64 + 32};
-    } else if (is_target) {
-      cl.slots_clean = false;
-    }
-    if (self_timed) {
-      rgck::knn_bulk(s, is_target, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, cl.segs.p, (double*)cl.nx.p, (double*)cl.ny.p,
-                     (double*)cl.nz.p, cl.spec_used ? dsm + 6 : nullptr, wide_r, own.a, own.b, nullptr, nullptr, 0, seeds, 0, fused ? &vf : nullptr);
-      c->prof_open.push_back(own);
-    } else {
-      // the scan: its deferred queries are resolved by the last workgroups of the same launch (coop_stream) -- unless the stage-by-stage
-      // profile wants the two apart.  The entry words must be "empty" on entry: filled once per allocation, the readers put it back.
-      const int coop_waves_s = cl.deferred_seen >= 0 ? cl.deferred_seen + cl.deferred_seen / 4 + 32 : n / 64 + 32;
-      stream_coop = !is_target && c->coop_stream_on && k <= 32 && !(c->prof_on && ((c->prof_mask >> RGC_K_KNN_COOP_SRC) & 1u));
-      if (stream_coop) {
-        int rc = slots_make_clean(c, cl, s);
-        if (rc) return rc;
-      }
-      if (!stream_coop && !fused) cl.slots_clean = false;  // (the plain list will be written over the slots; a cloud can change roles: rgc_swap_source_and_target)
-      ProfScope ps(c, kind, n, s);
-      rgck::knn_bulk(s, is_target, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, cl.segs.p, (double*)cl.nx.p, (double*)cl.ny.p,
-                     (double*)cl.nz.p, cl.spec_used ? dsm + 6 : nullptr, wide_r, nullptr, nullptr, nullptr, nullptr, 0, seeds, stream_coop ? coop_waves_s : 0,
-                     fused ? &vf : nullptr);
-    }
-    if (is_target) cl.cache_searched_lists = seeds.cache.nbr && seeds.warm && wide_r == 0;
-    if (seeds.seed && wide_r == 0) {
-      cl.seed_warm = true;
-      if (seeds.cache.nbr) cl.cache_live = true;
-    }
+    ProfScope ps(c, is_target ? RGC_K_KNN_COV : RGC_K_KNN_COV_SRC, n, s, /*records=*/!rt.self_timed);
+    if (rt.self_timed && ps.on) { o.ev0 = ps.r.a; o.ev1 = ps.r.b; }
+    rgck::knn_bulk(s, is_target, sc, k, df, nrm, o);
+  }
+  if (is_target) cl.cache_searched_lists = o.seeds.cache.nbr && o.seeds.warm && o.wide_r == 0;
+  if (o.seeds.seed && o.wide_r == 0) {
+    cl.seed_warm = true;
+    if (o.seeds.cache.nbr) cl.cache_live = true;
   }
   // The map's deferred queries (~100 of a million, one wave each: 20 us of latency) are resolved in the SAME launch as the voxel map's
-  // build (k_voxel_build_coop); the few voxels that hold one are recomputed behind it (k_voxel_patch).  The scan has no voxel map:
-  // its chain stays serial.
-  const bool coop_beside = is_target;  // (`fused`: inside the bulk launch itself, and the voxel map with them; k_voxel_seams below finishes it)
-  // grid of the cooperative launch: twice the deferred count of the previous cloud prepared here (consecutive clouds of a sequence
-  // defer about the same queries), n / 64 for the first one
-  const int coop_waves = cl.deferred_seen >= 0 ? cl.deferred_seen + cl.deferred_seen / 4 + 32 : n / 64 + 32;
-  if (!coop_beside && !stream_coop) {
-    ProfScope ps(c, is_target ? RGC_K_KNN_COOP : RGC_K_KNN_COOP_SRC, n, s);
-    rgck::knn_coop(s, is_target, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, cl.segs.p, (double*)cl.nx.p,
-                   (double*)cl.ny.p, (double*)cl.nz.p, cl.spec_used ? dsm + 6 : nullptr, coop_waves);
+  // build (k_voxel_build_coop); the few voxels that hold one are recomputed behind it (k_voxel_patch).  (`fused`: inside the bulk launch
+  // itself, and the voxel map with them; k_voxel_seams finishes it.)  The scan has no voxel map: its chain stays serial.
+  if (!is_target && !rt.stream_coop) {
+    ProfScope ps(c, RGC_K_KNN_COOP_SRC, n, s);
+    rgck::knn_coop(s, false, sc, k, df, nrm, coop_waves_est(cl));
   }
   if (is_target) {
-    int rc;
-    const size_t vmax = (size_t)(n < cl.grid.ncell ? n : cl.grid.ncell);
-    if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kVoxRec * vmax))) return rc;
-    if ((rc = ensure(c, cl.vox_cell, sizeof(int) * vmax))) return rc;
+    if ((rc = ensure_voxel_table(c, cl, cl.grid.ncell))) return rc;
+    const rgck::VoxelMap vm = cl.voxels();
     ProfScope ps(c, RGC_K_VOXEL, n);
-    if (fused) {
-      rgck::voxel_seams(s, (const float4*)cl.P.p, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p, (const int*)cl.start.p, cl.grid, n,
-                        cl.segs.p, (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p, cl.spec_used ? dsm + 6 : nullptr,
-                        cl.deferred_seen >= 0 ? 2 * cl.deferred_seen + 64 : n, c->prep_event_ext ? c->tgt_prepared : nullptr);
+    if (rt.fused) {
+      rgck::voxel_seams(s, sc, nrm, vm, df, patch_waves_est(cl), c->prep_event_ext ? c->tgt_prepared : nullptr);
       cl.prepared_recorded = c->prep_event_ext;
     } else {
-      rgck::voxel_build_coop(s, (const float4*)cl.P.p, (double*)cl.nx.p, (double*)cl.ny.p, (double*)cl.nz.p, (const int*)cl.start.p, cl.grid, n,
-                             (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p, k, cl.segs.p, cl.spec_used ? dsm + 6 : nullptr, coop_waves,
-                             cloud_seeds(cl, true));
-      rgck::voxel_patch(s, (const float4*)cl.P.p, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p, (const int*)cl.start.p,
-                        cl.grid, cl.segs.p, (const int*)cl.cell_voxel.p, (double*)cl.vox.p, cl.deferred_seen >= 0 ? 2 * cl.deferred_seen + 64 : n,
-                        (c->prep_event_ext && &cl == &c->tgt) ? c->tgt_prepared : nullptr);
+      rgck::voxel_build_coop(s, sc, nrm, vm, k, df, coop_waves_est(cl), o.seeds);
       cl.prepared_recorded = c->prep_event_ext && &cl == &c->tgt;
+      rgck::voxel_patch(s, sc, nrm, vm, df, patch_waves_est(cl), cl.prepared_recorded ? c->tgt_prepared : nullptr);
     }
     cl.nvox = -1;  // fetched lazily
   }
@@ -705,27 +741,29 @@ static int lazy_build(rgc_ctx* c, const float guess[16]) {
   }
   double T[16];
   for (int i = 0; i < 16; i++) T[i] = (double)guess[i];
-  int* counts = (int*)cl.segs.p + 1;  // [0] listed queries, [1] listed cells: behind the deferred-query counter, zeroed with it by k_rank_gather
-  const int* guard = cl.spec_used ? c->d_small + 6 : nullptr;
-  rgck::footprint(s, c->src.in, c->src.stride_f, c->src.n, pose_from(T), cl.grid, (int*)cl.need.p, cl.need_stamp, c->lazy_margin, (const float4*)cl.P.p, n,
-                  (const int*)cl.start.p, (int*)cl.qlist.p, (int*)cl.cell_list.p, counts, guard);
-  const int q_est = cl.lazy_nq_seen >= 0 ? cl.lazy_nq_seen + cl.lazy_nq_seen / 4 + 4096 : n;
+  int* counts = cl.segs.as<int>() + 1;  // [0] listed queries, [1] listed cells: behind the deferred-query counter, zeroed with it by k_rank_gather
+  const rgck::SortedCloud sc = cl.sorted();
+  const rgck::Normals nrm = cl.normals();
+  const rgck::VoxelMap vm = cl.voxels();
+  const rgck::DeferredBuf df = cl.deferred(guard_of(c, cl, true));
+  rgck::footprint(s, c->src.in, c->src.stride_f, c->src.n, pose_from(T), sc, cl.need.as<int>(), cl.need_stamp, c->lazy_margin, cl.qlist.as<int>(),
+                  cl.cell_list.as<int>(), counts, df.guard);
   const int c_est = cl.lazy_ncell_seen >= 0 ? cl.lazy_ncell_seen + cl.lazy_ncell_seen / 4 + 1024 : n / 8 + 1024;
   cl.slots_clean = false;  // (the plain deferred list is written over the entry words)
   {
+    rgck::KnnBulkOpts o;
+    o.qlist = cl.qlist.as<int>();
+    o.nq = counts;
+    o.q_est = cl.lazy_nq_seen >= 0 ? cl.lazy_nq_seen + cl.lazy_nq_seen / 4 + 4096 : n;
+    o.seeds = cloud_seeds(cl, true);
     ProfScope ps(c, RGC_K_KNN_COV, n, s);
-    rgck::knn_bulk(s, true, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, n, k, cl.segs.p, (double*)cl.nx.p, (double*)cl.ny.p, (double*)cl.nz.p,
-                   guard, 0, nullptr, nullptr, (const int*)cl.qlist.p, counts, q_est, cloud_seeds(cl, true));
+    rgck::knn_bulk(s, true, sc, k, df, nrm, o);
     if (cl.seed_on) cl.seed_warm = true;
   }
   {
-    const int coop_waves = cl.deferred_seen >= 0 ? cl.deferred_seen + cl.deferred_seen / 4 + 32 : n / 64 + 32;
     ProfScope ps(c, RGC_K_VOXEL, n);
-    rgck::voxel_cells_coop(s, (const float4*)cl.P.p, (double*)cl.nx.p, (double*)cl.ny.p, (double*)cl.nz.p, (const int*)cl.start.p, cl.grid, n,
-                           (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p, k, cl.segs.p, guard, coop_waves, (const int*)cl.cell_list.p,
-                           counts + 1, c_est, cloud_seeds(cl, true));
-    rgck::voxel_patch(s, (const float4*)cl.P.p, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p, (const int*)cl.start.p,
-                      cl.grid, cl.segs.p, (const int*)cl.cell_voxel.p, (double*)cl.vox.p, cl.deferred_seen >= 0 ? 2 * cl.deferred_seen + 64 : n);
+    rgck::voxel_cells_coop(s, sc, nrm, vm, k, df, coop_waves_est(cl), cl.cell_list.as<int>(), counts + 1, c_est, cloud_seeds(cl, true));
+    rgck::voxel_patch(s, sc, nrm, vm, df, patch_waves_est(cl));
   }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->tgt_prepared, s));  // (the map's preparation ends HERE now: what the solve goes behind, what another context's held scan waits for)
@@ -784,7 +822,7 @@ int set_cloud(rgc_ctx* c, Cloud& cl, bool is_target, const float* xyz, int n, in
       HIPCHK(c, hipEventRecord(c->src_in_ready, c->stream2));
       c->src_in_pending = true;
     }
-    cl.in = (const float*)cl.in_copy.p;
+    cl.in = cl.in_copy.as<const float>();
     // (a box known for the caller's HOST buffer -- the leaf filter's output, rgc_voxelgrid -- goes with the cloud to its device copy)
     if (is_target) {
       if (const rgc_ctx::BoxHint* h = find_hint(c, xyz, n)) { const rgc_ctx::BoxHint hh = *h; put_hint(c, cl.in, n, hh.lo, hh.hi); }
@@ -858,8 +896,7 @@ static int resolve_guards(rgc_ctx* c, int guard_t, int guard_s) {
     c->corr_valid = c->gicp_valid = false;
     c->deferred_known = false;
     if (gd[a] & 1) { cl[a]->n = 0; return fail(c, RGC_ERR_NONFINITE, "%s cloud contains non-finite or absurd coordinates", a == 0 ? "target" : "source"); }
-    static const bool trace = getenv("RGC_TRACE_ALLOC") != nullptr;
-    if (trace) fprintf(stderr, "[rgc] %s cloud left its speculative grid: prepared again\n", a == 0 ? "target" : "source");
+    if (trace_alloc()) fprintf(stderr, "[rgc] %s cloud left its speculative grid: prepared again\n", a == 0 ? "target" : "source");
     if (a == 0) drop_hints(c);  // (a hinted box that did not hold: its buffer was rewritten behind the library's back -- measure again)
     int rc = prepare_cloud(c, *cl[a], a == 0, /*force_bbox=*/true);
     if (rc) { cl[a]->n = 0; return rc; }
@@ -881,9 +918,7 @@ int check_target_owner(rgc_ctx* c) {
   }
   if (!alive) {  // its device buffers are gone with it
     c->tgt_owner = nullptr;
-    for (DevBuf* b : {&c->tgt.in_copy, &c->tgt.cell_of, &c->tgt.slot_of, &c->tgt.cnt, &c->tgt.start, &c->tgt.block_sums, &c->tgt.order_tmp, &c->tgt.P,
-                      &c->tgt.nx, &c->tgt.ny, &c->tgt.nz, &c->tgt.segs, &c->tgt.cell_voxel, &c->tgt.vox, &c->tgt.vox_cell, &c->tgt.c6})
-      release(*b);
+    for (DevBuf* b : shared_bufs(c->tgt)) release(*b);
     c->tgt.ready = false;
     c->tgt.n = 0;
     return fail(c, RGC_ERR_NO_INPUT, "the context whose target this one shared has been destroyed");
@@ -934,27 +969,34 @@ void unpack_system(const double sums[28], double H[36], double b[6]) {
   for (int a = 0; a < 6; a++) b[a] = sums[21 + a];
 }
 
+// the scan linearised at T against the map's voxels, on the route the scan was prepared on: the 28 sums to d_out, the count to d_small[8]
+static void enqueue_linearize(rgc_ctx* c, const double T[16], int noff, int want_H) {
+  const Cloud& src = c->src;
+  double* partials = c->partials.as<double>();
+  int* ipartials = c->ipartials.as<int>();
+  if (src.general)
+    rgck::linearize_general(c->stream, src.sorted(), src.c6.as<double>(), pose_from(T), c->tgt.grid, c->tgt.voxels(), noff, corr_of(c), want_H, partials,
+                            ipartials, c->d_out, c->d_small + 8);
+  else
+    rgck::linearize(c->stream, src.sorted(), src.normals(), pose_from(T), c->tgt.grid, c->tgt.voxels(), noff, corr_of(c), want_H, partials, ipartials,
+                    c->d_out, c->d_small + 8);
+}
+// the first ndoubles of the output block, home (one synchronisation)
+static int fetch_out(rgc_ctx* c, size_t ndoubles) {
+  HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double) * ndoubles, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
 static int do_linearize(rgc_ctx* c, const double T[16], double* H, double* b, double* cost) {
   int rc = need_inputs(c);
   if (rc) return rc;
   const int n = c->src.n, noff = noff_of(c->prm.neighbor_method);
-  if ((rc = ensure(c, c->corr_v, sizeof(int) * (size_t)n * noff))) return rc;
-  if ((rc = ensure(c, c->corr_M, sizeof(double) * 6 * (size_t)n * noff))) return rc;
-  const int nb = rgck::linearize_blocks(n);
-  if ((rc = ensure(c, c->partials, sizeof(double) * rgck::kAccum * (size_t)nb))) return rc;
-  if ((rc = ensure(c, c->ipartials, sizeof(int) * (size_t)nb))) return rc;
+  if ((rc = ensure_corr(c, n, noff, rgck::kAccum))) return rc;
   const int want = (H && b) ? 1 : 0;
   {
     ProfScope ps(c, RGC_K_LINEARIZE, n);
-    if (c->src.general)
-      rgck::linearize_general(c->stream, (const float4*)c->src.P.p, (const double*)c->src.c6.p, n, pose_from(T), c->tgt.grid, (const int*)c->tgt.cell_voxel.p,
-                              (const double*)c->tgt.vox.p, noff, (int*)c->corr_v.p, (double*)c->corr_M.p, want, (double*)c->partials.p,
-                              (int*)c->ipartials.p, c->d_out, c->d_small + 8);
-    else
-    rgck::linearize(c->stream, (const float4*)c->src.P.p,
-                    (const double*)c->src.nx.p, (const double*)c->src.ny.p, (const double*)c->src.nz.p, n, pose_from(T), c->tgt.grid,
-                    (const int*)c->tgt.cell_voxel.p, (const double*)c->tgt.vox.p, noff, (int*)c->corr_v.p, (double*)c->corr_M.p, want,
-                    (double*)c->partials.p, (int*)c->ipartials.p, c->d_out, c->d_small + 8);
+    enqueue_linearize(c, T, noff, want);
   }
   HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double) * rgck::kAccum, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->h_small + 8, c->d_small + 8, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -977,35 +1019,22 @@ static int do_linearize_try(rgc_ctx* c, const double x0[16], double lambda, doub
   int rc = need_inputs(c);
   if (rc) return rc;
   const int n = c->src.n, noff = noff_of(c->prm.neighbor_method);
-  if ((rc = ensure(c, c->corr_v, sizeof(int) * (size_t)n * noff))) return rc;
-  if ((rc = ensure(c, c->corr_M, sizeof(double) * 6 * (size_t)n * noff))) return rc;
-  const int nb = rgck::linearize_blocks(n);
-  if ((rc = ensure(c, c->partials, sizeof(double) * rgck::kAccum * (size_t)nb))) return rc;
-  if ((rc = ensure(c, c->ipartials, sizeof(int) * (size_t)nb))) return rc;
+  if ((rc = ensure_corr(c, n, noff, rgck::kAccum))) return rc;
   rgck::LmIn in;
   for (int i = 0; i < 16; i++) in.x0[i] = x0[i];
   in.lambda = lambda;
   in.init_factor = c->prm.lm_init_lambda_factor;
   {
     ProfScope ps(c, RGC_K_LINEARIZE, n);
-    if (c->src.general)
-      rgck::linearize_general(c->stream, (const float4*)c->src.P.p, (const double*)c->src.c6.p, n, pose_from(x0), c->tgt.grid, (const int*)c->tgt.cell_voxel.p,
-                              (const double*)c->tgt.vox.p, noff, (int*)c->corr_v.p, (double*)c->corr_M.p, 1, (double*)c->partials.p,
-                              (int*)c->ipartials.p, c->d_out, c->d_small + 8);
-    else
-    rgck::linearize(c->stream, (const float4*)c->src.P.p, (const double*)c->src.nx.p, (const double*)c->src.ny.p, (const double*)c->src.nz.p, n,
-                    pose_from(x0), c->tgt.grid, (const int*)c->tgt.cell_voxel.p, (const double*)c->tgt.vox.p, noff, (int*)c->corr_v.p,
-                    (double*)c->corr_M.p, 1, (double*)c->partials.p, (int*)c->ipartials.p, c->d_out, c->d_small + 8);
+    enqueue_linearize(c, x0, noff, 1);
     rgck::lm_try(c->stream, c->d_out, c->d_small + 8, in);
   }
   {
     ProfScope ps(c, RGC_K_ERROR, n);
-    rgck::compute_error_dev(c->stream, (const float4*)c->src.P.p, n, c->d_out + 38, (const double*)c->tgt.vox.p, noff, (const int*)c->corr_v.p,
-                            (const double*)c->corr_M.p, (double*)c->partials.p, c->d_out + 56);
+    rgck::compute_error_dev(c->stream, c->src.P.as<const float4>(), n, c->d_out + 38, c->tgt.vox.as<const double>(), noff, corr_of(c),
+                            c->partials.as<double>(), c->d_out + 56);
   }
-  HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double) * 57, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
+  if ((rc = fetch_out(c, 57))) return rc;
   c->corr_noff = noff;
   c->corr_n = n;
   c->corr_valid = true;
@@ -1028,13 +1057,10 @@ static int do_error(rgc_ctx* c, const double T[16], double* cost) {
   const int n = c->corr_n;
   {
     ProfScope ps(c, RGC_K_ERROR, n);
-    rgck::compute_error(c->stream, (const float4*)c->src.P.p, n, pose_from(T),
-                        (const double*)c->tgt.vox.p, c->corr_noff, (const int*)c->corr_v.p, (const double*)c->corr_M.p,
-                        (double*)c->partials.p, c->d_out);
+    rgck::compute_error(c->stream, c->src.P.as<const float4>(), n, pose_from(T), c->tgt.vox.as<const double>(), c->corr_noff, corr_of(c),
+                        c->partials.as<double>(), c->d_out);
   }
-  HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
+  if ((rc = fetch_out(c, 1))) return rc;
   c->stats.n_error++;
   *cost = c->h_out[0];
   return RGC_OK;
@@ -1047,12 +1073,9 @@ int do_fitness(rgc_ctx* c, const float T[16], double* out) {
   if ((rc = ensure(c, c->partials, sizeof(double) * (size_t)rgck::fitness_blocks(n) + 64))) return rc;
   {
     ProfScope ps(c, RGC_K_FITNESS, n);
-    rgck::fitness(c->stream, (const float4*)c->src.P.p, n, posef_from(T), (const float4*)c->tgt.P.p, (const int*)c->tgt.start.p,
-                  c->tgt.grid, (double*)c->partials.p, c->d_out, c->tgt.n);
+    rgck::fitness(c->stream, c->src.P.as<const float4>(), n, posef_from(T), c->tgt.sorted(), c->partials.as<double>(), c->d_out, /*scan_small_map=*/true);
   }
-  HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
+  if ((rc = fetch_out(c, 1))) return rc;
   *out = c->h_out[0] / (double)n;
   return RGC_OK;
 }
@@ -1090,10 +1113,10 @@ int build_measured_grid(rgc_ctx* c, Cloud& cl, double cell, int* dsm, int* hsm, 
   if ((rc = ensure(c, cl.order_tmp, sizeof(long long) * n))) return rc;
   if ((rc = ensure(c, cl.P, sizeof(float4) * ((size_t)n + 4)))) return rc;
   HIPCHK(c, hipMemsetAsync(cl.cnt.p, 0, (sizeof(int) * nc1 + 255) & ~(size_t)255, s));
-  rgck::count_cells(s, cl.in, cl.stride_f, n, g, (int*)cl.cell_of.p, (int*)cl.slot_of.p, (int*)cl.cnt.p);
-  rgck::scan_cells(s, (int*)cl.cnt.p, (int*)cl.start.p, (int)nc1, cl.block_sums.p, with_voxels ? (int*)cl.cell_voxel.p : nullptr, with_voxels ? dsm + 7 : nullptr);
-  rgck::place(s, n, (const int*)cl.cell_of.p, (const int*)cl.slot_of.p, (const int*)cl.start.p, (unsigned long long*)cl.order_tmp.p);
-  rgck::rank_gather(s, cl.in, cl.stride_f, n, (const int*)cl.cell_of.p, (const int*)cl.start.p, (const unsigned long long*)cl.order_tmp.p, (float4*)cl.P.p);
+  rgck::count_cells(s, cl.in, cl.stride_f, n, g, cl.cell_of.as<int>(), cl.slot_of.as<int>(), cl.cnt.as<int>());
+  rgck::scan_cells(s, cl.cnt.as<int>(), cl.start.as<int>(), (int)nc1, cl.block_sums.p, with_voxels ? cl.cell_voxel.as<int>() : nullptr, with_voxels ? dsm + 7 : nullptr);
+  rgck::place(s, n, cl.cell_of.as<int>(), cl.slot_of.as<int>(), cl.start.as<int>(), cl.order_tmp.as<unsigned long long>());
+  rgck::rank_gather(s, cl.in, cl.stride_f, n, cl.cell_of.as<int>(), cl.start.as<int>(), cl.order_tmp.as<unsigned long long>(), cl.P.as<float4>());
   return RGC_OK;
 }
 
@@ -1320,12 +1343,9 @@ int rgc_share_target(rgc_ctx* c, rgc_ctx* owner) {
   Cloud& d = c->tgt;
   const Cloud& o = owner->tgt;
   release_cloud(d);
-  DevBuf* db[] = {&d.in_copy, &d.cell_of, &d.slot_of, &d.cnt, &d.start, &d.block_sums, &d.order_tmp, &d.P, &d.nx, &d.ny, &d.nz, &d.segs,
-                  &d.cell_voxel, &d.vox, &d.vox_cell, &d.c6};
-  const DevBuf* ob[] = {&o.in_copy, &o.cell_of, &o.slot_of, &o.cnt, &o.start, &o.block_sums, &o.order_tmp, &o.P, &o.nx, &o.ny, &o.nz, &o.segs,
-                        &o.cell_voxel, &o.vox, &o.vox_cell, &o.c6};
+  const std::vector<DevBuf*> db = shared_bufs(d), ob = shared_bufs(owner->tgt);
   d.general = o.general;
-  for (size_t k = 0; k < sizeof(db) / sizeof(db[0]); k++) { db[k]->p = ob[k]->p; db[k]->cap = ob[k]->cap; db[k]->borrowed = ob[k]->p != nullptr; }
+  for (size_t k = 0; k < db.size(); k++) { db[k]->p = ob[k]->p; db[k]->cap = ob[k]->cap; db[k]->borrowed = ob[k]->p != nullptr; }
   d.in = o.in; d.stride_f = o.stride_f; d.n = o.n; d.grid = o.grid; d.grid = o.grid; d.nvox = o.nvox; d.deferred_seen = o.deferred_seen;
   d.spec_ok = false; d.spec_used = false; d.cnt_clean = 0; d.cnt_seen = nullptr; d.lazy = 0;
   d.ready = true;
@@ -1493,7 +1513,7 @@ static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, boo
   const int seq = want_fitness ? -c->lm_seq : c->lm_seq;  // what is posted: a finished state (> 0), or a finished state with its score (< 0)
   constexpr int kSpare = 3;
   // the stage-by-stage pass (events around the solve's regions) keeps the two apart: all steps, then the score
-  const bool staged = c->prof_on && ((c->prof_mask >> RGC_K_LINEARIZE) & 1u || (c->prof_mask >> RGC_K_FITNESS) & 1u);
+  const bool staged = profiled(c, RGC_K_LINEARIZE) || profiled(c, RGC_K_FITNESS);
   // The score is chained INTO the steps: the launch whose decision ends the solve scores the final pose and posts the result (k_lm_step).
   // No separate score launches, no blind steps between the deciding launch and the score.
   const bool fit_in_steps = want_fitness && !staged;
@@ -1502,31 +1522,25 @@ static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, boo
   // chained launches otherwise: the stage-by-stage profiling pass, a scan of more rows than CUs, a context without mapped host memory, and
   // RGC_LM_IMPL=chained -- and for any solve whose resident launch gave up (rgc_align_end).
   c->lm_resident = open && !staged && !c->lm_chained && post && nb_lm <= c->cu_count && nb_lm <= rgck::kLmSolveMaxGroups;
+  rgck::LmState* st = c->lm_state.as<rgck::LmState>();
+  const bool lazy = c->tgt.lazy == 2;
+  rgck::LmArgs a{};
+  a.src = c->src.sorted(); a.nrm = c->src.normals(); a.tgt = c->tgt.sorted(); a.vm = c->tgt.voxels();
+  a.noff = noff; a.corr[0] = corr_of(c); a.corr[1] = rgck::Corr{c->corr_v2.as<int>(), c->corr_M2.as<double>()};
+  a.partials = c->partials.as<double>(); a.st = st; a.nvox = c->d_small + 7; a.segs_t = c->tgt.segs.p; a.segs_s = c->src.segs.p;
+  a.h_post = post; a.seq = seq; a.fit_partials = fit_in_steps ? c->fit_partials.as<double>() : nullptr;
+  a.lazy_need = lazy ? c->tgt.need.as<const int>() : nullptr; a.lazy_stamp = c->tgt.need_stamp; a.lazy_counts = lazy ? c->tgt.segs.as<const int>() + 1 : nullptr;
+  a.h_early = (fit_in_steps && post) ? c->d_early : nullptr;
   if (c->lm_resident) {
-    rgck::lm_solve_resident(s, (const float4*)c->src.P.p, (const double*)c->src.nx.p, (const double*)c->src.ny.p, (const double*)c->src.nz.p, n,
-                            c->tgt.grid, (const int*)c->tgt.cell_voxel.p, (const double*)c->tgt.vox.p, noff, (int*)c->corr_v.p, (double*)c->corr_M.p,
-                            (int*)c->corr_v2.p, (double*)c->corr_M2.p, (double*)c->partials.p, (rgck::LmState*)c->lm_state.p, *open, c->d_small + 7,
-                            c->tgt.segs.p, c->src.segs.p, post, seq, fit_in_steps ? (const float4*)c->tgt.P.p : nullptr,
-                            fit_in_steps ? (const int*)c->tgt.start.p : nullptr, fit_in_steps ? (double*)c->fit_partials.p : nullptr, c->tgt.n,
-                            c->tgt.lazy == 2 ? (const int*)c->tgt.need.p : nullptr, c->tgt.need_stamp, c->tgt.lazy == 2 ? (const int*)c->tgt.segs.p + 1 : nullptr,
-                            fit_in_steps ? c->d_early : nullptr, c->lm_give_up_at);
+    rgck::lm_solve_resident(s, a, *open, c->lm_give_up_at);
     c->lm_j = 1;  // the finished state is image 0
     HIPCHK(c, hipEventRecord(c->lm_tail, s));
     c->lm_tail_stream = s;
     return RGC_OK;
   }
-  auto step = [&](const rgck::LmInit* op, hipStream_t on) {
-    rgck::lm_step(on, (const float4*)c->src.P.p, (const double*)c->src.nx.p, (const double*)c->src.ny.p, (const double*)c->src.nz.p, n,
-                  c->tgt.grid, (const int*)c->tgt.cell_voxel.p, (const double*)c->tgt.vox.p, noff, (int*)c->corr_v.p, (double*)c->corr_M.p,
-                  (int*)c->corr_v2.p, (double*)c->corr_M2.p, (double*)c->partials.p, (rgck::LmState*)c->lm_state.p, c->lm_j++, op, c->d_small + 7,
-                  c->tgt.segs.p, c->src.segs.p, post, seq, fit_in_steps ? (const float4*)c->tgt.P.p : nullptr,
-                  fit_in_steps ? (const int*)c->tgt.start.p : nullptr, fit_in_steps ? (double*)c->fit_partials.p : nullptr, c->tgt.n,
-                  c->tgt.lazy == 2 ? (const int*)c->tgt.need.p : nullptr, c->tgt.need_stamp, c->tgt.lazy == 2 ? (const int*)c->tgt.segs.p + 1 : nullptr,
-                  (fit_in_steps && post) ? c->d_early : nullptr);
-  };
+  auto step = [&](const rgck::LmInit* op, hipStream_t on) { rgck::lm_step(on, a, c->lm_j++, op); };
   auto score = [&]() {  // getFitnessScore at the final pose, chained blindly (on the image the last launch left)
-    rgck::fitness_lm(s, (const float4*)c->src.P.p, n, rgck::lm_image((rgck::LmState*)c->lm_state.p, c->lm_j - 1), (const float4*)c->tgt.P.p,
-                     (const int*)c->tgt.start.p, c->tgt.grid, (double*)c->fit_partials.p, post, c->lm_seq, c->tgt.n);
+    rgck::fitness_lm(s, a.src, rgck::lm_image(st, c->lm_j - 1), a.tgt, c->fit_partials.as<double>(), post, c->lm_seq);
   };
   hipStream_t tail = s;
   if (staged) {
@@ -1556,7 +1570,7 @@ static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, boo
   }
   // (a solve that POSTS its finished state needs no stream-ordered copy of it: the one case that reads the state otherwise -- a batch that
   // ends without a finished solve -- fetches it with a blocking copy once the stream has drained, rgc_align_end)
-  if (!post) HIPCHK(c, hipMemcpyAsync(c->h_lm, rgck::lm_image((rgck::LmState*)c->lm_state.p, c->lm_j - 1), sizeof(rgck::LmState), hipMemcpyDeviceToHost, tail));
+  if (!post) HIPCHK(c, hipMemcpyAsync(c->h_lm, rgck::lm_image(st, c->lm_j - 1), sizeof(rgck::LmState), hipMemcpyDeviceToHost, tail));
   HIPCHK(c, hipEventRecord(c->lm_tail, tail));
   c->lm_tail_stream = tail;
   return RGC_OK;
@@ -1613,13 +1627,9 @@ int rgc_align_begin(rgc_ctx* c, const float guess[16], int want_fitness) {
   // device-chained LM: the loop of :65-75 / :125-172 runs as a state machine on the device (k_lm_step);
   // the host only enqueues slots and reads the state back once per batch.
   const int n = c->src.n, noff = noff_of(P.neighbor_method);
-  if ((rc = ensure(c, c->corr_v, sizeof(int) * (size_t)n * noff))) return rc;
-  if ((rc = ensure(c, c->corr_M, sizeof(double) * 6 * (size_t)n * noff))) return rc;
-  const int nb = rgck::linearize_blocks(n);
+  if ((rc = ensure_corr(c, n, noff, (rgck::kAccum + 2) * 2))) return rc;  // (two halves of kAccum + 2 doubles per workgroup: rgck::LmArgs)
   if ((rc = ensure(c, c->corr_v2, sizeof(int) * (size_t)n * noff))) return rc;
   if ((rc = ensure(c, c->corr_M2, sizeof(double) * 6 * (size_t)n * noff))) return rc;
-  if ((rc = ensure(c, c->partials, sizeof(double) * (rgck::kAccum + 2) * (size_t)nb * 2))) return rc;  // (two halves: rgck::lm_step)
-  if ((rc = ensure(c, c->ipartials, sizeof(int) * (size_t)nb))) return rc;
   if (!c->lm_state.p) {
     if ((rc = ensure(c, c->lm_state, rgck::kLmAreaBytes))) return rc;
     // the score's ticket, the lazy target's miss flag and the resident solve's flags and give-up word start at 0
@@ -1639,13 +1649,10 @@ int rgc_align_begin(rgc_ctx* c, const float guess[16], int want_fitness) {
   // (a solve of o outer iterations without a rejected try needs o + 2 launches: the opening linearisation, one per try, and the one
   // whose decision ends it and scores the pose.  That many plus one stay on the solve's stream -- a launch too many there costs ~5 us in
   // front of the next frame, one too few a ~13 us hop to the other stream --, three more go aside as spares: lm_enqueue_batch)
-  int batch = 9;
-  if (c->lm_last_outer + 6 > batch) batch = c->lm_last_outer + 6;
-  if (batch > P.max_iterations + 2) batch = P.max_iterations + 2;
-  if (batch < 2) batch = 2;
+  const int batch = std::max(2, std::min(std::max(9, c->lm_last_outer + 6), P.max_iterations + 2));
   if (c->lm_seq >= 0x3fffffff) {  // the solve numbers start over: neither a flag of the resident solve nor its give-up word may carry an old one (rgck::k_lm_solve)
     c->lm_seq = 0;
-    HIPCHK(c, hipMemsetAsync((char*)c->lm_state.p + 3080, 0, rgck::kLmAreaBytes - 3080, c->solve_stream));
+    HIPCHK(c, hipMemsetAsync(c->lm_state.as<char>() + 3080, 0, rgck::kLmAreaBytes - 3080, c->solve_stream));
   }
   c->lm_seq++;
   if (join_late && (rc = join_source(c))) return rc;
@@ -1707,7 +1714,7 @@ int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fit
       const bool keep = c->lm_chained;
       c->lm_chained = true;
       // (workgroups that had reached the score before the others gave up have taken tickets nobody collected)
-      HIPCHK(c, hipMemsetAsync((char*)c->lm_state.p + 3076, 0, 4, c->solve_stream));
+      HIPCHK(c, hipMemsetAsync(c->lm_state.as<char>() + 3076, 0, 4, c->solve_stream));
       rc = lm_enqueue_batch(c, c->pend.batch, &c->pend.in, want_fitness);
       c->lm_chained = keep;
       if (rc) return rc;
@@ -1719,7 +1726,7 @@ int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fit
         // on the solve's own stream, never with the blocking hipMemcpy: that one goes through the NULL stream, whose hardware queue the
         // runtime creates at its first use -- 9 ms inside whichever frame first needed more launches than its batch held (the node's
         // "one slow frame" of rounds 3 and 4: frame 14 of the c2 stand-in)
-        HIPCHK(c, hipMemcpyAsync(c->h_lm, rgck::lm_image((rgck::LmState*)c->lm_state.p, c->lm_j - 1), sizeof(rgck::LmState), hipMemcpyDeviceToHost,
+        HIPCHK(c, hipMemcpyAsync(c->h_lm, rgck::lm_image(c->lm_state.as<rgck::LmState>(), c->lm_j - 1), sizeof(rgck::LmState), hipMemcpyDeviceToHost,
                                  c->lm_tail_stream));
         HIPCHK(c, hipStreamSynchronize(c->lm_tail_stream));
       }
@@ -1733,24 +1740,22 @@ int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fit
   c->src_pending = false;  // the solve came after the scan's preparation and has finished (its spare launches may still drain: lm_tail)
   c->main_has_target_prep = false;  // (the solve came after the map's preparation)
   c->small_clean[0] = c->small_clean[1] = true;  // the solve re-initialised both blocks after capturing them (chained: its first step; resident: the workgroup that finished it)
+  auto solve_again = [&]() {  // from the same guess (a copy: rgc_align_begin writes c->pend)
+    float guess[16];
+    memcpy(guess, c->pend.guess, sizeof(guess));
+    return rgc_align(c, guess, final_T, final_H, fitness, iterations, converged, lm_failed);
+  };
   {  // a cloud that did not fit its speculative grid: everything above ran on a parked cloud -- prepare it properly, solve again
     const int r = resolve_guards(c, S.pad & 0xff, (S.pad >> 8) & 0xff);
     if (r < 0) return r;
-    if (r > 0) {
-      float guess[16];
-      memcpy(guess, c->pend.guess, sizeof(guess));
-      return rgc_align(c, guess, final_T, final_H, fitness, iterations, converged, lm_failed);
-    }
+    if (r > 0) return solve_again();
   }
   if (c->tgt.lazy == 2 && S.pad2) {
     // lazy target: a look-up landed on an occupied voxel outside the part that was built (the pose moved further from the guess than the
     // margin covers).  The map is completed and the solve repeated from the same guess: the full build's result, bit for bit.
     c->stats.lazy_misses++;
-    int rc2 = complete_target(c);
-    if (rc2) return rc2;
-    float guess[16];
-    memcpy(guess, c->pend.guess, sizeof(guess));
-    return rgc_align(c, guess, final_T, final_H, fitness, iterations, converged, lm_failed);
+    if ((rc = complete_target(c))) return rc;
+    return solve_again();
   }
   const int n = c->src.n, noff = noff_of(c->prm.neighbor_method);
   if (S.cur) { std::swap(c->corr_v, c->corr_v2); std::swap(c->corr_M, c->corr_M2); }  // corr_v / corr_M = the valid buffer
@@ -1851,7 +1856,7 @@ int rgc_get_aligned(rgc_ctx* c, const float T[16], float* out, int stride_bytes)
   int rc = join_source(c);
   if (rc) return rc;
   if ((rc = ensure(c, c->scratch, sizeof(float) * 3 * (size_t)n))) return rc;
-  rgck::transform_f32(c->stream, c->src.in, c->src.stride_f, n, posef_from(T), (float*)c->scratch.p, 3);
+  rgck::transform_f32(c->stream, c->src.in, c->src.stride_f, n, posef_from(T), c->scratch.as<float>(), 3);
   if (stride_bytes == 12) {
     HIPCHK(c, hipMemcpyAsync(out, c->scratch.p, sizeof(float) * 3 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   } else {
@@ -1873,13 +1878,13 @@ static int get_covs(rgc_ctx* c, Cloud& cl, double* cov9, double* normals) {
     if (normals) return fail(c, RGC_ERR_UNSUPPORTED, "normals exist only under RegularizationMethod PLANE with an additive voxel mode");
     if (!cov9) return RGC_OK;
     if ((rc = ensure(c, c->scratch, sizeof(double) * 9 * (size_t)n))) return rc;
-    rgck::unsort6(c->stream, (const double*)cl.c6.p, (const float4*)cl.P.p, n, (double*)c->scratch.p);
+    rgck::unsort6(c->stream, cl.c6.as<double>(), cl.P.as<float4>(), n, c->scratch.as<double>());
     HIPCHK(c, hipMemcpyAsync(cov9, c->scratch.p, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RGC_OK;
   }
   if ((rc = ensure(c, c->scratch, sizeof(double) * 3 * (size_t)n))) return rc;
-  rgck::unsort3(c->stream, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p, (const float4*)cl.P.p, n, (double*)c->scratch.p);
+  rgck::unsort3(c->stream, cl.nx.as<double>(), cl.ny.as<double>(), cl.nz.as<double>(), cl.P.as<float4>(), n, c->scratch.as<double>());
   std::vector<double> tmp;
   double* dst = normals;
   if (!dst) { tmp.resize((size_t)n * 3); dst = tmp.data(); }
@@ -1903,6 +1908,17 @@ int rgc_get_target_covariances(rgc_ctx* c, double* cov9, double* normals) { retu
 // computed from the 20 nearest neighbours.  This path keeps a covariance as its unit normal (C = I - 0.999 n n^T, the PLANE
 // regularisation, fast_gicp_impl.hpp:280-293 -- the only form the reference's odometer produces): matrices of that form are
 // accepted (to 1e-9), anything else is RGC_ERR_INVALID.  The target's voxel map is rebuilt from the new covariances.
+// covariances in the caller's point order on the device (general route: 9 doubles per point, else the unit normal) into the cloud's sorted
+// arrays, and the target's voxel map rebuilt from them
+static void enqueue_given_covs(rgc_ctx* c, Cloud& cl, bool is_target, const double* d_cov) {
+  if (cl.general) {
+    rgck::sort6(c->stream, d_cov, cl.P.as<float4>(), cl.n, cl.c6.as<double>());
+    if (is_target) rgck::voxel_build_general(c->stream, cl.sorted(), cl.c6.as<double>(), cl.voxels(), c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE ? 1 : 0, nullptr);
+  } else {
+    rgck::sort3(c->stream, d_cov, cl.P.as<float4>(), cl.n, cl.nx.as<double>(), cl.ny.as<double>(), cl.nz.as<double>());
+    if (is_target) rgck::voxel_build(c->stream, cl.sorted(), cl.normals(), cl.voxels());
+  }
+}
 static int set_covs(rgc_ctx* c, Cloud& cl, bool is_target, const double* cov9, int n) {
   if (!cov9) return RGC_ERR_INVALID;
   if (!cl.ready) return fail(c, RGC_ERR_NO_INPUT, "cloud not set");
@@ -1916,12 +1932,8 @@ static int set_covs(rgc_ctx* c, Cloud& cl, bool is_target, const double* cov9, i
     if ((rc = join_source(c))) return rc;
     if ((rc = ensure(c, c->scratch, sizeof(double) * 9 * (size_t)n))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->scratch.p, cov9, sizeof(double) * 9 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    rgck::sort6(c->stream, (const double*)c->scratch.p, (const float4*)cl.P.p, n, (double*)cl.c6.p);
-    if (is_target) {
-      rgck::voxel_build_general(c->stream, (const float4*)cl.P.p, (const double*)cl.c6.p, (const int*)cl.start.p, cl.grid, n, (const int*)cl.cell_voxel.p,
-                                (double*)cl.vox.p, (int*)cl.vox_cell.p, c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE ? 1 : 0, nullptr);
-      c->tgt_generation++;
-    }
+    enqueue_given_covs(c, cl, is_target, c->scratch.as<double>());
+    if (is_target) c->tgt_generation++;
     HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's array is read until here)
     HIPCHK(c, hipGetLastError());
     c->corr_valid = c->gicp_valid = false;
@@ -1949,12 +1961,8 @@ static int set_covs(rgc_ctx* c, Cloud& cl, bool is_target, const double* cov9, i
   if ((rc = join_source(c))) return rc;
   if ((rc = ensure(c, c->scratch, sizeof(double) * 3 * (size_t)n))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->scratch.p, nrm.data(), sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  rgck::sort3(c->stream, (const double*)c->scratch.p, (const float4*)cl.P.p, n, (double*)cl.nx.p, (double*)cl.ny.p, (double*)cl.nz.p);
-  if (is_target) {
-    rgck::voxel_build(c->stream, (const float4*)cl.P.p, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p, (const int*)cl.start.p,
-                      cl.grid, n, (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p);
-    c->tgt_generation++;   // borrowers of this target must share again
-  }
+  enqueue_given_covs(c, cl, is_target, c->scratch.as<double>());
+  if (is_target) c->tgt_generation++;   // borrowers of this target must share again
   HIPCHK(c, hipStreamSynchronize(c->stream));   // (the host vector goes out of scope)
   HIPCHK(c, hipGetLastError());
   c->corr_valid = c->gicp_valid = false;
@@ -1992,29 +2000,28 @@ int rgc_swap_source_and_target(rgc_ctx* c) {
   // Covariances the CALLER set travel with their cloud (the reference swaps source_covs_ and target_covs_, fast_vgicp_impl.hpp:46-53):
   // taken out in the caller's point order here, put back into the new ordering behind the preparation (computed ones are simply
   // computed again: the same function of the cloud).
-  struct Kept { bool on = false; void* p = nullptr; } kept[2];  // [0]: the old source's (-> new target), [1]: the old target's (-> new source)
+  struct Kept { bool on = false; double* p = nullptr; } kept[2];  // [0]: the old source's (-> new target), [1]: the old target's (-> new source)
   auto drop_kept = [&]() { for (auto& k : kept) if (k.p) { (void)hipFree(k.p); k.p = nullptr; } };
   {
     Cloud* from[2] = {&c->src, &c->tgt};
     for (int a = 0; a < 2; a++) {
       if (!from[a]->covs_user) continue;
       kept[a].on = true;
-      if (hipMalloc(&kept[a].p, sizeof(double) * (from[a]->general ? 9 : 3) * (size_t)from[a]->n) != hipSuccess) { drop_kept(); return fail(c, RGC_ERR_HIP, "hipMalloc failed (swap)"); }
-      if (from[a]->general) rgck::unsort6(c->stream, (const double*)from[a]->c6.p, (const float4*)from[a]->P.p, from[a]->n, (double*)kept[a].p);
-      else
-      rgck::unsort3(c->stream, (const double*)from[a]->nx.p, (const double*)from[a]->ny.p, (const double*)from[a]->nz.p, (const float4*)from[a]->P.p,
-                    from[a]->n, (double*)kept[a].p);
+      if (hipMalloc((void**)&kept[a].p, sizeof(double) * (from[a]->general ? 9 : 3) * (size_t)from[a]->n) != hipSuccess) { drop_kept(); return fail(c, RGC_ERR_HIP, "hipMalloc failed (swap)"); }
+      const Cloud& f = *from[a];
+      if (f.general) rgck::unsort6(c->stream, f.c6.as<double>(), f.P.as<float4>(), f.n, kept[a].p);
+      else rgck::unsort3(c->stream, f.nx.as<double>(), f.ny.as<double>(), f.nz.as<double>(), f.P.as<float4>(), f.n, kept[a].p);
     }
     if (hipStreamSynchronize(c->stream) != hipSuccess) { drop_kept(); return fail(c, RGC_ERR_HIP, "hipStreamSynchronize failed (swap)"); }
   }
   // A target bound to the resident map (rgc_map_commit) was set from the map's own filter output buffer, which the NEXT commit overwrites:
   // as the scan it would keep pointing there (tests/fuzz/fuzz_api.py: swapped back later, it was prepared from another cloud's
   // points).  It takes a copy of its own with it.
-  if (c->map_target.p && c->tgt.in == (const float*)c->map_target.p) {
+  if (c->map_target.p && c->tgt.in == c->map_target.as<const float>()) {
     const size_t bytes = (size_t)c->tgt.n * 16;
     if ((rc = ensure(c, c->tgt.in_copy, bytes))) { drop_kept(); return rc; }
     if (hipMemcpyAsync(c->tgt.in_copy.p, c->map_target.p, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); drop_kept(); return fail(c, RGC_ERR_HIP, "swap: copy of the map's target failed"); }
-    c->tgt.in = (const float*)c->tgt.in_copy.p;
+    c->tgt.in = c->tgt.in_copy.as<const float>();
     c->tgt.stride_f = 4;
   }
   std::swap(c->src.in_copy, c->tgt.in_copy);
@@ -2027,24 +2034,11 @@ int rgc_swap_source_and_target(rgc_ctx* c) {
   if ((rc = prepare_cloud(c, c->src, false, /*force_bbox=*/true))) { drop_kept(); return rc; }
   if (kept[0].on || kept[1].on) {
     hipError_t e = hipStreamSynchronize(c->stream2);
-    if (e == hipSuccess && kept[0].on) {  // the old source's covariances on the new target: normals, then its voxel map from them
-      Cloud& cl = c->tgt;
-      if (cl.general) {
-        rgck::sort6(c->stream, (const double*)kept[0].p, (const float4*)cl.P.p, cl.n, (double*)cl.c6.p);
-        rgck::voxel_build_general(c->stream, (const float4*)cl.P.p, (const double*)cl.c6.p, (const int*)cl.start.p, cl.grid, cl.n, (const int*)cl.cell_voxel.p,
-                                  (double*)cl.vox.p, (int*)cl.vox_cell.p, c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE ? 1 : 0, nullptr);
-      } else {
-      rgck::sort3(c->stream, (const double*)kept[0].p, (const float4*)cl.P.p, cl.n, (double*)cl.nx.p, (double*)cl.ny.p, (double*)cl.nz.p);
-      rgck::voxel_build(c->stream, (const float4*)cl.P.p, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p, (const int*)cl.start.p,
-                        cl.grid, cl.n, (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p);
-      }
-      cl.covs_user = true;
-    }
-    if (e == hipSuccess && kept[1].on) {
-      Cloud& cl = c->src;
-      if (cl.general) rgck::sort6(c->stream, (const double*)kept[1].p, (const float4*)cl.P.p, cl.n, (double*)cl.c6.p);
-      else rgck::sort3(c->stream, (const double*)kept[1].p, (const float4*)cl.P.p, cl.n, (double*)cl.nx.p, (double*)cl.ny.p, (double*)cl.nz.p);
-      cl.covs_user = true;
+    Cloud* to[2] = {&c->tgt, &c->src};  // the old source's covariances on the new target (normals, then its voxel map from them), the old target's on the new source
+    for (int a = 0; a < 2 && e == hipSuccess; a++) {
+      if (!kept[a].on) continue;
+      enqueue_given_covs(c, *to[a], a == 0, kept[a].p);
+      to[a]->covs_user = true;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     drop_kept();
@@ -2161,8 +2155,8 @@ RGC_API int rgc_lab_deferred(rgc_ctx* c, int is_target, int* idx, float* thr, in
   HIPCHK(c, hipMemcpy(&cnt, cl.segs.p, sizeof(int), hipMemcpyDeviceToHost));
   *count = cnt;
   const int m = cnt < cap ? cnt : cap;
-  HIPCHK(c, hipMemcpy(idx, (const int*)cl.segs.p + 16, sizeof(int) * m, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(thr, (const int*)cl.segs.p + 16 + cl.n, sizeof(float) * m, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(idx, cl.segs.as<const int>() + 16, sizeof(int) * m, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(thr, cl.segs.as<const int>() + 16 + cl.n, sizeof(float) * m, hipMemcpyDeviceToHost));
   return RGC_OK;
 }
 #endif

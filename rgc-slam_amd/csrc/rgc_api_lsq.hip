@@ -151,7 +151,7 @@ static int ndt_set_cloud(rgc_ctx* c, int which, const float* xyz, int n, int str
   if ((rc = ensure(c, cl.in_copy, (size_t)n * 12))) return rc;
   HIPCHK(c, hipMemcpy2DAsync(cl.in_copy.p, 12, xyz, (size_t)stride_bytes, 12, (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
   if (!on_device) HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller owns a host buffer for the duration of the call only
-  cl.in = (const float*)cl.in_copy.p;
+  cl.in = cl.in_copy.as<const float>();
   cl.stride_f = 3;
   cl.n = n;
   cl.ready = false;
@@ -206,7 +206,7 @@ static int ndt_build(rgc_ctx* c, int which) {
   int rc;
   if ((rc = ndt_scratch(c))) return rc;
   hipStream_t s = c->stream;
-  int* dsm = (int*)c->ndt_small.p;
+  int* dsm = c->ndt_small.as<int>();
   int* hsm = c->ndt_h_small;
   if ((rc = build_measured_grid(c, cl, res, dsm, hsm, true, which ? "NDT source" : "NDT target", which ? "NDT source: voxel grid" : "NDT target: voxel grid"))) return rc;
   HIPCHK(c, hipMemcpyAsync(hsm + 7, dsm + 7, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -216,7 +216,7 @@ static int ndt_build(rgc_ctx* c, int which) {
   if (nvox < 1 || nvox > cl.n) return fail(c, RGC_ERR_HIP, "NDT voxel count %d out of range", nvox);
   if ((rc = ensure(c, cl.vox, sizeof(double) * rgck::kNdtRec * (size_t)nvox))) return rc;
   if ((rc = ensure(c, cl.vox_cell, sizeof(int) * (size_t)nvox))) return rc;
-  rgck::ndt_voxels(s, (const float4*)cl.P.p, (const int*)cl.start.p, cl.grid, (const int*)cl.cell_voxel.p, (double*)cl.vox.p, (int*)cl.vox_cell.p);
+  rgck::ndt_voxels(s, cl.sorted(), cl.voxels());
   HIPCHK(c, hipGetLastError());
   cl.nvox = nvox;
   cl.ready = true;
@@ -261,9 +261,9 @@ static int ndt_run_terms(rgc_ctx* c, const double T[16], bool find, bool want_H,
   const int nb = rgck::ndt_blocks(n);
   if ((rc = ensure(c, c->ndt_partials, sizeof(double) * rgck::kAccum * (size_t)nb))) return rc;
   if ((rc = ensure(c, c->ndt_ipartials, sizeof(int) * (size_t)nb))) return rc;
-  rgck::ndt_terms(c->stream, d2d, find ? 1 : 0, sc.in, sc.stride_f, (const double*)sc.vox.p, n, pose_from(T), pose_from(c->ndt_Tlin), tg.grid,
-                  (const int*)tg.cell_voxel.p, (const double*)tg.vox.p, (const int*)c->ndt_offs.p, noff, (int*)c->ndt_corr.p, want_H ? 1 : 0,
-                  (double*)c->ndt_partials.p, (int*)c->ndt_ipartials.p, (double*)c->ndt_out.p);
+  rgck::ndt_terms(c->stream, d2d, find ? 1 : 0, sc.in, sc.stride_f, sc.vox.as<const double>(), n, pose_from(T), pose_from(c->ndt_Tlin), tg.grid,
+                  tg.voxels(), c->ndt_offs.as<const int>(), noff, c->ndt_corr.as<int>(), want_H ? 1 : 0,
+                  c->ndt_partials.as<double>(), c->ndt_ipartials.as<int>(), c->ndt_out.as<double>());
   HIPCHK(c, hipMemcpyAsync(c->ndt_h_out, c->ndt_out.p, sizeof(double) * 29, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
@@ -424,8 +424,8 @@ static int gicp_need_inputs(rgc_ctx* c) {
 }
 
 static rgck::GicpCov gicp_cov_of(const Cloud& cl) {
-  if (cl.general) return rgck::GicpCov{(const double*)cl.c6.p, nullptr, nullptr, nullptr};
-  return rgck::GicpCov{nullptr, (const double*)cl.nx.p, (const double*)cl.ny.p, (const double*)cl.nz.p};
+  if (cl.general) return rgck::GicpCov{cl.c6.as<const double>(), nullptr, nullptr, nullptr};
+  return rgck::GicpCov{nullptr, cl.nx.as<const double>(), cl.ny.as<const double>(), cl.nz.as<const double>()};
 }
 
 // update_correspondences + linearize (fast_gicp_impl.hpp:115-211); the inputs have been checked (gicp_need_inputs)
@@ -442,10 +442,9 @@ static int gicp_do_linearize(rgc_ctx* c, const double T[16], double* H, double* 
   float T32[16];
   for (int i = 0; i < 16; i++) T32[i] = (float)T[i];  // trans.cast<float>(), :119
   const int want = (H && b) ? 1 : 0;
-  rgck::gicp_correspond(c->stream, (const float4*)sc.P.p, n, posef_from(T32), (const float4*)tg.P.p, (const int*)tg.start.p, tg.grid,
-                        c->gicp_dmax * c->gicp_dmax, (int*)c->gicp_corr.p, (float*)c->gicp_key.p);
-  rgck::gicp_terms(c->stream, (const float4*)sc.P.p, n, (const float4*)tg.P.p, tg.n, (const int*)c->gicp_corr.p, gicp_cov_of(sc), gicp_cov_of(tg), pose_from(T),
-                   want, (double*)c->gicp_M.p, (double*)c->gicp_partials.p, (double*)c->gicp_out.p);
+  rgck::gicp_correspond(c->stream, sc.sorted(), posef_from(T32), tg.sorted(), c->gicp_dmax * c->gicp_dmax, c->gicp_corr.as<int>(), c->gicp_key.as<float>());
+  rgck::gicp_terms(c->stream, sc.sorted(), tg.sorted(), c->gicp_corr.as<const int>(), gicp_cov_of(sc), gicp_cov_of(tg), pose_from(T), want,
+                   c->gicp_M.as<double>(), c->gicp_partials.as<double>(), c->gicp_out.as<double>());
   HIPCHK(c, hipMemcpyAsync(c->gicp_h_out, c->gicp_out.p, sizeof(double) * (rgck::kAccum + 1), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
@@ -463,8 +462,8 @@ static int gicp_do_error(rgc_ctx* c, const double T[16], double* cost) {
   if (!c->gicp_valid || c->gicp_n != c->src.n) return fail(c, RGC_ERR_INVALID, "rgc_gicp_compute_error needs a preceding rgc_gicp_linearize on the present clouds");
   const Cloud& sc = c->src;
   const Cloud& tg = c->tgt;
-  rgck::gicp_error(c->stream, (const float4*)sc.P.p, sc.n, (const float4*)tg.P.p, tg.n, (const int*)c->gicp_corr.p, (const double*)c->gicp_M.p, pose_from(T),
-                   (double*)c->gicp_partials.p, (double*)c->gicp_out.p);
+  rgck::gicp_error(c->stream, sc.sorted(), tg.sorted(), c->gicp_corr.as<const int>(), c->gicp_M.as<const double>(), pose_from(T),
+                   c->gicp_partials.as<double>(), c->gicp_out.as<double>());
   HIPCHK(c, hipMemcpyAsync(c->gicp_h_out, c->gicp_out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
@@ -507,11 +506,11 @@ int rgc_gicp_get_correspondences(rgc_ctx* c, int* idx, float* sq_dist) {
   int rc = check_target_owner(c);
   if (rc) return rc;
   if ((rc = ensure(c, c->scratch, (sizeof(int) + sizeof(float)) * (size_t)n))) return rc;
-  int* d_idx = (int*)c->scratch.p;
+  int* d_idx = c->scratch.as<int>();
   float* d_sq = (float*)(d_idx + n);
   HIPCHK(c, hipMemsetAsync(d_idx, 0xff, sizeof(int) * (size_t)n, c->stream));
   HIPCHK(c, hipMemsetAsync(d_sq, 0, sizeof(float) * (size_t)n, c->stream));
-  rgck::gicp_export(c->stream, (const float4*)c->src.P.p, n, (const float4*)c->tgt.P.p, c->tgt.n, (const int*)c->gicp_corr.p, (const float*)c->gicp_key.p, d_idx, d_sq);
+  rgck::gicp_export(c->stream, c->src.sorted(), c->tgt.sorted(), c->gicp_corr.as<const int>(), c->gicp_key.as<const float>(), d_idx, d_sq);
   if (idx) HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   if (sq_dist) HIPCHK(c, hipMemcpyAsync(sq_dist, d_sq, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -16,7 +16,7 @@ constexpr double kMapregCell[2] = {1.0, 1.4143};
 int prepare_map_grid(rgc_ctx* c, Cloud& cl, double cell) {
   int rc, hsm[8];
   if ((rc = ensure(c, c->mr_small, 64))) return rc;
-  if ((rc = build_measured_grid(c, cl, cell, (int*)c->mr_small.p, hsm, false, "feature map", "feature-map grid"))) return rc;
+  if ((rc = build_measured_grid(c, cl, cell, c->mr_small.as<int>(), hsm, false, "feature map", "feature-map grid"))) return rc;
   HIPCHK(c, hipGetLastError());
   cl.ready = true;
   return RGC_OK;
@@ -173,8 +173,8 @@ int mapreg_eval(rgc_ctx* c, const int nfeat[4], const double x[14], bool want_H,
                 const rgc_mapreg_imu* imu, MapregSystem* out) {
   const float* feat[4];
   const double* fac[4];
-  for (int s = 0; s < 4; s++) { feat[s] = (const float*)c->mr_feat[s].p; fac[s] = (const double*)c->mr_fac[s].p; }
-  rgck::mapreg_terms(c->stream, feat, fac, nfeat, x, 0.1, want_H ? 1 : 0, (double*)c->mr_partials.p, c->d_out);
+  for (int s = 0; s < 4; s++) { feat[s] = c->mr_feat[s].as<const float>(); fac[s] = c->mr_fac[s].as<const double>(); }
+  rgck::mapreg_terms(c->stream, feat, fac, nfeat, x, 0.1, want_H ? 1 : 0, c->mr_partials.as<double>(), c->d_out);
   HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double) * 56, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
@@ -219,7 +219,7 @@ static int mapreg_set_maps_impl(rgc_ctx* c, const float* corner_map, int n_corne
     } else {
       if ((rc = ensure(c, cl.in_copy, bytes))) return rc;
       HIPCHK(c, hipMemcpyAsync(cl.in_copy.p, src[m], bytes - (stride_bytes - 12), hipMemcpyHostToDevice, c->stream));
-      cl.in = (const float*)cl.in_copy.p;
+      cl.in = cl.in_copy.as<const float>();
     }
     cl.stride_f = stride_bytes / 4;
     cl.n = n[m];
@@ -250,8 +250,8 @@ int rgc_mapreg_associate(rgc_ctx* c, int kind, const float* feat_xyzw, int n, co
   int rc = mapreg_upload_features(c, kind, feat_xyzw, n);
   if (rc) return rc;
   const Cloud& m = c->mr_map[kind];
-  const rgck::MapregAssoc one{(const float*)c->mr_feat[kind].p, n, kind == 0 ? 1 : 0, rgck::Quat{q_xyzw[0], q_xyzw[1], q_xyzw[2], q_xyzw[3]},
-                              {t[0], t[1], t[2]}, (const float4*)m.P.p, (const int*)m.start.p, m.grid, (double*)c->mr_fac[kind].p, nullptr};
+  const rgck::MapregAssoc one{c->mr_feat[kind].as<const float>(), n, kind == 0 ? 1 : 0, rgck::Quat{q_xyzw[0], q_xyzw[1], q_xyzw[2], q_xyzw[3]},
+                              {t[0], t[1], t[2]}, m.P.as<const float4>(), m.start.as<const int>(), m.grid, c->mr_fac[kind].as<double>(), nullptr};
   rgck::mapreg_associate(c->stream, &one, 1);
   std::vector<double> tmp;
   double* dst = factors8;
@@ -291,14 +291,14 @@ int rgc_mapreg_optimize(rgc_ctx* c, const float* corner_cur, int n_ccur, const f
   for (int iter = 0; iter < 2; iter++) {  // :1076
     // association at the current estimate of both poses (frozen during the solve); the factor counts (the reference's
     // corner_num / surf_num ...) ride home with the first evaluation's synchronisation
-    int* dcnt = (int*)c->mr_small.p + 8;
+    int* dcnt = c->mr_small.as<int>() + 8;
     HIPCHK(c, hipMemsetAsync(dcnt, 0, 4 * sizeof(int), c->stream));
     rgck::MapregAssoc sets[4];
     for (int s = 0; s < 4; s++) {
       const double* q = poses + 7 * (s / 2);
       const Cloud& m = c->mr_map[s & 1];
-      sets[s] = rgck::MapregAssoc{(const float*)c->mr_feat[s].p, nfeat[s], (s & 1) == 0 ? 1 : 0, rgck::Quat{q[0], q[1], q[2], q[3]}, {q[4], q[5], q[6]},
-                                  (const float4*)m.P.p, (const int*)m.start.p, m.grid, (double*)c->mr_fac[s].p, dcnt + s};
+      sets[s] = rgck::MapregAssoc{c->mr_feat[s].as<const float>(), nfeat[s], (s & 1) == 0 ? 1 : 0, rgck::Quat{q[0], q[1], q[2], q[3]}, {q[4], q[5], q[6]},
+                                  m.P.as<const float4>(), m.start.as<const int>(), m.grid, c->mr_fac[s].as<double>(), dcnt + s};
     }
     rgck::mapreg_associate(c->stream, sets, 4);  // the four loops of :1092-1282 side by side
     HIPCHK(c, hipMemcpyAsync(c->h_small + 40, dcnt, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -389,14 +389,14 @@ int rgc_mapreg_linearize(rgc_ctx* c, const float* corner_cur, int n_ccur, const 
     if ((rc = mapreg_upload_features(c, s, feat[s], nfeat[s]))) return rc;
   const int nb = std::max(rgck::mapreg_blocks(n_ccur, n_scur), rgck::mapreg_blocks(n_clast, n_slast));
   if ((rc = ensure(c, c->mr_partials, sizeof(double) * 2 * rgck::kAccum * (size_t)(nb > 0 ? nb : 1)))) return rc;
-  int* dcnt = (int*)c->mr_small.p + 8;
+  int* dcnt = c->mr_small.as<int>() + 8;
   HIPCHK(c, hipMemsetAsync(dcnt, 0, 4 * sizeof(int), c->stream));
   rgck::MapregAssoc sets[4];
   for (int s = 0; s < 4; s++) {
     const double* q = poses_assoc + 7 * (s / 2);
     const Cloud& m = c->mr_map[s & 1];
-    sets[s] = rgck::MapregAssoc{(const float*)c->mr_feat[s].p, nfeat[s], (s & 1) == 0 ? 1 : 0, rgck::Quat{q[0], q[1], q[2], q[3]}, {q[4], q[5], q[6]},
-                                (const float4*)m.P.p, (const int*)m.start.p, m.grid, (double*)c->mr_fac[s].p, dcnt + s};
+    sets[s] = rgck::MapregAssoc{c->mr_feat[s].as<const float>(), nfeat[s], (s & 1) == 0 ? 1 : 0, rgck::Quat{q[0], q[1], q[2], q[3]}, {q[4], q[5], q[6]},
+                                m.P.as<const float4>(), m.start.as<const int>(), m.grid, c->mr_fac[s].as<double>(), dcnt + s};
   }
   rgck::mapreg_associate(c->stream, sets, 4);
   HIPCHK(c, hipMemcpyAsync(c->h_small + 40, dcnt, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -457,7 +457,7 @@ int rgc_map_insert(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, const
   if ((rc = map_reserve(c, c->map_cur ^ 1, c->map_n + n, false))) return rc;
   // surroundingCloud.push_back(transformPointCloud(FullPointsLessFlat, q_w_curr, t_w_curr)) (:1237), relative to the origin
   const double tr[3] = {t[0] - c->map_origin[0], t[1] - c->map_origin[1], t[2] - c->map_origin[2]};
-  rgck::transform_q(c->stream, d_in, stride_bytes / 4, n, rgck::Quat{q[0], q[1], q[2], q[3]}, tr, (float*)c->map_store[c->map_cur].p + 4 * c->map_n, 4);
+  rgck::transform_q(c->stream, d_in, stride_bytes / 4, n, rgck::Quat{q[0], q[1], q[2], q[3]}, tr, c->map_store[c->map_cur].as<float>() + 4 * c->map_n, 4);
   if (!on_device) HIPCHK(c, hipStreamSynchronize(c->stream));  // pre_in is re-used by the next staged call
   HIPCHK(c, hipGetLastError());
   rgc_ctx::MapKf kf{c->map_next_id++, c->map_n, n, {t[0], t[1], t[2]}};
@@ -495,7 +495,7 @@ int rgc_map_evict(rgc_ctx* c, int max_keyframes, const double center[3], double 
     size_t j = i, run = 0;
     const size_t base = keep[i].off;
     while (j < keep.size() && keep[j].off == base + run) { run += keep[j].n; j++; }
-    HIPCHK(c, hipMemcpyAsync((char*)c->map_store[other].p + off * 16, (const char*)c->map_store[c->map_cur].p + base * 16, run * 16,
+    HIPCHK(c, hipMemcpyAsync(c->map_store[other].as<char>() + off * 16, c->map_store[c->map_cur].as<const char>() + base * 16, run * 16,
                              hipMemcpyDeviceToDevice, c->stream));
     for (size_t k = i; k < j; k++) keep[k].off = off + (keep[k].off - base);
     off += run;
@@ -518,7 +518,7 @@ int rgc_map_rebase(rgc_ctx* c, const double new_origin[3]) {
     const int other = c->map_cur ^ 1;
     int rc = map_reserve(c, other, c->map_n, false);
     if (rc) return rc;
-    rgck::transform_q(c->stream, (const float*)c->map_store[c->map_cur].p, 4, (int)c->map_n, rgck::Quat{0, 0, 0, 1}, d, (float*)c->map_store[other].p, 4);
+    rgck::transform_q(c->stream, c->map_store[c->map_cur].as<const float>(), 4, (int)c->map_n, rgck::Quat{0, 0, 0, 1}, d, c->map_store[other].as<float>(), 4);
     HIPCHK(c, hipGetLastError());
     c->map_cur = other;
   }
@@ -550,9 +550,9 @@ int rgc_map_commit(rgc_ctx* c, float leaf, int* n_target) {
     c->map_bound = false;
     c->tgt.ready = false; c->tgt.n = 0; c->corr_valid = c->gicp_valid = false;
   }
-  if ((rc = rgc_voxelgrid(c, (const float*)c->map_store[c->map_cur].p, (int)c->map_n, 16, leaf, (float*)c->map_target.p, &nt, 1))) return rc;
+  if ((rc = rgc_voxelgrid(c, c->map_store[c->map_cur].as<const float>(), (int)c->map_n, 16, leaf, c->map_target.as<float>(), &nt, 1))) return rc;
   // setInputTarget (:1007): grid, exact-kNN covariances, Gaussian voxel map
-  if ((rc = set_cloud(c, c->tgt, true, (const float*)c->map_target.p, nt, 16, true))) return rc;
+  if ((rc = set_cloud(c, c->tgt, true, c->map_target.as<const float>(), nt, 16, true))) return rc;
   c->map_bound = true;
   c->map_dirty = false;
   c->map_leaf = leaf;
@@ -627,11 +627,11 @@ int rgc_pc2_unpack(rgc_ctx* c, const void* data, int n, const rgc_pc2_layout* L,
     d_xyzi = (float4*)xyzi_out; d_ring = ring_out; d_time = time_out;
   } else {
     if ((rc = ensure(c, c->pre_out, (size_t)n * 24))) return rc;
-    d_xyzi = (float4*)c->pre_out.p;
-    if (ring_out) d_ring = (int*)((char*)c->pre_out.p + (size_t)n * 16);
-    if (time_out) d_time = (float*)((char*)c->pre_out.p + (size_t)n * 20);
+    d_xyzi = c->pre_out.as<float4>();
+    if (ring_out) d_ring = (int*)(c->pre_out.as<char>() + (size_t)n * 16);
+    if (time_out) d_time = (float*)(c->pre_out.as<char>() + (size_t)n * 20);
   }
-  rgck::pc2_unpack(s, (const unsigned char*)c->pre_in.p, n, K, d_xyzi, d_ring, d_time);
+  rgck::pc2_unpack(s, c->pre_in.as<const unsigned char>(), n, K, d_xyzi, d_ring, d_time);
   if (!out_on_device) {
     HIPCHK(c, hipMemcpyAsync(xyzi_out, d_xyzi, (size_t)n * 16, hipMemcpyDeviceToHost, s));
     if (ring_out) HIPCHK(c, hipMemcpyAsync(ring_out, d_ring, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -651,7 +651,7 @@ int rgc_pc2_pack(rgc_ctx* c, int kind, const float* in, int n, int in_on_device,
   int rc = stage_in(c, in, n, cols * 4, in_on_device, &d_in);
   if (rc) return rc;
   if ((rc = ensure(c, c->pre_out, (size_t)n * step))) return rc;
-  rgck::pc2_pack(c->stream, d_in, cols, n, kind, (unsigned char*)c->pre_out.p);
+  rgck::pc2_pack(c->stream, d_in, cols, n, kind, c->pre_out.as<unsigned char>());
   HIPCHK(c, hipMemcpyAsync(data_out, c->pre_out.p, (size_t)n * step, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
@@ -741,7 +741,7 @@ static int icp_align_impl(rgc_ctx* c, const float* source, int ns, const float* 
     } else {
       if ((rc = ensure(c, tg.in_copy, bytes))) return rc;
       HIPCHK(c, hipMemcpyAsync(tg.in_copy.p, target, bytes - (stride_bytes - 12), hipMemcpyHostToDevice, s));
-      tg.in = (const float*)tg.in_copy.p;
+      tg.in = tg.in_copy.as<const float>();
     }
     tg.stride_f = stride_bytes / 4;
     tg.n = nt;
@@ -751,7 +751,7 @@ static int icp_align_impl(rgc_ctx* c, const float* source, int ns, const float* 
   const float* d_src;
   if ((rc = stage_in(c, source, ns, stride_bytes, on_device ? 1 : 0, &d_src))) return rc;  // the raw source, kept for the fitness score
   if ((rc = ensure(c, c->pre_out, sizeof(float4) * (size_t)ns))) return rc;
-  float4* cur = (float4*)c->pre_out.p;
+  float4* cur = c->pre_out.as<float4>();
   const rgck::PoseF I{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
   rgck::transform_f32(s, d_src, stride_bytes / 4, ns, I, (float*)cur, 4);  // identity guess: a plain copy to 16-byte points
   const int nb = rgck::linearize_blocks(ns);
@@ -760,8 +760,7 @@ static int icp_align_impl(rgc_ctx* c, const float* source, int ns, const float* 
   const double rot_thr = 1.0 - prm->transformation_epsilon, trans_thr = prm->transformation_epsilon;
   double prev_mse = DBL_MAX;
   for (;;) {
-    rgck::icp_accumulate(s, cur, ns, (const float4*)tg.P.p, (const int*)tg.start.p, tg.grid, prm->max_correspondence_distance,
-                         (double*)c->partials.p, c->d_out);
+    rgck::icp_accumulate(s, cur, ns, tg.sorted(), prm->max_correspondence_distance, c->partials.as<double>(), c->d_out);
     HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double) * 17, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
@@ -796,7 +795,7 @@ static int icp_align_impl(rgc_ctx* c, const float* source, int ns, const float* 
   // getFitnessScore(): the ORIGINAL source through the final transformation (fp32), mean squared 1-NN distance
   rgck::transform_f32(s, d_src, stride_bytes / 4, ns, posef_from(fin), (float*)cur, 4);
   if ((rc = ensure(c, c->fit_partials, sizeof(double) * (size_t)rgck::fitness_blocks(ns) + 64))) return rc;
-  rgck::fitness(s, cur, ns, I, (const float4*)tg.P.p, (const int*)tg.start.p, tg.grid, (double*)c->fit_partials.p, c->d_out);
+  rgck::fitness(s, cur, ns, I, tg.sorted(), c->fit_partials.as<double>(), c->d_out);
   HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
@@ -872,7 +871,7 @@ int rgc_kf_push(rgc_ctx* c, int id, const rgc_kf_pose* pose, const float* corner
     rec.off[k] = c->kf_n[k];
     rec.n[k] = n[k];
     if (!n[k]) continue;
-    char* dst = (char*)c->kf_store[k].p + c->kf_n[k] * 16;
+    char* dst = c->kf_store[k].as<char>() + c->kf_n[k] * 16;
     const hipMemcpyKind dir = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (stride_bytes == 16) HIPCHK(c, hipMemcpyAsync(dst, src[k], (size_t)n[k] * 16, dir, c->stream));
     else HIPCHK(c, hipMemcpy2DAsync(dst, 16, src[k], (size_t)stride_bytes, 16, (size_t)n[k], dir, c->stream));
@@ -951,7 +950,7 @@ int rgc_kf_assemble(rgc_ctx* c, const int* ids, int n_ids, unsigned kind_mask, f
   float4* d_raw = (float4*)out_xyzc;
   if (filter || !on_device) {
     if ((rc = ensure(c, c->kf_raw, (size_t)nr * 16))) return rc;
-    d_raw = (float4*)c->kf_raw.p;
+    d_raw = c->kf_raw.as<float4>();
   }
   // the segment table through pinned staging: [nseg segments][nseg + 1 first workgroups]
   const size_t seg_bytes = nseg * sizeof(rgck::KfSegment), tab_bytes = seg_bytes + (nseg + 1) * sizeof(int);
@@ -972,7 +971,7 @@ int rgc_kf_assemble(rgc_ctx* c, const int* ids, int n_ids, unsigned kind_mask, f
     for (int k = 0; k < RGC_KF_KINDS; k++) {
       if (!((kind_mask >> k) & 1u) || !r.n[k]) continue;
       rgck::KfSegment& S = hs[si];
-      S.src = (const float4*)c->kf_store[k].p + r.off[k];
+      S.src = c->kf_store[k].as<const float4>() + r.off[k];
       S.n = r.n[k];
       S.out0 = out0;
       S.q = rgck::Quat{r.q[0], r.q[1], r.q[2], r.q[3]};
@@ -988,7 +987,7 @@ int rgc_kf_assemble(rgc_ctx* c, const int* ids, int n_ids, unsigned kind_mask, f
   HIPCHK(c, hipEventRecord(c->kf_uploaded, s));
   c->kf_upload_pending = true;
   if (c->main_has_target_prep && map_prep_finished(c)) c->main_has_target_prep = false;  // it has drained
-  rgck::kf_assemble(s, (const rgck::KfSegment*)c->kf_table.p, (const int*)((const char*)c->kf_table.p + seg_bytes), (int)nseg, (int)blocks, d_raw);
+  rgck::kf_assemble(s, c->kf_table.as<const rgck::KfSegment>(), (const int*)(c->kf_table.as<const char>() + seg_bytes), (int)nseg, (int)blocks, d_raw);
   HIPCHK(c, hipGetLastError());
   if (!filter) {
     if (!on_device) HIPCHK(c, hipMemcpyAsync(out_xyzc, d_raw, (size_t)nr * 16, hipMemcpyDeviceToHost, s));
@@ -1002,7 +1001,7 @@ int rgc_kf_assemble(rgc_ctx* c, const int* ids, int n_ids, unsigned kind_mask, f
   float* d_f = out_xyzc;
   if (!direct) {
     if ((rc = ensure(c, c->kf_filt, (size_t)nr * 16))) return rc;
-    d_f = (float*)c->kf_filt.p;
+    d_f = c->kf_filt.as<float>();
   }
   rgc_vg_route rt{};
   rt.n = nr;

@@ -131,7 +131,7 @@ int pgo_upload(rgc_ctx* c, PgoHost& P) {
   if ((rc = ensure(c, c->pgo_M, 16 * ns * ns * sizeof(double)))) return rc;
   std::vector<int> hi;
   hi.reserve(ni);
-  int* di = (int*)c->pgo_i.p;
+  int* di = c->pgo_i.as<int>();
   auto put = [&](const std::vector<int>& v, size_t count) { const int* p = di + hi.size(); hi.insert(hi.end(), v.begin(), v.begin() + (long)count); return p; };
   P.G.n_nodes = P.n; P.G.n_edges = P.n_edges; P.G.fixed = P.fixed; P.G.n_sep = (int)ns;
   P.G.ij = put(P.ij, 2 * E);
@@ -141,7 +141,7 @@ int pgo_upload(rgc_ctx* c, PgoHost& P) {
   P.G.sep_of = put(P.sep_of, n);
   P.flag = di + hi.size();
   hi.resize(hi.size() + 4, 0);
-  double* dd = (double*)c->pgo_d.p;
+  double* dd = c->pgo_d.as<double>();
   auto take = [&](size_t count) { double* p = dd; dd += count; return p; };
   double* meas = take(6 * E);
   P.G.meas = meas;
@@ -214,7 +214,7 @@ int rgc_pgo_optimize(rgc_ctx* c, const int* ids, int n_ids, const rgc_pgo_loop* 
     if (gmax <= 1e-10) { stop = RGC_PGO_STOP_GRADIENT; break; }
     const int nxt = cur ^ 1;
     HIPCHK(c, hipMemsetAsync(P.flag, 0, sizeof(int), s));
-    rgck::pgo_solve(s, P.G, P.terms[cur], P.D[cur], P.g[cur], radius, P.ws, P.slots, (double*)c->pgo_M.p, P.d, P.flag);
+    rgck::pgo_solve(s, P.G, P.terms[cur], P.D[cur], P.g[cur], radius, P.ws, P.slots, c->pgo_M.as<double>(), P.d, P.flag);
     rgck::pgo_step(s, P.G, P.terms[cur], P.D[cur], P.g[cur], P.x_dev[cur], P.d, P.x_dev[nxt], P.part, P.out[cur] + 2);
     rgck::pgo_evaluate(s, P.G, P.x_dev[nxt], P.terms[nxt], P.D[nxt], P.g[nxt], P.out[nxt]);
     HIPCHK(c, hipGetLastError());
@@ -274,7 +274,7 @@ int rgc_pgo_linearize(rgc_ctx* c, const int* ids, int n_ids, const rgc_pgo_loop*
   int hflag = 0;
   if (solve) {
     HIPCHK(c, hipMemsetAsync(P.flag, 0, sizeof(int), s));
-    rgck::pgo_solve(s, P.G, P.terms[0], P.D[0], P.g[0], radius, P.ws, P.slots, (double*)c->pgo_M.p, P.d, P.flag);
+    rgck::pgo_solve(s, P.G, P.terms[0], P.D[0], P.g[0], radius, P.ws, P.slots, c->pgo_M.as<double>(), P.d, P.flag);
     if ((rc = pgo_fetch(c, &hflag, P.flag, sizeof(int)))) return rc;
   }
   HIPCHK(c, hipGetLastError());

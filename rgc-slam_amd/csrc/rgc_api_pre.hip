@@ -17,7 +17,7 @@ int rgcapi::stage_in(rgc_ctx* c, const float* p, int n, int stride_bytes, int on
   int rc = ensure(c, c->pre_in, bytes);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(c->pre_in.p, p, bytes, hipMemcpyHostToDevice, c->stream));
-  *d_in = (const float*)c->pre_in.p;
+  *d_in = c->pre_in.as<const float>();
   return RGC_OK;
 }
 
@@ -58,7 +58,7 @@ int rgc_transform_cloud(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, 
   float* d_out = out_xyzi;
   if (!on_device) {
     if ((rc = ensure(c, c->pre_out, sizeof(float) * 4 * (size_t)n))) return rc;
-    d_out = (float*)c->pre_out.p;
+    d_out = c->pre_out.as<float>();
   }
   rgck::transform_q(c->stream, d_in, stride_bytes / 4, n, rgck::Quat{q[0], q[1], q[2], q[3]}, t, d_out, 4);
   if (!on_device) HIPCHK(c, hipMemcpyAsync(out_xyzi, d_out, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -292,9 +292,9 @@ static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, fl
   cl.cnt_clean = std::max(cl.cnt_clean, nr1);  // (what lies beyond this call's rows was not touched: the scan's and the map's filter take turns)
   if (!c->vg_flags_clean) HIPCHK(c, hipMemsetAsync(dsm + 6, 0, sizeof(int), s));
   c->vg_flags_clean = false;
-  const bool packed = rgck::vg_rows(s, d_in, stride_f, n, inv, g, edge, seg_shift, (int*)cl.cell_of.p, (int*)cl.slot_of.p, (int*)c->vg_pos.p, (int*)cl.cnt.p,
-                                    (int*)cl.start.p, cl.block_sums.p, (unsigned long long*)c->vg_tmp.p, (int*)c->vg_order.p, (unsigned long long*)c->vg_leaf.p,
-                                    (int*)((char*)cl.block_sums.p + row_bs), d_out, dsm + 5);
+  const bool packed = rgck::vg_rows(s, d_in, stride_f, n, inv, g, edge, seg_shift, cl.cell_of.as<int>(), cl.slot_of.as<int>(), c->vg_pos.as<int>(), cl.cnt.as<int>(),
+                                    cl.start.as<int>(), cl.block_sums.p, c->vg_tmp.as<unsigned long long>(), c->vg_order.as<int>(), c->vg_leaf.as<unsigned long long>(),
+                                    (int*)(cl.block_sums.as<char>() + row_bs), d_out, dsm + 5);
   rt->chain = 1; rt->leaf_buckets = dense ? 1 : 0; rt->seg_shift = seg_shift; rt->nseg = rgck::vg_segments(g, seg_shift); rt->packed = packed ? 1 : 0;
   rt->edge = edge; rt->flags = 0;
   for (int a = 0; a < 3; a++) { rt->minb[a] = g.minb[a]; rt->div[a] = g.div[a]; }
@@ -330,7 +330,7 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
   float* d_out = out_xyzi;
   if (!on_device) {
     if ((rc = ensure(c, c->pre_out, sizeof(float) * 4 * (size_t)n))) return rc;
-    d_out = (float*)c->pre_out.p;
+    d_out = c->pre_out.as<float>();
   }
   // leaves added on every side of a measured box when the next cloud of this leaf size is filtered on it: 32 for a sweep (its rows are
   // what is counted and scanned), 8 for a dense cloud (its leaves are: a wider box is a longer scan)
@@ -575,8 +575,8 @@ static int frontend_impl(rgc_ctx* c, const float* xyzi, int n, int stride_bytes,
   // feature clouds in ONE buffer laid out like the pinned staging area behind the meta block, so that everything the host needs at the
   // end of the sweep comes down in ONE copy and the two small blocks are initialised by ONE
   for (int b = 0; b < 34; b++) if ((rc = ensure(c, c->fe[b], sizes[b] + 64))) return rc;
-#define FE(i, T) ((T*)c->fe[i].p)
-  unsigned char* const tail = (unsigned char*)c->fe[OUTD].p;
+#define FE(i, T) (c->fe[i].as<T>())
+  unsigned char* const tail = c->fe[OUTD].as<unsigned char>();
   int* const d_flags = (int*)(tail + kTailFlags);
   int* const d_st = (int*)(tail + kTailSt);
   float* const d_sharp = (float*)(tail + kTailFeat);
@@ -704,7 +704,7 @@ static int frontend_impl(rgc_ctx* c, const float* xyzi, int n, int stride_bytes,
 
 int rgc_frontend_cloud_device(rgc_ctx* c, float** d_cloud, int* n) {
   if (!c || !d_cloud || !n) return RGC_ERR_INVALID;
-  *d_cloud = c->fe_n_cloud > 0 ? (float*)c->fe[5].p : nullptr;  // CL: float4 {x, y, z, ring + 0.1 relTime}, ring-major
+  *d_cloud = c->fe_n_cloud > 0 ? c->fe[5].as<float>() : nullptr;  // CL: float4 {x, y, z, ring + 0.1 relTime}, ring-major
   *n = c->fe_n_cloud;
   return RGC_OK;
 }

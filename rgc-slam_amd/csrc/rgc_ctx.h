@@ -74,6 +74,7 @@ struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
   bool borrowed = false;  // p belongs to another context (rgc_share_target): never freed, never grown here
+  template <class T> T* as() const { return static_cast<T*>(p); }  // the one place the host files turn a buffer into a typed pointer
 };
 
 struct Cloud {
@@ -130,6 +131,10 @@ struct Cloud {
   bool prepared_recorded = false;  // the preparation's last launch carried the context's tgt_prepared event (no record packet behind it)
   bool cache_searched_lists = false;  // the last preparation's search was the seeded launch that reads the lists (rgc_stats::searched_target)
   int searched_known = -1;            // rgc_stats::searched_target of this preparation once it has been fetched (-1: not yet)
+  rgck::SortedCloud sorted() const { return {P.as<const float4>(), start.as<const int>(), grid, n}; }  // the typed views the launch wrappers take (rgc_kernels.h)
+  rgck::Normals normals() const { return {nx.as<double>(), ny.as<double>(), nz.as<double>()}; }
+  rgck::VoxelMap voxels() const { return {cell_voxel.as<const int>(), vox.as<double>(), vox_cell.as<int>()}; }
+  rgck::DeferredBuf deferred(const int* guard /* of the cloud's grid, nullable: guard_of, rgc_api.hip */) const { return {segs.p, guard}; }
 };
 
 struct ProfRegion {
@@ -201,7 +206,7 @@ struct rgc_ctx {
   int cu_count = 0;           // the device's compute units: the resident solve runs with at most one workgroup per CU
   bool lm_resident = false;   // the solve in flight went out as one resident launch
   int voxel_impl = 0;         // RGC_VOXEL_IMPL: 1 "separate", the voxel stage and the map's cooperative search always in launches of their own (k_voxel_build_coop,
-                              // k_voxel_patch); 2 "fused", inside the dense map's kNN launch (rgck::VoxFuse) wherever that launch runs; 0 (unset): fused on a
+                              // k_voxel_patch); 2 "fused", inside the dense map's kNN launch (rgck::KnnBulkOpts::fuse) wherever that launch runs; 0 (unset): fused on a
                               // context whose scans are held behind another context's target (src_held: a pipelined sequence), separate elsewhere
   bool src_held = false;      // the scan prepared last on this context was held by rgc_hold_source_until_target_of (src_hold_pending: the call came, the scan has not yet)
   bool src_hold_pending = false;

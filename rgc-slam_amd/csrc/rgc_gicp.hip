@@ -207,33 +207,33 @@ __global__ void __launch_bounds__(GICP_T) k_gicp_export(const float4* __restrict
   sq[o] = key[s];
 }
 
-void gicp_correspond(hipStream_t s, const float4* SP, int ns, PoseF T, const float4* TP, const int* tstart, Grid g, double dmax2, int* corr, float* key) {
-  const int nb = gicp_blocks(ns);
-  if (nb > 0) hipLaunchKernelGGL(k_gicp_correspond, dim3(nb), dim3(GICP_T), 0, s, SP, ns, T, TP, tstart, g, dmax2, corr, key);
+void gicp_correspond(hipStream_t s, const SortedCloud& src, PoseF T, const SortedCloud& tgt, double dmax2, int* corr, float* key) {
+  const int nb = gicp_blocks(src.n);
+  if (nb > 0) hipLaunchKernelGGL(k_gicp_correspond, dim3(nb), dim3(GICP_T), 0, s, src.P, src.n, T, tgt.P, tgt.start, tgt.grid, dmax2, corr, key);
 }
 
-void gicp_terms(hipStream_t s, const float4* SP, int ns, const float4* TP, int nt, const int* corr, const GicpCov& A, const GicpCov& B, Pose T, int want_H,
+void gicp_terms(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const GicpCov& A, const GicpCov& B, Pose T, int want_H,
                 double* M, double* partials, double* out29) {
-  const int nb = gicp_blocks(ns);
+  const int nb = gicp_blocks(src.n);
   if (nb <= 0) return;
 #define GICP_LAUNCH(GA, GB) \
-  hipLaunchKernelGGL((k_gicp_terms<GA, GB>), dim3(nb), dim3(GICP_T), 0, s, SP, ns, TP, nt, corr, A.c6, A.nx, A.ny, A.nz, B.c6, B.nx, B.ny, B.nz, T, want_H, M, partials)
+  hipLaunchKernelGGL((k_gicp_terms<GA, GB>), dim3(nb), dim3(GICP_T), 0, s, src.P, src.n, tgt.P, tgt.n, corr, A.c6, A.nx, A.ny, A.nz, B.c6, B.nx, B.ny, B.nz, T, want_H, M, partials)
   if (A.c6) { if (B.c6) GICP_LAUNCH(true, true); else GICP_LAUNCH(true, false); }
   else      { if (B.c6) GICP_LAUNCH(false, true); else GICP_LAUNCH(false, false); }
 #undef GICP_LAUNCH
   hipLaunchKernelGGL(k_gicp_fold, dim3(kGicpAcc), dim3(GICP_WAVE), 0, s, partials, nb, kGicpAcc, out29);
 }
 
-void gicp_error(hipStream_t s, const float4* SP, int ns, const float4* TP, int nt, const int* corr, const double* M, Pose T, double* partials, double* out1) {
-  const int nb = gicp_blocks(ns);
+void gicp_error(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const double* M, Pose T, double* partials, double* out1) {
+  const int nb = gicp_blocks(src.n);
   if (nb <= 0) return;
-  hipLaunchKernelGGL(k_gicp_error, dim3(nb), dim3(GICP_T), 0, s, SP, ns, TP, nt, corr, M, T, partials);
+  hipLaunchKernelGGL(k_gicp_error, dim3(nb), dim3(GICP_T), 0, s, src.P, src.n, tgt.P, tgt.n, corr, M, T, partials);
   hipLaunchKernelGGL(k_gicp_fold, dim3(1), dim3(GICP_WAVE), 0, s, partials, nb, 1, out1);
 }
 
-void gicp_export(hipStream_t s, const float4* SP, int ns, const float4* TP, int nt, const int* corr, const float* key, int* idx, float* sq) {
-  const int nb = gicp_blocks(ns);
-  if (nb > 0) hipLaunchKernelGGL(k_gicp_export, dim3(nb), dim3(GICP_T), 0, s, SP, ns, TP, nt, corr, key, idx, sq);
+void gicp_export(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const float* key, int* idx, float* sq) {
+  const int nb = gicp_blocks(src.n);
+  if (nb > 0) hipLaunchKernelGGL(k_gicp_export, dim3(nb), dim3(GICP_T), 0, s, src.P, src.n, tgt.P, tgt.n, corr, key, idx, sq);
 }
 
 }  // namespace rgck

@@ -101,7 +101,15 @@ struct LeafGrid { int minb[3]; int div[3]; };  // pcl::VoxelGrid leaf grid
 constexpr int kAccum = 28;  // 21 upper-triangular H + 6 b + 1 cost
 constexpr int kVoxRec = 10; // mean(3) cov6(6) num(1), doubles
 
-// Sorted points are float4 {x, y, z, original index (int bits)} grouped by grid cell.
+// ---- typed views of a prepared cloud's device buffers: what the wrappers below take (rgcapi::Cloud builds them, rgc_ctx.h) ----
+// Sorted points are float4 {x, y, z, original index (int bits)} grouped by grid cell; start[]: a cell's first point (ncell + 1 entries).
+struct SortedCloud { const float4* P; const int* start; Grid grid; int n; };
+struct Normals { double* nx; double* ny; double* nz; };  // the unit normal of every sorted point (its PLANE covariance is I - 0.999 n n^T)
+// the Gaussian voxel map laid out on a cloud's grid: a cell's voxel id (< 0: empty), kVoxRec doubles per voxel, a voxel's cell
+struct VoxelMap { const int* cell_voxel; double* vox; int* vox_cell; };
+// the bulk kNN launch's deferred-query buffer (deferred_bytes(n) bytes) and the guard of the cloud's grid (nullable): set, the kernels stand still
+struct DeferredBuf { void* buf; const int* guard; };
+struct Corr { int* v; double* M; };  // what a linearisation freezes per source point and offset: the voxel found and the Mahalanobis matrix (6 doubles)
 // ---- grid build ----
 void bbox(hipStream_t s, const float* in, int stride_f, int n, double res, int* mm6, int* flags, int hi = 0);
 // rf (nullable): in[] is first WRITTEN from rf->src (see Reframe; in must then be a 16-byte-stride device buffer this call may write)
@@ -132,114 +140,100 @@ struct KnnSeeds {
   KnnCache cache;  // (nbr == nullptr: no lists)
 };
 bool knn_seeds_apply(int n, int k);  // the seeded search exists for this cloud size and k
-// The dense map's launch over the whole map (target, wide_r == 0, no query list, not the seeded kernel) can do the voxel stage's work itself:
-// every workgroup builds the voxel records of the cells that start and end among its 256 sorted points, from the normals it has in
-// registers, and the launch's last workgroups resolve the deferred queries as they are published (coop_waves of them, sized like
-// knn_coop's).  voxel_seams then finishes the map: the cells that cross a workgroup boundary and the voxels of the deferred queries.
-// The deferred buffer's entry words must hold kDeferredSlotEmptyByte bytes on entry; voxel_seams leaves them so.
-struct VoxFuse {
-  const int* cell_voxel;
-  double* vox;
-  int* vox_cell;
-  int coop_waves;
-};
-bool knn_bulk_fuses_voxels(bool is_target, int n, int k, int wide_r, const int* qlist, const KnnSeeds& seeds);  // knn_bulk would honour `fuse`
-// wide_r = 2: the four-lanes-per-query search on the 5^3 block whatever the cloud (a sparse map)
-void knn_bulk(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* deferred, double* nx,
-              double* ny, double* nz, const int* guard = nullptr, int wide_r = 0,
-              hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr /* dense-map launch only (knn_bulk_times_itself): the launch's own start / stop times */,
-              // lazy target (dense-map launch only): the queries listed in qlist[0 .. *nq) are searched, nothing else; q_est sizes the launch
-              const int* qlist = nullptr, const int* nq = nullptr, int q_est = 0, const KnnSeeds& seeds = KnnSeeds{},
-              // the scan's launch only: > 0 = that many waves at the end of the launch resolve the deferred queries as they are published
-              // (no knn_coop launch behind it); the deferred buffer's entry words must hold kDeferredSlotEmptyByte bytes on entry
-              int stream_coop_waves = 0,
-              // the dense map's launch only, where knn_bulk_fuses_voxels says so (ignored elsewhere): see VoxFuse; voxel_seams must follow
-              const VoxFuse* fuse = nullptr);
 constexpr int kDeferredSlotEmptyByte = 0x80;
-// lazy target: stamp the cells of grid g within `margin` cells of the cell each point of the cloud falls into under T and list the occupied
-// ones (cell_list: their first sorted point; qlist: all their points; counts[0] / [1]: the lists' sizes, zeroed by rank_gather)
-// guard (nullable): the speculative grid's flag -- set: the map's points may lie outside the grid, nothing is listed
-void footprint(hipStream_t s, const float* in, int stride_f, int n, Pose T, Grid g, int* need, int stamp, int margin, const float4* P, int n_map,
-               const int* start, int* qlist, int* cell_list, int* counts, const int* guard = nullptr);
+// What a bulk launch may be asked for beyond the search itself; the defaults mean "absent", a call site sets its own fields only.
+struct KnnBulkOpts {
+  int wide_r = 0;  // 2: the four-lanes-per-query search on the 5^3 block whatever the cloud (a sparse map)
+  // the dense map's launch only (knn_bulk_times_itself): the launch's own start / stop times go into these events
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // lazy target (dense-map launch only): the queries listed in qlist[0 .. *nq) are searched, nothing else; q_est sizes the launch
+  const int *qlist = nullptr, *nq = nullptr;
+  int q_est = 0;
+  KnnSeeds seeds;
+  // > 0, the scan's launch and the map's with `fuse`: that many waves at the end of the launch resolve the deferred queries as they are published
+  // (no knn_coop launch behind it).  The deferred buffer's entry words must hold kDeferredSlotEmptyByte bytes on entry; the readers leave them so.
+  int coop_waves = 0;
+  // The dense map's launch over the whole map (target, wide_r == 0, no query list, not the seeded kernel: knn_bulk_fuses_voxels; ignored
+  // elsewhere) can do the voxel stage's work itself: every workgroup builds the voxel records of the cells that start and end among its 256
+  // sorted points, from the normals it has in registers, and the launch's last workgroups resolve the deferred queries (coop_waves).
+  // voxel_seams then finishes the map: the cells that cross a workgroup boundary and the voxels of the deferred queries.
+  VoxelMap fuse{};  // (vox == nullptr: not asked for)
+};
+// what knn_bulk would do with these options, answered by the function that picks the launch's variant
+bool knn_bulk_fuses_voxels(bool is_target, int n, int k, const KnnBulkOpts& o);  // it would honour a `fuse`
+bool knn_bulk_times_itself(bool is_target, int n, int k, const KnnBulkOpts& o);  // it would honour ev0 / ev1
+void knn_bulk(hipStream_t s, bool is_target, const SortedCloud& cl, int k, const DeferredBuf& df, const Normals& nrm, const KnnBulkOpts& o = KnnBulkOpts{});
+// lazy target: stamp the cells of the map's grid within `margin` cells of the cell each point of the cloud `in` falls into under T and list the
+// occupied ones (cell_list: their first sorted point; qlist: all their points; counts[0] / [1]: the lists' sizes, zeroed by rank_gather)
+// guard (nullable): the map's (DeferredBuf::guard) -- set: nothing is listed
+void footprint(hipStream_t s, const float* in, int stride_f, int n, Pose T, const SortedCloud& map, int* need, int stamp, int margin, int* qlist,
+               int* cell_list, int* counts, const int* guard = nullptr);
 // ... and the voxel pass over the listed cells, the map's deferred queries resolved beside it (k_voxel_cells_coop); voxel_patch follows
-void voxel_cells_coop(hipStream_t s, const float4* P, double* nx, double* ny, double* nz, const int* start, Grid g, int n, const int* cell_voxel,
-                      double* vox, int* vox_cell, int k, const void* deferred, const int* guard, int waves, const int* cell_list, const int* ncells,
-                      int cells_est, const KnnSeeds& seeds = KnnSeeds{});
-bool knn_bulk_times_itself(bool is_target, int wide_r);
+void voxel_cells_coop(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm, int k, const DeferredBuf& df, int waves,
+                      const int* cell_list, const int* ncells, int cells_est, const KnnSeeds& seeds = KnnSeeds{});
 // waves: one-wave workgroups that share the deferred list (clamped to [32, 8192])
-void knn_coop(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* deferred, double* nx,
-              double* ny, double* nz, const int* guard, int waves, const KnnSeeds& seeds = KnnSeeds{});
+void knn_coop(hipStream_t s, bool is_target, const SortedCloud& cl, int k, const DeferredBuf& df, const Normals& nrm, int waves, const KnnSeeds& seeds = KnnSeeds{});
 // ---- C3: Gaussian voxel map ----
-void voxel_build(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, const int* start, Grid g,
-                 int n, const int* cell_voxel, double* vox, int* vox_cell);
+void voxel_build(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm);
 // voxel_build and knn_coop (target) in one launch, followed by voxel_patch: see k_voxel_build_coop
-void voxel_build_coop(hipStream_t s, const float4* P, double* nx, double* ny, double* nz, const int* start, Grid g, int n, const int* cell_voxel,
-                      double* vox, int* vox_cell, int k, const void* deferred, const int* guard, int waves, const KnnSeeds& seeds = KnnSeeds{});
+void voxel_build_coop(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm, int k, const DeferredBuf& df, int waves, const KnnSeeds& seeds = KnnSeeds{});
 // the voxels that hold a deferred query, recomputed: lets the cooperative search run BESIDE voxel_build; lanes: about
-// the number of deferred queries (grid-stride loop)
-void voxel_patch(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, const int* start, Grid g, const void* deferred,
-                 const int* cell_voxel, double* vox, int lanes, hipEvent_t done = nullptr /* signalled by the launch's own completion */);
-// behind a knn_bulk that fused the voxel stage (VoxFuse): the cells that cross a boundary between two of its workgroups and the voxels of the
-// deferred queries (k_voxel_seams); patch_waves: about the number of deferred queries (they stride over the list)
-void voxel_seams(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, const int* start, Grid g, int n, void* deferred,
-                 const int* cell_voxel, double* vox, int* vox_cell, const int* guard, int patch_waves, hipEvent_t done = nullptr);
-// ---- C4/C5/C6 ----
-void linearize(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Pose T, Grid g,
-               const int* cell_voxel, const double* vox, int noff, int* corr_v, double* corr_M, int want_H, double* partials,
-               int* ncorr_partials, double* out28, int* out_ncorr);
+// the number of deferred queries (grid-stride loop, clamped to [64, 4096])
+void voxel_patch(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm, const DeferredBuf& df, int lanes,
+                 hipEvent_t done = nullptr /* signalled by the launch's own completion */);
+// behind a knn_bulk that fused the voxel stage (KnnBulkOpts::fuse): the cells that cross a boundary between two of its workgroups and the voxels
+// of the deferred queries (k_voxel_seams); patch_waves: about the number of deferred queries (they stride over the list)
+void voxel_seams(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm, const DeferredBuf& df, int patch_waves, hipEvent_t done = nullptr);
+// ---- C4/C5/C6 ---- (src at T against the target's voxel map vm on its grid g)
+void linearize(hipStream_t s, const SortedCloud& src, const Normals& nrm, Pose T, const Grid& g, const VoxelMap& vm, int noff, Corr corr, int want_H,
+               double* partials, int* ncorr_partials, double* out28, int* out_ncorr);
 // ---- the general covariance route (rgc_set_regularization_method other than PLANE, VoxelAccumulationMode::MULTIPLICATIVE): every point
 // through the cooperative search, a regularised 3x3 per point (c6: six doubles, SoA c6[a * n + i], sorted order) instead of a unit normal;
 // unoptimised by design.  method = rgc_regularization_method; guard (nullable): a tripped speculative-grid guard makes the kernels stand still
-void knn_cov6(hipStream_t s, const float4* P, const int* start, Grid g, int n, int k, int method, double* c6, const int* guard);
+void knn_cov6(hipStream_t s, const SortedCloud& cl, int k, int method, double* c6, const int* guard);
 // ... or, rgc_set_covariance_estimation(RGC_COV_RBF), the Gaussian-weighted moment of every point within max_dist (rgc_rbf.hip: semantics there).
 // reach: cells per axis a ball can span, reach_dist: the distance that bound was made for (rgcapi::rbf_reach)
-void rbf_cov6(hipStream_t s, const float4* P, const int* start, Grid g, int n, float kernel_width, float max_dist_sq, int reach, double reach_dist,
-              int method, double* c6, const int* guard);
-void voxel_build_general(hipStream_t s, const float4* P, const double* c6, const int* start, Grid g, int n, const int* cell_voxel, double* vox,
-                         int* vox_cell, int multiplicative, const int* guard);
-void linearize_general(hipStream_t s, const float4* P, const double* c6, int n, Pose T, Grid g, const int* cell_voxel, const double* vox, int noff,
-                       int* corr_v, double* corr_M, int want_H, double* partials, int* ncorr_partials, double* out28, int* out_ncorr);
+void rbf_cov6(hipStream_t s, const SortedCloud& cl, float kernel_width, float max_dist_sq, int reach, double reach_dist, int method, double* c6, const int* guard);
+void voxel_build_general(hipStream_t s, const SortedCloud& cl, const double* c6, const VoxelMap& vm, int multiplicative, const int* guard);
+void linearize_general(hipStream_t s, const SortedCloud& src, const double* c6, Pose T, const Grid& g, const VoxelMap& vm, int noff, Corr corr,
+                       int want_H, double* partials, int* ncorr_partials, double* out28, int* out_ncorr);
 void unsort6(hipStream_t s, const double* c6, const float4* P, int n, double* out9);
 void sort6(hipStream_t s, const double* in9, const float4* P, int n, double* c6);
-void compute_error(hipStream_t s, const float4* P, int n, Pose T, const double* vox, int noff, const int* corr_v,
-                   const double* corr_M, double* partials, double* out1);
+void compute_error(hipStream_t s, const float4* P, int n, Pose T, const double* vox, int noff, Corr corr, double* partials, double* out1);
 void lm_try(hipStream_t s, double* out, const int* ncorr, LmIn in);
-void compute_error_dev(hipStream_t s, const float4* P, int n, const double* Tdev, const double* vox, int noff, const int* corr_v,
-                       const double* corr_M, double* partials, double* out1);
-// launch number j of a solve of the device-chained LM (see k_lm_step; 0 opens the solve and takes *open); corr_*0 / corr_*1 are the two
-// correspondence buffers, the finished state's `cur` the valid one.  st: the 4096-byte LM area, zeroed once -- two state images (launch j
-// reads image (j - 1) & 1 and leaves image j & 1: lm_image(st, j_last) is the latest) and the loose words behind them.  partials:
-// 2 * linearize_blocks(n) rows of kAccum + 2 doubles (the launches alternate between the halves).
+void compute_error_dev(hipStream_t s, const float4* P, int n, const double* Tdev, const double* vox, int noff, Corr corr, double* partials, double* out1);
+// What a solve on the device works on, filled once per solve (rgcapi: lm_enqueue_batch).  st: the kLmAreaBytes LM area, zeroed once -- two
+// state images and the loose words behind them.  partials: 2 * linearize_blocks(src.n) rows of kAccum + 2 doubles (the chained launches
+// alternate between the halves).  corr: the two correspondence buffers, the finished state's `cur` the valid one.
+struct LmArgs {
+  SortedCloud src; Normals nrm;  // the scan
+  SortedCloud tgt; VoxelMap vm;  // the map: its grid and voxels; its sorted points for the score
+  int noff;
+  Corr corr[2];
+  double* partials; LmState* st;
+  const int* nvox; const void* segs_t; const void* segs_s;  // the frame's counters, carried home with the state: the map's voxel count, the clouds' deferred buffers
+  LmState* h_post; int seq;      // mapped host memory (nullable): a finished state is posted there, then seq in its `gen`; seq > 0: post when done; < 0: when done AND scored
+  double* fit_partials;          // non-null: the score is chained to the solve -- the launch whose decision ends it scores the final pose (as does a launch on a finished solve without a score)
+  // lazy target: the target is built for the cells stamped lazy_stamp in lazy_need[] only -- a look-up of any other occupied voxel
+  // raises LmState::pad2; lazy_counts: the lists' sizes, carried home in LmState::lazy_nq / lazy_ncell
+  const int* lazy_need; int lazy_stamp; const int* lazy_counts;
+  LmEarly* h_early;              // mapped host memory (nullable): the deciding launch posts the final pose there before it scores it
+};
+// launch number j of a solve of the device-chained LM (k_lm_step; 0 opens the solve and takes *open) reads image (j - 1) & 1 and leaves image j & 1
 inline LmState* lm_image(LmState* st, int j_last) { return st + (j_last & 1); }
-void lm_step(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Grid g, const int* cell_voxel,
-             const double* vox, int noff, int* corr_v0, double* corr_M0, int* corr_v1, double* corr_M1, double* partials, LmState* st,
-             int j, const LmInit* open, const int* nvox, const void* segs_t, const void* segs_s,
-             LmState* h_post = nullptr /* mapped host memory: a finished state is posted there, then seq in its `gen` */,
-             int seq = 0 /* > 0: post when done; < 0: post when done AND scored (by this kernel or fitness_lm) */,
-             // the fitness score chained to the solve (all non-null): the launch whose decision ends the solve scores the final pose (as does a
-             // launch on a finished solve without a score); TP / tstart: the map's sorted points and cell starts, nt its point count
-             const float4* TP = nullptr, const int* tstart = nullptr, double* fit_partials = nullptr, int nt = 0,
-             // lazy target: the target is built for the cells stamped lazy_stamp in lazy_need[] only -- a look-up of any other occupied voxel
-             // raises LmState::pad2; lazy_counts: the lists' sizes, carried home in LmState::lazy_nq / lazy_ncell
-             const int* lazy_need = nullptr, int lazy_stamp = 0, const int* lazy_counts = nullptr,
-             LmEarly* h_early = nullptr /* mapped host memory (nullable): the deciding launch posts the final pose there before it scores it */);
-// The whole solve in ONE resident launch (see k_lm_solve): lm_step's arguments without a launch number; the finished state is left in image 0
-// (lm_image(st, 0)).  st is kLmAreaBytes long, zeroed once; the caller keeps linearize_blocks(n) <= min(the device's CU count,
-// kLmSolveMaxGroups) -- all of them resident at once -- and finds a solve that gave up (a bounded wait ran out; give_up_at >= 0: workgroup 0
-// at that try, without waiting) as a stream that drained with nothing posted.  seq != 0 always: its magnitude tags the hand-over's words.
+void lm_step(hipStream_t s, const LmArgs& a, int j, const LmInit* open);
+// The whole solve in ONE resident launch (see k_lm_solve); the finished state is left in image 0 (lm_image(st, 0)).  The caller keeps
+// linearize_blocks(src.n) <= min(the device's CU count, kLmSolveMaxGroups) -- all of them resident at once -- and finds a solve that gave up
+// (a bounded wait ran out; give_up_at >= 0: workgroup 0 at that try, without waiting) as a stream that drained with nothing posted.
+// seq != 0 always: its magnitude tags the hand-over's words.
 constexpr int kLmAreaBytes = 8192, kLmSolveMaxGroups = 512;
 // The longest a workgroup waits for the others' rows, in ticks of the 100 MHz wall clock: 2 ms.  The workgroups of a solve are placed as
 // CU slots free up, so a wait can last as long as the longest kernel that may hold the slots: the map's kNN launch of a c-main frame, ~165 us.
 // Twelve times that, and still a bound on what a lost frame costs (the chained solve that follows takes ~0.15 ms).
 constexpr unsigned long long kLmSolveWaitTicks = 200000;
-void lm_solve_resident(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Grid g, const int* cell_voxel,
-              const double* vox, int noff, int* corr_v0, double* corr_M0, int* corr_v1, double* corr_M1, double* partials, LmState* st,
-              const LmInit& open, const int* nvox, const void* segs_t, const void* segs_s, LmState* h_post, int seq, const float4* TP,
-              const int* tstart, double* fit_partials, int nt, const int* lazy_need, int lazy_stamp, const int* lazy_counts, LmEarly* h_early,
-              int give_up_at);
-// nt: the target's point count (a small map is scanned whole by the wave for a query its first cube does not settle; 0: never)
-void fitness_lm(hipStream_t s, const float4* SP, int ns, LmState* st, const float4* TP, const int* tstart, Grid g, double* partials,
-                LmState* h_post = nullptr, int seq = 0, int nt = 0);
+void lm_solve_resident(hipStream_t s, const LmArgs& a, const LmInit& open, int give_up_at);
+// a map of at most 32768 points is scanned whole by the wave for a query its first cube does not settle
+void fitness_lm(hipStream_t s, const SortedCloud& src, LmState* st, const SortedCloud& tgt, double* partials, LmState* h_post = nullptr, int seq = 0);
 // ---- f1: mapping-node feature registration (RGC_mapping.cpp:1069-1358) ----
 // factor record = 8 doubles per feature: edge {a[3], b[3], var, valid}, plane {n[3], d, 0, 0, var, valid}
 struct MapregAssoc {  // one association loop: feature set (n x 4: x,y,z,weight), its pose, the map grid it is matched against
@@ -255,11 +249,10 @@ int mapreg_blocks(int ne, int np);
 void mapreg_terms(hipStream_t s, const float* const feat[4], const double* const fac[4], const int nfeat[4], const double x14[14], double huber_a,
                   int want_H, double* partials, double* out56);
 // ---- f4: one ICP iteration (1-NN correspondences within max_dist + the sums of the rigid fit); out28[0..16] = n, sum p, sum q, sum p q^T, sum d^2
-void icp_accumulate(hipStream_t s, const float4* SP, int ns, const float4* TP, const int* tstart, Grid g, double max_dist, double* partials,
-                    double* out28);
+void icp_accumulate(hipStream_t s, const float4* SP, int ns, const SortedCloud& tgt, double max_dist, double* partials, double* out28);
 // ---- C8 ----
-void fitness(hipStream_t s, const float4* SP, int ns, PoseF T, const float4* TP, const int* tstart, Grid g, double* partials,
-             double* out1, int nt = 0);
+// scan_small_map: a map of at most 32768 points is scanned whole by the wave for a query its first cube does not settle (as fitness_lm does)
+void fitness(hipStream_t s, const float4* SP, int ns, PoseF T, const SortedCloud& tgt, double* partials, double* out1, bool scan_small_map = false);
 // ---- misc ----
 void transform_f32(hipStream_t s, const float* in, int stride_f, int n, PoseF T, float* out, int out_stride_f);
 void unsort3(hipStream_t s, const double* a, const double* b, const double* c, const float4* P, int n, double* out3);
@@ -303,29 +296,29 @@ void pgo_step(hipStream_t s, const PgoGraph& G, const double* terms, const doubl
 // voxel record = kNdtRec doubles: mean(3), covariance after MIN_EIG (6: xx xy xz yy yz zz), number of points, its inverse (6), the covariance
 // before MIN_EIG (6), two unused.  The voxels are those of the grid's occupied cells (cell_voxel / vox_cell as for the VGICP map).
 constexpr int kNdtRec = 24;
-void ndt_voxels(hipStream_t s, const float4* P, const int* start, Grid g, const int* cell_voxel, double* vox, int* vox_cell);
+void ndt_voxels(hipStream_t s, const SortedCloud& cl, const VoxelMap& vm);
 int  ndt_blocks(int n);
 // the terms of n source elements (d2d: the records svox of the source's own map; else the points in / stride_f) against the target map
-// (g, cell_voxel, vox) at T.  find != 0: the voxels at T + offs[3 * o ..] are looked up and written to corr_v[o * n + i]; else that list is
+// (g, vm) at T.  find != 0: the voxels at T + offs[3 * o ..] are looked up and written to corr_v[o * n + i]; else that list is
 // read.  Tlin: the pose of the last linearisation (its rotation enters the D2D matrices).  partials: ndt_blocks(n) rows of kAccum doubles,
 // ipartials: as many ints; out29: the 28 sums and the number of terms.
-void ndt_terms(hipStream_t s, int d2d, int find, const float* in, int stride_f, const double* svox, int n, Pose T, Pose Tlin, Grid g, const int* cell_voxel,
-               const double* vox, const int* offs, int noff, int* corr_v, int want_H, double* partials, int* ipartials, double* out29);
+void ndt_terms(hipStream_t s, int d2d, int find, const float* in, int stride_f, const double* svox, int n, Pose T, Pose Tlin, const Grid& g,
+               const VoxelMap& vm, const int* offs, int noff, int* corr_v, int want_H, double* partials, int* ipartials, double* out29);
 // ---- FastGICP: GICP on exact nearest-neighbour correspondences (rgc_gicp.hip; fast_gicp::FastGICP, include/fast_gicp/gicp/impl/fast_gicp_impl.hpp:103-237) ----
 // the covariances of a prepared cloud, in its sorted order: c6 (the general route: six doubles per point, SoA) or, c6 == nullptr, its unit normal
 struct GicpCov { const double* c6; const double* nx; const double* ny; const double* nz; };
 int  gicp_blocks(int n);
 // the exact nearest target point of every source point at T (fp32, nn_search): corr[s] = its sorted position or -1 (key >= dmax2), key[s] =
 // the squared distance; s = the source's sorted order
-void gicp_correspond(hipStream_t s, const float4* SP, int ns, PoseF T, const float4* TP, const int* tstart, Grid g, double dmax2, int* corr, float* key);
-// the terms of that pair list at T: M (6 * ns doubles, SoA) <- the Mahalanobis matrices; partials: gicp_blocks(ns) rows of kAccum + 1 doubles;
-// out29: the 28 sums and the number of pairs
-void gicp_terms(hipStream_t s, const float4* SP, int ns, const float4* TP, int nt, const int* corr, const GicpCov& A, const GicpCov& B, Pose T, int want_H,
+void gicp_correspond(hipStream_t s, const SortedCloud& src, PoseF T, const SortedCloud& tgt, double dmax2, int* corr, float* key);
+// the terms of that pair list at T: M (6 * src.n doubles, SoA) <- the Mahalanobis matrices; partials: gicp_blocks(src.n) rows of kAccum + 1
+// doubles; out29: the 28 sums and the number of pairs.  A / B: the source's / the target's covariances
+void gicp_terms(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const GicpCov& A, const GicpCov& B, Pose T, int want_H,
                 double* M, double* partials, double* out29);
 // the cost of the same pairs under the same matrices at another pose
-void gicp_error(hipStream_t s, const float4* SP, int ns, const float4* TP, int nt, const int* corr, const double* M, Pose T, double* partials, double* out1);
+void gicp_error(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const double* M, Pose T, double* partials, double* out1);
 // the pair list in caller order: idx[i] = the neighbour's original index or -1, sq[i] = the key
-void gicp_export(hipStream_t s, const float4* SP, int ns, const float4* TP, int nt, const int* corr, const float* key, int* idx, float* sq);
+void gicp_export(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const float* key, int* idx, float* sq);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,

@@ -20,7 +20,7 @@
 //   C8, f4          k_fitness(_lm), k_icp_accumulate, k_transform_f32 (nn_search and the cell / cube / distance helpers it is made of: rgc_nn.h,
 //                   shared with rgc_gicp.hip)
 //   f1              k_mapreg_associate, k_mapreg_terms, k_mapreg_fold
-//   launch wrappers at the end (namespace rgck, declared in rgc_kernels.h)
+//   launch wrappers at the end (namespace rgck, declared in rgc_kernels.h): they unpack a cloud's typed views into the launch; bulk_route picks the bulk kNN variant
 #include "rgc_kernels.h"
 #include "rgc_nn.h"
 #include "rgc_lm.h"
@@ -4476,47 +4476,72 @@ void rank_gather(hipStream_t s, const float* in, int stride_f, int n, const int*
 size_t deferred_bytes(int n) { return sizeof(int) * (2 * (size_t)n + 16); }
 
 // deferred list: [cnt, pad x15][idx n][thr n]
-static Deferred deferred_of(const void* buf, int n) {
-  int* base = (int*)const_cast<void*>(buf);
-  return Deferred{base + 16, (float*)(base + 16 + (size_t)n), base, nullptr, nullptr, nullptr, nullptr, 0.f, KnnCache{}, 0,
+static Deferred deferred_of(const DeferredBuf& d, int n) {
+  int* base = (int*)d.buf;
+  return Deferred{base + 16, (float*)(base + 16 + (size_t)n), base, d.guard, nullptr, nullptr, nullptr, 0.f, KnnCache{}, 0,
                   0, base + 1, reinterpret_cast<unsigned long long*>(base + 16), 0};
 }
-
-bool knn_bulk_fuses_voxels(bool is_target, int n, int k, int wide_r, const int* qlist, const KnnSeeds& seeds) {
-  const bool seeded = k == 20 && seeds.seed && n <= kSeedMaxPoints && seeds.warm;  // (knn_bulk_kc's choice of the seeded kernel)
-  return is_target && wide_r == 0 && !qlist && !seeded && n > 0;
+// launches sized from the previous cloud's deferred count: the waves that share the deferred list, the one-wave workgroups that patch its voxels
+static int clamp_coop_waves(int w) { return w < 32 ? 32 : (w > 8192 ? 8192 : w); }
+static int clamp_patch_waves(int w) { return w < 64 ? 64 : (w > 4096 ? 4096 : w); }
+bool knn_seeds_apply(int n, int k) { return k == 20 && n <= kSeedMaxPoints; }
+// The variant of the bulk launch, decided HERE only: the launch takes it from bulk_route, and so do the questions the API asks before it
+// launches (knn_bulk_fuses_voxels, knn_bulk_times_itself).  kWide: four lanes per query on the 5^3 block (a sparse map); kListed: the lazy
+// target's query list; the dense map's whole-map launch: kSeeded from the last search's k-th distances, kFused with the voxel stage inside,
+// kPlain; kScan: the scan's four-lanes-per-query launch
+struct BulkRoute {
+  enum Kind { kWide, kListed, kSeeded, kFused, kPlain, kScan } kind;
+  bool seeds_ok;  // the launch reads and writes the seeds (and the lists): the map's dense search at k == 20 only
+  bool seeded;    // ... and some search has written them: the seeded kernel is worth launching
+};
+static BulkRoute bulk_route(bool is_target, int n, int k, const KnnBulkOpts& o, bool want_fuse) {
+  BulkRoute r{BulkRoute::kScan, false, false};
+  r.seeds_ok = is_target && o.wide_r != 2 && o.seeds.seed && knn_seeds_apply(n, k);
+  r.seeded = r.seeds_ok && o.seeds.warm;
+  if (o.wide_r == 2) r.kind = BulkRoute::kWide;
+  else if (!is_target) r.kind = BulkRoute::kScan;
+  else if (o.qlist) r.kind = BulkRoute::kListed;
+  else if (r.seeded) r.kind = BulkRoute::kSeeded;
+  else if (want_fuse && o.wide_r == 0 && n > 0) r.kind = BulkRoute::kFused;
+  else r.kind = BulkRoute::kPlain;
+  return r;
+}
+bool knn_bulk_fuses_voxels(bool is_target, int n, int k, const KnnBulkOpts& o) { return bulk_route(is_target, n, k, o, true).kind == BulkRoute::kFused; }
+bool knn_bulk_times_itself(bool is_target, int n, int k, const KnnBulkOpts& o) {  // (the dense map's whole-map launches)
+  const BulkRoute::Kind kind = bulk_route(is_target, n, k, o, o.fuse.vox != nullptr).kind;
+  return kind == BulkRoute::kSeeded || kind == BulkRoute::kFused || kind == BulkRoute::kPlain;
 }
 template <int KC, bool kExact>
-static void knn_bulk_kc(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* deferred,
-                        double* nx, double* ny, double* nz, const int* guard, int wide_r, hipEvent_t ev0, hipEvent_t ev1,
-                        const int* qlist, const int* nq, int q_est, const KnnSeeds& seeds, int stream_coop_waves, const VoxFuse* fuse) {
-  Deferred df = deferred_of(deferred, n);  // df.cnt was zeroed by k_rank_gather
-  df.guard = guard;
+static void knn_bulk_kc(hipStream_t s, bool is_target, const SortedCloud& cl, int k, const DeferredBuf& dbuf, const Normals& nrm, const KnnBulkOpts& o) {
+  const float4* P = cl.P;
+  const int *start = cl.start, n = cl.n;
+  const Grid& g = cl.grid;
+  double *const nx = nrm.nx, *const ny = nrm.ny, *const nz = nrm.nz;
+  const BulkRoute route = bulk_route(is_target, n, k, o, o.fuse.vox != nullptr);
+  const bool seeded = route.seeded, listed = route.kind == BulkRoute::kListed, timed = o.ev0 && o.ev1;
+  Deferred df = deferred_of(dbuf, n);  // df.cnt was zeroed by k_rank_gather
   df.split_sums = is_target ? 0 : 1;
-  df.qlist = qlist; df.nq = nq;
-  // seeds: the map's dense search at k == KC only; `warm` = some search has written them (the seeded kernel is worth launching)
-  const bool seeds_ok = is_target && kExact && wide_r != 2 && seeds.seed && n <= kSeedMaxPoints;
-  df.seed = seeds_ok ? seeds.seed : nullptr;
-  df.seed_slack = seeds.slack;
-  const bool seeded = seeds_ok && seeds.warm;
-  if (seeds_ok && seeds.cache.nbr) df.cache = seeds.cache;  // (the searches write the lists and certificates from the first launch on)
-  if (wide_r == 2) {
+  df.qlist = o.qlist; df.nq = o.nq;
+  df.seed = route.seeds_ok ? o.seeds.seed : nullptr;
+  df.seed_slack = o.seeds.slack;
+  if (route.seeds_ok && o.seeds.cache.nbr) df.cache = o.seeds.cache;  // (the searches write the lists and certificates from the first launch on)
+  if (route.kind == BulkRoute::kWide) {
     const size_t ldsw = (size_t)SpShape<2, true>::LDS * WAVE * sizeof(int);
     hipLaunchKernelGGL((k_knn_sp_wide<KC, 2, kExact>), dim3(nblk(n, WAVE / 4)), dim3(WAVE), ldsw, s, P, start, g, n, k, df, nx, ny, nz);
     return;
   }
   using CT = SpConfig<true>;
   using CS = SpConfig<false>;
-  const int T = is_target ? (seeded && !qlist ? kSeedT : CT::T) : CS::T;
+  const int T = is_target ? (route.kind == BulkRoute::kSeeded ? kSeedT : CT::T) : CS::T;
   // (the scan's launch lays its per-lane LDS columns out for the 3x3x3 block and again, for the queries that block does not settle, for the 5x5x5 one)
   const size_t lds = (size_t)(is_target ? (seeded ? std::max(SpShape<CT::R, CT::kClip>::LDS, SeedShape<KC>::LDS) : SpShape<CT::R, CT::kClip>::LDS)
                                         : std::max(SpShape<CS::R, CS::kClip>::LDS, SpShape<2, CS::kClip>::LDS)) * T * sizeof(int);
   // whole rounds of 8 XCDs x xcd_run blocks (excess blocks fall out at i >= n); lazy target: as many blocks as the listed queries are
   // expected to fill (the kernel strides over the list whatever its true length)
-  const int n_launch = (is_target && qlist) ? (q_est < T ? T : (q_est > n ? n : q_est)) : n;
+  const int n_launch = listed ? (o.q_est < T ? T : (o.q_est > n ? n : o.q_est)) : n;
   const int xcd_run = kXcdRunQueries / T;
-  int nb = (is_target && qlist) ? nblk(n_launch, T) : 8 * xcd_run * nblk(nblk(n, T), 8 * xcd_run);
-  if (seeded && !qlist && df.cache.nbr) {
+  int nb = listed ? nblk(n_launch, T) : 8 * xcd_run * nblk(nblk(n, T), 8 * xcd_run);
+  if (route.kind == BulkRoute::kSeeded && df.cache.nbr) {
     // the workgroups in front of the bulk ones search the listed queries: sized for 4 % of the map (they stride over longer lists)
     df.cache_nb = kTodoLists * std::max(1, nblk((int)(0.04 * (double)n / kTodoLists) + 1, T));
     nb += df.cache_nb;
@@ -4524,133 +4549,121 @@ static void knn_bulk_kc(hipStream_t s, bool is_target, const float4* P, const in
   // (ev0 / ev1: the launch's own start / stop times go into the caller's events -- no separate record packets around it)
   if constexpr (kExact) {
     if (seeded) {
-      if (qlist) hipLaunchKernelGGL((k_knn_sp_listed<KC, true, true>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
-      else if (ev0 && ev1) hipExtLaunchKernelGGL((k_knn_sp<KC, true, true, true>), dim3(nb), dim3(T), (std::uint32_t)lds, s, ev0, ev1, 0u, P, start, g, n, k, df, nx, ny, nz);
+      if (listed) hipLaunchKernelGGL((k_knn_sp_listed<KC, true, true>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
+      else if (timed) hipExtLaunchKernelGGL((k_knn_sp<KC, true, true, true>), dim3(nb), dim3(T), (std::uint32_t)lds, s, o.ev0, o.ev1, 0u, P, start, g, n, k, df, nx, ny, nz);
       else hipLaunchKernelGGL((k_knn_sp<KC, true, true, true>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
       return;
     }
   }
-  VoxOut vo{nullptr, nullptr, nullptr};
-  if (fuse && knn_bulk_fuses_voxels(is_target, n, k, wide_r, qlist, seeds)) {
-    // the workgroups build their own cells' voxel records, and the launch's last workgroups resolve the deferred queries (voxel_seams follows)
-    vo = VoxOut{fuse->vox, fuse->vox_cell, fuse->cell_voxel};
-    const int w = fuse->coop_waves;
-    df.coop_blocks = nblk(w < 32 ? 32 : (w > 8192 ? 8192 : w), T / WAVE);
-    static_assert(sizeof(CoopRows) * (CT::T / WAVE) <= (size_t)SpShape<CT::R, CT::kClip>::LDS * CT::T * sizeof(int), "the cooperative waves' scratch fits the bulk launch's LDS");
-    nb += df.coop_blocks;
-  }
-  if (is_target && qlist) hipLaunchKernelGGL((k_knn_sp_listed<KC, kExact>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
-  else if (is_target && vo.vox && ev0 && ev1) hipExtLaunchKernelGGL((k_knn_sp_vox<KC, kExact>), dim3(nb), dim3(T), (std::uint32_t)lds, s, ev0, ev1, 0u, P, start, g, n, k, df, nx, ny, nz, vo);
-  else if (is_target && vo.vox) hipLaunchKernelGGL((k_knn_sp_vox<KC, kExact>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz, vo);
-  else if (is_target && ev0 && ev1) hipExtLaunchKernelGGL((k_knn_sp<KC, true, kExact>), dim3(nb), dim3(T), (std::uint32_t)lds, s, ev0, ev1, 0u, P, start, g, n, k, df, nx, ny, nz);
-  else if (is_target) hipLaunchKernelGGL((k_knn_sp<KC, true, kExact>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
-  else {  // four lanes per query; the deferred queries resolved by the launch's last workgroups (coop_stream) when the caller asks for it
-    if (stream_coop_waves > 0) df.coop_blocks = nblk(stream_coop_waves < 32 ? 32 : (stream_coop_waves > 8192 ? 8192 : stream_coop_waves), T / WAVE);
-    static_assert(sizeof(CoopRows) * (CS::T / WAVE) <= (size_t)SpShape<CS::R, CS::kClip>::LDS * CS::T * sizeof(int), "the cooperative waves' scratch fits the bulk launch's LDS");
-    hipLaunchKernelGGL((k_knn_sp<KC, false, kExact>), dim3(nblk(n, T / 4) + df.coop_blocks), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
+  switch (route.kind) {
+    case BulkRoute::kListed: hipLaunchKernelGGL((k_knn_sp_listed<KC, kExact>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz); break;
+    case BulkRoute::kFused: {
+      // the workgroups build their own cells' voxel records, and the launch's last workgroups resolve the deferred queries (voxel_seams follows)
+      const VoxOut vo{o.fuse.vox, o.fuse.vox_cell, o.fuse.cell_voxel};
+      df.coop_blocks = nblk(clamp_coop_waves(o.coop_waves), T / WAVE);
+      static_assert(sizeof(CoopRows) * (CT::T / WAVE) <= (size_t)SpShape<CT::R, CT::kClip>::LDS * CT::T * sizeof(int), "the cooperative waves' scratch fits the bulk launch's LDS");
+      nb += df.coop_blocks;
+      if (timed) hipExtLaunchKernelGGL((k_knn_sp_vox<KC, kExact>), dim3(nb), dim3(T), (std::uint32_t)lds, s, o.ev0, o.ev1, 0u, P, start, g, n, k, df, nx, ny, nz, vo);
+      else hipLaunchKernelGGL((k_knn_sp_vox<KC, kExact>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz, vo);
+      break;
+    }
+    case BulkRoute::kPlain:
+      if (timed) hipExtLaunchKernelGGL((k_knn_sp<KC, true, kExact>), dim3(nb), dim3(T), (std::uint32_t)lds, s, o.ev0, o.ev1, 0u, P, start, g, n, k, df, nx, ny, nz);
+      else hipLaunchKernelGGL((k_knn_sp<KC, true, kExact>), dim3(nb), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
+      break;
+    default:  // kScan: four lanes per query; the deferred queries resolved by the launch's last workgroups (coop_stream) when the caller asks for it
+      if (o.coop_waves > 0) df.coop_blocks = nblk(clamp_coop_waves(o.coop_waves), T / WAVE);
+      static_assert(sizeof(CoopRows) * (CS::T / WAVE) <= (size_t)SpShape<CS::R, CS::kClip>::LDS * CS::T * sizeof(int), "the cooperative waves' scratch fits the bulk launch's LDS");
+      hipLaunchKernelGGL((k_knn_sp<KC, false, kExact>), dim3(nblk(n, T / 4) + df.coop_blocks), dim3(T), lds, s, P, start, g, n, k, df, nx, ny, nz);
   }
 }
-bool knn_seeds_apply(int n, int k) { return k == 20 && n <= kSeedMaxPoints; }
 static void deferred_seeds(Deferred& df, const KnnSeeds& seeds, int n, int k) {  // the cooperative search leaves its k-th distance as the point's seed
   if (seeds.seed && knn_seeds_apply(n, k)) { df.seed = seeds.seed; df.seed_slack = seeds.slack; }
 }
 template <int KC>
-static void knn_coop_kc(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* segs,
-                        double* nx, double* ny, double* nz, const int* guard, int waves, const KnnSeeds& seeds) {
-  Deferred df = deferred_of(segs, n);
-  df.guard = guard;
-  if (is_target) deferred_seeds(df, seeds, n, k);
+static void knn_coop_kc(hipStream_t s, bool is_target, const SortedCloud& cl, int k, const DeferredBuf& dbuf, const Normals& nrm, int waves, const KnnSeeds& seeds) {
+  Deferred df = deferred_of(dbuf, cl.n);
+  if (is_target) deferred_seeds(df, seeds, cl.n, k);
   // the number of deferred queries is only known on the device: `waves` one-wave workgroups share the list (each takes every
   // waves-th entry); the caller sizes it from the previous cloud of the sequence
-  const int nbc = waves < 32 ? 32 : (waves > 8192 ? 8192 : waves);
+  const int nbc = clamp_coop_waves(waves);
   if (is_target)
-    hipLaunchKernelGGL((k_knn_coop<KC, true>), dim3(nbc), dim3(WAVE), 0, s, P, start, g, k, df, nx, ny, nz);
+    hipLaunchKernelGGL((k_knn_coop<KC, true>), dim3(nbc), dim3(WAVE), 0, s, cl.P, cl.start, cl.grid, k, df, nrm.nx, nrm.ny, nrm.nz);
   else
-    hipLaunchKernelGGL((k_knn_coop<KC, false>), dim3(nbc), dim3(WAVE), 0, s, P, start, g, k, df, nx, ny, nz);
+    hipLaunchKernelGGL((k_knn_coop<KC, false>), dim3(nbc), dim3(WAVE), 0, s, cl.P, cl.start, cl.grid, k, df, nrm.nx, nrm.ny, nrm.nz);
 }
-bool knn_bulk_times_itself(bool is_target, int wide_r) { return is_target && wide_r != 2; }
-void knn_bulk(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* deferred, double* nx,
-              double* ny, double* nz, const int* guard, int wide_r, hipEvent_t ev0, hipEvent_t ev1, const int* qlist, const int* nq, int q_est,
-              const KnnSeeds& seeds, int stream_coop_waves, const VoxFuse* fuse) {
-  if (is_target || wide_r == 2) stream_coop_waves = 0;  // (the scan's four-lane search only)
+void knn_bulk(hipStream_t s, bool is_target, const SortedCloud& cl, int k, const DeferredBuf& df, const Normals& nrm, const KnnBulkOpts& o) {
   // (k == 20, the reference's setting, gets an instance without the general-k branches)
-  if (k == 20) knn_bulk_kc<20, true>(s, is_target, P, start, g, n, k, deferred, nx, ny, nz, guard, wide_r, ev0, ev1, qlist, nq, q_est, seeds, stream_coop_waves, fuse);
-  else if (k < 20) knn_bulk_kc<20, false>(s, is_target, P, start, g, n, k, deferred, nx, ny, nz, guard, wide_r, ev0, ev1, qlist, nq, q_est, seeds, stream_coop_waves, fuse);
-  else knn_bulk_kc<32, false>(s, is_target, P, start, g, n, k, deferred, nx, ny, nz, guard, wide_r, ev0, ev1, qlist, nq, q_est, seeds, stream_coop_waves, fuse);
+  if (k == 20) knn_bulk_kc<20, true>(s, is_target, cl, k, df, nrm, o);
+  else if (k < 20) knn_bulk_kc<20, false>(s, is_target, cl, k, df, nrm, o);
+  else knn_bulk_kc<32, false>(s, is_target, cl, k, df, nrm, o);
 }
 
-void knn_coop(hipStream_t s, bool is_target, const float4* P, const int* start, Grid g, int n, int k, const void* segs, double* nx,
-              double* ny, double* nz, const int* guard, int waves, const KnnSeeds& seeds) {
-  if (k <= 20) knn_coop_kc<20>(s, is_target, P, start, g, n, k, segs, nx, ny, nz, guard, waves, seeds);
-  else knn_coop_kc<32>(s, is_target, P, start, g, n, k, segs, nx, ny, nz, guard, waves, seeds);
+void knn_coop(hipStream_t s, bool is_target, const SortedCloud& cl, int k, const DeferredBuf& df, const Normals& nrm, int waves, const KnnSeeds& seeds) {
+  if (k <= 20) knn_coop_kc<20>(s, is_target, cl, k, df, nrm, waves, seeds);
+  else knn_coop_kc<32>(s, is_target, cl, k, df, nrm, waves, seeds);
 }
-void footprint(hipStream_t s, const float* in, int stride_f, int n, Pose T, Grid g, int* need, int stamp, int margin, const float4* P, int n_map,
-               const int* start, int* qlist, int* cell_list, int* counts, const int* guard) {
-  if (n > 0) hipLaunchKernelGGL(k_footprint, dim3(nblk(n, 256)), dim3(256), 0, s, in, stride_f, n, T, g, need, stamp, margin);
-  if (n_map > 0) hipLaunchKernelGGL(k_lazy_lists, dim3(nblk(n_map, kListT)), dim3(kListT), 0, s, P, n_map, g, start, need, stamp, qlist, cell_list, counts, guard);
+void footprint(hipStream_t s, const float* in, int stride_f, int n, Pose T, const SortedCloud& map, int* need, int stamp, int margin, int* qlist,
+               int* cell_list, int* counts, const int* guard) {
+  if (n > 0) hipLaunchKernelGGL(k_footprint, dim3(nblk(n, 256)), dim3(256), 0, s, in, stride_f, n, T, map.grid, need, stamp, margin);
+  if (map.n > 0) hipLaunchKernelGGL(k_lazy_lists, dim3(nblk(map.n, kListT)), dim3(kListT), 0, s, map.P, map.n, map.grid, map.start, need, stamp, qlist, cell_list, counts, guard);
 }
-void voxel_cells_coop(hipStream_t s, const float4* P, double* nx, double* ny, double* nz, const int* start, Grid g, int n, const int* cell_voxel,
-                      double* vox, int* vox_cell, int k, const void* deferred, const int* guard, int waves, const int* cell_list, const int* ncells,
-                      int cells_est, const KnnSeeds& seeds) {
-  Deferred df = deferred_of(deferred, n);
-  df.guard = guard;
-  deferred_seeds(df, seeds, n, k);
-  const int nbc = nblk(waves < 32 ? 32 : (waves > 8192 ? 8192 : waves), VOX_T / WAVE);
+void voxel_cells_coop(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm, int k, const DeferredBuf& dbuf, int waves,
+                      const int* cell_list, const int* ncells, int cells_est, const KnnSeeds& seeds) {
+  Deferred df = deferred_of(dbuf, cl.n);
+  deferred_seeds(df, seeds, cl.n, k);
+  const int nbc = nblk(clamp_coop_waves(waves), VOX_T / WAVE);
   const int nbv = nblk(cells_est < 256 ? 256 : (cells_est > (1 << 20) ? (1 << 20) : cells_est), VOX_T / WAVE);  // a wave per listed cell (grid-stride beyond the estimate)
-  if (k <= 20) hipLaunchKernelGGL((k_voxel_cells_coop<20>), dim3(nbc + nbv), dim3(VOX_T), 0, s, P, nx, ny, nz, start, g, cell_voxel, vox, vox_cell, nbc, k, df, cell_list, ncells);
-  else hipLaunchKernelGGL((k_voxel_cells_coop<32>), dim3(nbc + nbv), dim3(VOX_T), 0, s, P, nx, ny, nz, start, g, cell_voxel, vox, vox_cell, nbc, k, df, cell_list, ncells);
+  if (k <= 20) hipLaunchKernelGGL((k_voxel_cells_coop<20>), dim3(nbc + nbv), dim3(VOX_T), 0, s, cl.P, nrm.nx, nrm.ny, nrm.nz, cl.start, cl.grid, vm.cell_voxel, vm.vox, vm.vox_cell, nbc, k, df, cell_list, ncells);
+  else hipLaunchKernelGGL((k_voxel_cells_coop<32>), dim3(nbc + nbv), dim3(VOX_T), 0, s, cl.P, nrm.nx, nrm.ny, nrm.nz, cl.start, cl.grid, vm.cell_voxel, vm.vox, vm.vox_cell, nbc, k, df, cell_list, ncells);
 }
-void voxel_build(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, const int* start, Grid g,
-                 int n, const int* cell_voxel, double* vox, int* vox_cell) {
-  hipLaunchKernelGGL(k_voxel_build, dim3(nblk(n, VOX_T)), dim3(VOX_T), 0, s, P, nx, ny, nz, start, g, n, cell_voxel, vox, vox_cell);
+void voxel_build(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm) {
+  hipLaunchKernelGGL(k_voxel_build, dim3(nblk(cl.n, VOX_T)), dim3(VOX_T), 0, s, cl.P, nrm.nx, nrm.ny, nrm.nz, cl.start, cl.grid, cl.n, vm.cell_voxel, vm.vox, vm.vox_cell);
 }
-void voxel_build_coop(hipStream_t s, const float4* P, double* nx, double* ny, double* nz, const int* start, Grid g, int n, const int* cell_voxel,
-                      double* vox, int* vox_cell, int k, const void* deferred, const int* guard, int waves, const KnnSeeds& seeds) {
-  Deferred df = deferred_of(deferred, n);
-  df.guard = guard;
-  deferred_seeds(df, seeds, n, k);
-  const int nbv = nblk(n, VOX_T);
-  const int nbc = nblk(waves < 32 ? 32 : (waves > 8192 ? 8192 : waves), VOX_T / WAVE);
-  if (k <= 20) hipLaunchKernelGGL((k_voxel_build_coop<20>), dim3(nbv + nbc), dim3(VOX_T), 0, s, P, nx, ny, nz, start, g, n, cell_voxel, vox, vox_cell, nbc, k, df);
-  else hipLaunchKernelGGL((k_voxel_build_coop<32>), dim3(nbv + nbc), dim3(VOX_T), 0, s, P, nx, ny, nz, start, g, n, cell_voxel, vox, vox_cell, nbc, k, df);
+void voxel_build_coop(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm, int k, const DeferredBuf& dbuf, int waves, const KnnSeeds& seeds) {
+  Deferred df = deferred_of(dbuf, cl.n);
+  deferred_seeds(df, seeds, cl.n, k);
+  const int nbv = nblk(cl.n, VOX_T);
+  const int nbc = nblk(clamp_coop_waves(waves), VOX_T / WAVE);
+  if (k <= 20) hipLaunchKernelGGL((k_voxel_build_coop<20>), dim3(nbv + nbc), dim3(VOX_T), 0, s, cl.P, nrm.nx, nrm.ny, nrm.nz, cl.start, cl.grid, cl.n, vm.cell_voxel, vm.vox, vm.vox_cell, nbc, k, df);
+  else hipLaunchKernelGGL((k_voxel_build_coop<32>), dim3(nbv + nbc), dim3(VOX_T), 0, s, cl.P, nrm.nx, nrm.ny, nrm.nz, cl.start, cl.grid, cl.n, vm.cell_voxel, vm.vox, vm.vox_cell, nbc, k, df);
 }
-void voxel_patch(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, const int* start, Grid g, const void* deferred,
-                 const int* cell_voxel, double* vox, int lanes, hipEvent_t done) {
-  const int nb = lanes < 64 ? 64 : (lanes > 4096 ? 4096 : lanes);  // one-wave workgroups, one deferred entry each (grid-stride beyond)
+void voxel_patch(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm, const DeferredBuf& df, int lanes, hipEvent_t done) {
+  const int nb = clamp_patch_waves(lanes);  // one-wave workgroups, one deferred entry each (grid-stride beyond)
+  const int* deferred = (const int*)df.buf;
   // (done: the launch's own completion is the event -- no record packet between the map's last kernel and the solve's first step)
-  if (done) hipExtLaunchKernelGGL(k_voxel_patch, dim3(nb), dim3(WAVE), 0u, s, nullptr, done, 0u, P, nx, ny, nz, start, g, (const int*)deferred, cell_voxel, vox);
-  else hipLaunchKernelGGL(k_voxel_patch, dim3(nb), dim3(WAVE), 0, s, P, nx, ny, nz, start, g, (const int*)deferred, cell_voxel, vox);
+  if (done) hipExtLaunchKernelGGL(k_voxel_patch, dim3(nb), dim3(WAVE), 0u, s, nullptr, done, 0u, cl.P, nrm.nx, nrm.ny, nrm.nz, cl.start, cl.grid, deferred, vm.cell_voxel, vm.vox);
+  else hipLaunchKernelGGL(k_voxel_patch, dim3(nb), dim3(WAVE), 0, s, cl.P, nrm.nx, nrm.ny, nrm.nz, cl.start, cl.grid, deferred, vm.cell_voxel, vm.vox);
 }
-void voxel_seams(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, const int* start, Grid g, int n, void* deferred,
-                 const int* cell_voxel, double* vox, int* vox_cell, const int* guard, int patch_waves, hipEvent_t done) {
-  const int nseam = nblk(n, VOX_T) - 1;  // block boundaries inside the cloud
-  const int nb = nseam + (patch_waves < 64 ? 64 : (patch_waves > 4096 ? 4096 : patch_waves));  // one-wave workgroups; the patch waves stride over the list
+void voxel_seams(hipStream_t s, const SortedCloud& cl, const Normals& nrm, const VoxelMap& vm, const DeferredBuf& df, int patch_waves, hipEvent_t done) {
+  const int nseam = nblk(cl.n, VOX_T) - 1;  // block boundaries inside the cloud
+  const int nb = nseam + clamp_patch_waves(patch_waves);  // one-wave workgroups; the patch waves stride over the list
+  int* deferred = (int*)df.buf;
   // (done: the launch's own completion is the event, as voxel_patch's)
-  if (done) hipExtLaunchKernelGGL(k_voxel_seams, dim3(nb), dim3(WAVE), 0u, s, nullptr, done, 0u, P, nx, ny, nz, start, g, n, (int*)deferred, cell_voxel, vox, vox_cell, nseam, guard);
-  else hipLaunchKernelGGL(k_voxel_seams, dim3(nb), dim3(WAVE), 0, s, P, nx, ny, nz, start, g, n, (int*)deferred, cell_voxel, vox, vox_cell, nseam, guard);
+  if (done) hipExtLaunchKernelGGL(k_voxel_seams, dim3(nb), dim3(WAVE), 0u, s, nullptr, done, 0u, cl.P, nrm.nx, nrm.ny, nrm.nz, cl.start, cl.grid, cl.n, deferred, vm.cell_voxel, vm.vox, vm.vox_cell, nseam, df.guard);
+  else hipLaunchKernelGGL(k_voxel_seams, dim3(nb), dim3(WAVE), 0, s, cl.P, nrm.nx, nrm.ny, nrm.nz, cl.start, cl.grid, cl.n, deferred, vm.cell_voxel, vm.vox, vm.vox_cell, nseam, df.guard);
 }
-void linearize(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Pose T, Grid g,
-               const int* cell_voxel, const double* vox, int noff, int* corr_v, double* corr_M, int want_H, double* partials,
-               int* ncorr_partials, double* out28, int* out_ncorr) {
-  const int nb = linearize_blocks(n);
-  hipLaunchKernelGGL(k_linearize, dim3(nb), dim3(LIN_T), 0, s, P, nx, ny, nz, n, T, g, cell_voxel, vox, noff, corr_v, corr_M, want_H, partials, ncorr_partials);
+void linearize(hipStream_t s, const SortedCloud& src, const Normals& nrm, Pose T, const Grid& g, const VoxelMap& vm, int noff, Corr corr, int want_H,
+               double* partials, int* ncorr_partials, double* out28, int* out_ncorr) {
+  const int nb = linearize_blocks(src.n);
+  hipLaunchKernelGGL(k_linearize, dim3(nb), dim3(LIN_T), 0, s, src.P, nrm.nx, nrm.ny, nrm.nz, src.n, T, g, vm.cell_voxel, vm.vox, noff, corr.v, corr.M, want_H, partials, ncorr_partials);
   hipLaunchKernelGGL(k_fold<kAccum>, dim3(kAccum + 1), dim3(WAVE), 0, s, partials, nb, out28, ncorr_partials, out_ncorr);
 }
 // ---- the general covariance route ----
-void knn_cov6(hipStream_t s, const float4* P, const int* start, Grid g, int n, int k, int method, double* c6, const int* guard) {
-  const GenOut go{c6, method, n};
-  const int waves = n < 16384 ? n : 16384;
-  if (k <= 20) hipLaunchKernelGGL(k_knn_cov6<20>, dim3(waves), dim3(WAVE), 0, s, P, start, g, n, k, go, guard);
-  else hipLaunchKernelGGL(k_knn_cov6<32>, dim3(waves), dim3(WAVE), 0, s, P, start, g, n, k, go, guard);
+void knn_cov6(hipStream_t s, const SortedCloud& cl, int k, int method, double* c6, const int* guard) {
+  const GenOut go{c6, method, cl.n};
+  const int waves = cl.n < 16384 ? cl.n : 16384;
+  if (k <= 20) hipLaunchKernelGGL(k_knn_cov6<20>, dim3(waves), dim3(WAVE), 0, s, cl.P, cl.start, cl.grid, cl.n, k, go, guard);
+  else hipLaunchKernelGGL(k_knn_cov6<32>, dim3(waves), dim3(WAVE), 0, s, cl.P, cl.start, cl.grid, cl.n, k, go, guard);
 }
-void voxel_build_general(hipStream_t s, const float4* P, const double* c6, const int* start, Grid g, int n, const int* cell_voxel, double* vox,
-                         int* vox_cell, int multiplicative, const int* guard) {
-  hipLaunchKernelGGL(k_voxel_build_general, dim3(nblk(g.ncell, 256)), dim3(256), 0, s, P, c6, start, g.ncell, n, cell_voxel, vox, vox_cell, multiplicative, guard);
+void voxel_build_general(hipStream_t s, const SortedCloud& cl, const double* c6, const VoxelMap& vm, int multiplicative, const int* guard) {
+  const int ncell = cl.grid.ncell;
+  hipLaunchKernelGGL(k_voxel_build_general, dim3(nblk(ncell, 256)), dim3(256), 0, s, cl.P, c6, cl.start, ncell, cl.n, vm.cell_voxel, vm.vox, vm.vox_cell, multiplicative, guard);
 }
-void linearize_general(hipStream_t s, const float4* P, const double* c6, int n, Pose T, Grid g, const int* cell_voxel, const double* vox, int noff,
-                       int* corr_v, double* corr_M, int want_H, double* partials, int* ncorr_partials, double* out28, int* out_ncorr) {
-  const int nb = linearize_blocks(n);
-  hipLaunchKernelGGL(k_linearize_general, dim3(nb), dim3(LIN_T), 0, s, P, c6, n, T, g, cell_voxel, vox, noff, corr_v, corr_M, want_H, partials, ncorr_partials);
+void linearize_general(hipStream_t s, const SortedCloud& src, const double* c6, Pose T, const Grid& g, const VoxelMap& vm, int noff, Corr corr,
+                       int want_H, double* partials, int* ncorr_partials, double* out28, int* out_ncorr) {
+  const int nb = linearize_blocks(src.n);
+  hipLaunchKernelGGL(k_linearize_general, dim3(nb), dim3(LIN_T), 0, s, src.P, c6, src.n, T, g, vm.cell_voxel, vm.vox, noff, corr.v, corr.M, want_H, partials, ncorr_partials);
   hipLaunchKernelGGL(k_fold<kAccum>, dim3(kAccum + 1), dim3(WAVE), 0, s, partials, nb, out28, ncorr_partials, out_ncorr);
 }
 void unsort6(hipStream_t s, const double* c6, const float4* P, int n, double* out9) {
@@ -4659,53 +4672,49 @@ void unsort6(hipStream_t s, const double* c6, const float4* P, int n, double* ou
 void sort6(hipStream_t s, const double* in9, const float4* P, int n, double* c6) {
   hipLaunchKernelGGL(k_sort6, dim3(nblk(n, 256)), dim3(256), 0, s, in9, P, n, c6);
 }
-void compute_error(hipStream_t s, const float4* P, int n, Pose T, const double* vox, int noff, const int* corr_v,
-                   const double* corr_M, double* partials, double* out1) {
+void compute_error(hipStream_t s, const float4* P, int n, Pose T, const double* vox, int noff, Corr corr, double* partials, double* out1) {
   const int nb = linearize_blocks(n);
-  hipLaunchKernelGGL(k_error, dim3(nb), dim3(LIN_T), 0, s, P, n, T, vox, noff, corr_v, corr_M, partials);
+  hipLaunchKernelGGL(k_error, dim3(nb), dim3(LIN_T), 0, s, P, n, T, vox, noff, corr.v, corr.M, partials);
   hipLaunchKernelGGL(k_fold<1>, dim3(1), dim3(WAVE), 0, s, partials, nb, out1, (const int*)nullptr, (int*)nullptr);
 }
 void lm_try(hipStream_t s, double* out, const int* ncorr, LmIn in) {
   hipLaunchKernelGGL(k_lm_try, dim3(1), dim3(WAVE), 0, s, out, ncorr, in);
 }
-void compute_error_dev(hipStream_t s, const float4* P, int n, const double* Tdev, const double* vox, int noff, const int* corr_v,
-                       const double* corr_M, double* partials, double* out1) {
+void compute_error_dev(hipStream_t s, const float4* P, int n, const double* Tdev, const double* vox, int noff, Corr corr, double* partials, double* out1) {
   const int nb = linearize_blocks(n);
-  hipLaunchKernelGGL(k_error_dev, dim3(nb), dim3(LIN_T), 0, s, P, n, Tdev, vox, noff, corr_v, corr_M, partials);
+  hipLaunchKernelGGL(k_error_dev, dim3(nb), dim3(LIN_T), 0, s, P, n, Tdev, vox, noff, corr.v, corr.M, partials);
   hipLaunchKernelGGL(k_fold<1>, dim3(1), dim3(WAVE), 0, s, partials, nb, out1, (const int*)nullptr, (int*)nullptr);
 }
 // a map of at most this many points is scanned whole by the wave for a query its first cube does not settle (fitness_wave)
 static int fitness_scan_all(int nt) { return nt > 0 && nt <= 32768 ? nt : 0; }
-void lm_step(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Grid g, const int* cell_voxel,
-             const double* vox, int noff, int* corr_v0, double* corr_M0, int* corr_v1, double* corr_M1, double* partials, LmState* st,
-             int j, const LmInit* open, const int* nvox, const void* segs_t, const void* segs_s, LmState* h_post, int seq, const float4* TP,
-             const int* tstart, double* fit_partials, int nt, const int* lazy_need, int lazy_stamp, const int* lazy_counts, LmEarly* h_early) {
-  const FitArgs fa{TP, tstart, fit_partials, fitness_scan_all(nt), (TP && tstart && fit_partials) ? 1 : 0, lazy_need, lazy_stamp, lazy_counts, h_early};
-  hipLaunchKernelGGL(k_lm_step, dim3(linearize_blocks(n)), dim3(LIN_T), 0, s, P, nx, ny, nz, n, g, cell_voxel, vox, noff, corr_v0, corr_M0, corr_v1,
-                     corr_M1, partials, st, j, (j == 0 && open) ? *open : LmInit{}, nvox, (const int*)segs_t, (const int*)segs_s, h_post, seq, fa);
+// what the score chained to a solve needs (FitArgs): the map's sorted points where a score is chained, nothing of them otherwise
+static FitArgs fit_args_of(const LmArgs& a) {
+  const bool on = a.fit_partials != nullptr;
+  return FitArgs{on ? a.tgt.P : nullptr, on ? a.tgt.start : nullptr, a.fit_partials, fitness_scan_all(a.tgt.n), on ? 1 : 0,
+                 a.lazy_need, a.lazy_stamp, a.lazy_counts, a.h_early};
 }
-void lm_solve_resident(hipStream_t s, const float4* P, const double* nx, const double* ny, const double* nz, int n, Grid g, const int* cell_voxel,
-              const double* vox, int noff, int* corr_v0, double* corr_M0, int* corr_v1, double* corr_M1, double* partials, LmState* st,
-              const LmInit& open, const int* nvox, const void* segs_t, const void* segs_s, LmState* h_post, int seq, const float4* TP,
-              const int* tstart, double* fit_partials, int nt, const int* lazy_need, int lazy_stamp, const int* lazy_counts, LmEarly* h_early,
-              int give_up_at) {
-  const FitArgs fa{TP, tstart, fit_partials, fitness_scan_all(nt), (TP && tstart && fit_partials) ? 1 : 0, lazy_need, lazy_stamp, lazy_counts, h_early};
-  hipLaunchKernelGGL(k_lm_solve, dim3(linearize_blocks(n)), dim3(LIN_T), 0, s, P, nx, ny, nz, n, g, cell_voxel, vox, noff, corr_v0, corr_M0, corr_v1,
-                     corr_M1, partials, st, open, nvox, (const int*)segs_t, (const int*)segs_s, h_post, seq, fa, give_up_at);
+void lm_step(hipStream_t s, const LmArgs& a, int j, const LmInit* open) {
+  hipLaunchKernelGGL(k_lm_step, dim3(linearize_blocks(a.src.n)), dim3(LIN_T), 0, s, a.src.P, a.nrm.nx, a.nrm.ny, a.nrm.nz, a.src.n, a.tgt.grid, a.vm.cell_voxel,
+                     a.vm.vox, a.noff, a.corr[0].v, a.corr[0].M, a.corr[1].v, a.corr[1].M, a.partials, a.st, j, (j == 0 && open) ? *open : LmInit{}, a.nvox,
+                     (const int*)a.segs_t, (const int*)a.segs_s, a.h_post, a.seq, fit_args_of(a));
 }
-void fitness_lm(hipStream_t s, const float4* SP, int ns, LmState* st, const float4* TP, const int* tstart, Grid g, double* partials, LmState* h_post,
-                int seq, int nt) {
-  hipLaunchKernelGGL(k_fitness_lm, dim3(fitness_blocks(ns)), dim3(FIT_T), 0, s, SP, ns, st, TP, tstart, g, partials, h_post, seq, fitness_scan_all(nt));
+void lm_solve_resident(hipStream_t s, const LmArgs& a, const LmInit& open, int give_up_at) {
+  hipLaunchKernelGGL(k_lm_solve, dim3(linearize_blocks(a.src.n)), dim3(LIN_T), 0, s, a.src.P, a.nrm.nx, a.nrm.ny, a.nrm.nz, a.src.n, a.tgt.grid, a.vm.cell_voxel,
+                     a.vm.vox, a.noff, a.corr[0].v, a.corr[0].M, a.corr[1].v, a.corr[1].M, a.partials, a.st, open, a.nvox, (const int*)a.segs_t,
+                     (const int*)a.segs_s, a.h_post, a.seq, fit_args_of(a), give_up_at);
 }
-void fitness(hipStream_t s, const float4* SP, int ns, PoseF T, const float4* TP, const int* tstart, Grid g, double* partials, double* out1, int nt) {
+void fitness_lm(hipStream_t s, const SortedCloud& src, LmState* st, const SortedCloud& tgt, double* partials, LmState* h_post, int seq) {
+  hipLaunchKernelGGL(k_fitness_lm, dim3(fitness_blocks(src.n)), dim3(FIT_T), 0, s, src.P, src.n, st, tgt.P, tgt.start, tgt.grid, partials, h_post, seq,
+                     fitness_scan_all(tgt.n));
+}
+void fitness(hipStream_t s, const float4* SP, int ns, PoseF T, const SortedCloud& tgt, double* partials, double* out1, bool scan_small_map) {
   const int nb = fitness_blocks(ns);
-  hipLaunchKernelGGL(k_fitness, dim3(nb), dim3(FIT_T), 0, s, SP, ns, T, TP, tstart, g, partials, fitness_scan_all(nt));
+  hipLaunchKernelGGL(k_fitness, dim3(nb), dim3(FIT_T), 0, s, SP, ns, T, tgt.P, tgt.start, tgt.grid, partials, scan_small_map ? fitness_scan_all(tgt.n) : 0);
   hipLaunchKernelGGL(k_fold<1>, dim3(1), dim3(WAVE), 0, s, partials, nb, out1, (const int*)nullptr, (int*)nullptr);
 }
-void icp_accumulate(hipStream_t s, const float4* SP, int ns, const float4* TP, const int* tstart, Grid g, double max_dist, double* partials,
-                    double* out28) {
+void icp_accumulate(hipStream_t s, const float4* SP, int ns, const SortedCloud& tgt, double max_dist, double* partials, double* out28) {
   const int nb = linearize_blocks(ns);
-  hipLaunchKernelGGL(k_icp_accumulate, dim3(nb), dim3(LIN_T), 0, s, SP, ns, TP, tstart, g, max_dist, max_dist * max_dist, partials);
+  hipLaunchKernelGGL(k_icp_accumulate, dim3(nb), dim3(LIN_T), 0, s, SP, ns, tgt.P, tgt.start, tgt.grid, max_dist, max_dist * max_dist, partials);
   hipLaunchKernelGGL(k_fold<kAccum>, dim3(kAccum), dim3(WAVE), 0, s, partials, nb, out28, (const int*)nullptr, (int*)nullptr);
 }
 void transform_f32(hipStream_t s, const float* in, int stride_f, int n, PoseF T, float* out, int out_stride_f) {

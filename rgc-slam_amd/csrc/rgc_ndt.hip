@@ -272,16 +272,17 @@ __global__ void __launch_bounds__(NDT_WAVE) k_ndt_fold(const double* __restrict_
 
 int ndt_blocks(int n) { return (n + NDT_T - 1) / NDT_T; }
 
-void ndt_voxels(hipStream_t s, const float4* P, const int* start, Grid g, const int* cell_voxel, double* vox, int* vox_cell) {
-  if (g.ncell > 0) hipLaunchKernelGGL(k_ndt_voxels, dim3((g.ncell + 255) / 256), dim3(256), 0, s, P, start, g.ncell, cell_voxel, vox, vox_cell);
+void ndt_voxels(hipStream_t s, const SortedCloud& cl, const VoxelMap& vm) {
+  const int ncell = cl.grid.ncell;
+  if (ncell > 0) hipLaunchKernelGGL(k_ndt_voxels, dim3((ncell + 255) / 256), dim3(256), 0, s, cl.P, cl.start, ncell, vm.cell_voxel, vm.vox, vm.vox_cell);
 }
 
-void ndt_terms(hipStream_t s, int d2d, int find, const float* in, int stride_f, const double* svox, int n, Pose T, Pose Tlin, Grid g, const int* cell_voxel,
-               const double* vox, const int* offs, int noff, int* corr_v, int want_H, double* partials, int* ipartials, double* out29) {
+void ndt_terms(hipStream_t s, int d2d, int find, const float* in, int stride_f, const double* svox, int n, Pose T, Pose Tlin, const Grid& g,
+               const VoxelMap& vm, const int* offs, int noff, int* corr_v, int want_H, double* partials, int* ipartials, double* out29) {
   const int nb = ndt_blocks(n);
   if (nb <= 0) return;
 #define NDT_LAUNCH(D, F) \
-  hipLaunchKernelGGL((k_ndt_terms<D, F>), dim3(nb), dim3(NDT_T), 0, s, in, stride_f, svox, n, T, Tlin, g, cell_voxel, vox, offs, noff, corr_v, want_H, partials, ipartials)
+  hipLaunchKernelGGL((k_ndt_terms<D, F>), dim3(nb), dim3(NDT_T), 0, s, in, stride_f, svox, n, T, Tlin, g, vm.cell_voxel, vm.vox, offs, noff, corr_v, want_H, partials, ipartials)
   if (d2d) { if (find) NDT_LAUNCH(true, true); else NDT_LAUNCH(true, false); }
   else     { if (find) NDT_LAUNCH(false, true); else NDT_LAUNCH(false, false); }
 #undef NDT_LAUNCH

@@ -97,10 +97,9 @@ k_rbf_cov6(const float4* __restrict__ P, const int* __restrict__ start, Grid g, 
   for (int a = 0; a < 6; a++) c6[(size_t)a * n + i] = C[a];
 }
 
-void rbf_cov6(hipStream_t s, const float4* P, const int* start, Grid g, int n, float kernel_width, float max_dist_sq, int reach, double reach_dist,
-              int method, double* c6, const int* guard) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(k_rbf_cov6, dim3((n + RBF_T - 1) / RBF_T), dim3(RBF_T), 0, s, P, start, g, n, max_dist_sq, -(double)kernel_width, reach,
+void rbf_cov6(hipStream_t s, const SortedCloud& cl, float kernel_width, float max_dist_sq, int reach, double reach_dist, int method, double* c6, const int* guard) {
+  if (cl.n <= 0) return;
+  hipLaunchKernelGGL(k_rbf_cov6, dim3((cl.n + RBF_T - 1) / RBF_T), dim3(RBF_T), 0, s, cl.P, cl.start, cl.grid, cl.n, max_dist_sq, -(double)kernel_width, reach,
                      reach_dist, method, c6, guard);
 }
 
