@@ -207,10 +207,9 @@ static int map_wide_r_of(const rgc_ctx* c, const Cloud& cl) {
 static rgck::KnnSeeds cloud_seeds(const Cloud& cl, bool is_target);
 
 // ---- one place per rule ----
-// a cloud's block of the context's small scratch (d_small / h_small): the map's at +0, the scan's at +16; [6] of it: the flags = its grid's guard
-static int small_off(bool is_target) { return is_target ? 0 : 16; }
-// ... as the cloud's kernels take it: while the cloud sits on a speculative (or hinted) grid whose guard has not been read yet
-static int* guard_of(rgc_ctx* c, const Cloud& cl, bool is_target) { return cl.spec_used ? c->d_small + small_off(is_target) + 6 : nullptr; }
+// the guard of a cloud's grid (its block of the context's small scratch, rgck::SmallWords::block) as the cloud's kernels take it: while the
+// cloud sits on a speculative (or hinted) grid whose guard has not been read yet
+static int* guard_of(rgc_ctx* c, const Cloud& cl, bool is_target) { return cl.spec_used ? &c->d_small->block(is_target)->guard : nullptr; }
 // Launch sizes from the deferred count of the previous cloud prepared here (consecutive clouds of a sequence defer about the same queries;
 // n / 64 for the first one): the waves of a cooperative search, and the waves that patch the voxels of the deferred queries
 static int coop_waves_est(const Cloud& cl) { return cl.deferred_seen >= 0 ? cl.deferred_seen + cl.deferred_seen / 4 + 32 : cl.n / 64 + 32; }
@@ -291,17 +290,17 @@ static bool prep_known_grid(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bb
 }
 // ... the measured grid: the bounding-box kernel and its round trip, and the grid the NEXT cloud will try
 static int prep_measured_grid(rgc_ctx* c, Cloud& cl, bool is_target, double res, hipStream_t s) {
-  int* dsm = c->d_small + small_off(is_target);
-  int* hsm = c->h_small + small_off(is_target);
+  rgck::SmallBlock* dsm = c->d_small->block(is_target);
+  rgck::SmallBlock* hsm = c->h_small->block(is_target);
   rgck::Grid g{};
-  rgck::bbox(s, cl.in, cl.stride_f, cl.n, res, dsm, dsm + 6, is_target ? 0 : 1);
-  HIPCHK(c, hipMemcpyAsync(hsm, dsm, 7 * sizeof(int), hipMemcpyDeviceToHost, s));
+  rgck::bbox(s, cl.in, cl.stride_f, cl.n, res, dsm->lo, &dsm->guard, is_target ? 0 : 1);
+  HIPCHK(c, hipMemcpyAsync(hsm, dsm, offsetof(rgck::SmallBlock, nvox), hipMemcpyDeviceToHost, s));  // (box and guard)
   HIPCHK(c, hipStreamSynchronize(s));
-  if (hsm[6]) return fail(c, RGC_ERR_NONFINITE, "%s cloud contains non-finite or absurd coordinates", is_target ? "target" : "source");
+  if (hsm->guard) return fail(c, RGC_ERR_NONFINITE, "%s cloud contains non-finite or absurd coordinates", is_target ? "target" : "source");
   double ncell = 1.0;
   for (int a = 0; a < 3; a++) {
-    g.minc[a] = hsm[a];
-    g.dim[a] = hsm[3 + a] - hsm[a] + 1;
+    g.minc[a] = hsm->lo[a];
+    g.dim[a] = hsm->hi[a] - hsm->lo[a] + 1;
     ncell *= (double)g.dim[a];
   }
   if (ncell > (double)c->prm.max_cells || ncell > 2.0e9)
@@ -479,7 +478,7 @@ static void prep_build_grid(rgc_ctx* c, Cloud& cl, bool is_target, hipStream_t s
   int *cell_of = cl.cell_of.as<int>(), *start = cl.start.as<int>();
   rgck::count_cells(s, cl.in, cl.stride_f, n, cl.grid, cell_of, cl.slot_of.as<int>(), cl.cnt.as<int>(), hi, guard_of(c, cl, is_target), fuse_reframe ? &cl.rf : nullptr);
   rgck::scan_cells(s, cl.cnt.as<int>(), start, cl.grid.ncell + 1, cl.block_sums.p, is_target ? cl.cell_voxel.as<int>() : nullptr,
-                   is_target ? c->d_small + 7 : nullptr, hi, is_target ? nullptr : reinterpret_cast<float*>(c->d_small + 23));
+                   is_target ? &c->d_small->map.nvox : nullptr, hi, is_target ? nullptr : &c->d_small->scan.sum_sq);
   const bool with_cache = is_target && &cl == &c->tgt && cl.cache_on;
   const rgck::KnnSeeds sd = cloud_seeds(cl, is_target);
   rgck::place(s, n, cell_of, cl.slot_of.as<int>(), start, cl.order_tmp.as<unsigned long long>(), hi, with_cache ? &sd.cache : nullptr);
@@ -500,14 +499,14 @@ static int prepare_cloud(rgc_ctx* c, Cloud& cl, bool is_target, bool force_bbox 
   if ((rc = prep_order_streams(c, is_target))) return rc;
   {
     ProfScope ps(c, RGC_K_GRID, n, s);
-    // bbox accumulators + flag; the map's copy also zeroes [7], its voxel counter ([8] ncorr stays untouched; the scan's
-    // block lives at +16 and must not touch the map's counter)
+    // the cloud's whole block: bbox accumulators + guard, and the map's voxel counter / the scan's sum of count^2, a float accumulated by
+    // the cell scan (ncorr, behind the map's block, stays untouched)
     // ... unless the previous solve's first step has already put the block back to this image on the device (reinit_small_blocks)
     if (!c->small_clean[is_target ? 0 : 1]) {
       const int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
-      const size_t init_bytes = 8 * sizeof(int);  // the scan's eighth int (d_small[23]) is its sum of count^2, a float accumulated by the cell scan
-      memcpy(c->h_small + small_off(is_target), init, init_bytes);
-      HIPCHK(c, hipMemcpyAsync(c->d_small + small_off(is_target), c->h_small + small_off(is_target), init_bytes, hipMemcpyHostToDevice, s));
+      static_assert(sizeof(init) == sizeof(rgck::SmallBlock), "a block's initial image");
+      memcpy(c->h_small->block(is_target), init, sizeof(init));
+      HIPCHK(c, hipMemcpyAsync(c->d_small->block(is_target), c->h_small->block(is_target), sizeof(init), hipMemcpyHostToDevice, s));
     }
     c->small_clean[is_target ? 0 : 1] = false;  // this preparation uses it
     // The scan's kNN grid need not be the voxel grid (only the map's doubles as the voxel map), and the exact search returns the
@@ -937,10 +936,10 @@ static int validate_clouds(rgc_ctx* c, bool whole_target = true) {
   // nobody completes any more (a target replaced while a scan is set, then read through a getter: tests/fuzz/fuzz_api.py found it).
   if ((c->tgt.ready && c->tgt.spec_used) || (c->src.ready && c->src.spec_used)) {
     HIPCHK(c, hipStreamSynchronize(c->stream2));
-    HIPCHK(c, hipMemcpyAsync(c->h_small + 6, c->d_small + 6, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_small + 22, c->d_small + 22, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_small->map.guard, &c->d_small->map.guard, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->h_small->scan.guard, &c->d_small->scan.guard, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int r = resolve_guards(c, c->tgt.spec_used ? c->h_small[6] : 0, c->src.spec_used ? c->h_small[22] : 0);
+    const int r = resolve_guards(c, c->tgt.spec_used ? c->h_small->map.guard : 0, c->src.spec_used ? c->h_small->scan.guard : 0);
     if (r < 0) return r;
   }
   if (whole_target) { int rc = complete_target(c); if (rc) return rc; }  // (lazy target: whoever comes this way reads covariances or voxels the solve may not have needed)
@@ -969,17 +968,17 @@ void unpack_system(const double sums[28], double H[36], double b[6]) {
   for (int a = 0; a < 6; a++) b[a] = sums[21 + a];
 }
 
-// the scan linearised at T against the map's voxels, on the route the scan was prepared on: the 28 sums to d_out, the count to d_small[8]
+// the scan linearised at T against the map's voxels, on the route the scan was prepared on: the 28 sums to d_out, the count to d_small->ncorr
 static void enqueue_linearize(rgc_ctx* c, const double T[16], int noff, int want_H) {
   const Cloud& src = c->src;
   double* partials = c->partials.as<double>();
   int* ipartials = c->ipartials.as<int>();
   if (src.general)
     rgck::linearize_general(c->stream, src.sorted(), src.c6.as<double>(), pose_from(T), c->tgt.grid, c->tgt.voxels(), noff, corr_of(c), want_H, partials,
-                            ipartials, c->d_out, c->d_small + 8);
+                            ipartials, c->d_out, &c->d_small->ncorr);
   else
     rgck::linearize(c->stream, src.sorted(), src.normals(), pose_from(T), c->tgt.grid, c->tgt.voxels(), noff, corr_of(c), want_H, partials, ipartials,
-                    c->d_out, c->d_small + 8);
+                    c->d_out, &c->d_small->ncorr);
 }
 // the first ndoubles of the output block, home (one synchronisation)
 static int fetch_out(rgc_ctx* c, size_t ndoubles) {
@@ -999,13 +998,13 @@ static int do_linearize(rgc_ctx* c, const double T[16], double* H, double* b, do
     enqueue_linearize(c, T, noff, want);
   }
   HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double) * rgck::kAccum, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->h_small + 8, c->d_small + 8, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&c->h_small->ncorr, &c->d_small->ncorr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
   c->corr_noff = noff;
   c->corr_n = n;
   c->corr_valid = true;
-  c->stats.n_corr = c->h_small[8];
+  c->stats.n_corr = c->h_small->ncorr;
   c->stats.n_linearize++;
   if (want) unpack_system(c->h_out, H, b);
   if (cost) *cost = c->h_out[27];
@@ -1027,7 +1026,7 @@ static int do_linearize_try(rgc_ctx* c, const double x0[16], double lambda, doub
   {
     ProfScope ps(c, RGC_K_LINEARIZE, n);
     enqueue_linearize(c, x0, noff, 1);
-    rgck::lm_try(c->stream, c->d_out, c->d_small + 8, in);
+    rgck::lm_try(c->stream, c->d_out, &c->d_small->ncorr, in);
   }
   {
     ProfScope ps(c, RGC_K_ERROR, n);
@@ -1183,9 +1182,9 @@ int rgc_create(int hip_device, const rgc_params* params, rgc_ctx** out) {
   ok = ok && hipEventCreateWithFlags(&c->src_ready, kDevEvent) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->main_mark, kDevEvent) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->tgt_ready, kDevEvent) == hipSuccess;
-  ok = ok && hipMalloc((void**)&c->d_small, 48 * sizeof(int)) == hipSuccess;
+  ok = ok && hipMalloc((void**)&c->d_small, sizeof(rgck::SmallWords)) == hipSuccess;
   ok = ok && hipMalloc((void**)&c->d_out, 64 * sizeof(double)) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&c->h_small, 48 * sizeof(int), hipHostMallocDefault) == hipSuccess;
+  ok = ok && hipHostMalloc((void**)&c->h_small, sizeof(rgck::SmallWords), hipHostMallocDefault) == hipSuccess;
   ok = ok && hipHostMalloc((void**)&c->h_out, 64 * sizeof(double), hipHostMallocDefault) == hipSuccess;
   ok = ok && hipHostMalloc((void**)&c->h_lm, sizeof(rgck::LmState), hipHostMallocDefault) == hipSuccess;
   ok = ok && hipHostMalloc((void**)&c->h_post, sizeof(rgck::LmState), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
@@ -1350,7 +1349,8 @@ int rgc_share_target(rgc_ctx* c, rgc_ctx* owner) {
   d.spec_ok = false; d.spec_used = false; d.cnt_clean = 0; d.cnt_seen = nullptr; d.lazy = 0;
   d.ready = true;
   const int small[2] = {0, o.nvox};  // this context's copy of the target's guard (clear) and voxel count, which the solve reads
-  HIPCHK(c, hipMemcpyAsync(c->d_small + 6, small, sizeof(small), hipMemcpyHostToDevice, c->stream));  // (not the blocking form: it goes through the NULL stream)
+  static_assert(offsetof(rgck::SmallBlock, nvox) == offsetof(rgck::SmallBlock, guard) + sizeof(int), "guard and nvox in one copy");
+  HIPCHK(c, hipMemcpyAsync(&c->d_small->map.guard, small, sizeof(small), hipMemcpyHostToDevice, c->stream));  // (not the blocking form: it goes through the NULL stream)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->tgt_owner = owner;
   c->tgt_owner_gen = owner->tgt_generation;
@@ -1522,12 +1522,12 @@ static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, boo
   // chained launches otherwise: the stage-by-stage profiling pass, a scan of more rows than CUs, a context without mapped host memory, and
   // RGC_LM_IMPL=chained -- and for any solve whose resident launch gave up (rgc_align_end).
   c->lm_resident = open && !staged && !c->lm_chained && post && nb_lm <= c->cu_count && nb_lm <= rgck::kLmSolveMaxGroups;
-  rgck::LmState* st = c->lm_state.as<rgck::LmState>();
+  rgck::LmArea* area = c->lm_state.as<rgck::LmArea>();
   const bool lazy = c->tgt.lazy == 2;
   rgck::LmArgs a{};
   a.src = c->src.sorted(); a.nrm = c->src.normals(); a.tgt = c->tgt.sorted(); a.vm = c->tgt.voxels();
   a.noff = noff; a.corr[0] = corr_of(c); a.corr[1] = rgck::Corr{c->corr_v2.as<int>(), c->corr_M2.as<double>()};
-  a.partials = c->partials.as<double>(); a.st = st; a.nvox = c->d_small + 7; a.segs_t = c->tgt.segs.p; a.segs_s = c->src.segs.p;
+  a.partials = c->partials.as<double>(); a.area = area; a.small = c->d_small; a.segs_t = c->tgt.segs.p; a.segs_s = c->src.segs.p;
   a.h_post = post; a.seq = seq; a.fit_partials = fit_in_steps ? c->fit_partials.as<double>() : nullptr;
   a.lazy_need = lazy ? c->tgt.need.as<const int>() : nullptr; a.lazy_stamp = c->tgt.need_stamp; a.lazy_counts = lazy ? c->tgt.segs.as<const int>() + 1 : nullptr;
   a.h_early = (fit_in_steps && post) ? c->d_early : nullptr;
@@ -1540,7 +1540,7 @@ static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, boo
   }
   auto step = [&](const rgck::LmInit* op, hipStream_t on) { rgck::lm_step(on, a, c->lm_j++, op); };
   auto score = [&]() {  // getFitnessScore at the final pose, chained blindly (on the image the last launch left)
-    rgck::fitness_lm(s, a.src, rgck::lm_image(st, c->lm_j - 1), a.tgt, c->fit_partials.as<double>(), post, c->lm_seq);
+    rgck::fitness_lm(s, a.src, rgck::lm_image(area, c->lm_j - 1), a.tgt, c->fit_partials.as<double>(), post, c->lm_seq);
   };
   hipStream_t tail = s;
   if (staged) {
@@ -1570,7 +1570,7 @@ static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, boo
   }
   // (a solve that POSTS its finished state needs no stream-ordered copy of it: the one case that reads the state otherwise -- a batch that
   // ends without a finished solve -- fetches it with a blocking copy once the stream has drained, rgc_align_end)
-  if (!post) HIPCHK(c, hipMemcpyAsync(c->h_lm, rgck::lm_image(st, c->lm_j - 1), sizeof(rgck::LmState), hipMemcpyDeviceToHost, tail));
+  if (!post) HIPCHK(c, hipMemcpyAsync(c->h_lm, rgck::lm_image(area, c->lm_j - 1), sizeof(rgck::LmState), hipMemcpyDeviceToHost, tail));
   HIPCHK(c, hipEventRecord(c->lm_tail, tail));
   c->lm_tail_stream = tail;
   return RGC_OK;
@@ -1652,7 +1652,7 @@ int rgc_align_begin(rgc_ctx* c, const float guess[16], int want_fitness) {
   const int batch = std::max(2, std::min(std::max(9, c->lm_last_outer + 6), P.max_iterations + 2));
   if (c->lm_seq >= 0x3fffffff) {  // the solve numbers start over: neither a flag of the resident solve nor its give-up word may carry an old one (rgck::k_lm_solve)
     c->lm_seq = 0;
-    HIPCHK(c, hipMemsetAsync(c->lm_state.as<char>() + 3080, 0, rgck::kLmAreaBytes - 3080, c->solve_stream));
+    HIPCHK(c, hipMemsetAsync(&c->lm_state.as<rgck::LmArea>()->give_up, 0, sizeof(rgck::LmArea) - offsetof(rgck::LmArea, give_up), c->solve_stream));
   }
   c->lm_seq++;
   if (join_late && (rc = join_source(c))) return rc;
@@ -1665,25 +1665,25 @@ int rgc_align_begin(rgc_ctx* c, const float guess[16], int want_fitness) {
   return RGC_OK;
 }
 
-int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged, int* lm_failed) {
-  if (!c) return RGC_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));  // (before the general route's score below, too)
-  if (c->gen_res.on) {  // general route: solved in rgc_align_begin
-    auto& g = c->gen_res;
-    g.on = false;
-    if (final_T) memcpy(final_T, g.T, sizeof(g.T));
-    if (final_H) memcpy(final_H, g.H, sizeof(g.H));
-    if (iterations) *iterations = g.iterations;
-    if (converged) *converged = g.converged;
-    if (lm_failed) *lm_failed = g.lm_failed;
-    if (fitness) { if (g.has_fit) *fitness = g.fitness; else return do_fitness(c, g.T, fitness); }
-    return RGC_OK;
-  }
-  if (!c->pend.active) return fail(c, RGC_ERR_INVALID, "rgc_align_end without rgc_align_begin");
-  c->pend.active = false;
+// ---- rgc_align_end, step by step ----
+struct AlignOut { float* T; double* H; double* fitness; int *iterations, *converged, *lm_failed; };  // rgc_align_end's outputs, each nullable
+
+// the general route solved in rgc_align_begin: its stored result is handed over
+static int take_general_result(rgc_ctx* c, const AlignOut& out) {
+  auto& g = c->gen_res;
+  g.on = false;
+  if (out.T) memcpy(out.T, g.T, sizeof(g.T));
+  if (out.H) memcpy(out.H, g.H, sizeof(g.H));
+  if (out.iterations) *out.iterations = g.iterations;
+  if (out.converged) *out.converged = g.converged;
+  if (out.lm_failed) *out.lm_failed = g.lm_failed;
+  if (out.fitness) { if (g.has_fit) *out.fitness = g.fitness; else return do_fitness(c, g.T, out.fitness); }
+  return RGC_OK;
+}
+
+// S <- the finished state of the pending solve, enqueueing whatever it still needs to finish
+static int lm_wait_result(rgc_ctx* c, bool want_fitness, rgck::LmState& S) {
   int rc;
-  const bool want_fitness = c->pend.want_fitness;
-  rgck::LmState& S = c->lm_res;  // (not h_lm itself: the stream's copy into it may still be in flight when a posted state is taken)
   for (int guard = 0;; guard++) {
     // The device posts a finished solve's state into mapped host memory and then the solve's number: the host spins on that word and
     // leaves as soon as it shows up -- the blind launches behind the deciding one and the stream's copy drain in the background.
@@ -1714,7 +1714,7 @@ int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fit
       const bool keep = c->lm_chained;
       c->lm_chained = true;
       // (workgroups that had reached the score before the others gave up have taken tickets nobody collected)
-      HIPCHK(c, hipMemsetAsync(c->lm_state.as<char>() + 3076, 0, 4, c->solve_stream));
+      HIPCHK(c, hipMemsetAsync(&c->lm_state.as<rgck::LmArea>()->ticket, 0, sizeof(rgck::LmArea::ticket), c->solve_stream));
       rc = lm_enqueue_batch(c, c->pend.batch, &c->pend.in, want_fitness);
       c->lm_chained = keep;
       if (rc) return rc;
@@ -1726,17 +1726,80 @@ int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fit
         // on the solve's own stream, never with the blocking hipMemcpy: that one goes through the NULL stream, whose hardware queue the
         // runtime creates at its first use -- 9 ms inside whichever frame first needed more launches than its batch held (the node's
         // "one slow frame" of rounds 3 and 4: frame 14 of the c2 stand-in)
-        HIPCHK(c, hipMemcpyAsync(c->h_lm, rgck::lm_image(c->lm_state.as<rgck::LmState>(), c->lm_j - 1), sizeof(rgck::LmState), hipMemcpyDeviceToHost,
+        HIPCHK(c, hipMemcpyAsync(c->h_lm, rgck::lm_image(c->lm_state.as<rgck::LmArea>(), c->lm_j - 1), sizeof(rgck::LmState), hipMemcpyDeviceToHost,
                                  c->lm_tail_stream));
         HIPCHK(c, hipStreamSynchronize(c->lm_tail_stream));
       }
       memcpy(&S, c->h_lm, sizeof(S));
     }
     HIPCHK(c, hipGetLastError());
-    if (S.done || guard >= 400) break;
+    if (S.done || guard >= 400) return RGC_OK;
     // a solve that is still running after six outer iterations usually runs many more (up to 25): batches of six, fewer read-backs
     if ((rc = lm_enqueue_batch(c, 6, nullptr, want_fitness))) return rc;
   }
+}
+
+// what the finished state carries home beside the pose: the valid correspondence buffer, the frame's counters, the sizes of the next launches
+static void lm_adopt_result(rgc_ctx* c, const rgck::LmState& S) {
+  const int n = c->src.n, noff = noff_of(c->prm.neighbor_method);
+  if (S.cur) { std::swap(c->corr_v, c->corr_v2); std::swap(c->corr_M, c->corr_M2); }  // corr_v / corr_M = the valid buffer
+  c->corr_noff = noff; c->corr_n = n; c->corr_valid = S.n_lin > 0;
+  c->stats.n_corr = S.ncorr; c->stats.n_linearize = S.n_lin; c->stats.n_error = S.n_err;
+  c->tgt.nvox = c->stats.n_voxels = S.nvox;
+  c->stats.deferred_target = S.def_t; c->stats.deferred_source = S.def_s;
+  c->tgt.deferred_seen = S.def_t; c->src.deferred_seen = S.def_s;
+  c->deferred_known = true;
+  if (c->tgt.lazy == 2) { c->tgt.lazy_nq_seen = S.lazy_nq; c->tgt.lazy_ncell_seen = S.lazy_ncell; }
+  // (S.src_sq == 0: this scan's figure was consumed by an earlier solve on the same clouds -- the first step hands the counter back
+  // zeroed -- and the steering it caused stands)
+  if (S.src_sq > 0.f) c->stats.source_crowding = c->src.n > 0 ? (double)S.src_sq / (double)c->src.n : 0.0;
+  c->lm_last_outer = S.outer;
+  c->stats.outer_iterations = S.failed ? S.outer + 1 : S.outer;  // iterations started, like nr_iterations_ + 1
+}
+
+static void steer_scan_cell(rgc_ctx* c, const rgck::LmState& S) {
+  // steer the next scan's cell size: halve above 500 points per own cell, double below 40 -- up to twice the voxel size, which is where a
+  // 0.2 m leaf-filtered VLP-16 sweep (the odometer's source cloud) ends up: fewer of its far-field queries go to the cooperative
+  // kernel (frame body 0.76 -> 0.73 ms); a raw VLP-16 sweep (117) stays at the voxel size (2837 scans/s against 2683 at twice that).
+  // (With four lanes per query a crowded cell is
+  // cheap and a fine grid's far field -- every sparse query deferred to the cooperative kernel -- is what costs: an HDL-64 sweep,
+  // 1270 / 380 / 107 at 1 / 0.5 / 0.25 m, is fastest at 0.5 m (c3 529 -> 594 scans/s against the former threshold of 300, which took it
+  // to 0.25 m); two fused 64-beam sweeps, 2420 / 720 / 201, still want 0.25 m (184 against 139 scans/s at 0.5 m).)
+  if (S.src_sq > 0.f && c->src_res <= 0.0 && c->src.n > 0) {
+    const double cur = c->src.grid.res, crowd = c->stats.source_crowding;
+    double next = cur;
+    if (crowd > 500.0 && cur > 0.26 * c->prm.voxel_res) next = cur * 0.5;
+    else if (crowd < 40.0 && cur < 2.0 * c->prm.voxel_res) next = std::fmin(cur * 2.0, 2.0 * c->prm.voxel_res);  // a leaf-filtered sweep: 2 x voxel size
+    c->src_res_auto = next;
+  }
+}
+
+static int lm_write_outputs(rgc_ctx* c, const rgck::LmState& S, bool want_fitness, const AlignOut& out) {
+  float fin[16];
+  for (int i = 0; i < 16; i++) fin[i] = (float)S.x0[i];  // :77
+  if (out.T) memcpy(out.T, fin, sizeof(fin));
+  if (out.H) memcpy(out.H, S.Hfin, sizeof(double) * 36);
+  if (out.iterations) *out.iterations = c->stats.outer_iterations;
+  if (out.converged) *out.converged = S.conv != 0 ? 1 : 0;
+  if (out.lm_failed) *out.lm_failed = S.failed != 0 ? 1 : 0;
+  if (out.fitness) {
+    if (want_fitness && S.has_fit) *out.fitness = S.fit_sum / (double)c->src.n;
+    else return do_fitness(c, fin, out.fitness);
+  }
+  return RGC_OK;
+}
+
+int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged, int* lm_failed) {
+  if (!c) return RGC_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));  // (before the general route's score, too)
+  const AlignOut out{final_T, final_H, fitness, iterations, converged, lm_failed};
+  if (c->gen_res.on) return take_general_result(c, out);
+  if (!c->pend.active) return fail(c, RGC_ERR_INVALID, "rgc_align_end without rgc_align_begin");
+  c->pend.active = false;
+  int rc;
+  const bool want_fitness = c->pend.want_fitness;
+  rgck::LmState& S = c->lm_res;  // (not h_lm itself: the stream's copy into it may still be in flight when a posted state is taken)
+  if ((rc = lm_wait_result(c, want_fitness, S))) return rc;
   c->src_pending = false;  // the solve came after the scan's preparation and has finished (its spare launches may still drain: lm_tail)
   c->main_has_target_prep = false;  // (the solve came after the map's preparation)
   c->small_clean[0] = c->small_clean[1] = true;  // the solve re-initialised both blocks after capturing them (chained: its first step; resident: the workgroup that finished it)
@@ -1757,47 +1820,9 @@ int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fit
     if ((rc = complete_target(c))) return rc;
     return solve_again();
   }
-  const int n = c->src.n, noff = noff_of(c->prm.neighbor_method);
-  if (S.cur) { std::swap(c->corr_v, c->corr_v2); std::swap(c->corr_M, c->corr_M2); }  // corr_v / corr_M = the valid buffer
-  c->corr_noff = noff; c->corr_n = n; c->corr_valid = S.n_lin > 0;
-  c->stats.n_corr = S.ncorr; c->stats.n_linearize = S.n_lin; c->stats.n_error = S.n_err;
-  c->tgt.nvox = c->stats.n_voxels = S.nvox;
-  c->stats.deferred_target = S.def_t; c->stats.deferred_source = S.def_s;
-  c->tgt.deferred_seen = S.def_t; c->src.deferred_seen = S.def_s;
-  if (c->tgt.lazy == 2) { c->tgt.lazy_nq_seen = S.lazy_nq; c->tgt.lazy_ncell_seen = S.lazy_ncell; }
-  // (S.src_sq == 0: this scan's figure was consumed by an earlier solve on the same clouds -- the first step hands the counter back
-  // zeroed -- and the steering it caused stands)
-  if (S.src_sq > 0.f) c->stats.source_crowding = c->src.n > 0 ? (double)S.src_sq / (double)c->src.n : 0.0;
-  // steer the next scan's cell size: halve above 500 points per own cell, double below 40 -- up to twice the voxel size, which is where a
-  // 0.2 m leaf-filtered VLP-16 sweep (the odometer's source cloud) ends up: fewer of its far-field queries go to the cooperative
-  // kernel (frame body 0.76 -> 0.73 ms); a raw VLP-16 sweep (117) stays at the voxel size (2837 scans/s against 2683 at twice that).
-  // (With four lanes per query a crowded cell is
-  // cheap and a fine grid's far field -- every sparse query deferred to the cooperative kernel -- is what costs: an HDL-64 sweep,
-  // 1270 / 380 / 107 at 1 / 0.5 / 0.25 m, is fastest at 0.5 m (c3 529 -> 594 scans/s against the former threshold of 300, which took it
-  // to 0.25 m); two fused 64-beam sweeps, 2420 / 720 / 201, still want 0.25 m (184 against 139 scans/s at 0.5 m).)
-  if (S.src_sq > 0.f && c->src_res <= 0.0 && c->src.n > 0) {
-    const double cur = c->src.grid.res, crowd = c->stats.source_crowding;
-    double next = cur;
-    if (crowd > 500.0 && cur > 0.26 * c->prm.voxel_res) next = cur * 0.5;
-    else if (crowd < 40.0 && cur < 2.0 * c->prm.voxel_res) next = std::fmin(cur * 2.0, 2.0 * c->prm.voxel_res);  // a leaf-filtered sweep: 2 x voxel size
-    c->src_res_auto = next;
-  }
-  c->deferred_known = true;
-  const int iters = S.failed ? S.outer + 1 : S.outer;  // iterations started, like nr_iterations_ + 1
-  c->lm_last_outer = S.outer;
-  c->stats.outer_iterations = iters;
-  float fin[16];
-  for (int i = 0; i < 16; i++) fin[i] = (float)S.x0[i];  // :77
-  if (final_T) memcpy(final_T, fin, sizeof(fin));
-  if (final_H) memcpy(final_H, S.Hfin, sizeof(double) * 36);
-  if (iterations) *iterations = iters;
-  if (converged) *converged = S.conv != 0 ? 1 : 0;
-  if (lm_failed) *lm_failed = S.failed != 0 ? 1 : 0;
-  if (fitness) {
-    if (want_fitness && S.has_fit) *fitness = S.fit_sum / (double)n;
-    else if ((rc = do_fitness(c, fin, fitness))) return rc;
-  }
-  return RGC_OK;
+  lm_adopt_result(c, S);
+  steer_scan_cell(c, S);
+  return lm_write_outputs(c, S, want_fitness, out);
 }
 
 // lsq_registration_impl.hpp:53-79 (computeTransformation) + :125-172 (step_lm); SURVEY A.5
@@ -2052,9 +2077,9 @@ int rgc_swap_source_and_target(rgc_ctx* c) {
 
 static int fetch_nvox(rgc_ctx* c) {
   if (c->tgt.nvox >= 0) return RGC_OK;
-  HIPCHK(c, hipMemcpyAsync(c->h_small + 7, c->d_small + 7, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&c->h_small->map.nvox, &c->d_small->map.nvox, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->tgt.nvox = c->h_small[7];
+  c->tgt.nvox = c->h_small->map.nvox;
   c->stats.n_voxels = c->tgt.nvox;
   return RGC_OK;
 }

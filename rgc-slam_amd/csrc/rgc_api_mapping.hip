@@ -301,14 +301,15 @@ int rgc_mapreg_optimize(rgc_ctx* c, const float* corner_cur, int n_ccur, const f
                                   m.P.as<const float4>(), m.start.as<const int>(), m.grid, c->mr_fac[s].as<double>(), dcnt + s};
     }
     rgck::mapreg_associate(c->stream, sets, 4);  // the four loops of :1092-1282 side by side
-    HIPCHK(c, hipMemcpyAsync(c->h_small + 40, dcnt, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_small->mapreg.n, dcnt, sizeof(rgck::MapregCounts::n), hipMemcpyDeviceToHost, c->stream));
     // ceres::Solve restated: trust-region LM, <= 6 iterations (:1333-1341), Ceres 1.14 defaults: initial radius 1e4, damping diag(H)/radius clamped to [1e-6, 1e32], step accepted above a relative decrease of 1e-3
     double radius = 1e4, decrease_factor = 2.0;
     MapregSystem S, Sn;
     if ((rc = mapreg_eval(c, nfeat, poses, true, ground, imu, &S))) return rc;
     if (report) {
-      report[iter].n_edge_cur = c->h_small[40]; report[iter].n_plane_cur = c->h_small[41];
-      report[iter].n_edge_last = c->h_small[42]; report[iter].n_plane_last = c->h_small[43];
+      const int* nf = c->h_small->mapreg.n;
+      report[iter].n_edge_cur = nf[0]; report[iter].n_plane_cur = nf[1];
+      report[iter].n_edge_last = nf[2]; report[iter].n_plane_last = nf[3];
     }
     int it = 0, n_success = 0;
     const double initial_cost = S.cost;
@@ -399,7 +400,7 @@ int rgc_mapreg_linearize(rgc_ctx* c, const float* corner_cur, int n_ccur, const 
                                 m.P.as<const float4>(), m.start.as<const int>(), m.grid, c->mr_fac[s].as<double>(), dcnt + s};
   }
   rgck::mapreg_associate(c->stream, sets, 4);
-  HIPCHK(c, hipMemcpyAsync(c->h_small + 40, dcnt, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_small->mapreg.n, dcnt, sizeof(rgck::MapregCounts::n), hipMemcpyDeviceToHost, c->stream));
   for (int s = 0; s < 4 && factors8; s++)
     if (factors8[s] && nfeat[s] > 0)
       HIPCHK(c, hipMemcpyAsync(factors8[s], c->mr_fac[s].p, sizeof(double) * 8 * (size_t)nfeat[s], hipMemcpyDeviceToHost, c->stream));
@@ -408,7 +409,7 @@ int rgc_mapreg_linearize(rgc_ctx* c, const float* corner_cur, int n_ccur, const 
   memcpy(H, S.H, sizeof(S.H));
   memcpy(g, S.g, sizeof(S.g));
   *cost = S.cost;
-  for (int s = 0; s < 4; s++) n_factors[s] = c->h_small[40 + s];
+  for (int s = 0; s < 4; s++) n_factors[s] = c->h_small->mapreg.n[s];
   return RGC_OK;
 }
 

@@ -113,16 +113,16 @@ int rgc_set_target_reframed(rgc_ctx* c, const float* d_xyzi, int n, int stride_b
     // corners through q * p + t in fp64, a millimetre added for the fp32 rounding of the stored points
     const rgc_ctx::BoxHint* hin = find_hint(c, xyzi, n);
     if (!hin) {
-      int* dsm = c->d_small + 32;
-      int* hsm = c->h_small + 32;
+      rgck::SmallBlock* dsm = &c->d_small->hint;
+      rgck::SmallBlock* hsm = &c->h_small->hint;
       const int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
       memcpy(hsm, init, sizeof(init));
       HIPCHK(c, hipMemcpyAsync(dsm, hsm, sizeof(init), hipMemcpyHostToDevice, c->stream));
-      rgck::bbox(c->stream, d_in, stride_bytes / 4, n, 1.0, dsm, dsm + 6);
-      HIPCHK(c, hipMemcpyAsync(hsm, dsm, 7 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      rgck::bbox(c->stream, d_in, stride_bytes / 4, n, 1.0, dsm->lo, &dsm->guard);
+      HIPCHK(c, hipMemcpyAsync(hsm, dsm, offsetof(rgck::SmallBlock, nvox), hipMemcpyDeviceToHost, c->stream));  // (box and guard)
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      if (!hsm[6]) {
-        const double lo[3] = {hsm[0] + 0.5, hsm[1] + 0.5, hsm[2] + 0.5}, hi[3] = {hsm[3] + 1.5, hsm[4] + 1.5, hsm[5] + 1.5};
+      if (!hsm->guard) {
+        const double lo[3] = {hsm->lo[0] + 0.5, hsm->lo[1] + 0.5, hsm->lo[2] + 0.5}, hi[3] = {hsm->hi[0] + 1.5, hsm->hi[1] + 1.5, hsm->hi[2] + 1.5};
         put_hint(c, xyzi, n, lo, hi);
         hin = find_hint(c, xyzi, n);
       }
@@ -258,8 +258,8 @@ int rgc_align_end_reframe(rgc_ctx* c, rgc_ctx* next, double Tw[16], const float*
 static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, float inv, const rgck::LeafGrid& g, int edge, bool dense, float* d_out,
                           int* flags, int* n_out, rgc_vg_route* rt, int* h_result = nullptr) {
   hipStream_t s = c->stream;
-  int* dsm = c->d_small + 24;
-  int* hsm = c->h_small + 24;
+  int* const d_res = c->d_small->leaf_rows.res;        // rgck::vg_rows' res[3]; res[1], the live flag word, is the block's guard
+  const int* const h_res = c->h_small->leaf_rows.res;
   Cloud& cl = c->aux;
   int rc;
   // the sort's buckets: leaves for a dense cloud, whole grid rows for a sweep, and for a LARGE cloud in a box too big for leaf buckets
@@ -290,26 +290,26 @@ static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, fl
     HIPCHK(c, hipMemsetAsync(cl.cnt.p, 0, fill, s));
   }
   cl.cnt_clean = std::max(cl.cnt_clean, nr1);  // (what lies beyond this call's rows was not touched: the scan's and the map's filter take turns)
-  if (!c->vg_flags_clean) HIPCHK(c, hipMemsetAsync(dsm + 6, 0, sizeof(int), s));
+  if (!c->vg_flags_clean) HIPCHK(c, hipMemsetAsync(&c->d_small->leaf.guard, 0, sizeof(int), s));
   c->vg_flags_clean = false;
   const bool packed = rgck::vg_rows(s, d_in, stride_f, n, inv, g, edge, seg_shift, cl.cell_of.as<int>(), cl.slot_of.as<int>(), c->vg_pos.as<int>(), cl.cnt.as<int>(),
                                     cl.start.as<int>(), cl.block_sums.p, c->vg_tmp.as<unsigned long long>(), c->vg_order.as<int>(), c->vg_leaf.as<unsigned long long>(),
-                                    (int*)(cl.block_sums.as<char>() + row_bs), d_out, dsm + 5);
+                                    (int*)(cl.block_sums.as<char>() + row_bs), d_out, d_res);
   rt->chain = 1; rt->leaf_buckets = dense ? 1 : 0; rt->seg_shift = seg_shift; rt->nseg = rgck::vg_segments(g, seg_shift); rt->packed = packed ? 1 : 0;
   rt->edge = edge; rt->flags = 0;
   for (int a = 0; a < 3; a++) { rt->minb[a] = g.minb[a]; rt->div[a] = g.div[a]; }
   if (h_result) {  // (the finished chain leaves the flag word zeroed: the next chain on this stream finds it so)
-    HIPCHK(c, hipMemcpyAsync(h_result, dsm + 5, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(h_result, d_res, sizeof(rgck::LeafRows::res), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipEventRecord(c->vg_done, s));
     c->vg_flags_clean = true;
     return RGC_OK;
   }
-  HIPCHK(c, hipMemcpyAsync(hsm + 5, dsm + 5, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(c->h_small->leaf_rows.res, d_res, sizeof(rgck::LeafRows::res), hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   c->vg_flags_clean = true;
-  *flags = hsm[5];
-  *n_out = hsm[7];
-  rt->flags = hsm[5];
+  *flags = h_res[0];
+  *n_out = h_res[2];
+  rt->flags = h_res[0];
   return RGC_OK;
 }
 static bool vg_rows_fit(const rgck::LeafGrid& g, int n) {  // sparse enough for the sort over rows (else: over the leaves)
@@ -325,8 +325,8 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
   if (rc) return rc;
   const int stride_f = stride_bytes / 4;
   const float inv = 1.0f / leaf;  // inverse_leaf_size_
-  int* dsm = c->d_small + 24;
-  int* hsm = c->h_small + 24;
+  rgck::SmallBlock* dsm = &c->d_small->leaf;
+  rgck::SmallBlock* hsm = &c->h_small->leaf;
   float* d_out = out_xyzi;
   if (!on_device) {
     if ((rc = ensure(c, c->pre_out, sizeof(float) * 4 * (size_t)n))) return rc;
@@ -368,14 +368,14 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
     memcpy(hsm, init, sizeof(init));
     c->vg_flags_clean = false;
     HIPCHK(c, hipMemcpyAsync(dsm, hsm, sizeof(init), hipMemcpyHostToDevice, s));
-    rgck::vg_bbox(s, d_in, stride_f, n, inv, dsm, dsm + 6);
-    HIPCHK(c, hipMemcpyAsync(hsm, dsm, 7 * sizeof(int), hipMemcpyDeviceToHost, s));
+    rgck::vg_bbox(s, d_in, stride_f, n, inv, dsm->lo, &dsm->guard);
+    HIPCHK(c, hipMemcpyAsync(hsm, dsm, offsetof(rgck::SmallBlock, nvox), hipMemcpyDeviceToHost, s));  // (box and guard)
     HIPCHK(c, hipStreamSynchronize(s));
-    if (hsm[6]) return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)");
+    if (hsm->guard) return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)");
     c->vg_flags_clean = true;
     rgck::LeafGrid g{};
     double ncell = 1.0;
-    for (int a = 0; a < 3; a++) { g.minb[a] = hsm[a]; g.div[a] = hsm[3 + a] - hsm[a] + 1; ncell *= (double)g.div[a]; }
+    for (int a = 0; a < 3; a++) { g.minb[a] = hsm->lo[a]; g.div[a] = hsm->hi[a] - hsm->lo[a] + 1; ncell *= (double)g.div[a]; }
     for (int a = 0; a < 3; a++) { rt.minb[a] = g.minb[a]; rt.div[a] = g.div[a]; }
     {  // keep the measured box for the next cloud of this leaf size
       if (!box) { box = &c->vg_box[c->vg_box_next]; c->vg_box_next = (c->vg_box_next + 1) % 4; box->leaf = leaf; }
@@ -583,8 +583,9 @@ static int frontend_impl(rgc_ctx* c, const float* xyzi, int n, int stride_bytes,
   float* const d_flat = d_sharp + 5 * (size_t)fcap;
   float* const d_inten = d_flat + 5 * (size_t)fcap;
   const int init16[16] = {0, 0, 0, 0, 0, 0, 0, 0, INT_MAX, -1, INT_MAX, 0, 0, 0, 0, 0};  // flags (zero) + the filter's state
-  memcpy(c->h_small + 32, init16, sizeof(init16));
-  HIPCHK(c, hipMemcpyAsync(d_flags, c->h_small + 32, sizeof(init16), hipMemcpyHostToDevice, s));
+  static_assert(sizeof(init16) == sizeof(rgck::SmallWords::fe), "the front-end's staged words");
+  memcpy(c->h_small->fe, init16, sizeof(init16));
+  HIPCHK(c, hipMemcpyAsync(d_flags, c->h_small->fe, sizeof(init16), hipMemcpyHostToDevice, s));
   rgck::FeParams fp{NS, prm->min_range, prm->max_range};
   rgck::fe_filter(s, d_in, stride_f, n, fp, FE(RING, int), d_st, FE(RANK, int), FE(HIST, int));
   rgck::fe_half(s, d_in, stride_f, n, FE(RING, int), d_st);

@@ -170,12 +170,12 @@ struct rgc_ctx {
   int corr_noff = 0, corr_n = 0;
   bool corr_valid = false;
   // small device scratch + pinned host mirrors
-  int* d_small = nullptr;     // [0..5] target bbox, [6] flags, [7] nvox, [8] ncorr, [16..22] source bbox + flags
+  rgck::SmallWords* d_small = nullptr;  // the map's and the scan's blocks, ncorr, the leaf filter's block, the front-end's words
   double* d_out = nullptr;    // 28 doubles
-  int* h_small = nullptr;     // pinned, same layout
+  rgck::SmallWords* h_small = nullptr;  // pinned, same layout
   double* h_out = nullptr;    // pinned
   DevBuf scratch;             // getters
-  DevBuf lm_state;            // device-chained LM state (rgck::LmState)
+  DevBuf lm_state;            // the LM area (rgck::LmArea): the solve's two state images and the loose words behind them
   // f1: mapping-node feature registration (corner / surf feature maps: grid only, 1.5 m cells)
   Cloud mr_map[2];
   DevBuf mr_feat[4], mr_fac[4], mr_partials, mr_small;
@@ -198,7 +198,7 @@ struct rgc_ctx {
   struct { bool active = false; bool want_fitness = false; float guess[16]; rgck::LmInit in; int batch = 0; } pend;  // rgc_align_begin .. rgc_align_end (in, batch: what a chained solve of the same problem opens with)
   struct { bool on = false; int rc = 0; float T[16]; double H[36]; double fitness = 0; int iterations = 0, converged = 0, lm_failed = 0; bool has_fit = false; } gen_res;  // general route: rgc_align_begin solves at once, rgc_align_end hands this over
   int lm_last_outer = 0;      // outer iterations of the previous solve: sizes the next blind batch
-  bool small_clean[2] = {false, false};  // d_small block of the map / the scan holds its initial image (the last solve's first step restored it)
+  bool small_clean[2] = {false, false};  // d_small->map / d_small->scan holds its initial image (the last solve's first step restored it)
   hipStream_t solve_stream = nullptr;  // where the pending solve was enqueued (rgc_align_begin)
   bool solve_behind_map = RGC_SOLVE_BEHIND_MAP != 0;  // (build flag) 0: the solve always on the scan's (high-priority) stream, as in round 2
   bool lm_chained = false;    // RGC_LM_IMPL=chained: the solve as a chain of step launches (k_lm_step), never as one resident launch (k_lm_solve)
@@ -241,7 +241,7 @@ struct rgc_ctx {
   // miss when the re-framed map's box swings with the vehicle's yaw.  k_count's guard still checks it.
   struct BoxHint { const void* p = nullptr; int n = 0; double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}; double reach_xy = 0, reach_z = 0; } box_hint[4];
   int box_hint_next = 0;
-  bool vg_flags_clean = false;  // d_small[24 + 6] is known to be zero (a finished rows chain leaves it so)
+  bool vg_flags_clean = false;  // d_small->leaf.guard is known to be zero (a finished rows chain leaves it so)
   // rgc_voxelgrid_begin / _end: one filter of a device cloud in flight (enqueued on its kept box, result not yet looked at)
   struct VgPending { bool active = false, ready = false; const float* d_in = nullptr; int n = 0, stride_bytes = 0; float leaf = 0.f; float* d_out = nullptr;
                      rgck::LeafGrid g{};  // the leaf grid the pending filter was enqueued on
@@ -250,7 +250,7 @@ struct rgc_ctx {
                      } vg_pend;
   rgc_vg_route vg_route{};  // the last finished leaf filter (rgc_voxelgrid_route)
   hipEvent_t vg_done = nullptr;
-  int* h_vg = nullptr;  // pinned: the pending filter's three result ints (h_small's words are all taken: the front-end stages 16 ints at +32)
+  int* h_vg = nullptr;  // pinned: the pending filter's three result ints (h_small's words are all taken: the front-end stages 16 ints in SmallWords::fe)
   DevBuf fe[34];              // front-end buffers
   unsigned char* h_stage = nullptr;  // pinned staging of the front-end's small read-backs and feature clouds (a copy into pageable
   size_t h_stage_cap = 0;            // memory is staged by the runtime anyway, one blocking hop per call)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 
 namespace rgck {
 
@@ -86,7 +87,7 @@ struct LmState {  // device-resident state of LsqRegistration::computeTransforma
   int phase, done, conv, failed, outer, inner, n_lin, n_err, ncorr, ticketA, ticketB, max_outer, max_inner, has_fit;
   double fit_sum;                // sum of squared NN distances at the final pose (k_fitness_lm)
   int nvox, def_t, def_s, pad;   // frame counters carried home with the state; pad = grid guards, map | scan << 8
-  int gen, cmd, mode, cur;       // step kernels: mode, valid correspondence buffer; gen: the posted solve's number (host image); cmd, ticketA: unused
+  int gen, cmd, mode, cur;       // step kernels: mode, valid correspondence buffer; gen: the posted solve's number (host image); cmd: -1 in image 0 = a resident solve gave up (lm_solve_hand_over), else 0; ticketA: unused
   float src_sq; int pad2;        // sum over the scan's grid cells of count^2 (how crowded its cells are; steers the scan's cell size); pad2: the lazy target's miss flag
   int lazy_nq, lazy_ncell;       // lazy target: listed queries / cells of this frame (size the next frame's launches)
 };
@@ -95,6 +96,52 @@ struct LmInit { double x0[16], rot_eps, trans_eps, init_factor; int max_outer, m
 // needs only the pose to go on (the next frame's target of a dependent sequence, rgc_align_end_reframe) starts ~25 us earlier; pad / pad2:
 // the grid guards and the lazy target's miss flag as the finished state will carry them; gen: the solve's number, written last
 struct LmEarly { double x0[16]; int pad, pad2, outer, gen; };
+// The LM area: one per context, zeroed once (rgc_align_begin).  Launch j of a chained solve reads image[(j - 1) & 1] and leaves image[j & 1];
+// the resident solve leaves image[0].  Behind the images, the words that belong to neither:
+//   miss     the lazy target's miss flag ("a look-up hit an occupied voxel outside the part that was built"), set by any workgroup of any
+//            launch of a solve, taken into the finished state (pad2) and cleared by whoever finishes it
+//   ticket   of the score's fold (the one launch of a solve whose workgroups hand rows to each other)
+//   give_up  the resident solve's: the number of the solve a workgroup gave up on (a wait ran out, or RGC_LM_GIVE_UP_AT)
+//   flags    the resident solve's, one per workgroup, {solve number, try number}: written by that workgroup alone
+constexpr int kLmSolveMaxGroups = 512;
+struct LmArea {
+  LmState image[2];
+  char pad0[3 * 1024 - 2 * sizeof(LmState)];  // the loose words open the area's fourth KiB ...
+  int miss, ticket;
+  unsigned give_up;
+  char pad1[1024 - 3 * sizeof(int)];          // ... and the flags its second half
+  unsigned long long flags[kLmSolveMaxGroups];
+};
+static_assert(offsetof(LmArea, image) == 0 && offsetof(LmArea, image[1]) == sizeof(LmState), "the two state images lead the area");
+static_assert(offsetof(LmArea, miss) == 3072 && offsetof(LmArea, ticket) == 3076 && offsetof(LmArea, give_up) == 3080, "the loose words of the LM area");
+static_assert(offsetof(LmArea, flags) == 4096, "a flag per workgroup of the resident solve");
+constexpr int kLmAreaBytes = sizeof(LmArea);
+static_assert(kLmAreaBytes == 8192, "the LM area");
+// The context's small scratch (rgc_ctx::d_small, and h_small, its pinned mirror of the same layout): 48 ints.
+struct SmallBlock {  // what measures or guards one cloud's grid (k_bbox, k_count): the box's accumulators and the flag word
+  int lo[3], hi[3];
+  int guard;         // != 0: non-finite points (k_bbox) / the cloud left its speculative grid (k_count)
+  union { int nvox; float sum_sq; };  // the map: its voxel count (the cell scan); the scan: the sum over its cells of count^2
+};
+struct LeafRows { int box5[5]; int res[3]; };        // the leaf filter's rows chain (rgck::vg_rows) on the leaf block: res[1] is the block's guard
+struct MapregCounts { int staged8[8]; int n[4]; };   // the mapping registration's factor counts (host mirror only) on the front-end's words
+struct SmallWords {
+  SmallBlock map;    // [0..7]
+  int ncorr;         // [8] correspondences of the last linearize launch
+  int unused[7];
+  SmallBlock scan;   // [16..23]
+  union { SmallBlock leaf; LeafRows leaf_rows; };  // [24..31] the leaf filter: its bounding-box pass, then its rows chain
+  // [32..47] the front-end stages 16 ints here (host mirror, copied to its own flag block); the box of a map about to be re-framed is
+  // measured here (rgc_set_target_reframed); the mapping registration reads its four counts back into host words 40..43.  All three are
+  // enqueued on the context's MAIN stream, and each call waits for that stream before it reads the host words: the stream orders them.
+  union { int fe[16]; SmallBlock hint; MapregCounts mapreg; };
+  __host__ __device__ SmallBlock* block(bool is_target) { return is_target ? &map : &scan; }
+};
+static_assert(offsetof(SmallWords, map.guard) == 6 * 4 && offsetof(SmallWords, map.nvox) == 7 * 4 && offsetof(SmallWords, ncorr) == 8 * 4, "the map's block");
+static_assert(offsetof(SmallWords, scan) == 16 * 4 && offsetof(SmallWords, scan.guard) == 22 * 4 && offsetof(SmallWords, scan.sum_sq) == 23 * 4, "the scan's block");
+static_assert(offsetof(SmallWords, leaf) == 24 * 4 && offsetof(SmallWords, leaf_rows.res) == 29 * 4 && offsetof(SmallWords, leaf.guard) == 30 * 4, "the leaf filter's block");
+static_assert(offsetof(SmallWords, fe) == 32 * 4 && offsetof(SmallWords, hint) == 32 * 4 && offsetof(SmallWords, mapreg.n) == 40 * 4, "the front-end's words");
+static_assert(sizeof(SmallBlock) == 8 * 4 && sizeof(SmallWords) == 48 * 4, "48 ints");
 struct FeParams { int n_scans; double min_range, max_range; };
 struct LeafGrid { int minb[3]; int div[3]; };  // pcl::VoxelGrid leaf grid
 
@@ -202,16 +249,15 @@ void sort6(hipStream_t s, const double* in9, const float4* P, int n, double* c6)
 void compute_error(hipStream_t s, const float4* P, int n, Pose T, const double* vox, int noff, Corr corr, double* partials, double* out1);
 void lm_try(hipStream_t s, double* out, const int* ncorr, LmIn in);
 void compute_error_dev(hipStream_t s, const float4* P, int n, const double* Tdev, const double* vox, int noff, Corr corr, double* partials, double* out1);
-// What a solve on the device works on, filled once per solve (rgcapi: lm_enqueue_batch).  st: the kLmAreaBytes LM area, zeroed once -- two
-// state images and the loose words behind them.  partials: 2 * linearize_blocks(src.n) rows of kAccum + 2 doubles (the chained launches
+// What a solve on the device works on, filled once per solve (rgcapi: lm_enqueue_batch).  area: the LM area, zeroed once.  partials: 2 * linearize_blocks(src.n) rows of kAccum + 2 doubles (the chained launches
 // alternate between the halves).  corr: the two correspondence buffers, the finished state's `cur` the valid one.
 struct LmArgs {
   SortedCloud src; Normals nrm;  // the scan
   SortedCloud tgt; VoxelMap vm;  // the map: its grid and voxels; its sorted points for the score
   int noff;
   Corr corr[2];
-  double* partials; LmState* st;
-  const int* nvox; const void* segs_t; const void* segs_s;  // the frame's counters, carried home with the state: the map's voxel count, the clouds' deferred buffers
+  double* partials; LmArea* area;
+  SmallWords* small; const void* segs_t; const void* segs_s;  // the frame's counters, carried home with the state: the small scratch (nullable), the clouds' deferred buffers
   LmState* h_post; int seq;      // mapped host memory (nullable): a finished state is posted there, then seq in its `gen`; seq > 0: post when done; < 0: when done AND scored
   double* fit_partials;          // non-null: the score is chained to the solve -- the launch whose decision ends it scores the final pose (as does a launch on a finished solve without a score)
   // lazy target: the target is built for the cells stamped lazy_stamp in lazy_need[] only -- a look-up of any other occupied voxel
@@ -220,13 +266,12 @@ struct LmArgs {
   LmEarly* h_early;              // mapped host memory (nullable): the deciding launch posts the final pose there before it scores it
 };
 // launch number j of a solve of the device-chained LM (k_lm_step; 0 opens the solve and takes *open) reads image (j - 1) & 1 and leaves image j & 1
-inline LmState* lm_image(LmState* st, int j_last) { return st + (j_last & 1); }
+inline LmState* lm_image(LmArea* area, int j_last) { return &area->image[j_last & 1]; }
 void lm_step(hipStream_t s, const LmArgs& a, int j, const LmInit* open);
-// The whole solve in ONE resident launch (see k_lm_solve); the finished state is left in image 0 (lm_image(st, 0)).  The caller keeps
+// The whole solve in ONE resident launch (see k_lm_solve); the finished state is left in image 0.  The caller keeps
 // linearize_blocks(src.n) <= min(the device's CU count, kLmSolveMaxGroups) -- all of them resident at once -- and finds a solve that gave up
 // (a bounded wait ran out; give_up_at >= 0: workgroup 0 at that try, without waiting) as a stream that drained with nothing posted.
 // seq != 0 always: its magnitude tags the hand-over's words.
-constexpr int kLmAreaBytes = 8192, kLmSolveMaxGroups = 512;
 // The longest a workgroup waits for the others' rows, in ticks of the 100 MHz wall clock: 2 ms.  The workgroups of a solve are placed as
 // CU slots free up, so a wait can last as long as the longest kernel that may hold the slots: the map's kNN launch of a c-main frame, ~165 us.
 // Twelve times that, and still a bound on what a lost frame costs (the chained solve that follows takes ~0.15 ms).

@@ -3172,23 +3172,22 @@ void lab_lm_ts(unsigned long long* out, hipStream_t s) {
 // The frame's small counters have been captured into the LM state: put both clouds' blocks of d_small back to their initial image
 // (bounding-box accumulators, guard, the scan's sum of count^2), so that the NEXT preparation of either cloud needs no 32-byte
 // H2D copy in front of its first kernel (3.5 us of copy kernel + 4 us of gap at the head of each preparation chain).  The map's voxel
-// count (nvox[0]) and the correspondence count behind it stay: a resident target is solved against again.
-__device__ __forceinline__ void reinit_small_blocks(const int* nvox) {
-  int* t = const_cast<int*>(nvox) - 7;  // d_small: [0..5] map bbox, [6] map guard, [7] nvox; [16..21] scan bbox, [22] scan guard, [23] scan sum count^2
+// count (map.nvox) and the correspondence count behind it stay: a resident target is solved against again.
+__device__ __forceinline__ void reinit_small_blocks(SmallWords* small) {
 #pragma unroll
   for (int b = 0; b < 2; b++) {
-    int* m = t + 16 * b;
-    m[0] = m[1] = m[2] = INT_MAX;
-    m[3] = m[4] = m[5] = INT_MIN;
-    m[6] = 0;
+    SmallBlock* m = small->block(b == 0);
+    m->lo[0] = m->lo[1] = m->lo[2] = INT_MAX;
+    m->hi[0] = m->hi[1] = m->hi[2] = INT_MIN;
+    m->guard = 0;
   }
-  t[23] = 0;
+  small->scan.sum_sq = 0.f;
 }
 
-// The fresh state of a solve (:53-63) plus the frame's counters, on a zeroed image (k_lm_step's opening launch, lane 0 of workgroup 0).
+// The fresh state of a solve (:53-63) plus the frame's counters (small, nullable), on a zeroed image (lane 0 of a workgroup).
 // reinit: put the counters' blocks back at once (k_lm_solve does it itself when the solve has finished)
-__device__ __forceinline__ void lm_state_open(LmState& ls, const LmInit& in, const int* nvox, const int* __restrict__ def_t,
-                                              const int* __restrict__ def_s, bool reinit = true) {
+__device__ __forceinline__ void lm_state_open(LmState& ls, const LmInit& in, SmallWords* small, const int* __restrict__ def_t,
+                                              const int* __restrict__ def_s, bool reinit) {
 #pragma unroll
   for (int a = 0; a < 16; a++) ls.x0[a] = in.x0[a];
   ls.lambda = -1.0;  // :56
@@ -3200,12 +3199,12 @@ __device__ __forceinline__ void lm_state_open(LmState& ls, const LmInit& in, con
   ls.init_factor = in.init_factor;
   ls.max_outer = in.max_outer;
   ls.max_inner = in.max_inner;
-  ls.nvox = nvox ? *nvox : 0;
-  ls.pad = nvox ? (nvox[-1] | (nvox[15] << 8)) : 0;  // grid guards of map and scan (d_small[6], [22])
+  ls.nvox = small ? small->map.nvox : 0;
+  ls.pad = small ? (small->map.guard | (small->scan.guard << 8)) : 0;  // grid guards of map and scan
   ls.def_t = def_t ? *def_t : 0;
   ls.def_s = def_s ? *def_s : 0;
-  ls.src_sq = nvox ? __int_as_float(nvox[16]) : 0.f;  // d_small[23]
-  if (nvox && reinit) reinit_small_blocks(nvox);
+  ls.src_sq = small ? small->scan.sum_sq : 0.f;
+  if (small && reinit) reinit_small_blocks(small);
 }
 
 // The decision the sums of one launch call for, taken by lane 0 of a workgroup on its LDS copy `ls` of the state the launch ran from:
@@ -3359,20 +3358,6 @@ __device__ __forceinline__ void step_fitness_rows(const float4* __restrict__ SP,
   if (((int)threadIdx.x & (WAVE - 1)) == 0) __hip_atomic_store(&fa.partials[w], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The words of the LM area that are NOT part of either state image (rgc_align_begin, rgc_api.hip, allocates 4096 bytes and zeroes them once):
-//   +3072  the lazy target's miss flag ("a look-up hit an occupied voxel outside the part that was built"), set by any workgroup of any
-//          launch of a solve, taken into the finished state (pad2) and cleared by whoever finishes it
-//   +3076  the ticket of the score's fold (the one launch of a solve whose workgroups hand rows to each other)
-static_assert(2 * sizeof(LmState) <= 3072, "two state images in front of the area's loose words");
-__device__ __forceinline__ int* lm_area_miss(LmState* st) { return reinterpret_cast<int*>(reinterpret_cast<char*>(st) + 3072); }
-__device__ __forceinline__ int* lm_area_ticket(LmState* st) { return reinterpret_cast<int*>(reinterpret_cast<char*>(st) + 3076); }
-// ... and, behind the first 4096 bytes (kLmAreaBytes in all, zeroed once with them), what the resident solve (k_lm_solve) hands over with:
-//   +3080  its give-up word: the number of the solve a workgroup gave up on (a wait ran out, or RGC_LM_GIVE_UP_AT)
-//   +4096  one 64-bit flag per workgroup, {solve number, try number}: written by that workgroup alone
-__device__ __forceinline__ unsigned* lm_area_give_up(LmState* st) { return reinterpret_cast<unsigned*>(reinterpret_cast<char*>(st) + 3080); }
-__device__ __forceinline__ unsigned long long* lm_area_flags(LmState* st) { return reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(st) + 4096); }
-static_assert(kLmAreaBytes >= 4096 + 8 * kLmSolveMaxGroups, "a flag per workgroup of the resident solve");
-
 // The final pose of a finished solve (LDS state `ls`) into mapped host memory, then the solve's number: the whole workgroup takes part.
 __device__ __forceinline__ void post_early_pose(const LmState& ls, LmEarly* early, int* miss, int gen) {
   int* hw = reinterpret_cast<int*>(early);
@@ -3386,13 +3371,135 @@ __device__ __forceinline__ void post_early_pose(const LmState& ls, LmEarly* earl
   if (threadIdx.x == 0) __hip_atomic_store(&early->gen, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---- the pieces of a solve that k_lm_step (chained launches) and k_lm_solve (one resident launch) share: one body each ----
+constexpr int kLmStateWords = (int)(sizeof(LmState) / sizeof(int));
+
+// the workgroup's LDS state into a state image of the LM area
+__device__ __forceinline__ void lm_store_image(const LmState& ls, LmState* dst) {
+  const int* lw = reinterpret_cast<const int*>(&ls);
+  int* gw = reinterpret_cast<int*>(dst);
+  for (int u = threadIdx.x; u < kLmStateWords; u += LIN_T) gw[u] = lw[u];
+}
+
+// The fresh state of a solve (:53-63) with the frame's counters in the workgroup's LDS image, so that ONE read-back at the end carries
+// every statistic.  reinit: see lm_state_open
+__device__ __forceinline__ void lm_fresh_state(LmState& ls, const LmInit& in, SmallWords* small, const int* __restrict__ def_t,
+                                               const int* __restrict__ def_s, const FitArgs& fa, bool reinit) {
+  int* lw = reinterpret_cast<int*>(&ls);
+  for (int u = threadIdx.x; u < kLmStateWords; u += LIN_T) lw[u] = 0;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    lm_state_open(ls, in, small, def_t, def_s, reinit);
+    ls.lazy_nq = fa.counts ? fa.counts[0] : 0;
+    ls.lazy_ncell = fa.counts ? fa.counts[1] : 0;
+    ls.mode = LM_MODE_LIN;
+    if (in.max_outer <= 0) ls.done = 1;  // max_iterations <= 0: the guess is the answer (a later launch scores it if asked to)
+  }
+  __syncthreads();
+}
+
+// this thread's scan point and its normal
+struct LmPoint { float4 p; double n0, n1, n2; int i; };
+__device__ __forceinline__ LmPoint lm_load_point(const float4* __restrict__ P, const double* __restrict__ nx, const double* __restrict__ ny,
+                                                 const double* __restrict__ nz, int n) {
+  LmPoint q{make_float4(0.f, 0.f, 0.f, 0.f), 0.0, 0.0, 0.0, (int)(blockIdx.x * LIN_T + threadIdx.x)};
+  if (q.i < n) { q.p = P[q.i]; q.n0 = nx[q.i]; q.n1 = ny[q.i]; q.n2 = nz[q.i]; }
+  return q;
+}
+
+// One try's per-point work and the workgroup's row of its sums.  mode / cur: what the last decision left (LmState::mode, ::cur; LM_MODE_LIN, 0
+// in the launch that opens a chained solve); x_lin: the pose a linearisation of this try is taken at -- x0 in LM_MODE_LIN, else xi.
+// ls is read for the trial pose xi and the convergence test of the try, never in LM_MODE_LIN.  first: the developer build's stamp slot
+template <bool kWriteThrough>
+__device__ __forceinline__ void lm_try_rows(const LmState& ls, int mode, int cur, const double* x_lin, const LmPoint& q, int n, const Grid& g,
+                                            const int* __restrict__ cell_voxel, const double* __restrict__ vox, int noff, int* corr_v0,
+                                            double* corr_M0, int* corr_v1, double* corr_M1, int* miss, const FitArgs& fa, double* row, int first) {
+  (void)first;  // (< 0: the resident solve, which keeps its own stamps)
+  const bool final_try = mode != LM_MODE_LIN && lm_is_converged(ls.delta, ls.rot_eps, ls.trans_eps);
+  int* cv_cur = cur ? corr_v1 : corr_v0;
+  double* cm_cur = cur ? corr_M1 : corr_M0;
+  int* cv_nxt = cur ? corr_v0 : corr_v1;
+  double* cm_nxt = cur ? corr_M0 : corr_M1;
+  double acc[kStepAcc];
+#pragma unroll
+  for (int a = 0; a < kStepAcc; a++) acc[a] = 0.0;
+  if (mode != LM_MODE_LIN && q.i < n) acc[kAccum + 1] = error_point_pre(q.p, q.i, n, ls.xi, vox, noff, cv_cur, cm_cur);
+  if (mode != LM_MODE_B && !final_try) {
+    Pose T;
+    lm_load_pose(x_lin, T);
+    double lin[kAccum];
+#pragma unroll
+    for (int a = 0; a < kAccum; a++) lin[a] = 0.0;
+    int ncorr = 0;
+    if (q.i < n) linearize_point_pre(q.p, q.n0, q.n1, q.n2, q.i, n, T, g, cell_voxel, vox, noff, mode == LM_MODE_LIN ? cv_cur : cv_nxt,
+                                     mode == LM_MODE_LIN ? cm_cur : cm_nxt, 1, lin, ncorr, fa.need ? miss : nullptr, fa.need, fa.stamp);
+#pragma unroll
+    for (int a = 0; a < kAccum; a++) acc[a] = lin[a];
+    acc[kAccum] = (double)ncorr;  // exact: counts are far below 2^53
+  }
+#ifdef RGC_LAB
+  if (first >= 0) LAB_TS_MIN(1);
+#endif
+  block_reduce_store<kStepAcc, kWriteThrough>(acc, row);
+#ifdef RGC_LAB
+  if (first >= 0) LAB_TS_MIN(2);
+#endif
+}
+
+// The close of a solve, by every workgroup that holds its finished state `ls`: the final pose ahead of everything else, the score's rows and
+// their fold by the last arriver, the lazy target's miss flag, the state image, the post.  Only the workgroup that goes all the way -- the
+// score's last arriver, or workgroup 0 of a solve without a score -- writes.  What the two kernels do differently is theirs to say:
+//   was_done  the solve had finished before this launch (no early pose, no miss flag: an earlier close took them)
+//   score     the score is computed here
+//   image     the state image that is written
+//   reinit    (nullable) the small scratch whose blocks are put back here
+//   post      the state may be posted from here
+// turn_t0: the developer build's (RGC_LAB_TURN) stamp of the launch's start, 0: none
+__device__ __forceinline__ void lm_close(LmState& ls, bool was_done, bool score, LmState* image, SmallWords* reinit, bool post, LmArea* area,
+                                         const float4* __restrict__ P, int n, const Grid& g, const FitArgs& fa, LmState* __restrict__ h_post,
+                                         int seq, unsigned long long turn_t0) {
+  (void)turn_t0;
+  const int solve = seq < 0 ? -seq : seq;
+  if (score) {
+    // the score at the final pose, every wave its row; the last arriver folds them
+    if (fa.early && blockIdx.x == 0 && !was_done) {
+      // ... the final POSE first (every linearisation of this solve has run: the guards and the lazy target's miss flag are final too):
+      // whoever needs only the pose to go on does not wait for the score
+      post_early_pose(ls, fa.early, &area->miss, solve);
+#ifdef RGC_LAB_TURN
+      if (turn_t0 && threadIdx.x == 0) { const unsigned long long now = wall_clock64(); atomicExch(&g_lab_turn[3], now); atomicAdd(&g_lab_turn[5], now - turn_t0); }
+#endif
+    }
+    step_fitness_rows(P, n, ls.x0, g, fa);
+    if (!last_block_arrive(&area->ticket)) return;
+    if (threadIdx.x < WAVE) {
+      const double t = fitness_fold(fa.partials, fitness_blocks_dev(n));
+      if (threadIdx.x == 0) { ls.fit_sum = t; ls.has_fit = 1; }
+    }
+  } else if (blockIdx.x != 0) {
+    return;
+  }
+  if (threadIdx.x == 0) {
+    if (!was_done) {  // the lazy target's miss flag rides home with the state and is left cleared for the next solve
+      ls.pad2 = __hip_atomic_load(&area->miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&area->miss, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (reinit) reinit_small_blocks(reinit);
+  }
+  __syncthreads();
+  lm_store_image(ls, image);
+  // seq > 0: no score is chained to this solve -- a finished state is the frame's result; seq < 0: a finished state WITH its score is
+  // (from here, or from k_fitness_lm when the caller keeps the score apart)
+  if (post && (seq > 0 || ls.has_fit)) post_state_to_host(&ls, h_post, solve, LIN_T, false);
+}
+
 // One launch of the device-chained LM, launch number j of its solve (the host counts; 0 opens the solve).
 //
 // EVERY workgroup takes the decision the previous launch's sums call for, by itself: it reads the state image the previous launch
-// left (st[(j-1) & 1]) and that launch's rows, folds them in the fixed order, and its lane 0 runs accept / reject / terminate and the
+// left (area->image[(j-1) & 1]) and that launch's rows, folds them in the fixed order, and its lane 0 runs accept / reject / terminate and the
 // next LM try (lm_step_decide) on an LDS copy -- the same inputs and the same code in every workgroup, hence the same state.  Then it
 // does this launch's per-point work at the pose that decision produced and stores its row; workgroup 0 also stores the state image
-// (st[j & 1]: never the one the launch reads).  No workgroup waits for another inside a step: the kernel boundary is the only
+// (image[j & 1]: never the one the launch reads).  No workgroup waits for another inside a step: the kernel boundary is the only
 // synchronisation (the former step had both -- a ticket, a last arriver that fetched everyone's rows, decided and tried alone while
 // the launch's other 117 workgroups had left: ~2.8 us of a 14 us step).
 //
@@ -3409,54 +3516,36 @@ __device__ __forceinline__ void post_early_pose(const LmState& ls, LmEarly* earl
 //
 // The launch whose decision ENDS the solve computes getFitnessScore at the final pose (fa.on; the same grid covers the scan: four
 // waves per workgroup, one row per wave), its last-arriving workgroup folds the rows into the state and posts it to the host.  A
-// launch on a finished solve only hands the state image on (workgroup 0: st[(j-1) & 1] -> st[j & 1]) so that the host finds the
+// launch on a finished solve only hands the state image on (workgroup 0: image[(j-1) & 1] -> image[j & 1]) so that the host finds the
 // latest image behind its last launch whatever their number.
 __global__ void __launch_bounds__(LIN_T)
 k_lm_step(const float4* __restrict__ P, const double* __restrict__ nx, const double* __restrict__ ny, const double* __restrict__ nz, int n, Grid g,
           const int* __restrict__ cell_voxel, const double* __restrict__ vox, int noff, int* __restrict__ corr_v0, double* __restrict__ corr_M0,
-          int* __restrict__ corr_v1, double* __restrict__ corr_M1, double* __restrict__ partials, LmState* __restrict__ st, int j,
-          LmInit in, const int* __restrict__ nvox, const int* __restrict__ def_t, const int* __restrict__ def_s, LmState* __restrict__ h_post,
+          int* __restrict__ corr_v1, double* __restrict__ corr_M1, double* __restrict__ partials, LmArea* __restrict__ area, int j,
+          LmInit in, SmallWords* __restrict__ small, const int* __restrict__ def_t, const int* __restrict__ def_s, LmState* __restrict__ h_post,
           int seq, FitArgs fa) {
   wave_prio(2);  // a latency chain: issue ahead of whatever shares the CU (the other context's kNN, the next scan's preparation)
 #ifdef RGC_LAB_TURN
   const unsigned long long lab_turn_t0 = wall_clock64();
+#else
+  const unsigned long long lab_turn_t0 = 0;
 #endif
-  constexpr int kStateWords = (int)(sizeof(LmState) / sizeof(int));
   __shared__ LmState ls;
   __shared__ double folded[kStepAcc];
   const int first = j == 0;
   (void)first;
-  LmState* const sn = st + (j & 1);                                  // the image this launch leaves
+  LmState* const sn = &area->image[j & 1];                           // the image this launch leaves
   double* const rows_out = partials + (size_t)(j & 1) * gridDim.x * kStepAcc;
-  int* const miss = lm_area_miss(st);
-  auto store_image = [&](LmState* dst) {
-    const int* lw = reinterpret_cast<const int*>(&ls);
-    int* gw = reinterpret_cast<int*>(dst);
-    for (int u = threadIdx.x; u < kStateWords; u += LIN_T) gw[u] = lw[u];
-  };
   LAB_TS_MIN(0);
   // Everything this launch will need from memory that does not depend on the decision is asked for NOW, in one round trip: the state image,
   // this thread's rows of the previous launch, its scan point and normal.
-  const int i = blockIdx.x * LIN_T + threadIdx.x;
-  float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
-  double pn0 = 0.0, pn1 = 0.0, pn2 = 0.0;
-  if (i < n) { pp = P[i]; pn0 = nx[i]; pn1 = ny[i]; pn2 = nz[i]; }
+  const LmPoint q = lm_load_point(P, nx, ny, nz, n);
   if (j == 0) {
     // The opening launch: nobody reads the (stale) images; pose and thresholds come from the kernel arguments.  Workgroup 0 builds the
-    // fresh state (:53-63) with the frame's counters, so that ONE read-back at the end carries every statistic.
+    // fresh state; the others take the pose from the arguments and never read ls.
     if (blockIdx.x == 0) {
-      int* lw = reinterpret_cast<int*>(&ls);
-      for (int u = threadIdx.x; u < kStateWords; u += LIN_T) lw[u] = 0;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        lm_state_open(ls, in, nvox, def_t, def_s);
-        ls.lazy_nq = fa.counts ? fa.counts[0] : 0;
-        ls.lazy_ncell = fa.counts ? fa.counts[1] : 0;
-        ls.mode = LM_MODE_LIN;
-        if (in.max_outer <= 0) ls.done = 1;  // max_iterations <= 0: the guess is the answer (a later launch scores it if asked to)
-      }
-      __syncthreads();
-      store_image(sn);
+      lm_fresh_state(ls, in, small, def_t, def_s, fa, /*reinit=*/true);
+      lm_store_image(ls, sn);
       if (in.max_outer <= 0 && h_post && seq > 0) post_state_to_host(&ls, h_post, seq, LIN_T, false);
     }
     if (in.max_outer <= 0) return;
@@ -3464,14 +3553,14 @@ k_lm_step(const float4* __restrict__ P, const double* __restrict__ nx, const dou
     const double* const rows_in = partials + (size_t)((j - 1) & 1) * gridDim.x * kStepAcc;
     double rv[16];
     {
-      static_assert(kStateWords <= 2 * LIN_T, "two words of the image per thread");
+      static_assert(kLmStateWords <= 2 * LIN_T, "two words of the image per thread");
       int* lw = reinterpret_cast<int*>(&ls);
-      const int* gw = reinterpret_cast<const int*>(st + ((j - 1) & 1));
+      const int* gw = reinterpret_cast<const int*>(&area->image[(j - 1) & 1]);
       const int u0 = threadIdx.x, u1 = threadIdx.x + LIN_T;
-      const int w0 = gw[u0], w1 = u1 < kStateWords ? gw[u1] : 0;
+      const int w0 = gw[u0], w1 = u1 < kLmStateWords ? gw[u1] : 0;
       block_fold_rows_load16<kStepAcc>(rows_in, gridDim.x, rv);  // (rows of a finished solve are stale but valid memory; they are not used then)
       lw[u0] = w0;
-      if (u1 < kStateWords) lw[u1] = w1;
+      if (u1 < kLmStateWords) lw[u1] = w1;
     }
     __syncthreads();
     const bool was_done = ls.done != 0;
@@ -3485,68 +3574,17 @@ k_lm_step(const float4* __restrict__ P, const double* __restrict__ nx, const dou
       __syncthreads();
     }
     if (ls.done) {
+      // the solve ended with this launch's decision, or earlier: an unscored one (max_iterations <= 0) is scored, a finished one handed on
       const bool score = fa.on && !ls.has_fit;
-      if (score) {
-        // the solve ended with this launch's decision (or earlier, unscored: max_iterations <= 0): the score at the final pose, every
-        // wave its row; the last arriver folds them
-        if (fa.early && blockIdx.x == 0 && !was_done) {
-          // ... the final POSE first (every linearisation of this solve ran in an earlier launch: the guards and the lazy target's miss flag
-          // are final too): whoever needs only the pose to go on does not wait for the score
-          post_early_pose(ls, fa.early, miss, seq < 0 ? -seq : seq);
-#ifdef RGC_LAB_TURN
-          if (threadIdx.x == 0) { const unsigned long long now = wall_clock64(); atomicExch(&g_lab_turn[3], now); atomicAdd(&g_lab_turn[5], now - lab_turn_t0); }
-#endif
-        }
-        step_fitness_rows(P, n, ls.x0, g, fa);
-        if (!last_block_arrive(lm_area_ticket(st))) return;
-        if (threadIdx.x < WAVE) {
-          const double t = fitness_fold(fa.partials, fitness_blocks_dev(n));
-          if (threadIdx.x == 0) { ls.fit_sum = t; ls.has_fit = 1; }
-        }
-      } else if (blockIdx.x != 0) {
-        return;
-      }
-      if (threadIdx.x == 0 && !was_done) {  // the lazy target's miss flag rides home with the state and is left cleared for the next solve
-        ls.pad2 = __hip_atomic_load(miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(miss, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __syncthreads();
-      store_image(sn);
-      // seq > 0: no score is chained to this solve -- a finished state is the frame's result; seq < 0: a finished state WITH its score is
-      // (from here, or from k_fitness_lm when the caller keeps the score apart)
-      if (h_post && (!was_done || score) && (seq > 0 || ls.has_fit)) post_state_to_host(&ls, h_post, seq < 0 ? -seq : seq, LIN_T, false);
+      lm_close(ls, was_done, score, sn, /*reinit=*/nullptr, /*post=*/h_post && (!was_done || score), area, P, n, g, fa, h_post, seq, lab_turn_t0);
       return;
     }
   }
-  // ---- this launch's per-point work, at the pose the decision above arrived at ----
+  // ---- this launch's per-point work, at the pose the decision above arrived at (the opening launch: the guess) ----
   const int mode = j == 0 ? LM_MODE_LIN : ls.mode, cur = j == 0 ? 0 : ls.cur;
-  const bool final_try = mode != LM_MODE_LIN && lm_is_converged(ls.delta, ls.rot_eps, ls.trans_eps);
-  int* cv_cur = cur ? corr_v1 : corr_v0;
-  double* cm_cur = cur ? corr_M1 : corr_M0;
-  int* cv_nxt = cur ? corr_v0 : corr_v1;
-  double* cm_nxt = cur ? corr_M0 : corr_M1;
-  double acc[kStepAcc];
-#pragma unroll
-  for (int a = 0; a < kStepAcc; a++) acc[a] = 0.0;
-  if (mode != LM_MODE_LIN && i < n) acc[kAccum + 1] = error_point_pre(pp, i, n, ls.xi, vox, noff, cv_cur, cm_cur);
-  if (mode != LM_MODE_B && !final_try) {
-    Pose T;
-    if (j == 0) lm_load_pose(in.x0, T);
-    else lm_load_pose(mode == LM_MODE_LIN ? ls.x0 : ls.xi, T);
-    double lin[kAccum];
-#pragma unroll
-    for (int a = 0; a < kAccum; a++) lin[a] = 0.0;
-    int ncorr = 0;
-    if (i < n) linearize_point_pre(pp, pn0, pn1, pn2, i, n, T, g, cell_voxel, vox, noff, mode == LM_MODE_LIN ? cv_cur : cv_nxt,
-                                   mode == LM_MODE_LIN ? cm_cur : cm_nxt, 1, lin, ncorr, fa.need ? miss : nullptr, fa.need, fa.stamp);
-#pragma unroll
-    for (int a = 0; a < kAccum; a++) acc[a] = lin[a];
-    acc[kAccum] = (double)ncorr;  // exact: counts are far below 2^53
-  }
-  LAB_TS_MIN(1);
-  block_reduce_store<kStepAcc>(acc, rows_out + (size_t)blockIdx.x * kStepAcc);  // (read by the NEXT launch: plain stores)
-  LAB_TS_MIN(2);
-  if (j > 0 && blockIdx.x == 0) store_image(sn);
+  lm_try_rows<false>(ls, mode, cur, j == 0 ? in.x0 : mode == LM_MODE_LIN ? ls.x0 : ls.xi, q, n, g, cell_voxel, vox, noff, corr_v0, corr_M0, corr_v1,
+                     corr_M1, &area->miss, fa, rows_out + (size_t)blockIdx.x * kStepAcc, first);  // (read by the NEXT launch: plain stores)
+  if (j > 0 && blockIdx.x == 0) lm_store_image(ls, sn);
 }
 
 
@@ -3567,13 +3605,13 @@ k_lm_step(const float4* __restrict__ P, const double* __restrict__ nx, const dou
 // hook): workgroup 0 takes that way out at that try without waiting.
 //
 // false: this workgroup leaves the solve.
-__device__ __forceinline__ bool lm_solve_hand_over(LmState* st, unsigned solve, unsigned t, bool give_up_now) {
+__device__ __forceinline__ bool lm_solve_hand_over(LmArea* area, unsigned solve, unsigned t, bool give_up_now) {
   __shared__ int go_s;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's row stores (sc1) have reached memory
   __syncthreads();
   if (threadIdx.x < WAVE) {
-    unsigned long long* const flags = lm_area_flags(st);
-    unsigned* const give_up = lm_area_give_up(st);
+    unsigned long long* const flags = area->flags;
+    unsigned* const give_up = &area->give_up;
     const int lane = threadIdx.x, G = (int)gridDim.x;
     bool go = false, expired = give_up_now;
     if (!give_up_now) {
@@ -3594,7 +3632,7 @@ __device__ __forceinline__ bool lm_solve_hand_over(LmState* st, unsigned solve, 
     }
     if (expired && lane == 0) {
       __hip_atomic_store(give_up, solve, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&st[0].cmd, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&area->image[0].cmd, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (lane == 0) go_s = go ? 1 : 0;
   }
@@ -3605,31 +3643,15 @@ __device__ __forceinline__ bool lm_solve_hand_over(LmState* st, unsigned solve, 
 __global__ void __launch_bounds__(LIN_T)
 k_lm_solve(const float4* __restrict__ P, const double* __restrict__ nx, const double* __restrict__ ny, const double* __restrict__ nz, int n, Grid g,
            const int* __restrict__ cell_voxel, const double* __restrict__ vox, int noff, int* corr_v0, double* corr_M0, int* corr_v1, double* corr_M1,
-           double* partials, LmState* st, LmInit in, const int* nvox, const int* __restrict__ def_t, const int* __restrict__ def_s,
+           double* partials, LmArea* area, LmInit in, SmallWords* small, const int* __restrict__ def_t, const int* __restrict__ def_s,
            LmState* __restrict__ h_post, int seq, FitArgs fa, int give_up_at) {
   wave_prio(2);
-  constexpr int kStateWords = (int)(sizeof(LmState) / sizeof(int));
   __shared__ LmState ls;
   __shared__ double folded[kStepAcc];
   const unsigned solve = (unsigned)(seq < 0 ? -seq : seq);
-  int* const miss = lm_area_miss(st);
-  const int i = blockIdx.x * LIN_T + threadIdx.x;
-  float4 pp = make_float4(0.f, 0.f, 0.f, 0.f);
-  double pn0 = 0.0, pn1 = 0.0, pn2 = 0.0;
-  if (i < n) { pp = P[i]; pn0 = nx[i]; pn1 = ny[i]; pn2 = nz[i]; }
-  {  // the fresh state (:53-63), in every workgroup
-    int* lw = reinterpret_cast<int*>(&ls);
-    for (int u = threadIdx.x; u < kStateWords; u += LIN_T) lw[u] = 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      lm_state_open(ls, in, nvox, def_t, def_s, /*reinit=*/false);
-      ls.lazy_nq = fa.counts ? fa.counts[0] : 0;
-      ls.lazy_ncell = fa.counts ? fa.counts[1] : 0;
-      ls.mode = LM_MODE_LIN;
-      if (in.max_outer <= 0) ls.done = 1;  // max_iterations <= 0: the guess is the answer
-    }
-    __syncthreads();
-  }
+  const LmPoint q = lm_load_point(P, nx, ny, nz, n);
+  // the fresh state, in every workgroup; the counters' blocks are put back by the workgroup that finishes the solve (lm_close)
+  lm_fresh_state(ls, in, small, def_t, def_s, fa, /*reinit=*/false);
   const bool was_done = in.max_outer <= 0;
   if (!was_done) {
     // every decision but the opening one consumes a cost evaluation (at most max_outer * max_inner of them) and an outer iteration has at
@@ -3642,32 +3664,10 @@ k_lm_solve(const float4* __restrict__ P, const double* __restrict__ nx, const do
       if (blockIdx.x == 0 && threadIdx.x == 0 && t < 13) g_lab_ts[t < 5 ? t : t + 3] = wall_clock64();
 #endif
       // ---- this try's per-point work (k_lm_step's, at the pose the last decision arrived at) ----
-      const int mode = ls.mode, cur = ls.cur;
-      const bool final_try = mode != LM_MODE_LIN && lm_is_converged(ls.delta, ls.rot_eps, ls.trans_eps);
-      int* cv_cur = cur ? corr_v1 : corr_v0;
-      double* cm_cur = cur ? corr_M1 : corr_M0;
-      int* cv_nxt = cur ? corr_v0 : corr_v1;
-      double* cm_nxt = cur ? corr_M0 : corr_M1;
-      double acc[kStepAcc];
-#pragma unroll
-      for (int a = 0; a < kStepAcc; a++) acc[a] = 0.0;
-      if (mode != LM_MODE_LIN && i < n) acc[kAccum + 1] = error_point_pre(pp, i, n, ls.xi, vox, noff, cv_cur, cm_cur);
-      if (mode != LM_MODE_B && !final_try) {
-        Pose T;
-        lm_load_pose(mode == LM_MODE_LIN ? ls.x0 : ls.xi, T);
-        double lin[kAccum];
-#pragma unroll
-        for (int a = 0; a < kAccum; a++) lin[a] = 0.0;
-        int ncorr = 0;
-        if (i < n) linearize_point_pre(pp, pn0, pn1, pn2, i, n, T, g, cell_voxel, vox, noff, mode == LM_MODE_LIN ? cv_cur : cv_nxt,
-                                       mode == LM_MODE_LIN ? cm_cur : cm_nxt, 1, lin, ncorr, fa.need ? miss : nullptr, fa.need, fa.stamp);
-#pragma unroll
-        for (int a = 0; a < kAccum; a++) acc[a] = lin[a];
-        acc[kAccum] = (double)ncorr;
-      }
       double* const rows = partials + (size_t)(t & 1) * gridDim.x * kStepAcc;
-      block_reduce_store<kStepAcc, true>(acc, rows + (size_t)blockIdx.x * kStepAcc);
-      if (!lm_solve_hand_over(st, solve, (unsigned)t, blockIdx.x == 0 && t == give_up_at)) return;
+      lm_try_rows<true>(ls, ls.mode, ls.cur, ls.mode == LM_MODE_LIN ? ls.x0 : ls.xi, q, n, g, cell_voxel, vox, noff, corr_v0, corr_M0, corr_v1, corr_M1,
+                        &area->miss, fa, rows + (size_t)blockIdx.x * kStepAcc, /*first=*/-1);
+      if (!lm_solve_hand_over(area, solve, (unsigned)t, blockIdx.x == 0 && t == give_up_at)) return;
       // ---- everybody's rows, the fixed-order fold and the decision, in every workgroup ----
       double rv[16];
       block_fold_rows_load16<kStepAcc, true>(rows, gridDim.x, rv);
@@ -3681,33 +3681,9 @@ k_lm_solve(const float4* __restrict__ P, const double* __restrict__ nx, const do
     }
     if (t >= max_tries) return;  // (never: nothing is posted, the host solves again)
   }
-  // ---- the solve is over: the early pose, the score, the state (k_lm_step's closing launch) ----
-  const bool score = fa.on != 0;
-  if (score) {
-    if (fa.early && blockIdx.x == 0 && !was_done) post_early_pose(ls, fa.early, miss, (int)solve);
-    step_fitness_rows(P, n, ls.x0, g, fa);
-    if (!last_block_arrive(lm_area_ticket(st))) return;
-    if (threadIdx.x < WAVE) {
-      const double f = fitness_fold(fa.partials, fitness_blocks_dev(n));
-      if (threadIdx.x == 0) { ls.fit_sum = f; ls.has_fit = 1; }
-    }
-  } else if (blockIdx.x != 0) {
-    return;
-  }
-  if (threadIdx.x == 0) {
-    if (!was_done) {
-      ls.pad2 = __hip_atomic_load(miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(miss, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (nvox) reinit_small_blocks(nvox);  // every workgroup has captured the counters (each passed a hand-over or the score's ticket since)
-  }
-  __syncthreads();
-  {
-    const int* lw = reinterpret_cast<const int*>(&ls);
-    int* gw = reinterpret_cast<int*>(st);  // image 0: lm_image(st, 0)
-    for (int u = threadIdx.x; u < kStateWords; u += LIN_T) gw[u] = lw[u];
-  }
-  if (h_post && (seq > 0 || ls.has_fit)) post_state_to_host(&ls, h_post, (int)solve, LIN_T, false);
+  // ---- the solve is over: the early pose, the score, the state.  The counters' blocks are put back here: every workgroup has captured
+  // them (each passed a hand-over or the score's ticket since)
+  lm_close(ls, was_done, /*score=*/fa.on != 0, &area->image[0], /*reinit=*/small, /*post=*/h_post != nullptr, area, P, n, g, fa, h_post, seq, 0);
 }
 
 // fold per-block rows in a fixed order: block a (one wave) owns accumulator a; lane l sums rows l, l+64, ...
@@ -4695,12 +4671,12 @@ static FitArgs fit_args_of(const LmArgs& a) {
 }
 void lm_step(hipStream_t s, const LmArgs& a, int j, const LmInit* open) {
   hipLaunchKernelGGL(k_lm_step, dim3(linearize_blocks(a.src.n)), dim3(LIN_T), 0, s, a.src.P, a.nrm.nx, a.nrm.ny, a.nrm.nz, a.src.n, a.tgt.grid, a.vm.cell_voxel,
-                     a.vm.vox, a.noff, a.corr[0].v, a.corr[0].M, a.corr[1].v, a.corr[1].M, a.partials, a.st, j, (j == 0 && open) ? *open : LmInit{}, a.nvox,
+                     a.vm.vox, a.noff, a.corr[0].v, a.corr[0].M, a.corr[1].v, a.corr[1].M, a.partials, a.area, j, (j == 0 && open) ? *open : LmInit{}, a.small,
                      (const int*)a.segs_t, (const int*)a.segs_s, a.h_post, a.seq, fit_args_of(a));
 }
 void lm_solve_resident(hipStream_t s, const LmArgs& a, const LmInit& open, int give_up_at) {
   hipLaunchKernelGGL(k_lm_solve, dim3(linearize_blocks(a.src.n)), dim3(LIN_T), 0, s, a.src.P, a.nrm.nx, a.nrm.ny, a.nrm.nz, a.src.n, a.tgt.grid, a.vm.cell_voxel,
-                     a.vm.vox, a.noff, a.corr[0].v, a.corr[0].M, a.corr[1].v, a.corr[1].M, a.partials, a.st, open, a.nvox, (const int*)a.segs_t,
+                     a.vm.vox, a.noff, a.corr[0].v, a.corr[0].M, a.corr[1].v, a.corr[1].M, a.partials, a.area, open, a.small, (const int*)a.segs_t,
                      (const int*)a.segs_s, a.h_post, a.seq, fit_args_of(a), give_up_at);
 }
 void fitness_lm(hipStream_t s, const SortedCloud& src, LmState* st, const SortedCloud& tgt, double* partials, LmState* h_post, int seq) {

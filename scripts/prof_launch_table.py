@@ -1,11 +1,22 @@
 """The launch table of a rocprofv3 --kernel-trace csv: one row per (kernel, grid size, workgroup size, LDS bytes) with its launch count, sorted.
 With two traces it also says whether the two tables are the same multiset -- what a change of the host code that is meant to leave a frame's
 launch sequence alone has to show (run each library over the same driver, e.g. scripts/prof_dependent.py; RGC_HIP_LIB selects the library).
-    python scripts/prof_launch_table.py <trace dir A> [<trace dir B>] [--out-a FILE] [--out-b FILE]"""
+    python scripts/prof_launch_table.py <trace dir A> [<trace dir B>] [--out-a FILE] [--out-b FILE] [--no-params]
+--no-params: kernels are named without their parameter lists (a change that retypes a kernel's pointer arguments renames it in the trace)"""
 import collections
 import csv
 import glob
 import sys
+
+
+def without_params(name):
+    """k_fold<1>(double const*, int) -> k_fold<1>: cut at the first parenthesis outside the template arguments"""
+    depth = 0
+    for i, ch in enumerate(name):
+        depth += (ch == "<") - (ch == ">")
+        if ch == "(" and depth == 0:
+            return name[:i]
+    return name
 
 
 def table(trace_dir):
@@ -17,6 +28,8 @@ def table(trace_dir):
     t = collections.Counter()
     for r in rows:
         name = r["Kernel_Name"].replace("void ", "").replace("rgck::", "")
+        if "--no-params" in sys.argv:
+            name = without_params(name)
         t[(name, dims(r, "Grid_Size"), dims(r, "Workgroup_Size"), r[lds_key] if lds_key else "?")] += 1
     return t
 
