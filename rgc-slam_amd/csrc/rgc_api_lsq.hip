@@ -2,19 +2,9 @@
 // lsq_registration_impl.hpp:53-79, 125-172) and the two methods that are nothing else on the host: NDT (rgc_ndt_*) and FastGICP (rgc_gicp_*).
 // rgc_align's host-driven route (rgc_api.hip) runs on the same driver.  The kernels are in rgc_ndt.hip and rgc_gicp.hip.
 #include "rgc_ctx.h"
-#include "rgc_lm.h"
+#include "rgc_lm_decide.h"  // rgc_lm.h and the convergence test the device decides by (lsq_registration_impl.hpp:82-91)
 
 using namespace rgcapi;
-
-// lsq_registration_impl.hpp:82-91
-static bool is_converged(const double d[16], double rot_eps, double trans_eps) {
-  double m = 0;
-  for (int a = 0; a < 3; a++) {
-    for (int b = 0; b < 3; b++) m = std::fmax(m, std::fabs(d[a * 4 + b] - (a == b ? 1.0 : 0.0)) / rot_eps);
-    m = std::fmax(m, std::fabs(d[a * 4 + 3]) / trans_eps);
-  }
-  return m < 1;
-}
 
 // LsqRegistration::computeTransformation (lsq_registration_impl.hpp:53-79) + step_lm (:125-172); SURVEY A.5.  The scalar pieces (so3_exp, the
 // LDLT solve, the 4x4 product) are rgc_lm.h's, shared with the device.
@@ -60,7 +50,7 @@ int rgcapi::lm_solve(rgc_ctx* c, const LmSystem& sys, const float guess[16], LmR
       for (int i = 0; i < 6; i++) den += d[i] * (lambda * d[i] - b[i]);
       const double rho = (y0 - yi) / den;  // :145
       if (rho < 0) {  // :155-163
-        if (is_converged(delta, P.rotation_eps, P.translation_eps)) { ok = true; break; }
+        if (rgck::lm_is_converged(delta, P.rotation_eps, P.translation_eps)) { ok = true; break; }
         lambda = nu * lambda;
         nu = 2 * nu;
         continue;
@@ -72,7 +62,7 @@ int rgcapi::lm_solve(rgc_ctx* c, const LmSystem& sys, const float guess[16], LmR
       break;
     }
     if (!ok) { r->failed = true; break; }  // :69-72 "lm not converged!!"
-    r->conv = is_converged(delta, P.rotation_eps, P.translation_eps);  // :74
+    r->conv = rgck::lm_is_converged(delta, P.rotation_eps, P.translation_eps);  // :74
   }
   for (int i = 0; i < 16; i++) r->fin[i] = (float)x0[i];  // :77
   return RGC_OK;

@@ -86,6 +86,36 @@ def test_row_and_workgroup_edges(reg_mod, fx_reg, monkeypatch, n):
     assert fb == [0]
 
 
+def test_as_many_workgroups_as_compute_units(reg_mod, monkeypatch):
+    """the edge of the rule that picks the route, linearize_blocks(n) == the device's CU count: scans of 256 (cu - 1) + 1 and 256 cu points fill every
+    CU with one workgroup of the resident launch (the second to its last lane), 256 cu + 1 points need one workgroup more and go through the chained
+    launches by rule.  Each against RGC_LM_IMPL=chained bit for bit on a 100 k-point map; which route ran is read with the hook: a context made with
+    RGC_LM_GIVE_UP_AT=0 counts one fallback per resident solve and none for a solve that was chained anyway -- and the same bits either way"""
+    import subprocess
+    import sys
+    import rgc_slam_amd.synth as synth
+    # the CU count as torch reports it, not as the library read it; asked in a child process: this one's HIP runtime is the one the library bound to
+    # when it was loaded, and torch's own cannot start beside it (bench.py imports torch first for the same reason)
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    cu = int(r.stdout.split()[-1])
+    sizes = [256 * (cu - 1) + 1, 256 * cu, 256 * cu + 1]
+    world, tgt = synth.make_world_and_map(100000, seed=synth.SEED + 7)
+    T_true = synth.se3(synth.rot_zyx(0.01, 0.002, -0.001), [0.08, 0.03, 0.002])
+    src = synth.make_scan_n(world, T_true, sizes[-1], seed=synth.SEED + 7)["xyz"]
+    assert len(src) == sizes[-1]
+    fx = dict(tgt=tgt, src=src, guess=np.eye(4, dtype=np.float32))
+    ref = _chained(reg_mod, fx, monkeypatch, sizes)
+    got, fb = _run(reg_mod, fx, monkeypatch, None, sizes)
+    print(cu, sizes, [{k: g[k] for k in ("iters", "conv", "failed", "n_lin", "n_err", "n_corr")} for g in got])
+    assert got == ref
+    assert fb == [0, 0, 0]                      # alone, no solve of the default route gives up
+    hooked, fb = _run(reg_mod, fx, monkeypatch, None, sizes, give_up_at=0)
+    assert hooked == ref
+    assert np.diff([0] + fb).tolist() == [1, 1, 0]
+
+
 @pytest.mark.parametrize("max_it,lm_it,far", [(0, 10, False), (1, 10, False), (2, 10, False), (3, 10, False), (25, 1, True), (25, 2, True),
                                               (40, 10, True)])
 def test_the_solves_ends(reg_mod, fx_reg, monkeypatch, max_it, lm_it, far):
