@@ -317,6 +317,22 @@ typedef struct rgc_vg_route {
   int n, n_out;
 } rgc_vg_route;
 RGC_API int rgc_voxelgrid_route(rgc_ctx* ctx, rgc_vg_route* out);
+/* pcl::UniformSampling<PointT>::filter with setRadiusSearch(leaf) (src/RGC_mapping.cpp:1533-1536, 2497-2500): one INPUT point per occupied leaf, the
+ * one nearest the leaf's centre.  The argument rules, the meaning of on_device, the routes and the refusals are rgc_voxelgrid's (RGC_ERR_NONFINITE,
+ * RGC_ERR_GRID_TOO_LARGE, RGC_ERR_INVALID for a bad stride or leaf; n = 0 gives *n_out = 0); it is that filter's chain with another last launch, and
+ * rgc_voxelgrid_route reports it.  out_xyzc: n * 4 floats capacity; out_index (nullable): n ints, host or device like the clouds.
+ *   Semantics, restated from PCL's filters/impl/uniform_sampling.hpp FROM MEMORY [3P-memory] (PCL is not available to this project; SURVEY A.6
+ * says the same of VoxelGrid):
+ *   - the leaf grid is the leaf filter's: inv = 1.0f / leaf, ijk = floor(fp32(p * inv)), the same min_b, div and idx = i + j dx + k dx dy;
+ *   - a leaf's centre is c_a = fp32(fp32((float)ijk_a + 0.5f) * leaf) from the GLOBAL ijk; a point's key is d2 = (dx*dx + dy*dy) + dz*dz in fp32,
+ *     not contracted; the winner has the smallest (d2, input index) -- PCL walks the input in order and replaces on strict < only, the same rule;
+ *   - PCL's distance runs over the point's 4-float map; its fourth component adds the same constant to both sides of a comparison: ignored;
+ *   - the winner's 16 bytes go out unchanged, {x, y, z, c} (c = 0 for a 12-byte input, as in the leaf filter), its input index to out_index.
+ *   Defined here, unspecified in PCL: the leaves come in ASCENDING idx, the leaf filter's order (PCL walks an unordered_map).
+ *   A grid of more than INT_MAX leaves follows THIS LIBRARY's rule for rgc_voxelgrid: RGC_VG_PATH_UNFILTERED, output = input (bit for bit),
+ *   out_index = the identity.  What PCL's UniformSampling returns there is not known to this project. */
+RGC_API int rgc_uniform_sampling(rgc_ctx* ctx, const float* xyzc, int n, int stride_bytes, float leaf, float* out_xyzc, int* out_index /* nullable */,
+                                 int* n_out, int on_device);
 /* B9  vg_ICP::transformPointCloud(cloud, q, t) (src/RGC_odometer.cpp:1495-1514): q * p + t in fp64, stored fp32,
  * intensity copied; out_xyzi: n*4 floats.  on_device: both pointers are device memory and the call returns once the kernel is enqueued
  * on rgc_stream(ctx), like rgc_deskew. */
@@ -701,6 +717,57 @@ RGC_API int rgc_kf_set_poses(rgc_ctx* ctx, const int* ids, const rgc_kf_pose* po
 RGC_API int rgc_kf_get_info(rgc_ctx* ctx, rgc_kf_info* out);
 RGC_API int rgc_kf_assemble(rgc_ctx* ctx, const int* ids, int n_ids, unsigned kind_mask, float leaf, float* out_xyzc, int cap, int on_device,
                             int* n_raw, int* n_out);
+/* ---- which keyframes to assemble: the mapping node's three selections and what they rest on ----
+ * Travelled distance and angle (src/RGC_mapping.cpp:1887-1908): computed on the host by rgc_kf_push in fp32 and never recomputed (the reference does
+ * not either).  The first keyframe of a store has 0; then travel[p] = travel[p-1] + sqrtf((dx*dx + dy*dy) + dz*dz) with the differences against the
+ * pose stored AT THAT MOMENT for the previous position (cloudKeyPoses6D->back(), corrected or not), and travel_angle[p] = travel_angle[p-1] +
+ * fabsf(rad_delta), rad_delta = yaw - last.yaw as a float wrapped once by -+ 2 M_PI in double (:1903-1905).  rgc_kf_get_travel: either output nullable;
+ * an unknown id is RGC_ERR_INVALID, nothing written.
+ *   The radius gate of all three selections [3P-memory: pcl::KdTreeFLANN::radiusSearch over flann::L2_Simple<float>]:
+ * r2 = (float)((double)radius * (double)radius); a key pose is inside when d2 = (dx*dx + dy*dy) + dz*dz (fp32, not contracted) < r2.  STRICT: a pose
+ * exactly on the radius is outside.  The tests pin this rule; it is NOT pinned against FLANN itself, which is not available to this project.
+ *   The key positions are mirrored on the device as float4 {x, y, z, position} (with the travelled distances and ids beside them), uploaded again
+ * only when the store's revision has moved (push, rgc_kf_set_poses, an applied rgc_pgo_optimize, reset).  One gate launch computes d2 and the
+ * predicate; no kd-tree is built.  Results are bit-identical from run to run.
+ *   rgc_kf_select_surrounding (extractSurroundingKeyFramesAndMap, :1525-1548; radius 15, density 0.3 there): the key positions inside the gate
+ * around `center`, in ascending store position, through rgc_uniform_sampling at leaf `density`; out_ids = the winners' ids in ascending leaf
+ * index, *n_in_radius = poses inside the gate.  DEVIATION: the reference hands PCL the radius result in ascending DISTANCE, so on an exact tie of two
+ * poses' distances to a leaf centre its winner is the one nearer the query; here it is the one at the lower store position.  Only exact ties differ.
+ * (The reference's cache of transformed clouds, :1551-1595, is not reproduced: see rgc_kf_assemble.)
+ *   rgc_kf_select_global (publishGlobalMap, :2493-2505; density 0.5 there): the same over every key position.
+ *   rgc_kf_detect_loop (detectLoopClosure, :2141-2225).  L = the last store position.  R = history_search_radius + (travel[L] - distance_by_loop) *
+ * drift_factor in fp32 (:2148).  The gate uses r2 from R, so a negative R searches |R| while the threshold below uses the signed value, as the
+ * reference's text does.  A pose qualifies when it is inside the gate around pose L, fabsf(travel[p] - travel[L]) > loop_keyframe_dis_diff + R (fp32
+ * add) and id >= min_key_id.  The candidate is the qualifying pose with the smallest (d2, position): the reference's "first in sorted order that
+ * passes, skipping ids < 10" (:2159-2172) is this minimum -- DEVIATION only where FLANN orders two poses of EQUAL d2 otherwise.  None qualifying, or
+ * closest_id == latest_id: found = 0.  History (:2195-2216): for i = -history_search_num .. +history_search_num the position p_closest + i,
+ * skipped when < 0 or >= L, or when its id is < 0 or >= latest_id; the rest in that order to history_ids.  No corner or surf point among them (the
+ * reference's empty nearHistoryKeyFrameCloud): found = 0.  The candidate reports latest / closest ids and poses as stored now (closest_id = -1
+ * when nothing qualified), the signed search radius and the number of poses inside the gate.
+ *   Common: cap too small is RGC_ERR_INVALID with the counts reported and nothing written (rgc_kf_assemble's convention); an empty store gives empty
+ * results and found = 0; a non-finite argument, radius <= 0 or density <= 0 is RGC_ERR_INVALID; the leaf filter's refusals pass through
+ * (rgc_voxelgrid_route tells the route of the sampling).  State machine as the other rgc_kf_* calls: they run with a solve in flight. */
+typedef struct rgc_kf_loop_params {
+  float history_search_radius;   /* historyKeyframeSearchRadius = 5, :155 */
+  float drift_factor;            /* DRIFT_FACTOR = 0.02, :159 */
+  float distance_by_loop;        /* DistanceByLoop = 0: the caller's state, :158, 2130-2135 */
+  float loop_keyframe_dis_diff;  /* loopKeyframeDisDiff = 20, :160 */
+  int history_search_num;        /* historyKeyframeSearchNum = 50, :157 */
+  int min_key_id;                /* 10, :2166 */
+} rgc_kf_loop_params;
+typedef struct rgc_kf_loop_candidate {
+  int found;
+  int latest_id, closest_id;
+  rgc_kf_pose latest_pose, closest_pose;
+  float search_radius;
+  int n_in_radius;
+} rgc_kf_loop_candidate;
+RGC_API int rgc_kf_get_travel(rgc_ctx* ctx, const int* ids, int n, float* distance /* nullable */, float* angle /* nullable */);
+RGC_API int rgc_kf_select_surrounding(rgc_ctx* ctx, const float center[3], float radius, float density, int* out_ids, int cap, int* n_in_radius,
+                                      int* n_out);
+RGC_API int rgc_kf_select_global(rgc_ctx* ctx, float pose_density, int* out_ids, int cap, int* n_out);
+RGC_API void rgc_default_kf_loop_params(rgc_kf_loop_params* p);
+RGC_API int rgc_kf_detect_loop(rgc_ctx* ctx, const rgc_kf_loop_params* params, rgc_kf_loop_candidate* out, int* history_ids, int cap, int* n_history);
 /* rgc_mapreg_set_maps for maps that lie on the context's device (what rgc_kf_assemble(..., on_device = 1) wrote): the same checks, the same
  * grids, bit for bit, minus the upload.  The buffers are read in stream order on rgc_stream(ctx) and not kept. */
 RGC_API int rgc_mapreg_set_maps_device(rgc_ctx* ctx, const float* d_corner, int n_corner, const float* d_surf, int n_surf, int stride_bytes);

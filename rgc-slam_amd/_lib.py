@@ -114,6 +114,18 @@ class KfInfo(C.Structure):
 KF_CORNER, KF_SURF, KF_SCAN, KF_KINDS = 0, 1, 2, 3
 
 
+class KfLoopParams(C.Structure):
+    """rgc_kf_loop_params: the constants of detectLoopClosure (rgc_default_kf_loop_params)"""
+    _fields_ = [("history_search_radius", C.c_float), ("drift_factor", C.c_float), ("distance_by_loop", C.c_float), ("loop_keyframe_dis_diff", C.c_float),
+                ("history_search_num", C.c_int), ("min_key_id", C.c_int)]
+
+
+class KfLoopCandidate(C.Structure):
+    """rgc_kf_loop_candidate: what rgc_kf_detect_loop found"""
+    _fields_ = [("found", C.c_int), ("latest_id", C.c_int), ("closest_id", C.c_int), ("latest_pose", KfPose), ("closest_pose", KfPose),
+                ("search_radius", C.c_float), ("n_in_radius", C.c_int)]
+
+
 class PgoLoop(C.Structure):
     """rgc_pgo_loop: one loop edge of the 4-DoF pose graph (key_loop -> key_curr)"""
     _fields_ = [("key_curr", C.c_int), ("key_loop", C.c_int), ("t_loop_curr", C.c_double * 3), ("yaw_loop_curr_deg", C.c_double),
@@ -170,7 +182,7 @@ SYMBOLS = [
     "rgc_clear_source", "rgc_clear_target", "rgc_swap_source_and_target", "rgc_get_voxels",
     "rgc_get_stats", "rgc_device_alloc", "rgc_device_free", "rgc_host_alloc", "rgc_host_free", "rgc_upload", "rgc_download", "rgc_synchronize",
     "rgc_stream", "rgc_default_fe_params", "rgc_frontend", "rgc_extract_pose", "rgc_imu_preintegrate", "rgc_imu_filter_init", "rgc_imu_filter_push", "rgc_ground_gate_init", "rgc_ground_gate_remember", "rgc_ground_gate_step", "rgc_default_fuse_in", "rgc_fuse_pose", "rgc_compose_pose",
-    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_mapreg_linearize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_kf_reset", "rgc_kf_push", "rgc_kf_set_poses", "rgc_kf_get_info", "rgc_kf_assemble", "rgc_mapreg_set_maps_device", "rgc_icp_align_device",
+    "rgc_R2ypr", "rgc_ypr2R", "rgc_deskew", "rgc_voxelgrid", "rgc_voxelgrid_begin", "rgc_voxelgrid_end", "rgc_voxelgrid_route", "rgc_uniform_sampling", "rgc_transform_cloud", "rgc_set_target_reframed", "rgc_frontend_device", "rgc_frontend_cloud_device", "rgc_default_icp_params", "rgc_icp_align", "rgc_pc2_unpack", "rgc_pc2_pack", "rgc_pc2_point_fields", "rgc_tum_line", "rgc_pcd_write", "rgc_mapreg_set_maps", "rgc_mapreg_associate", "rgc_mapreg_optimize", "rgc_mapreg_linearize", "rgc_map_reset", "rgc_map_insert", "rgc_map_evict", "rgc_map_rebase", "rgc_map_commit", "rgc_map_get_info", "rgc_map_download", "rgc_kf_reset", "rgc_kf_push", "rgc_kf_set_poses", "rgc_kf_get_info", "rgc_kf_assemble", "rgc_kf_get_travel", "rgc_kf_select_surrounding", "rgc_kf_select_global", "rgc_default_kf_loop_params", "rgc_kf_detect_loop", "rgc_mapreg_set_maps_device", "rgc_icp_align_device",
     "rgc_default_pgo_params", "rgc_pgo_make_loop", "rgc_pgo_optimize", "rgc_pgo_linearize",
     "rgc_default_ndt_params", "rgc_ndt_set_params", "rgc_ndt_get_params", "rgc_ndt_set_target", "rgc_ndt_set_source", "rgc_ndt_set_target_device", "rgc_ndt_set_source_device", "rgc_ndt_clear_source", "rgc_ndt_clear_target", "rgc_ndt_swap_source_and_target", "rgc_ndt_linearize", "rgc_ndt_compute_error", "rgc_ndt_num_correspondences", "rgc_ndt_align", "rgc_ndt_get_voxels", "rgc_ndt_get_raw_covariances",
     "rgc_gicp_set_max_correspondence_distance", "rgc_gicp_get_max_correspondence_distance", "rgc_gicp_linearize", "rgc_gicp_compute_error", "rgc_gicp_num_correspondences", "rgc_gicp_get_correspondences", "rgc_gicp_align",
@@ -321,6 +333,7 @@ def load():
     L.rgc_voxelgrid_begin.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp]
     L.rgc_voxelgrid_end.argtypes = [vp, ip]
     L.rgc_voxelgrid_route.argtypes = [vp, C.POINTER(VgRoute)]
+    L.rgc_uniform_sampling.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, ip, C.c_int]
     L.rgc_transform_cloud.argtypes = [vp, vp, C.c_int, C.c_int, dp, dp, vp, C.c_int]
     L.rgc_set_target_reframed.argtypes = [vp, vp, C.c_int, C.c_int, dp, dp, vp]
     L.rgc_default_icp_params.argtypes = [C.POINTER(IcpParams)]
@@ -350,6 +363,12 @@ def load():
     L.rgc_kf_set_poses.argtypes = [vp, ip, C.POINTER(KfPose), C.c_int]
     L.rgc_kf_get_info.argtypes = [vp, C.POINTER(KfInfo)]
     L.rgc_kf_assemble.argtypes = [vp, ip, C.c_int, C.c_uint, C.c_float, vp, C.c_int, C.c_int, ip, ip]
+    L.rgc_kf_get_travel.argtypes = [vp, ip, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.rgc_kf_select_surrounding.argtypes = [vp, C.POINTER(C.c_float), C.c_float, C.c_float, ip, C.c_int, ip, ip]
+    L.rgc_kf_select_global.argtypes = [vp, C.c_float, ip, C.c_int, ip]
+    L.rgc_default_kf_loop_params.argtypes = [C.POINTER(KfLoopParams)]
+    L.rgc_default_kf_loop_params.restype = None
+    L.rgc_kf_detect_loop.argtypes = [vp, C.POINTER(KfLoopParams), C.POINTER(KfLoopCandidate), ip, C.c_int, ip]
     L.rgc_mapreg_set_maps_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int]
     L.rgc_icp_align_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(IcpParams), fp, C.POINTER(IcpResult)]
     L.rgc_default_pgo_params.argtypes = [C.POINTER(PgoParams)]

@@ -10,6 +10,8 @@
 //   rgc_icp_align_device(ctx, source.data(), source.size(), target.data(), target.size(), 16, &icp_params, T, &result);
 //   loops.push_back(rgc::makeLoop(latestPose, loopPose, T, latestId, loopId));            // the loop edge of :2086-2107
 //   rgc_pgo_report rep = store.optimizePoseGraph(ids, loops);                             // PoseGraphOptimize4DoF (:2303-2466): the poses are corrected
+//   rgc::LoopDetection d = store.detectLoop();            // detectLoopClosure (:2141-2225): which pair, which history keyframes
+//   std::vector<int> near = store.selectSurrounding(x, y, z, 15.f, 0.3f), all = store.selectGlobal(0.5f);   // (:1525-1548, 2493-2505)
 //
 // Errors throw std::runtime_error carrying rgc_last_error().  No CPU fallback.
 #pragma once
@@ -59,6 +61,25 @@ inline rgc_pgo_loop makeLoop(const rgc_kf_pose& latest_pose, const rgc_kf_pose& 
   return l;
 }
 
+// pcl::UniformSampling on the device (rgc_uniform_sampling): per occupied leaf the point of the host cloud nearest the leaf's centre, leaves in ascending
+// leaf index; n x 4 floats {x, y, z, c} and, when asked for, the winners' input indices
+inline std::vector<float> uniformSampling(rgc_ctx* ctx, const float* xyzc, int n, int stride_bytes, float leaf, std::vector<int>* index = nullptr) {
+  std::vector<float> out((std::size_t)(n > 0 ? n : 1) * 4);
+  if (index) index->assign((std::size_t)(n > 0 ? n : 1), 0);
+  int n_out = 0;
+  const int rc = rgc_uniform_sampling(ctx, xyzc, n, stride_bytes, leaf, out.data(), index ? index->data() : nullptr, &n_out, 0);
+  if (rc != RGC_OK) throw std::runtime_error(std::string("rgc_uniform_sampling: ") + rgc_status_string(rc) + ": " + rgc_last_error(ctx));
+  out.resize((std::size_t)n_out * 4);
+  if (index) index->resize((std::size_t)n_out);
+  return out;
+}
+
+// what rgc::KeyframeStore::detectLoop returns: the candidate and the history keyframes (the ICP target's ids, in order)
+struct LoopDetection {
+  rgc_kf_loop_candidate candidate;
+  std::vector<int> history_ids;
+};
+
 class KeyframeStore {
 public:
   enum Kind : unsigned { CORNER = 1u << RGC_KF_CORNER, SURF = 1u << RGC_KF_SURF, SCAN = 1u << RGC_KF_SCAN };
@@ -98,6 +119,44 @@ public:
     chk(rgc_kf_set_poses(ctx_, ids.data(), poses.data(), (int)ids.size()));
   }
   rgc_kf_info info() { rgc_kf_info i; chk(rgc_kf_get_info(ctx_, &i)); return i; }
+
+  // travelled distance / accumulated |yaw change| up to each keyframe, fixed at its push (:1887-1908); either output nullable
+  void travel(const std::vector<int>& ids, std::vector<float>* distance, std::vector<float>* angle = nullptr) {
+    if (distance) distance->assign(ids.size(), 0.f);
+    if (angle) angle->assign(ids.size(), 0.f);
+    chk(rgc_kf_get_travel(ctx_, ids.data(), (int)ids.size(), distance && !ids.empty() ? distance->data() : nullptr, angle && !ids.empty() ? angle->data() : nullptr));
+  }
+  // extractSurroundingKeyFramesAndMap's selection (:1525-1548): the key poses strictly within `radius` of the centre, thinned by UniformSampling at leaf
+  // `density`; ids in ascending leaf index.  n_in_radius (nullable): poses inside the radius
+  std::vector<int> selectSurrounding(float x, float y, float z, float radius = 15.f, float density = 0.3f, int* n_in_radius = nullptr) {
+    const float c[3] = {x, y, z};
+    std::vector<int> out((std::size_t)info().n_keyframes + 1);
+    int n_in = 0, n_out = 0;
+    chk(rgc_kf_select_surrounding(ctx_, c, radius, density, out.data(), (int)out.size(), &n_in, &n_out));
+    out.resize((std::size_t)n_out);
+    if (n_in_radius) *n_in_radius = n_in;
+    return out;
+  }
+  // publishGlobalMap's selection (:2493-2505): UniformSampling of every key position
+  std::vector<int> selectGlobal(float pose_density = 0.5f) {
+    std::vector<int> out((std::size_t)info().n_keyframes + 1);
+    int n_out = 0;
+    chk(rgc_kf_select_global(ctx_, pose_density, out.data(), (int)out.size(), &n_out));
+    out.resize((std::size_t)n_out);
+    return out;
+  }
+  // detectLoopClosure (:2141-2225) for the last keyframe pushed; params nullable: rgc_default_kf_loop_params
+  LoopDetection detectLoop(const rgc_kf_loop_params* params = nullptr) {
+    rgc_kf_loop_params p;
+    rgc_default_kf_loop_params(&p);
+    if (params) p = *params;
+    LoopDetection d;
+    d.history_ids.resize((std::size_t)info().n_keyframes + 1);
+    int n_history = 0;
+    chk(rgc_kf_detect_loop(ctx_, &p, &d.candidate, d.history_ids.data(), (int)d.history_ids.size(), &n_history));
+    d.history_ids.resize((std::size_t)n_history);
+    return d;
+  }
 
   // PoseGraphOptimize4DoF (:2303-2466) over the keyframes `ids` in that order; apply: the store's poses are corrected (all or nothing);
   // corrected (nullable): the ids.size() corrected poses either way; params (nullable): Ceres' iteration cap and initial radius

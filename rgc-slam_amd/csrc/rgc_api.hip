@@ -1256,7 +1256,8 @@ void rgc_destroy(rgc_ctx* c) {
   release(c->fit_partials);
   if (c->vg_done) (void)hipEventDestroy(c->vg_done);
   if (c->h_vg) (void)hipHostFree(c->h_vg);
-  for (DevBuf* b : {&c->kf_store[0], &c->kf_store[1], &c->kf_store[2], &c->kf_table, &c->kf_raw, &c->kf_filt}) release(*b);
+  for (DevBuf* b : {&c->kf_store[0], &c->kf_store[1], &c->kf_store[2], &c->kf_table, &c->kf_raw, &c->kf_filt, &c->us_index, &c->kf_pos, &c->kf_travel,
+                    &c->kf_ids, &c->kf_flag, &c->kf_scan, &c->kf_bsum, &c->kf_sel, &c->kf_sel_out, &c->kf_small}) release(*b);
   if (c->kf_h_table) (void)hipHostFree(c->kf_h_table);
   for (DevBuf* b : {&c->pgo_i, &c->pgo_d, &c->pgo_M}) release(*b);
   release_cloud(c->ndt_cl[0]);

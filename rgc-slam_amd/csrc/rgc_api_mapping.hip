@@ -867,6 +867,17 @@ int rgc_kf_push(rgc_ctx* c, int id, const rgc_kf_pose* pose, const float* corner
   rec.id = id;
   rec.pose = *pose;
   rgc_host_key_pose_quat(pose->roll, pose->pitch, pose->yaw, rec.q);
+  // travel_distance / travel_angle (:1887-1908), fp32, against the pose stored NOW for the previous position (cloudKeyPoses6D->back(), corrected or
+  // not); never recomputed afterwards
+  if (!c->kf.empty()) {
+    const rgc_ctx::KfRec& last = c->kf.back();
+    const float dx = pose->x - last.pose.x, dy = pose->y - last.pose.y, dz = pose->z - last.pose.z;
+    rec.travel = last.travel + sqrtf((dx * dx + dy * dy) + dz * dz);
+    float rad_delta = pose->yaw - last.pose.yaw;
+    if (rad_delta > M_PI) rad_delta = rad_delta - M_PI * 2;    // (float op double: in double, stored as float, :1904-1905)
+    if (rad_delta < -M_PI) rad_delta = rad_delta + M_PI * 2;
+    rec.travel_angle = last.travel_angle + fabsf(rad_delta);
+  }
   bool copied = false;
   for (int k = 0; k < RGC_KF_KINDS; k++) {
     rec.off[k] = c->kf_n[k];
@@ -906,6 +917,190 @@ int rgc_kf_get_info(rgc_ctx* c, rgc_kf_info* out) {
   out->n_keyframes = (int)c->kf.size();
   for (int k = 0; k < RGC_KF_KINDS; k++) out->n_points[k] = (long long)c->kf_n[k];
   out->revision = c->kf_rev;
+  return RGC_OK;
+}
+
+int rgc_kf_get_travel(rgc_ctx* c, const int* ids, int n, float* distance, float* angle) {
+  if (!c || n < 0 || (n && !ids)) return RGC_ERR_INVALID;
+  for (int i = 0; i < n; i++)
+    if (!c->kf_index.count(ids[i])) return fail(c, RGC_ERR_INVALID, "rgc_kf_get_travel: keyframe %d is not in the store", ids[i]);
+  for (int i = 0; i < n; i++) {
+    const rgc_ctx::KfRec& r = c->kf[c->kf_index[ids[i]]];
+    if (distance) distance[i] = r.travel;
+    if (angle) angle[i] = r.travel_angle;
+  }
+  return RGC_OK;
+}
+
+}  // extern "C"
+
+// ---- the selections: which keyframes to assemble (extractSurroundingKeyFramesAndMap :1525-1548, detectLoopClosure :2141-2225, publishGlobalMap
+// :2493-2505).  One gate launch over the device mirror of the key positions, then UniformSampling's chain or a 64-bit minimum. ----
+static int kf_mirror(rgc_ctx* c) {   // the mirror holds the store's current revision on return
+  const size_t n = c->kf.size();
+  if (c->kf_mirror_rev == c->kf_rev && c->kf_pos.p) return RGC_OK;
+  int rc;
+  if ((rc = ensure(c, c->kf_pos, 16 * n)) || (rc = ensure(c, c->kf_travel, 4 * n)) || (rc = ensure(c, c->kf_ids, 4 * n))) return rc;
+  std::vector<float> hp(4 * n), ht(n);
+  std::vector<int> hi(n);
+  for (size_t p = 0; p < n; p++) {
+    const rgc_ctx::KfRec& r = c->kf[p];
+    const int pi = (int)p;
+    hp[4 * p] = r.pose.x; hp[4 * p + 1] = r.pose.y; hp[4 * p + 2] = r.pose.z;
+    memcpy(&hp[4 * p + 3], &pi, 4);   // the position's bits: the fourth float is only ever copied
+    ht[p] = r.travel;
+    hi[p] = r.id;
+  }
+  HIPCHK(c, hipMemcpyAsync(c->kf_pos.p, hp.data(), 16 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->kf_travel.p, ht.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->kf_ids.p, hi.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->kf_mirror_rev = c->kf_rev;
+  return RGC_OK;
+}
+// the gate of every selection: r2 = (float)((double)radius * (double)radius), inside when dist2 < r2 (strict)
+static float kf_gate_r2(float radius) { return (float)((double)radius * (double)radius); }
+// gate launch over the mirror; small4 <- {number inside, 0, the loop search's minimum (two words)}.  flags: the in-radius flags are kept for a compaction
+static int kf_run_gate(rgc_ctx* c, const float q[3], float r2, int loop, float travel_last, float thr, int min_id, bool flags, unsigned small4[4]) {
+  const int n = (int)c->kf.size();
+  int rc;
+  if ((rc = ensure(c, c->kf_small, 16))) return rc;
+  if (flags && (rc = ensure(c, c->kf_flag, 4 * (size_t)n))) return rc;
+  const unsigned init[4] = {0u, 0u, ~0u, ~0u};
+  HIPCHK(c, hipMemcpyAsync(c->kf_small.p, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+  rgck::kf_gate(c->stream, c->kf_pos.as<const float4>(), c->kf_travel.as<const float>(), c->kf_ids.as<const int>(), n, q, r2, loop, travel_last, thr, min_id,
+                flags ? c->kf_flag.as<int>() : nullptr, c->kf_small.as<unsigned>());
+  HIPCHK(c, hipMemcpyAsync(small4, c->kf_small.p, 16, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+// UniformSampling of m device points {x, y, z, position} at leaf `density`; the winners' ids in ascending leaf index
+static int kf_sample_ids(rgc_ctx* c, const float* d_pts, int m, float density, int* out_ids, int cap, int* n_out, const char* who) {
+  int rc;
+  if ((rc = ensure(c, c->kf_sel_out, 16 * (size_t)m))) return rc;
+  rgc_vg_route rt{};
+  rt.n = m;
+  int no = 0;
+  rc = voxelgrid_run(c, d_pts, m, 16, density, c->kf_sel_out.as<float>(), &no, 1, rt, rgck::kVgModePick, nullptr);
+  rt.status = rc;
+  rt.n_out = no;
+  c->vg_route = rt;
+  if (rc) return rc;
+  *n_out = no;
+  if (no > cap) return fail(c, RGC_ERR_INVALID, "%s: %d keyframes selected, room for %d", who, no, cap);
+  std::vector<float> h(4 * (size_t)no);
+  if (no) HIPCHK(c, hipMemcpyAsync(h.data(), c->kf_sel_out.p, 16 * (size_t)no, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int j = 0; j < no; j++) {
+    int p;
+    memcpy(&p, &h[4 * (size_t)j + 3], 4);
+    if (p < 0 || p >= (int)c->kf.size()) return fail(c, RGC_ERR_HIP, "%s: the sampling returned position %d of %d", who, p, (int)c->kf.size());
+    out_ids[j] = c->kf[p].id;
+  }
+  return RGC_OK;
+}
+
+extern "C" {
+
+int rgc_kf_select_surrounding(rgc_ctx* c, const float center[3], float radius, float density, int* out_ids, int cap, int* n_in_radius, int* n_out) {
+  if (!c || !center || !n_in_radius || !n_out || cap < 0 || (cap && !out_ids)) return RGC_ERR_INVALID;
+  *n_in_radius = *n_out = 0;
+  if (!std::isfinite(center[0]) || !std::isfinite(center[1]) || !std::isfinite(center[2]) || !std::isfinite(radius) || !std::isfinite(density) || !(radius > 0.f) ||
+      !(density > 0.f))
+    return fail(c, RGC_ERR_INVALID, "rgc_kf_select_surrounding: the centre, radius > 0 and density > 0 must be finite");
+  const int n = (int)c->kf.size();
+  if (n == 0) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = kf_mirror(c))) return rc;
+  unsigned small4[4];
+  if ((rc = kf_run_gate(c, center, kf_gate_r2(radius), 0, 0.f, 0.f, 0, true, small4))) return rc;
+  const int m = (int)small4[0];
+  *n_in_radius = m;
+  if (m == 0) { rgc_vg_route rt{}; c->vg_route = rt; return RGC_OK; }
+  if ((rc = ensure(c, c->kf_scan, 4 * (size_t)n)) || (rc = ensure(c, c->kf_bsum, 4 * ((size_t)n / 2048 + 2))) || (rc = ensure(c, c->kf_sel, 16 * (size_t)m))) return rc;
+  rgck::exclusive_scan(c->stream, c->kf_flag.as<const int>(), c->kf_scan.as<int>(), n, c->kf_bsum.as<int>());
+  rgck::kf_compact(c->stream, c->kf_pos.as<const float4>(), c->kf_flag.as<const int>(), c->kf_scan.as<const int>(), n, c->kf_sel.as<float4>());
+  HIPCHK(c, hipGetLastError());
+  return kf_sample_ids(c, c->kf_sel.as<const float>(), m, density, out_ids, cap, n_out, "rgc_kf_select_surrounding");
+}
+
+int rgc_kf_select_global(rgc_ctx* c, float pose_density, int* out_ids, int cap, int* n_out) {
+  if (!c || !n_out || cap < 0 || (cap && !out_ids)) return RGC_ERR_INVALID;
+  *n_out = 0;
+  if (!std::isfinite(pose_density) || !(pose_density > 0.f)) return fail(c, RGC_ERR_INVALID, "rgc_kf_select_global: the density must be finite and > 0");
+  const int n = (int)c->kf.size();
+  if (n == 0) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = kf_mirror(c))) return rc;
+  return kf_sample_ids(c, c->kf_pos.as<const float>(), n, pose_density, out_ids, cap, n_out, "rgc_kf_select_global");
+}
+
+void rgc_default_kf_loop_params(rgc_kf_loop_params* p) {
+  if (!p) return;
+  p->history_search_radius = 5.0f;    // historyKeyframeSearchRadius, :155
+  p->drift_factor = 0.02f;            // DRIFT_FACTOR, :159
+  p->distance_by_loop = 0.0f;         // DistanceByLoop, :158 (the caller's state, :2130-2135)
+  p->loop_keyframe_dis_diff = 20.0f;  // loopKeyframeDisDiff, :160
+  p->history_search_num = 50;         // historyKeyframeSearchNum, :157
+  p->min_key_id = 10;                 // :2166
+}
+
+int rgc_kf_detect_loop(rgc_ctx* c, const rgc_kf_loop_params* prm, rgc_kf_loop_candidate* out, int* history_ids, int cap, int* n_history) {
+  if (!c || !prm || !out || !n_history || cap < 0 || (cap && !history_ids)) return RGC_ERR_INVALID;
+  memset(out, 0, sizeof(*out));
+  out->latest_id = out->closest_id = -1;
+  *n_history = 0;
+  if (!std::isfinite(prm->history_search_radius) || !std::isfinite(prm->drift_factor) || !std::isfinite(prm->distance_by_loop) ||
+      !std::isfinite(prm->loop_keyframe_dis_diff) || prm->history_search_num < 0)
+    return fail(c, RGC_ERR_INVALID, "rgc_kf_detect_loop: the parameters must be finite, history_search_num >= 0");
+  const int n = (int)c->kf.size();
+  if (n == 0) return RGC_OK;
+  const int L = n - 1;
+  const rgc_ctx::KfRec& last = c->kf[L];
+  // poseGraphSearchRadius (:2148) in fp32; the search takes its square, the travel threshold its signed value (:2164)
+  const float R = prm->history_search_radius + (last.travel - prm->distance_by_loop) * prm->drift_factor;
+  const float thr = prm->loop_keyframe_dis_diff + R;
+  if (!std::isfinite(R) || !std::isfinite(thr)) return fail(c, RGC_ERR_INVALID, "rgc_kf_detect_loop: the search radius is not finite");
+  out->latest_id = last.id;
+  out->latest_pose = last.pose;
+  out->search_radius = R;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = kf_mirror(c))) return rc;
+  const float q[3] = {last.pose.x, last.pose.y, last.pose.z};
+  unsigned small4[4];
+  if ((rc = kf_run_gate(c, q, kf_gate_r2(R), 1, last.travel, thr, prm->min_key_id, false, small4))) return rc;
+  out->n_in_radius = (int)small4[0];
+  if (small4[2] == ~0u && small4[3] == ~0u) return RGC_OK;   // nothing qualifies
+  const int pc = (int)small4[2];                                // (little endian: the low word is the position)
+  if (pc < 0 || pc >= n) return fail(c, RGC_ERR_HIP, "rgc_kf_detect_loop: the search returned position %d of %d", pc, n);
+  const rgc_ctx::KfRec& cl = c->kf[pc];
+  out->closest_id = cl.id;
+  out->closest_pose = cl.pose;
+  if (cl.id == last.id) return RGC_OK;
+  // the history window (:2195-2216): positions either side of the closest one, before the latest, ids in [0, latest id)
+  int nh = 0;
+  long long pts = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    nh = 0;
+    for (long long i = -(long long)prm->history_search_num; i <= (long long)prm->history_search_num; i++) {
+      const long long p = (long long)pc + i;
+      if (p < 0 || p >= L) continue;
+      const rgc_ctx::KfRec& r = c->kf[(size_t)p];
+      if (r.id < 0 || r.id >= last.id) continue;
+      if (pass == 0) pts += (long long)r.n[0] + (long long)r.n[1];
+      else history_ids[nh] = r.id;
+      nh++;
+    }
+    if (pass == 0) {
+      *n_history = nh;
+      if (nh > cap) return fail(c, RGC_ERR_INVALID, "rgc_kf_detect_loop: %d history keyframes, room for %d", nh, cap);
+    }
+  }
+  out->found = pts > 0 ? 1 : 0;    // an empty nearHistoryKeyFrameCloud: no loop (:2218)
   return RGC_OK;
 }
 

@@ -256,7 +256,8 @@ int rgc_align_end_reframe(rgc_ctx* c, rgc_ctx* next, double Tw[16], const float*
 // h_result (nullable): the chain is only ENQUEUED -- its three result ints go to h_result (pinned), c->vg_done is recorded behind the
 // copy, and the caller picks them up later (rgc_voxelgrid_begin / _end); flags / n_out are not written then.
 static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, float inv, const rgck::LeafGrid& g, int edge, bool dense, float* d_out,
-                          int* flags, int* n_out, rgc_vg_route* rt, int* h_result = nullptr) {
+                          int* flags, int* n_out, rgc_vg_route* rt, int* h_result = nullptr, int mode = rgck::kVgModeCentroid, float leaf = 0.f,
+                          int* d_index = nullptr) {
   hipStream_t s = c->stream;
   int* const d_res = c->d_small->leaf_rows.res;        // rgck::vg_rows' res[3]; res[1], the live flag word, is the block's guard
   const int* const h_res = c->h_small->leaf_rows.res;
@@ -294,7 +295,7 @@ static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, fl
   c->vg_flags_clean = false;
   const bool packed = rgck::vg_rows(s, d_in, stride_f, n, inv, g, edge, seg_shift, cl.cell_of.as<int>(), cl.slot_of.as<int>(), c->vg_pos.as<int>(), cl.cnt.as<int>(),
                                     cl.start.as<int>(), cl.block_sums.p, c->vg_tmp.as<unsigned long long>(), c->vg_order.as<int>(), c->vg_leaf.as<unsigned long long>(),
-                                    (int*)(cl.block_sums.as<char>() + row_bs), d_out, d_res);
+                                    (int*)(cl.block_sums.as<char>() + row_bs), d_out, d_res, mode, leaf, d_index);
   rt->chain = 1; rt->leaf_buckets = dense ? 1 : 0; rt->seg_shift = seg_shift; rt->nseg = rgck::vg_segments(g, seg_shift); rt->packed = packed ? 1 : 0;
   rt->edge = edge; rt->flags = 0;
   for (int a = 0; a < 3; a++) { rt->minb[a] = g.minb[a]; rt->div[a] = g.div[a]; }
@@ -317,7 +318,8 @@ static bool vg_rows_fit(const rgck::LeafGrid& g, int n) {  // sparse enough for 
   return ncell <= 2147483647.0 && ncell > 64.0 * (double)n && nrows <= 64.0e6;
 }
 
-int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt) {
+int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt,
+                          int mode, int* out_index) {
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const float* d_in;
@@ -331,6 +333,12 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
   if (!on_device) {
     if ((rc = ensure(c, c->pre_out, sizeof(float) * 4 * (size_t)n))) return rc;
     d_out = c->pre_out.as<float>();
+  }
+  // UniformSampling (mode = kVgModePick): the winners' input indices beside the points, staged like them for a host caller
+  int* d_index = mode == rgck::kVgModePick ? out_index : nullptr;
+  if (d_index && !on_device) {
+    if ((rc = ensure(c, c->us_index, sizeof(int) * (size_t)n))) return rc;
+    d_index = c->us_index.as<int>();
   }
   // leaves added on every side of a measured box when the next cloud of this leaf size is filtered on it: 32 for a sweep (its rows are
   // what is counted and scanned), 8 for a dense cloud (its leaves are: a wider box is a longer scan)
@@ -353,7 +361,7 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
       int flags = 0, no = 0;
       rt.kept_box = 1;
       rt.path = RGC_VG_PATH_KEPT;
-      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, sparse ? ps : pd, (sparse ? kPadSparse : kPadDense) / 2, !sparse, d_out, &flags, &no, &rt))) return rc;
+      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, sparse ? ps : pd, (sparse ? kPadSparse : kPadDense) / 2, !sparse, d_out, &flags, &no, &rt, nullptr, mode, leaf, d_index))) return rc;
       rt.kept_flags = flags;
       if (flags & 1) return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)");
       if (flags & 6) { box->valid = false; rt.box_invalidated = 1; }  // outside: measure and repeat now; near a face: measure at the next call
@@ -387,23 +395,25 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
     if (ncell > 2147483647.0) {
       // PCL: "Leaf size is too small for the input dataset. Integer indices would overflow." -> output = input
       rt.path = RGC_VG_PATH_UNFILTERED;
-      rgck::transform_q(s, d_in, stride_f, n, rgck::Quat{0, 0, 0, 1}, (const double[3]){0, 0, 0}, d_out, 4);
+      if (mode == rgck::kVgModePick) rgck::us_copy(s, d_in, stride_f, n, d_out, d_index);
+      else rgck::transform_q(s, d_in, stride_f, n, rgck::Quat{0, 0, 0, 1}, (const double[3]){0, 0, 0}, d_out, 4);
       *n_out = n;
       HIPCHK(c, hipStreamSynchronize(s));
     } else if (vg_rows_fit(g, n)) {
       int flags = 0;
-      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, false, d_out, &flags, n_out, &rt))) return rc;
+      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, false, d_out, &flags, n_out, &rt, nullptr, mode, leaf, d_index))) return rc;
       hint_from_leaf_grid(c, out_xyzi, *n_out, g, leaf);
     } else {
       // a dense cloud: the same chain with the leaves themselves as the sort's buckets
       if (ncell > (double)c->prm.max_cells) return fail(c, RGC_ERR_GRID_TOO_LARGE, "leaf grid %d x %d x %d exceeds max_cells", g.div[0], g.div[1], g.div[2]);
       int flags = 0;
-      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, true, d_out, &flags, n_out, &rt))) return rc;
+      if ((rc = voxelgrid_rows(c, d_in, stride_f, n, inv, g, 0, true, d_out, &flags, n_out, &rt, nullptr, mode, leaf, d_index))) return rc;
       hint_from_leaf_grid(c, out_xyzi, *n_out, g, leaf);
     }
   }
   if (!on_device) {
     HIPCHK(c, hipMemcpyAsync(out_xyzi, d_out, sizeof(float) * 4 * (size_t)*n_out, hipMemcpyDeviceToHost, s));
+    if (d_index) HIPCHK(c, hipMemcpyAsync(out_index, d_index, sizeof(int) * (size_t)*n_out, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
   }
   HIPCHK(c, hipGetLastError());
@@ -419,6 +429,22 @@ int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float 
   rgc_vg_route rt{};
   rt.n = n;
   const int rc = n == 0 ? RGC_OK : voxelgrid_run(c, xyzi, n, stride_bytes, leaf, out_xyzi, n_out, on_device, rt);
+  rt.status = rc;
+  rt.n_out = *n_out;
+  c->vg_route = rt;
+  return rc;
+}
+
+// pcl::UniformSampling: rgc_voxelgrid's chain with another last launch (rgck::k_us_rows_pick) -- the same routes, the same refusals
+int rgc_uniform_sampling(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, float leaf, float* out_xyzc, int* out_index, int* n_out, int on_device) {
+  if (!c || !xyzc || !out_xyzc || !n_out || n < 0) return RGC_ERR_INVALID;
+  if (!stride_ok(stride_bytes) || !(leaf > 0.f) || !std::isfinite(leaf)) return fail(c, RGC_ERR_INVALID, "bad stride or leaf size");
+  *n_out = 0;
+  rgc_vg_route rt{};
+  rt.n = n;
+  int rc = RGC_OK;
+  if (n > 0 && on_device && out_index) rc = check_device_range(c, out_index, sizeof(int) * (size_t)n, "rgc_uniform_sampling: out_index");
+  if (n > 0 && !rc) rc = voxelgrid_run(c, xyzc, n, stride_bytes, leaf, out_xyzc, n_out, on_device, rt, rgck::kVgModePick, out_index);
   rt.status = rc;
   rt.n_out = *n_out;
   c->vg_route = rt;

@@ -233,6 +233,7 @@ struct rgc_ctx {
   double src_res_auto = 0.0;  // adaptive cell size of the scan's kNN grid, steered by how crowded its cells were in the previous frame (0 = voxel_res)
   Cloud aux;                  // grid scratch of rgc_voxelgrid
   DevBuf pre_in, pre_out, vg_order, vg_pos, vg_tmp, vg_leaf;  // B2/B3/B9 staging
+  DevBuf us_index;            // rgc_uniform_sampling: the winners' indices of a host caller
   struct VgBox { float leaf = 0.f; bool valid = false; rgck::LeafGrid g{}; } vg_box[4];  // measured leaf boxes of earlier clouds, by leaf size
   int vg_box_next = 0;
   // Bounding boxes the library knows WITHOUT measuring: rgc_set_target_reframed maps the input's box (measured once per input buffer)
@@ -281,7 +282,8 @@ struct rgc_ctx {
   // f5: the mapping node's keyframe store.  Body-frame points (x,y,z,c, 16 B) per kind in kf_store[kind], a keyframe's clouds as one
   // contiguous run each; the key poses (and the quaternions the reference's chain makes of them) stay on the host and travel with every
   // assembly's segment table.
-  struct KfRec { int id; size_t off[RGC_KF_KINDS]; int n[RGC_KF_KINDS]; rgc_kf_pose pose; double q[4]; };
+  struct KfRec { int id; size_t off[RGC_KF_KINDS]; int n[RGC_KF_KINDS]; rgc_kf_pose pose; double q[4];
+                 float travel, travel_angle; };  // travelled distance / angle up to this keyframe, fixed at its push (src/RGC_mapping.cpp:1887-1908)
   DevBuf kf_store[RGC_KF_KINDS];
   size_t kf_n[RGC_KF_KINDS] = {0, 0, 0};
   std::vector<KfRec> kf;
@@ -292,6 +294,10 @@ struct rgc_ctx {
   size_t kf_h_cap = 0;
   hipEvent_t kf_uploaded = nullptr;        // recorded behind the table's copy: the staging is rewritten only after it
   bool kf_upload_pending = false;
+  // the selections (rgc_kf_select_*, rgc_kf_detect_loop): a device mirror of the key positions, float4 {x, y, z, position}, with the travelled
+  // distances and the ids beside it -- uploaded when the store's revision has moved since the last upload -- and the selections' scratch
+  DevBuf kf_pos, kf_travel, kf_ids, kf_flag, kf_scan, kf_bsum, kf_sel, kf_sel_out, kf_small;
+  unsigned long long kf_mirror_rev = ~0ull;   // the revision the mirror holds
   // the 4-DoF pose graph over the store's key poses (rgc_pgo_*): buffers of its own -- the graph's index tables, every double array of a solve
   // (two evaluations: the accepted state and the candidate), the separators' dense system
   DevBuf pgo_i, pgo_d, pgo_M;
@@ -382,7 +388,8 @@ inline bool pose12_finite(const T* m) {
 // ---- rgc_api_pre.hip ----
 int stage_in(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, const float** d_in);
 // rgc_voxelgrid after its argument checks; rt: what rgc_voxelgrid_route reports, filled as the call goes (the caller adds status and n_out)
-int voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt);
+int voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt,
+                  int mode = rgck::kVgModeCentroid, int* out_index = nullptr);  // mode = rgck::kVgModePick: UniformSampling, out_index (nullable) as out_xyzi
 void host_eig3_sym(const double S[6], double ev[3], double V[9]);  // Jacobi; eigenvalues ASCENDING, columns of V
 
 // ---- rgc_api_lsq.hip: the LM driver of every registration method ----

@@ -317,6 +317,13 @@ void transform_q(hipStream_t s, const float* in, int stride_f, int n, Quat q, co
 constexpr int kKfBlock = 256;
 struct KfSegment { const float4* src; int n; int out0; Quat q; double t[3]; };
 void kf_assemble(hipStream_t s, const KfSegment* seg, const int* blk0, int nseg, int nblocks, float4* out);
+// the keyframe selections' radius gate over the mirror of the key positions (pos[p] = {x, y, z, p}): flag[p] (nullable) = d2 < r2, small[0] += the
+// number inside; loop != 0: the 64-bit word at small + 2 takes the minimum of (bits of d2) << 32 | p over the positions that are inside, have
+// |travel[p] - travel_last| > thr and ids[p] >= min_id.  small: four words, {0, 0, ~0, ~0} on entry
+void kf_gate(hipStream_t s, const float4* pos, const float* travel, const int* ids, int n, const float q[3], float r2, int loop, float travel_last, float thr,
+             int min_id, int* flag, unsigned* small);
+// out[scan[p]] = pos[p] for every flagged p (scan = the exclusive scan of flag)
+void kf_compact(hipStream_t s, const float4* pos, const int* flag, const int* scan, int n, float4* out);
 // ---- 4-DoF pose graph over the key poses (rgc_pgo.hip; PoseGraphOptimize4DoF, src/RGC_mapping.cpp:2303-2466) ----
 // The graph on the device.  Positions 0 .. n_nodes - 1, 4 unknowns each {yaw in degrees, t}; edges: the n_nodes - 1 odometry edges e = n
 // (n -> n + 1), then the used loops; ij: 2 ints per edge, meas: 6 doubles per edge {m[3], rel_yaw, pitch, roll}; fixed: the constant
@@ -375,7 +382,12 @@ int vg_segments(const LeafGrid& g, int seg_shift);
 // returns true when the chain used the packed record (k_vg_rows_place<true> / k_vg_rows_rank<true>), false for the unpacked one
 bool vg_rows(hipStream_t s, const float* in, int stride_f, int n, float inv, LeafGrid g, int edge, int seg_shift, int* row_of, int* lx, int* slot_then_pos, int* cnt,
              int* start, void* row_block_sums, unsigned long long* tmp, int* order, unsigned long long* leaf, int* head_block_sums, float* out,
-             int* res);
+             int* res, int mode = 0, float leafsz = 0.f, int* out_index = nullptr);
+// mode of the chain's last launch: the leaf's centroid (pcl::VoxelGrid), or the member nearest the leaf's centre with its input index in
+// out_index (nullable) (pcl::UniformSampling; leafsz = the leaf size the centre is computed with)
+constexpr int kVgModeCentroid = 0, kVgModePick = 1;
+// UniformSampling's unfiltered copy: out = the points' bits, out_index (nullable) = the identity
+void us_copy(hipStream_t s, const float* in, int stride_f, int n, float* out, int* out_index);
 
 // ---- A1-A8 front-end (rgc_frontend.hip) ----
 int fe_blocks(int n);

@@ -39,4 +39,49 @@ void kf_assemble(hipStream_t s, const KfSegment* seg, const int* blk0, int nseg,
   if (nseg > 0 && nblocks > 0) hipLaunchKernelGGL(k_kf_assemble, dim3(nblocks), dim3(kKfBlock), 0, s, seg, blk0, nseg, out);
 }
 
+// ---- the mapping node's keyframe selections (src/RGC_mapping.cpp:1525-1548, 2141-2225, 2493-2505) over the device mirror of the key positions ----
+// One lane per store position p: d2 = (dx*dx + dy*dy) + dz*dz in fp32, uncontracted (flann::L2_Simple<float> [3P-memory]); inside = d2 < r2, strict.
+//   flag[p] (nullable) = inside, the input of the ordered compaction;  small[0] += the number inside (one add per wave);
+//   loop != 0: a position qualifies when it is inside, |travel[p] - travel_last| > thr and ids[p] >= min_id; the two words at small + 2 take the
+//   64-bit minimum of (bits of d2) << 32 | p -- d2 >= 0, so bit order is value order, and a minimum is the same in any arrival order.
+__global__ void __launch_bounds__(256) k_kf_gate(const float4* __restrict__ pos, const float* __restrict__ travel, const int* __restrict__ ids, int n, float qx,
+                                                 float qy, float qz, float r2, int loop, float travel_last, float thr, int min_id, int* __restrict__ flag,
+                                                 unsigned* small) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  bool inside = false;
+  unsigned long long key = ~0ull;
+  if (p < n) {
+    const float4 c = pos[p];
+    const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    inside = d2 < r2;
+    if (flag) flag[p] = inside ? 1 : 0;
+    if (loop && inside && fabsf(travel[p] - travel_last) > thr && ids[p] >= min_id) key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)p;
+  }
+  const unsigned long long m = __ballot(inside);
+  const int lane = threadIdx.x & 63;
+  if (m && lane == 0) atomicAdd(&small[0], (unsigned)__popcll(m));
+  if (loop) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(key, o);
+      key = other < key ? other : key;
+    }
+    if (lane == 0 && key != ~0ull) atomicMin(reinterpret_cast<unsigned long long*>(small + 2), key);
+  }
+}
+// the in-radius positions in ascending store position: out[scan[p]] = {x, y, z, position} of every flagged p
+__global__ void k_kf_compact(const float4* __restrict__ pos, const int* __restrict__ flag, const int* __restrict__ scan, int n, float4* __restrict__ out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < n && flag[p]) out[scan[p]] = pos[p];
+}
+
+void kf_gate(hipStream_t s, const float4* pos, const float* travel, const int* ids, int n, const float q[3], float r2, int loop, float travel_last, float thr,
+             int min_id, int* flag, unsigned* small) {
+  if (n > 0) hipLaunchKernelGGL(k_kf_gate, dim3((n + 255) / 256), dim3(256), 0, s, pos, travel, ids, n, q[0], q[1], q[2], r2, loop, travel_last, thr, min_id, flag, small);
+}
+void kf_compact(hipStream_t s, const float4* pos, const int* flag, const int* scan, int n, float4* out) {
+  if (n > 0) hipLaunchKernelGGL(k_kf_compact, dim3((n + 255) / 256), dim3(256), 0, s, pos, flag, scan, n, out);
+}
+
 }  // namespace rgck

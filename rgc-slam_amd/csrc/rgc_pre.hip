@@ -297,6 +297,68 @@ k_vg_rows_centroid(const float* __restrict__ in, int stride_f, int n, const int*
   o[0] = a0 / cnt; o[1] = a1 / cnt; o[2] = a2 / cnt; o[3] = a3 / cnt;
 }
 
+// pcl::UniformSampling (filters/impl/uniform_sampling.hpp [3P-memory]) as the SAME chain with another last launch: the leaf's head walks
+// its members in ascending point index and keeps the one nearest the leaf's centre,
+//   c_a = fp32(fp32((float)ijk_a + 0.5f) * leaf) from the GLOBAL ijk = floor(fp32(p * inv)) of the head's own point (every member's is the same),
+//   d2  = (dx*dx + dy*dy) + dz*dz in fp32, uncontracted (dist2 of rgc_nn.h),
+// replaced on strict < only: the winner is the smallest (d2, point index), PCL's rule for an input walked in order.  The winner's point goes out
+// unchanged ({x, y, z, c}, c = 0 for a 12-byte point) with its input index beside it, at the leaf's output number.  res[] as k_vg_rows_centroid.
+__global__ void __launch_bounds__(256)
+k_us_rows_pick(const float* __restrict__ in, int stride_f, int n, float inv, float leafsz, const int* __restrict__ order,
+               const unsigned long long* __restrict__ leaf, const int* __restrict__ pos, const int* __restrict__ block_sums, float* __restrict__ out,
+               int* __restrict__ out_index, int* res) {
+  __shared__ int part[256 / WAVE];
+  const int sb = (int)((blockIdx.x * 256u) / VG_SCAN_B);
+  int acc = 0;
+  for (int j = threadIdx.x; j < sb; j += 256) acc += block_sums[j];
+#pragma unroll
+  for (int o = WAVE / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = acc;
+  __syncthreads();
+  int pre = 0;
+#pragma unroll
+  for (int w = 0; w < 256 / WAVE; w++) pre += part[w];
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= n) return;
+  const unsigned long long me = leaf[s];
+  const bool head = s == 0 || leaf[s - 1] != me;
+  const int op = pos[s] + pre;
+  if (s == n - 1) {
+    res[2] = op + (head ? 1 : 0);
+    res[0] = res[1];
+    res[1] = 0;
+  }
+  if (!head) return;
+  int best = order[s];
+  const float* p = in + (size_t)best * stride_f;
+  float bx = p[0], by = p[1], bz = p[2];
+  const float cx = (floorf(bx * inv) + 0.5f) * leafsz, cy = (floorf(by * inv) + 0.5f) * leafsz, cz = (floorf(bz * inv) + 0.5f) * leafsz;
+  float dx = bx - cx, dy = by - cy, dz = bz - cz;
+  float bd = (dx * dx + dy * dy) + dz * dz;
+  for (int t = s + 1; t < n && leaf[t] == me; t++) {
+    const int i = order[t];
+    const float* q = in + (size_t)i * stride_f;
+    const float x = q[0], y = q[1], z = q[2];
+    dx = x - cx; dy = y - cy; dz = z - cz;
+    const float d = (dx * dx + dy * dy) + dz * dz;
+    if (d < bd) { bd = d; best = i; bx = x; by = y; bz = z; }
+  }
+  float* o = out + (size_t)op * 4;
+  o[0] = bx; o[1] = by; o[2] = bz;
+  o[3] = stride_f > 3 ? in[(size_t)best * stride_f + 3] : 0.f;
+  if (out_index) out_index[op] = best;
+}
+// the unfiltered copy of UniformSampling (a grid of more than INT_MAX leaves): the points' bits as they are, the identity beside them
+__global__ void k_us_copy(const float* __restrict__ in, int stride_f, int n, float* __restrict__ out, int* __restrict__ out_index) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* p = in + (size_t)i * stride_f;
+  float* o = out + (size_t)i * 4;
+  o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+  o[3] = stride_f > 3 ? p[3] : 0.f;
+  if (out_index) out_index[i] = i;
+}
+
 static inline int nblk(long long n, int t) { return (int)((n + t - 1) / t); }
 
 void deskew(hipStream_t s, float* xyzi, int stride_f, int n, Quat qinv, const double t[3]) {
@@ -311,7 +373,7 @@ void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int
 int vg_segments(const LeafGrid& g, int seg_shift) { return seg_shift >= 31 ? 1 : (int)(((long long)g.div[0] + (1ll << seg_shift) - 1) >> seg_shift); }
 bool vg_rows(hipStream_t s, const float* in, int stride_f, int n, float inv, LeafGrid g, int edge, int seg_shift, int* row_of, int* lx, int* slot_then_pos, int* cnt,
              int* start, void* row_block_sums, unsigned long long* tmp, int* order, unsigned long long* leaf, int* head_block_sums, float* out,
-             int* res) {
+             int* res, int mode, float leafsz, int* out_index) {
   const int nseg = vg_segments(g, seg_shift);
   const int nr1 = g.div[1] * g.div[2] * nseg + 1;
   hipLaunchKernelGGL(k_vg_rows_count, dim3(nblk(n, 256)), dim3(256), 0, s, in, stride_f, n, inv, g, edge, seg_shift, nseg, row_of, lx, cnt, slot_then_pos, res + 1);
@@ -325,8 +387,14 @@ bool vg_rows(hipStream_t s, const float* in, int stride_f, int n, float inv, Lea
     hipLaunchKernelGGL(k_vg_rows_rank<false>, dim3(nblk(n, 256)), dim3(256), 0, s, n, row_of, start, tmp, order, leaf);
   }
   hipLaunchKernelGGL(k_vg_rows_heads, dim3(nblk(n, VG_SCAN_B)), dim3(VG_SCAN_T), 0, s, leaf, n, slot_then_pos, head_block_sums);
-  hipLaunchKernelGGL(k_vg_rows_centroid, dim3(nblk(n, 256)), dim3(256), 0, s, in, stride_f, n, order, leaf, slot_then_pos, head_block_sums, out, res);
+  if (mode == kVgModePick)
+    hipLaunchKernelGGL(k_us_rows_pick, dim3(nblk(n, 256)), dim3(256), 0, s, in, stride_f, n, inv, leafsz, order, leaf, slot_then_pos, head_block_sums, out, out_index, res);
+  else
+    hipLaunchKernelGGL(k_vg_rows_centroid, dim3(nblk(n, 256)), dim3(256), 0, s, in, stride_f, n, order, leaf, slot_then_pos, head_block_sums, out, res);
   return packed;
+}
+void us_copy(hipStream_t s, const float* in, int stride_f, int n, float* out, int* out_index) {
+  if (n > 0) hipLaunchKernelGGL(k_us_copy, dim3(nblk(n, 256)), dim3(256), 0, s, in, stride_f, n, out, out_index);
 }
 
 

@@ -8,6 +8,14 @@ pcl::VoxelGrid (src/RGC_mapping.cpp:1503-1616 the surrounding maps of f1, :2180-
     target = store.assemble(history_ids, (KF_CORNER, KF_SURF), leaf=0.4, device=True)
     icp.setInputTarget(target)                               # rgc_icp_align_device: no download, no upload
 
+and with the three places where it finds WHICH keyframes to assemble with a kd-tree over the key poses and a pcl::UniformSampling
+(:1525-1548, 2141-2225, 2493-2505):
+
+    near = store.select_surrounding(position, 15.0, 0.3)     # ids: key poses within 15 m, thinned at 0.3 m
+    loop = store.detect_loop()                               # found, latest_id, closest_id, the poses, history_ids (the ICP target's keyframes)
+    everything = store.select_global(0.5)                    # ids of the global map's keyframes
+    distance, angle = store.travel(ids)                      # travelled distance / angle per keyframe, fixed at its push (:1887-1908)
+
 Nothing is computed on the CPU; without librgc_hip.so / an MI355X this raises."""
 from __future__ import annotations
 
@@ -131,6 +139,61 @@ class KeyframeStore:
         i = _lib.KfInfo()
         self._chk(self._L.rgc_kf_get_info(self._h, C.byref(i)))
         return dict(n_keyframes=i.n_keyframes, n_points=list(i.n_points), revision=i.revision)
+
+    def travel(self, ids):
+        """(distance, angle) float32 arrays: the travelled distance and accumulated |yaw change| up to each keyframe, fixed at its push
+        (src/RGC_mapping.cpp:1887-1908)"""
+        i = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        d, a = np.zeros(i.shape[0], np.float32), np.zeros(i.shape[0], np.float32)
+        fp = C.POINTER(C.c_float)
+        self._chk(self._L.rgc_kf_get_travel(self._h, i.ctypes.data_as(_ip) if i.shape[0] else None, i.shape[0], d.ctypes.data_as(fp), a.ctypes.data_as(fp)))
+        return d, a
+
+    def _n(self):
+        return self.info()["n_keyframes"]
+
+    def select_surrounding(self, center, radius=15.0, density=0.3, return_count=False):
+        """extractSurroundingKeyFramesAndMap's selection (:1525-1548): the ids of the key poses strictly within ``radius`` of ``center``, thinned by
+        UniformSampling at leaf ``density``, in ascending leaf index; with ``return_count`` also the number of poses inside the radius"""
+        q = np.ascontiguousarray(center, dtype=np.float32).ravel()
+        if q.shape[0] != 3:
+            raise RgcError(_lib.ERR_INVALID, "the centre is (x, y, z)")
+        cap = self._n()
+        out = np.empty(max(cap, 1), np.int32)
+        nin, no = C.c_int(0), C.c_int(0)
+        self._chk(self._L.rgc_kf_select_surrounding(self._h, q.ctypes.data_as(C.POINTER(C.c_float)), float(radius), float(density), out.ctypes.data_as(_ip), cap,
+                                                    C.byref(nin), C.byref(no)))
+        ids = out[:no.value].copy()
+        return (ids, nin.value) if return_count else ids
+
+    def select_global(self, pose_density=0.5):
+        """publishGlobalMap's selection (:2493-2505): UniformSampling of every key position at leaf ``pose_density``; ids in ascending leaf index"""
+        cap = self._n()
+        out = np.empty(max(cap, 1), np.int32)
+        no = C.c_int(0)
+        self._chk(self._L.rgc_kf_select_global(self._h, float(pose_density), out.ctypes.data_as(_ip), cap, C.byref(no)))
+        return out[:no.value].copy()
+
+    def detect_loop(self, **params):
+        """detectLoopClosure (:2141-2225) for the last keyframe pushed.  ``params`` override rgc_default_kf_loop_params (history_search_radius,
+        drift_factor, distance_by_loop, loop_keyframe_dis_diff, history_search_num, min_key_id).  Returns a dict: found, latest_id, closest_id,
+        latest_pose, closest_pose (6 floats each), search_radius, n_in_radius, history_ids (int32 array, the target's keyframes in order)."""
+        prm = _lib.KfLoopParams()
+        self._L.rgc_default_kf_loop_params(C.byref(prm))
+        for k, v in params.items():
+            if k not in dict(_lib.KfLoopParams._fields_):
+                raise RgcError(_lib.ERR_INVALID, f"no loop parameter {k}")
+            setattr(prm, k, v)
+        cap = min(self._n(), 2 * max(int(prm.history_search_num), 0) + 1)
+        hist = np.empty(max(cap, 1), np.int32)
+        cand, nh = _lib.KfLoopCandidate(), C.c_int(0)
+        self._chk(self._L.rgc_kf_detect_loop(self._h, C.byref(prm), C.byref(cand), hist.ctypes.data_as(_ip), cap, C.byref(nh)))
+        def pose(p):
+            return np.array([p.x, p.y, p.z, p.roll, p.pitch, p.yaw], np.float32)
+
+        return dict(found=bool(cand.found), latest_id=cand.latest_id, closest_id=cand.closest_id, latest_pose=pose(cand.latest_pose),
+                    closest_pose=pose(cand.closest_pose), search_radius=float(cand.search_radius), n_in_radius=cand.n_in_radius,
+                    history_ids=hist[:nh.value].copy())
 
     def optimize_pose_graph(self, ids, loops, apply=True, max_iterations=None, initial_radius=None):
         """PoseGraphOptimize4DoF (src/RGC_mapping.cpp:2303-2466) over the keyframes ``ids`` in one call: ``loops`` are ``_lib.PgoLoop`` records

@@ -54,6 +54,17 @@ class Preprocessor:
         self._chk(self._L.rgc_voxelgrid(self._h, a.ctypes.data, a.shape[0], a.strides[0], float(leaf), out.ctypes.data, C.byref(n), 0))
         return out[:n.value].copy()
 
+    def uniformSampling(self, xyzc, leaf, return_index=False):
+        """pcl::UniformSampling setRadiusSearch(leaf) + filter (RGC_mapping.cpp:1533-1536): per occupied leaf the input point nearest the leaf's
+        centre, leaves in ascending leaf index; (m, 4) float32, and the winners' input indices (m,) int32 with ``return_index``."""
+        a = np.ascontiguousarray(xyzc, dtype=np.float32)
+        out = np.empty((a.shape[0], 4), np.float32)
+        idx = np.empty(a.shape[0], np.int32)
+        n = C.c_int(0)
+        self._chk(self._L.rgc_uniform_sampling(self._h, a.ctypes.data, a.shape[0], a.strides[0], float(leaf), out.ctypes.data, idx.ctypes.data if return_index else None,
+                                               C.byref(n), 0))
+        return (out[:n.value].copy(), idx[:n.value].copy()) if return_index else out[:n.value].copy()
+
     def voxelGridRoute(self):
         """what the last voxelGridFilter on this object did (rgc_voxelgrid_route), as a dict of the rgc_vg_route fields"""
         r = _lib.VgRoute()

@@ -523,3 +523,16 @@ class PipelinedVGICP:
             g = T if next_guess is None else next_guess(i, T)
             out.append(T)
         return out
+
+
+def uniform_sampling(points, leaf, return_index=False, device: int = 0):
+    """pcl::UniformSampling on the device (rgc_uniform_sampling): per occupied leaf of size ``leaf`` the point of ``points`` (n, >=3) float32
+    nearest the leaf's centre, ties to the lower index, leaves in ascending leaf index.  Returns (m, 4) float32 {x, y, z, c} (the points
+    unchanged; c = 0 for 3-column input), with ``return_index`` also their indices (m,) int32.  One context per call: a caller with a stream
+    of clouds keeps an ``odometry.Preprocessor`` and calls its ``uniformSampling``."""
+    from .odometry import Preprocessor
+    pre = Preprocessor(device)
+    try:
+        return pre.uniformSampling(points, leaf, return_index)
+    finally:
+        pre.close()
