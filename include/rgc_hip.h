@@ -944,6 +944,56 @@ RGC_API int rgc_gicp_get_correspondences(rgc_ctx* ctx, int* idx, float* sq_dist)
 RGC_API int rgc_gicp_align(rgc_ctx* ctx, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged,
                            int* lm_failed);
 
+/* ---- FastGICPMultiPoints: GICP on radius-merged target distributions: fast_gicp::FastGICPMultiPoints
+ * (include/fast_gicp/gicp/experimental/fast_gicp_mp.hpp:40-53, include/fast_gicp/gicp/experimental/fast_gicp_mp_impl.hpp:92-221) ----
+ * The one registration of the family whose correspondence is a RADIUS SEARCH: every source point is matched against the distance-weighted merge of
+ * every target Gaussian within neighbor_search_radius of it.  On the context's OWN source and target and their covariances as they are, exactly as
+ * rgc_gicp_* (either covariance route, caller-set covariances, lazy -- completed first --, re-framed, borrowed and map-bound targets); refused with a
+ * solve in flight; no source, no target, a NULL or non-finite pose: RGC_ERR_INVALID.  (The entry points are rgc_gicpmp_*: the prefix rgc_gicp_ is
+ * FastGICP's own set.)
+ *   For a pose T (row-major 4x4) and every source point p_i (citations: fast_gicp_mp_impl.hpp):
+ *   q = float(T) p_i in fp32, ((m0 x + m1 y) + m2 z) + m3, never contracted (:141).  N_i = every target point j whose fp32 key
+ * ((dx dx + dy dy) + dz dz) < r2, strict, r2 = (float)((double)r * (double)r) -- pcl::KdTreeFLANN::radiusSearch's rule (:145); nothing capped,
+ * nothing approximated.  w_j = max(1e-3, min(1, 1 - (double)(float)sqrt((double)key_j) / r)) (:184-185).  In fp64: sw = sum w_j, mean_B =
+ * sum w_j b_j / sw, cov_B = sum w_j C_B[j] / sw (:180-195; the reference's casts of the two to fp32 are not made).  A point with an empty N_i is
+ * skipped (:176).  For the others a = R p_i + t, d = mean_B - a, M = (cov_B + R C_A[i] R^T)^-1 (the 3x3 block of :199-202), loss l = M d, J =
+ * M [skew(a) | -I] (:203-213); the system is plain Gauss-Newton over those rows: with D = [skew(a) | -I] and W = M M, cost = sum d^T W d, H = sum
+ * D^T W D, b = sum D^T W d -- M SQUARED, the reference's definition.  Every sum runs in a fixed order: results are bit-identical from run to run
+ * and between host- and device-pointer inputs.
+ *   rgc_gicpmp_align (:92-108): up to max_iterations times linearise at T, solve H delta = -b (undamped, the host LM driver's 6x6 factorisation),
+ * T <- [so3_exp(delta_r) | delta_t] T; converged (:118-127) when max(|so3_exp(delta_r) - I|_max / rotation_epsilon, |delta_t|_max /
+ * transformation_epsilon) < 1, tested after the update.  iterations = linearisations made.  A refused or non-finite solve, or no source point with
+ * a neighbour: the solve stops at the last good pose with failed = 1 (the status is RGC_OK, as rgc_gicp_align reports lm_failed).  Deviations from
+ * the reference (its update of the pose, its missing solver, its un-normalised covariances, neighbour order, fp64): DESIGN.md section 6.
+ *   The kept results (rgc_gicpmp_num_correspondences, _get_merged, _get_neighbors) are those of the last linearisation; they drop wherever
+ * FastGICP's frozen list drops, and on rgc_gicpmp_set_params (RGC_ERR_INVALID until the next linearisation). */
+typedef struct rgc_gicp_mp_params {
+  double neighbor_search_radius;   /* neighbor_search_radius_ (0.5)  fast_gicp_mp_impl.hpp:35; finite, > 0, float(r r) finite */
+  int    max_iterations;           /* max_iterations_ (64)           fast_gicp_mp_impl.hpp:29; >= 1 */
+  double rotation_epsilon;         /* rotation_epsilon_ (1e-5)       fast_gicp_mp_impl.hpp:30; > 0 */
+  double transformation_epsilon;   /* transformation_epsilon_ (1e-5) fast_gicp_mp_impl.hpp:31; > 0 */
+} rgc_gicp_mp_params;
+RGC_API void rgc_default_gicp_mp_params(rgc_gicp_mp_params* p);
+RGC_API int rgc_gicpmp_set_params(rgc_ctx* ctx, const rgc_gicp_mp_params* p);
+RGC_API int rgc_gicpmp_get_params(const rgc_ctx* ctx, rgc_gicp_mp_params* p);
+/* H, b as rgc_gicp_linearize (both or neither); cost nullable */
+RGC_API int rgc_gicpmp_linearize(rgc_ctx* ctx, const double T[16], double H[36], double b[6], double* cost);
+/* of the last linearisation: the source points with at least one neighbour, and the total of |N_i| (either may be NULL) */
+RGC_API int rgc_gicpmp_num_correspondences(rgc_ctx* ctx, int* n_points, long long* n_pairs);
+/* of the last linearisation: the target points the gather looked at over all source points (the members of every grid row range a ball reaches):
+ * what the pairs cost to find */
+RGC_API int rgc_gicpmp_num_candidates(rgc_ctx* ctx, long long* n_candidates);
+/* per source point in caller order, n_source entries each (any may be NULL): |N_i|, sw, mean_B (3), cov_B (6: xx xy xz yy yz zz); where count is 0
+ * the other three are zeros */
+RGC_API int rgc_gicpmp_get_merged(rgc_ctx* ctx, int* count, double* sum_w, double* mean3, double* cov6);
+/* the rows N_i in CSR form, caller order: offsets (n_source + 1 entries), idx (original target indices) and sq_dist (the fp32 keys), cap entries
+ * each.  The order inside a row is unspecified but the same from run to run.  *n_total = the total whatever cap is; cap < *n_total:
+ * RGC_ERR_INVALID and no row is written. */
+RGC_API int rgc_gicpmp_get_neighbors(rgc_ctx* ctx, int* offsets, int* idx, float* sq_dist, int cap, long long* n_total);
+/* outputs as rgc_gicp_align's (any may be NULL); final_H = the H of the last step taken (identity if none) */
+RGC_API int rgc_gicpmp_align(rgc_ctx* ctx, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged,
+                             int* failed);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

@@ -159,6 +159,11 @@ class NdtParams(C.Structure):
     _fields_ = [("resolution", C.c_double), ("distance_mode", C.c_int), ("neighbor_method", C.c_int), ("neighbor_radius", C.c_double)]
 
 
+class GicpMpParams(C.Structure):
+    """rgc_gicp_mp_params: the settings of FastGICPMultiPoints (rgc_gicpmp_set_params)"""
+    _fields_ = [("neighbor_search_radius", C.c_double), ("max_iterations", C.c_int), ("rotation_epsilon", C.c_double), ("transformation_epsilon", C.c_double)]
+
+
 NDT_P2D, NDT_D2D = 0, 1
 NDT_DIRECT27, NDT_DIRECT7, NDT_DIRECT1, NDT_DIRECT_RADIUS = 0, 1, 2, 3
 NDT_MAX_OFFSETS = 512
@@ -186,6 +191,7 @@ SYMBOLS = [
     "rgc_default_pgo_params", "rgc_pgo_make_loop", "rgc_pgo_optimize", "rgc_pgo_linearize",
     "rgc_default_ndt_params", "rgc_ndt_set_params", "rgc_ndt_get_params", "rgc_ndt_set_target", "rgc_ndt_set_source", "rgc_ndt_set_target_device", "rgc_ndt_set_source_device", "rgc_ndt_clear_source", "rgc_ndt_clear_target", "rgc_ndt_swap_source_and_target", "rgc_ndt_linearize", "rgc_ndt_compute_error", "rgc_ndt_num_correspondences", "rgc_ndt_align", "rgc_ndt_get_voxels", "rgc_ndt_get_raw_covariances",
     "rgc_gicp_set_max_correspondence_distance", "rgc_gicp_get_max_correspondence_distance", "rgc_gicp_linearize", "rgc_gicp_compute_error", "rgc_gicp_num_correspondences", "rgc_gicp_get_correspondences", "rgc_gicp_align",
+    "rgc_default_gicp_mp_params", "rgc_gicpmp_set_params", "rgc_gicpmp_get_params", "rgc_gicpmp_linearize", "rgc_gicpmp_num_correspondences", "rgc_gicpmp_num_candidates", "rgc_gicpmp_get_merged", "rgc_gicpmp_get_neighbors", "rgc_gicpmp_align",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
@@ -397,6 +403,16 @@ def load():
     L.rgc_gicp_num_correspondences.argtypes = [vp, ip]
     L.rgc_gicp_get_correspondences.argtypes = [vp, ip, fp]
     L.rgc_gicp_align.argtypes = [vp, fp, fp, dp, dp, ip, ip, ip]
+    L.rgc_default_gicp_mp_params.argtypes = [C.POINTER(GicpMpParams)]
+    L.rgc_default_gicp_mp_params.restype = None
+    L.rgc_gicpmp_set_params.argtypes = [vp, C.POINTER(GicpMpParams)]
+    L.rgc_gicpmp_get_params.argtypes = [vp, C.POINTER(GicpMpParams)]
+    L.rgc_gicpmp_linearize.argtypes = [vp, dp, dp, dp, dp]
+    L.rgc_gicpmp_num_correspondences.argtypes = [vp, ip, C.POINTER(C.c_longlong)]
+    L.rgc_gicpmp_num_candidates.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.rgc_gicpmp_get_merged.argtypes = [vp, ip, dp, dp, dp]
+    L.rgc_gicpmp_get_neighbors.argtypes = [vp, ip, ip, fp, C.c_int, C.POINTER(C.c_longlong)]
+    L.rgc_gicpmp_align.argtypes = [vp, fp, fp, dp, dp, ip, ip, ip]
     L.rgc_profile_enable.argtypes = [vp, C.c_int]
     L.rgc_profile_select.argtypes = [vp, C.c_uint]
     L.rgc_profile_reset.argtypes = [vp]

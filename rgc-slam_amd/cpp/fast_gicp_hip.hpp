@@ -136,4 +136,141 @@ private:
   int iterations_ = 0, converged_ = 0, lm_failed_ = 0;
 };
 
+// Stands in for fast_gicp::FastGICPMultiPoints<PointSource, PointTarget> (rgc_slam/include/fast_gicp/gicp/experimental/fast_gicp_mp.hpp:40-53,
+// fast_gicp_mp_impl.hpp:92-221) over rgc_gicpmp_*: every source point against the distance-weighted merge of every target Gaussian within the search
+// radius, plain Gauss-Newton.  The reference's public names, the pcl::Registration calls FastGICPHip has, and the setter the reference forgot
+// (setNeighborSearchRadius).  setRotationEpsilon / setTransformationEpsilon / setMaximumIterations set THIS method's limits (1e-5, 1e-5, 64).
+//
+//   rgc::FastGICPMultiPointsHip mp(0);                      // or FastGICPMultiPointsHip(other.context()) on the clouds of another adaptor (not owned)
+//   mp.setNeighborSearchRadius(0.5); mp.setInputTarget(map); mp.setInputSource(scan);
+//   mp.align(guess);  mp.getFinalTransformation();  mp.hasConverged();
+class FastGICPMultiPointsHip {
+public:
+  typedef std::array<float, 16> Matrix4f;    // row-major
+  typedef std::array<double, 16> Matrix4d;   // row-major
+  typedef std::array<double, 36> Matrix6d;
+  typedef std::array<double, 6> Vector6d;
+
+  explicit FastGICPMultiPointsHip(int hip_device = 0, const rgc_params* params = nullptr) : own_(true) {
+    const int rc = rgc_create(hip_device, params, &ctx_);
+    if (rc != RGC_OK) throw std::runtime_error(std::string("rgc_create: ") + rgc_status_string(rc));
+    init();
+  }
+  explicit FastGICPMultiPointsHip(rgc_ctx* ctx) : ctx_(ctx), own_(false) {
+    if (!ctx) throw std::runtime_error("rgc::FastGICPMultiPointsHip: null context");
+    init();
+  }
+  ~FastGICPMultiPointsHip() { if (own_ && ctx_) rgc_destroy(ctx_); }
+  FastGICPMultiPointsHip(const FastGICPMultiPointsHip&) = delete;
+  FastGICPMultiPointsHip& operator=(const FastGICPMultiPointsHip&) = delete;
+
+  rgc_ctx* context() const { return ctx_; }
+
+  void setNumThreads(int) {}                 // CPU threads (fast_gicp_mp_impl.hpp:47-55): nothing to set on the GPU
+  void setNeighborSearchRadius(double r) { rgc_gicp_mp_params p = mp_params(); p.neighbor_search_radius = r; check(rgc_gicpmp_set_params(ctx_, &p), "rgc_gicpmp_set_params"); }
+  double getNeighborSearchRadius() const { return mp_params().neighbor_search_radius; }
+  void setRotationEpsilon(double e) { rgc_gicp_mp_params p = mp_params(); p.rotation_epsilon = e; check(rgc_gicpmp_set_params(ctx_, &p), "rgc_gicpmp_set_params"); }
+  void setTransformationEpsilon(double e) { rgc_gicp_mp_params p = mp_params(); p.transformation_epsilon = e; check(rgc_gicpmp_set_params(ctx_, &p), "rgc_gicpmp_set_params"); }
+  void setMaximumIterations(int n) { rgc_gicp_mp_params p = mp_params(); p.max_iterations = n; check(rgc_gicpmp_set_params(ctx_, &p), "rgc_gicpmp_set_params"); }
+  void setCorrespondenceRandomness(int k) {
+    rgc_params p;
+    check(rgc_get_params(ctx_, &p), "rgc_get_params");
+    p.k_correspondences = k;
+    check(rgc_set_params(ctx_, &p), "rgc_set_params");
+  }
+  void setRegularizationMethod(int method) { check(rgc_set_regularization_method(ctx_, method), "rgc_set_regularization_method"); }
+
+  template <typename CloudPtr> void setInputTarget(const CloudPtr& cloud) {
+    check(rgc_set_target(ctx_, &cloud->points[0].x, (int)cloud->points.size(), (int)sizeof(cloud->points[0])), "rgc_set_target");
+  }
+  template <typename CloudPtr> void setInputSource(const CloudPtr& cloud) {
+    n_source_ = (int)cloud->points.size();
+    check(rgc_set_source(ctx_, &cloud->points[0].x, n_source_, (int)sizeof(cloud->points[0])), "rgc_set_source");
+  }
+  void setInputTargetDevice(const float* d_xyz, int n, int stride_bytes) { check(rgc_set_target_device(ctx_, d_xyz, n, stride_bytes), "rgc_set_target_device"); }
+  void setInputSourceDevice(const float* d_xyz, int n, int stride_bytes) {
+    n_source_ = n;
+    check(rgc_set_source_device(ctx_, d_xyz, n, stride_bytes), "rgc_set_source_device");
+  }
+  void setSourceCovariances(const std::vector<double>& cov9) { check(rgc_set_source_covariances(ctx_, cov9.data(), (int)(cov9.size() / 9)), "rgc_set_source_covariances"); }
+  void setTargetCovariances(const std::vector<double>& cov9) { check(rgc_set_target_covariances(ctx_, cov9.data(), (int)(cov9.size() / 9)), "rgc_set_target_covariances"); }
+  void clearSource() { n_source_ = 0; check(rgc_clear_source(ctx_), "rgc_clear_source"); }
+  void clearTarget() { check(rgc_clear_target(ctx_), "rgc_clear_target"); }
+
+  double linearize(const Matrix4d& T, Matrix6d* H = nullptr, Vector6d* b = nullptr) {
+    double cost = 0.0;
+    check(rgc_gicpmp_linearize(ctx_, T.data(), H && b ? H->data() : nullptr, H && b ? b->data() : nullptr, &cost), "rgc_gicpmp_linearize");
+    return cost;
+  }
+  // of the last linearize: the source points with a neighbour / the neighbours of all of them
+  int numCorrespondences() {
+    int n = 0;
+    check(rgc_gicpmp_num_correspondences(ctx_, &n, nullptr), "rgc_gicpmp_num_correspondences");
+    return n;
+  }
+  long long numPairs() {
+    long long m = 0;
+    check(rgc_gicpmp_num_correspondences(ctx_, nullptr, &m), "rgc_gicpmp_num_correspondences");
+    return m;
+  }
+  long long numCandidates() {   // target points the gather looked at over all source points
+    long long m = 0;
+    check(rgc_gicpmp_num_candidates(ctx_, &m), "rgc_gicpmp_num_candidates");
+    return m;
+  }
+  // the merge of the last linearize in the source's order: |N_i|, sw, mean_B (3 per point), cov_B (6 per point: xx xy xz yy yz zz)
+  void merged(std::vector<int>& count, std::vector<double>& sum_w, std::vector<double>& mean3, std::vector<double>& cov6) {
+    count.assign((size_t)n_source_, 0);
+    sum_w.assign((size_t)n_source_, 0.0);
+    mean3.assign((size_t)n_source_ * 3, 0.0);
+    cov6.assign((size_t)n_source_ * 6, 0.0);
+    check(rgc_gicpmp_get_merged(ctx_, count.data(), sum_w.data(), mean3.data(), cov6.data()), "rgc_gicpmp_get_merged");
+  }
+  // the rows N_i in CSR form: row i = idx[offsets[i] .. offsets[i + 1]), original target indices, and their fp32 keys
+  void neighbors(std::vector<int>& offsets, std::vector<int>& idx, std::vector<float>& sq_dist) {
+    const long long total = numPairs();
+    if (total > 2147483647LL) throw std::runtime_error("rgc::FastGICPMultiPointsHip::neighbors: more than 2^31 - 1 neighbours");
+    offsets.assign((size_t)n_source_ + 1, 0);
+    idx.assign((size_t)total, -1);
+    sq_dist.assign((size_t)total, 0.f);
+    long long n_total = 0;
+    check(rgc_gicpmp_get_neighbors(ctx_, offsets.data(), idx.data(), sq_dist.data(), (int)total, &n_total), "rgc_gicpmp_get_neighbors");
+  }
+
+  void align(const Matrix4f& guess) {
+    check(rgc_gicpmp_align(ctx_, guess.data(), final_.data(), hessian_.data(), &fitness_, &iterations_, &converged_, &failed_), "rgc_gicpmp_align");
+  }
+  void align() {
+    const Matrix4f I = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+    align(I);
+  }
+  const Matrix4f& getFinalTransformation() const { return final_; }
+  const Matrix6d& getFinalHessian() const { return hessian_; }
+  double getFitnessScore() const { return fitness_; }
+  bool hasConverged() const { return converged_ != 0; }
+  bool failed() const { return failed_ != 0; }
+  int iterations() const { return iterations_; }
+
+private:
+  void init() {
+    final_ = Matrix4f{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+    hessian_.fill(0.0);
+  }
+  rgc_gicp_mp_params mp_params() const {
+    rgc_gicp_mp_params p;
+    check(rgc_gicpmp_get_params(ctx_, &p), "rgc_gicpmp_get_params");
+    return p;
+  }
+  void check(int rc, const char* what) const {
+    if (rc != RGC_OK) throw std::runtime_error(std::string(what) + ": " + rgc_last_error(ctx_));
+  }
+  rgc_ctx* ctx_ = nullptr;
+  bool own_ = false;
+  int n_source_ = 0;
+  Matrix4f final_;
+  Matrix6d hessian_;
+  double fitness_ = 0.0;
+  int iterations_ = 0, converged_ = 0, failed_ = 0;
+};
+
 }  // namespace rgc

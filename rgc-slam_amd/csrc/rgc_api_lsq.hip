@@ -1,6 +1,7 @@
 // rgc_api_lsq.hip -- the host LM driver every registration method shares (LsqRegistration::computeTransformation and step_lm,
 // lsq_registration_impl.hpp:53-79, 125-172) and the two methods that are nothing else on the host: NDT (rgc_ndt_*) and FastGICP (rgc_gicp_*).
-// rgc_align's host-driven route (rgc_api.hip) runs on the same driver.  The kernels are in rgc_ndt.hip and rgc_gicp.hip.
+// rgc_align's host-driven route (rgc_api.hip) runs on the same driver.  The kernels are in rgc_ndt.hip and rgc_gicp.hip.  FastGICPMultiPoints
+// (rgc_gicpmp_*, kernels in rgc_gicp_mp.hip) has a plain Gauss-Newton loop of its own over the driver's scalar pieces.
 #include "rgc_ctx.h"
 #include "rgc_lm_decide.h"  // rgc_lm.h and the convergence test the device decides by (lsq_registration_impl.hpp:82-91)
 
@@ -519,6 +520,209 @@ int rgc_gicp_align(rgc_ctx* c, const float guess[16], float final_T[16], double 
   LmResult r;
   if ((rc = lm_solve(c, sys, guess, &r))) return rc;
   r.write(final_T, final_H, iterations, converged, lm_failed);
+  if (fitness) {
+    if (!pose12_finite(r.fin)) *fitness = (double)NAN;
+    else if ((rc = do_fitness(c, r.fin, fitness))) return rc;
+  }
+  return RGC_OK;
+}
+
+// ---- FastGICPMultiPoints: GICP on radius-merged target distributions (include/fast_gicp/gicp/experimental/fast_gicp_mp_impl.hpp:92-221) on the context's own clouds ----
+void rgc_default_gicp_mp_params(rgc_gicp_mp_params* p) {
+  if (!p) return;
+  p->neighbor_search_radius = 0.5;   // fast_gicp_mp_impl.hpp:35
+  p->max_iterations = 64;            // :29
+  p->rotation_epsilon = 1e-5;        // :30
+  p->transformation_epsilon = 1e-5;  // :31
+}
+
+// r2 as pcl::KdTreeFLANN::radiusSearch hands it to FLANN: the fp64 product rounded to fp32
+static float gicp_mp_r2(double r) { return (float)(r * r); }
+
+int rgc_gicpmp_set_params(rgc_ctx* c, const rgc_gicp_mp_params* p) {
+  if (!c || !p) return RGC_ERR_INVALID;
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  const double r = p->neighbor_search_radius;
+  if (!std::isfinite(r) || !(r > 0.0) || !std::isfinite(gicp_mp_r2(r)))
+    return fail(c, RGC_ERR_INVALID, "rgc_gicpmp_set_params: the radius must be finite and > 0, and its square a finite float");
+  if (p->max_iterations < 1) return fail(c, RGC_ERR_INVALID, "rgc_gicpmp_set_params: max_iterations must be >= 1");
+  if (!(p->rotation_epsilon > 0.0) || !(p->transformation_epsilon > 0.0)) return fail(c, RGC_ERR_INVALID, "rgc_gicpmp_set_params: the epsilons must be > 0");
+  c->gicp_mp_prm = *p;
+  c->gicp_mp_valid = false;
+  return RGC_OK;
+}
+
+int rgc_gicpmp_get_params(const rgc_ctx* c, rgc_gicp_mp_params* p) {
+  if (!c || !p) return RGC_ERR_INVALID;
+  *p = c->gicp_mp_prm;
+  return RGC_OK;
+}
+
+static int gicp_mp_need_inputs(rgc_ctx* c) {
+  const int rc = gicp_need_inputs(c);
+  if (rc) return rc;
+  if (!c->gicp_mp_h_out) HIPCHK(c, hipHostMalloc((void**)&c->gicp_mp_h_out, sizeof(double) * 32, hipHostMallocDefault));
+  return ensure(c, c->gicp_mp_out, sizeof(double) * 32);
+}
+
+// update_correspondences + loss_ls (fast_gicp_mp_impl.hpp:130-221) as the normal equations of its rows; the inputs have been checked
+static int gicp_mp_do_linearize(rgc_ctx* c, const double T[16], double* H, double* b, double* cost) {
+  const Cloud& sc = c->src;
+  const Cloud& tg = c->tgt;
+  const int n = sc.n, nb = rgck::gicp_mp_blocks(n);
+  int rc;
+  c->gicp_mp_valid = false;
+  if ((rc = ensure(c, c->gicp_mp_merged, sizeof(double) * rgck::kGicpMpMerged * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_mp_cand, sizeof(int) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_mp_partials, sizeof(double) * rgck::kGicpMpAcc * (size_t)nb))) return rc;
+  for (int i = 0; i < 16; i++) c->gicp_mp_T32[i] = (float)T[i];  // trans (Matrix4f), :131-133
+  const double r = c->gicp_mp_prm.neighbor_search_radius;
+  const int want = (H && b) ? 1 : 0;
+  rgck::gicp_mp_merge(c->stream, sc.sorted(), posef_from(c->gicp_mp_T32), tg.sorted(), gicp_cov_of(tg), gicp_mp_r2(r), r, c->gicp_mp_merged.as<double>(),
+                      c->gicp_mp_cand.as<int>());
+  rgck::gicp_mp_terms(c->stream, sc.sorted(), c->gicp_mp_merged.as<const double>(), gicp_cov_of(sc), pose_from(T), want, c->gicp_mp_partials.as<double>(),
+                      c->gicp_mp_out.as<double>());
+  HIPCHK(c, hipMemcpyAsync(c->gicp_mp_h_out, c->gicp_mp_out.p, sizeof(double) * rgck::kGicpMpAcc, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  const double* o = c->gicp_mp_h_out;
+  c->gicp_mp_valid = true;
+  c->gicp_mp_n = n;
+  c->gicp_mp_points = (int)o[28];
+  c->gicp_mp_pairs = (long long)o[29];
+  if (want) unpack_system(o, H, b);
+  if (cost) *cost = o[27];
+  return RGC_OK;
+}
+
+int rgc_gicpmp_linearize(rgc_ctx* c, const double T[16], double H[36], double b[6], double* cost) {
+  if (!c || !T) return RGC_ERR_INVALID;
+  if (!gicp_pose_ok(T)) return fail(c, RGC_ERR_INVALID, "rgc_gicpmp_linearize: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = gicp_mp_need_inputs(c);
+  return rc ? rc : gicp_mp_do_linearize(c, T, H, b, cost);
+}
+
+// the kept results are there, and are those of the present clouds
+static int gicp_mp_need_results(rgc_ctx* c, const char* who) {
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  if (!c->gicp_mp_valid || !c->src.ready || !c->tgt.ready || c->gicp_mp_n != c->src.n)
+    return fail(c, RGC_ERR_INVALID, "%s needs a preceding rgc_gicpmp_linearize on the present clouds and settings", who);
+  return RGC_OK;
+}
+
+int rgc_gicpmp_num_correspondences(rgc_ctx* c, int* n_points, long long* n_pairs) {
+  if (!c) return RGC_ERR_INVALID;
+  const int rc = gicp_mp_need_results(c, "rgc_gicpmp_num_correspondences");
+  if (rc) return rc;
+  if (n_points) *n_points = c->gicp_mp_points;
+  if (n_pairs) *n_pairs = c->gicp_mp_pairs;
+  return RGC_OK;
+}
+
+// what the gather looked at to find them: the candidates of all source points (every point of every grid row range the balls reach)
+int rgc_gicpmp_num_candidates(rgc_ctx* c, long long* n_candidates) {
+  if (!c || !n_candidates) return RGC_ERR_INVALID;
+  const int rc = gicp_mp_need_results(c, "rgc_gicpmp_num_candidates");
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<int> cand((size_t)c->src.n);
+  HIPCHK(c, hipMemcpyAsync(cand.data(), c->gicp_mp_cand.p, sizeof(int) * cand.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  long long t = 0;
+  for (int v : cand) t += v;
+  *n_candidates = t;
+  return RGC_OK;
+}
+
+int rgc_gicpmp_get_merged(rgc_ctx* c, int* count, double* sum_w, double* mean3, double* cov6) {
+  if (!c) return RGC_ERR_INVALID;
+  int rc = gicp_mp_need_results(c, "rgc_gicpmp_get_merged");
+  if (rc) return rc;
+  if (!count && !sum_w && !mean3 && !cov6) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)c->src.n;
+  if ((rc = ensure(c, c->gicp_mp_scratch, (sizeof(double) * 10 + sizeof(int)) * n))) return rc;
+  double* d_sw = c->gicp_mp_scratch.as<double>();
+  double* d_mean = d_sw + n;
+  double* d_cov = d_mean + 3 * n;
+  int* d_count = (int*)(d_cov + 6 * n);
+  HIPCHK(c, hipMemsetAsync(c->gicp_mp_scratch.p, 0, (sizeof(double) * 10 + sizeof(int)) * n, c->stream));
+  rgck::gicp_mp_export(c->stream, c->src.sorted(), c->gicp_mp_merged.as<const double>(), d_count, d_sw, d_mean, d_cov);
+  if (count) HIPCHK(c, hipMemcpyAsync(count, d_count, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+  if (sum_w) HIPCHK(c, hipMemcpyAsync(sum_w, d_sw, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  if (mean3) HIPCHK(c, hipMemcpyAsync(mean3, d_mean, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+  if (cov6) HIPCHK(c, hipMemcpyAsync(cov6, d_cov, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+
+int rgc_gicpmp_get_neighbors(rgc_ctx* c, int* offsets, int* idx, float* sq_dist, int cap, long long* n_total) {
+  if (!c || !n_total) return RGC_ERR_INVALID;
+  int rc = gicp_mp_need_results(c, "rgc_gicpmp_get_neighbors");
+  if (rc) return rc;
+  *n_total = c->gicp_mp_pairs;
+  if (cap < 0 || (long long)cap < c->gicp_mp_pairs) return fail(c, RGC_ERR_INVALID, "rgc_gicpmp_get_neighbors: cap is smaller than the %lld neighbours there are", c->gicp_mp_pairs);
+  if (!offsets && !idx && !sq_dist) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((rc = check_target_owner(c))) return rc;
+  // count (caller order) -> exclusive scan -> fill: [counts n + 1][offsets n + 1][block sums][idx total][keys total]
+  const size_t n1 = (size_t)c->src.n + 1, nbs = n1 / 2048 + 2, total = (size_t)c->gicp_mp_pairs;
+  if ((rc = ensure(c, c->gicp_mp_scratch, sizeof(int) * (2 * n1 + nbs + 2 * total)))) return rc;
+  int* d_cnt = c->gicp_mp_scratch.as<int>();
+  int* d_off = d_cnt + n1;
+  int* d_bs = d_off + n1;
+  int* d_idx = d_bs + nbs;
+  float* d_sq = (float*)(d_idx + total);
+  HIPCHK(c, hipMemsetAsync(d_cnt, 0, sizeof(int) * n1, c->stream));
+  rgck::gicp_mp_export(c->stream, c->src.sorted(), c->gicp_mp_merged.as<const double>(), d_cnt, nullptr, nullptr, nullptr);
+  rgck::exclusive_scan(c->stream, d_cnt, d_off, (int)n1, d_bs);
+  const double r = c->gicp_mp_prm.neighbor_search_radius;
+  if (total) rgck::gicp_mp_fill(c->stream, c->src.sorted(), posef_from(c->gicp_mp_T32), c->tgt.sorted(), gicp_mp_r2(r), r, d_off, d_idx, d_sq);
+  if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, d_off, sizeof(int) * n1, hipMemcpyDeviceToHost, c->stream));
+  if (idx && total) HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int) * total, hipMemcpyDeviceToHost, c->stream));
+  if (sq_dist && total) HIPCHK(c, hipMemcpyAsync(sq_dist, d_sq, sizeof(float) * total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+
+// computeTransformation (fast_gicp_mp_impl.hpp:80-115): plain Gauss-Newton.  The update is the one the Jacobian skew(R p + t) is derived for and every
+// other driver here makes, T <- [so3_exp(d_r) | d_t] T (rgclm::lm_try at lambda = 0: the undamped solve of the host LM driver's 6x6 factorisation);
+// the reference's own (:101-102) turns R alone.  Convergence (:118-127) is tested after the update.
+int rgc_gicpmp_align(rgc_ctx* c, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged, int* failed) {
+  if (!c || !guess) return RGC_ERR_INVALID;
+  if (!pose12_finite(guess)) return fail(c, RGC_ERR_INVALID, "rgc_gicpmp_align: the guess is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = gicp_mp_need_inputs(c);
+  if (rc) return rc;
+  const rgc_gicp_mp_params& P = c->gicp_mp_prm;
+  LmResult r;
+  for (int i = 0; i < 12; i++) r.x0[i] = (double)guess[i];
+  r.x0[12] = r.x0[13] = r.x0[14] = 0.0;
+  r.x0[15] = 1.0;
+  r.conv = r.failed = false;
+  r.iters = 0;
+  memset(r.Hfin, 0, sizeof(r.Hfin));
+  for (int i = 0; i < 6; i++) r.Hfin[i * 7] = 1.0;
+  for (int it = 0; it < P.max_iterations; it++) {  // :92
+    if (!gicp_pose_ok(r.x0)) { r.failed = true; break; }
+    r.iters = it + 1;
+    double H[36], b[6], y0, d[6], delta[16], xi[16];
+    if ((rc = gicp_mp_do_linearize(c, r.x0, H, b, &y0))) return rc;  // :95-97
+    if (c->gicp_mp_points == 0) { r.failed = true; break; }
+    rgclm::lm_try(H, b, 0.0, r.x0, d, delta, xi);                   // :99-102
+    bool finite = true;
+    for (int i = 0; i < 6; i++) finite = finite && std::isfinite(d[i]);
+    for (int i = 0; i < 12; i++) finite = finite && std::isfinite(xi[i]);
+    if (!finite) { r.failed = true; break; }
+    memcpy(r.x0, xi, sizeof(xi));
+    memcpy(r.Hfin, H, sizeof(H));
+    if (rgck::lm_is_converged(delta, P.rotation_epsilon, P.transformation_epsilon)) { r.conv = true; break; }  // :104-107
+  }
+  for (int i = 0; i < 16; i++) r.fin[i] = (float)r.x0[i];
+  r.write(final_T, final_H, iterations, converged, failed);
   if (fitness) {
     if (!pose12_finite(r.fin)) *fitness = (double)NAN;
     else if ((rc = do_fitness(c, r.fin, fitness))) return rc;

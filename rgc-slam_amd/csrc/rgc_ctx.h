@@ -324,6 +324,16 @@ struct rgc_ctx {
   double* gicp_h_out = nullptr;           // pinned: 32 doubles
   bool gicp_valid = false;
   int gicp_n = 0, gicp_kept = 0;
+  // FastGICPMultiPoints (rgc_gicpmp_*) on the same clouds: the merged list of the last rgc_gicpmp_linearize (rgck::kGicpMpMerged doubles per sorted
+  // source point), the fp32 pose and radius it was made under (the read-out of the members walks the candidates again).  gicp_mp_valid falls
+  // wherever gicp_valid falls, and on rgc_gicpmp_set_params
+  rgc_gicp_mp_params gicp_mp_prm{0.5, 64, 1e-5, 1e-5};
+  DevBuf gicp_mp_merged, gicp_mp_cand, gicp_mp_partials, gicp_mp_out, gicp_mp_scratch;
+  double* gicp_mp_h_out = nullptr;        // pinned: 32 doubles
+  bool gicp_mp_valid = false;
+  int gicp_mp_n = 0, gicp_mp_points = 0;
+  long long gicp_mp_pairs = 0;
+  float gicp_mp_T32[16] = {0};
   rgc_stats stats{};
   // profiling
   bool prof_on = false;

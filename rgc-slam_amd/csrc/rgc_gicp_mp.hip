@@ -1,0 +1,353 @@
+// rgc_gicp_mp.hip -- gfx950 kernels of FastGICPMultiPoints: GICP of every source point against the distance-weighted merge of EVERY target Gaussian
+// within a radius of it.  Reference: fast_gicp::FastGICPMultiPoints (include/fast_gicp/gicp/experimental/fast_gicp_mp.hpp,
+// include/fast_gicp/gicp/experimental/fast_gicp_mp_impl.hpp:92-221); written from its formulas, in the project's arithmetic: the query and the search
+// key in fp32 (never FMA-contracted: -ffp-contract=off), everything after them fp64, every sum in a fixed order, no floating-point atomics.
+// Citations are relative to rgc_slam/ of the reference (ROBOT-WSC/RGC-SLAM).
+// A translation unit of its own: the device code of every other kernel of the library stays what it was.  The radius gather (k_gicp_mp_merge: fp32
+// candidates, eleven fp64 accumulators) and the term (k_gicp_mp_terms: 30 accumulators) are two kernels, as in rgc_gicp.hip -- no spill, no private
+// segment, no accumulator registers; nothing waits on another workgroup.
+#include "rgc_kernels.h"
+#include "rgc_nn.h"
+
+namespace rgck {
+
+constexpr int MP_T = 256;     // threads per workgroup
+constexpr int MP_WAVE = 64;
+// Lanes per query of the gather.  A query's neighbour count ranges from none to the whole target, so one lane per query leaves a wave waiting for
+// its longest row; a group of lanes strides the candidates of one query and folds its accumulators in a fixed shuffle tree.  8 was the fastest of
+// 1, 8, 16 and 64 on the measured clouds (30 k-point scans, 24 to 123 candidates per query; EXPERIMENTS.md, "FastGICPMultiPoints").
+#ifdef RGC_LAB_MP_GROUP  // developer build (-DRGC_LAB_MP_GROUP=1|8|16|64): the group sizes scripts/bench_gicp_mp.py compares
+constexpr int MP_GROUP = RGC_LAB_MP_GROUP;
+#else
+constexpr int MP_GROUP = 8;
+#endif
+static_assert(MP_GROUP >= 1 && MP_GROUP <= MP_WAVE && !(MP_GROUP & (MP_GROUP - 1)), "a power of two of lanes within a wave");
+
+int gicp_mp_blocks(int n) { return (n + MP_T - 1) / MP_T; }
+
+// The part of the target's grid the ball of radius `reach` about the query can touch: per axis the cells of q - reach and q + reach, clipped
+// to the grid.  reach = r (1 + 1e-5): a point whose fp32 key is below r2 lies within r (1 + 3 * 2^-24) of the query in exact arithmetic (the
+// key's three products and two sums round by 2^-24 each, the differences of fp32 coordinates at most as much again), and it lies in the cell
+// its own coordinates name (the grid's rule, cell_coord) -- so no member of the ball is outside this block.  A cell too many costs
+// candidates; a cell too few would be a wrong answer.  empty: the ball misses the grid.
+struct MpBlock { int lo[3], hi[3]; bool empty; };
+__device__ __forceinline__ int mp_cell_rel(double x, const Grid& g, int a) {
+  const double u = floor(g.inv_res != 0.0 ? x * g.inv_res - 0.5 : x / g.res - 0.5) - (double)g.minc[a];
+  return (int)fmin(fmax(u, -1.0), (double)g.dim[a]);  // (clamped in fp64: a query far outside the grid must not overflow the int)
+}
+__device__ __forceinline__ MpBlock mp_block(const double q[3], double reach, const Grid& g) {
+  MpBlock B;
+  B.empty = false;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    B.lo[a] = max(mp_cell_rel(q[a] - reach, g, a), 0);
+    B.hi[a] = min(mp_cell_rel(q[a] + reach, g, a), g.dim[a] - 1);
+    B.empty = B.empty || B.lo[a] > B.hi[a];
+  }
+  return B;
+}
+// distance from x to the cell c of axis a (0 inside it)
+__device__ __forceinline__ double mp_gap(const Grid& g, int a, int c, double x) {
+  const double wall = cell_wall(g, a, c);
+  return fmax(0.0, fmax(wall - x, x - (wall + g.res)));
+}
+
+// Every candidate of the query (qx, qy, qz): the cells of a grid row are consecutive in the sorted target (for_each_cube_row's contiguous row
+// ranges), so the block is (hi_y - lo_y + 1) (hi_z - lo_z + 1) ranges; a row the ball cannot reach is skipped.  Lane `lane` of a group of G
+// takes every G-th candidate of the concatenated ranges (the running count carries over from row to row: short rows do not idle lanes).
+// f(i): sorted position i.  Returns the number of candidates (of all lanes).
+template <int G, typename F>
+__device__ __forceinline__ int mp_walk(const double q[3], double reach, const int* __restrict__ tstart, const Grid& g, int lane, F&& f) {
+  const MpBlock B = mp_block(q, reach, g);
+  int cnt = 0;
+  if (B.empty) return 0;
+  const double reach2 = reach * reach;
+  for (int z = B.lo[2]; z <= B.hi[2]; z++) {
+    const double gz = mp_gap(g, 2, z, q[2]);
+    for (int y = B.lo[1]; y <= B.hi[1]; y++) {
+      const double gy = mp_gap(g, 1, y, q[1]);
+      if (gy * gy + gz * gz > reach2) continue;
+      const int a = tstart[cell_index(g, B.lo[0], y, z)], b = tstart[cell_index(g, B.hi[0], y, z) + 1];
+      int i = a + ((lane - cnt) & (G - 1));
+      cnt += b - a;
+      for (; i < b; i += G) f(i);
+    }
+  }
+  return cnt;
+}
+
+__device__ __forceinline__ void mp_query(const float4& sp, const PoseF& T, float& qx, float& qy, float& qz) {
+  const float x = sp.x, y = sp.y, z = sp.z;  // fast_gicp_mp_impl.hpp:141, as k_gicp_correspond computes it
+  qx = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+  qy = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+  qz = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+}
+
+// the covariance of sorted target point s as its upper triangle, as rgc_gicp.hip's gicp_cov6 (fast_gicp_impl.hpp:280-293)
+template <bool kGeneral>
+__device__ __forceinline__ void mp_cov6(const double* __restrict__ c6, const double* __restrict__ nx, const double* __restrict__ ny,
+                                        const double* __restrict__ nz, int n, int s, double C[6]) {
+  if (kGeneral) {
+#pragma unroll
+    for (int a = 0; a < 6; a++) C[a] = c6[(size_t)a * n + s];
+  } else {
+    const double v0 = nx[s], v1 = ny[s], v2 = nz[s];
+    C[0] = 1.0 - 0.999 * v0 * v0; C[1] = 0.0 - 0.999 * v0 * v1; C[2] = 0.0 - 0.999 * v0 * v2;
+    C[3] = 1.0 - 0.999 * v1 * v1; C[4] = 0.0 - 0.999 * v1 * v2;
+    C[5] = 1.0 - 0.999 * v2 * v2;
+  }
+}
+
+constexpr int kMpMerged = kGicpMpMerged;  // count, sum of weights, mean (3), covariance (6: xx xy xz yy yz zz)
+
+// fast_gicp_mp_impl.hpp:139-153 (update_correspondences: the radius search) and :180-195 (the merge of loss_ls) for sorted source point s, by a
+// group of G lanes: N = every target point whose fp32 key ((dx dx + dy dy) + dz dz) < r2, strict (pcl::KdTreeFLANN::radiusSearch's rule, r2 =
+// float(r r)); w = max(1e-3, min(1, 1 - float(sqrt(key)) / r)) (:184-185; the fp32 square root, correctly rounded: the fp64 root of an fp32 value
+// rounded to fp32 is that); sw = sum w, mean = sum w b / sw, cov = sum w C_B / sw, fp64 (the reference's casts of the two to fp32 are not made).
+// Order of a sum: a lane's candidates ascending in the sorted target, then the group's shuffle tree.  out: SoA [kMpMerged][ns], zeros behind a count
+// of 0.  cand (nullable): candidates looked at per query.
+template <int G, bool kGenB>
+__global__ void __launch_bounds__(MP_T) k_gicp_mp_merge(const float4* __restrict__ SP, int ns, PoseF T, const float4* __restrict__ TP, const int* __restrict__ tstart,
+                                                        Grid g, int nt, float r2, double r, double reach, const double* __restrict__ c6B,
+                                                        const double* __restrict__ nxB, const double* __restrict__ nyB, const double* __restrict__ nzB,
+                                                        double* __restrict__ out, int* __restrict__ cand) {
+  const int s = blockIdx.x * (MP_T / G) + threadIdx.x / G, lane = threadIdx.x & (G - 1);
+  double acc[kMpMerged];
+#pragma unroll
+  for (int a = 0; a < kMpMerged; a++) acc[a] = 0.0;
+  int ncand = 0;
+  if (s < ns) {  // (a whole group takes this branch or none of it does)
+    float qx, qy, qz;
+    mp_query(SP[s], T, qx, qy, qz);
+    const double q[3] = {(double)qx, (double)qy, (double)qz};
+    ncand = mp_walk<G>(q, reach, tstart, g, lane, [&](int i) {
+      const float4 cp = point_at(TP, (unsigned)i << 4);
+      const float key = dist2(qx, qy, qz, cp);
+      if (key < r2) {
+        const double w = fmax(1e-3, fmin(1.0, 1.0 - (double)(float)sqrt((double)key) / r));
+        double C[6];
+        mp_cov6<kGenB>(c6B, nxB, nyB, nzB, nt, i, C);
+        acc[0] += 1.0;
+        acc[1] += w;
+        acc[2] += w * (double)cp.x; acc[3] += w * (double)cp.y; acc[4] += w * (double)cp.z;
+#pragma unroll
+        for (int a = 0; a < 6; a++) acc[5 + a] += w * C[a];
+      }
+    });
+  }
+  if (G > 1) {
+#pragma unroll
+    for (int a = 0; a < kMpMerged; a++) {
+      double v = acc[a];
+#pragma unroll
+      for (int o = G / 2; o > 0; o >>= 1) v += __shfl_down(v, o, G);
+      acc[a] = v;
+    }
+  }
+  if (s < ns && lane == 0) {
+    const bool any = acc[0] > 0.0;
+    out[s] = acc[0];
+    out[(size_t)ns + s] = acc[1];
+#pragma unroll
+    for (int a = 2; a < kMpMerged; a++) out[(size_t)a * ns + s] = any ? acc[a] / acc[1] : 0.0;
+    if (cand) cand[s] = ncand;
+  }
+}
+
+// inverse of a symmetric 3x3 by its adjugate (rgc_gicp.hip's gicp_inv_sym3); false (M untouched) if the determinant is exactly zero
+__device__ __forceinline__ bool mp_inv_sym3(const double S[6], double M[6]) {
+  const double a = S[0], b = S[1], c = S[2], d = S[3], e = S[4], f = S[5];
+  const double c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
+  const double det = a * c00 + b * c01 + c * c02;
+  if (det == 0.0) return false;
+  const double id = 1.0 / det;
+  M[0] = c00 * id; M[1] = c01 * id; M[2] = c02 * id;
+  M[3] = (a * f - c * c) * id; M[4] = (b * c - a * e) * id; M[5] = (a * d - b * b) * id;
+  return true;
+}
+
+// Sum of the block's NACC accumulators in a FIXED order: the six shuffle steps of a wave, then the four waves ascending (rgc_gicp.hip's gicp_block_store)
+template <int NACC>
+__device__ __forceinline__ void mp_block_store(double (&acc)[NACC], double* __restrict__ row) {
+  __shared__ double red[MP_T / MP_WAVE][NACC];
+  const int lane = threadIdx.x & (MP_WAVE - 1), w = threadIdx.x / MP_WAVE;
+#pragma unroll
+  for (int a = 0; a < NACC; a++) {
+    double v = acc[a];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    if (lane == 0) red[w][a] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NACC) {
+    double t = red[0][threadIdx.x];
+#pragma unroll
+    for (int j = 1; j < MP_T / MP_WAVE; j++) t += red[j][threadIdx.x];
+    row[threadIdx.x] = t;
+  }
+}
+
+constexpr int kMpAcc = kGicpMpAcc;  // 21 upper-triangular H, 6 b, the cost, the source points with a neighbour, the neighbours (exact in a double: < 2^53)
+
+// fast_gicp_mp_impl.hpp:197-213 for sorted source point s with a non-empty ball (:176): a = R p + t, d = mean_B - a, M = (cov_B + R C_A[s] R^T)^-1
+// (the 3x3 block of the reference's 4x4 with RCR(3,3) = 1, :199-202), loss l = M d (:203,212), J = M [skew(a) | -I] (:205-209,213).  The system is
+// plain Gauss-Newton over those rows: with D = [skew(a) | -I] and W = M M, cost += d^T W d, H += D^T W D, b += D^T W d -- the weighting is M SQUARED,
+// the reference's definition, not GICP's M.  One lane per sorted source point.
+template <bool kGenA>
+__global__ void __launch_bounds__(MP_T) k_gicp_mp_terms(const float4* __restrict__ SP, int ns, const double* __restrict__ merged, const double* __restrict__ c6A,
+                                                        const double* __restrict__ nxA, const double* __restrict__ nyA, const double* __restrict__ nzA, Pose T,
+                                                        int want_H, double* __restrict__ partials) {
+  const int s = blockIdx.x * MP_T + threadIdx.x;
+  double acc[kMpAcc];
+#pragma unroll
+  for (int a = 0; a < kMpAcc; a++) acc[a] = 0.0;
+  const double count = s < ns ? merged[s] : 0.0;
+  if (count > 0.0) {
+    const float4 sp = SP[s];
+    const double p0 = (double)sp.x, p1 = (double)sp.y, p2 = (double)sp.z;
+    double CA[6], S[6];
+    mp_cov6<kGenA>(c6A, nxA, nyA, nzA, ns, s, CA);
+    const double Cs[3][3] = {{CA[0], CA[1], CA[2]}, {CA[1], CA[3], CA[4]}, {CA[2], CA[4], CA[5]}};
+    double RC[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+      for (int b = 0; b < 3; b++) RC[a][b] = T.R[3 * a] * Cs[0][b] + T.R[3 * a + 1] * Cs[1][b] + T.R[3 * a + 2] * Cs[2][b];
+    {
+      int u = 0;
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = a; b < 3; b++) {
+          S[u] = merged[(size_t)(5 + u) * ns + s] + (RC[a][0] * T.R[3 * b] + RC[a][1] * T.R[3 * b + 1] + RC[a][2] * T.R[3 * b + 2]);
+          u++;
+        }
+    }
+    double M[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    mp_inv_sym3(S, M);
+    // W = M M (symmetric: M is)
+    const double W[6] = {M[0] * M[0] + M[1] * M[1] + M[2] * M[2], M[0] * M[1] + M[1] * M[3] + M[2] * M[4], M[0] * M[2] + M[1] * M[4] + M[2] * M[5],
+                         M[1] * M[1] + M[3] * M[3] + M[4] * M[4], M[1] * M[2] + M[3] * M[4] + M[4] * M[5], M[2] * M[2] + M[4] * M[4] + M[5] * M[5]};
+    const double q0 = T.R[0] * p0 + T.R[1] * p1 + T.R[2] * p2 + T.t[0];
+    const double q1 = T.R[3] * p0 + T.R[4] * p1 + T.R[5] * p2 + T.t[1];
+    const double q2 = T.R[6] * p0 + T.R[7] * p1 + T.R[8] * p2 + T.t[2];
+    const double e0 = merged[(size_t)2 * ns + s] - q0, e1 = merged[(size_t)3 * ns + s] - q1, e2 = merged[(size_t)4 * ns + s] - q2;
+    const double We0 = W[0] * e0 + W[1] * e1 + W[2] * e2;
+    const double We1 = W[1] * e0 + W[3] * e1 + W[4] * e2;
+    const double We2 = W[2] * e0 + W[4] * e1 + W[5] * e2;
+    acc[27] = e0 * We0 + e1 * We1 + e2 * We2;
+    acc[28] = 1.0;
+    acc[29] = count;
+    if (want_H) {
+      const double J[3][6] = {{0.0, -q2, q1, -1.0, 0.0, 0.0}, {q2, 0.0, -q0, 0.0, -1.0, 0.0}, {-q1, q0, 0.0, 0.0, 0.0, -1.0}};
+      double WJ[3][6];
+#pragma unroll
+      for (int c = 0; c < 6; c++) {
+        WJ[0][c] = W[0] * J[0][c] + W[1] * J[1][c] + W[2] * J[2][c];
+        WJ[1][c] = W[1] * J[0][c] + W[3] * J[1][c] + W[4] * J[2][c];
+        WJ[2][c] = W[2] * J[0][c] + W[4] * J[1][c] + W[5] * J[2][c];
+      }
+      int u = 0;
+#pragma unroll
+      for (int a = 0; a < 6; a++) {
+#pragma unroll
+        for (int c = a; c < 6; c++) {
+          acc[u] = J[0][a] * WJ[0][c] + J[1][a] * WJ[1][c] + J[2][a] * WJ[2][c];
+          u++;
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < 6; a++) acc[21 + a] = J[0][a] * We0 + J[1][a] * We1 + J[2][a] * We2;
+    }
+  }
+  mp_block_store<kMpAcc>(acc, partials + (size_t)blockIdx.x * kMpAcc);
+}
+
+// the workgroups' rows folded in a fixed order, one wave per column (rgc_gicp.hip's k_gicp_fold)
+__global__ void __launch_bounds__(MP_WAVE) k_gicp_mp_fold(const double* __restrict__ partials, int nb, int ncol, double* __restrict__ out) {
+  const int col = blockIdx.x, lane = threadIdx.x;
+  double t = 0.0;
+  for (int b = lane; b < nb; b += MP_WAVE) t += partials[(size_t)b * ncol + col];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o);
+  if (lane == 0) out[col] = t;
+}
+
+// the merge's results in CALLER order (each output nullable): count[i], sum_w[i], mean3[3 i ..], cov6[6 i ..] of source point i
+__global__ void __launch_bounds__(MP_T) k_gicp_mp_export(const float4* __restrict__ SP, int ns, const double* __restrict__ merged, int* __restrict__ count,
+                                                         double* __restrict__ sum_w, double* __restrict__ mean3, double* __restrict__ cov6) {
+  const int s = blockIdx.x * MP_T + threadIdx.x;
+  if (s >= ns) return;
+  const int o = __float_as_int(SP[s].w);
+  if (o < 0 || o >= ns) return;
+  if (count) count[o] = (int)merged[s];
+  if (sum_w) sum_w[o] = merged[(size_t)ns + s];
+  if (mean3) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) mean3[(size_t)3 * o + a] = merged[(size_t)(2 + a) * ns + s];
+  }
+  if (cov6) {
+#pragma unroll
+    for (int a = 0; a < 6; a++) cov6[(size_t)6 * o + a] = merged[(size_t)(5 + a) * ns + s];
+  }
+}
+
+// the rows N_i in CSR form and caller order: off = the exclusive scan of the counts k_gicp_mp_export leaves (off[o] .. off[o + 1]); one lane per
+// sorted source point walks its candidates again -- the same fp32 query, key and strict test as the merge -- and writes its members' original
+// indices and keys, ascending in the sorted target (a fixed order: the same from run to run)
+__global__ void __launch_bounds__(MP_T) k_gicp_mp_fill(const float4* __restrict__ SP, int ns, PoseF T, const float4* __restrict__ TP, const int* __restrict__ tstart,
+                                                       Grid g, float r2, double reach, const int* __restrict__ off, int* __restrict__ idx, float* __restrict__ sq) {
+  const int s = blockIdx.x * MP_T + threadIdx.x;
+  if (s >= ns) return;
+  const float4 sp = SP[s];
+  const int o = __float_as_int(sp.w);
+  if (o < 0 || o >= ns) return;
+  float qx, qy, qz;
+  mp_query(sp, T, qx, qy, qz);
+  const double q[3] = {(double)qx, (double)qy, (double)qz};
+  int at = off[o];
+  const int end = off[o + 1];
+  mp_walk<1>(q, reach, tstart, g, 0, [&](int i) {
+    const float4 cp = point_at(TP, (unsigned)i << 4);
+    const float key = dist2(qx, qy, qz, cp);
+    if (key < r2 && at < end) {
+      idx[at] = __float_as_int(cp.w);
+      sq[at] = key;
+      at++;
+    }
+  });
+}
+
+void gicp_mp_merge(hipStream_t s, const SortedCloud& src, PoseF T, const SortedCloud& tgt, const GicpCov& B, float r2, double r, double* merged, int* cand) {
+  const long long lanes = (long long)src.n * MP_GROUP;
+  const int nb = (int)((lanes + MP_T - 1) / MP_T);
+  if (nb <= 0) return;
+  const double reach = r * (1.0 + 1e-5);
+  if (B.c6)
+    hipLaunchKernelGGL((k_gicp_mp_merge<MP_GROUP, true>), dim3(nb), dim3(MP_T), 0, s, src.P, src.n, T, tgt.P, tgt.start, tgt.grid, tgt.n, r2, r, reach, B.c6, B.nx, B.ny,
+                       B.nz, merged, cand);
+  else
+    hipLaunchKernelGGL((k_gicp_mp_merge<MP_GROUP, false>), dim3(nb), dim3(MP_T), 0, s, src.P, src.n, T, tgt.P, tgt.start, tgt.grid, tgt.n, r2, r, reach, B.c6, B.nx, B.ny,
+                       B.nz, merged, cand);
+}
+
+void gicp_mp_terms(hipStream_t s, const SortedCloud& src, const double* merged, const GicpCov& A, Pose T, int want_H, double* partials, double* out30) {
+  const int nb = gicp_mp_blocks(src.n);
+  if (nb <= 0) return;
+  if (A.c6) hipLaunchKernelGGL((k_gicp_mp_terms<true>), dim3(nb), dim3(MP_T), 0, s, src.P, src.n, merged, A.c6, A.nx, A.ny, A.nz, T, want_H, partials);
+  else      hipLaunchKernelGGL((k_gicp_mp_terms<false>), dim3(nb), dim3(MP_T), 0, s, src.P, src.n, merged, A.c6, A.nx, A.ny, A.nz, T, want_H, partials);
+  hipLaunchKernelGGL(k_gicp_mp_fold, dim3(kMpAcc), dim3(MP_WAVE), 0, s, partials, nb, kMpAcc, out30);
+}
+
+void gicp_mp_export(hipStream_t s, const SortedCloud& src, const double* merged, int* count, double* sum_w, double* mean3, double* cov6) {
+  const int nb = gicp_mp_blocks(src.n);
+  if (nb > 0) hipLaunchKernelGGL(k_gicp_mp_export, dim3(nb), dim3(MP_T), 0, s, src.P, src.n, merged, count, sum_w, mean3, cov6);
+}
+
+void gicp_mp_fill(hipStream_t s, const SortedCloud& src, PoseF T, const SortedCloud& tgt, float r2, double r, const int* off, int* idx, float* sq) {
+  const int nb = gicp_mp_blocks(src.n);
+  if (nb > 0)
+    hipLaunchKernelGGL(k_gicp_mp_fill, dim3(nb), dim3(MP_T), 0, s, src.P, src.n, T, tgt.P, tgt.start, tgt.grid, r2, r * (1.0 + 1e-5), off, idx, sq);
+}
+
+}  // namespace rgck

@@ -371,6 +371,20 @@ void gicp_terms(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, c
 void gicp_error(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const double* M, Pose T, double* partials, double* out1);
 // the pair list in caller order: idx[i] = the neighbour's original index or -1, sq[i] = the key
 void gicp_export(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const float* key, int* idx, float* sq);
+// ---- FastGICPMultiPoints: GICP on radius-merged target distributions (rgc_gicp_mp.hip; fast_gicp::FastGICPMultiPoints,
+// include/fast_gicp/gicp/experimental/fast_gicp_mp_impl.hpp:92-221) ----
+constexpr int kGicpMpMerged = 11;  // per source point: neighbours, sum of weights, merged mean (3), merged covariance (6)
+constexpr int kGicpMpAcc = kAccum + 2;  // the 28 sums, the source points with a neighbour, the neighbours
+int  gicp_mp_blocks(int n);
+// the exact radius gather at T (fp32 query and key, key < r2 strict) and the weighted merge of the members' Gaussians: merged = SoA
+// [kGicpMpMerged][src.n] in the source's sorted order; cand (nullable): candidates looked at per source point.  B: the target's covariances
+void gicp_mp_merge(hipStream_t s, const SortedCloud& src, PoseF T, const SortedCloud& tgt, const GicpCov& B, float r2, double r, double* merged, int* cand);
+// the terms of the merged list at T; partials: gicp_mp_blocks(src.n) rows of kGicpMpAcc doubles; out30: the sums.  A: the source's covariances
+void gicp_mp_terms(hipStream_t s, const SortedCloud& src, const double* merged, const GicpCov& A, Pose T, int want_H, double* partials, double* out30);
+// the merged list in caller order (each output nullable): count[i], sum_w[i], mean3[3 i ..], cov6[6 i ..]
+void gicp_mp_export(hipStream_t s, const SortedCloud& src, const double* merged, int* count, double* sum_w, double* mean3, double* cov6);
+// the members themselves: off = the exclusive scan of the caller-order counts (src.n + 1 entries); idx / sq: original target index and key
+void gicp_mp_fill(hipStream_t s, const SortedCloud& src, PoseF T, const SortedCloud& tgt, float r2, double r, const int* off, int* idx, float* sq);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,

@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import RgcError  # noqa: F401  (re-exported)
+from ._lib import GicpMpParams, RgcError  # noqa: F401  (RgcError re-exported)
 from .registration import FastVGICP
 
 _dp, _fp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
@@ -69,6 +69,117 @@ class FastGICP(FastVGICP):
         it, cv, lf = C.c_int(0), C.c_int(0), C.c_int(0)
         self._chk(self._L.rgc_gicp_align(self._h, g.ctypes.data_as(_fp), fin.ctypes.data_as(_fp), H.ctypes.data_as(_dp),
                                          C.byref(fit) if want_fitness else None, C.byref(it), C.byref(cv), C.byref(lf)))
+        self._final, self._H = fin.reshape(4, 4), H.reshape(6, 6)
+        self._iterations, self._converged, self._lm_failed = it.value, bool(cv.value), bool(lf.value)
+        self._fitness = fit.value if want_fitness else None
+        if not want_output:
+            return None
+        out = np.empty((self._n_src, 3), np.float32)
+        self._chk(self._L.rgc_get_aligned(self._h, fin.ctypes.data_as(_fp), out.ctypes.data_as(_fp), 12))
+        return out
+
+
+class FastGICPMultiPoints(FastVGICP):
+    """fast_gicp::FastGICPMultiPoints (include/fast_gicp/gicp/experimental/fast_gicp_mp.hpp:40-53, fast_gicp_mp_impl.hpp:92-221) behind rgc_gicpmp_*: every
+    source point against the distance-weighted merge of every target Gaussian within the search radius, plain Gauss-Newton.  On the clouds of a
+    registration.FastVGICP context like FastGICP above; setRotationEpsilon, setTransformationEpsilon and setMaximumIterations set THIS method's limits
+    (defaults 1e-5, 1e-5, 64: fast_gicp_mp_impl.hpp:29-31), not the context's LM settings.
+
+        mp = FastGICPMultiPoints(device=0)
+        mp.setNeighborSearchRadius(0.5); mp.setInputTarget(map_cloud); mp.setInputSource(scan)
+        mp.align(guess, want_output=False); T = mp.getFinalTransformation(); ok = mp.hasConverged()"""
+
+    def __init__(self, device: int = 0):
+        super().__init__(device)
+        self._mp = GicpMpParams()
+        self._chk(self._L.rgc_gicpmp_get_params(self._h, C.byref(self._mp)))
+
+    def _push_mp(self):
+        self._chk(self._L.rgc_gicpmp_set_params(self._h, C.byref(self._mp)))
+
+    def _set_mp(self, name, value):
+        old = getattr(self._mp, name)
+        setattr(self._mp, name, value)
+        try:
+            self._push_mp()
+        except RgcError:
+            setattr(self._mp, name, old)
+            raise
+
+    def setNeighborSearchRadius(self, r):             # neighbor_search_radius_ (fast_gicp_mp.hpp:72; the reference has no setter for it)
+        self._set_mp("neighbor_search_radius", float(r))
+
+    def getNeighborSearchRadius(self) -> float:
+        return self._mp.neighbor_search_radius
+
+    def setRotationEpsilon(self, e):                  # fast_gicp_mp_impl.hpp:42-44
+        self._set_mp("rotation_epsilon", float(e))
+
+    def setTransformationEpsilon(self, e):            # pcl::Registration; is_converged, :124
+        self._set_mp("transformation_epsilon", float(e))
+
+    def setMaximumIterations(self, n):                # pcl::Registration; :92
+        self._set_mp("max_iterations", int(n))
+
+    def setNumThreads(self, n):                       # fast_gicp_mp_impl.hpp:47-55: CPU threads; nothing to set on the GPU
+        pass
+
+    def linearize(self, T, want_H=True):
+        """returns (cost, H, b) -- H and b None unless want_H"""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+        H, b, cost = np.zeros(36), np.zeros(6), C.c_double(0.0)
+        self._chk(self._L.rgc_gicpmp_linearize(self._h, T.ctypes.data_as(_dp), H.ctypes.data_as(_dp) if want_H else None,
+                                               b.ctypes.data_as(_dp) if want_H else None, C.byref(cost)))
+        return (cost.value, H.reshape(6, 6), b) if want_H else (cost.value, None, None)
+
+    def compute_error(self, T):
+        raise NotImplementedError("FastGICPMultiPoints has no frozen cost (the reference class has no compute_error)")
+
+    def _counts(self):
+        n, m = C.c_int(0), C.c_longlong(0)
+        self._chk(self._L.rgc_gicpmp_num_correspondences(self._h, C.byref(n), C.byref(m)))
+        return n.value, m.value
+
+    @property
+    def num_correspondences(self) -> int:
+        """source points with at least one neighbour at the last linearize"""
+        return self._counts()[0]
+
+    @property
+    def num_pairs(self) -> int:
+        """neighbours of all source points at the last linearize"""
+        return self._counts()[1]
+
+    @property
+    def num_candidates(self) -> int:
+        """target points the gather looked at over all source points at the last linearize"""
+        m = C.c_longlong(0)
+        self._chk(self._L.rgc_gicpmp_num_candidates(self._h, C.byref(m)))
+        return m.value
+
+    def merged(self):
+        """(count int32 (n,), sum_w (n,), mean (n, 3), cov6 (n, 6: xx xy xz yy yz zz)) of the last linearize, in the source's order"""
+        n = self._n_src
+        cnt, sw, mean, cov = np.empty(n, np.int32), np.empty(n), np.empty((n, 3)), np.empty((n, 6))
+        self._chk(self._L.rgc_gicpmp_get_merged(self._h, cnt.ctypes.data_as(_ip), sw.ctypes.data_as(_dp), mean.ctypes.data_as(_dp), cov.ctypes.data_as(_dp)))
+        return cnt, sw, mean, cov
+
+    def neighbors(self, cap=None):
+        """(offsets int32 (n + 1,), idx int32, sq_dist float32) of the last linearize: row i is idx[offsets[i]:offsets[i + 1]], original target indices"""
+        total = self.num_pairs if cap is None else int(cap)
+        off, idx, sq = np.empty(self._n_src + 1, np.int32), np.empty(max(total, 1), np.int32), np.empty(max(total, 1), np.float32)
+        nt = C.c_longlong(0)
+        self._chk(self._L.rgc_gicpmp_get_neighbors(self._h, off.ctypes.data_as(_ip), idx.ctypes.data_as(_ip), sq.ctypes.data_as(_fp), total, C.byref(nt)))
+        return off, idx[:nt.value], sq[:nt.value]
+
+    def align(self, guess=None, want_output=True, want_fitness=False):
+        """pcl::Registration::align(output, guess): the transformed source cloud (n, 3) float32, or None if want_output=False"""
+        g = np.ascontiguousarray(np.eye(4) if guess is None else guess, dtype=np.float32).reshape(16)
+        fin, H = np.empty(16, np.float32), np.empty(36)
+        fit = C.c_double(0.0)
+        it, cv, lf = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self._L.rgc_gicpmp_align(self._h, g.ctypes.data_as(_fp), fin.ctypes.data_as(_fp), H.ctypes.data_as(_dp),
+                                           C.byref(fit) if want_fitness else None, C.byref(it), C.byref(cv), C.byref(lf)))
         self._final, self._H = fin.reshape(4, 4), H.reshape(6, 6)
         self._iterations, self._converged, self._lm_failed = it.value, bool(cv.value), bool(lf.value)
         self._fitness = fit.value if want_fitness else None
