@@ -11,15 +11,9 @@ using namespace rgcapi;
 // LDLT solve, the 4x4 product) are rgc_lm.h's, shared with the device.
 int rgcapi::lm_solve(rgc_ctx* c, const LmSystem& sys, const float guess[16], LmResult* r) {
   const rgc_params& P = c->prm;
+  r->open(guess);
   double* x0 = r->x0;
-  for (int i = 0; i < 12; i++) x0[i] = (double)guess[i];
-  x0[12] = x0[13] = x0[14] = 0.0;
-  x0[15] = 1.0;
   double lambda = -1.0;  // :56
-  r->conv = r->failed = false;
-  r->iters = 0;
-  memset(r->Hfin, 0, sizeof(r->Hfin));
-  for (int i = 0; i < 6; i++) r->Hfin[i * 7] = 1.0;  // final_hessian_.setIdentity(), :21
   for (int it = 0; it < P.max_iterations && !r->conv; it++) {  // :65
     r->iters = it + 1;
     double H[36], b[6], y0, delta[16], d[6], xi[16], yi;
@@ -66,6 +60,14 @@ int rgcapi::lm_solve(rgc_ctx* c, const LmSystem& sys, const float guess[16], LmR
     r->conv = rgck::lm_is_converged(delta, P.rotation_eps, P.translation_eps);  // :74
   }
   for (int i = 0; i < 16; i++) r->fin[i] = (float)x0[i];  // :77
+  return RGC_OK;
+}
+
+// the k folded sums of a method (d_out, behind the launches on the context's stream) in its pinned buffer h_out, the launches checked
+static int read_sums(rgc_ctx* c, double* h_out, const DevBuf& d_out, int k) {
+  HIPCHK(c, hipMemcpyAsync(h_out, d_out.p, sizeof(double) * k, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
   return RGC_OK;
 }
 
@@ -255,9 +257,7 @@ static int ndt_run_terms(rgc_ctx* c, const double T[16], bool find, bool want_H,
   rgck::ndt_terms(c->stream, d2d, find ? 1 : 0, sc.in, sc.stride_f, sc.vox.as<const double>(), n, pose_from(T), pose_from(c->ndt_Tlin), tg.grid,
                   tg.voxels(), c->ndt_offs.as<const int>(), noff, c->ndt_corr.as<int>(), want_H ? 1 : 0,
                   c->ndt_partials.as<double>(), c->ndt_ipartials.as<int>(), c->ndt_out.as<double>());
-  HIPCHK(c, hipMemcpyAsync(c->ndt_h_out, c->ndt_out.p, sizeof(double) * 29, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
+  if ((rc = read_sums(c, c->ndt_h_out, c->ndt_out, 29))) return rc;
   memcpy(out, c->ndt_h_out, sizeof(double) * 29);
   if (find) {
     c->ndt_corr_valid = true;
@@ -436,9 +436,7 @@ static int gicp_do_linearize(rgc_ctx* c, const double T[16], double* H, double* 
   rgck::gicp_correspond(c->stream, sc.sorted(), posef_from(T32), tg.sorted(), c->gicp_dmax * c->gicp_dmax, c->gicp_corr.as<int>(), c->gicp_key.as<float>());
   rgck::gicp_terms(c->stream, sc.sorted(), tg.sorted(), c->gicp_corr.as<const int>(), gicp_cov_of(sc), gicp_cov_of(tg), pose_from(T), want,
                    c->gicp_M.as<double>(), c->gicp_partials.as<double>(), c->gicp_out.as<double>());
-  HIPCHK(c, hipMemcpyAsync(c->gicp_h_out, c->gicp_out.p, sizeof(double) * (rgck::kAccum + 1), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
+  if ((rc = read_sums(c, c->gicp_h_out, c->gicp_out, rgck::kAccum + 1))) return rc;
   const double* o = c->gicp_h_out;
   c->gicp_valid = true;
   c->gicp_n = n;
@@ -455,9 +453,8 @@ static int gicp_do_error(rgc_ctx* c, const double T[16], double* cost) {
   const Cloud& tg = c->tgt;
   rgck::gicp_error(c->stream, sc.sorted(), tg.sorted(), c->gicp_corr.as<const int>(), c->gicp_M.as<const double>(), pose_from(T),
                    c->gicp_partials.as<double>(), c->gicp_out.as<double>());
-  HIPCHK(c, hipMemcpyAsync(c->gicp_h_out, c->gicp_out.p, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
+  const int rc = read_sums(c, c->gicp_h_out, c->gicp_out, 1);
+  if (rc) return rc;
   *cost = c->gicp_h_out[0];
   return RGC_OK;
 }
@@ -509,6 +506,13 @@ int rgc_gicp_get_correspondences(rgc_ctx* c, int* idx, float* sq_dist) {
   return RGC_OK;
 }
 
+// the fitness score of a solve's final pose as rgc_align gives it (NaN for a pose that is not finite); fitness is nullable
+static int gicp_final_fitness(rgc_ctx* c, const LmResult& r, double* fitness) {
+  if (!fitness) return RGC_OK;
+  if (!pose12_finite(r.fin)) { *fitness = (double)NAN; return RGC_OK; }
+  return do_fitness(c, r.fin, fitness);
+}
+
 // computeTransformation (lm_solve) over the two calls above; the fitness score of the final pose as rgc_align gives it
 int rgc_gicp_align(rgc_ctx* c, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged, int* lm_failed) {
   if (!c || !guess) return RGC_ERR_INVALID;
@@ -520,11 +524,7 @@ int rgc_gicp_align(rgc_ctx* c, const float guess[16], float final_T[16], double 
   LmResult r;
   if ((rc = lm_solve(c, sys, guess, &r))) return rc;
   r.write(final_T, final_H, iterations, converged, lm_failed);
-  if (fitness) {
-    if (!pose12_finite(r.fin)) *fitness = (double)NAN;
-    else if ((rc = do_fitness(c, r.fin, fitness))) return rc;
-  }
-  return RGC_OK;
+  return gicp_final_fitness(c, r, fitness);
 }
 
 // ---- FastGICPMultiPoints: GICP on radius-merged target distributions (include/fast_gicp/gicp/experimental/fast_gicp_mp_impl.hpp:92-221) on the context's own clouds ----
@@ -582,9 +582,7 @@ static int gicp_mp_do_linearize(rgc_ctx* c, const double T[16], double* H, doubl
                       c->gicp_mp_cand.as<int>());
   rgck::gicp_mp_terms(c->stream, sc.sorted(), c->gicp_mp_merged.as<const double>(), gicp_cov_of(sc), pose_from(T), want, c->gicp_mp_partials.as<double>(),
                       c->gicp_mp_out.as<double>());
-  HIPCHK(c, hipMemcpyAsync(c->gicp_mp_h_out, c->gicp_mp_out.p, sizeof(double) * rgck::kGicpMpAcc, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipGetLastError());
+  if ((rc = read_sums(c, c->gicp_mp_h_out, c->gicp_mp_out, rgck::kGicpMpAcc))) return rc;
   const double* o = c->gicp_mp_h_out;
   c->gicp_mp_valid = true;
   c->gicp_mp_n = n;
@@ -699,13 +697,7 @@ int rgc_gicpmp_align(rgc_ctx* c, const float guess[16], float final_T[16], doubl
   if (rc) return rc;
   const rgc_gicp_mp_params& P = c->gicp_mp_prm;
   LmResult r;
-  for (int i = 0; i < 12; i++) r.x0[i] = (double)guess[i];
-  r.x0[12] = r.x0[13] = r.x0[14] = 0.0;
-  r.x0[15] = 1.0;
-  r.conv = r.failed = false;
-  r.iters = 0;
-  memset(r.Hfin, 0, sizeof(r.Hfin));
-  for (int i = 0; i < 6; i++) r.Hfin[i * 7] = 1.0;
+  r.open(guess);
   for (int it = 0; it < P.max_iterations; it++) {  // :92
     if (!gicp_pose_ok(r.x0)) { r.failed = true; break; }
     r.iters = it + 1;
@@ -723,11 +715,7 @@ int rgc_gicpmp_align(rgc_ctx* c, const float guess[16], float final_T[16], doubl
   }
   for (int i = 0; i < 16; i++) r.fin[i] = (float)r.x0[i];
   r.write(final_T, final_H, iterations, converged, failed);
-  if (fitness) {
-    if (!pose12_finite(r.fin)) *fitness = (double)NAN;
-    else if ((rc = do_fitness(c, r.fin, fitness))) return rc;
-  }
-  return RGC_OK;
+  return gicp_final_fitness(c, r, fitness);
 }
 
 }  // extern "C"

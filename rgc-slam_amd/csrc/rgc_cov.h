@@ -1,6 +1,7 @@
 // rgc_cov.h -- what a neighbourhood's second moment becomes: the symmetric 3x3 device helpers (one Jacobi rotation, the eigen-decomposition,
 // the inverse) and the RegularizationMethod applied to a covariance, shared by the translation units that estimate covariances:
-// rgc_kernels.hip (cov6_of behind the exact kNN, the PLANE normal, the solve) and rgc_rbf.hip (k_rbf_cov6).  Everything here is
+// rgc_kernels.hip (cov6_of behind the exact kNN, the PLANE normal, the solve) and rgc_rbf.hip (k_rbf_cov6); inv_sym3 is also the one inverse of
+// the Mahalanobis terms of rgc_ndt.hip, rgc_gicp.hip and rgc_gicp_mp.hip (their other shared pieces: rgc_terms.h).  Everything here is
 // __forceinline__, as in rgc_nn.h: each kernel inlines its own copy.  Compile with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>

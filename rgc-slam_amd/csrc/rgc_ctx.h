@@ -418,6 +418,15 @@ struct LmResult {
   float fin[16];            // ... the pose as the caller gets it (lsq_registration_impl.hpp:77)
   int iters;                // outer iterations started
   bool conv, failed;
+  void open(const float guess[16]) {  // x0 = the guess, final_hessian_.setIdentity() (lsq_registration_impl.hpp:21), nothing decided yet
+    for (int i = 0; i < 12; i++) x0[i] = (double)guess[i];
+    x0[12] = x0[13] = x0[14] = 0.0;
+    x0[15] = 1.0;
+    memset(Hfin, 0, sizeof(Hfin));
+    for (int i = 0; i < 6; i++) Hfin[i * 7] = 1.0;
+    conv = failed = false;
+    iters = 0;
+  }
   void write(float final_T[16], double final_H[36], int* iterations, int* converged, int* lm_failed) const {  // (each nullable)
     if (final_T) memcpy(final_T, fin, sizeof(fin));
     if (final_H) memcpy(final_H, Hfin, sizeof(Hfin));

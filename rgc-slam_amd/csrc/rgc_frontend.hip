@@ -9,17 +9,12 @@
 #include <limits.h>
 
 #include "rgc_kernels.h"
+#include "rgc_terms.h"
 
 namespace rgck {
 
 constexpr int WAVE = 64;
 constexpr int FE_T = 256;
-
-__device__ __forceinline__ double fe_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
 
 // ---- A1 + A2a: validity, ring id (:111-113, :141-183, :732-763) ----
 __device__ __forceinline__ int ring_of(float x, float y, float z, int NS) {
@@ -336,19 +331,7 @@ k_fe_ground(const float4* __restrict__ C, int cs_in, const int* __restrict__ csp
   }
   if (j < cs) { gmark[j] = mult > 0 ? 1 : 0; mult_out[j] = mult; seedcnt[j] = sc; }
   else if (j < cs_in) seedcnt[j] = 0;  // the scan of the seed counts runs over the launch's bound
-  __shared__ double red[FE_T / WAVE][11];
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-#pragma unroll
-  for (int a = 0; a < 11; a++) {
-    const double v = fe_wave_sum(acc[a]);
-    if (lane == 0) red[w][a] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 11) {
-    double s = 0;
-    for (int t = 0; t < FE_T / WAVE; t++) s += red[t][threadIdx.x];
-    partials[(size_t)blockIdx.x * 11 + threadIdx.x] = s;
-  }
+  block_sum_store<FE_T>(acc, partials + (size_t)blockIdx.x * 11);  // (its rows are folded from +0.0: k_fe_fold_fit)
 }
 
 // distance pass (:386-402): sums {sum dw, sum dw * n.p} with multiplicity
@@ -357,7 +340,7 @@ k_fe_ground_dist(const float4* __restrict__ C, int cs_in, const int* __restrict_
   // fit: centre (3), normal (3), eigenvectors (9), ground present (1) -- written by k_fe_fold_fit, never seen by the host in between
   const int cs = csp ? min(cs_in, *csp) : cs_in;  // the sweep's size on the device (k_fe_hist_scan), cs_in = the launch's bound
   const int j = blockIdx.x * FE_T + threadIdx.x;
-  double a0 = 0, a1 = 0;
+  double acc[2] = {0, 0};
   if (fit[15] != 0.0 && j < cs && mult[j] > 0) {
     const double cx = fit[0], cy = fit[1], cz = fit[2], nx = fit[3], ny = fit[4], nz = fit[5];
     const float4 p = C[j];
@@ -365,19 +348,10 @@ k_fe_ground_dist(const float4* __restrict__ C, int cs_in, const int* __restrict_
     const double dl = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     double dw = dl == 0 ? 1.0 : 1 - 100 * fabs((nx * d[0] + ny * d[1] + nz * d[2]) / dl);
     if (dw < 0) dw = 0.1;
-    a0 = dw * mult[j];
-    a1 = dw * mult[j] * (nx * (double)p.x + ny * (double)p.y + nz * (double)p.z);
+    acc[0] = dw * mult[j];
+    acc[1] = dw * mult[j] * (nx * (double)p.x + ny * (double)p.y + nz * (double)p.z);
   }
-  __shared__ double red[FE_T / WAVE][2];
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-  a0 = fe_wave_sum(a0); a1 = fe_wave_sum(a1);
-  if (lane == 0) { red[w][0] = a0; red[w][1] = a1; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double s = 0;
-    for (int t = 0; t < FE_T / WAVE; t++) s += red[t][threadIdx.x];
-    partials[(size_t)blockIdx.x * 2 + threadIdx.x] = s;
-  }
+  block_sum_store<FE_T>(acc, partials + (size_t)blockIdx.x * 2);  // (its rows are folded from +0.0: k_fe_fold)
 }
 
 // Plane through the weighted ground set (:358-377) on the device, so that the host does not have to see the sums before the distance
@@ -431,9 +405,7 @@ __device__ void fe_ground_fit(const double* g11, double* __restrict__ fit) {
 __global__ void __launch_bounds__(11 * WAVE) k_fe_fold_fit(const double* __restrict__ partials, int nrows, double* __restrict__ out11, double* __restrict__ fit) {
   __shared__ double g[11];
   const int a = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
-  double sum = 0;
-  for (int r = lane; r < nrows; r += WAVE) sum += partials[(size_t)r * 11 + a];
-  sum = fe_wave_sum(sum);
+  const double sum = fold_column(partials, nrows, 11, a, lane);
   if (lane == 0) { out11[a] = sum; g[a] = sum; }
   __syncthreads();
   if (threadIdx.x == 0) fe_ground_fit(g, fit);
@@ -442,9 +414,7 @@ __global__ void __launch_bounds__(11 * WAVE) k_fe_fold_fit(const double* __restr
 // fixed-order fold of per-block rows (deterministic)
 __global__ void __launch_bounds__(WAVE) k_fe_fold(const double* __restrict__ partials, int nrows, int ncols, double* __restrict__ out) {
   const int a = blockIdx.x, lane = threadIdx.x;
-  double s = 0;
-  for (int r = lane; r < nrows; r += WAVE) s += partials[(size_t)r * ncols + a];
-  s = fe_wave_sum(s);
+  const double s = fold_column(partials, nrows, ncols, a, lane);
   if (lane == 0) out[a] = s;
 }
 

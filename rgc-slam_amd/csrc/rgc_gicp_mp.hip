@@ -3,11 +3,14 @@
 // include/fast_gicp/gicp/experimental/fast_gicp_mp_impl.hpp:92-221); written from its formulas, in the project's arithmetic: the query and the search
 // key in fp32 (never FMA-contracted: -ffp-contract=off), everything after them fp64, every sum in a fixed order, no floating-point atomics.
 // Citations are relative to rgc_slam/ of the reference (ROBOT-WSC/RGC-SLAM).
-// A translation unit of its own: the device code of every other kernel of the library stays what it was.  The radius gather (k_gicp_mp_merge: fp32
+// A translation unit of its own, over the pieces every solver shares: the term (under W = M M), the covariance of a sorted point, the shuffle-tree
+// block store and the column fold are rgc_terms.h's, the inverse rgc_cov.h's, the fp32 query rgc_nn.h's.  The radius gather (k_gicp_mp_merge: fp32
 // candidates, eleven fp64 accumulators) and the term (k_gicp_mp_terms: 30 accumulators) are two kernels, as in rgc_gicp.hip -- no spill, no private
 // segment, no accumulator registers; nothing waits on another workgroup.
 #include "rgc_kernels.h"
 #include "rgc_nn.h"
+#include "rgc_cov.h"
+#include "rgc_terms.h"
 
 namespace rgck {
 
@@ -76,28 +79,6 @@ __device__ __forceinline__ int mp_walk(const double q[3], double reach, const in
   return cnt;
 }
 
-__device__ __forceinline__ void mp_query(const float4& sp, const PoseF& T, float& qx, float& qy, float& qz) {
-  const float x = sp.x, y = sp.y, z = sp.z;  // fast_gicp_mp_impl.hpp:141, as k_gicp_correspond computes it
-  qx = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
-  qy = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
-  qz = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
-}
-
-// the covariance of sorted target point s as its upper triangle, as rgc_gicp.hip's gicp_cov6 (fast_gicp_impl.hpp:280-293)
-template <bool kGeneral>
-__device__ __forceinline__ void mp_cov6(const double* __restrict__ c6, const double* __restrict__ nx, const double* __restrict__ ny,
-                                        const double* __restrict__ nz, int n, int s, double C[6]) {
-  if (kGeneral) {
-#pragma unroll
-    for (int a = 0; a < 6; a++) C[a] = c6[(size_t)a * n + s];
-  } else {
-    const double v0 = nx[s], v1 = ny[s], v2 = nz[s];
-    C[0] = 1.0 - 0.999 * v0 * v0; C[1] = 0.0 - 0.999 * v0 * v1; C[2] = 0.0 - 0.999 * v0 * v2;
-    C[3] = 1.0 - 0.999 * v1 * v1; C[4] = 0.0 - 0.999 * v1 * v2;
-    C[5] = 1.0 - 0.999 * v2 * v2;
-  }
-}
-
 constexpr int kMpMerged = kGicpMpMerged;  // count, sum of weights, mean (3), covariance (6: xx xy xz yy yz zz)
 
 // fast_gicp_mp_impl.hpp:139-153 (update_correspondences: the radius search) and :180-195 (the merge of loss_ls) for sorted source point s, by a
@@ -118,7 +99,8 @@ __global__ void __launch_bounds__(MP_T) k_gicp_mp_merge(const float4* __restrict
   int ncand = 0;
   if (s < ns) {  // (a whole group takes this branch or none of it does)
     float qx, qy, qz;
-    mp_query(SP[s], T, qx, qy, qz);
+    const float4 sp = SP[s];
+    transform_f32(T, sp.x, sp.y, sp.z, qx, qy, qz);  // fast_gicp_mp_impl.hpp:141
     const double q[3] = {(double)qx, (double)qy, (double)qz};
     ncand = mp_walk<G>(q, reach, tstart, g, lane, [&](int i) {
       const float4 cp = point_at(TP, (unsigned)i << 4);
@@ -126,7 +108,7 @@ __global__ void __launch_bounds__(MP_T) k_gicp_mp_merge(const float4* __restrict
       if (key < r2) {
         const double w = fmax(1e-3, fmin(1.0, 1.0 - (double)(float)sqrt((double)key) / r));
         double C[6];
-        mp_cov6<kGenB>(c6B, nxB, nyB, nzB, nt, i, C);
+        point_cov6<kGenB>(c6B, nxB, nyB, nzB, nt, i, C);
         acc[0] += 1.0;
         acc[1] += w;
         acc[2] += w * (double)cp.x; acc[3] += w * (double)cp.y; acc[4] += w * (double)cp.z;
@@ -154,39 +136,6 @@ __global__ void __launch_bounds__(MP_T) k_gicp_mp_merge(const float4* __restrict
   }
 }
 
-// inverse of a symmetric 3x3 by its adjugate (rgc_gicp.hip's gicp_inv_sym3); false (M untouched) if the determinant is exactly zero
-__device__ __forceinline__ bool mp_inv_sym3(const double S[6], double M[6]) {
-  const double a = S[0], b = S[1], c = S[2], d = S[3], e = S[4], f = S[5];
-  const double c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
-  const double det = a * c00 + b * c01 + c * c02;
-  if (det == 0.0) return false;
-  const double id = 1.0 / det;
-  M[0] = c00 * id; M[1] = c01 * id; M[2] = c02 * id;
-  M[3] = (a * f - c * c) * id; M[4] = (b * c - a * e) * id; M[5] = (a * d - b * b) * id;
-  return true;
-}
-
-// Sum of the block's NACC accumulators in a FIXED order: the six shuffle steps of a wave, then the four waves ascending (rgc_gicp.hip's gicp_block_store)
-template <int NACC>
-__device__ __forceinline__ void mp_block_store(double (&acc)[NACC], double* __restrict__ row) {
-  __shared__ double red[MP_T / MP_WAVE][NACC];
-  const int lane = threadIdx.x & (MP_WAVE - 1), w = threadIdx.x / MP_WAVE;
-#pragma unroll
-  for (int a = 0; a < NACC; a++) {
-    double v = acc[a];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    if (lane == 0) red[w][a] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NACC) {
-    double t = red[0][threadIdx.x];
-#pragma unroll
-    for (int j = 1; j < MP_T / MP_WAVE; j++) t += red[j][threadIdx.x];
-    row[threadIdx.x] = t;
-  }
-}
-
 constexpr int kMpAcc = kGicpMpAcc;  // 21 upper-triangular H, 6 b, the cost, the source points with a neighbour, the neighbours (exact in a double: < 2^53)
 
 // fast_gicp_mp_impl.hpp:197-213 for sorted source point s with a non-empty ball (:176): a = R p + t, d = mean_B - a, M = (cov_B + R C_A[s] R^T)^-1
@@ -206,7 +155,8 @@ __global__ void __launch_bounds__(MP_T) k_gicp_mp_terms(const float4* __restrict
     const float4 sp = SP[s];
     const double p0 = (double)sp.x, p1 = (double)sp.y, p2 = (double)sp.z;
     double CA[6], S[6];
-    mp_cov6<kGenA>(c6A, nxA, nyA, nzA, ns, s, CA);
+    point_cov6<kGenA>(c6A, nxA, nyA, nzA, ns, s, CA);
+    // (R C_A R^T in place, as in k_gicp_terms and for its reason: rgc_terms.h, rcrt6)
     const double Cs[3][3] = {{CA[0], CA[1], CA[2]}, {CA[1], CA[3], CA[4]}, {CA[2], CA[4], CA[5]}};
     double RC[3][3];
 #pragma unroll
@@ -224,7 +174,7 @@ __global__ void __launch_bounds__(MP_T) k_gicp_mp_terms(const float4* __restrict
         }
     }
     double M[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    mp_inv_sym3(S, M);
+    inv_sym3(S, M);
     // W = M M (symmetric: M is)
     const double W[6] = {M[0] * M[0] + M[1] * M[1] + M[2] * M[2], M[0] * M[1] + M[1] * M[3] + M[2] * M[4], M[0] * M[2] + M[1] * M[4] + M[2] * M[5],
                          M[1] * M[1] + M[3] * M[3] + M[4] * M[4], M[1] * M[2] + M[3] * M[4] + M[4] * M[5], M[2] * M[2] + M[4] * M[4] + M[5] * M[5]};
@@ -232,44 +182,17 @@ __global__ void __launch_bounds__(MP_T) k_gicp_mp_terms(const float4* __restrict
     const double q1 = T.R[3] * p0 + T.R[4] * p1 + T.R[5] * p2 + T.t[1];
     const double q2 = T.R[6] * p0 + T.R[7] * p1 + T.R[8] * p2 + T.t[2];
     const double e0 = merged[(size_t)2 * ns + s] - q0, e1 = merged[(size_t)3 * ns + s] - q1, e2 = merged[(size_t)4 * ns + s] - q2;
-    const double We0 = W[0] * e0 + W[1] * e1 + W[2] * e2;
-    const double We1 = W[1] * e0 + W[3] * e1 + W[4] * e2;
-    const double We2 = W[2] * e0 + W[4] * e1 + W[5] * e2;
-    acc[27] = e0 * We0 + e1 * We1 + e2 * We2;
+    gn_term<false>(W, q0, q1, q2, e0, e1, e2, 1.0, want_H, acc);  // the term under W = M M; no weight
     acc[28] = 1.0;
     acc[29] = count;
-    if (want_H) {
-      const double J[3][6] = {{0.0, -q2, q1, -1.0, 0.0, 0.0}, {q2, 0.0, -q0, 0.0, -1.0, 0.0}, {-q1, q0, 0.0, 0.0, 0.0, -1.0}};
-      double WJ[3][6];
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        WJ[0][c] = W[0] * J[0][c] + W[1] * J[1][c] + W[2] * J[2][c];
-        WJ[1][c] = W[1] * J[0][c] + W[3] * J[1][c] + W[4] * J[2][c];
-        WJ[2][c] = W[2] * J[0][c] + W[4] * J[1][c] + W[5] * J[2][c];
-      }
-      int u = 0;
-#pragma unroll
-      for (int a = 0; a < 6; a++) {
-#pragma unroll
-        for (int c = a; c < 6; c++) {
-          acc[u] = J[0][a] * WJ[0][c] + J[1][a] * WJ[1][c] + J[2][a] * WJ[2][c];
-          u++;
-        }
-      }
-#pragma unroll
-      for (int a = 0; a < 6; a++) acc[21 + a] = J[0][a] * We0 + J[1][a] * We1 + J[2][a] * We2;
-    }
   }
-  mp_block_store<kMpAcc>(acc, partials + (size_t)blockIdx.x * kMpAcc);
+  block_sum_store<MP_T>(acc, partials + (size_t)blockIdx.x * kMpAcc);
 }
 
-// the workgroups' rows folded in a fixed order, one wave per column (rgc_gicp.hip's k_gicp_fold)
+// the workgroups' rows folded in a fixed order, one wave per column (fold_column)
 __global__ void __launch_bounds__(MP_WAVE) k_gicp_mp_fold(const double* __restrict__ partials, int nb, int ncol, double* __restrict__ out) {
   const int col = blockIdx.x, lane = threadIdx.x;
-  double t = 0.0;
-  for (int b = lane; b < nb; b += MP_WAVE) t += partials[(size_t)b * ncol + col];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o);
+  const double t = fold_column(partials, nb, ncol, col, lane);
   if (lane == 0) out[col] = t;
 }
 
@@ -303,7 +226,7 @@ __global__ void __launch_bounds__(MP_T) k_gicp_mp_fill(const float4* __restrict_
   const int o = __float_as_int(sp.w);
   if (o < 0 || o >= ns) return;
   float qx, qy, qz;
-  mp_query(sp, T, qx, qy, qz);
+  transform_f32(T, sp.x, sp.y, sp.z, qx, qy, qz);
   const double q[3] = {(double)qx, (double)qy, (double)qz};
   int at = off[o];
   const int end = off[o + 1];

@@ -25,6 +25,7 @@
 #include "rgc_nn.h"
 #include "rgc_lm.h"
 #include "rgc_cov.h"
+#include "rgc_terms.h"
 #include <hip/hip_ext.h>
 
 #include <limits.h>
@@ -48,11 +49,7 @@ __device__ __forceinline__ int wave_max(int v) {
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
   return v;
 }
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-  return v;
-}
+// (wave_sum: rgc_terms.h)
 
 __device__ __forceinline__ void wave_lds_fence() {  // LDS is in-order within a wave: only the compiler must not reorder
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -2870,22 +2867,9 @@ __device__ __forceinline__ void neighbor_offset(int noff, int o, int& ox, int& o
 template <int NACC, bool kWriteThrough = false>
 __device__ __forceinline__ void block_reduce_store(double (&acc)[NACC], double* __restrict__ row) {
   static_assert(NACC <= 32 && LIN_T == 256, "thread -> (accumulator, eighth) mapping");
-  if constexpr (NACC <= 2) {
-    __shared__ double red[LIN_T / WAVE][NACC];
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-#pragma unroll
-    for (int a = 0; a < NACC; a++) {
-      double v = wave_sum(acc[a]);
-      if (lane == 0) red[w][a] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NACC) {
-      double s = 0;
-#pragma unroll
-      for (int j = 0; j < LIN_T / WAVE; j++) s += red[j][threadIdx.x];
-      if (kWriteThrough) __hip_atomic_store(&row[threadIdx.x], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else row[threadIdx.x] = s;
-    }
+  if constexpr (NACC <= 2) {  // (k_error, k_error_dev: one sum -- the shuffle-tree store of rgc_terms.h; their rows are folded from +0.0, k_fold)
+    static_assert(!kWriteThrough, "no row of one or two sums is handed over inside a launch");
+    block_sum_store<LIN_T>(acc, row);
   } else {
     constexpr int PITCH = NACC | 1;  // odd pitch: the quads of a wave spread over the banks
     __shared__ double quads[LIN_T / 4][PITCH];
@@ -2917,21 +2901,26 @@ __device__ __forceinline__ void block_reduce_store(double (&acc)[NACC], double* 
   }
 }
 
-// (the body, with the point and its normal already in registers: k_lm_step fetches them before it takes the previous launch's decision)
-__device__ __forceinline__ void linearize_point_pre(const float4 pp, const double a0, const double a1, const double a2, int i, int n, const Pose& T,
-                                                    const Grid& g, const int* __restrict__ cell_voxel, const double* __restrict__ vox, int noff,
-                                                    int* __restrict__ corr_v, double* __restrict__ corr_M, int want_H, double (&acc)[kAccum],
-                                                    int& ncorr, int* __restrict__ miss = nullptr, const int* __restrict__ need = nullptr, int stamp = 0) {
+// R C_A R^T of a source point under its unit normal n: I - 0.999 (R n)(R n)^T
+__device__ __forceinline__ void rcrt6_of_normal(const Pose& T, const double a0, const double a1, const double a2, double (&CA)[6]) {
+  const double r0 = T.R[0] * a0 + T.R[1] * a1 + T.R[2] * a2;
+  const double r1 = T.R[3] * a0 + T.R[4] * a1 + T.R[5] * a2;
+  const double r2 = T.R[6] * a0 + T.R[7] * a1 + T.R[8] * a2;
+  CA[0] = 1.0 - 0.999 * r0 * r0; CA[1] = -0.999 * r0 * r1; CA[2] = -0.999 * r0 * r2;
+  CA[3] = 1.0 - 0.999 * r1 * r1; CA[4] = -0.999 * r1 * r2; CA[5] = 1.0 - 0.999 * r2 * r2;
+}
+
+// per-point work of FastVGICP::update_correspondences + linearize (fast_vgicp_impl.hpp:73-180) for sorted source point i, the point already in
+// registers (k_lm_step fetches it before it takes the previous launch's decision).  CA = R C_A R^T, the caller's: from the unit normal
+// (rcrt6_of_normal, the tuned route) or from the six entries (rcrt6, the general route).
+__device__ __forceinline__ void linearize_point(const float4 pp, const double (&CA)[6], int i, int n, const Pose& T, const Grid& g,
+                                                const int* __restrict__ cell_voxel, const double* __restrict__ vox, int noff,
+                                                int* __restrict__ corr_v, double* __restrict__ corr_M, int want_H, double (&acc)[kAccum],
+                                                int& ncorr, int* __restrict__ miss = nullptr, const int* __restrict__ need = nullptr, int stamp = 0) {
     const double p0 = (double)pp.x, p1 = (double)pp.y, p2 = (double)pp.z;
     const double q0 = T.R[0] * p0 + T.R[1] * p1 + T.R[2] * p2 + T.t[0];
     const double q1 = T.R[3] * p0 + T.R[4] * p1 + T.R[5] * p2 + T.t[1];
     const double q2 = T.R[6] * p0 + T.R[7] * p1 + T.R[8] * p2 + T.t[2];
-    // R C_A R^T = I - 0.999 (R n)(R n)^T
-    const double r0 = T.R[0] * a0 + T.R[1] * a1 + T.R[2] * a2;
-    const double r1 = T.R[3] * a0 + T.R[4] * a1 + T.R[5] * a2;
-    const double r2 = T.R[6] * a0 + T.R[7] * a1 + T.R[8] * a2;
-    const double CA[6] = {1.0 - 0.999 * r0 * r0, -0.999 * r0 * r1, -0.999 * r0 * r2,
-                          1.0 - 0.999 * r1 * r1, -0.999 * r1 * r2, 1.0 - 0.999 * r2 * r2};
     const int cx = (int)floor(q0 / g.res - 0.5) - g.minc[0];
     const int cy = (int)floor(q1 / g.res - 0.5) - g.minc[1];
     const int cz = (int)floor(q2 / g.res - 0.5) - g.minc[2];
@@ -2964,41 +2953,8 @@ __device__ __forceinline__ void linearize_point_pre(const float4 pp, const doubl
       ncorr++;
       const double e0 = rec[0] - q0, e1 = rec[1] - q1, e2 = rec[2] - q2;
       const double w = sqrt(rec[9]);
-      const double Me0 = M[0] * e0 + M[1] * e1 + M[2] * e2;
-      const double Me1 = M[1] * e0 + M[3] * e1 + M[4] * e2;
-      const double Me2 = M[2] * e0 + M[4] * e1 + M[5] * e2;
-      acc[27] += w * (e0 * Me0 + e1 * Me1 + e2 * Me2);
-      if (!want_H) continue;
-      // J = [skew(q) | -I]  (3x6), columns [rot, trans]; H += w J^T M J, b += w J^T M e
-      const double J[3][6] = {{0.0, -q2, q1, -1.0, 0.0, 0.0}, {q2, 0.0, -q0, 0.0, -1.0, 0.0}, {-q1, q0, 0.0, 0.0, 0.0, -1.0}};
-      double MJ[3][6];
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        MJ[0][c] = M[0] * J[0][c] + M[1] * J[1][c] + M[2] * J[2][c];
-        MJ[1][c] = M[1] * J[0][c] + M[3] * J[1][c] + M[4] * J[2][c];
-        MJ[2][c] = M[2] * J[0][c] + M[4] * J[1][c] + M[5] * J[2][c];
-      }
-      int u = 0;
-#pragma unroll
-      for (int a = 0; a < 6; a++) {
-#pragma unroll
-        for (int c = a; c < 6; c++) {
-          acc[u] += w * (J[0][a] * MJ[0][c] + J[1][a] * MJ[1][c] + J[2][a] * MJ[2][c]);
-          u++;
-        }
-      }
-#pragma unroll
-      for (int a = 0; a < 6; a++) acc[21 + a] += w * (J[0][a] * Me0 + J[1][a] * Me1 + J[2][a] * Me2);
+      gn_term<true>(M, q0, q1, q2, e0, e1, e2, w, want_H, acc);  // cost += w e^T M e, H += w J^T M J, b += w J^T M e
     }
-}
-
-// per-point work of FastVGICP::update_correspondences + linearize (fast_vgicp_impl.hpp:73-180) for sorted source point i
-__device__ __forceinline__ void linearize_point(const float4* __restrict__ P, const double* __restrict__ nx, const double* __restrict__ ny,
-                                                const double* __restrict__ nz, int i, int n, const Pose& T, const Grid& g,
-                                                const int* __restrict__ cell_voxel, const double* __restrict__ vox, int noff,
-                                                int* __restrict__ corr_v, double* __restrict__ corr_M, int want_H, double (&acc)[kAccum],
-                                                int& ncorr, int* __restrict__ miss = nullptr, const int* __restrict__ need = nullptr, int stamp = 0) {
-  linearize_point_pre(P[i], nx[i], ny[i], nz[i], i, n, T, g, cell_voxel, vox, noff, corr_v, corr_M, want_H, acc, ncorr, miss, need, stamp);
 }
 
 __device__ __forceinline__ void block_count_store(int ncorr, int* __restrict__ dst) {  // exact integer block sum -> *dst
@@ -3025,7 +2981,11 @@ k_linearize(const float4* __restrict__ P,
 #pragma unroll
   for (int a = 0; a < kAccum; a++) acc[a] = 0.0;
   int ncorr = 0;
-  if (i < n) linearize_point(P, nx, ny, nz, i, n, T, g, cell_voxel, vox, noff, corr_v, corr_M, want_H, acc, ncorr);
+  if (i < n) {
+    double CA[6];
+    rcrt6_of_normal(T, nx[i], ny[i], nz[i], CA);
+    linearize_point(P[i], CA, i, n, T, g, cell_voxel, vox, noff, corr_v, corr_M, want_H, acc, ncorr);
+  }
   block_reduce_store<kAccum>(acc, partials + (size_t)blockIdx.x * kAccum);
   block_count_store(ncorr, ncorr_partials + blockIdx.x);
 }
@@ -3317,8 +3277,12 @@ __device__ __forceinline__ void lm_try_rows(const LmState& ls, int mode, int cur
 #pragma unroll
     for (int a = 0; a < kAccum; a++) lin[a] = 0.0;
     int ncorr = 0;
-    if (q.i < n) linearize_point_pre(q.p, q.n0, q.n1, q.n2, q.i, n, T, g, cell_voxel, vox, noff, mode == LM_MODE_LIN ? cv_cur : cv_nxt,
-                                     mode == LM_MODE_LIN ? cm_cur : cm_nxt, 1, lin, ncorr, fa.need ? miss : nullptr, fa.need, fa.stamp);
+    if (q.i < n) {
+      double CA[6];
+      rcrt6_of_normal(T, q.n0, q.n1, q.n2, CA);
+      linearize_point(q.p, CA, q.i, n, T, g, cell_voxel, vox, noff, mode == LM_MODE_LIN ? cv_cur : cv_nxt, mode == LM_MODE_LIN ? cm_cur : cm_nxt, 1, lin,
+                      ncorr, fa.need ? miss : nullptr, fa.need, fa.stamp);
+    }
 #pragma unroll
     for (int a = 0; a < kAccum; a++) acc[a] = lin[a];
     acc[kAccum] = (double)ncorr;  // exact: counts are far below 2^53
@@ -3579,9 +3543,7 @@ __global__ void __launch_bounds__(WAVE) k_fold(const double* __restrict__ partia
                                                 const int* __restrict__ ipartials, int* __restrict__ iout) {
   const int a = blockIdx.x, lane = threadIdx.x;
   if (a < NACC) {
-    double s = 0;
-    for (int r = lane; r < nrows; r += WAVE) s += partials[(size_t)r * NACC + a];
-    s = wave_sum(s);
+    const double s = fold_column(partials, nrows, NACC, a, lane);
     if (lane == 0) out[a] = s;
   } else if (ipartials) {
     int c = 0;
@@ -3615,11 +3577,8 @@ k_error(const float4* __restrict__ P, int n, Pose T, const double* __restrict__ 
 __device__ __forceinline__ float fitness_point(const float4* __restrict__ SP, int i, const PoseF& T, const float4* __restrict__ TP,
                                                const int* __restrict__ tstart, const Grid& g, bool* unresolved = nullptr, float* moved = nullptr) {
   const float4 sp = SP[i];
-  const float x = sp.x, y = sp.y, z = sp.z;
-  const float px = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
-  const float py = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
-  const float pz = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
-  float best;
+  float px, py, pz, best;
+  transform_f32(T, sp.x, sp.y, sp.z, px, py, pz);
   int bs;
   nn_search<false>(px, py, pz, TP, tstart, g, 1.0e300, best, bs, unresolved);
   if (moved) { moved[0] = px; moved[1] = py; moved[2] = pz; }
@@ -3775,11 +3734,8 @@ __global__ void k_transform_f32(const float* __restrict__ in, int stride_f, int 
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float* p = in + (size_t)i * stride_f;
-  const float x = p[0], y = p[1], z = p[2];
   float* o = out + (size_t)i * ostride_f;
-  o[0] = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
-  o[1] = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
-  o[2] = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+  transform_f32(T, p[0], p[1], p[2], o[0], o[1], o[2]);
 }
 
 __global__ void k_unsort3(const double* __restrict__ a, const double* __restrict__ b, const double* __restrict__ c,
@@ -3940,63 +3896,8 @@ k_voxel_build_general(const float4* __restrict__ P, const double* __restrict__ c
   vox_cell[v] = cell;
 }
 
-// FastVGICP::update_correspondences + linearize (fast_vgicp_impl.hpp:73-180) for sorted source point i with a GENERAL source covariance:
-// linearize_point_pre above with R C_A R^T computed from the six entries instead of from the normal
-__device__ __forceinline__ void linearize_point_general(const float4 pp, const double* __restrict__ c6, int i, int n, const Pose& T, const Grid& g,
-                                                        const int* __restrict__ cell_voxel, const double* __restrict__ vox, int noff,
-                                                        int* __restrict__ corr_v, double* __restrict__ corr_M, int want_H, double (&acc)[kAccum],
-                                                        int& ncorr) {
-  const double p0 = (double)pp.x, p1 = (double)pp.y, p2 = (double)pp.z;
-  const double q0 = T.R[0] * p0 + T.R[1] * p1 + T.R[2] * p2 + T.t[0];
-  const double q1 = T.R[3] * p0 + T.R[4] * p1 + T.R[5] * p2 + T.t[1];
-  const double q2 = T.R[6] * p0 + T.R[7] * p1 + T.R[8] * p2 + T.t[2];
-  const double Cs[3][3] = {{c6[i], c6[(size_t)n + i], c6[2 * (size_t)n + i]},
-                           {c6[(size_t)n + i], c6[3 * (size_t)n + i], c6[4 * (size_t)n + i]},
-                           {c6[2 * (size_t)n + i], c6[4 * (size_t)n + i], c6[5 * (size_t)n + i]}};
-  double RC[3][3], RCR[3][3];
-  for (int a = 0; a < 3; a++)
-    for (int b = 0; b < 3; b++) RC[a][b] = T.R[3 * a] * Cs[0][b] + T.R[3 * a + 1] * Cs[1][b] + T.R[3 * a + 2] * Cs[2][b];
-  for (int a = 0; a < 3; a++)
-    for (int b = 0; b < 3; b++) RCR[a][b] = RC[a][0] * T.R[3 * b] + RC[a][1] * T.R[3 * b + 1] + RC[a][2] * T.R[3 * b + 2];
-  const double CA[6] = {RCR[0][0], RCR[0][1], RCR[0][2], RCR[1][1], RCR[1][2], RCR[2][2]};
-  const int cx = (int)floor(q0 / g.res - 0.5) - g.minc[0];
-  const int cy = (int)floor(q1 / g.res - 0.5) - g.minc[1];
-  const int cz = (int)floor(q2 / g.res - 0.5) - g.minc[2];
-  for (int o = 0; o < noff; o++) {
-    int ox, oy, oz;
-    neighbor_offset(noff, o, ox, oy, oz);
-    const int x = cx + ox, y = cy + oy, z = cz + oz;
-    int v = -1;
-    if (x >= 0 && x < g.dim[0] && y >= 0 && y < g.dim[1] && z >= 0 && z < g.dim[2]) v = cell_voxel[cell_index(g, x, y, z)];
-    const size_t slot = (size_t)o * n + i;
-    corr_v[slot] = v;
-    if (v < 0) continue;
-    const double* rec = vox + (size_t)v * kVoxRec;
-    double S[6], M[6];
-    for (int a = 0; a < 6; a++) S[a] = rec[3 + a] + CA[a];
-    if (!inv_sym3(S, M)) { for (int a = 0; a < 6; a++) M[a] = 0.0; }
-    for (int a = 0; a < 6; a++) corr_M[((size_t)a * noff + o) * n + i] = M[a];
-    ncorr++;
-    const double e0 = rec[0] - q0, e1 = rec[1] - q1, e2 = rec[2] - q2;
-    const double w = sqrt(rec[9]);
-    const double Me0 = M[0] * e0 + M[1] * e1 + M[2] * e2;
-    const double Me1 = M[1] * e0 + M[3] * e1 + M[4] * e2;
-    const double Me2 = M[2] * e0 + M[4] * e1 + M[5] * e2;
-    acc[27] += w * (e0 * Me0 + e1 * Me1 + e2 * Me2);
-    if (!want_H) continue;
-    const double J[3][6] = {{0.0, -q2, q1, -1.0, 0.0, 0.0}, {q2, 0.0, -q0, 0.0, -1.0, 0.0}, {-q1, q0, 0.0, 0.0, 0.0, -1.0}};
-    double MJ[3][6];
-    for (int c = 0; c < 6; c++) {
-      MJ[0][c] = M[0] * J[0][c] + M[1] * J[1][c] + M[2] * J[2][c];
-      MJ[1][c] = M[1] * J[0][c] + M[3] * J[1][c] + M[4] * J[2][c];
-      MJ[2][c] = M[2] * J[0][c] + M[4] * J[1][c] + M[5] * J[2][c];
-    }
-    int u = 0;
-    for (int a = 0; a < 6; a++)
-      for (int c = a; c < 6; c++) { acc[u] += w * (J[0][a] * MJ[0][c] + J[1][a] * MJ[1][c] + J[2][a] * MJ[2][c]); u++; }
-    for (int a = 0; a < 6; a++) acc[21 + a] += w * (J[0][a] * Me0 + J[1][a] * Me1 + J[2][a] * Me2);
-  }
-}
+// FastVGICP::update_correspondences + linearize (fast_vgicp_impl.hpp:73-180) with a GENERAL source covariance: linearize_point with R C_A R^T
+// from the six entries instead of from the normal
 __global__ void __launch_bounds__(LIN_T)
 k_linearize_general(const float4* __restrict__ P, const double* __restrict__ c6, int n, Pose T, Grid g, const int* __restrict__ cell_voxel,
                     const double* __restrict__ vox, int noff, int* __restrict__ corr_v, double* __restrict__ corr_M, int want_H,
@@ -4006,7 +3907,12 @@ k_linearize_general(const float4* __restrict__ P, const double* __restrict__ c6,
 #pragma unroll
   for (int a = 0; a < kAccum; a++) acc[a] = 0.0;
   int ncorr = 0;
-  if (i < n) linearize_point_general(P[i], c6, i, n, T, g, cell_voxel, vox, noff, corr_v, corr_M, want_H, acc, ncorr);
+  if (i < n) {
+    double C[6], CA[6];
+    point_cov6<true>(c6, nullptr, nullptr, nullptr, n, i, C);
+    rcrt6(T.R, C, CA);
+    linearize_point(P[i], CA, i, n, T, g, cell_voxel, vox, noff, corr_v, corr_M, want_H, acc, ncorr);
+  }
   block_reduce_store<kAccum>(acc, partials + (size_t)blockIdx.x * kAccum);
   block_count_store(ncorr, ncorr_partials + blockIdx.x);
 }
@@ -4270,9 +4176,7 @@ k_mapreg_terms(MapregPose pose0, MapregPose pose1, double huber_a, int want_H, d
 __global__ void __launch_bounds__(WAVE) k_mapreg_fold(const double* __restrict__ partials, int nrows, double* __restrict__ out56) {
   const int b = blockIdx.x / kAccum, a = blockIdx.x % kAccum, lane = threadIdx.x;
   const double* base = partials + (size_t)b * nrows * kAccum;
-  double s = 0;
-  for (int r = lane; r < nrows; r += WAVE) s += base[(size_t)r * kAccum + a];
-  s = wave_sum(s);
+  const double s = fold_column(base, nrows, kAccum, a, lane);
   if (lane == 0) out56[b * kAccum + a] = s;
 }
 

@@ -2,8 +2,12 @@
 // CUDA (src/fast_gicp/cuda/ndt_cuda.cu, src/fast_gicp/cuda/ndt_compute_derivatives.cu, src/fast_gicp/cuda/gaussian_voxelmap.cu,
 // src/fast_gicp/cuda/covariance_regularization.cu); written from its formulas, in the project's arithmetic: fp32 points, everything after them fp64,
 // every sum in a fixed order, no floating-point atomics.  Citations are relative to rgc_slam/ of the reference (ROBOT-WSC/RGC-SLAM).
-// A translation unit of its own: the device code of every other kernel of the library stays what it was.
+// A translation unit of its own, over the pieces every solver shares: the term, R C R^T and the block store with the term count are
+// rgc_terms.h's, the inverse rgc_cov.h's.  Its own on purpose: ndt_jacobi_rot / ndt_min_eig (another threshold and closed form than rgc_cov.h's
+// jacobi_rot) and k_ndt_fold (one lane adds the rows sequentially: another order than fold_column's).
 #include "rgc_kernels.h"
+#include "rgc_cov.h"
+#include "rgc_terms.h"
 
 #include <climits>
 
@@ -101,52 +105,9 @@ __global__ void __launch_bounds__(256) k_ndt_voxels(const float4* __restrict__ P
   vox_cell[v] = cell;
 }
 
-__device__ __forceinline__ bool ndt_inv_sym3(const double S[6], double M[6]) {
-  const double a = S[0], b = S[1], c = S[2], d = S[3], e = S[4], f = S[5];
-  const double c00 = d * f - e * e, c01 = c * e - b * f, c02 = b * e - c * d;
-  const double det = a * c00 + b * c01 + c * c02;
-  if (det == 0.0) return false;
-  const double id = 1.0 / det;
-  M[0] = c00 * id; M[1] = c01 * id; M[2] = c02 * id;
-  M[3] = (a * f - c * c) * id; M[4] = (b * c - a * e) * id; M[5] = (a * d - b * b) * id;
-  return true;
-}
-
 __device__ __forceinline__ int ndt_coord(double x, double res) {
   const double u = floor(x / res - 0.5);
   return fabs(u) < 1.0e9 ? (int)u : INT_MIN;  // (a coordinate no grid holds: no voxel)
-}
-
-// Sum of the block's kAccum accumulators and of its term count in a FIXED order: the six shuffle steps of a wave, then the four waves
-// ascending.  row: kAccum doubles, cnt: one int.
-__device__ __forceinline__ void ndt_block_store(double (&acc)[kAccum], int nterm, double* __restrict__ row, int* __restrict__ cnt) {
-  __shared__ double red[NDT_T / NDT_WAVE][kAccum];
-  __shared__ int cred[NDT_T / NDT_WAVE];
-  const int lane = threadIdx.x & (NDT_WAVE - 1), w = threadIdx.x / NDT_WAVE;
-#pragma unroll
-  for (int a = 0; a < kAccum; a++) {
-    double v = acc[a];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    if (lane == 0) red[w][a] = v;
-  }
-  int c = nterm;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-  if (lane == 0) cred[w] = c;
-  __syncthreads();
-  if (threadIdx.x < kAccum) {
-    double t = red[0][threadIdx.x];
-#pragma unroll
-    for (int j = 1; j < NDT_T / NDT_WAVE; j++) t += red[j][threadIdx.x];
-    row[threadIdx.x] = t;
-  }
-  if (threadIdx.x == kAccum) {
-    int t = 0;
-#pragma unroll
-    for (int j = 0; j < NDT_T / NDT_WAVE; j++) t += cred[j];
-    *cnt = t;
-  }
 }
 
 // The terms of one source element (src/fast_gicp/cuda/ndt_compute_derivatives.cu:50-91 P2D, :120-163 D2D) over every offset of the neighbour
@@ -171,17 +132,8 @@ __global__ void __launch_bounds__(NDT_T) k_ndt_terms(const float* __restrict__ i
     if (kD2D) {
       const double* sr = svox + (size_t)i * kNdtRec;
       p0 = sr[0]; p1 = sr[1]; p2 = sr[2];
-      const double Cs[3][3] = {{sr[3], sr[4], sr[5]}, {sr[4], sr[6], sr[7]}, {sr[5], sr[7], sr[8]}};
-      double RC[3][3];
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = 0; b < 3; b++) RC[a][b] = Tlin.R[3 * a] * Cs[0][b] + Tlin.R[3 * a + 1] * Cs[1][b] + Tlin.R[3 * a + 2] * Cs[2][b];
-      int u = 0;
-#pragma unroll
-      for (int a = 0; a < 3; a++)
-#pragma unroll
-        for (int b = a; b < 3; b++) RCR[u++] = RC[a][0] * Tlin.R[3 * b] + RC[a][1] * Tlin.R[3 * b + 1] + RC[a][2] * Tlin.R[3 * b + 2];
+      const double CA[6] = {sr[3], sr[4], sr[5], sr[6], sr[7], sr[8]};
+      rcrt6(Tlin.R, CA, RCR);
     } else {
       const float* p = in + (size_t)i * stride_f;
       p0 = (double)p[0]; p1 = (double)p[1]; p2 = (double)p[2];
@@ -215,7 +167,7 @@ __global__ void __launch_bounds__(NDT_T) k_ndt_terms(const float* __restrict__ i
         double S[6];
 #pragma unroll
         for (int a = 0; a < 6; a++) S[a] = rec[3 + a] + RCR[a];
-        if (!ndt_inv_sym3(S, M)) {
+        if (!inv_sym3(S, M)) {
 #pragma unroll
           for (int a = 0; a < 6; a++) M[a] = 0.0;
         }
@@ -226,34 +178,10 @@ __global__ void __launch_bounds__(NDT_T) k_ndt_terms(const float* __restrict__ i
       nterm++;
       const double e0 = rec[0] - q0, e1 = rec[1] - q1, e2 = rec[2] - q2;
       const double w = res2 / (res2 + (e0 * e0 + e1 * e1 + e2 * e2));  // Cauchy (:15-18,78,150)
-      const double Me0 = M[0] * e0 + M[1] * e1 + M[2] * e2;
-      const double Me1 = M[1] * e0 + M[3] * e1 + M[4] * e2;
-      const double Me2 = M[2] * e0 + M[4] * e1 + M[5] * e2;
-      acc[27] += w * (e0 * Me0 + e1 * Me1 + e2 * Me2);
-      if (!want_H) continue;
-      // J = [skew(q) | -I] (3 x 6), columns [rotation, translation]; H += w J^T M J, b += w J^T M e (:81-88)
-      const double J[3][6] = {{0.0, -q2, q1, -1.0, 0.0, 0.0}, {q2, 0.0, -q0, 0.0, -1.0, 0.0}, {-q1, q0, 0.0, 0.0, 0.0, -1.0}};
-      double MJ[3][6];
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        MJ[0][c] = M[0] * J[0][c] + M[1] * J[1][c] + M[2] * J[2][c];
-        MJ[1][c] = M[1] * J[0][c] + M[3] * J[1][c] + M[4] * J[2][c];
-        MJ[2][c] = M[2] * J[0][c] + M[4] * J[1][c] + M[5] * J[2][c];
-      }
-      int u = 0;
-#pragma unroll
-      for (int a = 0; a < 6; a++) {
-#pragma unroll
-        for (int c = a; c < 6; c++) {
-          acc[u] += w * (J[0][a] * MJ[0][c] + J[1][a] * MJ[1][c] + J[2][a] * MJ[2][c]);
-          u++;
-        }
-      }
-#pragma unroll
-      for (int a = 0; a < 6; a++) acc[21 + a] += w * (J[0][a] * Me0 + J[1][a] * Me1 + J[2][a] * Me2);
+      gn_term<true>(M, q0, q1, q2, e0, e1, e2, w, want_H, acc);  // cost += w e^T M e, H += w J^T M J, b += w J^T M e (:81-88)
     }
   }
-  ndt_block_store(acc, nterm, partials + (size_t)blockIdx.x * kAccum, ipartials + blockIdx.x);
+  block_sum_count_store<NDT_T>(acc, nterm, partials + (size_t)blockIdx.x * kAccum, ipartials + blockIdx.x);
 }
 
 // the workgroups' rows in ascending order: out[0 .. kAccum) the sums, out[kAccum] the number of terms

@@ -1,7 +1,8 @@
 // rgc_nn.h -- the exact nearest-neighbour search on a cloud's grid (sorted float4 points, cell starts) and the device helpers it is made of,
-// shared by the translation units that search: rgc_kernels.hip (k_fitness, k_icp_accumulate, the kNN kernels use the helpers) and rgc_gicp.hip
-// (k_gicp_correspond).  Everything here is __forceinline__: each kernel inlines its own copy, the device code of a translation unit that
-// included these definitions in place is unchanged.  Compile with -ffp-contract=off (dist2).
+// shared by the translation units that search: rgc_kernels.hip (k_fitness, k_icp_accumulate, the kNN kernels use the helpers), rgc_gicp.hip
+// (k_gicp_correspond) and rgc_gicp_mp.hip (the radius gather); transform_f32 is the fp32 query of all of them.  Everything here is
+// __forceinline__: each kernel inlines its own copy, the device code of a translation unit that included these definitions in place is
+// unchanged.  Compile with -ffp-contract=off (dist2).
 #pragma once
 #include "rgc_kernels.h"
 
@@ -39,6 +40,14 @@ __device__ __forceinline__ float dist2(float px, float py, float pz, const float
   const f32x2 dd = d * d;
   const float dz = pz - c.z;
   return (dd.x + dd.y) + dz * dz;
+}
+
+// the fp32 query of a search: T.cast<float>() * p with the association ((m0 x + m1 y) + m2 z) + m3 per row, never contracted -- the one
+// definition of k_fitness, k_transform_f32, k_gicp_correspond and the FastGICPMultiPoints gather
+__device__ __forceinline__ void transform_f32(const PoseF& T, float x, float y, float z, float& qx, float& qy, float& qz) {
+  qx = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+  qy = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+  qz = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
 }
 
 // sorted point at a 32-bit BYTE offset: base in SGPRs + one VGPR offset, no 64-bit address arithmetic per candidate

@@ -193,6 +193,22 @@ def test_terms_general_route(mod, data, name, k):
     g.close()
 
 
+@pytest.mark.parametrize("n", [2, 63, 257, 16500])
+def test_terms_block_sum_and_fold_shapes(mod, data, n):
+    """the term kernel's block sums and the fold at source sizes of a partial wave (63), a second workgroup of one lane (257) and more than 64 partial
+    rows (16500: the fold's second stride).  One lane alone cannot be had: a cloud needs at least k = 2 points (test_tiny_targets), so the smallest
+    source is 2 points.  The same reference and bound as every other term test here."""
+    rng = np.random.default_rng(4100 + n)
+    Ti = np.linalg.inv(data["T"])
+    src = (nr.scene(rng, n).astype(np.float64) @ Ti[:3, :3].T + Ti[:3, 3] + rng.normal(0, 0.01, (n, 3))).astype(np.float32)
+    tgt = data["tgt"][:6000]
+    g = _product(mod, tgt, src, k=2 if n < 20 else 20)
+    ref = _reference(g, tgt, src)
+    _check_terms(g, ref, [data["T"]], "source of %d" % n)
+    assert g.num_correspondences == n
+    g.close()
+
+
 def test_terms_without_regularisation_on_a_volumetric_cloud(mod):
     """REG_NONE keeps the raw kNN covariance: only a cloud that fills a volume (uniform in a box, noisy) has covariances that can be inverted"""
     rng = np.random.default_rng(77)

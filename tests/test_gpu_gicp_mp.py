@@ -181,6 +181,23 @@ def test_terms_on_the_four_covariance_route_pairs(mod, general_src, general_tgt)
         owner.close()
 
 
+@pytest.mark.parametrize("n", [2, 63, 257, 16500])
+def test_terms_block_sum_and_fold_shapes(mod, n):
+    """the term kernel's block sums and the fold at source sizes of a partial wave (63), a second workgroup of one lane (257) and more than 64 partial
+    rows (16500: the fold's second stride).  One lane alone cannot be had: a cloud needs at least k = 2 points (test_one_point_target_is_refused), so
+    the smallest source is 2 points.  The same reference and bound as every other term test here."""
+    d = mc.scene_data()
+    tgt, T = d["tgt"][:4000], d["T"]
+    rng = np.random.default_rng(4200 + n)
+    Ti = np.linalg.inv(T)                                       # noisy copies of target points seen from T: every ball holds at least its own point
+    src = (tgt[rng.choice(len(tgt), n, replace=n > len(tgt))].astype(np.float64) @ Ti[:3, :3].T + Ti[:3, 3] + rng.normal(0, 0.01, (n, 3))).astype(np.float32)
+    g = _product(mod, tgt, src, 0.5, k=2 if n < 20 else 20)
+    ref = _reference(g, tgt, src, 0.5)
+    _check_terms(g, ref, T, "source of %d" % n)
+    assert g.num_correspondences == n
+    g.close()
+
+
 def test_terms_with_user_set_covariances(mod):
     tgt, src, T = _small()
     donor = _product(mod, tgt, src, 0.5, k=8)

@@ -71,6 +71,21 @@ def test_readout_vs_reference(reg, name):
             assert abs(out["g"][a]) < 1e-12 * np.abs(out["g"]).max()
 
 
+@pytest.mark.parametrize("name", list(mc.SHAPE_SPECS) + ["n257"])
+def test_block_sum_and_fold_shapes(reg, name):
+    """one factor, 63, 257 and 16500 factors in the current pose (mapreg_cases.SHAPE_SPECS): the same reference and bar as test_readout_vs_reference"""
+    c = mc.build(name)
+    out = _linearize(reg, c)
+    n_cur = len(c["feat"][0]) + len(c["feat"][1])
+    assert n_cur == {"shape_1": 1, "shape_63": 63, "n257": 257, "shape_16500": 16500}[name] and sum(out["n_factors"][:2]) >= min(n_cur, 50)
+    e = ref.evaluate(mc.problem(c, out["factors"]), c["x0"])
+    dev, zeros_ok = ref.deviation(e, out["H"], out["g"], out["cost"])
+    print(f"{name}: {out['n_factors']} factors, |gpu - reference| / sum |terms| = {dev:.3e} (bar {mc.bar_of(c):.2e})")
+    assert np.array_equal(out["H"], out["H"].T) and zeros_ok and out["cost"] > 0
+    assert dev <= mc.bar_of(c)
+    assert _same(out, _linearize(reg, c, want_factors=False))
+
+
 def test_routes_give_the_same_bits(reg):
     """host maps / device maps, strides 12, 16 and 32, a fresh context / one that has just solved the largest case, a repeated call"""
     from rgc_slam_amd import mapping

@@ -142,6 +142,45 @@ def test_linearize_and_compute_error(mod, data, mode, method, radius, res):
     print("mode %d method %d r %.1f res %.1f: %d terms, worst relative difference %.3g" % (mode, method, radius, res, ref.num_terms(), worst))
 
 
+@pytest.fixture(scope="module")
+def shape_clouds():
+    """a dense 6000-point room of 4 m (voxels of 0.5 m with far more than 6 points) and a lattice of 16500 points, ONE per voxel of 0.5 m (each
+    0.02 m at most off its voxel's centre), nearest the room's fullest voxel first: the first n of them are n source points (P2D's elements) in n
+    source voxels (D2D's).  The pose: 0.03 m along every axis, no rotation -- no point and no voxel mean comes near a wall."""
+    rng = np.random.default_rng(9201)
+    res = 0.5
+    tgt = nr.scene(rng, 6000, half=2.0)
+    vm = nr.VoxelMap(tgt, res)
+    c0 = vm.coords[np.argmax(vm.n)]
+    g = np.stack(np.meshgrid(np.arange(-13, 13), np.arange(-13, 13), np.arange(-12, 13), indexing="ij"), -1).reshape(-1, 3)
+    g = g[np.argsort((g * g).sum(1), kind="stable")][:16500] + c0
+    src = ((g + 1.0) * res + rng.uniform(-0.02, 0.02, g.shape)).astype(np.float32)   # voxel c holds [(c + 0.5) res, (c + 1.5) res): centre (c + 1) res
+    T = np.eye(4)
+    T[:3, 3] = 0.03
+    assert len(np.unique(nr.voxel_coord(src.astype(np.float64), res), axis=0)) == 16500
+    return dict(tgt=tgt, src=src, T=T, res=res)
+
+
+@pytest.mark.parametrize("n", [1, 63, 257, 16500])
+@pytest.mark.parametrize("mode", [nr.P2D, nr.D2D])
+def test_block_sum_and_fold_shapes(mod, shape_clouds, mode, n):
+    """the term kernel's block sums (with the term count) and the fold at 1 source element (one lane), 63 (a partial wave), 257 (a second workgroup of
+    one lane) and 16500 (65 partial rows); the reference and the bound of test_linearize_and_compute_error"""
+    d = dict(tgt=shape_clouds["tgt"], src=shape_clouds["src"][:n])
+    r, ref = _product(mod, d, mode, nr.DIRECT7, 0.0, shape_clouds["res"]), _reference(d, mode, nr.DIRECT7, 0.0, shape_clouds["res"])
+    if mode == nr.D2D:
+        assert len(r.voxels(1)["n"]) == n
+    for T in (shape_clouds["T"], np.eye(4)):
+        y, H, b = r.linearize(T)
+        yr, Hr, br = ref.linearize(T)
+        assert r.num_correspondences() == ref.num_terms() and ref.num_terms() >= 1
+        errs = (abs(y - yr) / abs(yr), np.abs(H - Hr).max() / np.abs(Hr).max(), np.abs(b - br).max() / np.abs(br).max())
+        print("mode %d, %d elements: %d terms, relative differences %.3g %.3g %.3g" % ((mode, n, ref.num_terms()) + errs))
+        assert max(errs) <= 1e-5, errs
+        assert np.array_equal(H, H.T) and r.linearize(T, want_H=False)[0] == y
+        assert r.compute_error(T) == pytest.approx(y, rel=1e-13)
+
+
 def _pose_error(A, B):
     D = np.linalg.inv(A) @ B
     ang = np.arccos(np.clip(0.5 * (np.trace(D[:3, :3]) - 1), -1, 1))
