@@ -944,6 +944,41 @@ RGC_API int rgc_gicp_get_correspondences(rgc_ctx* ctx, int* idx, float* sq_dist)
 RGC_API int rgc_gicp_align(rgc_ctx* ctx, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged,
                            int* lm_failed);
 
+/* ---- FastGICPSingleThread: GICP with anchor-cached correspondences: fast_gicp::FastGICPSingleThread (include/fast_gicp/gicp/fast_gicp_st.hpp:20-65,
+ * include/fast_gicp/gicp/impl/fast_gicp_st_impl.hpp:19-125), the FastGICP that searches a point again only when it has to ----
+ * On the context's OWN source and target and their covariances as they are, exactly as rgc_gicp_* (either covariance route, caller-set
+ * covariances, lazy -- completed first --, re-framed, borrowed and map-bound targets); refused with a solve in flight; no source, no target, a
+ * NULL or non-finite pose: RGC_ERR_INVALID.  d_max is FastGICP's own setting (rgc_gicp_set_max_correspondence_distance); the LM and convergence
+ * settings are the context's rgc_params.  It is NOT FastGICP with a faster search: a point that is not searched again keeps its pair, its keys
+ * and its Mahalanobis matrix from the pose it was last searched at, so the numbers differ from rgc_gicp_*'s.
+ *   State per source point: corr, key1, key2 (fp32), the anchor (3 fp32), M (6 fp64).  For a pose T (row-major 4x4) and every source point p_i
+ * (citations: fast_gicp_st_impl.hpp):
+ *   q = float(T) p_i in fp32, ((m0 x + m1 y) + m2 z) + m3, never contracted (:44).  If the point has an anchor a_i (:46-54): d2 = (dx dx + dy dy)
+ * + dz dz of q - a_i in fp32, d = (double)(float)sqrt((double)d2), max_first = (double)(float)sqrt((double)key1) + d, min_second =
+ * (double)(float)sqrt((double)key2) - d; the point is SKIPPED iff max_first < min_second (:51, strict, fp64) and everything it has stays.
+ * Otherwise it is SEARCHED (:56-75): key1 = the smallest fp32 key ((dx dx + dy dy) + dz dz) over the target and j its point, ties to the smaller
+ * index, exactly as rgc_gicp_*; key2 = the second smallest key of the multiset (== key1 where the nearest is tied or duplicated; +INF when the
+ * target has one point -- the reference reads a stale value there); corr = j iff (double)key1 < d_max^2 (:58, strict) else -1; the anchor
+ * becomes q (:61); for a kept pair M = (C_B[j] + R C_A[i] R^T)^-1 at THIS pose (:67-75).  Then FastGICP's term for every pair with corr >= 0
+ * under the stored M (:80-120).  As in the reference a skipped point keeps its pair (or its -1) after it crosses d_max.  Every reduction runs in
+ * a fixed order: results are bit-identical from run to run and between host- and device-pointer inputs.
+ *   Frozen cost: rgc_gicpst_compute_error is the cost of the state as it is at the pose it is given (:122-125).
+ *   The state (anchors included) drops on rgc_gicpst_reset, at the start of rgc_gicpst_align (:19-22) and wherever FastGICP's frozen list drops;
+ * the next linearisation then searches every point, and until then the read-outs and rgc_gicpst_compute_error are RGC_ERR_INVALID.  A new
+ * d_max does not drop it.  Deviations from the reference: DESIGN.md section 6. */
+RGC_API int rgc_gicpst_reset(rgc_ctx* ctx);
+/* H, b as rgc_gicp_linearize (both or neither); cost nullable */
+RGC_API int rgc_gicpst_linearize(rgc_ctx* ctx, const double T[16], double H[36], double b[6], double* cost);
+RGC_API int rgc_gicpst_compute_error(rgc_ctx* ctx, const double T[16], double* cost);
+RGC_API int rgc_gicpst_num_correspondences(rgc_ctx* ctx, int* n_kept);             /* pairs with corr >= 0 after the last rgc_gicpst_linearize */
+RGC_API int rgc_gicpst_num_searched(rgc_ctx* ctx, int* n_searched);                /* points the last rgc_gicpst_linearize searched */
+/* the state after the last rgc_gicpst_linearize in caller order, n_source entries each (any may be NULL): idx = the target point's index or -1,
+ * sq_dist / second_sq_dist = key1 / key2 at the point's anchor, searched = 1 where the last linearisation searched the point, else 0 */
+RGC_API int rgc_gicpst_get_correspondences(rgc_ctx* ctx, int* idx, float* sq_dist, float* second_sq_dist, int* searched);
+/* outputs as rgc_gicp_align's (any may be NULL) */
+RGC_API int rgc_gicpst_align(rgc_ctx* ctx, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged,
+                             int* lm_failed);
+
 /* ---- FastGICPMultiPoints: GICP on radius-merged target distributions: fast_gicp::FastGICPMultiPoints
  * (include/fast_gicp/gicp/experimental/fast_gicp_mp.hpp:40-53, include/fast_gicp/gicp/experimental/fast_gicp_mp_impl.hpp:92-221) ----
  * The one registration of the family whose correspondence is a RADIUS SEARCH: every source point is matched against the distance-weighted merge of

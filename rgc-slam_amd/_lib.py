@@ -191,6 +191,7 @@ SYMBOLS = [
     "rgc_default_pgo_params", "rgc_pgo_make_loop", "rgc_pgo_optimize", "rgc_pgo_linearize",
     "rgc_default_ndt_params", "rgc_ndt_set_params", "rgc_ndt_get_params", "rgc_ndt_set_target", "rgc_ndt_set_source", "rgc_ndt_set_target_device", "rgc_ndt_set_source_device", "rgc_ndt_clear_source", "rgc_ndt_clear_target", "rgc_ndt_swap_source_and_target", "rgc_ndt_linearize", "rgc_ndt_compute_error", "rgc_ndt_num_correspondences", "rgc_ndt_align", "rgc_ndt_get_voxels", "rgc_ndt_get_raw_covariances",
     "rgc_gicp_set_max_correspondence_distance", "rgc_gicp_get_max_correspondence_distance", "rgc_gicp_linearize", "rgc_gicp_compute_error", "rgc_gicp_num_correspondences", "rgc_gicp_get_correspondences", "rgc_gicp_align",
+    "rgc_gicpst_reset", "rgc_gicpst_linearize", "rgc_gicpst_compute_error", "rgc_gicpst_num_correspondences", "rgc_gicpst_num_searched", "rgc_gicpst_get_correspondences", "rgc_gicpst_align",
     "rgc_default_gicp_mp_params", "rgc_gicpmp_set_params", "rgc_gicpmp_get_params", "rgc_gicpmp_linearize", "rgc_gicpmp_num_correspondences", "rgc_gicpmp_num_candidates", "rgc_gicpmp_get_merged", "rgc_gicpmp_get_neighbors", "rgc_gicpmp_align",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
@@ -403,6 +404,13 @@ def load():
     L.rgc_gicp_num_correspondences.argtypes = [vp, ip]
     L.rgc_gicp_get_correspondences.argtypes = [vp, ip, fp]
     L.rgc_gicp_align.argtypes = [vp, fp, fp, dp, dp, ip, ip, ip]
+    L.rgc_gicpst_reset.argtypes = [vp]
+    L.rgc_gicpst_linearize.argtypes = [vp, dp, dp, dp, dp]
+    L.rgc_gicpst_compute_error.argtypes = [vp, dp, dp]
+    L.rgc_gicpst_num_correspondences.argtypes = [vp, ip]
+    L.rgc_gicpst_num_searched.argtypes = [vp, ip]
+    L.rgc_gicpst_get_correspondences.argtypes = [vp, ip, fp, fp, ip]
+    L.rgc_gicpst_align.argtypes = [vp, fp, fp, dp, dp, ip, ip, ip]
     L.rgc_default_gicp_mp_params.argtypes = [C.POINTER(GicpMpParams)]
     L.rgc_default_gicp_mp_params.restype = None
     L.rgc_gicpmp_set_params.argtypes = [vp, C.POINTER(GicpMpParams)]

@@ -36,7 +36,7 @@ public:
     if (!ctx) throw std::runtime_error("rgc::FastGICPHip: null context");
     init();
   }
-  ~FastGICPHip() { if (own_ && ctx_) rgc_destroy(ctx_); }
+  virtual ~FastGICPHip() { if (own_ && ctx_) rgc_destroy(ctx_); }
   FastGICPHip(const FastGICPHip&) = delete;
   FastGICPHip& operator=(const FastGICPHip&) = delete;
 
@@ -78,29 +78,30 @@ public:
     n_source_ = st.n_source;
   }
 
-  double linearize(const Matrix4d& T, Matrix6d* H = nullptr, Vector6d* b = nullptr) {
+  // (virtual where FastGICPSingleThreadHip below overrides, as the reference class overrides FastGICP: fast_gicp_st.hpp:53-60)
+  virtual double linearize(const Matrix4d& T, Matrix6d* H = nullptr, Vector6d* b = nullptr) {
     double cost = 0.0;
     check(rgc_gicp_linearize(ctx_, T.data(), H && b ? H->data() : nullptr, H && b ? b->data() : nullptr, &cost), "rgc_gicp_linearize");
     return cost;
   }
-  double compute_error(const Matrix4d& T) {
+  virtual double compute_error(const Matrix4d& T) {
     double cost = 0.0;
     check(rgc_gicp_compute_error(ctx_, T.data(), &cost), "rgc_gicp_compute_error");
     return cost;
   }
-  int numCorrespondences() {
+  virtual int numCorrespondences() {
     int n = 0;
     check(rgc_gicp_num_correspondences(ctx_, &n), "rgc_gicp_num_correspondences");
     return n;
   }
   // the pairs of the last linearize in the source's order: idx -1 where rejected, sq_dist the key even there
-  void getCorrespondences(std::vector<int>& idx, std::vector<float>& sq_dist) {
+  virtual void getCorrespondences(std::vector<int>& idx, std::vector<float>& sq_dist) {
     idx.assign((size_t)n_source_, -1);
     sq_dist.assign((size_t)n_source_, 0.f);
     check(rgc_gicp_get_correspondences(ctx_, idx.data(), sq_dist.data()), "rgc_gicp_get_correspondences");
   }
 
-  void align(const Matrix4f& guess) {
+  virtual void align(const Matrix4f& guess) {
     check(rgc_gicp_align(ctx_, guess.data(), final_.data(), hessian_.data(), &fitness_, &iterations_, &converged_, &lm_failed_), "rgc_gicp_align");
   }
   void align() {
@@ -114,7 +115,7 @@ public:
   bool lmFailed() const { return lm_failed_ != 0; }
   int iterations() const { return iterations_; }
 
-private:
+protected:
   void init() {
     final_ = Matrix4f{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
     hessian_.fill(0.0);
@@ -134,6 +135,61 @@ private:
   Matrix6d hessian_;
   double fitness_ = 0.0;
   int iterations_ = 0, converged_ = 0, lm_failed_ = 0;
+};
+
+// Stands in for fast_gicp::FastGICPSingleThread<PointSource, PointTarget> (rgc_slam/include/fast_gicp/gicp/fast_gicp_st.hpp:20-65,
+// impl/fast_gicp_st_impl.hpp:19-125) over rgc_gicpst_*, and derives from FastGICPHip as that class derives from FastGICP: the clouds, the covariances and
+// the settings are FastGICP's; linearize, compute_error, align and the read-outs are overridden.  A source point keeps an anchor and is searched again
+// only when the triangle inequality cannot prove its nearest neighbour unchanged; a point that is not searched keeps its pair and its Mahalanobis
+// matrix.  align() drops the anchors first (:19-22); reset() drops them between linearisations.
+//
+//   rgc::FastGICPSingleThreadHip st(0);                    // or FastGICPSingleThreadHip(other.context()) on the clouds of another adaptor (not owned)
+//   st.setInputTarget(map); st.setInputSource(scan);
+//   st.align(guess);  st.getFinalTransformation();  st.numSearched();
+class FastGICPSingleThreadHip : public FastGICPHip {
+public:
+  explicit FastGICPSingleThreadHip(int hip_device = 0, const rgc_params* params = nullptr) : FastGICPHip(hip_device, params) {}
+  explicit FastGICPSingleThreadHip(rgc_ctx* ctx) : FastGICPHip(ctx) {}
+
+  void reset() { check(rgc_gicpst_reset(ctx_), "rgc_gicpst_reset"); }
+  double linearize(const Matrix4d& T, Matrix6d* H = nullptr, Vector6d* b = nullptr) override {
+    double cost = 0.0;
+    check(rgc_gicpst_linearize(ctx_, T.data(), H && b ? H->data() : nullptr, H && b ? b->data() : nullptr, &cost), "rgc_gicpst_linearize");
+    return cost;
+  }
+  double compute_error(const Matrix4d& T) override {
+    double cost = 0.0;
+    check(rgc_gicpst_compute_error(ctx_, T.data(), &cost), "rgc_gicpst_compute_error");
+    return cost;
+  }
+  int numCorrespondences() override {
+    int n = 0;
+    check(rgc_gicpst_num_correspondences(ctx_, &n), "rgc_gicpst_num_correspondences");
+    return n;
+  }
+  int numSearched() {   // source points the last linearize searched
+    int n = 0;
+    check(rgc_gicpst_num_searched(ctx_, &n), "rgc_gicpst_num_searched");
+    return n;
+  }
+  void getCorrespondences(std::vector<int>& idx, std::vector<float>& sq_dist) override {
+    idx.assign((size_t)n_source_, -1);
+    sq_dist.assign((size_t)n_source_, 0.f);
+    check(rgc_gicpst_get_correspondences(ctx_, idx.data(), sq_dist.data(), nullptr, nullptr), "rgc_gicpst_get_correspondences");
+  }
+  // the state after the last linearize in the source's order: idx -1 where not kept, the keys to the nearest and the second nearest at the point's
+  // anchor, searched 1 where the last linearize searched the point
+  void getCorrespondences(std::vector<int>& idx, std::vector<float>& sq_dist, std::vector<float>& second_sq_dist, std::vector<int>& searched) {
+    idx.assign((size_t)n_source_, -1);
+    sq_dist.assign((size_t)n_source_, 0.f);
+    second_sq_dist.assign((size_t)n_source_, 0.f);
+    searched.assign((size_t)n_source_, 0);
+    check(rgc_gicpst_get_correspondences(ctx_, idx.data(), sq_dist.data(), second_sq_dist.data(), searched.data()), "rgc_gicpst_get_correspondences");
+  }
+  using FastGICPHip::align;
+  void align(const Matrix4f& guess) override {
+    check(rgc_gicpst_align(ctx_, guess.data(), final_.data(), hessian_.data(), &fitness_, &iterations_, &converged_, &lm_failed_), "rgc_gicpst_align");
+  }
 };
 
 // Stands in for fast_gicp::FastGICPMultiPoints<PointSource, PointTarget> (rgc_slam/include/fast_gicp/gicp/experimental/fast_gicp_mp.hpp:40-53,

@@ -1,6 +1,7 @@
 // rgc_api_lsq.hip -- the host LM driver every registration method shares (LsqRegistration::computeTransformation and step_lm,
 // lsq_registration_impl.hpp:53-79, 125-172) and the two methods that are nothing else on the host: NDT (rgc_ndt_*) and FastGICP (rgc_gicp_*).
-// rgc_align's host-driven route (rgc_api.hip) runs on the same driver.  The kernels are in rgc_ndt.hip and rgc_gicp.hip.  FastGICPMultiPoints
+// rgc_align's host-driven route (rgc_api.hip) runs on the same driver, and so does FastGICPSingleThread (rgc_gicpst_*, kernels in rgc_gicp_st.hip:
+// FastGICP with anchor-cached correspondences).  The kernels are in rgc_ndt.hip and rgc_gicp.hip.  FastGICPMultiPoints
 // (rgc_gicpmp_*, kernels in rgc_gicp_mp.hip) has a plain Gauss-Newton loop of its own over the driver's scalar pieces.
 #include "rgc_ctx.h"
 #include "rgc_lm_decide.h"  // rgc_lm.h and the convergence test the device decides by (lsq_registration_impl.hpp:82-91)
@@ -521,6 +522,148 @@ int rgc_gicp_align(rgc_ctx* c, const float guess[16], float final_T[16], double 
   int rc = gicp_need_inputs(c);
   if (rc) return rc;
   static const LmSystem sys = {gicp_do_linearize, gicp_do_error, nullptr, gicp_pose_ok};
+  LmResult r;
+  if ((rc = lm_solve(c, sys, guess, &r))) return rc;
+  r.write(final_T, final_H, iterations, converged, lm_failed);
+  return gicp_final_fitness(c, r, fitness);
+}
+
+// ---- FastGICPSingleThread: GICP with anchor-cached correspondences (include/fast_gicp/gicp/impl/fast_gicp_st_impl.hpp:19-125) on the context's own clouds ----
+static rgck::GicpStState gicp_st_state(rgc_ctx* c) {
+  return rgck::GicpStState{c->gicp_st_corr.as<int>(), c->gicp_st_key1.as<float>(), c->gicp_st_key2.as<float>(), c->gicp_st_anchor.as<float4>(),
+                           c->gicp_st_M.as<double>(), c->gicp_st_searched.as<int>(), c->gicp_st_list.as<int>(), c->gicp_st_count.as<int>()};
+}
+
+// update_correspondences + linearize (fast_gicp_st_impl.hpp:25-120); the inputs have been checked (gicp_need_inputs).  Without a state of the
+// present clouds every point is searched (is_first, :31); the host does not wait for the number searched: it comes back with the sums
+static int gicp_st_do_linearize(rgc_ctx* c, const double T[16], double* H, double* b, double* cost) {
+  const Cloud& sc = c->src;
+  const Cloud& tg = c->tgt;
+  const int n = sc.n, nb = rgck::gicp_blocks(n);
+  const int first = (c->gicp_st_valid && c->gicp_st_n == n) ? 0 : 1;
+  int rc;
+  c->gicp_st_valid = false;
+  if ((rc = ensure(c, c->gicp_st_corr, sizeof(int) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_st_key1, sizeof(float) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_st_key2, sizeof(float) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_st_anchor, sizeof(float) * 4 * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_st_M, sizeof(double) * 6 * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_st_searched, sizeof(int) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_st_list, sizeof(int) * (size_t)n))) return rc;
+  if ((rc = ensure(c, c->gicp_st_count, sizeof(int) * 4))) return rc;
+  if ((rc = ensure(c, c->gicp_partials, sizeof(double) * rgck::kGicpStAcc * (size_t)nb))) return rc;
+  float T32[16];
+  for (int i = 0; i < 16; i++) T32[i] = (float)T[i];  // x.cast<float>(), :29
+  const int want = (H && b) ? 1 : 0;
+  const rgck::GicpStState st = gicp_st_state(c);
+  if (first) HIPCHK(c, hipMemsetAsync(st.count, 0, sizeof(int), c->stream));  // (afterwards the term kernel leaves the counter at zero)
+  rgck::gicpst_correspond(c->stream, sc.sorted(), posef_from(T32), tg.sorted(), c->gicp_dmax * c->gicp_dmax, first, st);
+  rgck::gicpst_terms(c->stream, sc.sorted(), tg.sorted(), st, gicp_cov_of(sc), gicp_cov_of(tg), pose_from(T), want, c->gicp_partials.as<double>(),
+                     c->gicp_out.as<double>());
+  if ((rc = read_sums(c, c->gicp_h_out, c->gicp_out, rgck::kGicpStAcc))) return rc;
+  const double* o = c->gicp_h_out;
+  c->gicp_st_valid = true;
+  c->gicp_st_n = n;
+  c->gicp_st_kept = (int)o[28];
+  c->gicp_st_searched_n = (int)o[29];
+  if (want) unpack_system(o, H, b);
+  if (cost) *cost = o[27];
+  return RGC_OK;
+}
+
+// compute_error (fast_gicp_st_impl.hpp:122-125: linearize without H and b, which leaves the state alone, :81-85) -- FastGICP's frozen cost over this state
+static int gicp_st_do_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c->gicp_st_valid || c->gicp_st_n != c->src.n)
+    return fail(c, RGC_ERR_INVALID, "rgc_gicpst_compute_error needs a preceding rgc_gicpst_linearize on the present clouds");
+  rgck::gicp_error(c->stream, c->src.sorted(), c->tgt.sorted(), c->gicp_st_corr.as<const int>(), c->gicp_st_M.as<const double>(), pose_from(T),
+                   c->gicp_partials.as<double>(), c->gicp_out.as<double>());
+  const int rc = read_sums(c, c->gicp_h_out, c->gicp_out, 1);
+  if (rc) return rc;
+  *cost = c->gicp_h_out[0];
+  return RGC_OK;
+}
+
+int rgc_gicpst_reset(rgc_ctx* c) {
+  if (!c) return RGC_ERR_INVALID;
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  c->gicp_st_valid = false;
+  return RGC_OK;
+}
+
+int rgc_gicpst_linearize(rgc_ctx* c, const double T[16], double H[36], double b[6], double* cost) {
+  if (!c || !T) return RGC_ERR_INVALID;
+  if (!gicp_pose_ok(T)) return fail(c, RGC_ERR_INVALID, "rgc_gicpst_linearize: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = gicp_need_inputs(c);
+  return rc ? rc : gicp_st_do_linearize(c, T, H, b, cost);
+}
+
+int rgc_gicpst_compute_error(rgc_ctx* c, const double T[16], double* cost) {
+  if (!c || !T || !cost) return RGC_ERR_INVALID;
+  if (!gicp_pose_ok(T)) return fail(c, RGC_ERR_INVALID, "rgc_gicpst_compute_error: the pose is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = gicp_need_inputs(c);
+  return rc ? rc : gicp_st_do_error(c, T, cost);
+}
+
+// the state is there, and is that of the present clouds
+static int gicp_st_need_state(rgc_ctx* c, const char* who) {
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  if (!c->gicp_st_valid || !c->src.ready || !c->tgt.ready || c->gicp_st_n != c->src.n)
+    return fail(c, RGC_ERR_INVALID, "%s needs a preceding rgc_gicpst_linearize on the present clouds", who);
+  return RGC_OK;
+}
+
+int rgc_gicpst_num_correspondences(rgc_ctx* c, int* n) {
+  if (!c || !n) return RGC_ERR_INVALID;
+  const int rc = gicp_st_need_state(c, "rgc_gicpst_num_correspondences");
+  if (rc) return rc;
+  *n = c->gicp_st_kept;
+  return RGC_OK;
+}
+
+int rgc_gicpst_num_searched(rgc_ctx* c, int* n_searched) {
+  if (!c || !n_searched) return RGC_ERR_INVALID;
+  const int rc = gicp_st_need_state(c, "rgc_gicpst_num_searched");
+  if (rc) return rc;
+  *n_searched = c->gicp_st_searched_n;
+  return RGC_OK;
+}
+
+int rgc_gicpst_get_correspondences(rgc_ctx* c, int* idx, float* sq_dist, float* second_sq_dist, int* searched) {
+  if (!c) return RGC_ERR_INVALID;
+  int rc = gicp_st_need_state(c, "rgc_gicpst_get_correspondences");
+  if (rc) return rc;
+  if (!idx && !sq_dist && !second_sq_dist && !searched) return RGC_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)c->src.n;
+  if ((rc = check_target_owner(c))) return rc;
+  if ((rc = ensure(c, c->scratch, 16 * n))) return rc;
+  int* d_idx = c->scratch.as<int>();
+  float* d_sq = (float*)(d_idx + n);
+  float* d_sq2 = d_sq + n;
+  int* d_was = (int*)(d_sq2 + n);
+  HIPCHK(c, hipMemsetAsync(d_idx, 0xff, sizeof(int) * n, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_sq, 0, 12 * n, c->stream));
+  rgck::gicpst_export(c->stream, c->src.sorted(), c->tgt.sorted(), gicp_st_state(c), d_idx, d_sq, d_sq2, d_was);
+  if (idx) HIPCHK(c, hipMemcpyAsync(idx, d_idx, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+  if (sq_dist) HIPCHK(c, hipMemcpyAsync(sq_dist, d_sq, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+  if (second_sq_dist) HIPCHK(c, hipMemcpyAsync(second_sq_dist, d_sq2, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+  if (searched) HIPCHK(c, hipMemcpyAsync(searched, d_was, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  return RGC_OK;
+}
+
+// computeTransformation (fast_gicp_st_impl.hpp:19-22): anchors_.clear(), then LsqRegistration's driver (lm_solve) over the two calls above
+int rgc_gicpst_align(rgc_ctx* c, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged, int* lm_failed) {
+  if (!c || !guess) return RGC_ERR_INVALID;
+  if (!pose12_finite(guess)) return fail(c, RGC_ERR_INVALID, "rgc_gicpst_align: the guess is not finite");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = gicp_need_inputs(c);
+  if (rc) return rc;
+  c->gicp_st_valid = false;  // :20
+  static const LmSystem sys = {gicp_st_do_linearize, gicp_st_do_error, nullptr, gicp_pose_ok};
   LmResult r;
   if ((rc = lm_solve(c, sys, guess, &r))) return rc;
   r.write(final_T, final_H, iterations, converged, lm_failed);

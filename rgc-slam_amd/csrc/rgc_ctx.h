@@ -334,6 +334,14 @@ struct rgc_ctx {
   int gicp_mp_n = 0, gicp_mp_points = 0;
   long long gicp_mp_pairs = 0;
   float gicp_mp_T32[16] = {0};
+  // FastGICPSingleThread (rgc_gicpst_*) on the same clouds: per sorted source point the pair, the keys to the nearest and the second nearest at
+  // its anchor, the anchor and the Mahalanobis matrix of the pose it was last searched at (rgck::GicpStState), the compaction's list and
+  // counter.  gicp_st_valid = the state (anchors included) is that of the present clouds: it falls wherever gicp_valid falls, on
+  // rgc_gicpst_reset and at the start of rgc_gicpst_align; the next linearisation then searches every point.  The sums' scratch is FastGICP's
+  // (gicp_partials, gicp_out, gicp_h_out)
+  DevBuf gicp_st_corr, gicp_st_key1, gicp_st_key2, gicp_st_anchor, gicp_st_M, gicp_st_searched, gicp_st_list, gicp_st_count;
+  bool gicp_st_valid = false;
+  int gicp_st_n = 0, gicp_st_kept = 0, gicp_st_searched_n = 0;
   rgc_stats stats{};
   // profiling
   bool prof_on = false;

@@ -155,6 +155,10 @@ void gicp_error(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, c
   hipLaunchKernelGGL(k_gicp_fold, dim3(1), dim3(GICP_WAVE), 0, s, partials, nb, 1, out1);
 }
 
+void gicp_fold(hipStream_t s, const double* partials, int nb, int ncol, double* out) {
+  if (nb > 0 && ncol > 0) hipLaunchKernelGGL(k_gicp_fold, dim3(ncol), dim3(GICP_WAVE), 0, s, partials, nb, ncol, out);
+}
+
 void gicp_export(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const float* key, int* idx, float* sq) {
   const int nb = gicp_blocks(src.n);
   if (nb > 0) hipLaunchKernelGGL(k_gicp_export, dim3(nb), dim3(GICP_T), 0, s, src.P, src.n, tgt.P, tgt.n, corr, key, idx, sq);

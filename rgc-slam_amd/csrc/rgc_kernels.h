@@ -371,6 +371,23 @@ void gicp_terms(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, c
 void gicp_error(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const double* M, Pose T, double* partials, double* out1);
 // the pair list in caller order: idx[i] = the neighbour's original index or -1, sq[i] = the key
 void gicp_export(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const int* corr, const float* key, int* idx, float* sq);
+// nb rows of ncol doubles folded to out[ncol] in a fixed order (k_gicp_fold: one wave per column)
+void gicp_fold(hipStream_t s, const double* partials, int nb, int ncol, double* out);
+// ---- FastGICPSingleThread: GICP with anchor-cached correspondences (rgc_gicp_st.hip; fast_gicp::FastGICPSingleThread,
+// include/fast_gicp/gicp/impl/fast_gicp_st_impl.hpp:19-125) ----
+constexpr int kGicpStAcc = kAccum + 2;  // the 28 sums, the kept pairs, the points searched
+// the per-point state in the source's sorted order (src.n entries each; M: 6 * src.n doubles, SoA; anchor.w unused) and the compaction's
+// scratch: searched (0 / 1 of the last linearisation), list (the points it searched, in no fixed order), count (one int: how many)
+struct GicpStState { int* corr; float* key1; float* key2; float4* anchor; double* M; int* searched; int* list; int* count; };
+// the skip test of every source point at T and the two-nearest search of those that fail it (first != 0: of all of them); *st.count must be
+// zero on entry (in stream order) and holds the number searched afterwards, until gicpst_terms zeroes it again
+void gicpst_correspond(hipStream_t s, const SortedCloud& src, PoseF T, const SortedCloud& tgt, double dmax2, int first, const GicpStState& st);
+// the terms of the state at T (M computed and stored where searched, loaded elsewhere); partials: gicp_blocks(src.n) rows of kGicpStAcc
+// doubles; out30: the sums (the 28, the kept pairs, the points searched).  Leaves *st.count at zero
+void gicpst_terms(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const GicpStState& st, const GicpCov& A, const GicpCov& B, Pose T, int want_H,
+                  double* partials, double* out30);
+// the state in caller order (each output nullable)
+void gicpst_export(hipStream_t s, const SortedCloud& src, const SortedCloud& tgt, const GicpStState& st, int* idx, float* sq, float* sq2, int* was);
 // ---- FastGICPMultiPoints: GICP on radius-merged target distributions (rgc_gicp_mp.hip; fast_gicp::FastGICPMultiPoints,
 // include/fast_gicp/gicp/experimental/fast_gicp_mp_impl.hpp:92-221) ----
 constexpr int kGicpMpMerged = 11;  // per source point: neighbours, sum of weights, merged mean (3), merged covariance (6)

@@ -1,6 +1,7 @@
 // rgc_nn.h -- the exact nearest-neighbour search on a cloud's grid (sorted float4 points, cell starts) and the device helpers it is made of,
 // shared by the translation units that search: rgc_kernels.hip (k_fitness, k_icp_accumulate, the kNN kernels use the helpers), rgc_gicp.hip
-// (k_gicp_correspond) and rgc_gicp_mp.hip (the radius gather); transform_f32 is the fp32 query of all of them.  Everything here is
+// (k_gicp_correspond), rgc_gicp_st.hip (k_gicpst_search: nn_search2, the nearest and the second nearest) and rgc_gicp_mp.hip (the radius
+// gather); transform_f32 is the fp32 query of all of them.  Everything here is
 // __forceinline__: each kernel inlines its own copy, the device code of a translation unit that included these definitions in place is
 // unchanged.  Compile with -ffp-contract=off (dist2).
 #pragma once
@@ -195,6 +196,127 @@ __device__ __forceinline__ void nn_search(float px, float py, float pz, const fl
     }
     if (best < INFINITY) {
       const double need = sqrt((double)best) * (1.0 + 1e-5);
+      rn = r + 1;
+      while (rn < rmax) {
+        const double b = cube_bound(g, c, q, rn);
+        if (b == 1.0e300 || b > need) break;
+        rn++;
+      }
+    } else {
+      rn = r + max(1, (r + 1) / 2);
+    }
+    r = min(rn, rmax);
+  }
+}
+
+// Exact nearest AND second-nearest neighbour of (px,py,pz) in the sorted target (FastGICPSingleThread's nearestKSearch(pt, 2),
+// fast_gicp_st_impl.hpp:56-60): nn_search's own-cell-first and cube-walk structure over the two smallest candidates under the total order
+// (key, original index).  best / bs = the smallest's key and sorted position (ties to the smaller original index, as nn_search), second = the
+// second smallest key of the multiset of keys (== best where the nearest is tied or duplicated; INFINITY when the target holds one point).
+// The update is IDEMPOTENT: original indices are unique, so a candidate seen again IS (best, bo) or (second, so) or ranks behind both, and
+// changes nothing -- the clamped tail loads of scan and the re-scans of a growing cube cannot count a point twice into second.
+// Every early exit bounds SECOND, not best: a ball that holds the nearest alone proves nothing about the second nearest.  second >= best, so
+// the ball of second holds every candidate for either (an equal-key tie of best with a smaller index included).
+__device__ __forceinline__ void nn_search2(float px, float py, float pz, const float4* __restrict__ TP, const int* __restrict__ tstart,
+                                           const Grid& g, float& best, int& bs, float& second) {
+  const int c[3] = {cell_coord(px, g) - g.minc[0], cell_coord(py, g) - g.minc[1], cell_coord(pz, g) - g.minc[2]};
+  const double q[3] = {(double)px, (double)py, (double)pz};
+  int rmax = 0, r = 1;
+  bool inside = true;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    rmax = max(rmax, max(c[a], g.dim[a] - 1 - c[a]));
+    r = max(r, max(-c[a], c[a] - (g.dim[a] - 1)));  // first cube that touches the grid when the query lies outside
+    inside = inside && c[a] >= 0 && c[a] < g.dim[a];
+  }
+  best = second = INFINITY;
+  bs = -1;
+  int bo = INT_MAX, so = INT_MAX;
+  auto take = [&](const float4& cp, int s) {
+    const float d = dist2(px, py, pz, cp);
+    const int o = __float_as_int(cp.w);
+    // (selects of values, not branches over which variable to write: the compiler kept the pairs in registers only this way)
+    const bool first = d < best || (d == best && o < bo);
+    const bool next = !first && o != bo && (d < second || (d == second && o < so));
+    second = first ? best : (next ? d : second);
+    so = first ? bo : (next ? o : so);
+    best = first ? d : best;
+    bs = first ? s : bs;
+    bo = first ? o : bo;
+  };
+  auto scan = [&](int s0, int s1) {
+    int s = s0;
+    unsigned off = (unsigned)s0 << 4;
+    for (; s + 8 <= s1; s += 8, off += 128) {  // eight loads in flight, as nn_search
+      float4 cc[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) cc[u] = point_at(TP, off + 16u * u);
+#pragma unroll
+      for (int u = 0; u < 8; u++) take(cc[u], s + u);
+    }
+    if (s < s1) {  // 1..7 left: clamped loads (a repeated candidate changes nothing: the update is idempotent)
+      const int last = s1 - 1;
+      float4 cc[7];
+#pragma unroll
+      for (int u = 0; u < 7; u++) cc[u] = point_at(TP, (unsigned)min(s + u, last) << 4);
+#pragma unroll
+      for (int u = 0; u < 7; u++) take(cc[u], min(s + u, last));
+    }
+  };
+  if (inside) {
+    const int own = cell_index(g, c[0], c[1], c[2]);
+    const int o0 = tstart[own], o1 = tstart[own + 1];
+    scan(o0, o1);
+    if (second < INFINITY) {  // (two points of the own cell at least: one alone bounds nothing)
+      const double bound = cube_bound(g, c, q, 0);
+      if (bound == 1.0e300 || (bound > 0.0 && (double)second < bound * bound * (1.0 - 1e-5))) return;
+      // the ball of the SECOND nearest of the own cell: only the neighbouring cells it reaches can hold a point that changes either of the two
+      const double b1 = cube_bound(g, c, q, 1);
+      if (b1 == 1.0e300 || (b1 > 0.0 && (double)second < b1 * b1 * (1.0 - 1e-5))) {
+        const double rad2 = (double)second * (1.0 + 1e-5);
+        double wl[3], wh[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+          const double wall = cell_wall(g, a, c[a]);
+          wl[a] = q[a] - wall;
+          wh[a] = wall + g.res - q[a];
+        }
+        int ra[9], rb[9];
+#pragma unroll
+        for (int r = 0; r < 9; r++) {
+          const int dy = r % 3 - 1, dz = r / 3 - 1;
+          const int y = c[1] + dy, z = c[2] + dz;
+          const double gy = dy < 0 ? wl[1] : (dy > 0 ? wh[1] : 0.0), gz = dz < 0 ? wl[2] : (dz > 0 ? wh[2] : 0.0);
+          const double m = gy * gy + gz * gz;
+          const bool need = y >= 0 && y < g.dim[1] && z >= 0 && z < g.dim[2] && m <= rad2;
+          const int xa = (c[0] > 0 && wl[0] * wl[0] + m <= rad2) ? c[0] - 1 : c[0];
+          const int xb = (c[0] < g.dim[0] - 1 && wh[0] * wh[0] + m <= rad2) ? c[0] + 1 : c[0];
+          ra[r] = need ? tstart[cell_index(g, xa, y, z)] : 0;
+          rb[r] = need ? tstart[cell_index(g, xb, y, z) + 1] : 0;
+        }
+#pragma unroll
+        for (int r = 0; r < 9; r++) {
+          if (r == 4) {  // the own row: its own cell has been scanned
+            if (ra[4] < o0) scan(ra[4], o0);
+            if (rb[4] > o1) scan(o1, rb[4]);
+          } else if (rb[r] > ra[r]) {
+            scan(ra[r], rb[r]);
+          }
+        }
+        return;
+      }
+    }
+  }
+  for (;;) {
+    // cube [c-r, c+r]^3 as contiguous row ranges of the sorted target (a re-scanned candidate changes nothing)
+    for_each_cube_row(g, c, r, tstart, scan);
+    if (r >= rmax) break;
+    const double bound = cube_bound(g, c, q, r);
+    if (bound == 1.0e300) break;
+    int rn;
+    if (second < INFINITY) {
+      if (bound > 0.0 && (double)second < bound * bound * (1.0 - 1e-5)) break;
+      const double need = sqrt((double)second) * (1.0 + 1e-5);
       rn = r + 1;
       while (rn < rmax) {
         const double b = cube_bound(g, c, q, rn);

@@ -79,6 +79,72 @@ class FastGICP(FastVGICP):
         return out
 
 
+class FastGICPSingleThread(FastGICP):
+    """fast_gicp::FastGICPSingleThread (include/fast_gicp/gicp/fast_gicp_st.hpp:20-65, impl/fast_gicp_st_impl.hpp:19-125) behind rgc_gicpst_*: FastGICP
+    whose source points keep an anchor and are searched again only when the triangle inequality cannot prove their nearest neighbour unchanged; a point
+    that is not searched keeps its pair, its keys and its Mahalanobis matrix.  Derives from FastGICP as the reference class does: the clouds, the
+    covariances and setMaxCorrespondenceDistance are FastGICP's; linearize / compute_error / align / num_correspondences / correspondences are this
+    method's.  align() drops the anchors first (:19-22); reset() drops them between linearisations.
+
+        st = FastGICPSingleThread(device=0)
+        st.setInputTarget(map_cloud); st.setInputSource(scan)
+        st.align(guess, want_output=False); T = st.getFinalTransformation(); searched_last = st.num_searched()"""
+
+    def reset(self):                                  # anchors_.clear() (fast_gicp_st_impl.hpp:20): the next linearize searches every point
+        self._chk(self._L.rgc_gicpst_reset(self._h))
+
+    def linearize(self, T, want_H=True):
+        """returns (cost, H, b) -- H and b None unless want_H"""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+        H, b, cost = np.zeros(36), np.zeros(6), C.c_double(0.0)
+        self._chk(self._L.rgc_gicpst_linearize(self._h, T.ctypes.data_as(_dp), H.ctypes.data_as(_dp) if want_H else None,
+                                               b.ctypes.data_as(_dp) if want_H else None, C.byref(cost)))
+        return (cost.value, H.reshape(6, 6), b) if want_H else (cost.value, None, None)
+
+    def compute_error(self, T) -> float:
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
+        cost = C.c_double(0.0)
+        self._chk(self._L.rgc_gicpst_compute_error(self._h, T.ctypes.data_as(_dp), C.byref(cost)))
+        return cost.value
+
+    @property
+    def num_correspondences(self) -> int:
+        n = C.c_int(0)
+        self._chk(self._L.rgc_gicpst_num_correspondences(self._h, C.byref(n)))
+        return n.value
+
+    def num_searched(self) -> int:
+        """source points the last linearize searched (all of them on the first one after a reset)"""
+        n = C.c_int(0)
+        self._chk(self._L.rgc_gicpst_num_searched(self._h, C.byref(n)))
+        return n.value
+
+    def correspondences(self):
+        """(idx, sq_dist, second_sq_dist, searched) after the last linearize, in the source's order: idx int32, -1 where not kept; the fp32 keys to the
+        nearest and the second nearest at the point's anchor; searched bool, True where the last linearize searched the point"""
+        n = self._n_src
+        idx, sq, sq2, was = np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.int32)
+        self._chk(self._L.rgc_gicpst_get_correspondences(self._h, idx.ctypes.data_as(_ip), sq.ctypes.data_as(_fp), sq2.ctypes.data_as(_fp), was.ctypes.data_as(_ip)))
+        return idx, sq, sq2, was.astype(bool)
+
+    def align(self, guess=None, want_output=True, want_fitness=False):
+        """pcl::Registration::align(output, guess): the transformed source cloud (n, 3) float32, or None if want_output=False"""
+        g = np.ascontiguousarray(np.eye(4) if guess is None else guess, dtype=np.float32).reshape(16)
+        fin, H = np.empty(16, np.float32), np.empty(36)
+        fit = C.c_double(0.0)
+        it, cv, lf = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self._L.rgc_gicpst_align(self._h, g.ctypes.data_as(_fp), fin.ctypes.data_as(_fp), H.ctypes.data_as(_dp),
+                                           C.byref(fit) if want_fitness else None, C.byref(it), C.byref(cv), C.byref(lf)))
+        self._final, self._H = fin.reshape(4, 4), H.reshape(6, 6)
+        self._iterations, self._converged, self._lm_failed = it.value, bool(cv.value), bool(lf.value)
+        self._fitness = fit.value if want_fitness else None
+        if not want_output:
+            return None
+        out = np.empty((self._n_src, 3), np.float32)
+        self._chk(self._L.rgc_get_aligned(self._h, fin.ctypes.data_as(_fp), out.ctypes.data_as(_fp), 12))
+        return out
+
+
 class FastGICPMultiPoints(FastVGICP):
     """fast_gicp::FastGICPMultiPoints (include/fast_gicp/gicp/experimental/fast_gicp_mp.hpp:40-53, fast_gicp_mp_impl.hpp:92-221) behind rgc_gicpmp_*: every
     source point against the distance-weighted merge of every target Gaussian within the search radius, plain Gauss-Newton.  On the clouds of a

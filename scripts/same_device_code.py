@@ -1,7 +1,8 @@
 """Do two builds of the library hold the same gfx950 device code?  Extracts the code objects of both (llvm-objdump --offloading, in scratch directories) and
 compares, per code object, the SHA-256 of the .text section and the kernel descriptors' resources (scripts/kernel_resources.py).  Used to show that the
 in-tree librgc_hip.so is what the committed sources build to, and that a change meant to leave the product alone (a comment, a default-off flag) did.  No GPU.
-    python scripts/same_device_code.py <library A> <library B>"""
+    python scripts/same_device_code.py <library A> <library B> [--subset]
+--subset: B may hold code objects A has not (a new translation unit); every code object of A must be in B unchanged."""
 import hashlib
 import os
 import shutil
@@ -29,7 +30,8 @@ def text_hashes(lib):
 
 
 def main():
-    a, b = sys.argv[1], sys.argv[2]
+    subset = "--subset" in sys.argv[1:]
+    a, b = [x for x in sys.argv[1:] if x != "--subset"][:2]
     ha, hb = text_hashes(a), text_hashes(b)
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import kernel_resources as kr
@@ -45,6 +47,20 @@ def main():
         for n in sorted(set(da) | set(db)):
             if da.get(n) != db.get(n):
                 print("  ", n[:90], da.get(n), "->", db.get(n))
+    if subset:  # B = A plus new translation units: every code object of A is in B byte for byte, every kernel of A keeps its resources in B
+        left = list(hb)
+        kept = 0
+        for h in ha:
+            if h in left:
+                left.remove(h)
+                kept += 1
+        db = dict((r[0], r[1:]) for r in rb)
+        same_kernels = all(db.get(r[0]) == r[1:] for r in ra)
+        print(f"--subset: {kept} of {len(ha)} code objects of A are in B byte for byte (.text), {len(left)} code object(s) only in B with {len(rb) - len(ra)} more kernels;",
+              "every kernel of A has the same resources in B" if same_kernels else "a kernel of A has other resources in B")
+        for n in sorted(set(db) - set(r[0] for r in ra)):
+            print("   only in B:", n[:110], db[n])
+        sys.exit(0 if kept == len(ha) and same_kernels else 1)
     sys.exit(0 if same_text and same_res else 1)
 
 
