@@ -61,7 +61,7 @@ typedef enum rgc_status {
  * A HIP error is reported once, by the call it happened in (RGC_ERR_HIP, rgc_last_error); it does not surface again. */
 
 /* enum order = fast_gicp::NeighborSearchMethod, include/fast_gicp/gicp/gicp_settings.hpp:8 */
-typedef enum rgc_neighbor_method { RGC_DIRECT27 = 0, RGC_DIRECT7 = 1, RGC_DIRECT1 = 2 } rgc_neighbor_method;
+typedef enum rgc_neighbor_method { RGC_DIRECT27 = 0, RGC_DIRECT7 = 1, RGC_DIRECT1 = 2, RGC_DIRECT_RADIUS = 3 } rgc_neighbor_method;
 
 /* Parameter block = the setters the odometer calls on fast_gicp::FastVGICP (src/RGC_odometer.cpp:998-1006)
  * plus the constructor defaults they leave untouched.  Defaults: rgc_default_params(). */
@@ -133,6 +133,38 @@ RGC_API void rgc_destroy(rgc_ctx* ctx);
  * clouds the context holds again, from their inputs (a device cloud must still be where it was set from); refused with a solve in flight. */
 RGC_API int  rgc_set_params(rgc_ctx* ctx, const rgc_params* params);
 RGC_API int  rgc_get_params(const rgc_ctx* ctx, rgc_params* params);
+/* FastVGICPCuda::setNeighborSearchMethod(method, radius) (include/fast_gicp/gicp/fast_vgicp_cuda.hpp:60, impl/fast_vgicp_cuda_impl.hpp:58-61,
+ * src/fast_gicp/cuda/fast_vgicp_cuda.cu:42-95; NeighborSearchMethod::DIRECT_RADIUS, gicp_settings.hpp:8, "supported on only VGICP_CUDA").
+ * RGC_DIRECT_RADIUS looks a source point up in every voxel whose integer offset (i, j, k) from the point's own cell lies in
+ * [-ceil(r), ceil(r)]^3 with sqrt((double)(i*i + j*j + k*k)) <= r + 1e-3, in nested i, j, k order (fast_vgicp_cuda.cu:77-91): 1 offset below
+ * r = 0.999, 7 from there, 19 from 1.4133, 27 from 1.7311, 33 at 2.0, 123 at 3.0, 485 at 4.9.  Every hit is a correspondence of its own with
+ * the term of the other methods (src/fast_gicp/cuda/compute_derivatives.cu:50-92): w = sqrt(num_points), M = (C_B + R C_A R^T)^-1,
+ * J = [skew(R a + t), -I].
+ *   rgc_neighbor_offsets      the offset table of a method (0..2: the lists of fast_vgicp_voxel.hpp:10-44, in their order; 3: the rule above):
+ *                             *n = the table's size, at most cap offsets (3 ints each) written to xyz (NULL: the size alone).  Host code, no
+ *                             context, no GPU.  The table is also NDT's (rgc_ndt_set_params).  RGC_ERR_INVALID: NULL n, a method outside 0..3,
+ *                             under method 3 a radius that is not finite and >= 0 or a table above RGC_NDT_MAX_OFFSETS (r >= 4.9...).
+ *   rgc_set_neighbor_search   methods 0..2 ignore the radius, whatever it is (the reference's default argument is -1.0), and the stored one
+ *                             stays; method 3 needs a finite radius >= 0 whose table has at most RGC_NDT_MAX_OFFSETS offsets: otherwise
+ *                             RGC_ERR_INVALID and nothing changes.  (The reference builds an EMPTY table for a negative radius and solves over
+ *                             nothing: not reproduced.)  Refused with a solve in flight, like rgc_set_params.  Drops no cloud; the
+ *                             correspondences the last linearisation froze stay what rgc_compute_error evaluates (rgc_set_params' rule).
+ *   rgc_get_neighbor_search   the selection and the stored radius (0.0 on a new context).
+ * rgc_params keeps its layout: rgc_get_params reports neighbor_method == 3 while the radius method is selected, and while it is selected
+ * rgc_set_params accepts 3 and keeps the stored radius, so get / modify / set round-trips (and an adaptor that pushes the whole block from every
+ * setter keeps the selection).  The block carries no radius, so it cannot SELECT the method: 3 in rgc_set_params or rgc_create on a context
+ * whose selection is another method is RGC_ERR_INVALID, as before -- rgc_set_neighbor_search selects it.
+ * Under RGC_DIRECT_RADIUS rgc_linearize, rgc_compute_error, rgc_num_correspondences and rgc_align* run over a kernel of their own (a group of
+ * lanes per source point, the table walked in strides) on both covariance routes, and the solve is ALWAYS driven by the host LM loop, whatever
+ * RGC_LM_IMPL says: rgc_align_begin solves at once and rgc_align_end (and rgc_align_end_reframe through it) hands the result over, the rule of
+ * the general route; rgc_set_target_lazy has no effect (a lazy target is completed before the solve: the full build's results).  Re-framed,
+ * shared, borrowed, map-bound and swapped targets need nothing new.  The frozen list costs 52 bytes per source point and offset.
+ * Results are bit-identical from run to run and between host and device inputs; fp64 after the fp32 points (the reference: fp32), a dense
+ * grid (the reference's hash table gives up after max_bucket_scan_count probes: not reproduced), sums in a fixed order (the reference's
+ * thrust reduction: unspecified). */
+RGC_API int  rgc_neighbor_offsets(int method, double radius, int* xyz /* 3 * cap ints, nullable */, int cap, int* n);
+RGC_API int  rgc_set_neighbor_search(rgc_ctx* ctx, int method, double radius);
+RGC_API int  rgc_get_neighbor_search(const rgc_ctx* ctx, int* method, double* radius);
 RGC_API const char* rgc_last_error(const rgc_ctx* ctx);
 RGC_API const char* rgc_status_string(int status);
 RGC_API const char* rgc_version(void);

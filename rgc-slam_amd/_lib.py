@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RGC_HIP_LIB") or os.path.join(_HERE, "librgc_hip.so")  # RGC_HIP_LIB: developer override (A/B builds)
 
-DIRECT27, DIRECT7, DIRECT1 = 0, 1, 2
+DIRECT27, DIRECT7, DIRECT1, DIRECT_RADIUS = 0, 1, 2, 3
 
 K_GRID, K_KNN_COV, K_VOXEL, K_LINEARIZE, K_ERROR, K_FITNESS, K_KNN_COV_SRC, K_KNN_COOP, K_KNN_COOP_SRC, K_COUNT = range(10)
 
@@ -179,7 +179,7 @@ class RgcError(RuntimeError):
 
 # every symbol include/rgc_hip.h declares (checked by tests/test_abi.py against the header text)
 SYMBOLS = [
-    "rgc_default_params", "rgc_create", "rgc_destroy", "rgc_set_params", "rgc_get_params", "rgc_last_error",
+    "rgc_default_params", "rgc_create", "rgc_destroy", "rgc_set_params", "rgc_get_params", "rgc_neighbor_offsets", "rgc_set_neighbor_search", "rgc_get_neighbor_search", "rgc_last_error",
     "rgc_status_string", "rgc_version", "rgc_set_target", "rgc_set_source", "rgc_set_target_device",
     "rgc_set_source_device", "rgc_linearize", "rgc_compute_error", "rgc_num_correspondences", "rgc_align", "rgc_align_begin", "rgc_align_end", "rgc_align_end_reframe", "rgc_share_target", "rgc_hold_source_until_target_of", "rgc_set_target_lazy", "rgc_set_knn_reuse", "rgc_get_knn_reuse", "rgc_set_regularization_method", "rgc_set_voxel_accumulation_mode",
     "rgc_set_covariance_estimation", "rgc_get_covariance_estimation", "rgc_set_rbf_kernel", "rgc_get_rbf_kernel",
@@ -267,6 +267,9 @@ def load():
     L.rgc_destroy.restype = None
     L.rgc_set_params.argtypes = [vp, C.POINTER(Params)]
     L.rgc_get_params.argtypes = [vp, C.POINTER(Params)]
+    L.rgc_neighbor_offsets.argtypes = [C.c_int, C.c_double, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
+    L.rgc_set_neighbor_search.argtypes = [vp, C.c_int, C.c_double]
+    L.rgc_get_neighbor_search.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     L.rgc_last_error.argtypes = [vp]
     L.rgc_last_error.restype = C.c_char_p
     L.rgc_status_string.argtypes = [C.c_int]

@@ -29,7 +29,7 @@
 
 namespace rgc {
 
-enum class NeighborSearchMethod { DIRECT27 = RGC_DIRECT27, DIRECT7 = RGC_DIRECT7, DIRECT1 = RGC_DIRECT1 };  // gicp_settings.hpp:8
+enum class NeighborSearchMethod { DIRECT27 = RGC_DIRECT27, DIRECT7 = RGC_DIRECT7, DIRECT1 = RGC_DIRECT1, DIRECT_RADIUS = RGC_DIRECT_RADIUS };  // gicp_settings.hpp:8
 enum class RegularizationMethod { NONE, MIN_EIG, NORMALIZED_MIN_EIG, PLANE, FROBENIUS };                    // gicp_settings.hpp:6
 enum class VoxelAccumulationMode { ADDITIVE, ADDITIVE_WEIGHTED, MULTIPLICATIVE };                            // gicp_settings.hpp:10
 enum class NearestNeighborMethod { CPU_PARALLEL_KDTREE, GPU_BRUTEFORCE, GPU_RBF_KERNEL };                    // fast_vgicp_cuda.hpp:21
@@ -55,7 +55,21 @@ public:
   void setRotationEpsilon(double e) { p_.rotation_eps = e; push(); }               // lsq_registration_impl.hpp:27-29
   void setInitialLambdaFactor(double f) { p_.lm_init_lambda_factor = f; push(); }  // lsq_registration_impl.hpp:32-34
   void setCorrespondenceRandomness(int k) { p_.k_correspondences = k; push(); }    // fast_gicp_impl.hpp:41-43
-  void setNeighborSearchMethod(NeighborSearchMethod m) { p_.neighbor_method = (int)m; push(); }
+  // FastVGICPCuda's (method, radius) (fast_vgicp_cuda.hpp:60): the radius counts under DIRECT_RADIUS only (rgc_set_neighbor_search in rgc_hip.h).  A
+  // refused selection stays pending like a refused parameter block; an accepted one goes into the block the other setters push.
+  void setNeighborSearchMethod(NeighborSearchMethod m, double radius = -1.0) {
+    ns_method_ = (int)m; ns_radius_ = radius;
+    const int rc = rgc_set_neighbor_search(ctx_, ns_method_, ns_radius_);
+    ns_dirty_ = rc != RGC_OK;
+    if (!ns_dirty_) p_.neighbor_method = ns_method_;
+    note(rc);
+  }
+  NeighborSearchMethod getNeighborSearchMethod(double* radius = nullptr) const {
+    int m = RGC_DIRECT1; double r = 0.0;
+    rgc_get_neighbor_search(ctx_, &m, &r);
+    if (radius) *radius = r;
+    return (NeighborSearchMethod)m;
+  }
   // the odometer leaves both at the constructor's values (PLANE, fast_gicp_impl.hpp:20; ADDITIVE, fast_vgicp_impl.hpp:24), which run on the
   // tuned kernels; every other value is implemented on the library's general route (rgc_set_regularization_method in rgc_hip.h: a 3x3 per
   // point, unoptimised).  Select before setInputTarget / setInputSource: a change drops the clouds that were set under the other setting.
@@ -192,10 +206,16 @@ private:
   // call that computes something offers them again (params()) -- and throws if they are still refused
   void note(int rc) { setter_status_ = rc; setter_error_ = rc == RGC_OK ? std::string() : std::string(rgc_status_string(rc)) + ": " + rgc_last_error(ctx_); }
   void push() { const int rc = rgc_set_params(ctx_, &p_); params_dirty_ = rc != RGC_OK; note(rc); }
-  void params() { if (params_dirty_) { chk(rgc_set_params(ctx_, &p_)); params_dirty_ = false; } }
+  void params() {
+    if (ns_dirty_) { chk(rgc_set_neighbor_search(ctx_, ns_method_, ns_radius_)); ns_dirty_ = false; p_.neighbor_method = ns_method_; }
+    if (params_dirty_) { chk(rgc_set_params(ctx_, &p_)); params_dirty_ = false; }
+  }
   int setter_status_ = RGC_OK;
   std::string setter_error_;
   bool params_dirty_ = false;
+  bool ns_dirty_ = false;  // a neighbour selection the library refused, offered again by params()
+  int ns_method_ = RGC_DIRECT1;
+  double ns_radius_ = -1.0;
   rgc_ctx* ctx_ = nullptr;
   rgc_params p_{};
   float final_[16];

@@ -1,5 +1,6 @@
 // rgc_api.hip -- host side of librgc_hip.so, the core: context, device buffers, the clouds' preparation, the VGICP registration
-// (rgc_align*, rgc_linearize, ...), its getters and setters, statistics and profiling.  The per-point work is in rgc_kernels.hip.  The
+// (rgc_align*, rgc_linearize, ...), its getters and setters, statistics and profiling.  The per-point work is in rgc_kernels.hip (the
+// linearisation under RGC_DIRECT_RADIUS: rgc_vgicp_radius.hip).  The
 // rest of the C-ABI of include/rgc_hip.h: rgc_api_pre.hip (B2 / B3 / B9, the front end), rgc_api_mapping.hip (f1-f5), rgc_api_lsq.hip
 // (the LM driver of lsq_registration_impl.hpp:53-172 that rgc_align's host route shares with NDT and FastGICP); rgc_ctx.h is what they share.
 //
@@ -147,12 +148,27 @@ static void prof_collect(rgc_ctx* c) {
   c->prof_open.clear();
 }
 
-static int noff_of(int method) { return method == RGC_DIRECT1 ? 1 : (method == RGC_DIRECT7 ? 7 : 27); }
+// RGC_DIRECT_RADIUS: the context's offset table (made from the stored radius where no rgc_set_neighbor_search has made it yet: a radius that was
+// stored has passed that call's checks, and the initial 0.0 is the own cell alone)
+static bool radius_method(const rgc_ctx* c) { return c->prm.neighbor_method == RGC_DIRECT_RADIUS; }
+static const std::vector<int>& radius_table(rgc_ctx* c) {
+  if (c->vr_offs_h.empty()) { neighbor_offsets_of(RGC_DIRECT_RADIUS, c->nbr_radius, c->vr_offs_h); c->vr_offs_dirty = true; }
+  return c->vr_offs_h;
+}
+static int noff_of(rgc_ctx* c) {
+  const int method = c->prm.neighbor_method;
+  if (method == RGC_DIRECT_RADIUS) return (int)radius_table(c).size() / 3;
+  return method == RGC_DIRECT1 ? 1 : (method == RGC_DIRECT7 ? 7 : 27);
+}
 
 static int check_params(rgc_ctx* c, const rgc_params* p) {
   if (!(p->voxel_res > 0.0) || !std::isfinite(p->voxel_res)) return fail(c, RGC_ERR_INVALID, "voxel_res must be > 0");
   if (p->k_correspondences < 2 || p->k_correspondences > kMaxK) return fail(c, RGC_ERR_INVALID, "k_correspondences must be in [2,%d]", kMaxK);
-  if (p->neighbor_method < RGC_DIRECT27 || p->neighbor_method > RGC_DIRECT1) return fail(c, RGC_ERR_INVALID, "bad neighbor_method");
+  if (p->neighbor_method < RGC_DIRECT27 || p->neighbor_method > RGC_DIRECT_RADIUS) return fail(c, RGC_ERR_INVALID, "bad neighbor_method");
+  // RGC_DIRECT_RADIUS needs a radius, which this block does not carry: it is SELECTED by rgc_set_neighbor_search alone.  While it is the
+  // selection a block that names it is taken (what rgc_get_params handed out comes back: get / modify / set keeps it, with the stored radius)
+  if (p->neighbor_method == RGC_DIRECT_RADIUS && c->prm.neighbor_method != RGC_DIRECT_RADIUS)
+    return fail(c, RGC_ERR_INVALID, "RGC_DIRECT_RADIUS is selected with rgc_set_neighbor_search (it takes the radius)");
   if (p->max_iterations < 0 || p->lm_max_iterations < 1) return fail(c, RGC_ERR_INVALID, "bad iteration limits");
   if (!(p->rotation_eps > 0) || !(p->translation_eps > 0)) return fail(c, RGC_ERR_INVALID, "epsilons must be > 0");
   if (p->max_cells < 1) return fail(c, RGC_ERR_INVALID, "max_cells must be >= 1");
@@ -223,7 +239,8 @@ static int ensure_voxel_table(rgc_ctx* c, Cloud& cl, int ncell) {
 }
 // what a linearisation of n source points freezes and folds: corr_v / corr_M for noff offsets, row_doubles per workgroup in partials
 static int ensure_corr(rgc_ctx* c, int n, int noff, size_t row_doubles) {
-  const size_t nb = (size_t)rgck::linearize_blocks(n);
+  // (RGC_DIRECT_RADIUS: a workgroup of its linearisation takes fewer points -- more rows than k_error's, which folds into the same buffer)
+  const size_t nb = (size_t)std::max(rgck::linearize_blocks(n), radius_method(c) ? rgck::vgicp_radius_blocks(n) : 0);
   int rc;
   if ((rc = ensure(c, c->corr_v, sizeof(int) * (size_t)n * noff))) return rc;
   if ((rc = ensure(c, c->corr_M, sizeof(double) * 6 * (size_t)n * noff))) return rc;
@@ -969,16 +986,36 @@ void unpack_system(const double sums[28], double H[36], double b[6]) {
 }
 
 // the scan linearised at T against the map's voxels, on the route the scan was prepared on: the 28 sums to d_out, the count to d_small->ncorr
-static void enqueue_linearize(rgc_ctx* c, const double T[16], int noff, int want_H) {
+// RGC_DIRECT_RADIUS: over the offset table, a group of lanes per source point (rgc_vgicp_radius.hip); the table goes to the device when it has
+// changed since the last linearisation (in stream order on the context's stream: behind every launch that reads the former one)
+static int enqueue_linearize(rgc_ctx* c, const double T[16], int noff, int want_H) {
   const Cloud& src = c->src;
   double* partials = c->partials.as<double>();
   int* ipartials = c->ipartials.as<int>();
+  if (radius_method(c)) {
+    const std::vector<int>& tab = radius_table(c);
+    if (c->vr_offs_dirty || !c->vr_offs.p) {
+      int rc = ensure(c, c->vr_offs, sizeof(int) * (size_t)kMaxNeighborOffsets);
+      if (rc) return rc;
+      // (the packed copy lives in the context: the asynchronous copy may read it after this call; every linearisation ends in a synchronisation
+      // of the stream, so the next selection finds it read)
+      c->vr_packed_h.resize((size_t)noff);
+      for (int o = 0; o < noff; o++) c->vr_packed_h[o] = rgck::vgicp_radius_pack(tab[3 * o], tab[3 * o + 1], tab[3 * o + 2]);
+      HIPCHK(c, hipMemcpyAsync(c->vr_offs.p, c->vr_packed_h.data(), sizeof(int) * (size_t)noff, hipMemcpyHostToDevice, c->stream));
+      c->vr_offs_dirty = false;
+    }
+    const rgck::GicpCov A{src.general ? src.c6.as<const double>() : nullptr, src.nx.as<const double>(), src.ny.as<const double>(), src.nz.as<const double>()};
+    rgck::vgicp_radius_linearize(c->stream, src.sorted(), A, pose_from(T), c->tgt.grid, c->tgt.voxels(), c->vr_offs.as<const int>(), noff, corr_of(c), want_H,
+                                 partials, ipartials, c->d_out, &c->d_small->ncorr);
+    return RGC_OK;
+  }
   if (src.general)
     rgck::linearize_general(c->stream, src.sorted(), src.c6.as<double>(), pose_from(T), c->tgt.grid, c->tgt.voxels(), noff, corr_of(c), want_H, partials,
                             ipartials, c->d_out, &c->d_small->ncorr);
   else
     rgck::linearize(c->stream, src.sorted(), src.normals(), pose_from(T), c->tgt.grid, c->tgt.voxels(), noff, corr_of(c), want_H, partials, ipartials,
                     c->d_out, &c->d_small->ncorr);
+  return RGC_OK;
 }
 // the first ndoubles of the output block, home (one synchronisation)
 static int fetch_out(rgc_ctx* c, size_t ndoubles) {
@@ -990,12 +1027,12 @@ static int fetch_out(rgc_ctx* c, size_t ndoubles) {
 static int do_linearize(rgc_ctx* c, const double T[16], double* H, double* b, double* cost) {
   int rc = need_inputs(c);
   if (rc) return rc;
-  const int n = c->src.n, noff = noff_of(c->prm.neighbor_method);
+  const int n = c->src.n, noff = noff_of(c);
   if ((rc = ensure_corr(c, n, noff, rgck::kAccum))) return rc;
   const int want = (H && b) ? 1 : 0;
   {
     ProfScope ps(c, RGC_K_LINEARIZE, n);
-    enqueue_linearize(c, T, noff, want);
+    if ((rc = enqueue_linearize(c, T, noff, want))) return rc;
   }
   HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(double) * rgck::kAccum, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(&c->h_small->ncorr, &c->d_small->ncorr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -1017,7 +1054,7 @@ static int do_linearize_try(rgc_ctx* c, const double x0[16], double lambda, doub
                      double* lambda_used, double* yi) {
   int rc = need_inputs(c);
   if (rc) return rc;
-  const int n = c->src.n, noff = noff_of(c->prm.neighbor_method);
+  const int n = c->src.n, noff = noff_of(c);
   if ((rc = ensure_corr(c, n, noff, rgck::kAccum))) return rc;
   rgck::LmIn in;
   for (int i = 0; i < 16; i++) in.x0[i] = x0[i];
@@ -1025,7 +1062,7 @@ static int do_linearize_try(rgc_ctx* c, const double x0[16], double lambda, doub
   in.init_factor = c->prm.lm_init_lambda_factor;
   {
     ProfScope ps(c, RGC_K_LINEARIZE, n);
-    enqueue_linearize(c, x0, noff, 1);
+    if ((rc = enqueue_linearize(c, x0, noff, 1))) return rc;
     rgck::lm_try(c->stream, c->d_out, &c->d_small->ncorr, in);
   }
   {
@@ -1262,7 +1299,7 @@ void rgc_destroy(rgc_ctx* c) {
   for (DevBuf* b : {&c->pgo_i, &c->pgo_d, &c->pgo_M}) release(*b);
   release_cloud(c->ndt_cl[0]);
   release_cloud(c->ndt_cl[1]);
-  for (DevBuf* b : {&c->ndt_offs, &c->ndt_corr, &c->ndt_partials, &c->ndt_ipartials, &c->ndt_small, &c->ndt_out}) release(*b);
+  for (DevBuf* b : {&c->vr_offs, &c->ndt_offs, &c->ndt_corr, &c->ndt_partials, &c->ndt_ipartials, &c->ndt_small, &c->ndt_out}) release(*b);
   if (c->ndt_h_out) (void)hipHostFree(c->ndt_h_out);
   if (c->ndt_h_small) (void)hipHostFree(c->ndt_h_small);
   for (DevBuf* b : {&c->gicp_corr, &c->gicp_key, &c->gicp_M, &c->gicp_partials, &c->gicp_out}) release(*b);
@@ -1291,6 +1328,9 @@ int rgc_set_params(rgc_ctx* c, const rgc_params* p) {
   if (rc) return rc;
   const bool redo = p->voxel_res != c->prm.voxel_res || p->k_correspondences != c->prm.k_correspondences;
   if (redo && solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");  // (the clouds are prepared again below)
+  // (away from RGC_DIRECT_RADIUS with its solved result waiting to be handed over: refused like rgc_set_neighbor_search)
+  if (p->neighbor_method != c->prm.neighbor_method && radius_method(c) && solve_in_flight(c))
+    return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
   if (redo) HIPCHK(c, hipSetDevice(c->device));  // (the re-preparation launches kernels: like every entry point that does, whatever device the calling thread had current)
   if (p->voxel_res != c->prm.voxel_res) c->src_res_auto = 0.0;
   c->prm = *p;
@@ -1315,6 +1355,32 @@ int rgc_set_params(rgc_ctx* c, const rgc_params* p) {
 int rgc_get_params(const rgc_ctx* c, rgc_params* p) {
   if (!c || !p) return RGC_ERR_INVALID;
   *p = c->prm;
+  return RGC_OK;
+}
+
+// FastVGICPCuda::setNeighborSearchMethod(method, radius): fast_vgicp_cuda.hpp:60, impl/fast_vgicp_cuda_impl.hpp:58-61, fast_vgicp_cuda.cu:42-95
+int rgc_set_neighbor_search(rgc_ctx* c, int method, double radius) {
+  if (!c) return RGC_ERR_INVALID;
+  if (method < RGC_DIRECT27 || method > RGC_DIRECT_RADIUS) return fail(c, RGC_ERR_INVALID, "rgc_set_neighbor_search: no neighbour method %d", method);
+  if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
+  if (method == RGC_DIRECT_RADIUS) {
+    if (!std::isfinite(radius) || radius < 0.0) return fail(c, RGC_ERR_INVALID, "rgc_set_neighbor_search: RGC_DIRECT_RADIUS needs a finite radius >= 0");
+    std::vector<int> offs;
+    if (!neighbor_offsets_of(method, radius, offs))
+      return fail(c, RGC_ERR_INVALID, "rgc_set_neighbor_search: radius %g has more than %d offsets", radius, kMaxNeighborOffsets);
+    c->nbr_radius = radius;
+    c->vr_offs_h.swap(offs);
+    c->vr_offs_dirty = true;  // (uploaded by the next linearisation, in stream order)
+  }
+  // (the correspondences the last linearisation froze stay in force, with their own offset count: rgc_set_params' rule for a new method)
+  c->prm.neighbor_method = method;
+  return RGC_OK;
+}
+
+int rgc_get_neighbor_search(const rgc_ctx* c, int* method, double* radius) {
+  if (!c || !method || !radius) return RGC_ERR_INVALID;
+  *method = c->prm.neighbor_method;
+  *radius = c->nbr_radius;
   return RGC_OK;
 }
 
@@ -1512,7 +1578,7 @@ int rgc_num_correspondences(rgc_ctx* c, int* n) {
 // solve from its opening to its posted result), otherwise one batch of blind LM steps (the first launch of a solve opens it), the fitness
 // kernel behind them and the state's read-back.
 static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, bool want_fitness) {
-  const int n = c->src.n, noff = noff_of(c->prm.neighbor_method), nb_lm = rgck::linearize_blocks(n);
+  const int n = c->src.n, noff = noff_of(c), nb_lm = rgck::linearize_blocks(n);
   hipStream_t s = c->solve_stream;  // see rgc_align_begin
   rgck::LmState* post = (c->post_on && c->d_post) ? c->d_post : nullptr;
   const int seq = want_fitness ? -c->lm_seq : c->lm_seq;  // what is posted: a finished state (> 0), or a finished state with its score (< 0)
@@ -1587,7 +1653,7 @@ static int lm_enqueue_batch(rgc_ctx* c, int batch, const rgck::LmInit* open, boo
 int rgc_align_begin(rgc_ctx* c, const float guess[16], int want_fitness) {
   if (!c || !guess) return RGC_ERR_INVALID;
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-  if (general_route(c)) {  // no asynchronous form on the general route: the solve runs now, rgc_align_end hands its result over
+  if (general_route(c) || radius_method(c)) {  // no asynchronous form on the general route or under RGC_DIRECT_RADIUS: the solve runs now, rgc_align_end hands its result over
     auto& g = c->gen_res;
     g.on = false;
     g.rc = rgc_align(c, guess, g.T, g.H, want_fitness ? &g.fitness : nullptr, &g.iterations, &g.converged, &g.lm_failed);
@@ -1631,7 +1697,7 @@ int rgc_align_begin(rgc_ctx* c, const float guess[16], int want_fitness) {
   const rgc_params& P = c->prm;
   // device-chained LM: the loop of :65-75 / :125-172 runs as a state machine on the device (k_lm_step);
   // the host only enqueues slots and reads the state back once per batch.
-  const int n = c->src.n, noff = noff_of(P.neighbor_method);
+  const int n = c->src.n, noff = noff_of(c);
   if ((rc = ensure_corr(c, n, noff, (rgck::kAccum + 2) * 2))) return rc;  // (two halves of kAccum + 2 doubles per workgroup: rgck::LmArgs)
   if ((rc = ensure(c, c->corr_v2, sizeof(int) * (size_t)n * noff))) return rc;
   if ((rc = ensure(c, c->corr_M2, sizeof(double) * 6 * (size_t)n * noff))) return rc;
@@ -1746,7 +1812,7 @@ static int lm_wait_result(rgc_ctx* c, bool want_fitness, rgck::LmState& S) {
 
 // what the finished state carries home beside the pose: the valid correspondence buffer, the frame's counters, the sizes of the next launches
 static void lm_adopt_result(rgc_ctx* c, const rgck::LmState& S) {
-  const int n = c->src.n, noff = noff_of(c->prm.neighbor_method);
+  const int n = c->src.n, noff = noff_of(c);
   if (S.cur) { std::swap(c->corr_v, c->corr_v2); std::swap(c->corr_M, c->corr_M2); }  // corr_v / corr_M = the valid buffer
   c->corr_noff = noff; c->corr_n = n; c->corr_valid = S.n_lin > 0;
   c->stats.n_corr = S.ncorr; c->stats.n_linearize = S.n_lin; c->stats.n_error = S.n_err;
@@ -1834,11 +1900,12 @@ int rgc_align_end(rgc_ctx* c, float final_T[16], double final_H[36], double* fit
 int rgc_align(rgc_ctx* c, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations,
               int* converged, int* lm_failed) {
   if (!c || !guess) return RGC_ERR_INVALID;
-  if (!c->lm_host && !general_route(c)) {
+  if (!c->lm_host && !general_route(c) && !radius_method(c)) {
     const int rc0 = rgc_align_begin(c, guess, fitness != nullptr);
     return rc0 ? rc0 : rgc_align_end(c, final_T, final_H, fitness, iterations, converged, lm_failed);
   }
-  // (the general covariance route solves here as well: the device-chained driver's step kernel takes the source's NORMAL)
+  // (the general covariance route solves here as well: the device-chained driver's step kernel takes the source's NORMAL; and RGC_DIRECT_RADIUS,
+  // whose linearisation is a launch of its own over the offset table -- 19 to 485 look-ups per point: the hand-offs the device LM hides do not dominate)
   // ---- RGC_LM_IMPL=host: the shared host driver (rgc_api_lsq.hip) over the public fine-seam kernels, the first try of every outer
   // iteration on the device (do_linearize_try) -- a cross-check of the device-chained driver ----
   HIPCHK(c, hipSetDevice(c->device));

@@ -72,19 +72,8 @@ static int read_sums(rgc_ctx* c, double* h_out, const DevBuf& d_out, int k) {
   return RGC_OK;
 }
 
-extern "C" {
-
-// ---- NDT registration (P2D / D2D) on a Gaussian voxel map: fast_gicp::NDTCuda (src/fast_gicp/cuda/ndt_cuda.cu, ndt_compute_derivatives.cu) ----
-void rgc_default_ndt_params(rgc_ndt_params* p) {
-  if (!p) return;
-  p->resolution = 1.0;                     // src/fast_gicp/cuda/ndt_cuda.cu:15
-  p->distance_mode = RGC_NDT_D2D;          // :21
-  p->neighbor_method = RGC_NDT_DIRECT7;    // :22
-  p->neighbor_radius = 0.0;
-}
-
-// the offsets of a neighbour method in the reference's order (src/fast_gicp/cuda/ndt_cuda.cu:35-88); false: more than RGC_NDT_MAX_OFFSETS
-static bool ndt_offsets_of(int method, double radius, std::vector<int>& o) {
+// the offsets of a neighbour method in the reference's order (rgc_ctx.h): src/fast_gicp/cuda/ndt_cuda.cu:35-88, fast_vgicp_cuda.cu:42-95
+bool rgcapi::neighbor_offsets_of(int method, double radius, std::vector<int>& o, int cap) {
   o.clear();
   if (method == RGC_NDT_DIRECT1) { o = {0, 0, 0}; return true; }
   if (method == RGC_NDT_DIRECT7) { o = {0, 0, 0, 1, 0, 0, -1, 0, 0, 0, 1, 0, 0, -1, 0, 0, 0, 1, 0, 0, -1}; return true; }
@@ -100,10 +89,21 @@ static bool ndt_offsets_of(int method, double radius, std::vector<int>& o) {
     for (int j = -range; j <= range; j++)
       for (int k = -range; k <= range; k++)
         if (std::sqrt((double)(i * i + j * j + k * k)) <= radius + 1e-3) {
-          if ((int)o.size() / 3 >= RGC_NDT_MAX_OFFSETS) return false;
+          if ((int)o.size() / 3 >= cap) return false;
           o.push_back(i); o.push_back(j); o.push_back(k);
         }
   return true;
+}
+
+extern "C" {
+
+// ---- NDT registration (P2D / D2D) on a Gaussian voxel map: fast_gicp::NDTCuda (src/fast_gicp/cuda/ndt_cuda.cu, ndt_compute_derivatives.cu) ----
+void rgc_default_ndt_params(rgc_ndt_params* p) {
+  if (!p) return;
+  p->resolution = 1.0;                     // src/fast_gicp/cuda/ndt_cuda.cu:15
+  p->distance_mode = RGC_NDT_D2D;          // :21
+  p->neighbor_method = RGC_NDT_DIRECT7;    // :22
+  p->neighbor_radius = 0.0;
 }
 
 static void ndt_drop_terms(rgc_ctx* c) { c->ndt_corr_valid = false; c->ndt_terms = 0; }
@@ -117,7 +117,7 @@ int rgc_ndt_set_params(rgc_ctx* c, const rgc_ndt_params* p) {
   if (p->neighbor_method == RGC_NDT_DIRECT_RADIUS) {
     if (!std::isfinite(p->neighbor_radius) || p->neighbor_radius < 0.0) return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: DIRECT_RADIUS needs a finite radius >= 0");
   }
-  if (!ndt_offsets_of(p->neighbor_method, p->neighbor_radius, offs))
+  if (!neighbor_offsets_of(p->neighbor_method, p->neighbor_radius, offs))
     return fail(c, RGC_ERR_INVALID, "rgc_ndt_set_params: radius %g has more than %d offsets", p->neighbor_radius, RGC_NDT_MAX_OFFSETS);
   if (p->resolution != c->ndt_prm.resolution || p->distance_mode != c->ndt_prm.distance_mode) ndt_drop_terms(c);
   c->ndt_prm = *p;
@@ -129,6 +129,19 @@ int rgc_ndt_set_params(rgc_ctx* c, const rgc_ndt_params* p) {
 int rgc_ndt_get_params(const rgc_ctx* c, rgc_ndt_params* p) {
   if (!c || !p) return RGC_ERR_INVALID;
   *p = c->ndt_prm;
+  return RGC_OK;
+}
+
+// the offset table of a neighbour method as VGICP and NDT walk it: host code, no context (rgc_hip.h)
+int rgc_neighbor_offsets(int method, double radius, int* xyz, int cap, int* n) {
+  if (!n || cap < 0) return RGC_ERR_INVALID;  // (xyz == NULL: the size alone)
+  if (method < RGC_DIRECT27 || method > RGC_DIRECT_RADIUS) return RGC_ERR_INVALID;
+  if (method == RGC_DIRECT_RADIUS && (!std::isfinite(radius) || radius < 0.0)) return RGC_ERR_INVALID;
+  std::vector<int> o;
+  if (!neighbor_offsets_of(method, radius, o)) return RGC_ERR_INVALID;  // more than RGC_NDT_MAX_OFFSETS
+  const int total = (int)o.size() / 3;
+  if (xyz) memcpy(xyz, o.data(), sizeof(int) * 3 * (size_t)std::min(cap, total));
+  *n = total;
   return RGC_OK;
 }
 
@@ -237,7 +250,7 @@ static int ndt_run_terms(rgc_ctx* c, const double T[16], bool find, bool want_H,
   const Cloud& sc = c->ndt_cl[1];
   const int n = find ? (d2d ? sc.nvox : sc.n) : c->ndt_corr_n;
   if (find) {
-    if (c->ndt_offs_h.empty()) ndt_offsets_of(c->ndt_prm.neighbor_method, c->ndt_prm.neighbor_radius, c->ndt_offs_h);
+    if (c->ndt_offs_h.empty()) neighbor_offsets_of(c->ndt_prm.neighbor_method, c->ndt_prm.neighbor_radius, c->ndt_offs_h);
     if (c->ndt_offs_dirty) {
       if ((rc = ensure(c, c->ndt_offs, sizeof(int) * 3 * RGC_NDT_MAX_OFFSETS))) return rc;
       HIPCHK(c, hipStreamSynchronize(c->stream));  // (a launch that reads the former list may still run)

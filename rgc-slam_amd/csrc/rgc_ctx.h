@@ -169,6 +169,12 @@ struct rgc_ctx {
                               // always name the VALID one after a solve
   int corr_noff = 0, corr_n = 0;
   bool corr_valid = false;
+  // RGC_DIRECT_RADIUS (rgc_set_neighbor_search; prm.neighbor_method carries the method): the stored radius, its offset table (3 ints per offset, the
+  // reference's order: neighbor_offsets_of) and the table on the device (one packed int per offset, rgck::vgicp_radius_pack), uploaded when it changed
+  double nbr_radius = 0.0;
+  std::vector<int> vr_offs_h, vr_packed_h;
+  DevBuf vr_offs;
+  bool vr_offs_dirty = true;
   // small device scratch + pinned host mirrors
   rgck::SmallWords* d_small = nullptr;  // the map's and the scan's blocks, ncorr, the leaf filter's block, the front-end's words
   double* d_out = nullptr;    // 28 doubles
@@ -445,5 +451,11 @@ struct LmResult {
 };
 // computeTransformation from `guess` under c->prm's limits; an error of a system call ends it with that code (r is not complete then)
 int lm_solve(rgc_ctx* c, const LmSystem& sys, const float guess[16], LmResult* r);
+// The offsets of a fast_gicp::NeighborSearchMethod (0 DIRECT27, 1 DIRECT7, 2 DIRECT1, 3 DIRECT_RADIUS: include/fast_gicp/gicp/gicp_settings.hpp:8) in
+// the reference's order, 3 ints per offset -- the ONE generator of NDT's list (src/fast_gicp/cuda/ndt_cuda.cu:35-88) and VGICP's
+// (src/fast_gicp/cuda/fast_vgicp_cuda.cu:42-95), which are the same lists.  cap: the most offsets a caller takes (kMaxNeighborOffsets for a list
+// a kernel is to walk); false: the radius has more (o is incomplete then).  The radius is read under method 3 only and must be finite and >= 0.
+constexpr int kMaxNeighborOffsets = RGC_NDT_MAX_OFFSETS;  // the cap of both lists, under its one name
+bool neighbor_offsets_of(int method, double radius, std::vector<int>& o, int cap = kMaxNeighborOffsets);
 
 }  // namespace rgcapi

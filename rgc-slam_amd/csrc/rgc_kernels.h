@@ -402,6 +402,16 @@ void gicp_mp_terms(hipStream_t s, const SortedCloud& src, const double* merged, 
 void gicp_mp_export(hipStream_t s, const SortedCloud& src, const double* merged, int* count, double* sum_w, double* mean3, double* cov6);
 // the members themselves: off = the exclusive scan of the caller-order counts (src.n + 1 entries); idx / sq: original target index and key
 void gicp_mp_fill(hipStream_t s, const SortedCloud& src, PoseF T, const SortedCloud& tgt, float r2, double r, const int* off, int* idx, float* sq);
+// ---- VGICP's DIRECT_RADIUS neighbour method (rgc_vgicp_radius.hip; fast_gicp::FastVGICPCuda::setNeighborSearchMethod(method, radius),
+// src/fast_gicp/cuda/fast_vgicp_cuda.cu:42-95) ----
+int  vgicp_radius_blocks(int n);   // workgroups (rows of partials) of a linearisation of n source points
+int  vgicp_radius_group();         // lanes per source point of this build
+// one table entry: the three offsets as signed bytes, x | y << 8 | z << 16 (|offset| <= ceil(radius) <= 5 under RGC_NDT_MAX_OFFSETS)
+inline int vgicp_radius_pack(int x, int y, int z) { return (x & 0xff) | ((y & 0xff) << 8) | ((z & 0xff) << 16); }
+// linearize / linearize_general over the table offs[0 .. noff) (device memory): A.c6 != nullptr = the general route's six entries, else the unit
+// normal.  corr: noff * src.n entries as linearize leaves them; partials: vgicp_radius_blocks(src.n) rows of kAccum doubles, ncorr_partials: as many ints
+void vgicp_radius_linearize(hipStream_t s, const SortedCloud& src, const GicpCov& A, Pose T, const Grid& g, const VoxelMap& vm, const int* offs, int noff,
+                            Corr corr, int want_H, double* partials, int* ncorr_partials, double* out28, int* out_ncorr);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,

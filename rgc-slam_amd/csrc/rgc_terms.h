@@ -1,6 +1,6 @@
 // rgc_terms.h -- the device code the solvers share: the Gauss-Newton term of one Mahalanobis correspondence, R C R^T of a six-entry covariance,
 // the covariance of a sorted point, and the fixed-order sums (a wave's shuffle tree, the shuffle-tree block store, the column fold).  Included by
-// rgc_kernels.hip (VGICP, the mapping registration's fold), rgc_ndt.hip, rgc_gicp.hip, rgc_gicp_mp.hip and rgc_frontend.hip; the symmetric 3x3
+// rgc_kernels.hip (VGICP, the mapping registration's fold), rgc_vgicp_radius.hip, rgc_ndt.hip, rgc_gicp.hip, rgc_gicp_mp.hip and rgc_frontend.hip; the symmetric 3x3
 // inverse they use is rgc_cov.h's inv_sym3, the fp32 query transform rgc_nn.h's transform_f32.  Everything here is __forceinline__, as in those
 // two headers: each kernel inlines its own copy, no __global__ lives here.  The project's arithmetic holds for every caller alike -- fp64 after
 // the fp32 key, every sum in a fixed order, no contraction (compile with -ffp-contract=off) -- so one definition serves them all bit for bit.

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DIRECT1, DIRECT7, DIRECT27, Params, RgcError, Stats
+from ._lib import DIRECT1, DIRECT7, DIRECT27, DIRECT_RADIUS, Params, RgcError, Stats
 
 
 def _f32c(a):
@@ -23,7 +23,7 @@ def _f32c(a):
 
 
 class NeighborSearchMethod:  # include/fast_gicp/gicp/gicp_settings.hpp:8
-    DIRECT27, DIRECT7, DIRECT1 = DIRECT27, DIRECT7, DIRECT1
+    DIRECT27, DIRECT7, DIRECT1, DIRECT_RADIUS = DIRECT27, DIRECT7, DIRECT1, DIRECT_RADIUS
 
 
 class FastVGICP:
@@ -87,8 +87,30 @@ class FastVGICP:
     def setCorrespondenceRandomness(self, k):        # fast_gicp_impl.hpp:41-43
         self._p.k_correspondences = int(k); self._push()
 
-    def setNeighborSearchMethod(self, m):            # fast_vgicp_impl.hpp:37-39
-        self._p.neighbor_method = int(m); self._push()
+    def setNeighborSearchMethod(self, m, radius=-1.0):  # fast_vgicp_impl.hpp:37-39; FastVGICPCuda's (m, radius): fast_vgicp_cuda_impl.hpp:58-61
+        """DIRECT27 / DIRECT7 / DIRECT1 ignore the radius; DIRECT_RADIUS looks up every voxel within `radius` cells (rgc_set_neighbor_search)"""
+        self._chk(self._L.rgc_set_neighbor_search(self._h, int(m), float(radius)))
+        self._p.neighbor_method = int(m)  # (the block the other setters push carries the method; the context keeps the radius)
+
+    def getNeighborSearchMethod(self):
+        """(method, radius): the selection and the stored radius (rgc_get_neighbor_search)"""
+        m, r = C.c_int(0), C.c_double(0)
+        self._chk(self._L.rgc_get_neighbor_search(self._h, C.byref(m), C.byref(r)))
+        return int(m.value), float(r.value)
+
+    @staticmethod
+    def neighbor_offsets(method, radius=-1.0):
+        """the (n, 3) integer offset table of a neighbour method, in the order the kernels walk it (rgc_neighbor_offsets: host code, no GPU)"""
+        L = _lib.load()
+        n = C.c_int(0)
+        rc = L.rgc_neighbor_offsets(int(method), float(radius), None, 0, C.byref(n))
+        if rc != 0:
+            raise RgcError(rc, L.rgc_status_string(rc).decode() + " (rgc_neighbor_offsets)")
+        out = np.zeros((n.value, 3), np.int32)
+        rc = L.rgc_neighbor_offsets(int(method), float(radius), out.ctypes.data_as(C.POINTER(C.c_int)), n.value, C.byref(n))
+        if rc != 0:
+            raise RgcError(rc, L.rgc_status_string(rc).decode() + " (rgc_neighbor_offsets)")
+        return out
 
     # accepted and ignored, exactly like the reference for FastVGICP (SURVEY A.4/A.5)
     def setMaxCorrespondenceDistance(self, d):       # unused by FastVGICP (only kd-tree FastGICP, fast_gicp_impl.hpp:136)
