@@ -1061,6 +1061,54 @@ RGC_API int rgc_gicpmp_get_neighbors(rgc_ctx* ctx, int* offsets, int* idx, float
 RGC_API int rgc_gicpmp_align(rgc_ctx* ctx, const float guess[16], float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged,
                              int* failed);
 
+/* ---- the search index: exact k nearest neighbours and radius search of arbitrary queries: pcl::KdTreeFLANN::nearestKSearch / radiusSearch as the
+ * reference calls them (src/RGC_mapping.cpp:1097,1147,1196,1243: 5-NN in the corner and surf maps; src/RGC_mapping.cpp:1537,2157: radius search over
+ * the key poses; include/fast_gicp/gicp/impl/fast_gicp_impl.hpp:133,254; include/fast_gicp/gicp/impl/fast_gicp_st_impl.hpp:56;
+ * include/fast_gicp/gicp/impl/fast_vgicp_cuda_impl.hpp:161; include/fast_gicp/gicp/experimental/fast_gicp_mp_impl.hpp:145,148,233) ----
+ * The index is a cloud of the context's OWN: rgc_search_set_cloud copies a host cloud, or counting-sorts a device cloud into the library's buffer (the
+ * input need not stay alive after the call returns), and builds a grid over its measured box.  It is independent of the context's source and target
+ * and of every other subsystem; a solve in flight refuses its calls (RGC_ERR_INVALID).  n <= 2^27 points.
+ *   Key: the fp32 ((dx dx + dy dy) + dz dz), never FMA-contracted -- flann::L2_Simple<float>, the key of every other search of this library; sq_dist
+ * returns it.  Order: ascending (key, original index), a total order: a row is unique whatever the grid, the cell size or the launch shape, and results
+ * are bit-identical from run to run and between host and device pointers.
+ *   rgc_search_knn: k in 1..RGC_SEARCH_MAX_K.  Row i (k entries) holds the min(k, n) smallest of query i under that order; entries behind min(k, n)
+ * are idx = -1, sq_dist = +inf (PCL shrinks k to n; a fixed row width with a sentinel is this library's form of that).
+ *   rgc_search_radius: a point is a member iff key < r2, strict, r2 = (float)((double)radius * (double)radius) -- the rule rgc_gicpmp_* documents for
+ * pcl::KdTreeFLANN::radiusSearch; radius finite and > 0, r2 finite.  max_nn = 0: every member, nothing capped.  max_nn in 1..RGC_SEARCH_MAX_K: the
+ * max_nn smallest members under the order (FLANN's bounded result set under an exact search); a larger max_nn is RGC_ERR_INVALID.  Rows are CSR:
+ * offsets (nq + 1 entries), idx and sq_dist (cap entries each; sq_dist nullable).  sorted != 0: rows ascending under the order (PCL's default,
+ * sorted_results_ = true); sorted = 0: the order inside a row is unspecified (the grid's: it moves with the cell size) but the same from run to run.  *n_total is always the total;
+ * cap < *n_total: RGC_ERR_INVALID, no row and no offset written, *n_total still set (rgc_gicpmp_get_neighbors' protocol: size the second call with
+ * it).  A total beyond 2^31 - 1 is RGC_ERR_INVALID too (the offsets are 32-bit).
+ *   on_device covers the queries AND the outputs, as in rgc_kf_assemble: all host memory or all device memory of the context's GPU.
+ *   Refusals: no index: RGC_ERR_NO_INPUT; nq = 0: RGC_OK (offsets[0] = 0); nq < 0, k or max_nn out of range, a bad stride, a NULL it needs:
+ * RGC_ERR_INVALID; a non-finite coordinate in the indexed cloud or in a query: RGC_ERR_NONFINITE, detected on the device (the grid build's flag
+ * word; a query kernel searches nothing for such a query and raises a flag) -- no output is written, and for the cloud the context holds no index.
+ *   cell: > 0 is the grid's cell size as given (RGC_ERR_GRID_TOO_LARGE as elsewhere, rgc_params::max_cells); 0 selects it: the box's extent is
+ * measured in cells of 1 m (of 1/16 m when no axis spans more than 8 of those), cell = the power of two nearest cbrt(4 V / n) with V the product of
+ * the three extents (about four points per cell of a filled box), within [2^-8, 2^16] m, doubled while the grid would hold more than
+ * max(4 n, 4096) cells.  Results never depend on it.
+ *   rgc_search_get_info: the index, and what the LAST query call cost: the indexed points it looked at, the queries whose cube of cells grew beyond
+ * its first size (the 3 x 3 x 3 block about the query's cell; rgc_search_knn and a bounded radius search), the rows that took the sort's long route
+ * (an uncapped sorted radius search; rows up to rgc_search_sort_window() members are sorted in one pass). */
+#define RGC_SEARCH_MAX_K 32
+typedef struct rgc_search_info {
+  int n;                       /* points indexed (0: no index)                                    */
+  double cell;                 /* the grid's cell size in use                                     */
+  long long cells;             /* cells of the grid                                               */
+  long long candidates;        /* last query call: indexed points looked at over all queries      */
+  int grown;                   /* last query call: queries whose cube of cells had to grow        */
+  int rows_sorted_long;        /* last query call: radius rows longer than the sort window        */
+} rgc_search_info;
+RGC_API int rgc_search_set_cloud(rgc_ctx* ctx, const float* xyz, int n, int stride_bytes, int on_device, double cell);
+RGC_API int rgc_search_clear(rgc_ctx* ctx);
+RGC_API int rgc_search_get_info(rgc_ctx* ctx, rgc_search_info* info);
+/* host code, no context */
+RGC_API int rgc_search_sort_window(void);
+RGC_API int rgc_search_knn(rgc_ctx* ctx, const float* queries, int nq, int stride_bytes, int on_device, int k, int* idx, float* sq_dist);
+RGC_API int rgc_search_radius(rgc_ctx* ctx, const float* queries, int nq, int stride_bytes, int on_device, double radius, int max_nn, int sorted,
+                              int* offsets, int* idx, float* sq_dist, long long cap, long long* n_total);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

@@ -164,6 +164,13 @@ class GicpMpParams(C.Structure):
     _fields_ = [("neighbor_search_radius", C.c_double), ("max_iterations", C.c_int), ("rotation_epsilon", C.c_double), ("transformation_epsilon", C.c_double)]
 
 
+class SearchInfo(C.Structure):
+    """rgc_search_info: the search index and what its last query call cost (rgc_search_get_info)"""
+    _fields_ = [("n", C.c_int), ("cell", C.c_double), ("cells", C.c_longlong), ("candidates", C.c_longlong), ("grown", C.c_int), ("rows_sorted_long", C.c_int)]
+
+
+SEARCH_MAX_K = 32
+
 NDT_P2D, NDT_D2D = 0, 1
 NDT_DIRECT27, NDT_DIRECT7, NDT_DIRECT1, NDT_DIRECT_RADIUS = 0, 1, 2, 3
 NDT_MAX_OFFSETS = 512
@@ -193,6 +200,7 @@ SYMBOLS = [
     "rgc_gicp_set_max_correspondence_distance", "rgc_gicp_get_max_correspondence_distance", "rgc_gicp_linearize", "rgc_gicp_compute_error", "rgc_gicp_num_correspondences", "rgc_gicp_get_correspondences", "rgc_gicp_align",
     "rgc_gicpst_reset", "rgc_gicpst_linearize", "rgc_gicpst_compute_error", "rgc_gicpst_num_correspondences", "rgc_gicpst_num_searched", "rgc_gicpst_get_correspondences", "rgc_gicpst_align",
     "rgc_default_gicp_mp_params", "rgc_gicpmp_set_params", "rgc_gicpmp_get_params", "rgc_gicpmp_linearize", "rgc_gicpmp_num_correspondences", "rgc_gicpmp_num_candidates", "rgc_gicpmp_get_merged", "rgc_gicpmp_get_neighbors", "rgc_gicpmp_align",
+    "rgc_search_set_cloud", "rgc_search_clear", "rgc_search_get_info", "rgc_search_sort_window", "rgc_search_knn", "rgc_search_radius",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
@@ -424,6 +432,12 @@ def load():
     L.rgc_gicpmp_get_merged.argtypes = [vp, ip, dp, dp, dp]
     L.rgc_gicpmp_get_neighbors.argtypes = [vp, ip, ip, fp, C.c_int, C.POINTER(C.c_longlong)]
     L.rgc_gicpmp_align.argtypes = [vp, fp, fp, dp, dp, ip, ip, ip]
+    L.rgc_search_set_cloud.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double]
+    L.rgc_search_clear.argtypes = [vp]
+    L.rgc_search_get_info.argtypes = [vp, C.POINTER(SearchInfo)]
+    L.rgc_search_sort_window.argtypes = []
+    L.rgc_search_knn.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.rgc_search_radius.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.rgc_profile_enable.argtypes = [vp, C.c_int]
     L.rgc_profile_select.argtypes = [vp, C.c_uint]
     L.rgc_profile_reset.argtypes = [vp]

@@ -1306,6 +1306,10 @@ void rgc_destroy(rgc_ctx* c) {
   if (c->gicp_h_out) (void)hipHostFree(c->gicp_h_out);
   for (DevBuf* b : {&c->gicp_mp_merged, &c->gicp_mp_cand, &c->gicp_mp_partials, &c->gicp_mp_out, &c->gicp_mp_scratch}) release(*b);
   if (c->gicp_mp_h_out) (void)hipHostFree(c->gicp_mp_h_out);
+  release_cloud(c->search_cl);
+  for (DevBuf* b : {&c->search_q, &c->search_cnt, &c->search_off, &c->search_bs, &c->search_row_idx, &c->search_row_sq, &c->search_ent, &c->search_tmp, &c->search_idx,
+                    &c->search_sq, &c->search_small}) release(*b);
+  if (c->search_h) (void)hipHostFree(c->search_h);
   for (DevBuf* b : {&c->gicp_st_corr, &c->gicp_st_key1, &c->gicp_st_key2, &c->gicp_st_anchor, &c->gicp_st_M, &c->gicp_st_searched, &c->gicp_st_list, &c->gicp_st_count})
     release(*b);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);

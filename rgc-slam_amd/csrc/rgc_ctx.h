@@ -348,6 +348,14 @@ struct rgc_ctx {
   DevBuf gicp_st_corr, gicp_st_key1, gicp_st_key2, gicp_st_anchor, gicp_st_M, gicp_st_searched, gicp_st_list, gicp_st_count;
   bool gicp_st_valid = false;
   int gicp_st_n = 0, gicp_st_kept = 0, gicp_st_searched_n = 0;
+  // The search index (rgc_search_*, rgc_api_search.hip): a cloud of its own with the grid only, independent of the context's source and target; the
+  // staged host queries, the query calls' scratch (counts, offsets, block sums, fixed-width rows, packed entries and the long sort's second row, the
+  // results of a host caller), the read-out words on the device and their pinned mirror behind the eight ints of the grid's measurement
+  Cloud search_cl;
+  bool search_set = false;
+  rgc_search_info search_info{};
+  DevBuf search_q, search_cnt, search_off, search_bs, search_row_idx, search_row_sq, search_ent, search_tmp, search_idx, search_sq, search_small;
+  unsigned char* search_h = nullptr;  // pinned: int[8], then rgck::SearchStats
   rgc_stats stats{};
   // profiling
   bool prof_on = false;

@@ -412,6 +412,30 @@ inline int vgicp_radius_pack(int x, int y, int z) { return (x & 0xff) | ((y & 0x
 // normal.  corr: noff * src.n entries as linearize leaves them; partials: vgicp_radius_blocks(src.n) rows of kAccum doubles, ncorr_partials: as many ints
 void vgicp_radius_linearize(hipStream_t s, const SortedCloud& src, const GicpCov& A, Pose T, const Grid& g, const VoxelMap& vm, const int* offs, int noff,
                             Corr corr, int want_H, double* partials, int* ncorr_partials, double* out28, int* out_ncorr);
+// ---- the search index (rgc_search.hip; pcl::KdTreeFLANN::nearestKSearch / radiusSearch, e.g. src/RGC_mapping.cpp:1097,1537) ----
+// The read-out words of one query call, zeroed by the caller: candidates looked at, queries whose cube grew, members found, rows that took the sort's
+// long route; nonfinite != 0: a query had a non-finite coordinate (its row is empty); longest: the longest row of search_count
+struct SearchStats { unsigned long long candidates, grown, members, rows_long; int nonfinite, longest; };
+constexpr int kSearchMaxK = 32;           // the largest list tier of k_search_knn
+// Rows up to this many members are sorted in one pass of k_search_sort_rows: 4096 packed 64-bit entries = 32 KiB of the CU's 160 KiB of LDS, so
+// four workgroups fit on a CU beside the 2 KiB small instantiation's
+constexpr int kSearchSortWindow = 4096;
+int  search_group();         // lanes per query of this build
+int  search_sort_window();
+int  search_tier(int k);     // the list length k_search_knn runs k with: 4, 8, 16 or 32
+// queries: Q[i * qstride_f + 0..2].  Row i of out_idx / out_sq (k entries each): the min(k, members) smallest under (key, original index), -1 / +inf
+// behind them; out_cnt[i]: how many.  bounded != 0: members are the points with key < r2 (r: the radius r2 was made from), else every point
+void search_knn(hipStream_t s, const float* Q, int qstride_f, int nq, const SortedCloud& cl, int k, int bounded, float r2, double r, int* out_idx, float* out_sq,
+                int* out_cnt, SearchStats* st);
+// search_knn's rows into CSR: off = the exclusive scan of cnt; sq nullable
+void search_compact(hipStream_t s, const int* row_idx, const float* row_sq, const int* cnt, const int* off, int nq, int width, int* idx, float* sq);
+// the uncapped radius search: the members per query, then (off = the exclusive scan of the counts) the members as packed entries
+// (key bits << 32 | original index), ascending in the sorted cloud inside a row
+void search_count(hipStream_t s, const float* Q, int qstride_f, int nq, const SortedCloud& cl, float r2, double r, int* out_cnt, SearchStats* st);
+void search_fill(hipStream_t s, const float* Q, int qstride_f, int nq, const SortedCloud& cl, float r2, double r, const int* off, unsigned long long* ent);
+// every row ascending; longest: the longest row (SearchStats::longest); tmp: as many entries as ent (read only where a row exceeds the window)
+void search_sort_rows(hipStream_t s, const int* off, int nq, int longest, unsigned long long* ent, unsigned long long* tmp, SearchStats* st);
+void search_unpack(hipStream_t s, const unsigned long long* ent, long long total, int* idx, float* sq /* nullable */);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,
