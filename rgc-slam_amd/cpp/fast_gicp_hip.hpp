@@ -20,39 +20,22 @@
 
 namespace rgc {
 
-class FastGICPHip {
+// What the adaptors below share: the context (owned, or another adaptor's), the clouds and covariances handed to it, the results of the last align().
+class GICPHipBase {
 public:
   typedef std::array<float, 16> Matrix4f;    // row-major
   typedef std::array<double, 16> Matrix4d;   // row-major
   typedef std::array<double, 36> Matrix6d;
   typedef std::array<double, 6> Vector6d;
 
-  explicit FastGICPHip(int hip_device = 0, const rgc_params* params = nullptr) : own_(true) {
-    const int rc = rgc_create(hip_device, params, &ctx_);
-    if (rc != RGC_OK) throw std::runtime_error(std::string("rgc_create: ") + rgc_status_string(rc));
-    init();
-  }
-  explicit FastGICPHip(rgc_ctx* ctx) : ctx_(ctx), own_(false) {
-    if (!ctx) throw std::runtime_error("rgc::FastGICPHip: null context");
-    init();
-  }
-  virtual ~FastGICPHip() { if (own_ && ctx_) rgc_destroy(ctx_); }
-  FastGICPHip(const FastGICPHip&) = delete;
-  FastGICPHip& operator=(const FastGICPHip&) = delete;
+  virtual ~GICPHipBase() { if (own_ && ctx_) rgc_destroy(ctx_); }
+  GICPHipBase(const GICPHipBase&) = delete;
+  GICPHipBase& operator=(const GICPHipBase&) = delete;
 
   rgc_ctx* context() const { return ctx_; }
 
   void setCorrespondenceRandomness(int k) { rgc_params p = params(); p.k_correspondences = k; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
-  void setMaximumIterations(int n) { rgc_params p = params(); p.max_iterations = n; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
-  void setTransformationEpsilon(double e) { rgc_params p = params(); p.translation_eps = e; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
-  void setRotationEpsilon(double e) { rgc_params p = params(); p.rotation_eps = e; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
   void setRegularizationMethod(int method) { check(rgc_set_regularization_method(ctx_, method), "rgc_set_regularization_method"); }
-  void setMaxCorrespondenceDistance(double d) { check(rgc_gicp_set_max_correspondence_distance(ctx_, d), "rgc_gicp_set_max_correspondence_distance"); }
-  double getMaxCorrespondenceDistance() const {
-    double d = 0.0;
-    check(rgc_gicp_get_max_correspondence_distance(ctx_, &d), "rgc_gicp_get_max_correspondence_distance");
-    return d;
-  }
 
   template <typename CloudPtr> void setInputTarget(const CloudPtr& cloud) {
     check(rgc_set_target(ctx_, &cloud->points[0].x, (int)cloud->points.size(), (int)sizeof(cloud->points[0])), "rgc_set_target");
@@ -71,6 +54,58 @@ public:
   void setTargetCovariances(const std::vector<double>& cov9) { check(rgc_set_target_covariances(ctx_, cov9.data(), (int)(cov9.size() / 9)), "rgc_set_target_covariances"); }
   void clearSource() { n_source_ = 0; check(rgc_clear_source(ctx_), "rgc_clear_source"); }
   void clearTarget() { check(rgc_clear_target(ctx_), "rgc_clear_target"); }
+
+  const Matrix4f& getFinalTransformation() const { return final_; }
+  const Matrix6d& getFinalHessian() const { return hessian_; }
+  double getFitnessScore() const { return fitness_; }
+  bool hasConverged() const { return converged_ != 0; }
+  int iterations() const { return iterations_; }
+
+protected:
+  GICPHipBase(int hip_device, const rgc_params* params) : own_(true) {
+    const int rc = rgc_create(hip_device, params, &ctx_);
+    if (rc != RGC_OK) throw std::runtime_error(std::string("rgc_create: ") + rgc_status_string(rc));
+    init();
+  }
+  GICPHipBase(rgc_ctx* ctx, const char* who) : ctx_(ctx), own_(false) {
+    if (!ctx) throw std::runtime_error(std::string(who) + ": null context");
+    init();
+  }
+  void init() {
+    final_ = Matrix4f{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+    hessian_.fill(0.0);
+  }
+  rgc_params params() const {
+    rgc_params p;
+    check(rgc_get_params(ctx_, &p), "rgc_get_params");
+    return p;
+  }
+  void check(int rc, const char* what) const {
+    if (rc != RGC_OK) throw std::runtime_error(std::string(what) + ": " + rgc_last_error(ctx_));
+  }
+  rgc_ctx* ctx_ = nullptr;
+  bool own_ = false;
+  int n_source_ = 0;
+  Matrix4f final_;
+  Matrix6d hessian_;
+  double fitness_ = 0.0;
+  int iterations_ = 0, converged_ = 0, failed_ = 0;   // failed_: the solve gave up (lmFailed() / failed())
+};
+
+class FastGICPHip : public GICPHipBase {
+public:
+  explicit FastGICPHip(int hip_device = 0, const rgc_params* params = nullptr) : GICPHipBase(hip_device, params) {}
+  explicit FastGICPHip(rgc_ctx* ctx) : GICPHipBase(ctx, "rgc::FastGICPHip") {}
+
+  void setMaximumIterations(int n) { rgc_params p = params(); p.max_iterations = n; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
+  void setTransformationEpsilon(double e) { rgc_params p = params(); p.translation_eps = e; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
+  void setRotationEpsilon(double e) { rgc_params p = params(); p.rotation_eps = e; check(rgc_set_params(ctx_, &p), "rgc_set_params"); }
+  void setMaxCorrespondenceDistance(double d) { check(rgc_gicp_set_max_correspondence_distance(ctx_, d), "rgc_gicp_set_max_correspondence_distance"); }
+  double getMaxCorrespondenceDistance() const {
+    double d = 0.0;
+    check(rgc_gicp_get_max_correspondence_distance(ctx_, &d), "rgc_gicp_get_max_correspondence_distance");
+    return d;
+  }
   void swapSourceAndTarget() {
     check(rgc_swap_source_and_target(ctx_), "rgc_swap_source_and_target");
     rgc_stats st;
@@ -102,39 +137,13 @@ public:
   }
 
   virtual void align(const Matrix4f& guess) {
-    check(rgc_gicp_align(ctx_, guess.data(), final_.data(), hessian_.data(), &fitness_, &iterations_, &converged_, &lm_failed_), "rgc_gicp_align");
+    check(rgc_gicp_align(ctx_, guess.data(), final_.data(), hessian_.data(), &fitness_, &iterations_, &converged_, &failed_), "rgc_gicp_align");
   }
   void align() {
     const Matrix4f I = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
     align(I);
   }
-  const Matrix4f& getFinalTransformation() const { return final_; }
-  const Matrix6d& getFinalHessian() const { return hessian_; }
-  double getFitnessScore() const { return fitness_; }
-  bool hasConverged() const { return converged_ != 0; }
-  bool lmFailed() const { return lm_failed_ != 0; }
-  int iterations() const { return iterations_; }
-
-protected:
-  void init() {
-    final_ = Matrix4f{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
-    hessian_.fill(0.0);
-  }
-  rgc_params params() const {
-    rgc_params p;
-    check(rgc_get_params(ctx_, &p), "rgc_get_params");
-    return p;
-  }
-  void check(int rc, const char* what) const {
-    if (rc != RGC_OK) throw std::runtime_error(std::string(what) + ": " + rgc_last_error(ctx_));
-  }
-  rgc_ctx* ctx_ = nullptr;
-  bool own_ = false;
-  int n_source_ = 0;
-  Matrix4f final_;
-  Matrix6d hessian_;
-  double fitness_ = 0.0;
-  int iterations_ = 0, converged_ = 0, lm_failed_ = 0;
+  bool lmFailed() const { return failed_ != 0; }
 };
 
 // Stands in for fast_gicp::FastGICPSingleThread<PointSource, PointTarget> (rgc_slam/include/fast_gicp/gicp/fast_gicp_st.hpp:20-65,
@@ -188,7 +197,7 @@ public:
   }
   using FastGICPHip::align;
   void align(const Matrix4f& guess) override {
-    check(rgc_gicpst_align(ctx_, guess.data(), final_.data(), hessian_.data(), &fitness_, &iterations_, &converged_, &lm_failed_), "rgc_gicpst_align");
+    check(rgc_gicpst_align(ctx_, guess.data(), final_.data(), hessian_.data(), &fitness_, &iterations_, &converged_, &failed_), "rgc_gicpst_align");
   }
 };
 
@@ -200,27 +209,10 @@ public:
 //   rgc::FastGICPMultiPointsHip mp(0);                      // or FastGICPMultiPointsHip(other.context()) on the clouds of another adaptor (not owned)
 //   mp.setNeighborSearchRadius(0.5); mp.setInputTarget(map); mp.setInputSource(scan);
 //   mp.align(guess);  mp.getFinalTransformation();  mp.hasConverged();
-class FastGICPMultiPointsHip {
+class FastGICPMultiPointsHip : public GICPHipBase {
 public:
-  typedef std::array<float, 16> Matrix4f;    // row-major
-  typedef std::array<double, 16> Matrix4d;   // row-major
-  typedef std::array<double, 36> Matrix6d;
-  typedef std::array<double, 6> Vector6d;
-
-  explicit FastGICPMultiPointsHip(int hip_device = 0, const rgc_params* params = nullptr) : own_(true) {
-    const int rc = rgc_create(hip_device, params, &ctx_);
-    if (rc != RGC_OK) throw std::runtime_error(std::string("rgc_create: ") + rgc_status_string(rc));
-    init();
-  }
-  explicit FastGICPMultiPointsHip(rgc_ctx* ctx) : ctx_(ctx), own_(false) {
-    if (!ctx) throw std::runtime_error("rgc::FastGICPMultiPointsHip: null context");
-    init();
-  }
-  ~FastGICPMultiPointsHip() { if (own_ && ctx_) rgc_destroy(ctx_); }
-  FastGICPMultiPointsHip(const FastGICPMultiPointsHip&) = delete;
-  FastGICPMultiPointsHip& operator=(const FastGICPMultiPointsHip&) = delete;
-
-  rgc_ctx* context() const { return ctx_; }
+  explicit FastGICPMultiPointsHip(int hip_device = 0, const rgc_params* params = nullptr) : GICPHipBase(hip_device, params) {}
+  explicit FastGICPMultiPointsHip(rgc_ctx* ctx) : GICPHipBase(ctx, "rgc::FastGICPMultiPointsHip") {}
 
   void setNumThreads(int) {}                 // CPU threads (fast_gicp_mp_impl.hpp:47-55): nothing to set on the GPU
   void setNeighborSearchRadius(double r) { rgc_gicp_mp_params p = mp_params(); p.neighbor_search_radius = r; check(rgc_gicpmp_set_params(ctx_, &p), "rgc_gicpmp_set_params"); }
@@ -228,30 +220,6 @@ public:
   void setRotationEpsilon(double e) { rgc_gicp_mp_params p = mp_params(); p.rotation_epsilon = e; check(rgc_gicpmp_set_params(ctx_, &p), "rgc_gicpmp_set_params"); }
   void setTransformationEpsilon(double e) { rgc_gicp_mp_params p = mp_params(); p.transformation_epsilon = e; check(rgc_gicpmp_set_params(ctx_, &p), "rgc_gicpmp_set_params"); }
   void setMaximumIterations(int n) { rgc_gicp_mp_params p = mp_params(); p.max_iterations = n; check(rgc_gicpmp_set_params(ctx_, &p), "rgc_gicpmp_set_params"); }
-  void setCorrespondenceRandomness(int k) {
-    rgc_params p;
-    check(rgc_get_params(ctx_, &p), "rgc_get_params");
-    p.k_correspondences = k;
-    check(rgc_set_params(ctx_, &p), "rgc_set_params");
-  }
-  void setRegularizationMethod(int method) { check(rgc_set_regularization_method(ctx_, method), "rgc_set_regularization_method"); }
-
-  template <typename CloudPtr> void setInputTarget(const CloudPtr& cloud) {
-    check(rgc_set_target(ctx_, &cloud->points[0].x, (int)cloud->points.size(), (int)sizeof(cloud->points[0])), "rgc_set_target");
-  }
-  template <typename CloudPtr> void setInputSource(const CloudPtr& cloud) {
-    n_source_ = (int)cloud->points.size();
-    check(rgc_set_source(ctx_, &cloud->points[0].x, n_source_, (int)sizeof(cloud->points[0])), "rgc_set_source");
-  }
-  void setInputTargetDevice(const float* d_xyz, int n, int stride_bytes) { check(rgc_set_target_device(ctx_, d_xyz, n, stride_bytes), "rgc_set_target_device"); }
-  void setInputSourceDevice(const float* d_xyz, int n, int stride_bytes) {
-    n_source_ = n;
-    check(rgc_set_source_device(ctx_, d_xyz, n, stride_bytes), "rgc_set_source_device");
-  }
-  void setSourceCovariances(const std::vector<double>& cov9) { check(rgc_set_source_covariances(ctx_, cov9.data(), (int)(cov9.size() / 9)), "rgc_set_source_covariances"); }
-  void setTargetCovariances(const std::vector<double>& cov9) { check(rgc_set_target_covariances(ctx_, cov9.data(), (int)(cov9.size() / 9)), "rgc_set_target_covariances"); }
-  void clearSource() { n_source_ = 0; check(rgc_clear_source(ctx_), "rgc_clear_source"); }
-  void clearTarget() { check(rgc_clear_target(ctx_), "rgc_clear_target"); }
 
   double linearize(const Matrix4d& T, Matrix6d* H = nullptr, Vector6d* b = nullptr) {
     double cost = 0.0;
@@ -300,33 +268,14 @@ public:
     const Matrix4f I = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
     align(I);
   }
-  const Matrix4f& getFinalTransformation() const { return final_; }
-  const Matrix6d& getFinalHessian() const { return hessian_; }
-  double getFitnessScore() const { return fitness_; }
-  bool hasConverged() const { return converged_ != 0; }
   bool failed() const { return failed_ != 0; }
-  int iterations() const { return iterations_; }
 
 private:
-  void init() {
-    final_ = Matrix4f{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
-    hessian_.fill(0.0);
-  }
   rgc_gicp_mp_params mp_params() const {
     rgc_gicp_mp_params p;
     check(rgc_gicpmp_get_params(ctx_, &p), "rgc_gicpmp_get_params");
     return p;
   }
-  void check(int rc, const char* what) const {
-    if (rc != RGC_OK) throw std::runtime_error(std::string(what) + ": " + rgc_last_error(ctx_));
-  }
-  rgc_ctx* ctx_ = nullptr;
-  bool own_ = false;
-  int n_source_ = 0;
-  Matrix4f final_;
-  Matrix6d hessian_;
-  double fitness_ = 0.0;
-  int iterations_ = 0, converged_ = 0, failed_ = 0;
 };
 
 }  // namespace rgc

@@ -104,6 +104,13 @@ static void release_cloud(Cloud& cl) {
   for (DevBuf* b : shared_bufs(cl)) release(*b);
   for (DevBuf* b : {&cl.need, &cl.qlist, &cl.cell_list, &cl.seed, &cl.nbr, &cl.rank_of, &cl.pos_of, &cl.qrank, &cl.map_copy, &cl.todo, &cl.cache_small}) release(*b);
 }
+// a registration method's record (rgc_ctx.h): its device buffers and its pinned mirrors
+template <class Record>
+static void release_record(Record& r) {
+  for (DevBuf* b : r.bufs()) release(*b);
+  for (void* p : r.pinned())
+    if (p) (void)hipHostFree(p);
+}
 
 // ---- profiling regions (HIP events on the context's stream) ----
 static bool profiled(const rgc_ctx* c, int kind) { return c->prof_on && ((c->prof_mask >> kind) & 1u); }  // the profile is on and wants this kind of region
@@ -810,7 +817,7 @@ int set_cloud(rgc_ctx* c, Cloud& cl, bool is_target, const float* xyz, int n, in
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
   cl.ready = false;
   cl.n = 0;
-  c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false;
+  drop_frozen(c);
   c->deferred_known = false;
   if (is_target) c->map_bound = false;
   if (!xyz || n < 0) return fail(c, RGC_ERR_INVALID, "null cloud");
@@ -909,7 +916,7 @@ static int resolve_guards(rgc_ctx* c, int guard_t, int guard_s) {
     if (!cl[a]->ready || cl[a]->n <= 0) continue;  // (a cloud cleared since -- rgc_clear_source / _target --: its guard word is the last cloud's, there is nothing to prepare again)
     if (!gd[a]) continue;
     cl[a]->ready = false;
-    c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false;
+    drop_frozen(c);
     c->deferred_known = false;
     if (gd[a] & 1) { cl[a]->n = 0; return fail(c, RGC_ERR_NONFINITE, "%s cloud contains non-finite or absurd coordinates", a == 0 ? "target" : "source"); }
     if (trace_alloc()) fprintf(stderr, "[rgc] %s cloud left its speculative grid: prepared again\n", a == 0 ? "target" : "source");
@@ -1297,21 +1304,18 @@ void rgc_destroy(rgc_ctx* c) {
                     &c->kf_ids, &c->kf_flag, &c->kf_scan, &c->kf_bsum, &c->kf_sel, &c->kf_sel_out, &c->kf_small}) release(*b);
   if (c->kf_h_table) (void)hipHostFree(c->kf_h_table);
   for (DevBuf* b : {&c->pgo_i, &c->pgo_d, &c->pgo_M}) release(*b);
-  release_cloud(c->ndt_cl[0]);
-  release_cloud(c->ndt_cl[1]);
-  for (DevBuf* b : {&c->vr_offs, &c->ndt_offs, &c->ndt_corr, &c->ndt_partials, &c->ndt_ipartials, &c->ndt_small, &c->ndt_out}) release(*b);
-  if (c->ndt_h_out) (void)hipHostFree(c->ndt_h_out);
-  if (c->ndt_h_small) (void)hipHostFree(c->ndt_h_small);
-  for (DevBuf* b : {&c->gicp_corr, &c->gicp_key, &c->gicp_M, &c->gicp_partials, &c->gicp_out}) release(*b);
-  if (c->gicp_h_out) (void)hipHostFree(c->gicp_h_out);
-  for (DevBuf* b : {&c->gicp_mp_merged, &c->gicp_mp_cand, &c->gicp_mp_partials, &c->gicp_mp_out, &c->gicp_mp_scratch}) release(*b);
-  if (c->gicp_mp_h_out) (void)hipHostFree(c->gicp_mp_h_out);
+  release(c->vr_offs);
+  release_cloud(c->ndt.cl[0]);
+  release_cloud(c->ndt.cl[1]);
+  release_record(c->ndt);
+  release_record(c->gicp_sums);
+  release_record(c->gicp);
+  release_record(c->gicp_st);
+  release_record(c->gicp_mp);
   release_cloud(c->search_cl);
   for (DevBuf* b : {&c->search_q, &c->search_cnt, &c->search_off, &c->search_bs, &c->search_row_idx, &c->search_row_sq, &c->search_ent, &c->search_tmp, &c->search_idx,
                     &c->search_sq, &c->search_small}) release(*b);
   if (c->search_h) (void)hipHostFree(c->search_h);
-  for (DevBuf* b : {&c->gicp_st_corr, &c->gicp_st_key1, &c->gicp_st_key2, &c->gicp_st_anchor, &c->gicp_st_M, &c->gicp_st_searched, &c->gicp_st_list, &c->gicp_st_count})
-    release(*b);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1340,7 +1344,7 @@ int rgc_set_params(rgc_ctx* c, const rgc_params* p) {
   c->prm = *p;
   // The correspondences the last linearisation froze stay what rgc_compute_error uses (with their own offset count, corr_noff) unless the
   // clouds are prepared again: the reference's setters, setNeighborSearchMethod among them, leave voxel_correspondences_ alone.
-  if (redo) c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false;
+  if (redo) drop_frozen(c);
   if (redo) {  // covariances / voxel map depend on these: recompute from the resident inputs
     if (c->tgt_owner) {
       // a BORROWED target (rgc_share_target) is the owner's, prepared under the owner's settings, and its input buffer is the owner's to
@@ -1431,7 +1435,7 @@ int rgc_share_target(rgc_ctx* c, rgc_ctx* owner) {
   c->tgt_owner_gen = owner->tgt_generation;
   c->tgt_owner_uid = owner->uid;
   c->map_bound = false;
-  c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false;
+  drop_frozen(c);
   c->deferred_known = false;
   c->main_has_target_prep = false;
   c->stats.n_target = o.n; c->stats.target_cells = o.grid.ncell; c->stats.n_voxels = o.nvox;
@@ -1455,7 +1459,7 @@ int rgc_set_regularization_method(rgc_ctx* c, int method) {
   if (method < RGC_REG_NONE || method > RGC_REG_FROBENIUS) return fail(c, RGC_ERR_INVALID, "rgc_set_regularization_method: %d is not a RegularizationMethod", method);
   if (method != c->reg_method) {  // the covariances of the clouds set so far were computed under the other method (the reference computes them at align())
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false; c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
   }
   c->reg_method = method;
   return RGC_OK;
@@ -1466,7 +1470,7 @@ int rgc_set_covariance_estimation(rgc_ctx* c, int method) {
   if (method != RGC_COV_KNN && method != RGC_COV_RBF) return fail(c, RGC_ERR_INVALID, "rgc_set_covariance_estimation: %d is neither RGC_COV_KNN nor RGC_COV_RBF", method);
   if (method != c->cov_method) {  // the clouds' covariances were estimated the other way: the rule of rgc_set_regularization_method
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false; c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
   }
   c->cov_method = method;
   return RGC_OK;
@@ -1487,7 +1491,7 @@ int rgc_set_rbf_kernel(rgc_ctx* c, double kernel_width, double max_dist) {
   if (max_dist <= 0.0) max_dist = 5.0 * kernel_width;  // fast_vgicp_cuda_impl.hpp:46-51
   if (c->cov_method == RGC_COV_RBF && (kernel_width != c->rbf_width || max_dist != c->rbf_max_dist)) {
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false; c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
   }
   c->rbf_width = kernel_width;
   c->rbf_max_dist = max_dist;
@@ -1507,7 +1511,7 @@ int rgc_set_voxel_accumulation_mode(rgc_ctx* c, int mode) {
   const bool was = c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE, is = mode == RGC_VOXEL_MULTIPLICATIVE;
   if (was != is) {  // (ADDITIVE <-> ADDITIVE_WEIGHTED changes nothing: one voxel class in the vendored FastVGICP, fast_vgicp_voxel.hpp:137-141)
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false; c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
   }
   c->voxel_mode = mode;
   return RGC_OK;
@@ -2037,7 +2041,7 @@ static int set_covs(rgc_ctx* c, Cloud& cl, bool is_target, const double* cov9, i
     if (is_target) c->tgt_generation++;
     HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's array is read until here)
     HIPCHK(c, hipGetLastError());
-    c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false;
+    drop_frozen(c);
     cl.covs_user = true;
     return RGC_OK;
   }
@@ -2066,7 +2070,7 @@ static int set_covs(rgc_ctx* c, Cloud& cl, bool is_target, const double* cov9, i
   if (is_target) c->tgt_generation++;   // borrowers of this target must share again
   HIPCHK(c, hipStreamSynchronize(c->stream));   // (the host vector goes out of scope)
   HIPCHK(c, hipGetLastError());
-  c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false;
+  drop_frozen(c);
   cl.covs_user = true;
   return RGC_OK;
 }
@@ -2077,13 +2081,13 @@ int rgc_set_target_covariances(rgc_ctx* c, const double* cov9, int n) { return c
 int rgc_clear_source(rgc_ctx* c) {
   if (!c) return RGC_ERR_INVALID;
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-  c->src.ready = false; c->src.n = 0; c->src.spec_used = false; c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false; c->deferred_known = false;
+  c->src.ready = false; c->src.n = 0; c->src.spec_used = false; drop_frozen(c); c->deferred_known = false;
   return RGC_OK;
 }
 int rgc_clear_target(rgc_ctx* c) {
   if (!c) return RGC_ERR_INVALID;
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-  c->tgt.ready = false; c->tgt.n = 0; c->tgt.spec_used = false; c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false; c->deferred_known = false; c->map_bound = false;
+  c->tgt.ready = false; c->tgt.n = 0; c->tgt.spec_used = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
   return RGC_OK;
 }
 
@@ -2130,7 +2134,7 @@ int rgc_swap_source_and_target(rgc_ctx* c) {
   std::swap(c->src.stride_f, c->tgt.stride_f);
   std::swap(c->src.n, c->tgt.n);
   c->src.ready = c->tgt.ready = false;
-  c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false; c->deferred_known = false; c->map_bound = false;
+  drop_frozen(c); c->deferred_known = false; c->map_bound = false;
   if ((rc = prepare_cloud(c, c->tgt, true, /*force_bbox=*/true))) { drop_kept(); return rc; }
   if ((rc = prepare_cloud(c, c->src, false, /*force_bbox=*/true))) { drop_kept(); return rc; }
   if (kept[0].on || kept[1].on) {

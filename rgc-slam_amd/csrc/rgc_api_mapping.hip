@@ -438,7 +438,7 @@ int rgc_map_reset(rgc_ctx* c, const double origin[3]) {
   c->map_n = 0;
   c->map_dirty = true;
   c->map_ntarget = 0;
-  if (c->map_bound) { c->tgt.ready = false; c->tgt.n = 0; c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false; c->map_bound = false; }
+  if (c->map_bound) { c->tgt.ready = false; c->tgt.n = 0; drop_frozen(c); c->map_bound = false; }
   for (int a = 0; a < 3; a++) c->map_origin[a] = origin ? origin[a] : 0.0;
   c->map_rev++;
   return RGC_OK;
@@ -528,7 +528,7 @@ int rgc_map_rebase(rgc_ctx* c, const double new_origin[3]) {
   c->map_rev++;
   if (c->map_bound) {  // the committed target is in the OLD origin's coordinates: an align before the next rgc_map_commit must fail, not drift
     c->tgt.ready = false;
-    c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false;
+    drop_frozen(c);
   }
   return RGC_OK;
 }
@@ -549,7 +549,7 @@ int rgc_map_commit(rgc_ctx* c, float leaf, int* n_target) {
   // downSizeFilter2.setInputCloud(laserCloudsubmap); filter (:985-991) -- on the resident store, nothing crosses PCIe
   if (c->map_bound) {  // from here on the buffer no longer holds the cloud the bound target was set from: whatever fails below, that target goes
     c->map_bound = false;
-    c->tgt.ready = false; c->tgt.n = 0; c->corr_valid = c->gicp_valid = c->gicp_mp_valid = c->gicp_st_valid = false;
+    c->tgt.ready = false; c->tgt.n = 0; drop_frozen(c);
   }
   if ((rc = rgc_voxelgrid(c, c->map_store[c->map_cur].as<const float>(), (int)c->map_n, 16, leaf, c->map_target.as<float>(), &nt, 1))) return rc;
   // setInputTarget (:1007): grid, exact-kNN covariances, Gaussian voxel map

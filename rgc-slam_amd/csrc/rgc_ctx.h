@@ -137,6 +137,73 @@ struct Cloud {
   rgck::DeferredBuf deferred(const int* guard /* of the cloud's grid, nullable: guard_of, rgc_api.hip */) const { return {segs.p, guard}; }
 };
 
+// ---- the registration methods beside VGICP: what each keeps between its calls.  bufs(): its device buffers, once (rgc_destroy walks them);
+// pinned(): its page-locked host mirrors.  `valid` = the frozen state is that of the present clouds and settings
+struct Sums {  // where a method's term kernels fold to: per-block partials, the folded sums, their pinned mirror (32 doubles)
+  DevBuf partials, out;
+  double* h_out = nullptr;
+  std::vector<DevBuf*> bufs() { return {&partials, &out}; }
+  std::vector<void*> pinned() { return {h_out}; }
+};
+
+// NDT registration (rgc_ndt_*): two clouds of its own (0 target, 1 source) with their grids and voxel maps (Cloud::cell_voxel / vox / vox_cell,
+// records of rgck::kNdtRec doubles), the offsets of the neighbour method, the frozen term list of the last linearisation
+struct NdtRecord {
+  rgc_ndt_params prm{1.0, RGC_NDT_D2D, RGC_NDT_DIRECT7, 0.0};
+  Cloud cl[2];
+  bool set[2] = {false, false};       // a cloud has been handed over (its points are in Cloud::in_copy, 12-byte stride)
+  bool built[2] = {false, false};     // ... and its voxel map is built, at resolution built_res
+  double built_res[2] = {0.0, 0.0};
+  std::vector<int> offs_h;            // 3 ints per offset, the order of the reference's list
+  DevBuf offs, corr, ipartials, small;
+  Sums sums;
+  bool offs_dirty = true;
+  int* h_small = nullptr;             // pinned: 8 ints
+  bool valid = false;                 // corr holds the list of n elements x noff offsets made under mode at Tlin
+  int n = 0, noff = 0, mode = 0, terms = 0;
+  double Tlin[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  std::vector<DevBuf*> bufs() { return {&offs, &corr, &ipartials, &small, &sums.partials, &sums.out}; }
+  std::vector<void*> pinned() { return {sums.h_out, h_small}; }
+};
+
+// FastGICP (rgc_gicp_*) on the context's own source and target: the pair list of the last rgc_gicp_linearize (per sorted source point the
+// neighbour's position in the target's sorted array or -1, and the fp32 key) and its Mahalanobis matrices
+struct GicpRecord {
+  double dmax = (double)FLT_MAX;      // corr_dist_threshold_ (fast_gicp_impl.hpp:18: std::numeric_limits<float>::max())
+  DevBuf corr, key, M;
+  bool valid = false;
+  int n = 0, kept = 0;
+  std::vector<DevBuf*> bufs() { return {&corr, &key, &M}; }
+  std::vector<void*> pinned() { return {}; }
+};
+
+// FastGICPSingleThread (rgc_gicpst_*) on the same clouds: per sorted source point the pair, the keys to the nearest and the second nearest at
+// its anchor, the anchor and the Mahalanobis matrix of the pose it was last searched at (rgck::GicpStState), the compaction's list and
+// counter.  valid covers the anchors: it falls on rgc_gicpst_reset and at the start of rgc_gicpst_align too; the next linearisation then
+// searches every point
+struct GicpStRecord {
+  DevBuf corr, key1, key2, anchor, M, searched, list, count;
+  bool valid = false;
+  int n = 0, kept = 0, searched_n = 0;
+  std::vector<DevBuf*> bufs() { return {&corr, &key1, &key2, &anchor, &M, &searched, &list, &count}; }
+  std::vector<void*> pinned() { return {}; }
+};
+
+// FastGICPMultiPoints (rgc_gicpmp_*) on the same clouds: the merged list of the last rgc_gicpmp_linearize (rgck::kGicpMpMerged doubles per sorted
+// source point), the fp32 pose and radius it was made under (the read-out of the members walks the candidates again).  valid falls on
+// rgc_gicpmp_set_params too
+struct GicpMpRecord {
+  rgc_gicp_mp_params prm{0.5, 64, 1e-5, 1e-5};
+  DevBuf merged, cand, scratch;
+  Sums sums;
+  bool valid = false;
+  int n = 0, points = 0;
+  long long pairs = 0;
+  float T32[16] = {0};
+  std::vector<DevBuf*> bufs() { return {&merged, &cand, &scratch, &sums.partials, &sums.out}; }
+  std::vector<void*> pinned() { return {sums.h_out}; }
+};
+
 struct ProfRegion {
   hipEvent_t a, b;
   int kind;
@@ -307,47 +374,13 @@ struct rgc_ctx {
   // the 4-DoF pose graph over the store's key poses (rgc_pgo_*): buffers of its own -- the graph's index tables, every double array of a solve
   // (two evaluations: the accepted state and the candidate), the separators' dense system
   DevBuf pgo_i, pgo_d, pgo_M;
-  // NDT registration (rgc_ndt_*): two clouds of its own (0 target, 1 source) with their grids and voxel maps (Cloud::cell_voxel / vox / vox_cell,
-  // records of rgck::kNdtRec doubles), the offsets of the neighbour method, the frozen term list of the last linearisation
-  rgc_ndt_params ndt_prm{1.0, RGC_NDT_D2D, RGC_NDT_DIRECT7, 0.0};
-  Cloud ndt_cl[2];
-  bool ndt_set[2] = {false, false};       // a cloud has been handed over (its points are in Cloud::in_copy, 12-byte stride)
-  bool ndt_built[2] = {false, false};     // ... and its voxel map is built, at resolution ndt_built_res
-  double ndt_built_res[2] = {0.0, 0.0};
-  std::vector<int> ndt_offs_h;            // 3 ints per offset, the order of the reference's list
-  DevBuf ndt_offs, ndt_corr, ndt_partials, ndt_ipartials, ndt_small, ndt_out;
-  bool ndt_offs_dirty = true;
-  double* ndt_h_out = nullptr;            // pinned: 32 doubles
-  int* ndt_h_small = nullptr;             // pinned: 8 ints
-  bool ndt_corr_valid = false;            // ndt_corr holds the list of ndt_corr_n elements x ndt_corr_noff offsets made under ndt_corr_mode at ndt_Tlin
-  int ndt_corr_n = 0, ndt_corr_noff = 0, ndt_corr_mode = 0, ndt_terms = 0;
-  double ndt_Tlin[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  // FastGICP (rgc_gicp_*) on the context's own source and target: the pair list of the last rgc_gicp_linearize (per sorted source point the
-  // neighbour's position in the target's sorted array or -1, and the fp32 key), its Mahalanobis matrices, scratch of its own.  gicp_valid
-  // falls wherever corr_valid falls: a cloud set, cleared, swapped, given covariances or prepared again
-  double gicp_dmax = (double)FLT_MAX;     // corr_dist_threshold_ (fast_gicp_impl.hpp:18: std::numeric_limits<float>::max())
-  DevBuf gicp_corr, gicp_key, gicp_M, gicp_partials, gicp_out;
-  double* gicp_h_out = nullptr;           // pinned: 32 doubles
-  bool gicp_valid = false;
-  int gicp_n = 0, gicp_kept = 0;
-  // FastGICPMultiPoints (rgc_gicpmp_*) on the same clouds: the merged list of the last rgc_gicpmp_linearize (rgck::kGicpMpMerged doubles per sorted
-  // source point), the fp32 pose and radius it was made under (the read-out of the members walks the candidates again).  gicp_mp_valid falls
-  // wherever gicp_valid falls, and on rgc_gicpmp_set_params
-  rgc_gicp_mp_params gicp_mp_prm{0.5, 64, 1e-5, 1e-5};
-  DevBuf gicp_mp_merged, gicp_mp_cand, gicp_mp_partials, gicp_mp_out, gicp_mp_scratch;
-  double* gicp_mp_h_out = nullptr;        // pinned: 32 doubles
-  bool gicp_mp_valid = false;
-  int gicp_mp_n = 0, gicp_mp_points = 0;
-  long long gicp_mp_pairs = 0;
-  float gicp_mp_T32[16] = {0};
-  // FastGICPSingleThread (rgc_gicpst_*) on the same clouds: per sorted source point the pair, the keys to the nearest and the second nearest at
-  // its anchor, the anchor and the Mahalanobis matrix of the pose it was last searched at (rgck::GicpStState), the compaction's list and
-  // counter.  gicp_st_valid = the state (anchors included) is that of the present clouds: it falls wherever gicp_valid falls, on
-  // rgc_gicpst_reset and at the start of rgc_gicpst_align; the next linearisation then searches every point.  The sums' scratch is FastGICP's
-  // (gicp_partials, gicp_out, gicp_h_out)
-  DevBuf gicp_st_corr, gicp_st_key1, gicp_st_key2, gicp_st_anchor, gicp_st_M, gicp_st_searched, gicp_st_list, gicp_st_count;
-  bool gicp_st_valid = false;
-  int gicp_st_n = 0, gicp_st_kept = 0, gicp_st_searched_n = 0;
+  // The registration methods beside VGICP, each in a record of its own (rgcapi::NdtRecord and the three below it): NDT on two clouds of its own, the three GICP variants on the
+  // context's source and target.  gicp_sums is the fixed-order sums' scratch of FastGICP and FastGICPSingleThread, which never run at the same time.
+  rgcapi::NdtRecord ndt;
+  rgcapi::Sums gicp_sums;
+  rgcapi::GicpRecord gicp;
+  rgcapi::GicpStRecord gicp_st;
+  rgcapi::GicpMpRecord gicp_mp;
   // The search index (rgc_search_*, rgc_api_search.hip): a cloud of its own with the grid only, independent of the context's source and target; the
   // staged host queries, the query calls' scratch (counts, offsets, block sums, fixed-width rows, packed entries and the long sort's second row, the
   // results of a host caller), the read-out words on the device and their pinned mirror behind the eight ints of the grid's measurement
@@ -368,6 +401,10 @@ struct rgc_ctx {
 };
 
 namespace rgcapi {
+
+// What invalidates a frozen linearisation, in one place: VGICP's correspondences and the state of every method on the context's own clouds.  They
+// fall together wherever a cloud is set, cleared, swapped, shared, given covariances or prepared again (NDT has clouds of its own: ndt_drop_terms)
+inline void drop_frozen(rgc_ctx* c) { c->corr_valid = c->gicp.valid = c->gicp_st.valid = c->gicp_mp.valid = false; }
 
 #define HIPCHK(c, expr)                                                                                    \
   do {                                                                                                     \
@@ -459,6 +496,10 @@ struct LmResult {
 };
 // computeTransformation from `guess` under c->prm's limits; an error of a system call ends it with that code (r is not complete then)
 int lm_solve(rgc_ctx* c, const LmSystem& sys, const float guess[16], LmResult* r);
+// the k folded sums of a method (s.out, behind its launches on the context's stream) in s.h_out, the launches checked; read_system: those of a
+// linearisation (k >= 28) -- H and b out of them when both are wanted, and the cost (each nullable)
+int read_sums(rgc_ctx* c, const Sums& s, int k);
+int read_system(rgc_ctx* c, const Sums& s, int k, double* H, double* b, double* cost);
 // The offsets of a fast_gicp::NeighborSearchMethod (0 DIRECT27, 1 DIRECT7, 2 DIRECT1, 3 DIRECT_RADIUS: include/fast_gicp/gicp/gicp_settings.hpp:8) in
 // the reference's order, 3 ints per offset -- the ONE generator of NDT's list (src/fast_gicp/cuda/ndt_cuda.cu:35-88) and VGICP's
 // (src/fast_gicp/cuda/fast_vgicp_cuda.cu:42-95), which are the same lists.  cap: the most offsets a caller takes (kMaxNeighborOffsets for a list

@@ -19,12 +19,16 @@ import ctypes as C
 import numpy as np
 
 from ._lib import GicpMpParams, RgcError  # noqa: F401  (RgcError re-exported)
+from ._lsq import lsq_seam
 from .registration import FastVGICP
 
 _dp, _fp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
 
 
+@lsq_seam("linearize", "compute_error", "num_correspondences", "align")
 class FastGICP(FastVGICP):
+    _family = "rgc_gicp"
+
     def setMaxCorrespondenceDistance(self, d):       # fast_gicp_impl.hpp:136: a pair is kept iff its squared distance < d * d
         self._chk(self._L.rgc_gicp_set_max_correspondence_distance(self._h, float(d)))
         self._max_corr_dist = float(d)
@@ -34,26 +38,7 @@ class FastGICP(FastVGICP):
         self._chk(self._L.rgc_gicp_get_max_correspondence_distance(self._h, C.byref(d)))
         return d.value
 
-    # ---- LsqRegistration's seam (fast_gicp_impl.hpp:155-237) ----
-    def linearize(self, T, want_H=True):
-        """returns (cost, H, b) -- H and b None unless want_H"""
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-        H, b, cost = np.zeros(36), np.zeros(6), C.c_double(0.0)
-        self._chk(self._L.rgc_gicp_linearize(self._h, T.ctypes.data_as(_dp), H.ctypes.data_as(_dp) if want_H else None,
-                                             b.ctypes.data_as(_dp) if want_H else None, C.byref(cost)))
-        return (cost.value, H.reshape(6, 6), b) if want_H else (cost.value, None, None)
-
-    def compute_error(self, T) -> float:
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-        cost = C.c_double(0.0)
-        self._chk(self._L.rgc_gicp_compute_error(self._h, T.ctypes.data_as(_dp), C.byref(cost)))
-        return cost.value
-
-    @property
-    def num_correspondences(self) -> int:
-        n = C.c_int(0)
-        self._chk(self._L.rgc_gicp_num_correspondences(self._h, C.byref(n)))
-        return n.value
+    # (LsqRegistration's seam, fast_gicp_impl.hpp:155-237: linearize / compute_error / num_correspondences / align are _lsq.py's over rgc_gicp_*)
 
     def correspondences(self):
         """(idx, sq_dist) of the last linearize, in the source's order: idx int32, -1 where rejected; sq_dist float32, the key even there"""
@@ -61,24 +46,8 @@ class FastGICP(FastVGICP):
         self._chk(self._L.rgc_gicp_get_correspondences(self._h, idx.ctypes.data_as(_ip), sq.ctypes.data_as(_fp)))
         return idx, sq
 
-    def align(self, guess=None, want_output=True, want_fitness=False):
-        """pcl::Registration::align(output, guess): the transformed source cloud (n, 3) float32, or None if want_output=False"""
-        g = np.ascontiguousarray(np.eye(4) if guess is None else guess, dtype=np.float32).reshape(16)
-        fin, H = np.empty(16, np.float32), np.empty(36)
-        fit = C.c_double(0.0)
-        it, cv, lf = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._chk(self._L.rgc_gicp_align(self._h, g.ctypes.data_as(_fp), fin.ctypes.data_as(_fp), H.ctypes.data_as(_dp),
-                                         C.byref(fit) if want_fitness else None, C.byref(it), C.byref(cv), C.byref(lf)))
-        self._final, self._H = fin.reshape(4, 4), H.reshape(6, 6)
-        self._iterations, self._converged, self._lm_failed = it.value, bool(cv.value), bool(lf.value)
-        self._fitness = fit.value if want_fitness else None
-        if not want_output:
-            return None
-        out = np.empty((self._n_src, 3), np.float32)
-        self._chk(self._L.rgc_get_aligned(self._h, fin.ctypes.data_as(_fp), out.ctypes.data_as(_fp), 12))
-        return out
 
-
+@lsq_seam("linearize", "compute_error", "num_correspondences", "align")
 class FastGICPSingleThread(FastGICP):
     """fast_gicp::FastGICPSingleThread (include/fast_gicp/gicp/fast_gicp_st.hpp:20-65, impl/fast_gicp_st_impl.hpp:19-125) behind rgc_gicpst_*: FastGICP
     whose source points keep an anchor and are searched again only when the triangle inequality cannot prove their nearest neighbour unchanged; a point
@@ -89,29 +58,10 @@ class FastGICPSingleThread(FastGICP):
         st = FastGICPSingleThread(device=0)
         st.setInputTarget(map_cloud); st.setInputSource(scan)
         st.align(guess, want_output=False); T = st.getFinalTransformation(); searched_last = st.num_searched()"""
+    _family = "rgc_gicpst"
 
     def reset(self):                                  # anchors_.clear() (fast_gicp_st_impl.hpp:20): the next linearize searches every point
         self._chk(self._L.rgc_gicpst_reset(self._h))
-
-    def linearize(self, T, want_H=True):
-        """returns (cost, H, b) -- H and b None unless want_H"""
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-        H, b, cost = np.zeros(36), np.zeros(6), C.c_double(0.0)
-        self._chk(self._L.rgc_gicpst_linearize(self._h, T.ctypes.data_as(_dp), H.ctypes.data_as(_dp) if want_H else None,
-                                               b.ctypes.data_as(_dp) if want_H else None, C.byref(cost)))
-        return (cost.value, H.reshape(6, 6), b) if want_H else (cost.value, None, None)
-
-    def compute_error(self, T) -> float:
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-        cost = C.c_double(0.0)
-        self._chk(self._L.rgc_gicpst_compute_error(self._h, T.ctypes.data_as(_dp), C.byref(cost)))
-        return cost.value
-
-    @property
-    def num_correspondences(self) -> int:
-        n = C.c_int(0)
-        self._chk(self._L.rgc_gicpst_num_correspondences(self._h, C.byref(n)))
-        return n.value
 
     def num_searched(self) -> int:
         """source points the last linearize searched (all of them on the first one after a reset)"""
@@ -127,24 +77,8 @@ class FastGICPSingleThread(FastGICP):
         self._chk(self._L.rgc_gicpst_get_correspondences(self._h, idx.ctypes.data_as(_ip), sq.ctypes.data_as(_fp), sq2.ctypes.data_as(_fp), was.ctypes.data_as(_ip)))
         return idx, sq, sq2, was.astype(bool)
 
-    def align(self, guess=None, want_output=True, want_fitness=False):
-        """pcl::Registration::align(output, guess): the transformed source cloud (n, 3) float32, or None if want_output=False"""
-        g = np.ascontiguousarray(np.eye(4) if guess is None else guess, dtype=np.float32).reshape(16)
-        fin, H = np.empty(16, np.float32), np.empty(36)
-        fit = C.c_double(0.0)
-        it, cv, lf = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._chk(self._L.rgc_gicpst_align(self._h, g.ctypes.data_as(_fp), fin.ctypes.data_as(_fp), H.ctypes.data_as(_dp),
-                                           C.byref(fit) if want_fitness else None, C.byref(it), C.byref(cv), C.byref(lf)))
-        self._final, self._H = fin.reshape(4, 4), H.reshape(6, 6)
-        self._iterations, self._converged, self._lm_failed = it.value, bool(cv.value), bool(lf.value)
-        self._fitness = fit.value if want_fitness else None
-        if not want_output:
-            return None
-        out = np.empty((self._n_src, 3), np.float32)
-        self._chk(self._L.rgc_get_aligned(self._h, fin.ctypes.data_as(_fp), out.ctypes.data_as(_fp), 12))
-        return out
 
-
+@lsq_seam("linearize", "align")
 class FastGICPMultiPoints(FastVGICP):
     """fast_gicp::FastGICPMultiPoints (include/fast_gicp/gicp/experimental/fast_gicp_mp.hpp:40-53, fast_gicp_mp_impl.hpp:92-221) behind rgc_gicpmp_*: every
     source point against the distance-weighted merge of every target Gaussian within the search radius, plain Gauss-Newton.  On the clouds of a
@@ -154,6 +88,7 @@ class FastGICPMultiPoints(FastVGICP):
         mp = FastGICPMultiPoints(device=0)
         mp.setNeighborSearchRadius(0.5); mp.setInputTarget(map_cloud); mp.setInputSource(scan)
         mp.align(guess, want_output=False); T = mp.getFinalTransformation(); ok = mp.hasConverged()"""
+    _family = "rgc_gicpmp"
 
     def __init__(self, device: int = 0):
         super().__init__(device)
@@ -189,14 +124,6 @@ class FastGICPMultiPoints(FastVGICP):
 
     def setNumThreads(self, n):                       # fast_gicp_mp_impl.hpp:47-55: CPU threads; nothing to set on the GPU
         pass
-
-    def linearize(self, T, want_H=True):
-        """returns (cost, H, b) -- H and b None unless want_H"""
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-        H, b, cost = np.zeros(36), np.zeros(6), C.c_double(0.0)
-        self._chk(self._L.rgc_gicpmp_linearize(self._h, T.ctypes.data_as(_dp), H.ctypes.data_as(_dp) if want_H else None,
-                                               b.ctypes.data_as(_dp) if want_H else None, C.byref(cost)))
-        return (cost.value, H.reshape(6, 6), b) if want_H else (cost.value, None, None)
 
     def compute_error(self, T):
         raise NotImplementedError("FastGICPMultiPoints has no frozen cost (the reference class has no compute_error)")
@@ -237,20 +164,3 @@ class FastGICPMultiPoints(FastVGICP):
         nt = C.c_longlong(0)
         self._chk(self._L.rgc_gicpmp_get_neighbors(self._h, off.ctypes.data_as(_ip), idx.ctypes.data_as(_ip), sq.ctypes.data_as(_fp), total, C.byref(nt)))
         return off, idx[:nt.value], sq[:nt.value]
-
-    def align(self, guess=None, want_output=True, want_fitness=False):
-        """pcl::Registration::align(output, guess): the transformed source cloud (n, 3) float32, or None if want_output=False"""
-        g = np.ascontiguousarray(np.eye(4) if guess is None else guess, dtype=np.float32).reshape(16)
-        fin, H = np.empty(16, np.float32), np.empty(36)
-        fit = C.c_double(0.0)
-        it, cv, lf = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._chk(self._L.rgc_gicpmp_align(self._h, g.ctypes.data_as(_fp), fin.ctypes.data_as(_fp), H.ctypes.data_as(_dp),
-                                           C.byref(fit) if want_fitness else None, C.byref(it), C.byref(cv), C.byref(lf)))
-        self._final, self._H = fin.reshape(4, 4), H.reshape(6, 6)
-        self._iterations, self._converged, self._lm_failed = it.value, bool(cv.value), bool(lf.value)
-        self._fitness = fit.value if want_fitness else None
-        if not want_output:
-            return None
-        out = np.empty((self._n_src, 3), np.float32)
-        self._chk(self._L.rgc_get_aligned(self._h, fin.ctypes.data_as(_fp), out.ctypes.data_as(_fp), 12))
-        return out

@@ -15,11 +15,15 @@ import numpy as np
 
 from . import _lib
 from ._lib import NDT_P2D, NDT_D2D, NDT_DIRECT27, NDT_DIRECT7, NDT_DIRECT1, NDT_DIRECT_RADIUS, RgcError  # noqa: F401  (re-exported)
+from ._lsq import lsq_seam
 
 _dp, _fp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
 
 
+@lsq_seam("linearize", "compute_error")
 class NDTRegistration:
+    _family = "rgc_ndt"
+
     def __init__(self, device: int = 0, owner=None, params: "_lib.Params | None" = None):
         self._L = _lib.load()
         self._own = owner is None
@@ -93,21 +97,7 @@ class NDTRegistration:
     def clearTarget(self): self._chk(self._L.rgc_ndt_clear_target(self._h))
     def swapSourceAndTarget(self): self._chk(self._L.rgc_ndt_swap_source_and_target(self._h))
 
-    # ---- LsqRegistration's seam (ndt_cuda_impl.hpp:81-90) ----
-    def linearize(self, T, want_H=True):
-        """returns (cost, H, b) -- H and b None unless want_H"""
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-        H, b, cost = np.zeros(36), np.zeros(6), C.c_double(0.0)
-        self._chk(self._L.rgc_ndt_linearize(self._h, T.ctypes.data_as(_dp), H.ctypes.data_as(_dp) if want_H else None,
-                                            b.ctypes.data_as(_dp) if want_H else None, C.byref(cost)))
-        return (cost.value, H.reshape(6, 6), b) if want_H else (cost.value, None, None)
-
-    def compute_error(self, T) -> float:
-        T = np.ascontiguousarray(T, dtype=np.float64).reshape(16)
-        cost = C.c_double(0.0)
-        self._chk(self._L.rgc_ndt_compute_error(self._h, T.ctypes.data_as(_dp), C.byref(cost)))
-        return cost.value
-
+    # ---- LsqRegistration's seam (ndt_cuda_impl.hpp:81-90): linearize and compute_error are _lsq.py's over rgc_ndt_* ----
     def num_correspondences(self) -> int:
         n = C.c_int(0)
         self._chk(self._L.rgc_ndt_num_correspondences(self._h, C.byref(n)))

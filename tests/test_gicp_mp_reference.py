@@ -178,6 +178,10 @@ def test_the_mirrors_carry_the_method_names():
     assert gicp.FastGICPMultiPoints.setRotationEpsilon is not registration.FastVGICP.setRotationEpsilon
     hpp = open(os.path.join(PKG, "cpp", "fast_gicp_hip.hpp")).read()
     body = hpp[hpp.index("class FastGICPMultiPointsHip"):]
+    base = re.match(r"class FastGICPMultiPointsHip\s*:\s*public\s+(\w+)", body)   # (its public base's members are its own: what it shares with FastGICPHip is declared once)
+    if base:
+        inherited = hpp[hpp.index("class %s {" % base.group(1)):]
+        body += inherited[:inherited.index("\nprotected:")]
     for m in CPP_METHODS:
         assert re.search(r"\b%s\s*\(" % m, body), m
 
