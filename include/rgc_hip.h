@@ -1109,6 +1109,58 @@ RGC_API int rgc_search_knn(rgc_ctx* ctx, const float* queries, int nq, int strid
 RGC_API int rgc_search_radius(rgc_ctx* ctx, const float* queries, int nq, int stride_bytes, int on_device, double radius, int max_nn, int sorted,
                               int* offsets, int* idx, float* sq_dist, long long cap, long long* n_total);
 
+/* ---- the outlier filters: pcl::StatisticalOutlierRemoval (SOR) and pcl::RadiusOutlierRemoval (ROR) of a cloud against itself, the two filters a
+ * PCL-based LiDAR pipeline runs before a cloud goes into a map.  (The reference's three nodes do not call them; they complete the PCL filter family
+ * beside rgc_voxelgrid and rgc_uniform_sampling.) ----
+ *   Argument rules, on_device and the record format are rgc_uniform_sampling's: x, y, z as floats at the head of each record of stride_bytes; on_device
+ * covers the cloud AND every output (all host memory or all device memory of the context's GPU); out_xyzc receives 16-byte records x, y, z, c that go
+ * out unchanged (c = the float behind z, 0 for a 12-byte stride); out_index the kept points' input indices; both need room for n entries and either
+ * may be NULL.  The output is in ASCENDING INPUT INDEX: PCL keeps the input's order.  *n_out = points kept.
+ *   The filters build a grid of their own over the cloud (the search index's machinery and its automatic cell rule): a caller's search index, source
+ * and target are untouched.  A solve in flight refuses the calls (RGC_ERR_INVALID), as it refuses the search index.  rgc_outlier_set_cell fixes the
+ * grid's cell size for tests and tuning (0 = automatic; finite and >= 0); NO OUTPUT BIT DEPENDS ON IT, mean / stddev / threshold included.
+ *   Key: the fp32 ((dx dx + dy dy) + dz dz), never FMA-contracted, as everywhere in this library.
+ *   rgc_outlier_statistical -- restated from PCL's filters/impl/statistical_outlier_removal.hpp FROM MEMORY [3P-memory] (PCL is not available to this
+ * project):
+ *   Row: for point i the mean_k + 1 smallest keys over the whole cloud, the point itself included.  Entry 0 is dropped: it is the point itself or a
+ * duplicate of it, either way the key 0 PCL drops as "k = 0 is the query point".
+ *   Mean distance: d_i = (float)(sum over r = 1 .. mean_k of (double)sqrtf(key_r) / mean_k), the sum in fp64 in ascending rank (tied keys have equal
+ * roots: the sum is unique), sqrtf the correctly rounded fp32 root.  out_mean_dist (nullable, n floats) receives d.
+ *   Statistics: sum = sum of d_i, sq_sum = sum of (double)d_i (double)d_i (exact in fp64), both summed IN INPUT-INDEX ORDER in a fixed order: bit-identical
+ * from run to run and independent of the grid.  mean = sum / n, variance = (sq_sum - sum sum / n) / (n - 1) clamped at 0, stddev = sqrt(variance),
+ * threshold = mean + std_mul stddev, computed on the device.
+ *   Decision: point i is kept iff (double)d_i <= threshold; with negative != 0 iff (double)d_i > threshold.
+ *   Deviations from PCL: PCL sums sequentially and squares in fp32 before widening -- here fp64 after the key, as everywhere in this library; PCL takes
+ * the root of a negative rounding residue (NaN: every point removed) -- here the variance is clamped; PCL reads past the row when n <= mean_k -- here
+ * that is refused.  A hazard PCL shares and this library does not fix: when every d_i is equal and n is no power of two, mean may round one ulp under
+ * d, and every point then counts as an outlier.
+ *   Refusals: mean_k outside 1..RGC_OUTLIER_MAX_MEAN_K, n < 0, 0 < n < 2, n <= mean_k, a non-finite std_mul, a bad stride, a NULL cloud or n_out:
+ * RGC_ERR_INVALID; n = 0: RGC_OK with *n_out = 0; a non-finite coordinate: RGC_ERR_NONFINITE, detected on the device, nothing written;
+ * RGC_ERR_GRID_TOO_LARGE as elsewhere.
+ *   rgc_outlier_radius [3P-memory: filters/impl/radius_outlier_removal.hpp]:
+ *   Count: count_i = the cloud's points with key < r2, strict, r2 = (float)((double)radius * (double)radius) -- rgc_search_radius' membership rule; the
+ * point itself is a member.  Point i is kept iff count_i - 1 >= min_neighbors; negative inverts this.  out_count (nullable, n ints) requested: the exact
+ * count_i of every point; not requested: a point's walk may stop once its count exceeds min_neighbors (the same set is kept).
+ *   Ranges: radius finite and > 0, r2 finite, min_neighbors >= 0 (RGC_ERR_INVALID); the other refusals as above, and n >= 1 suffices.
+ *   Deviation from PCL: its dense-cloud shortcut (nearestKSearch(min_pts + 1) and <= against r^2) counts a neighbour exactly on the radius as inside,
+ * its radiusSearch route does not; this library uses the strict rule on every route.
+ *   rgc_outlier_get_info: the LAST filter call. */
+#define RGC_OUTLIER_MAX_MEAN_K 63
+typedef struct rgc_outlier_info {
+  int n, n_out;                   /* points in, points kept                                       */
+  double mean, stddev, threshold; /* SOR only (0 for ROR): of the mean distances, as the device computed them */
+  double cell;                    /* the grid the call used: its cell size                        */
+  long long cells;                /* ... and its cells                                            */
+  long long candidates;           /* indexed points looked at over all points                     */
+  int grown;                      /* SOR: points whose cube of cells had to grow                  */
+} rgc_outlier_info;
+RGC_API int rgc_outlier_statistical(rgc_ctx* ctx, const float* xyzc, int n, int stride_bytes, int on_device, int mean_k, double std_mul, int negative,
+                                    float* out_xyzc /* nullable */, int* out_index /* nullable */, float* out_mean_dist /* nullable, n */, int* n_out);
+RGC_API int rgc_outlier_radius(rgc_ctx* ctx, const float* xyzc, int n, int stride_bytes, int on_device, double radius, int min_neighbors, int negative,
+                               float* out_xyzc /* nullable */, int* out_index /* nullable */, int* out_count /* nullable, n */, int* n_out);
+RGC_API int rgc_outlier_get_info(rgc_ctx* ctx, rgc_outlier_info* info);
+RGC_API int rgc_outlier_set_cell(rgc_ctx* ctx, double cell);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

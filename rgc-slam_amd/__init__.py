@@ -2,7 +2,7 @@
 
 Holds only what the hot path needs: ``csrc/`` (HIP kernels + C-ABI ``librgc_hip.so``), the
 host-side mirror of the reference's registration interface (``registration.FastVGICP``), the
-ctypes binding (``_lib``), the search index (``search.KdTree``: exact k-NN and radius search of arbitrary queries) and the synthetic data
-generator (``synth``; data only).
+ctypes binding (``_lib``), the search index (``search.KdTree``: exact k-NN and radius search of arbitrary queries), the outlier filters
+(``filters.StatisticalOutlierRemoval`` / ``filters.RadiusOutlierRemoval``) and the synthetic data generator (``synth``; data only).
 """
-__all__ = ["synth", "search"]
+__all__ = ["synth", "search", "filters"]

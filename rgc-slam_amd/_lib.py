@@ -171,6 +171,15 @@ class SearchInfo(C.Structure):
 
 SEARCH_MAX_K = 32
 
+
+class OutlierInfo(C.Structure):
+    """rgc_outlier_info: the last outlier filter call (rgc_outlier_get_info)"""
+    _fields_ = [("n", C.c_int), ("n_out", C.c_int), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double), ("cell", C.c_double),
+                ("cells", C.c_longlong), ("candidates", C.c_longlong), ("grown", C.c_int)]
+
+
+OUTLIER_MAX_MEAN_K = 63
+
 NDT_P2D, NDT_D2D = 0, 1
 NDT_DIRECT27, NDT_DIRECT7, NDT_DIRECT1, NDT_DIRECT_RADIUS = 0, 1, 2, 3
 NDT_MAX_OFFSETS = 512
@@ -201,6 +210,7 @@ SYMBOLS = [
     "rgc_gicpst_reset", "rgc_gicpst_linearize", "rgc_gicpst_compute_error", "rgc_gicpst_num_correspondences", "rgc_gicpst_num_searched", "rgc_gicpst_get_correspondences", "rgc_gicpst_align",
     "rgc_default_gicp_mp_params", "rgc_gicpmp_set_params", "rgc_gicpmp_get_params", "rgc_gicpmp_linearize", "rgc_gicpmp_num_correspondences", "rgc_gicpmp_num_candidates", "rgc_gicpmp_get_merged", "rgc_gicpmp_get_neighbors", "rgc_gicpmp_align",
     "rgc_search_set_cloud", "rgc_search_clear", "rgc_search_get_info", "rgc_search_sort_window", "rgc_search_knn", "rgc_search_radius",
+    "rgc_outlier_statistical", "rgc_outlier_radius", "rgc_outlier_get_info", "rgc_outlier_set_cell",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
@@ -438,6 +448,10 @@ def load():
     L.rgc_search_sort_window.argtypes = []
     L.rgc_search_knn.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     L.rgc_search_radius.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.rgc_outlier_statistical.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, ip]
+    L.rgc_outlier_radius.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, ip]
+    L.rgc_outlier_get_info.argtypes = [vp, C.POINTER(OutlierInfo)]
+    L.rgc_outlier_set_cell.argtypes = [vp, C.c_double]
     L.rgc_profile_enable.argtypes = [vp, C.c_int]
     L.rgc_profile_select.argtypes = [vp, C.c_uint]
     L.rgc_profile_reset.argtypes = [vp]

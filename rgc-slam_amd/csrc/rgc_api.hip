@@ -1316,6 +1316,9 @@ void rgc_destroy(rgc_ctx* c) {
   for (DevBuf* b : {&c->search_q, &c->search_cnt, &c->search_off, &c->search_bs, &c->search_row_idx, &c->search_row_sq, &c->search_ent, &c->search_tmp, &c->search_idx,
                     &c->search_sq, &c->search_small}) release(*b);
   if (c->search_h) (void)hipHostFree(c->search_h);
+  release_cloud(c->filter_cl);
+  for (DevBuf* b : {&c->filter_in, &c->filter_val, &c->filter_flag, &c->filter_off, &c->filter_bs, &c->filter_partials, &c->filter_out, &c->filter_idx, &c->filter_small}) release(*b);
+  if (c->filter_h) (void)hipHostFree(c->filter_h);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -32,7 +32,7 @@ void search_drop(rgc_ctx* c) {
 }
 
 // the cloud's box in cells of `res` (rgck::bbox: the grid build's measurement and its flag word): hsm[0..2] lowest, hsm[3..5] highest cell
-int search_measure(rgc_ctx* c, const Cloud& cl, double res, int* dsm, int* hsm) {
+int search_measure(rgc_ctx* c, const char* who, const Cloud& cl, double res, int* dsm, int* hsm) {
   const int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
   memcpy(hsm, init, sizeof(init));
   HIPCHK(c, hipMemcpyAsync(dsm, hsm, 7 * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -40,7 +40,7 @@ int search_measure(rgc_ctx* c, const Cloud& cl, double res, int* dsm, int* hsm) 
   HIPCHK(c, hipMemcpyAsync(hsm, dsm, 7 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipGetLastError());
-  if (hsm[6]) return fail(c, RGC_ERR_NONFINITE, "rgc_search_set_cloud: the cloud contains non-finite or absurd coordinates");
+  if (hsm[6]) return fail(c, RGC_ERR_NONFINITE, "%s: the cloud contains non-finite or absurd coordinates", who);
   return RGC_OK;
 }
 
@@ -107,6 +107,33 @@ int copy_out(rgc_ctx* c, void* dst, const void* src, size_t bytes, int on_device
 
 }  // namespace
 
+// The measured grid of a cloud that is searched by the rows of its cells (the search index, the outlier filters): the flag word is read before
+// anything is indexed; *cell > 0 is the cell size as given, 0 selects it by the rule include/rgc_hip.h states (and *cell returns it)
+int rgcapi::build_search_grid(rgc_ctx* c, Cloud& cl, double* cell_io, int* dsm, int* hsm, const char* who, const char* name, const char* grid_name) {
+  int rc;
+  double cell = *cell_io;
+  const int n = cl.n;
+  if ((rc = search_measure(c, who, cl, 1.0, dsm, hsm))) return rc;
+  double far = 0.0, cells_est = 1.0;
+  for (int a = 0; a < 3; a++) far = std::max(far, std::max(std::fabs((double)hsm[a]), std::fabs((double)hsm[3 + a])) + 2.0);
+  if (cell == 0.0) {
+    bool small = true;
+    for (int a = 0; a < 3; a++) small = small && hsm[3 + a] - hsm[a] + 1 <= 8;
+    double unit = 1.0;
+    if (small) {
+      unit = 1.0 / 16.0;
+      if ((rc = search_measure(c, who, cl, unit, dsm, hsm))) return rc;
+    }
+    cell = auto_cell(hsm, unit, n, c->prm.max_cells);
+  } else {
+    // a cell coordinate must fit an int, and the grid the context's max_cells (build_measured_grid counts the cells exactly)
+    for (int a = 0; a < 3; a++) cells_est *= std::max(1.0, ((double)hsm[3 + a] - (double)hsm[a] - 1.0) / cell);
+    if (far / cell >= 1073741824.0 || cells_est > (double)c->prm.max_cells) return fail(c, RGC_ERR_GRID_TOO_LARGE, "%s exceeds max_cells", grid_name);
+  }
+  *cell_io = cell;
+  return build_measured_grid(c, cl, cell, dsm, hsm, false, name, grid_name);
+}
+
 extern "C" {
 
 int rgc_search_sort_window(void) { return rgck::search_sort_window(); }
@@ -136,25 +163,10 @@ int rgc_search_set_cloud(rgc_ctx* c, const float* xyz, int n, int stride_bytes, 
   cl.n = n;
   int* dsm = c->search_small.as<int>();
   int* hsm = reinterpret_cast<int*>(c->search_h);
-  auto give_up = [&](int code) { search_drop(c); return code; };
-  if ((rc = search_measure(c, cl, 1.0, dsm, hsm))) return give_up(rc);  // (the flag word is read before anything is indexed)
-  double far = 0.0, cells_est = 1.0;
-  for (int a = 0; a < 3; a++) far = std::max(far, std::max(std::fabs((double)hsm[a]), std::fabs((double)hsm[3 + a])) + 2.0);
-  if (cell == 0.0) {
-    bool small = true;
-    for (int a = 0; a < 3; a++) small = small && hsm[3 + a] - hsm[a] + 1 <= 8;
-    double unit = 1.0;
-    if (small) {
-      unit = 1.0 / 16.0;
-      if ((rc = search_measure(c, cl, unit, dsm, hsm))) return give_up(rc);
-    }
-    cell = auto_cell(hsm, unit, n, c->prm.max_cells);
-  } else {
-    // a cell coordinate must fit an int, and the grid the context's max_cells (build_measured_grid counts the cells exactly)
-    for (int a = 0; a < 3; a++) cells_est *= std::max(1.0, ((double)hsm[3 + a] - (double)hsm[a] - 1.0) / cell);
-    if (far / cell >= 1073741824.0 || cells_est > (double)c->prm.max_cells) return give_up(fail(c, RGC_ERR_GRID_TOO_LARGE, "search grid exceeds max_cells"));
+  if ((rc = build_search_grid(c, cl, &cell, dsm, hsm, "rgc_search_set_cloud", "search cloud", "search grid"))) {
+    search_drop(c);
+    return rc;
   }
-  if ((rc = build_measured_grid(c, cl, cell, dsm, hsm, false, "search cloud", "search grid"))) return give_up(rc);
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's buffer has been read: it need not outlive the call
   HIPCHK(c, hipGetLastError());
   cl.in = nullptr;

@@ -389,6 +389,14 @@ struct rgc_ctx {
   rgc_search_info search_info{};
   DevBuf search_q, search_cnt, search_off, search_bs, search_row_idx, search_row_sq, search_ent, search_tmp, search_idx, search_sq, search_small;
   unsigned char* search_h = nullptr;  // pinned: int[8], then rgck::SearchStats
+  // The outlier filters (rgc_outlier_*, rgc_api_filters.hip): a cloud of their own with the grid only (the caller's search index, source and target are
+  // untouched); a host caller's staged records, the mean distances / counts, the flags and their scan, the fixed-order sums' rows, a host caller's
+  // results, the grid's measurement and the read-out words on the device with their pinned mirror (int[8], the number kept, rgck::OutlierStats)
+  Cloud filter_cl;
+  DevBuf filter_in, filter_val, filter_flag, filter_off, filter_bs, filter_partials, filter_out, filter_idx, filter_small;
+  unsigned char* filter_h = nullptr;
+  rgc_outlier_info outlier_info{};
+  double outlier_cell = 0.0;          // rgc_outlier_set_cell: 0 = the search index's automatic rule
   rgc_stats stats{};
   // profiling
   bool prof_on = false;
@@ -460,6 +468,12 @@ int stage_in(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device,
 int voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt,
                   int mode = rgck::kVgModeCentroid, int* out_index = nullptr);  // mode = rgck::kVgModePick: UniformSampling, out_index (nullable) as out_xyzi
 void host_eig3_sym(const double S[6], double ev[3], double V[9]);  // Jacobi; eigenvalues ASCENDING, columns of V
+
+// ---- rgc_api_search.hip ----
+// The measured grid of a cloud that is searched by the rows of its cells (the search index, the outlier filters).  *cell > 0: the cell size as given
+// (RGC_ERR_GRID_TOO_LARGE beyond max_cells); 0: chosen by the rule include/rgc_hip.h states for rgc_search_set_cloud, and returned.  dsm / hsm: eight
+// scratch ints on the device / the host; who: the entry point, name / grid_name: the cloud, in the error messages.  RGC_ERR_NONFINITE before anything is indexed
+int build_search_grid(rgc_ctx* c, Cloud& cl, double* cell, int* dsm, int* hsm, const char* who, const char* name, const char* grid_name);
 
 // ---- rgc_api_lsq.hip: the LM driver of every registration method ----
 // A registration problem as the driver sees it.  Either linearize + error (the driver makes the first try of an outer iteration itself, on

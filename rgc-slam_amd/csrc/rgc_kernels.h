@@ -436,6 +436,27 @@ void search_fill(hipStream_t s, const float* Q, int qstride_f, int nq, const Sor
 // every row ascending; longest: the longest row (SearchStats::longest); tmp: as many entries as ent (read only where a row exceeds the window)
 void search_sort_rows(hipStream_t s, const int* off, int nq, int longest, unsigned long long* ent, unsigned long long* tmp, SearchStats* st);
 void search_unpack(hipStream_t s, const unsigned long long* ent, long long total, int* idx, float* sq /* nullable */);
+// ---- the outlier filters (rgc_outlier_*, rgc_filters.hip): a cloud against itself on a grid of its own; every output at the ORIGINAL index ----
+// What a call reads back: SOR's statistics as k_sor_fold posts them, and the read-out words -- indexed points looked at (word 0), points whose cube of cells
+// grew (word 1) -- as kOutlierSlots partial sums a cache line apart: a workgroup adds its sums into slot (block & (kOutlierSlots - 1)), the host adds the
+// slots.  (One word for every wave of a launch to add into serialises the launch: at 1 M points the kernels' time was the atomics', whatever the walk did.)
+constexpr int kOutlierSlots = 32;
+struct OutlierStats { double mean, stddev, threshold, pad; unsigned long long words[kOutlierSlots][8]; };
+constexpr int kOutlierMaxMeanK = 63;  // mean_k + 1 entries: the largest list tier of k_sor_meandist
+int  outlier_group();          // lanes per point of this build
+int  outlier_tier(int mean_k); // the list length k_sor_meandist runs mean_k with: 4, 8, 16, 32 or 64
+int  outlier_stat_rows(int n); // rows of two doubles sor_stats needs in `partials`
+// out_d[i] = (float)(sum over ranks 1 .. mean_k of (double)sqrtf(key) / mean_k), the ranks of point i's ascending keys over the whole cloud (itself rank 0)
+void sor_meandist(hipStream_t s, const SortedCloud& cl, int mean_k, float* out_d, OutlierStats* st);
+// sum d and sum d d in input-index order (fixed order), then st->mean / stddev / threshold = mean + std_mul stddev (variance clamped at 0)
+void sor_stats(hipStream_t s, const float* d, int n, double std_mul, double* partials, OutlierStats* st);
+// out_cnt[i] = the points with key < r2 about point i (itself one of them; r: the radius r2 was made from); exact == 0: a lower bound > min_nb where the
+// count exceeds min_nb (the walk stops there)
+void ror_count(hipStream_t s, const SortedCloud& cl, float r2, double r, int min_nb, int exact, int* out_cnt, OutlierStats* st);
+// flag[0 .. n]: kept (flag[n] = 0); d != nullptr: (double)d[i] <= st->threshold, else cnt[i] - 1 >= min_nb; negative inverts
+void outlier_flag(hipStream_t s, const float* d, const int* cnt, int n, const OutlierStats* st, int min_nb, int negative, int* flag);
+// off = the exclusive scan of flag: the kept points' 16-byte records (c = 0 for a 12-byte stride) and input indices in ascending input index; each nullable
+void outlier_emit(hipStream_t s, const float* in, int stride_f, int n, const int* flag, const int* off, float* out, int* out_index);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,

@@ -65,6 +65,26 @@ class Preprocessor:
                                                C.byref(n), 0))
         return (out[:n.value].copy(), idx[:n.value].copy()) if return_index else out[:n.value].copy()
 
+    def statisticalOutlierRemoval(self, xyzc, mean_k, std_mul, negative=False, return_index=False):
+        """pcl::StatisticalOutlierRemoval setMeanK(mean_k) + setStddevMulThresh(std_mul) + filter (rgc_outlier_statistical): the points whose mean
+        distance to their mean_k nearest neighbours is <= mean + std_mul stddev, in input order; (m, 4) float32, and their input indices with
+        ``return_index``."""
+        return self._outlier(xyzc, return_index, lambda p, n, st, out, idx, cnt: self._L.rgc_outlier_statistical(
+            self._h, p, n, st, 0, int(mean_k), float(std_mul), 1 if negative else 0, out, idx, None, cnt))
+
+    def radiusOutlierRemoval(self, xyzc, radius, min_neighbors, negative=False, return_index=False):
+        """pcl::RadiusOutlierRemoval setRadiusSearch(radius) + setMinNeighborsInRadius(min_neighbors) + filter (rgc_outlier_radius)"""
+        return self._outlier(xyzc, return_index, lambda p, n, st, out, idx, cnt: self._L.rgc_outlier_radius(
+            self._h, p, n, st, 0, float(radius), int(min_neighbors), 1 if negative else 0, out, idx, None, cnt))
+
+    def _outlier(self, xyzc, return_index, call):
+        a = np.ascontiguousarray(xyzc, dtype=np.float32)
+        out = np.empty((a.shape[0], 4), np.float32)
+        idx = np.empty(a.shape[0], np.int32)
+        n = C.c_int(0)
+        self._chk(call(a.ctypes.data, a.shape[0], a.strides[0], out.ctypes.data, idx.ctypes.data if return_index else None, C.byref(n)))
+        return (out[:n.value].copy(), idx[:n.value].copy()) if return_index else out[:n.value].copy()
+
     def voxelGridRoute(self):
         """what the last voxelGridFilter on this object did (rgc_voxelgrid_route), as a dict of the rgc_vg_route fields"""
         r = _lib.VgRoute()
