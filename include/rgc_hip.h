@@ -1161,6 +1161,50 @@ RGC_API int rgc_outlier_radius(rgc_ctx* ctx, const float* xyzc, int n, int strid
 RGC_API int rgc_outlier_get_info(rgc_ctx* ctx, rgc_outlier_info* info);
 RGC_API int rgc_outlier_set_cell(rgc_ctx* ctx, double cell);
 
+/* ---- Euclidean cluster extraction: pcl::EuclideanClusterExtraction of a cloud, the first structural operation a LiDAR pipeline runs on one (small
+ * clusters dropped as noise before a scan goes into a map, movable objects cut out of a keyframe, what is left after the ground is removed).  (The
+ * reference's three nodes do not call the PCL class, as they do not call the outlier filters; it completes the per-point PCL toolbox beside
+ * rgc_search_* and rgc_outlier_*.) ----
+ *   rgc_cluster_extract -- restated from PCL's segmentation/impl/extract_clusters.hpp FROM MEMORY [3P-memory] (PCL is not available to this project):
+ *   Graph: points i and j are joined iff key(i, j) < r2, strict, r2 = (float)((double)tolerance * (double)tolerance) -- rgc_search_radius' and
+ * rgc_outlier_radius' membership rule.  Key: the fp32 ((dx dx + dy dy) + dz dz), never FMA-contracted, as everywhere in this library; it is exactly
+ * symmetric in fp32, so the graph is undirected and its connected components are well defined.  Duplicates (key 0) are always joined.
+ *   Clusters: PCL grows a cluster from the lowest unprocessed index by breadth-first radiusSearch, marks everything it reaches as processed whether or
+ * not the cluster is then kept, sorts the cluster's indices and keeps it iff min_size <= size <= max_size, both inclusive.  Hence a cluster IS a
+ * connected component; a component over max_size is dropped whole, and its points go to no other cluster.
+ *   Order: clusters by size descending, then by smallest member index ascending (a total order); members inside a cluster in ascending input index.
+ * No output bit depends on the grid, on its cell size, on the launch shape or on the run; host-pointer and device-pointer calls give identical bytes.
+ *   Outputs (each nullable): labels[i], i < n = the rank of i's cluster in that order, or -1 when the point is in no kept cluster; offsets[0 ..
+ * n_clusters] and indices[0 .. n_clustered) = the clusters in CSR form (cluster r is indices[offsets[r] .. offsets[r + 1])).  Entries behind those ranges
+ * are left untouched.  labels and indices need room for n ints, offsets for n + 1: a cluster table is never longer, which spares the size-then-fill
+ * protocol of rgc_search_radius.  *n_clusters = clusters kept.
+ *   Argument rules, on_device and the record format are rgc_outlier_radius': x, y, z as floats at the head of each record of stride_bytes; on_device
+ * covers the cloud AND every output; n <= 2^27.  The call builds a grid of its own over the cloud (the search index's machinery and automatic cell
+ * rule): a caller's search index, source and target are untouched.  A solve in flight refuses the call (RGC_ERR_INVALID).  rgc_cluster_set_cell fixes
+ * the grid's cell size for tests and tuning (0 = automatic; finite and >= 0); NO OUTPUT BIT DEPENDS ON IT.
+ *   Refusals: tolerance not finite or <= 0, r2 not finite, min_size < 1, max_size < min_size, n < 0, a bad stride, a NULL cloud (n > 0), context or
+ * n_clusters: RGC_ERR_INVALID; n = 0: RGC_OK with zero clusters and offsets[0] = 0 if offsets is given; a non-finite coordinate: RGC_ERR_NONFINITE,
+ * detected on the device by the grid build, nothing written; RGC_ERR_GRID_TOO_LARGE as elsewhere; RGC_ERR_HIP with a message and nothing written
+ * should a union-find loop of the linking kernels ever run past its iteration cap (a logic error surfaces as a code, not as a kernel that does not end).
+ * PCL's defaults (min_size 1, max_size INT_MAX) are accepted.
+ *   Deviations from PCL: the order among clusters of equal size -- PCL's final unstable std::sort by size leaves ties unspecified, here the smaller
+ * smallest member index goes first; PCL's optional indices-subset input and ConditionalEuclideanClustering are not built.
+ *   rgc_cluster_get_info: the LAST rgc_cluster_extract. */
+typedef struct rgc_cluster_info {
+  int n;                 /* points in                                                     */
+  int n_components;      /* connected components before the size limits                   */
+  int n_clusters;        /* components kept                                               */
+  int n_clustered;       /* points in kept clusters                                       */
+  int largest;           /* size of the largest component, kept or not                    */
+  double cell;           /* the grid the call used: its cell size                         */
+  long long cells;       /* ... and its cells                                             */
+  long long candidates;  /* indexed points looked at over all points (as rgc_outlier_info) */
+} rgc_cluster_info;
+RGC_API int rgc_cluster_extract(rgc_ctx* ctx, const float* xyzc, int n, int stride_bytes, int on_device, double tolerance, int min_size, int max_size,
+                                int* labels /* nullable, n */, int* offsets /* nullable, n + 1 */, int* indices /* nullable, n */, int* n_clusters);
+RGC_API int rgc_cluster_get_info(rgc_ctx* ctx, rgc_cluster_info* info);
+RGC_API int rgc_cluster_set_cell(rgc_ctx* ctx, double cell);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

@@ -180,6 +180,13 @@ class OutlierInfo(C.Structure):
 
 OUTLIER_MAX_MEAN_K = 63
 
+
+class ClusterInfo(C.Structure):
+    """rgc_cluster_info: the last rgc_cluster_extract (rgc_cluster_get_info)"""
+    _fields_ = [("n", C.c_int), ("n_components", C.c_int), ("n_clusters", C.c_int), ("n_clustered", C.c_int), ("largest", C.c_int), ("cell", C.c_double),
+                ("cells", C.c_longlong), ("candidates", C.c_longlong)]
+
+
 NDT_P2D, NDT_D2D = 0, 1
 NDT_DIRECT27, NDT_DIRECT7, NDT_DIRECT1, NDT_DIRECT_RADIUS = 0, 1, 2, 3
 NDT_MAX_OFFSETS = 512
@@ -211,6 +218,7 @@ SYMBOLS = [
     "rgc_default_gicp_mp_params", "rgc_gicpmp_set_params", "rgc_gicpmp_get_params", "rgc_gicpmp_linearize", "rgc_gicpmp_num_correspondences", "rgc_gicpmp_num_candidates", "rgc_gicpmp_get_merged", "rgc_gicpmp_get_neighbors", "rgc_gicpmp_align",
     "rgc_search_set_cloud", "rgc_search_clear", "rgc_search_get_info", "rgc_search_sort_window", "rgc_search_knn", "rgc_search_radius",
     "rgc_outlier_statistical", "rgc_outlier_radius", "rgc_outlier_get_info", "rgc_outlier_set_cell",
+    "rgc_cluster_extract", "rgc_cluster_get_info", "rgc_cluster_set_cell",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
@@ -452,6 +460,9 @@ def load():
     L.rgc_outlier_radius.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, ip]
     L.rgc_outlier_get_info.argtypes = [vp, C.POINTER(OutlierInfo)]
     L.rgc_outlier_set_cell.argtypes = [vp, C.c_double]
+    L.rgc_cluster_extract.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, ip]
+    L.rgc_cluster_get_info.argtypes = [vp, C.POINTER(ClusterInfo)]
+    L.rgc_cluster_set_cell.argtypes = [vp, C.c_double]
     L.rgc_profile_enable.argtypes = [vp, C.c_int]
     L.rgc_profile_select.argtypes = [vp, C.c_uint]
     L.rgc_profile_reset.argtypes = [vp]

@@ -1319,6 +1319,9 @@ void rgc_destroy(rgc_ctx* c) {
   release_cloud(c->filter_cl);
   for (DevBuf* b : {&c->filter_in, &c->filter_val, &c->filter_flag, &c->filter_off, &c->filter_bs, &c->filter_partials, &c->filter_out, &c->filter_idx, &c->filter_small}) release(*b);
   if (c->filter_h) (void)hipHostFree(c->filter_h);
+  release_cloud(c->cluster_cl);
+  for (DevBuf* b : {&c->cluster_in, &c->cluster_work, &c->cluster_hist, &c->cluster_bs, &c->cluster_small}) release(*b);
+  if (c->cluster_h) (void)hipHostFree(c->cluster_h);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);

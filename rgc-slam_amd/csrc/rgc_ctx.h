@@ -406,6 +406,14 @@ struct rgc_ctx {
   long long prof_launches[kProfKinds] = {0};
   double prof_ms[kProfKinds] = {0};
   long long prof_points[kProfKinds] = {0};
+  // Euclidean cluster extraction (rgc_cluster_*, rgc_api_cluster.hip), behind everything else so that no older member moves: a cloud of its own with the grid only; a host caller's staged records; the int
+  // arrays of a call carved from ONE buffer (the union-find, the per-point and per-cluster tables, the radix sort's two pairs of arrays, a host
+  // caller's results); the radix histograms and the scans' block sums; the grid's measurement, the counts and rgck::ClusterStats with their pinned mirror
+  Cloud cluster_cl;
+  DevBuf cluster_in, cluster_work, cluster_hist, cluster_bs, cluster_small;
+  unsigned char* cluster_h = nullptr;
+  rgc_cluster_info cluster_info{};
+  double cluster_cell = 0.0;          // rgc_cluster_set_cell: 0 = the search index's automatic rule
 };
 
 namespace rgcapi {

@@ -457,6 +457,32 @@ void ror_count(hipStream_t s, const SortedCloud& cl, float r2, double r, int min
 void outlier_flag(hipStream_t s, const float* d, const int* cnt, int n, const OutlierStats* st, int min_nb, int negative, int* flag);
 // off = the exclusive scan of flag: the kept points' 16-byte records (c = 0 for a 12-byte stride) and input indices in ascending input index; each nullable
 void outlier_emit(hipStream_t s, const float* in, int stride_f, int n, const int* flag, const int* off, float* out, int* out_index);
+// ---- Euclidean cluster extraction (rgc_cluster_*, rgc_cluster.hip): the connected components of the key < r2 graph of a cloud on a grid of its own ----
+// What a call reads back: the error word (!= 0: a find / unite loop ran past its iteration cap -- a logic error, RGC_ERR_HIP) and the read-out words as
+// kClusterSlots partial results a cache line apart, as OutlierStats': word 0 indexed points looked at (summed), word 1 components (summed), word 2 the
+// largest component's size (the slots' maximum)
+constexpr int kClusterSlots = 32;
+struct ClusterStats { int err; int pad[15]; unsigned long long words[kClusterSlots][8]; };
+constexpr int kClusterRadixTile = 1024;   // pairs per workgroup of a radix pass
+constexpr int kClusterRadixDigits = 256;  // 8-bit digits
+int  cluster_group();              // lanes per point of this build's linking kernel
+int  cluster_radix_tiles(int m);   // workgroups of a radix pass over m pairs: hist / hist_off hold kClusterRadixDigits * tiles + 1 ints
+// parent / lead / size: n ints each, on SORTED positions.  After this chain parent[x] is x's root, lead[root] the component's smallest ORIGINAL index,
+// size[root] its points.  r: the tolerance r2 was made from
+void cluster_link(hipStream_t s, const SortedCloud& cl, float r2, double r, int* parent, int* lead, int* size, ClusterStats* st);
+// at the ORIGINAL index i: comp[i] the leader of i's component, csize[i] its size, flag_p[i] = min_size <= size <= max_size, flag_l[i] = flag_p[i] and
+// i is the leader; flag_p[n] = flag_l[n] = 0.  Components and the largest size go to st
+void cluster_assign(hipStream_t s, const SortedCloud& cl, const int* parent, const int* lead, const int* size, int min_size, int max_size, int* comp, int* csize,
+                    int* flag_p, int* flag_l, ClusterStats* st);
+// off_l = the exclusive scan of flag_l: the kept leaders in ascending input index, key = n - size, val = the leader
+void cluster_emit(hipStream_t s, int n, const int* flag_l, const int* off_l, const int* csize, int* key, int* val);
+// a STABLE ascending sort of m (key, val) pairs on the low `bits` bits of the key, ceil(bits / 8) passes between key[0] / val[0] and key[1] / val[1];
+// returns which of the two holds the result (0 when no pass was needed: bits = 0 or m <= 1).  block_sums: as exclusive_scan's for the histogram
+int  cluster_radix_sort(hipStream_t s, int m, int bits, int* key[2], int* val[2], int* hist, int* hist_off, int* block_sums);
+// rank_at[val[r]] = r, sizes[r] = n - key[r] for r < m; sizes[m] = 0
+void cluster_rank(hipStream_t s, int n, int m, const int* key, const int* val, int* rank_at, int* sizes);
+// labels[i] (nullable) = flag_p[i] ? rank_at[comp[i]] : -1; pkey / pval (nullable together) at off_p[i]: that rank and i, for the kept points
+void cluster_labels(hipStream_t s, int n, const int* flag_p, const int* off_p, const int* comp, const int* rank_at, int* labels, int* pkey, int* pval);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,

@@ -85,6 +85,19 @@ class Preprocessor:
         self._chk(call(a.ctypes.data, a.shape[0], a.strides[0], out.ctypes.data, idx.ctypes.data if return_index else None, C.byref(n)))
         return (out[:n.value].copy(), idx[:n.value].copy()) if return_index else out[:n.value].copy()
 
+    def euclideanClusterExtraction(self, xyzc, tolerance, min_size=1, max_size=2**31 - 1):
+        """pcl::EuclideanClusterExtraction setClusterTolerance(tolerance) + setMinClusterSize + setMaxClusterSize + extract (rgc_cluster_extract):
+        (labels, offsets, indices) -- labels (n,) int32, the rank of every point's cluster (size descending, then smallest member ascending) or -1;
+        cluster r is indices[offsets[r]:offsets[r + 1]], members ascending"""
+        a = np.ascontiguousarray(xyzc, dtype=np.float32)
+        n = a.shape[0]
+        labels, offsets, indices = np.empty(n, np.int32), np.empty(n + 1, np.int32), np.empty(n, np.int32)
+        m = C.c_int(0)
+        self._chk(self._L.rgc_cluster_extract(self._h, a.ctypes.data, n, a.strides[0], 0, float(tolerance), int(min_size), int(max_size), labels.ctypes.data,
+                                              offsets.ctypes.data, indices.ctypes.data, C.byref(m)))
+        offsets = offsets[:m.value + 1].copy()
+        return labels, offsets, indices[:int(offsets[-1])].copy()
+
     def voxelGridRoute(self):
         """what the last voxelGridFilter on this object did (rgc_voxelgrid_route), as a dict of the rgc_vg_route fields"""
         r = _lib.VgRoute()
