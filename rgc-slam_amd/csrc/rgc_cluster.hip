@@ -6,8 +6,7 @@
 // index, and every atomic is an integer one (CAS, min, add, max).
 //
 // k_cl_init        parent[x] = x, lead[x] = INT_MAX, size[x] = 0 over the sorted positions
-// k_cl_link<G>     a group of G lanes per sorted point walks the block of cells its ball can touch (k_ror_count's walk and row-gap test, restated here
-//                  as rgc_filters.hip restates rgc_search.hip's: those files' device code stays byte-identical), only over sorted positions BELOW its
+// k_cl_link<G>     a group of G lanes per sorted point walks the block of cells its ball can touch (k_ror_count's walk: ball_rows of rgc_nn.h), only over sorted positions BELOW its
 //                  own -- every edge is seen once -- and unites the two components of every member with key < r2 (cl_unite)
 // k_cl_flatten     (a separate launch) every position points at its root
 // k_cl_census      atomicMin of the ORIGINAL index and atomicAdd of the count into the root's slots, one pair per run of equal roots in a wave
@@ -93,10 +92,10 @@ __device__ __forceinline__ int cl_unite(int* __restrict__ parent, int a, int b, 
 // into the workgroup's slot: one integer atomic per workgroup and word.  Called by every thread of the workgroup
 __device__ __forceinline__ void cl_stats_add(ClusterStats* st, unsigned long long w0, unsigned long long w1, unsigned long long mx) {
   __shared__ unsigned long long part[CL_T / CL_WAVE][3];
+  w0 = wave_sum_u64(w0);
+  w1 = wave_sum_u64(w1);
 #pragma unroll
   for (int o = CL_WAVE / 2; o > 0; o >>= 1) {
-    w0 += __shfl_down(w0, o, CL_WAVE);
-    w1 += __shfl_down(w1, o, CL_WAVE);
     const unsigned long long t = __shfl_down(mx, o, CL_WAVE);
     mx = t > mx ? t : mx;
   }
@@ -126,12 +125,6 @@ __global__ void __launch_bounds__(CL_T) k_cl_init(int n, int* __restrict__ paren
   size[x] = 0;
 }
 
-// the cell of x along axis a, relative to the grid, clamped in fp64 to [-1, dim] (sr_cell_rel of rgc_search.hip, restated)
-__device__ __forceinline__ int cl_cell_rel(double x, const Grid& g, int a) {
-  const double u = floor(g.inv_res != 0.0 ? x * g.inv_res - 0.5 : x / g.res - 0.5) - (double)g.minc[a];
-  return (int)fmin(fmax(u, -1.0), (double)g.dim[a]);
-}
-
 template <int G>
 __global__ void __launch_bounds__(CL_T) k_cl_link(const float4* __restrict__ TP, const int* __restrict__ tstart, Grid g, int n, float r2, double reach,
                                                   int* __restrict__ parent, ClusterStats* __restrict__ st) {
@@ -141,43 +134,27 @@ __global__ void __launch_bounds__(CL_T) k_cl_link(const float4* __restrict__ TP,
     const float4 me = point_at(TP, (unsigned)si << 4);
     const float px = me.x, py = me.y, pz = me.z;
     const double q[3] = {(double)px, (double)py, (double)pz};
-    // the block of cells the ball of radius `reach` about the point can touch (reach = r (1 + 1e-5): argued at mp_block, rgc_gicp_mp.hip)
-    int lo[3], hi[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      lo[a] = max(cl_cell_rel(q[a] - reach, g, a), 0);
-      hi[a] = min(cl_cell_rel(q[a] + reach, g, a), g.dim[a] - 1);
-    }
-    // only the sorted positions below si are linked from here (the others link to si): the layers above the point's own hold none of them
-    hi[2] = min(hi[2], cell_coord(pz, g) - g.minc[2]);
-    const double reach2 = reach * reach;
+    // the rows of the ball of radius `reach` about the point (ball_block / ball_rows of rgc_nn.h, where reach = r (1 + 1e-5) is argued), the in-step rule
+    CellBlock B = ball_block(q, reach, g);
+    // only the sorted positions below si are linked from here (the others link to si): the layers above the point's own hold none of them ...
+    B.hi[2] = min(B.hi[2], cell_coord(pz, g) - g.minc[2]);
     int cnt = 0, root = si;  // root: a position of si's component, its root as this lane last saw it
-    bool dead = false;       // the error route: a unite ran out of its budget, the lane leaves
-    for (int z = lo[2]; z <= hi[2] && !dead; z++) {
-      const double wz = cell_wall(g, 2, z), gz = fmax(0.0, fmax(wz - q[2], q[2] - (wz + g.res)));
-      for (int yb = lo[1]; yb <= hi[1] && !dead; yb += CL_ROWS) {
-        int ra[CL_ROWS], rb[CL_ROWS];  // (CL_ROWS row ranges fetched together, as in k_ror_count)
+    bool dead = false;       // the error route: a unite ran out of its budget, the lane leaves (after the batch of rows)
+    ball_rows<CL_ROWS>(B, q, reach, tstart, g, [&](const int (&ra)[CL_ROWS], const int (&rb)[CL_ROWS]) {
 #pragma unroll
-        for (int u = 0; u < CL_ROWS; u++) {
-          const int y = min(yb + u, hi[1]);
-          const double wy = cell_wall(g, 1, y), gy = fmax(0.0, fmax(wy - q[1], q[1] - (wy + g.res)));
-          const int a = tstart[cell_index(g, lo[0], y, z)], b = min(tstart[cell_index(g, hi[0], y, z) + 1], si);
-          ra[u] = a;
-          rb[u] = yb + u <= hi[1] && gy * gy + gz * gz <= reach2 ? b : a;  // (the ball cannot reach a row beyond the gap: empty)
-        }
-#pragma unroll
-        for (int u = 0; u < CL_ROWS; u++) {
-          cnt += max(rb[u] - ra[u], 0);
-          for (int i = ra[u] + lane; i < rb[u] && !dead; i += G) {
-            if (dist2(px, py, pz, point_at(TP, (unsigned)i << 4)) < r2 && cl_load(parent + i) != root) {
-              const int r = cl_unite(parent, root, i, n, &st->err);
-              dead = r < 0;
-              root = dead ? root : r;
-            }
+      for (int u = 0; u < CL_ROWS; u++) {
+        const int b = min(rb[u], si);  // ... and every row ends at si
+        cnt += max(b - ra[u], 0);
+        for (int i = first_in_step(ra[u], lane); i < b && !dead; i += G) {
+          if (dist2(px, py, pz, point_at(TP, (unsigned)i << 4)) < r2 && cl_load(parent + i) != root) {
+            const int r = cl_unite(parent, root, i, n, &st->err);
+            dead = r < 0;
+            root = dead ? root : r;
           }
         }
       }
-    }
+      return !dead;
+    });
     if (lane == 0) cand = (unsigned long long)cnt;
   }
   cl_stats_add(st, cand, 0, 0);

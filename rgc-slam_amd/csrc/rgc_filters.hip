@@ -7,14 +7,12 @@
 // k_sor_meandist<KT, G>  the mean_k + 1 (<= KT) smallest KEYS of a sorted point, by a group of G lanes striding the row ranges of the cube of cells
 //                        about its cell, with k_search_knn's running count, cube growth and cube_bound exit (the lists start over when the cube
 //                        grows).  Each lane keeps an ascending list of KT 32-bit keys (non-negative fp32 bit patterns order as integers) in
-//                        registers: every index into the list is a compile-time constant of a fully unrolled loop, and a candidate is compared
-//                        with the list's tail first.  The G lists are merged by mean_k + 1 rounds of a group-wide minimum (of tied heads the lowest
+//                        registers (list_insert of rgc_nn.h).  The G lists are merged by mean_k + 1 rounds of a group-wide minimum (of tied heads the lowest
 //                        lane pops: equal keys have equal roots, the sum does not depend on who wins); the leader drops rank 0 (the point itself or
 //                        a duplicate of it) and adds the roots of ranks 1 .. mean_k in fp64 in rank order as the merge proceeds.
 // k_sor_stats / k_sor_fold  sum d and sum d d in fp64 IN INPUT-INDEX ORDER with the fixed-order sums of rgc_terms.h; then one lane computes mean,
 //                        stddev and threshold and posts them: no host round trip between the passes
-// k_ror_count<G, kExact> the members of a sorted point's ball (key < r2, strict), the ball walk of k_search_count (sr_ball_walk's block and gap test,
-//                        restated here as rgc_search.hip restates mp_walk: that file's device code stays byte-identical); kExact = false: the group
+// k_ror_count<G, kExact> the members of a sorted point's ball (key < r2, strict), the ball walk of k_search_count, three rows fetched together; kExact = false: the group
 //                        stops walking once its count exceeds min_neighbors (the decision is made; the count it writes is then a lower bound)
 // k_outlier_flag         the decision of every point in input order (SOR: (double)d <= threshold; ROR: count - 1 >= min_neighbors; negative inverts)
 // k_outlier_emit         (after the library's exclusive_scan of the flags) records and indices, ascending input index
@@ -43,11 +41,8 @@ int outlier_group() { return FL_GROUP; }
 // workgroup's slot: one integer atomic per workgroup and word, spread over kOutlierSlots cache lines.  Called by every thread of the workgroup
 __device__ __forceinline__ void fl_stats_add(OutlierStats* st, unsigned long long cand, unsigned long long grew) {
   __shared__ unsigned long long part[FL_T / FL_WAVE][2];
-#pragma unroll
-  for (int o = FL_WAVE / 2; o > 0; o >>= 1) {
-    cand += __shfl_down(cand, o, FL_WAVE);
-    grew += __shfl_down(grew, o, FL_WAVE);
-  }
+  cand = wave_sum_u64(cand);
+  grew = wave_sum_u64(grew);
   if ((threadIdx.x & (FL_WAVE - 1)) == 0) {
     part[threadIdx.x / FL_WAVE][0] = cand;
     part[threadIdx.x / FL_WAVE][1] = grew;
@@ -73,61 +68,33 @@ __global__ void __launch_bounds__(FL_T) k_sor_meandist(const float4* __restrict_
     const double q[3] = {(double)px, (double)py, (double)pz};
     // the point's own cell: it was sorted into the grid by this rule, so it lies inside
     const int c[3] = {cell_coord(px, g) - g.minc[0], cell_coord(py, g) - g.minc[1], cell_coord(pz, g) - g.minc[2]};
-    int rmax = 0, r = 1;
-#pragma unroll
-    for (int a = 0; a < 3; a++) rmax = max(rmax, max(c[a], g.dim[a] - 1 - c[a]));
+    int rmax, r;
+    cube_first(c, g, r, rmax);  // (r = 1: the cell lies inside)
     unsigned L[KT];
     double sum = 0.0;
     for (;;) {
 #pragma unroll
       for (int u = 0; u < KT; u++) L[u] = kFlNone;  // the lists start over at every cube
-      const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.dim[2] - 1);
-      const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.dim[1] - 1);
-      const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.dim[0] - 1);
       int cnt = 0;
-      for (int z = z0; z <= z1; z++)
-        for (int yb = y0; yb <= y1; yb += FL_ROWS) {
-          int ra[FL_ROWS], rb[FL_ROWS];  // FL_ROWS row ranges fetched together: one round trip, not one per row (a row past the cube: its neighbour's, taken as empty)
+      cube_rows<FL_ROWS>(c, r, tstart, g, [&](const int (&ra)[FL_ROWS], const int (&rb)[FL_ROWS]) {
 #pragma unroll
-          for (int u = 0; u < FL_ROWS; u++) {
-            const int y = min(yb + u, y1);
-            const int a = tstart[cell_index(g, x0, y, z)], b = tstart[cell_index(g, x1, y, z) + 1];
-            ra[u] = a;
-            rb[u] = yb + u <= y1 ? b : a;
-          }
-#pragma unroll
-          for (int u = 0; u < FL_ROWS; u++) {
-            const int a = ra[u], b = rb[u];
-            int i = a + ((lane - cnt) & (G - 1));
-            cnt += b - a;
-            for (; i < b; i += G) {
-              const unsigned e = __float_as_uint(dist2(px, py, pz, point_at(TP, (unsigned)i << 4)));
-              if (e < L[KT - 1]) {  // (the tail first: most candidates end here once the list is warm)
-#pragma unroll
-                for (int v = KT - 1; v > 0; v--) L[v] = e < L[v - 1] ? L[v - 1] : (e < L[v] ? e : L[v]);
-                L[0] = e < L[0] ? e : L[0];
-              }
-            }
-          }
+        for (int u = 0; u < FL_ROWS; u++) {
+          int i = first_carried<G>(ra[u], lane, cnt);
+          cnt += rb[u] - ra[u];
+          for (; i < rb[u]; i += G) list_insert(L, __float_as_uint(dist2(px, py, pz, point_at(TP, (unsigned)i << 4))));
         }
+        return true;
+      });
       cand += (unsigned long long)cnt;
       // the G lists merged: k1 rounds of the group's minimum; of the lanes whose head it is the lowest pops
       int found = 0;
       unsigned kth_bits = 0x7f800000u;
       sum = 0.0;
       for (int j = 0; j < k1; j++) {
-        unsigned m = L[0];
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) {
-          const unsigned other = __shfl_xor(m, o, G);
-          m = other < m ? other : m;
-        }
+        const unsigned m = group_min<G>(L[0]);
         const bool any = m != kFlNone;
         const unsigned heads = (unsigned)(__ballot(any && m == L[0]) >> shift) & ((1u << G) - 1u);
-        const bool win = any && lane == __ffs(heads) - 1;
-#pragma unroll
-        for (int u = 0; u < KT - 1; u++) L[u] = win ? L[u + 1] : L[u];
-        L[KT - 1] = win ? kFlNone : L[KT - 1];
+        list_pop(L, any && lane == __ffs(heads) - 1);
         if (any) {
           found++;
           kth_bits = m;
@@ -140,21 +107,9 @@ __global__ void __launch_bounds__(FL_T) k_sor_meandist(const float4* __restrict_
       if (bound == 1.0e300) break;
       const bool full = found == k1;
       const float kth = __uint_as_float(kth_bits);
-      if (full && bound > 0.0 && (double)kth < bound * bound * (1.0 - 1e-5)) break;  // the K-TH entry is provably inside the cube
+      if (full && key_inside(kth, bound)) break;  // the K-TH entry is provably inside the cube
       grew = 1;
-      int rn;
-      if (full) {
-        const double need = sqrt((double)kth) * (1.0 + 1e-5);
-        rn = r + 1;
-        while (rn < rmax) {
-          const double b = cube_bound(g, c, q, rn);
-          if (b == 1.0e300 || b > need) break;
-          rn++;
-        }
-      } else {
-        rn = r + max(1, (r + 1) / 2);
-      }
-      r = min(rn, rmax);
+      r = cube_next(g, c, q, r, rmax, full, key_reach(kth));
     }
     if (lane == 0) {
       out_d[__float_as_int(me.w)] = (float)(sum / (double)(k1 - 1));
@@ -192,12 +147,6 @@ __global__ void __launch_bounds__(2 * FL_WAVE) k_sor_fold(const double* __restri
   }
 }
 
-// the cell of x along axis a, relative to the grid, clamped in fp64 to [-1, dim] (sr_cell_rel of rgc_search.hip, restated)
-__device__ __forceinline__ int fl_cell_rel(double x, const Grid& g, int a) {
-  const double u = floor(g.inv_res != 0.0 ? x * g.inv_res - 0.5 : x / g.res - 0.5) - (double)g.minc[a];
-  return (int)fmin(fmax(u, -1.0), (double)g.dim[a]);
-}
-
 template <int G, bool kExact>
 __global__ void __launch_bounds__(FL_T) k_ror_count(const float4* __restrict__ TP, const int* __restrict__ tstart, Grid g, int n, float r2, double reach, int min_nb,
                                                     int* __restrict__ out_cnt, OutlierStats* __restrict__ st) {
@@ -207,41 +156,21 @@ __global__ void __launch_bounds__(FL_T) k_ror_count(const float4* __restrict__ T
     const float4 me = point_at(TP, (unsigned)si << 4);
     const float px = me.x, py = me.y, pz = me.z;
     const double q[3] = {(double)px, (double)py, (double)pz};
-    // the block of cells the ball of radius `reach` about the point can touch (reach = r (1 + 1e-5): argued at mp_block, rgc_gicp_mp.hip)
-    int lo[3], hi[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      lo[a] = max(fl_cell_rel(q[a] - reach, g, a), 0);
-      hi[a] = min(fl_cell_rel(q[a] + reach, g, a), g.dim[a] - 1);
-    }
-    const double reach2 = reach * reach;
+    // the rows of the ball of radius `reach` about the point (ball_block / ball_rows of rgc_nn.h, where reach = r (1 + 1e-5) is argued), the in-step rule
     int mine = 0, total = 0, cnt = 0;
-    bool done = false;
-    for (int z = lo[2]; z <= hi[2] && !done; z++) {
-      const double wz = cell_wall(g, 2, z), gz = fmax(0.0, fmax(wz - q[2], q[2] - (wz + g.res)));
-      for (int yb = lo[1]; yb <= hi[1] && !done; yb += FL_ROWS) {
-        int ra[FL_ROWS], rb[FL_ROWS];  // (FL_ROWS row ranges fetched together, as in k_sor_meandist)
+    ball_rows<FL_ROWS>(ball_block(q, reach, g), q, reach, tstart, g, [&](const int (&ra)[FL_ROWS], const int (&rb)[FL_ROWS]) {
 #pragma unroll
-        for (int u = 0; u < FL_ROWS; u++) {
-          const int y = min(yb + u, hi[1]);
-          const double wy = cell_wall(g, 1, y), gy = fmax(0.0, fmax(wy - q[1], q[1] - (wy + g.res)));
-          const int a = tstart[cell_index(g, lo[0], y, z)], b = tstart[cell_index(g, hi[0], y, z) + 1];
-          ra[u] = a;
-          rb[u] = yb + u <= hi[1] && gy * gy + gz * gz <= reach2 ? b : a;  // (the ball cannot reach a row beyond the gap: empty)
-        }
-#pragma unroll
-        for (int u = 0; u < FL_ROWS; u++) {
-          cnt += rb[u] - ra[u];
-          for (int i = ra[u] + lane; i < rb[u]; i += G) mine += dist2(px, py, pz, point_at(TP, (unsigned)i << 4)) < r2 ? 1 : 0;
-        }
-        if (!kExact) {  // the decision is made once the group's count exceeds min_neighbors (count - 1 >= min_neighbors)
-          total = mine;
-#pragma unroll
-          for (int o = G / 2; o > 0; o >>= 1) total += __shfl_xor(total, o, G);
-          done = total > min_nb;
-        }
+      for (int u = 0; u < FL_ROWS; u++) {
+        cnt += rb[u] - ra[u];
+        for (int i = first_in_step(ra[u], lane); i < rb[u]; i += G) mine += dist2(px, py, pz, point_at(TP, (unsigned)i << 4)) < r2 ? 1 : 0;
       }
-    }
+      if (kExact) return true;
+      // the decision is made once the group's count exceeds min_neighbors (count - 1 >= min_neighbors): once per batch of rows
+      total = mine;
+#pragma unroll
+      for (int o = G / 2; o > 0; o >>= 1) total += __shfl_xor(total, o, G);
+      return total <= min_nb;
+    });
     if (kExact) {
       total = mine;
 #pragma unroll

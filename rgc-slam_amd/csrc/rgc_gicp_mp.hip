@@ -4,7 +4,7 @@
 // key in fp32 (never FMA-contracted: -ffp-contract=off), everything after them fp64, every sum in a fixed order, no floating-point atomics.
 // Citations are relative to rgc_slam/ of the reference (ROBOT-WSC/RGC-SLAM).
 // A translation unit of its own, over the pieces every solver shares: the term (under W = M M), the covariance of a sorted point, the shuffle-tree
-// block store and the column fold are rgc_terms.h's, the inverse rgc_cov.h's, the fp32 query rgc_nn.h's.  The radius gather (k_gicp_mp_merge: fp32
+// block store and the column fold are rgc_terms.h's, the inverse rgc_cov.h's, the fp32 query and the ball's walk rgc_nn.h's.  The radius gather (k_gicp_mp_merge: fp32
 // candidates, eleven fp64 accumulators) and the term (k_gicp_mp_terms: 30 accumulators) are two kernels, as in rgc_gicp.hip -- no spill, no private
 // segment, no accumulator registers; nothing waits on another workgroup.
 #include "rgc_kernels.h"
@@ -28,54 +28,18 @@ static_assert(MP_GROUP >= 1 && MP_GROUP <= MP_WAVE && !(MP_GROUP & (MP_GROUP - 1
 
 int gicp_mp_blocks(int n) { return (n + MP_T - 1) / MP_T; }
 
-// The part of the target's grid the ball of radius `reach` about the query can touch: per axis the cells of q - reach and q + reach, clipped
-// to the grid.  reach = r (1 + 1e-5): a point whose fp32 key is below r2 lies within r (1 + 3 * 2^-24) of the query in exact arithmetic (the
-// key's three products and two sums round by 2^-24 each, the differences of fp32 coordinates at most as much again), and it lies in the cell
-// its own coordinates name (the grid's rule, cell_coord) -- so no member of the ball is outside this block.  A cell too many costs
-// candidates; a cell too few would be a wrong answer.  empty: the ball misses the grid.
-struct MpBlock { int lo[3], hi[3]; bool empty; };
-__device__ __forceinline__ int mp_cell_rel(double x, const Grid& g, int a) {
-  const double u = floor(g.inv_res != 0.0 ? x * g.inv_res - 0.5 : x / g.res - 0.5) - (double)g.minc[a];
-  return (int)fmin(fmax(u, -1.0), (double)g.dim[a]);  // (clamped in fp64: a query far outside the grid must not overflow the int)
-}
-__device__ __forceinline__ MpBlock mp_block(const double q[3], double reach, const Grid& g) {
-  MpBlock B;
-  B.empty = false;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    B.lo[a] = max(mp_cell_rel(q[a] - reach, g, a), 0);
-    B.hi[a] = min(mp_cell_rel(q[a] + reach, g, a), g.dim[a] - 1);
-    B.empty = B.empty || B.lo[a] > B.hi[a];
-  }
-  return B;
-}
-// distance from x to the cell c of axis a (0 inside it)
-__device__ __forceinline__ double mp_gap(const Grid& g, int a, int c, double x) {
-  const double wall = cell_wall(g, a, c);
-  return fmax(0.0, fmax(wall - x, x - (wall + g.res)));
-}
-
-// Every candidate of the query (qx, qy, qz): the cells of a grid row are consecutive in the sorted target (for_each_cube_row's contiguous row
-// ranges), so the block is (hi_y - lo_y + 1) (hi_z - lo_z + 1) ranges; a row the ball cannot reach is skipped.  Lane `lane` of a group of G
-// takes every G-th candidate of the concatenated ranges (the running count carries over from row to row: short rows do not idle lanes).
-// f(i): sorted position i.  Returns the number of candidates (of all lanes).
+// Every candidate of the query q: the rows of the ball's block of cells (ball_block / ball_rows of rgc_nn.h, where reach = r (1 + 1e-5) is argued),
+// one at a time.  Lane `lane` of a group of G takes every G-th candidate of the concatenated ranges (the carry-over rule).  f(i): sorted position i.
+// Returns the number of candidates (of all lanes).
 template <int G, typename F>
 __device__ __forceinline__ int mp_walk(const double q[3], double reach, const int* __restrict__ tstart, const Grid& g, int lane, F&& f) {
-  const MpBlock B = mp_block(q, reach, g);
   int cnt = 0;
-  if (B.empty) return 0;
-  const double reach2 = reach * reach;
-  for (int z = B.lo[2]; z <= B.hi[2]; z++) {
-    const double gz = mp_gap(g, 2, z, q[2]);
-    for (int y = B.lo[1]; y <= B.hi[1]; y++) {
-      const double gy = mp_gap(g, 1, y, q[1]);
-      if (gy * gy + gz * gz > reach2) continue;
-      const int a = tstart[cell_index(g, B.lo[0], y, z)], b = tstart[cell_index(g, B.hi[0], y, z) + 1];
-      int i = a + ((lane - cnt) & (G - 1));
-      cnt += b - a;
-      for (; i < b; i += G) f(i);
-    }
-  }
+  ball_rows<1>(ball_block(q, reach, g), q, reach, tstart, g, [&](const int (&a)[1], const int (&b)[1]) {
+    int i = first_carried<G>(a[0], lane, cnt);
+    cnt += b[0] - a[0];
+    for (; i < b[0]; i += G) f(i);
+    return true;
+  });
   return cnt;
 }
 

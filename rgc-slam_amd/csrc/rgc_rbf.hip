@@ -41,6 +41,7 @@ k_rbf_cov6(const float4* __restrict__ P, const int* __restrict__ start, Grid g, 
   const bool live = i <= i1;
   const float4 q = P[live ? i : i1];
   // the run's box of cells: positions ascend with the cell index (x fastest, then y, then z), so the first and the last query bound it
+  // (not rgc_nn.h's ball_block: the box of a RUN of queries widened by `reach` whole cells, not the cells of one query's q -+ reach)
   const float4 qa = P[i0], qb = P[i1];
   int lo[3] = {cell_coord(qa.x, g) - g.minc[0], cell_coord(qa.y, g) - g.minc[1], cell_coord(qa.z, g) - g.minc[2]};
   int hi[3] = {cell_coord(qb.x, g) - g.minc[0], cell_coord(qb.y, g) - g.minc[1], cell_coord(qb.z, g) - g.minc[2]};

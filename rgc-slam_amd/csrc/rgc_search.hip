@@ -12,8 +12,8 @@
 //                       list is a compile-time constant of a fully unrolled loop.  The G lists are merged by k rounds of a group-wide minimum
 //                       (__shfl_xor); the winner pops its head.  A cube that does not prove the row complete GROWS AND THE LISTS START OVER:
 //                       nothing is carried from the smaller cube, so a candidate seen again cannot enter a list twice.  Every exit bounds the
-//                       K-TH entry: the row is complete when it is full and its k-th key lies provably inside the cube (cube_bound, with
-//                       nn_search's allowance 1 - 1e-5 for the fp32 key against the exact distance), or when the cube covers the grid (a row of
+//                       K-TH entry: the row is complete when it is full and its k-th key lies provably inside the cube (the rule of key_inside,
+//                       rgc_nn.h: cube_bound with the allowance for the fp32 key against the exact distance), or when the cube covers the grid (a row of
 //                       min(k, n) entries ends there).  bounded != 0: the member test key < r2 joins, and a cube whose faces are beyond `reach`
 //                       ends the search (nothing unscanned can be a member) -- radiusSearch with max_nn > 0; the rows come out sorted.
 // k_search_compact      the bounded rows (fixed width) into CSR
@@ -44,22 +44,17 @@ constexpr int SR_SMALL = 256;                  // rows up to this many members a
 int search_group() { return SR_GROUP; }
 int search_sort_window() { return kSearchSortWindow; }
 
-// the query's cell along axis a, relative to the grid, clamped in fp64 to [-1, dim]: a query far outside the grid must not overflow the int.
-// Inside the grid this is cell_coord - minc.  A clamped cell is a cell nearer the grid than the query's own: the cubes about it, clipped to
-// the grid, are cubes of cells all the same, and cube_bound measures their faces from the query's true coordinates
-__device__ __forceinline__ int sr_cell_rel(double x, const Grid& g, int a) {
-  const double u = floor(g.inv_res != 0.0 ? x * g.inv_res - 0.5 : x / g.res - 0.5) - (double)g.minc[a];
-  return (int)fmin(fmax(u, -1.0), (double)g.dim[a]);
-}
 __device__ __forceinline__ bool sr_finite(float x, float y, float z) { return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY; }
 
 // the read-out words (SearchStats): sums of a wave's group leaders, one integer atomic per wave and word
 __device__ __forceinline__ void sr_stats_add(unsigned long long* word, unsigned long long v) {
-#pragma unroll
-  for (int o = SR_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, SR_WAVE);
+  v = wave_sum_u64(v);
   if ((threadIdx.x & (SR_WAVE - 1)) == 0 && v) atomicAdd(word, v);
 }
 
+// (The ONE kernel that keeps the cube walk, the list and the next-radius loop written out instead of rgc_nn.h's cube_rows / list_insert / cube_next:
+// on those its KT = 32 instantiation measured 25 to 65 % slower in two separate visits -- EXPERIMENTS.md, "One grid walk" -- with the same registers
+// and the same instruction mix.  The rules are rgc_nn.h's; a change to one of them there has to be made here too.)
 template <int KT, int G>
 __global__ void __launch_bounds__(SR_T) k_search_knn(const float* __restrict__ Q, int qstride_f, int nq, const float4* __restrict__ TP, const int* __restrict__ tstart,
                                                      Grid g, int k, int bounded, float r2, double reach, int* __restrict__ out_idx, float* __restrict__ out_sq,
@@ -79,7 +74,7 @@ __global__ void __launch_bounds__(SR_T) k_search_knn(const float* __restrict__ Q
       int c[3], rmax = 0, r = 1;
 #pragma unroll
       for (int a = 0; a < 3; a++) {
-        c[a] = sr_cell_rel(q[a], g, a);
+        c[a] = cell_rel(q[a], g, a);
         rmax = max(rmax, max(c[a], g.dim[a] - 1 - c[a]));
         r = max(r, max(-c[a], c[a] - (g.dim[a] - 1)));  // (1 with the clamp: the first cube touches the grid)
       }
@@ -178,32 +173,17 @@ __global__ void __launch_bounds__(SR_T) k_search_compact(const int* __restrict__
   if (sq) sq[at] = row_sq[t];
 }
 
-// The part of the grid the ball of radius `reach` about the query can touch (mp_block of rgc_gicp_mp.hip, where reach = r (1 + 1e-5) is argued),
-// walked by a group of G lanes in steps of G candidates: f(i, valid) is called by the whole group together, i = sorted position, valid = i is
+// The rows of the ball of radius `reach` about the query (ball_block / ball_rows of rgc_nn.h, where reach = r (1 + 1e-5) is argued), walked by a
+// group of G lanes in steps of G candidates (the in-step rule): f(i, valid) is called by the whole group together, i = sorted position, valid = i is
 // inside its row range.  Returns the number of candidates.
 template <int G, typename F>
 __device__ __forceinline__ int sr_ball_walk(const double q[3], double reach, const int* __restrict__ tstart, const Grid& g, int lane, F&& f) {
-  int lo[3], hi[3];
-  bool empty = false;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    lo[a] = max(sr_cell_rel(q[a] - reach, g, a), 0);
-    hi[a] = min(sr_cell_rel(q[a] + reach, g, a), g.dim[a] - 1);
-    empty = empty || lo[a] > hi[a];
-  }
-  if (empty) return 0;
-  const double reach2 = reach * reach;
   int cnt = 0;
-  for (int z = lo[2]; z <= hi[2]; z++) {
-    const double wz = cell_wall(g, 2, z), gz = fmax(0.0, fmax(wz - q[2], q[2] - (wz + g.res)));
-    for (int y = lo[1]; y <= hi[1]; y++) {
-      const double wy = cell_wall(g, 1, y), gy = fmax(0.0, fmax(wy - q[1], q[1] - (wy + g.res)));
-      if (gy * gy + gz * gz > reach2) continue;  // the ball cannot reach this row
-      const int a = tstart[cell_index(g, lo[0], y, z)], b = tstart[cell_index(g, hi[0], y, z) + 1];
-      cnt += b - a;
-      for (int i0 = a; i0 < b; i0 += G) f(i0 + lane, i0 + lane < b);
-    }
-  }
+  ball_rows<1>(ball_block(q, reach, g), q, reach, tstart, g, [&](const int (&a)[1], const int (&b)[1]) {
+    cnt += b[0] - a[0];
+    for (int i0 = a[0]; i0 < b[0]; i0 += G) f(first_in_step(i0, lane), first_in_step(i0, lane) < b[0]);
+    return true;
+  });
   return cnt;
 }
 
