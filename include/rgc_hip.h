@@ -1205,6 +1205,92 @@ RGC_API int rgc_cluster_extract(rgc_ctx* ctx, const float* xyzc, int n, int stri
 RGC_API int rgc_cluster_get_info(rgc_ctx* ctx, rgc_cluster_info* info);
 RGC_API int rgc_cluster_set_cell(rgc_ctx* ctx, double cell);
 
+/* ---- RANSAC plane segmentation: pcl::SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE, SAC_RANSAC, setOptimizeCoefficients, and the
+ * pcl::ExtractIndices step behind it -- the ground removal between the outlier filters and rgc_cluster_extract ("what is left after the ground is
+ * removed").  (The reference's three nodes do not call the PCL class; its only plane fit is the front-end's ring-tabulated ground stage.)  The result is a
+ * pure function of the cloud, the parameters and the seed: no output bit depends on the launch shape, the batch size or the run. ----
+ *   rgc_plane_segment -- PCL's part restated FROM MEMORY [3P-memory] (PCL is not available to this project).
+ *   Record format and on_device are rgc_outlier_radius': x, y, z as floats at the head of each record of stride_bytes; on_device covers the cloud,
+ * out_xyzc and out_index; coeff, n_out, out_counts, samples and the info are always host memory; n <= 2^27.  No grid is built.  A solve in flight
+ * refuses the call (RGC_ERR_INVALID).
+ *   Hypothesis stream: stream position t = 0, 1, 2, ... yields a triple (i0, i1, i2) of distinct point indices.  With samples != NULL (host, 3 *
+ * n_samples ints) position t is samples[3t .. 3t + 2] and the stream ends at n_samples; an index outside [0, n) or two equal indices in a triple is
+ * RGC_ERR_INVALID before anything runs.  Otherwise (n_samples is ignored) the triple is rgc_plane_sample(seed, t, n) and the stream ends at 10 *
+ * max_iterations.  rgc_plane_sample is a counter-based generator, a pure host function (no context, no GPU: rgc_neighbor_offsets' precedent), in
+ * unsigned 64-bit arithmetic (mod 2^64):
+ *     mix(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *     r_j = mix(seed + (3 t + j + 1) * 0x9E3779B97F4A7C15), j = 0, 1, 2        (splitmix64 started at seed: its outputs 3t + 1 .. 3t + 3)
+ *     i0 = r_0 % n;   i1 = (i0 + 1 + r_1 % (n - 1)) % n;   i2 = the (r_2 % (n - 2))-th index, counting from 0 ascending, not in {i0, i1}
+ * -- distinct by construction, never a retry.  n < 3 or a NULL ijk: RGC_ERR_INVALID.
+ *   Model of a triple, in fp64 from the fp32 points p0, p1, p2, in this operation order, never FMA-contracted:
+ *     e1 = p1 - p0, e2 = p2 - p0;   c = (e1y e2z - e1z e2y,  e1z e2x - e1x e2z,  e1x e2y - e1y e2x);   u.v stands for (ux vx + uy vy) + uz vz
+ *     n = c / sqrt(c.c) (three divisions);   d = -(n.p0);   the stored model is ((float)nx, (float)ny, (float)nz, (float)d).
+ * A position is INVALID, and counts as skipped, iff !(c.c > 1e-12 * ((e1.e1) * (e2.e2))) (collinear or coincident), or n, d or a stored value is not
+ * finite, or -- model_type = RGC_PLANE_PERPENDICULAR [3P-memory: SampleConsensusModelPerpendicularPlane, the normal within eps_angle of the axis] --
+ * fabs(n.a) < cos(eps_angle) in fp64, a = axis / sqrt(axis.axis).
+ *   Score: point p is an inlier of a model (a, b, c, d) iff fabsf(((a x + b y) + c z) + d) < thr, STRICT, in fp32, never FMA-contracted, thr =
+ * (float)distance_threshold -- the library's strict rule.  The score of a position is its inlier count over the whole cloud.
+ *   Decision: the sequential loop over the stream [3P-memory: sample_consensus/impl/ransac.hpp].  best = -1, k = 1, iterations = 0, skipped = 0.  At each
+ * position: an invalid one adds to skipped only.  A valid one with count > best (strict: the earlier position wins a tie) becomes the best; then w =
+ * (double)best / n, q = min(max(1 - (w w) w, DBL_EPSILON), 1 - DBL_EPSILON), k = log(1 - probability) / log(q) in fp64 on the host; then ++iterations,
+ * and the loop stops if iterations >= k or iterations == max_iterations.  The loop also stops behind the stream's last position.  The positions are
+ * scored in batches and the loop is replayed over their counts: positions evaluated past the stop are ignored, so the result is the same for every
+ * batch size.  Deviations from PCL: PCL allows max_iterations + 1 iterations; PCL draws its samples with rand() (and redraws, up to a cap, a sample
+ * its isSampleGood rejects, which tests coordinate RATIOS where this tests the cross product); PCL's skipped-count limit is this stream end.
+ *   Inliers and refinement: the inliers are the points within the rule of the best model, in ascending input index.  optimize != 0 and at least 3
+ * inliers [3P-memory: SACSegmentation::segment, then optimizeModelCoefficients]: the centroid m = (sum p) / count and S = (sum (p - m)(p - m)^T) / count
+ * in fp64, each sum a fixed-order sum over the inliers in ascending input index (blocks of 256 consecutive indices, the library's fixed-order sums);
+ * the refined normal is the eigenvector of S's smallest eigenvalue by eig3_sym (cyclic Jacobi), negated if its fp64 dot product with the RANSAC
+ * normal is < 0; d = -(n.m); the result rounded to fp32; the inlier set re-selected over the whole cloud with the refined model.  coeff[4] are the
+ * fp32 values that selected the reported inliers, widened to double: the rule applied to coeff reproduces the reported set exactly.
+ *   Outputs: out_index / out_xyzc follow the outlier filters' rules -- ascending input index, 16-byte records, room for n, each nullable, entries
+ * behind *n_out untouched; negative != 0: they receive the complement, the ground-removed cloud that goes straight into rgc_cluster_extract on the
+ * device.  *n_out = points written (counted also when both are NULL).  out_counts (nullable, host): one int per stream position the decision used
+ * (positions 0 .. info.positions - 1): the count, -1 for an invalid position; untouched behind them.
+ *   Refusals: RGC_ERR_INVALID for n < 0, 0 < n < 3, n > 2^27, a threshold not finite or <= 0 (as a float too), probability outside (0, 1),
+ * max_iterations < 1, a model_type outside 0..1, and for RGC_PLANE_PERPENDICULAR eps_angle outside [0, pi / 2] or a zero or non-finite axis, a bad
+ * stride, n_samples < 0, a NULL context, params, cloud (n > 0), coeff or n_out -- nothing is written.  n = 0: RGC_OK, nothing found, zero
+ * coefficients.  A non-finite coordinate: RGC_ERR_NONFINITE, detected on the device by the first walk of the cloud, nothing written.  No valid
+ * position in the stream: RGC_OK with n_inliers = 0 and zero coefficients (PCL prints an error); there is no model then, so no point is an inlier and
+ * negative != 0 writes the whole cloud.
+ *   rgc_plane_set_batch: the positions scored per launch and host round trip (1 .. RGC_PLANE_MAX_BATCH; 0 = automatic: min(max_iterations, 64));
+ * NO OUTPUT BIT DEPENDS ON IT.  rgc_plane_get_info: the LAST rgc_plane_segment. */
+enum { RGC_PLANE_PLANE = 0, RGC_PLANE_PERPENDICULAR = 1 };
+#define RGC_PLANE_MAX_BATCH 1024
+typedef struct rgc_plane_params {
+  double distance_threshold;  /* PCL's default is 0: it must be set                            */
+  double probability;         /* 0.99                                                          */
+  double eps_angle;           /* radians; RGC_PLANE_PERPENDICULAR only                         */
+  double axis[3];             /* RGC_PLANE_PERPENDICULAR only                                  */
+  unsigned long long seed;    /* of the generated stream (no samples)                          */
+  int max_iterations;         /* 50                                                            */
+  int optimize;               /* 1: setOptimizeCoefficients                                    */
+  int model_type;             /* RGC_PLANE_PLANE                                               */
+  int reserved;
+} rgc_plane_params;
+typedef struct rgc_plane_info {
+  int n;                      /* points in                                                     */
+  int n_inliers;              /* inliers of the reported coefficients                          */
+  int iterations;             /* valid positions the decision counted                          */
+  int best_count;             /* the best position's count, before refinement (-1: none)       */
+  int batch;                  /* positions per launch the call used                            */
+  int launches;               /* scoring launches = host round trips of the decision           */
+  int refined;                /* 1: the coefficients are the refinement's                      */
+  int reserved;
+  long long positions;        /* stream positions the decision used (iterations + skipped)     */
+  long long skipped;          /* invalid positions among them                                  */
+  long long best_position;    /* -1: none                                                      */
+  double k;                   /* the final k                                                   */
+  double ransac_coeff[4];     /* the best model before refinement (fp32 values widened)        */
+} rgc_plane_info;
+RGC_API void rgc_default_plane_params(rgc_plane_params* p);
+RGC_API int rgc_plane_segment(rgc_ctx* ctx, const float* xyzc, int n, int stride_bytes, int on_device, const rgc_plane_params* params,
+                              const int* samples /* nullable, host, 3 * n_samples */, int n_samples, int negative, double* coeff /* 4, host */,
+                              float* out_xyzc /* nullable, n records */, int* out_index /* nullable, n */, int* out_counts /* nullable, host */, int* n_out);
+RGC_API int rgc_plane_get_info(rgc_ctx* ctx, rgc_plane_info* info);
+RGC_API int rgc_plane_set_batch(rgc_ctx* ctx, int batch);
+RGC_API int rgc_plane_sample(unsigned long long seed, unsigned long long t, int n, int* ijk /* 3 */);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

@@ -187,6 +187,22 @@ class ClusterInfo(C.Structure):
                 ("cells", C.c_longlong), ("candidates", C.c_longlong)]
 
 
+class PlaneParams(C.Structure):
+    """rgc_plane_params (rgc_default_plane_params)"""
+    _fields_ = [("distance_threshold", C.c_double), ("probability", C.c_double), ("eps_angle", C.c_double), ("axis", C.c_double * 3), ("seed", C.c_ulonglong),
+                ("max_iterations", C.c_int), ("optimize", C.c_int), ("model_type", C.c_int), ("reserved", C.c_int)]
+
+
+class PlaneInfo(C.Structure):
+    """rgc_plane_info: the last rgc_plane_segment (rgc_plane_get_info)"""
+    _fields_ = [("n", C.c_int), ("n_inliers", C.c_int), ("iterations", C.c_int), ("best_count", C.c_int), ("batch", C.c_int), ("launches", C.c_int), ("refined", C.c_int),
+                ("reserved", C.c_int), ("positions", C.c_longlong), ("skipped", C.c_longlong), ("best_position", C.c_longlong), ("k", C.c_double),
+                ("ransac_coeff", C.c_double * 4)]
+
+
+PLANE_PLANE, PLANE_PERPENDICULAR = 0, 1
+PLANE_MAX_BATCH = 1024
+
 NDT_P2D, NDT_D2D = 0, 1
 NDT_DIRECT27, NDT_DIRECT7, NDT_DIRECT1, NDT_DIRECT_RADIUS = 0, 1, 2, 3
 NDT_MAX_OFFSETS = 512
@@ -219,6 +235,7 @@ SYMBOLS = [
     "rgc_search_set_cloud", "rgc_search_clear", "rgc_search_get_info", "rgc_search_sort_window", "rgc_search_knn", "rgc_search_radius",
     "rgc_outlier_statistical", "rgc_outlier_radius", "rgc_outlier_get_info", "rgc_outlier_set_cell",
     "rgc_cluster_extract", "rgc_cluster_get_info", "rgc_cluster_set_cell",
+    "rgc_default_plane_params", "rgc_plane_segment", "rgc_plane_get_info", "rgc_plane_set_batch", "rgc_plane_sample",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
@@ -463,6 +480,12 @@ def load():
     L.rgc_cluster_extract.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, ip]
     L.rgc_cluster_get_info.argtypes = [vp, C.POINTER(ClusterInfo)]
     L.rgc_cluster_set_cell.argtypes = [vp, C.c_double]
+    L.rgc_default_plane_params.argtypes = [C.POINTER(PlaneParams)]
+    L.rgc_default_plane_params.restype = None
+    L.rgc_plane_segment.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PlaneParams), vp, C.c_int, C.c_int, vp, vp, vp, vp, ip]
+    L.rgc_plane_get_info.argtypes = [vp, C.POINTER(PlaneInfo)]
+    L.rgc_plane_set_batch.argtypes = [vp, C.c_int]
+    L.rgc_plane_sample.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_int, ip]
     L.rgc_profile_enable.argtypes = [vp, C.c_int]
     L.rgc_profile_select.argtypes = [vp, C.c_uint]
     L.rgc_profile_reset.argtypes = [vp]

@@ -1322,6 +1322,8 @@ void rgc_destroy(rgc_ctx* c) {
   release_cloud(c->cluster_cl);
   for (DevBuf* b : {&c->cluster_in, &c->cluster_work, &c->cluster_hist, &c->cluster_bs, &c->cluster_small}) release(*b);
   if (c->cluster_h) (void)hipHostFree(c->cluster_h);
+  for (DevBuf* b : {&c->plane_in, &c->plane_samples, &c->plane_bat, &c->plane_flag, &c->plane_off, &c->plane_bs, &c->plane_rows, &c->plane_out, &c->plane_idx, &c->plane_fit}) release(*b);
+  if (c->plane_h) (void)hipHostFree(c->plane_h);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);

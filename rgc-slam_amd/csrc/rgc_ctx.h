@@ -414,6 +414,13 @@ struct rgc_ctx {
   unsigned char* cluster_h = nullptr;
   rgc_cluster_info cluster_info{};
   double cluster_cell = 0.0;          // rgc_cluster_set_cell: 0 = the search index's automatic rule
+  // RANSAC plane segmentation (rgc_plane_*, rgc_api_plane.hip), behind everything else again: a host caller's staged records and samples; a batch's
+  // non-finite word, models and counts (one contiguous read-back) with their pinned mirror, which also holds the final rgck::PlaneFit and the number
+  // written; the flags, their scan and its block sums; the fixed-order sums' rows; a host caller's results
+  DevBuf plane_in, plane_samples, plane_bat, plane_flag, plane_off, plane_bs, plane_rows, plane_out, plane_idx, plane_fit;
+  unsigned char* plane_h = nullptr;
+  rgc_plane_info plane_info{};
+  int plane_batch = 0;                // rgc_plane_set_batch: 0 = automatic
 };
 
 namespace rgcapi {

@@ -98,6 +98,24 @@ class Preprocessor:
         offsets = offsets[:m.value + 1].copy()
         return labels, offsets, indices[:int(offsets[-1])].copy()
 
+    def planeSegmentation(self, xyzc, distance_threshold, max_iterations=50, probability=0.99, optimize=True, seed=0, negative=False, axis=None, eps_angle=0.0):
+        """pcl::SACSegmentation (SACMODEL_PLANE, or SACMODEL_PERPENDICULAR_PLANE when an axis is given; SAC_RANSAC) + pcl::ExtractIndices
+        (rgc_plane_segment): (records (m, 4) float32, indices (m,) int32, coefficients (4,) float64) -- the inliers in input order, or with
+        negative=True everything else (the ground-removed cloud)"""
+        a = np.ascontiguousarray(xyzc, dtype=np.float32)
+        n = a.shape[0]
+        p = _lib.PlaneParams()
+        self._L.rgc_default_plane_params(C.byref(p))
+        p.distance_threshold, p.max_iterations, p.probability, p.optimize, p.seed = float(distance_threshold), int(max_iterations), float(probability), int(bool(optimize)), int(seed)
+        if axis is not None:
+            p.model_type, p.eps_angle = _lib.PLANE_PERPENDICULAR, float(eps_angle)
+            p.axis[:] = [float(v) for v in axis]
+        out, idx, coeff = np.empty((n, 4), np.float32), np.empty(n, np.int32), np.zeros(4, np.float64)
+        m = C.c_int(0)
+        self._chk(self._L.rgc_plane_segment(self._h, a.ctypes.data, n, a.strides[0], 0, C.byref(p), None, 0, 1 if negative else 0, coeff.ctypes.data, out.ctypes.data,
+                                            idx.ctypes.data, None, C.byref(m)))
+        return out[:m.value].copy(), idx[:m.value].copy(), coeff
+
     def voxelGridRoute(self):
         """what the last voxelGridFilter on this object did (rgc_voxelgrid_route), as a dict of the rgc_vg_route fields"""
         r = _lib.VgRoute()
