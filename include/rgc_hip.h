@@ -1291,6 +1291,76 @@ RGC_API int rgc_plane_get_info(rgc_ctx* ctx, rgc_plane_info* info);
 RGC_API int rgc_plane_set_batch(rgc_ctx* ctx, int batch);
 RGC_API int rgc_plane_sample(unsigned long long seed, unsigned long long t, int n, int* ijk /* 3 */);
 
+/* ---- surface normal estimation: pcl::NormalEstimation, a unit normal and a curvature per point from the second moment of its neighbourhood -- the step a
+ * PCL pipeline runs beside the outlier filters, the ground removal and the clustering, and what region growing, SACMODEL_NORMAL_PLANE and point-to-plane
+ * terms start from.  (The reference's three nodes do not call the PCL class; rgc_get_target_covariances gives the registration target's normals only,
+ * with the solve's k, in fp64 and without a radius, a viewpoint, a curvature or a second cloud to search in.)  Nothing of a neighbour row reaches memory. ----
+ *   rgc_normal_estimate -- restated from PCL's features/impl/normal_3d.hpp and features/normal_3d.h FROM MEMORY [3P-memory] (PCL is not available to this
+ * project).
+ *   Argument rules, on_device and the record format are the outlier filters': x, y, z as floats at the head of each record of its cloud's stride; on_device
+ * covers BOTH clouds AND every output (all host memory or all device memory of the context's GPU); n and n_surface <= 2^27.  The call builds a grid of
+ * its own over the surface cloud (the search index's machinery and its automatic cell rule): a caller's search index, source and target are untouched.
+ * A solve in flight refuses the call (RGC_ERR_INVALID).  rgc_normal_set_cell fixes the grid's cell size for tests and tuning (0 = automatic; finite and
+ * >= 0); what depends on it is said under Moments.
+ *   Neighbourhood: the neighbours of query i = record i of xyzc come from `surface` (setSearchSurface), or from xyzc itself when surface is NULL
+ * (n_surface and surface_stride_bytes are then ignored).  Key: the fp32 ((dx dx + dy dy) + dz dz), never FMA-contracted, as everywhere in this library.
+ *   k route (params->k in 3..RGC_NORMAL_MAX_K, radius = 0; setKSearch): the min(k, n_surface) smallest entries in ascending (key, index) -- the search
+ * index's total order, so a row is unique whatever ties at its k-th place.  The point itself is a member when the cloud is its own surface, as
+ * nearestKSearch returns it.
+ *   Radius route (params->radius > 0, k = 0; setRadiusSearch): every surface point with key < r2, STRICT, r2 = (float)((double)radius * (double)radius) --
+ * rgc_search_radius' and rgc_outlier_radius' membership rule.  There is no cap on the members.
+ *   out_count[i] = m_i, the members used.
+ *   Moments: everything is fp64 about the query q.  d_j = (double)P_j - (double)q per axis, S1 = sum d_j, S2 = sum d_j d_j^T (each product rounded, then
+ * added), mean = S1 / m, centroid = q + mean, cov = S2 / m - mean mean^T: PCL's computeMeanAndCovarianceMatrix, which normalises by the count m and not
+ * by m - 1, with the origin shifted to the query.  k route: ONE chain in ascending rank -- no output bit depends on the grid, the cell size, the launch
+ * shape or the run.  Radius route: a fixed order that is a function of the grid and the query alone (every lane of the query's group adds its members in
+ * ascending position of the grid's sorted array, the lanes' chains are added in lane order; no floating-point atomic): the bits are identical from run to
+ * run and between host-pointer and device-pointer calls, the count m does not depend on the grid, THE LAST BITS OF THE MOMENTS -- and with them of every
+ * floating-point output of this route -- MAY DEPEND ON THE CELL SIZE.
+ *   Normal: the eigen-decomposition of cov by cyclic Jacobi (the library's eig3_sym); the normal is the column of the smallest eigenvalue, which is the
+ * LAST of a descending selection sort of the three eigenvalues, exact ties included (the rule of the registration target's normals), of unit length.
+ * curvature = (float)(|lambda_min| / trace), trace = (cov_xx + cov_yy) + cov_zz, when trace > 0, else 0.
+ *   Sign: flip = 1 (PCL, flipNormalTowardsViewpoint): the normal is negated when ((vx - qx) nx + (vy - qy) ny) + (vz - qz) nz < 0, evaluated in fp64 in this
+ * order, never contracted; an exact 0 keeps the sign the solver gave.  flip = 0: the component of largest magnitude is made positive, the first one
+ * on ties.  out_normal4[i] = the fp32 rounding of the fp64 normal, and the curvature.
+ *   Too few members: m < 3 gives four quiet NaNs in out_normal4 and NaN rows in out_cov6 / out_centroid, as PCL does (it clears is_dense); out_count still
+ * holds m.  *n_valid counts the other queries.
+ *   Refusals (RGC_ERR_INVALID, nothing written): both or neither of k / radius set, k outside 3..RGC_NORMAL_MAX_K, radius or r2 not finite or <= 0 (a
+ * negative k or radius is out of range), a non-finite viewpoint, flip not 0 / 1, a bad stride, a NULL cloud with n > 0, surface != NULL with n_surface
+ * <= 0, a cloud beyond 2^27 points, NULL params / n_valid / context, n < 0.  n = 0: RGC_OK with *n_valid = 0.  A non-finite coordinate in either cloud:
+ * RGC_ERR_NONFINITE, detected on the device before the estimate runs, nothing written.  RGC_ERR_GRID_TOO_LARGE as elsewhere.
+ *   Deviations from PCL: fp64 moments about the query where PCL sums fp32 unshifted (its result degrades with the distance from the origin; this one
+ * does not); the strict radius rule (key < r2) on every route; the tie rule of equal eigenvalues and the sign of an exact 0 (PCL leaves both to Eigen);
+ * the flip = 0 sign rule (PCL has none); m < 3 is NaN also on the k route when the surface holds fewer than three points.  Not built: the indices subset
+ * (setIndices), the OMP and integral-image variants, PointNormal output packing.
+ *   rgc_normal_get_info: the LAST rgc_normal_estimate. */
+#define RGC_NORMAL_MAX_K 32
+enum { RGC_NORMAL_ROUTE_K = 0, RGC_NORMAL_ROUTE_RADIUS = 1 };
+typedef struct rgc_normal_params {
+  int k;              /* setKSearch: 3 .. RGC_NORMAL_MAX_K selects the k route, 0 = not this route */
+  int flip;           /* 1 (PCL): flipNormalTowardsViewpoint; 0: the written sign rule above       */
+  double radius;      /* setRadiusSearch: > 0 selects the radius route; exactly one of k, radius   */
+  float viewpoint[3]; /* setViewPoint, default 0 0 0                                               */
+  int reserved;
+} rgc_normal_params;
+typedef struct rgc_normal_info {
+  int n, n_surface;      /* queries, surface points (= n when the cloud is its own surface)      */
+  int n_valid;           /* queries with three members or more                                   */
+  int route;             /* RGC_NORMAL_ROUTE_K / RGC_NORMAL_ROUTE_RADIUS                          */
+  double cell;           /* the grid the call used: its cell size                                */
+  long long cells;       /* ... and its cells                                                    */
+  long long candidates;  /* indexed points looked at over all queries                            */
+  int grown;             /* k route: queries whose cube of cells had to grow                     */
+  int reserved;
+} rgc_normal_info;
+RGC_API void rgc_default_normal_params(rgc_normal_params* p); /* k = 0, radius = 0, flip = 1, viewpoint 0 0 0: a caller must choose a route, as in PCL */
+RGC_API int rgc_normal_estimate(rgc_ctx* ctx, const float* xyzc, int n, int stride_bytes, const float* surface /* nullable */, int n_surface,
+                                int surface_stride_bytes, int on_device, const rgc_normal_params* params,
+                                float* out_normal4 /* nullable, n x (nx, ny, nz, curvature) */, double* out_cov6 /* nullable, n x {xx,xy,xz,yy,yz,zz} */,
+                                double* out_centroid /* nullable, n x 3 */, int* out_count /* nullable, n */, int* n_valid);
+RGC_API int rgc_normal_get_info(rgc_ctx* ctx, rgc_normal_info* info);
+RGC_API int rgc_normal_set_cell(rgc_ctx* ctx, double cell);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

@@ -203,6 +203,21 @@ class PlaneInfo(C.Structure):
 PLANE_PLANE, PLANE_PERPENDICULAR = 0, 1
 PLANE_MAX_BATCH = 1024
 
+
+class NormalParams(C.Structure):
+    """rgc_normal_params (rgc_default_normal_params)"""
+    _fields_ = [("k", C.c_int), ("flip", C.c_int), ("radius", C.c_double), ("viewpoint", C.c_float * 3), ("reserved", C.c_int)]
+
+
+class NormalInfo(C.Structure):
+    """rgc_normal_info: the last rgc_normal_estimate (rgc_normal_get_info)"""
+    _fields_ = [("n", C.c_int), ("n_surface", C.c_int), ("n_valid", C.c_int), ("route", C.c_int), ("cell", C.c_double), ("cells", C.c_longlong),
+                ("candidates", C.c_longlong), ("grown", C.c_int), ("reserved", C.c_int)]
+
+
+NORMAL_MAX_K = 32
+NORMAL_ROUTE_K, NORMAL_ROUTE_RADIUS = 0, 1
+
 NDT_P2D, NDT_D2D = 0, 1
 NDT_DIRECT27, NDT_DIRECT7, NDT_DIRECT1, NDT_DIRECT_RADIUS = 0, 1, 2, 3
 NDT_MAX_OFFSETS = 512
@@ -236,6 +251,7 @@ SYMBOLS = [
     "rgc_outlier_statistical", "rgc_outlier_radius", "rgc_outlier_get_info", "rgc_outlier_set_cell",
     "rgc_cluster_extract", "rgc_cluster_get_info", "rgc_cluster_set_cell",
     "rgc_default_plane_params", "rgc_plane_segment", "rgc_plane_get_info", "rgc_plane_set_batch", "rgc_plane_sample",
+    "rgc_default_normal_params", "rgc_normal_estimate", "rgc_normal_get_info", "rgc_normal_set_cell",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
@@ -486,6 +502,11 @@ def load():
     L.rgc_plane_get_info.argtypes = [vp, C.POINTER(PlaneInfo)]
     L.rgc_plane_set_batch.argtypes = [vp, C.c_int]
     L.rgc_plane_sample.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_int, ip]
+    L.rgc_default_normal_params.argtypes = [C.POINTER(NormalParams)]
+    L.rgc_default_normal_params.restype = None
+    L.rgc_normal_estimate.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(NormalParams), vp, vp, vp, vp, ip]
+    L.rgc_normal_get_info.argtypes = [vp, C.POINTER(NormalInfo)]
+    L.rgc_normal_set_cell.argtypes = [vp, C.c_double]
     L.rgc_profile_enable.argtypes = [vp, C.c_int]
     L.rgc_profile_select.argtypes = [vp, C.c_uint]
     L.rgc_profile_reset.argtypes = [vp]

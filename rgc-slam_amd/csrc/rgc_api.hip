@@ -1324,6 +1324,9 @@ void rgc_destroy(rgc_ctx* c) {
   if (c->cluster_h) (void)hipHostFree(c->cluster_h);
   for (DevBuf* b : {&c->plane_in, &c->plane_samples, &c->plane_bat, &c->plane_flag, &c->plane_off, &c->plane_bs, &c->plane_rows, &c->plane_out, &c->plane_idx, &c->plane_fit}) release(*b);
   if (c->plane_h) (void)hipHostFree(c->plane_h);
+  release_cloud(c->normal_cl);
+  for (DevBuf* b : {&c->normal_q, &c->normal_surf, &c->normal_n4, &c->normal_cov, &c->normal_cen, &c->normal_cnt, &c->normal_small}) release(*b);
+  if (c->normal_h) (void)hipHostFree(c->normal_h);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -421,6 +421,14 @@ struct rgc_ctx {
   unsigned char* plane_h = nullptr;
   rgc_plane_info plane_info{};
   int plane_batch = 0;                // rgc_plane_set_batch: 0 = automatic
+  // Surface normal estimation (rgc_normal_*, rgc_api_normals.hip), behind everything else again: the surface cloud's grid (a cloud of its own, the grid
+  // only); a host caller's staged queries and surface (12-byte records) and results; the grid's measurement, the queries' flag and rgck::NormalStats
+  // with their pinned mirror
+  Cloud normal_cl;
+  DevBuf normal_q, normal_surf, normal_n4, normal_cov, normal_cen, normal_cnt, normal_small;
+  unsigned char* normal_h = nullptr;
+  rgc_normal_info normal_info{};
+  double normal_cell = 0.0;           // rgc_normal_set_cell: 0 = the search index's automatic rule
 };
 
 namespace rgcapi {

@@ -483,6 +483,24 @@ int  cluster_radix_sort(hipStream_t s, int m, int bits, int* key[2], int* val[2]
 void cluster_rank(hipStream_t s, int n, int m, const int* key, const int* val, int* rank_at, int* sizes);
 // labels[i] (nullable) = flag_p[i] ? rank_at[comp[i]] : -1; pkey / pval (nullable together) at off_p[i]: that rank and i, for the kept points
 void cluster_labels(hipStream_t s, int n, const int* flag_p, const int* off_p, const int* comp, const int* rank_at, int* labels, int* pkey, int* pval);
+// ---- surface normal estimation (rgc_normal_*, rgc_normals.hip): a normal and a curvature per query from its neighbourhood in a surface cloud's grid ----
+// What a call reads back: the queries' non-finite flag and the read-out words as kNormalSlots partial sums a cache line apart, as OutlierStats': word 0
+// indexed points looked at, word 1 queries whose cube of cells grew (k route), word 2 valid queries (three members or more)
+constexpr int kNormalSlots = 32;
+struct NormalStats { int nonfinite; int pad[15]; unsigned long long words[kNormalSlots][8]; };
+struct NormalSign { float vx, vy, vz; int flip; };                  // the viewpoint and the sign rule (rgc_normal_params)
+struct NormalOut { float* n4; double* cov6; double* cen; int* cnt; };  // per query, each nullable: (nx, ny, nz, curvature), {xx,xy,xz,yy,yz,zz}, the centroid, the members
+int  normal_group();         // lanes per query of this build's k route ...
+int  normal_radius_group();  // ... and radius route
+int  normal_tier(int k);     // the list length k_nrm_knn runs k with: 4, 8, 16 or 32
+// *flag = 1 if a query has a non-finite coordinate (untouched otherwise)
+void normal_check(hipStream_t s, const float* Q, int qstride_f, int nq, int* flag);
+// the k route: the min(k, cl.n) smallest (key, original index) of every query; SP / sstride_f: the surface cloud's records at their ORIGINAL indices.
+// Q == nullptr (both routes): the queries are the cloud's own points (nq = cl.n), walked in the grid's sorted order, each written at its original index
+void normal_knn(hipStream_t s, const float* Q, int qstride_f, int nq, const float* SP, int sstride_f, const SortedCloud& cl, int k, const NormalSign& sg, const NormalOut& out,
+                NormalStats* st);
+// the radius route: every member with key < r2 (r: the radius r2 was made from)
+void normal_radius(hipStream_t s, const float* Q, int qstride_f, int nq, const SortedCloud& cl, float r2, double r, const NormalSign& sg, const NormalOut& out, NormalStats* st);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,

@@ -116,6 +116,21 @@ class Preprocessor:
                                             idx.ctypes.data, None, C.byref(m)))
         return out[:m.value].copy(), idx[:m.value].copy(), coeff
 
+    def normalEstimation(self, xyzc, k=0, radius=0.0, viewpoint=(0.0, 0.0, 0.0), surface=None, flip=True):
+        """pcl::NormalEstimation setKSearch(k) or setRadiusSearch(radius) + setViewPoint + setSearchSurface + compute (rgc_normal_estimate):
+        (n, 4) float32 rows nx, ny, nz, curvature at every point of xyzc, NaN where fewer than three neighbours were found"""
+        a = np.ascontiguousarray(xyzc, dtype=np.float32)
+        s = np.ascontiguousarray(surface, dtype=np.float32) if surface is not None else None
+        p = _lib.NormalParams()
+        self._L.rgc_default_normal_params(C.byref(p))
+        p.k, p.radius, p.flip = int(k), float(radius), int(bool(flip))
+        p.viewpoint[:] = [float(v) for v in viewpoint]
+        out = np.empty((a.shape[0], 4), np.float32)
+        m = C.c_int(0)
+        self._chk(self._L.rgc_normal_estimate(self._h, a.ctypes.data, a.shape[0], a.strides[0], s.ctypes.data if s is not None else None, s.shape[0] if s is not None else 0,
+                                              s.strides[0] if s is not None else 0, 0, C.byref(p), out.ctypes.data, None, None, None, C.byref(m)))
+        return out
+
     def voxelGridRoute(self):
         """what the last voxelGridFilter on this object did (rgc_voxelgrid_route), as a dict of the rgc_vg_route fields"""
         r = _lib.VgRoute()
