@@ -1361,6 +1361,75 @@ RGC_API int rgc_normal_estimate(rgc_ctx* ctx, const float* xyzc, int n, int stri
 RGC_API int rgc_normal_get_info(rgc_ctx* ctx, rgc_normal_info* info);
 RGC_API int rgc_normal_set_cell(rgc_ctx* ctx, double cell);
 
+/* ---- FPFH descriptors: pcl::FPFHEstimation, a 33-bin Fast Point Feature Histogram per point from the point's neighbourhood and the normals of everything
+ * within a radius -- the first consumer of rgc_normal_estimate's normals, the standard descriptor of global registration and place re-recognition, and on
+ * the loop-closure path (rgc_kf_detect_loop -> rgc_icp_align) what gives an initial guess that does not depend on the odometry's drift.  (The reference's
+ * three nodes do not call the PCL class.)  No neighbour row reaches memory and nothing is looped over on the host. ----
+ *   rgc_fpfh_estimate -- restated from PCL's features/impl/fpfh.hpp, features/fpfh.h and features/impl/pfh_tools.hpp (computePairFeatures) FROM MEMORY
+ * [3P-memory] (PCL is not available to this project).
+ *   Inputs: queries xyzc (n records) and an optional `surface` (setSearchSurface, n_surface records; NULL: xyzc is its own surface, n_surface and
+ * surface_stride_bytes are then ignored).  `normals`: one record of three floats (nx, ny, nz at the head of a record of normal_stride_bytes) per SURFACE
+ * point -- per xyzc point when surface is NULL.  With a 16-byte stride rgc_normal_estimate's out_normal4 is passed as it is, on the device.  Normals are
+ * used as given and are not re-normalised.  Argument rules, on_device and the record format are rgc_normal_estimate's: on_device covers every cloud, the
+ * normals AND every output (all host memory or all device memory of the context's GPU); n and n_surface <= 2^27.  The call builds a grid of its own over
+ * the surface cloud (the search index's machinery and its automatic cell rule): a caller's search index, source and target are untouched.
+ * A solve in flight refuses the call (RGC_ERR_INVALID).  rgc_fpfh_set_cell fixes the grid's cell size for tests and tuning (0 = automatic; finite and
+ * >= 0).
+ *   Rows: the radius route only.  params->radius > 0, r2 = (float)((double)radius * (double)radius).  Surface point j is a member of the row of point p
+ * when the library's fp32 key ((dx dx + dy dy) + dz dz), never FMA-contracted, is < r2, STRICT.  m_p is the row size; it includes p itself when p is a
+ * surface point.
+ *   Valid surface point: its three normal components are finite.  A non-finite COORDINATE in either cloud is RGC_ERR_NONFINITE, as elsewhere, detected
+ * on the device before anything is written; a non-finite NORMAL is data (rgc_normal_estimate emits NaN rows).
+ *   Pair term of a valid surface point s (normal a) with row member t (normal b), everything in fp64 from the fp32 inputs, every product rounded and
+ * then added, never contracted.  The pair is skipped if the fp32 key is 0 or t is not valid.  d = t - s per axis; f4 = sqrt((dx dx + dy dy) + dz dz);
+ * c1 = (ax dx + ay dy) + az dz, c2 likewise with b.  Swap iff |c1| < |c2|, strict: the decision is on the numerators, not on quotients or acos.  If
+ * swapped u = b, n2 = a, d = -d, f3 = -c2 / f4; otherwise u = a, n2 = b, f3 = c1 / f4.  v = d x u, vn = sqrt((vx vx + vy vy) + vz vz); the pair is
+ * skipped if vn == 0; v /= vn per component.  w = u x v.  f2 = (vx n2x + vy n2y) + vz n2z.  f1 = atan2((wx n2x + wy n2y) + wz n2z, (ux n2x + uy n2y) +
+ * uz n2z).  Bins, each clamped to 0..10: b1 = floor(11 ((f1 + pi) (1 / (2 pi)))), b2 = floor(11 ((f2 + 1) 0.5)), b3 = floor(11 ((f3 + 1) 0.5)).
+ *   SPFH of s: three blocks of 11 INTEGER counts of its non-skipped pairs (bins b1, 11 + b2, 22 + b3), plus m_s; skipped pairs still count in m_s.  As
+ * numbers SPFH_s[b] = count inc_s, inc_s = 100.0 / (double)(m_s - 1); every entry is zero when m_s <= 1 or s is not valid.  The counts are exact: no bit
+ * depends on the order, the grid, the cell size or the launch.  out_spfh (n_surface x 33, nullable) and out_spfh_count (n_surface, nullable; n rows when
+ * surface is NULL) read them out: out_spfh_count holds m_s, and -1 (with a row of zeros) where the SPFH was not computed.
+ *   Which SPFHs are computed: with surface == NULL every point's; with a separate surface only those of surface points that are a member of some
+ * query's row (a mark pass over the queries, a compaction, then the SPFH pass over the marked points).  info.n_spfh reports how many: a function of the
+ * inputs alone.
+ *   FPFH of query q: over its row members j with key > 0 and j valid, w_j = 1.0 / (double)key_j, F[b] = sum_j ((double)count_j[b] inc_j) w_j.  As in PCL
+ * the query's own SPFH is not part of its FPFH, and the query's own normal is never read.  Per block of 11, sum = F[0] + ... + F[10] in ascending bin;
+ * if sum != 0, out[b] = (float)(F[b] (100.0 / sum)), otherwise the block is 0.  Summation order: as on the normals' radius route a fixed function of
+ * the grid and the query alone -- ONE chain per bin, the members added in the order the query's walk over the grid meets them (layer by layer, row by
+ * row of cells, ascending position in the grid's sorted array); no floating-point atomic: the bits are identical from run to run and between
+ * host-pointer and device-pointer calls, the counts do not depend on the grid, THE LAST BITS OF out_fpfh MAY DEPEND ON THE CELL SIZE.
+ * out_count[i] = m_q.  m_q == 0 (possible only with a separate surface) gives 33 quiet NaNs; *n_valid counts the other queries.
+ *   Refusals (RGC_ERR_INVALID, nothing written): radius or r2 not finite or <= 0, a bad stride (a cloud's or the normals': < 12, not a multiple of 4 or
+ * > 4096), a NULL cloud or NULL normals with n > 0, surface != NULL with n_surface <= 0, a cloud beyond 2^27 points, NULL params / n_valid / context,
+ * n < 0.  n = 0: RGC_OK with *n_valid = 0.  RGC_ERR_GRID_TOO_LARGE as elsewhere.
+ *   Deviations from PCL: fp64 pair terms where PCL uses fp32; the swap test on the numerators where PCL compares acosf values; the strict radius rule
+ * (key < r2); invalid normals skipped pair by pair where PCL propagates NaN or requires a dense cloud.  Not built: the k route, the indices subset
+ * (setIndices), setNrSubdivisions other than 11 / 11 / 11, FPFHEstimationOMP, descriptor matching and the SAC-IA / prerejective alignment on top.
+ *   rgc_fpfh_get_info: the LAST rgc_fpfh_estimate. */
+#define RGC_FPFH_BINS 33
+typedef struct rgc_fpfh_params {
+  double radius;   /* setRadiusSearch: > 0; the default 0 is refused -- a caller must choose */
+  int reserved[2];
+} rgc_fpfh_params;
+typedef struct rgc_fpfh_info {
+  int n, n_surface;      /* queries, surface points (= n when the cloud is its own surface)      */
+  int n_valid;           /* queries with at least one member                                     */
+  int n_spfh;            /* surface points whose SPFH was computed                               */
+  double cell;           /* the grid the call used: its cell size                                */
+  long long cells;       /* ... and its cells                                                    */
+  long long pairs;       /* non-skipped pair terms                                               */
+  long long candidates;  /* indexed points looked at over all passes                             */
+  int reserved[2];
+} rgc_fpfh_info;
+RGC_API void rgc_default_fpfh_params(rgc_fpfh_params* p); /* radius = 0: a caller must choose */
+RGC_API int rgc_fpfh_estimate(rgc_ctx* ctx, const float* xyzc, int n, int stride_bytes, const float* surface /* nullable */, int n_surface,
+                              int surface_stride_bytes, const float* normals, int normal_stride_bytes, int on_device, const rgc_fpfh_params* params,
+                              float* out_fpfh /* nullable, n x 33 */, unsigned* out_spfh /* nullable, n_surface x 33 */,
+                              int* out_spfh_count /* nullable, n_surface */, int* out_count /* nullable, n */, int* n_valid);
+RGC_API int rgc_fpfh_get_info(rgc_ctx* ctx, rgc_fpfh_info* info);
+RGC_API int rgc_fpfh_set_cell(rgc_ctx* ctx, double cell);
+
 /* ---- in-library kernel timing with HIP events on the context's stream (bench.py roofline) ---- */
 enum {
   RGC_K_GRID = 0,      /* bbox + count + scan + scatter + rank/gather                         */

@@ -218,6 +218,20 @@ class NormalInfo(C.Structure):
 NORMAL_MAX_K = 32
 NORMAL_ROUTE_K, NORMAL_ROUTE_RADIUS = 0, 1
 
+
+class FpfhParams(C.Structure):
+    """rgc_fpfh_params (rgc_default_fpfh_params)"""
+    _fields_ = [("radius", C.c_double), ("reserved", C.c_int * 2)]
+
+
+class FpfhInfo(C.Structure):
+    """rgc_fpfh_info: the last rgc_fpfh_estimate (rgc_fpfh_get_info)"""
+    _fields_ = [("n", C.c_int), ("n_surface", C.c_int), ("n_valid", C.c_int), ("n_spfh", C.c_int), ("cell", C.c_double), ("cells", C.c_longlong),
+                ("pairs", C.c_longlong), ("candidates", C.c_longlong), ("reserved", C.c_int * 2)]
+
+
+FPFH_BINS = 33
+
 NDT_P2D, NDT_D2D = 0, 1
 NDT_DIRECT27, NDT_DIRECT7, NDT_DIRECT1, NDT_DIRECT_RADIUS = 0, 1, 2, 3
 NDT_MAX_OFFSETS = 512
@@ -252,6 +266,7 @@ SYMBOLS = [
     "rgc_cluster_extract", "rgc_cluster_get_info", "rgc_cluster_set_cell",
     "rgc_default_plane_params", "rgc_plane_segment", "rgc_plane_get_info", "rgc_plane_set_batch", "rgc_plane_sample",
     "rgc_default_normal_params", "rgc_normal_estimate", "rgc_normal_get_info", "rgc_normal_set_cell",
+    "rgc_default_fpfh_params", "rgc_fpfh_estimate", "rgc_fpfh_get_info", "rgc_fpfh_set_cell",
     "rgc_profile_enable", "rgc_profile_select", "rgc_profile_reset", "rgc_profile_get", "rgc_profile_name",
 ]
 
@@ -507,6 +522,11 @@ def load():
     L.rgc_normal_estimate.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(NormalParams), vp, vp, vp, vp, ip]
     L.rgc_normal_get_info.argtypes = [vp, C.POINTER(NormalInfo)]
     L.rgc_normal_set_cell.argtypes = [vp, C.c_double]
+    L.rgc_default_fpfh_params.argtypes = [C.POINTER(FpfhParams)]
+    L.rgc_default_fpfh_params.restype = None
+    L.rgc_fpfh_estimate.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.POINTER(FpfhParams), vp, vp, vp, vp, ip]
+    L.rgc_fpfh_get_info.argtypes = [vp, C.POINTER(FpfhInfo)]
+    L.rgc_fpfh_set_cell.argtypes = [vp, C.c_double]
     L.rgc_profile_enable.argtypes = [vp, C.c_int]
     L.rgc_profile_select.argtypes = [vp, C.c_uint]
     L.rgc_profile_reset.argtypes = [vp]

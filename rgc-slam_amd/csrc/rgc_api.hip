@@ -1327,6 +1327,9 @@ void rgc_destroy(rgc_ctx* c) {
   release_cloud(c->normal_cl);
   for (DevBuf* b : {&c->normal_q, &c->normal_surf, &c->normal_n4, &c->normal_cov, &c->normal_cen, &c->normal_cnt, &c->normal_small}) release(*b);
   if (c->normal_h) (void)hipHostFree(c->normal_h);
+  release_cloud(c->fpfh_cl);
+  for (DevBuf* b : {&c->fpfh_q, &c->fpfh_surf, &c->fpfh_nrm, &c->fpfh_n4, &c->fpfh_flag, &c->fpfh_off, &c->fpfh_bs, &c->fpfh_list, &c->fpfh_spfh, &c->fpfh_m, &c->fpfh_out, &c->fpfh_cnt, &c->fpfh_small}) release(*b);
+  if (c->fpfh_h) (void)hipHostFree(c->fpfh_h);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -18,8 +18,9 @@ static_assert(kStatsAt + sizeof(rgck::NormalStats) <= kSmallBytes, "the read-out
 rgck::NormalStats* dev_stats(rgc_ctx* c) { return reinterpret_cast<rgck::NormalStats*>(c->normal_small.as<unsigned char>() + kStatsAt); }
 const rgck::NormalStats* host_stats(rgc_ctx* c) { return reinterpret_cast<const rgck::NormalStats*>(c->normal_h + kStatsAt); }
 
-// a cloud on the device: the caller's pointer, or a host caller's records packed to 12 bytes in `stage`
-int stage_cloud(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, DevBuf& stage, const char* what, const float** d, int* stride_f) {
+}  // namespace
+
+int rgcapi::stage_cloud(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, DevBuf& stage, const char* what, const float** d, int* stride_f) {
   int rc;
   if (on_device) {
     if ((rc = check_device_range(c, p, (size_t)n * stride_bytes - (stride_bytes - 12), what))) return rc;
@@ -33,24 +34,6 @@ int stage_cloud(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_devi
   *stride_f = 3;
   return RGC_OK;
 }
-
-// where an output goes on the device: the caller's buffer, or scratch for a host caller; nullptr when it is not asked for
-template <class T>
-int place_output(rgc_ctx* c, T* user, size_t bytes, int on_device, DevBuf& scratch, const char* what, T** d) {
-  *d = nullptr;
-  if (!user) return RGC_OK;
-  int rc;
-  if (on_device) {
-    if ((rc = check_device_range(c, user, bytes, what))) return rc;
-    *d = user;
-    return RGC_OK;
-  }
-  if ((rc = ensure(c, scratch, bytes))) return rc;
-  *d = scratch.as<T>();
-  return RGC_OK;
-}
-
-}  // namespace
 
 extern "C" {
 

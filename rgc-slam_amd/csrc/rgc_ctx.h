@@ -429,6 +429,15 @@ struct rgc_ctx {
   unsigned char* normal_h = nullptr;
   rgc_normal_info normal_info{};
   double normal_cell = 0.0;           // rgc_normal_set_cell: 0 = the search index's automatic rule
+  // FPFH descriptors (rgc_fpfh_*, rgc_api_fpfh.hip), behind everything else again: the surface cloud's grid (a cloud of its own, the grid only); a host
+  // caller's staged queries, surface and normals (12-byte records); the normals as float4 with their validity in w; the marks of a separate surface,
+  // their scan, its block sums and the list of marked sorted positions; the SPFH counts and row sizes (scratch when the caller does not ask for them), a
+  // host caller's descriptors and counts; the grid's measurement, the queries' flag and rgck::FpfhStats with their pinned mirror
+  Cloud fpfh_cl;
+  DevBuf fpfh_q, fpfh_surf, fpfh_nrm, fpfh_n4, fpfh_flag, fpfh_off, fpfh_bs, fpfh_list, fpfh_spfh, fpfh_m, fpfh_out, fpfh_cnt, fpfh_small;
+  unsigned char* fpfh_h = nullptr;
+  rgc_fpfh_info fpfh_info{};
+  double fpfh_cell = 0.0;             // rgc_fpfh_set_cell: 0 = the search index's automatic rule
 };
 
 namespace rgcapi {
@@ -497,6 +506,25 @@ void host_eig3_sym(const double S[6], double ev[3], double V[9]);  // Jacobi; ei
 // (RGC_ERR_GRID_TOO_LARGE beyond max_cells); 0: chosen by the rule include/rgc_hip.h states for rgc_search_set_cloud, and returned.  dsm / hsm: eight
 // scratch ints on the device / the host; who: the entry point, name / grid_name: the cloud, in the error messages.  RGC_ERR_NONFINITE before anything is indexed
 int build_search_grid(rgc_ctx* c, Cloud& cl, double* cell, int* dsm, int* hsm, const char* who, const char* name, const char* grid_name);
+
+// ---- rgc_api_normals.hip: what the feature estimators (normals, FPFH) share ----
+// a cloud on the device: the caller's pointer, or a host caller's records packed to 12 bytes in `stage`
+int stage_cloud(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, DevBuf& stage, const char* what, const float** d, int* stride_f);
+// where an output goes on the device: the caller's buffer, or scratch for a host caller; nullptr when it is not asked for
+template <class T>
+int place_output(rgc_ctx* c, T* user, size_t bytes, int on_device, DevBuf& scratch, const char* what, T** d) {
+  *d = nullptr;
+  if (!user) return RGC_OK;
+  int rc;
+  if (on_device) {
+    if ((rc = check_device_range(c, user, bytes, what))) return rc;
+    *d = user;
+    return RGC_OK;
+  }
+  if ((rc = ensure(c, scratch, bytes))) return rc;
+  *d = scratch.as<T>();
+  return RGC_OK;
+}
 
 // ---- rgc_api_lsq.hip: the LM driver of every registration method ----
 // A registration problem as the driver sees it.  Either linearize + error (the driver makes the first try of an outer iteration itself, on

@@ -501,6 +501,25 @@ void normal_knn(hipStream_t s, const float* Q, int qstride_f, int nq, const floa
                 NormalStats* st);
 // the radius route: every member with key < r2 (r: the radius r2 was made from)
 void normal_radius(hipStream_t s, const float* Q, int qstride_f, int nq, const SortedCloud& cl, float r2, double r, const NormalSign& sg, const NormalOut& out, NormalStats* st);
+// ---- FPFH descriptors (rgc_fpfh_*, rgc_fpfh.hip): 33 bins per query from the normals of a surface cloud's balls, in two passes over its grid ----
+// What a call reads back, as NormalStats: word 0 indexed points looked at (every pass), word 1 non-skipped pair terms, word 2 queries with a member
+constexpr int kFpfhSlots = 32;
+constexpr int kFpfhBins = 33;
+struct FpfhStats { int nonfinite; int pad[15]; unsigned long long words[kFpfhSlots][8]; };
+// *flag = 1 if a query has a non-finite coordinate (Q nullable: the cloud is its own surface, its grid build checks it); N4[i] = the normal of surface
+// point i with w = 1 where its three components are finite, else 0
+void fpfh_check(hipStream_t s, const float* Q, int qstride_f, int nq, const float* N, int nstride_f, int ns, float4* N4, int* flag);
+// flag[sorted position] = 1 for every member (key < r2) of some query's ball; flag[0 .. cl.n] was zeroed by the caller
+void fpfh_mark(hipStream_t s, const float* Q, int qstride_f, int nq, const SortedCloud& cl, float r2, double r, int* flag, FpfhStats* st);
+// list[off[i]] = i for every flagged sorted position i (off = the exclusive scan of flag)
+void fpfh_list(hipStream_t s, const int* flag, const int* off, int ns, int* list);
+// the SPFH counts (33 per point) and row sizes of the listed sorted positions (list == nullptr: of every point), written at the points' ORIGINAL indices;
+// n_list: the list's length, on the device
+void fpfh_spfh(hipStream_t s, const SortedCloud& cl, const int* list, const int* n_list, const float4* N4, float r2, double r, unsigned* spfh, int* m, FpfhStats* st);
+// the descriptors (out, nullable: 33 floats per query) and row sizes (cnt, nullable).  Q == nullptr: the queries are the cloud's own points, walked in
+// the grid's sorted order, each written at its original index
+void fpfh_combine(hipStream_t s, const float* Q, int qstride_f, int nq, const SortedCloud& cl, const unsigned* spfh, const int* m, float r2, double r, float* out, int* cnt,
+                  FpfhStats* st);
 void vg_bbox(hipStream_t s, const float* in, int stride_f, int n, float inv, int* mm6, int* flags);
 // sparse leaf grids: counting sort over (y, z) rows, rank by (leaf x, index) inside a row -- the whole filter as one chain of launches.
 // edge > 0: g is a box kept from an earlier cloud (see rgc_pre.hip).  res[0] <- flags of this run (1 non-finite point, 2 point outside g,

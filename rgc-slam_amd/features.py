@@ -10,7 +10,9 @@ include/rgc_hip.h (which state the neighbourhood, the moments, the normal, the s
     ne.getCovariances(); ne.getCentroids(); ne.getCounts(); ne.info()   # of the last compute(with_moments=True): (n, 6) / (n, 3) float64, (n,) int32
 
 A device cloud is used where it lies; its results are computed into device memory and downloaded.  Results are numpy arrays.  Nothing is computed on
-the CPU; without librgc_hip.so / an MI355X this raises."""
+the CPU; without librgc_hip.so / an MI355X this raises.
+
+FPFHEstimation (pcl::FPFHEstimation, the rgc_fpfh_* entry points) is the consumer of those normals; its own docstring shows the calls."""
 from __future__ import annotations
 
 import ctypes as C
@@ -147,4 +149,112 @@ class NormalEstimation(KdTree):
 
     def getValidCount(self):
         """queries with three members or more, of the last compute()"""
+        return self._n_valid
+
+
+class FPFHEstimation(KdTree):
+    """pcl::FPFHEstimation with PCL's member names, behind the rgc_fpfh_* entry points of include/rgc_hip.h (which state the rows, the pair term, the
+    SPFH counts, the weighting, the normalisation and the refusals).  The context, the cloud forms and the device staging are search.KdTree's.
+
+        fe = FPFHEstimation(device=0)                      # or (owner=other): in the context of another object of this package
+        fe.setInputCloud(keypoints)                        # (n, >=3) float32, a keyframes.DeviceCloud, or a tensor on the context's GPU
+        fe.setSearchSurface(dense)                         # optional: the cloud the neighbours come from (None: the input cloud itself)
+        fe.setInputNormals(normals)                        # (n_surface, >=3) float32 in any of those forms: NormalEstimation.compute()'s rows as they are
+        fe.setRadiusSearch(0.5)
+        fpfh = fe.compute()                                # (n, 33) float32; NaN rows where a query has no member
+        fe.getSPFH(); fe.getCounts(); fe.getValidCount(); fe.info()   # of the last compute(with_spfh=True): ((n_surface, 33) uint32, (n_surface,) int32), (n,) int32"""
+
+    def __init__(self, device: int = 0, owner=None):
+        super().__init__(device, owner)
+        self._init_params()
+
+    def _init_params(self):
+        self._cloud = self._surface = self._normals = None
+        self._radius = 0.0                                   # a caller must choose
+        self._spfh = self._spfh_cnt = self._cnt = self._n_valid = None
+
+    def setInputCloud(self, points):
+        self._cloud = points
+        self._spfh = self._spfh_cnt = self._cnt = self._n_valid = None
+
+    def setSearchSurface(self, points):
+        self._surface = points
+
+    def setInputNormals(self, normals):
+        """one row per SURFACE point (per input point without a search surface): nx, ny, nz first; used as given"""
+        self._normals = normals
+
+    def setRadiusSearch(self, radius: float):
+        radius = float(radius)
+        with np.errstate(over="ignore"):
+            r2 = np.float32(radius * radius) if np.isfinite(radius) else np.float32(np.inf)
+        if not (np.isfinite(radius) and radius > 0 and np.isfinite(r2) and r2 > 0):
+            raise RgcError(_lib.ERR_INVALID, "the radius must be finite and > 0, float32(r r) finite and > 0")
+        self._radius = radius
+
+    def getRadiusSearch(self) -> float:
+        return self._radius
+
+    def setCell(self, cell: float):
+        """the grid's cell size, for tests and tuning (0 = automatic) (rgc_fpfh_set_cell)"""
+        self._chk(self._L.rgc_fpfh_set_cell(self._h, float(cell)))
+
+    def info(self) -> dict:
+        s = _lib.FpfhInfo()
+        self._chk(self._L.rgc_fpfh_get_info(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in _lib.FpfhInfo._fields_ if k != "reserved"}
+
+    def compute(self, with_spfh: bool = False):
+        """(n, 33) float32 descriptors of every input point; with_spfh: the first pass' counts and row sizes are kept too (getSPFH)"""
+        if self._cloud is None:
+            raise RgcError(_lib.ERR_NO_INPUT, "no input cloud (setInputCloud)")
+        if self._normals is None:
+            raise RgcError(_lib.ERR_NO_INPUT, "no normals (setInputNormals)")
+        if self._radius == 0.0:
+            raise RgcError(_lib.ERR_INVALID, "no radius (setRadiusSearch)")
+        p, n, stride, dev, _keep = self._points(self._cloud)
+        sp, ns, sstride, _keep2 = None, 0, 0, None
+        if self._surface is not None:
+            sp, ns, sstride, sdev, _keep2 = self._points(self._surface)
+            if sdev != dev:
+                raise RgcError(_lib.ERR_INVALID, "the input cloud, the search surface and the normals are all host memory or all device memory")
+        npt, nn, nstride, ndev, _keep3 = self._points(self._normals)
+        rows = ns if self._surface is not None else n
+        if ndev != dev or nn != rows:
+            raise RgcError(_lib.ERR_INVALID, "one normal per surface point, in the memory the clouds are in")
+        prm = _lib.FpfhParams()
+        prm.radius = self._radius
+        out = np.empty((n, _lib.FPFH_BINS), np.float32)
+        cnt = np.empty(n, np.int32)
+        spfh = np.empty((rows, _lib.FPFH_BINS), np.uint32) if with_spfh else None
+        scnt = np.empty(rows, np.int32) if with_spfh else None
+        valid = C.c_int(0)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        hosts = (out, spfh, scnt, cnt)
+        if not dev:
+            self._chk(self._L.rgc_fpfh_estimate(self._h, p, n, stride, sp, ns, sstride, npt, nstride, 0, C.byref(prm), *[ptr(a) for a in hosts], C.byref(valid)))
+        else:
+            devs = [self._dev(a.nbytes) if a is not None else None for a in hosts]
+            try:
+                self._chk(self._L.rgc_fpfh_estimate(self._h, p, n, stride, sp, ns, sstride, npt, nstride, 1, C.byref(prm), *devs, C.byref(valid)))
+                for a, d in zip(hosts, devs):
+                    if a is not None:
+                        self._down(a, d)
+            finally:
+                for d in devs:
+                    if d is not None:
+                        self._L.rgc_device_free(self._h, d)
+        self._spfh, self._spfh_cnt, self._cnt, self._n_valid = spfh, scnt, cnt, valid.value
+        return out
+
+    def getSPFH(self):
+        """((n_surface, 33) uint32 counts, (n_surface,) int32 row sizes, -1 where not computed) of the last compute(with_spfh=True), else (None, None)"""
+        return self._spfh, self._spfh_cnt
+
+    def getCounts(self):
+        """(n,) int32: the row size of every query, of the last compute()"""
+        return self._cnt
+
+    def getValidCount(self):
+        """queries with at least one member, of the last compute()"""
         return self._n_valid

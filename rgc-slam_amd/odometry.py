@@ -131,6 +131,21 @@ class Preprocessor:
                                               s.strides[0] if s is not None else 0, 0, C.byref(p), out.ctypes.data, None, None, None, C.byref(m)))
         return out
 
+    def fpfhEstimation(self, xyzc, normals, radius, surface=None):
+        """pcl::FPFHEstimation setInputNormals + setRadiusSearch(radius) + setSearchSurface + compute (rgc_fpfh_estimate): (n, 33) float32 descriptors of
+        every point of xyzc from the normals of the surface cloud (of xyzc itself without one), NaN rows where a query has no member"""
+        a = np.ascontiguousarray(xyzc, dtype=np.float32)
+        s = np.ascontiguousarray(surface, dtype=np.float32) if surface is not None else None
+        nr = np.ascontiguousarray(normals, dtype=np.float32)
+        p = _lib.FpfhParams()
+        self._L.rgc_default_fpfh_params(C.byref(p))
+        p.radius = float(radius)
+        out = np.empty((a.shape[0], _lib.FPFH_BINS), np.float32)
+        m = C.c_int(0)
+        self._chk(self._L.rgc_fpfh_estimate(self._h, a.ctypes.data, a.shape[0], a.strides[0], s.ctypes.data if s is not None else None, s.shape[0] if s is not None else 0,
+                                            s.strides[0] if s is not None else 0, nr.ctypes.data, nr.strides[0], 0, C.byref(p), out.ctypes.data, None, None, None, C.byref(m)))
+        return out
+
     def voxelGridRoute(self):
         """what the last voxelGridFilter on this object did (rgc_voxelgrid_route), as a dict of the rgc_vg_route fields"""
         r = _lib.VgRoute()
