@@ -180,7 +180,16 @@ RGC_API const char* rgc_version(void);
  * -- the one host round trip of these calls; results are unaffected.  A cloud that does not fit is prepared again, transparently,
  * when the first call that consumes it finds out; by the same token RGC_ERR_NONFINITE / RGC_ERR_GRID_TOO_LARGE for such a cloud
  * may be returned by that consuming call (rgc_align, rgc_linearize, a getter ...) instead of by rgc_set_*.  RGC_SPEC_GRID=0 in
- * the environment restores the immediate check. */
+ * the environment restores the immediate check.
+ * What is a function of the clouds alone, and what is not: the neighbour sets, the target's covariances and the voxel map are -- bit for bit, on
+ * every route and on any context.  The SOURCE's kNN grid is steered by the scans the context has seen: its cell size follows how crowded the
+ * previous scan's cells were (it starts at the voxel size, and rgc_set_params with another voxel_res puts it back there), and its box is the one
+ * kept from the previous scans, widened, while the next scan fits it.  The four-lane search sums a point's moments in that grid's order, the box
+ * decides which far-field points go to the cooperative kernel instead (rgc_stats::deferred_source), which sums them in another, and a
+ * linearisation's sums run over the scan in the grid's order: THE LAST BITS OF THE SOURCE'S COVARIANCES -- and of cost, H, b and final_H -- MAY
+ * DEPEND ON THE SCANS THE CONTEXT HAS SEEN BEFORE (measured: one ulp in 4 of 5729 rows behind another sweep).  They are identical from run to
+ * run for the same sequence of calls, and between host and device inputs.  (tests/one_context_ops.py puts the cell size and the box back
+ * before every registration it compares with a context of its own: route().) */
 RGC_API int rgc_set_target(rgc_ctx* ctx, const float* xyz, int n, int stride_bytes);
 RGC_API int rgc_set_source(rgc_ctx* ctx, const float* xyz, int n, int stride_bytes);
 /* same, but xyz is DEVICE memory on the context's device (cloud already resident in HBM).
@@ -219,7 +228,12 @@ RGC_API int rgc_align(rgc_ctx* ctx, const float guess[16], float final_T[16], do
  * BETWEEN the two halves the context refuses (RGC_ERR_INVALID, "a solve is in flight") everything that would touch the solve's inputs:
  * new clouds, clearing or swapping them, another begin or a blocking rgc_align, the settings that re-route a cloud, the getters,
  * rgc_map_commit (but for the no-op commit of an unchanged map).  The same on the general covariance route, where rgc_align_begin runs the
- * solve at once and keeps its result for rgc_align_end. */
+ * solve at once and keeps its result for rgc_align_end.
+ * Everything else RUNS with a solve in flight and leaves the solve's result what it would have been: the front-end, the leaf filter (whole and
+ * in its two halves), rgc_uniform_sampling, rgc_deskew, rgc_transform_cloud, the PointCloud2 (un)packing, rgc_icp_align*, the rgc_mapreg_* calls,
+ * rgc_map_reset / insert / evict / rebase of a map the solve's target is not bound to, and the blocks that say so themselves below (the keyframe
+ * store, the pose graph, NDT); the search index and the features built on its walk (outlier filters, clustering, plane, normals, FPFH) are
+ * refused, as their own blocks say.  tests/one_context_ops.py holds one column of this per operation. */
 RGC_API int rgc_align_begin(rgc_ctx* ctx, const float guess[16], int want_fitness);
 RGC_API int rgc_align_end(rgc_ctx* ctx, float final_T[16], double final_H[36], double* fitness, int* iterations, int* converged,
                           int* lm_failed);
