@@ -104,12 +104,13 @@ static void release_cloud(Cloud& cl) {
   for (DevBuf* b : shared_bufs(cl)) release(*b);
   for (DevBuf* b : {&cl.need, &cl.qlist, &cl.cell_list, &cl.seed, &cl.nbr, &cl.rank_of, &cl.pos_of, &cl.qrank, &cl.map_copy, &cl.todo, &cl.cache_small}) release(*b);
 }
-// a registration method's record (rgc_ctx.h): its device buffers and its pinned mirrors
+// a record of a registration method or a cloud operation (rgc_ctx.h): its device buffers, its pinned mirrors, its clouds
 template <class Record>
 static void release_record(Record& r) {
   for (DevBuf* b : r.bufs()) release(*b);
   for (void* p : r.pinned())
     if (p) (void)hipHostFree(p);
+  for (Cloud* cl : r.clouds()) release_cloud(*cl);
 }
 
 // ---- profiling regions (HIP events on the context's stream) ----
@@ -1305,31 +1306,17 @@ void rgc_destroy(rgc_ctx* c) {
   if (c->kf_h_table) (void)hipHostFree(c->kf_h_table);
   for (DevBuf* b : {&c->pgo_i, &c->pgo_d, &c->pgo_M}) release(*b);
   release(c->vr_offs);
-  release_cloud(c->ndt.cl[0]);
-  release_cloud(c->ndt.cl[1]);
   release_record(c->ndt);
   release_record(c->gicp_sums);
   release_record(c->gicp);
   release_record(c->gicp_st);
   release_record(c->gicp_mp);
-  release_cloud(c->search_cl);
-  for (DevBuf* b : {&c->search_q, &c->search_cnt, &c->search_off, &c->search_bs, &c->search_row_idx, &c->search_row_sq, &c->search_ent, &c->search_tmp, &c->search_idx,
-                    &c->search_sq, &c->search_small}) release(*b);
-  if (c->search_h) (void)hipHostFree(c->search_h);
-  release_cloud(c->filter_cl);
-  for (DevBuf* b : {&c->filter_in, &c->filter_val, &c->filter_flag, &c->filter_off, &c->filter_bs, &c->filter_partials, &c->filter_out, &c->filter_idx, &c->filter_small}) release(*b);
-  if (c->filter_h) (void)hipHostFree(c->filter_h);
-  release_cloud(c->cluster_cl);
-  for (DevBuf* b : {&c->cluster_in, &c->cluster_work, &c->cluster_hist, &c->cluster_bs, &c->cluster_small}) release(*b);
-  if (c->cluster_h) (void)hipHostFree(c->cluster_h);
-  for (DevBuf* b : {&c->plane_in, &c->plane_samples, &c->plane_bat, &c->plane_flag, &c->plane_off, &c->plane_bs, &c->plane_rows, &c->plane_out, &c->plane_idx, &c->plane_fit}) release(*b);
-  if (c->plane_h) (void)hipHostFree(c->plane_h);
-  release_cloud(c->normal_cl);
-  for (DevBuf* b : {&c->normal_q, &c->normal_surf, &c->normal_n4, &c->normal_cov, &c->normal_cen, &c->normal_cnt, &c->normal_small}) release(*b);
-  if (c->normal_h) (void)hipHostFree(c->normal_h);
-  release_cloud(c->fpfh_cl);
-  for (DevBuf* b : {&c->fpfh_q, &c->fpfh_surf, &c->fpfh_nrm, &c->fpfh_n4, &c->fpfh_flag, &c->fpfh_off, &c->fpfh_bs, &c->fpfh_list, &c->fpfh_spfh, &c->fpfh_m, &c->fpfh_out, &c->fpfh_cnt, &c->fpfh_small}) release(*b);
-  if (c->fpfh_h) (void)hipHostFree(c->fpfh_h);
+  release_record(c->search);
+  release_record(c->outlier);
+  release_record(c->cluster);
+  release_record(c->plane);
+  release_record(c->normal);
+  release_record(c->fpfh);
   if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);

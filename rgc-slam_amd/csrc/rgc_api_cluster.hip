@@ -1,7 +1,7 @@
 // rgc_api_cluster.hip -- host side of Euclidean cluster extraction (rgc_cluster_*): pcl::EuclideanClusterExtraction of a cloud on a grid of the call's own
-// (rgc_ctx::cluster_cl, built by build_search_grid like the search index's and the outlier filters': the same automatic cell rule).  The kernels are
+// (rgcapi::ClusterRecord, built by index_cloud like the search index's and the outlier filters': the same automatic cell rule).  The kernels are
 // rgc_cluster.hip's; the semantics are stated in include/rgc_hip.h.
-//   Host round trips of a call: the grid build's own (build_search_grid measures the box before it sizes the grid, as for every cloud searched by rows);
+//   Host round trips of a call: index_cloud's grid build's own (it measures the box before it sizes the grid, as for every cloud searched by rows);
 // then ONE mid-chain read-back -- the error word, the read-out words, the number of kept clusters and of clustered points: the host needs them to size
 // the two sorts' passes -- and the wait at the end (with a host caller's downloads in front of it).  What can refuse a call (the arguments, the grid
 // build's flag word, the error word) does so before anything is written to the caller.
@@ -12,12 +12,8 @@ using namespace rgcapi;
 namespace {
 
 constexpr int kClusterMaxPoints = 1 << 27;  // point_at's 32-bit byte offsets rely on it
-constexpr size_t kCountsAt = 32;            // rgc_ctx::cluster_small / cluster_h: the 8 ints of the grid's measurement, the two counts (the scans' last offsets) ...
-constexpr size_t kStatsAt = 64;             // ... and what the kernels post (rgck::ClusterStats)
-constexpr size_t kSmallBytes = 4096;
-static_assert(kStatsAt + sizeof(rgck::ClusterStats) <= kSmallBytes, "the read-out words fit");
 
-// the int arrays of a call, slices of rgc_ctx::cluster_work (a slice: n + 1 ints, rounded up to 16 bytes)
+// the int arrays of a call, slices of ClusterRecord::work (a slice: n + 1 ints, rounded up to 16 bytes)
 enum Slice {
   kParent = 0, kLead, kSize,     // the union-find and the census, on SORTED positions; dead behind cluster_assign: the sorts' first three arrays
   kComp, kCsize, kFlagP, kFlagL, kOffP, kOffL,  // at the ORIGINAL index
@@ -27,7 +23,7 @@ enum Slice {
   kSlices
 };
 
-rgck::ClusterStats* dev_stats(rgc_ctx* c) { return reinterpret_cast<rgck::ClusterStats*>(c->cluster_small.as<unsigned char>() + kStatsAt); }
+rgck::ClusterStats* dev_stats(rgc_ctx* c) { return stats<rgck::ClusterStats>(c->cluster.f); }  // (the frame's own words are the two counts: the scans' last offsets)
 int bit_length(unsigned v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
 
 }  // namespace
@@ -36,14 +32,12 @@ extern "C" {
 
 int rgc_cluster_set_cell(rgc_ctx* c, double cell) {
   if (!c) return RGC_ERR_INVALID;
-  if (!std::isfinite(cell) || cell < 0.0) return fail(c, RGC_ERR_INVALID, "rgc_cluster_set_cell: cell must be finite and >= 0");
-  c->cluster_cell = cell;
-  return RGC_OK;
+  return set_cell_of(c, &c->cluster.f.cell, cell, "rgc_cluster_set_cell");
 }
 
 int rgc_cluster_get_info(rgc_ctx* c, rgc_cluster_info* info) {
   if (!c || !info) return RGC_ERR_INVALID;
-  *info = c->cluster_info;
+  *info = c->cluster.info;
   return RGC_OK;
 }
 
@@ -62,50 +56,31 @@ int rgc_cluster_extract(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, 
   const size_t nn = (size_t)n;
   int rc;
   if (on_device) {
-    if (n && (rc = check_device_range(c, xyzc, nn * stride_bytes - (stride_bytes - 12), "input cloud"))) return rc;
+    if (n && (rc = check_device_range(c, xyzc, record_bytes(n, stride_bytes, false), "input cloud"))) return rc;
     if (labels && n && (rc = check_device_range(c, labels, sizeof(int) * nn, "labels"))) return rc;
     if (offsets && (rc = check_device_range(c, offsets, sizeof(int) * (nn + 1), "offsets"))) return rc;
     if (indices && n && (rc = check_device_range(c, indices, sizeof(int) * nn, "indices"))) return rc;
   }
   *n_clusters = 0;
-  c->cluster_info = rgc_cluster_info{};
-  if (n == 0) {
-    if (offsets && on_device) {
-      HIPCHK(c, hipMemsetAsync(offsets, 0, sizeof(int), s));
-      HIPCHK(c, hipStreamSynchronize(s));
-    } else if (offsets) {
-      offsets[0] = 0;
-    }
-    return RGC_OK;
-  }
-  if ((rc = ensure(c, c->cluster_small, kSmallBytes))) return rc;
-  if (!c->cluster_h) HIPCHK(c, hipHostMalloc((void**)&c->cluster_h, kSmallBytes, hipHostMallocDefault));
-  const float* d_in = xyzc;
-  if (!on_device) {
-    const size_t bytes = nn * stride_bytes - (stride_bytes - 12);
-    if ((rc = ensure(c, c->cluster_in, bytes))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->cluster_in.p, xyzc, bytes, hipMemcpyHostToDevice, s));
-    d_in = c->cluster_in.as<const float>();
-  }
+  c->cluster.info = rgc_cluster_info{};
+  if (n == 0) return write_empty_offsets(c, offsets, on_device);
+  rgcapi::ClusterRecord& r = c->cluster;
+  if ((rc = frame_open(c, r.f))) return rc;
+  const float* d_in = xyzc;  // (a device caller's cloud was looked up above)
+  if (!on_device && (rc = stage_records(c, xyzc, n, stride_bytes, 0, false, r.in, "input cloud", &d_in))) return rc;
   const size_t slice = (nn + 1 + 3) & ~(size_t)3;
   const int tiles = rgck::cluster_radix_tiles(n);
   const size_t hist_n = (size_t)rgck::kClusterRadixDigits * tiles + 1, hist_slice = (hist_n + 3) & ~(size_t)3;
-  if ((rc = ensure(c, c->cluster_work, sizeof(int) * slice * kSlices))) return rc;
-  if ((rc = ensure(c, c->cluster_hist, sizeof(int) * hist_slice * 2))) return rc;
-  if ((rc = ensure(c, c->cluster_bs, sizeof(int) * (std::max(nn + 1, hist_n) / 2048 + 2)))) return rc;
-  int* const work = c->cluster_work.as<int>();
+  if ((rc = ensure(c, r.work, sizeof(int) * slice * kSlices))) return rc;
+  if ((rc = ensure(c, r.hist, sizeof(int) * hist_slice * 2))) return rc;
+  if ((rc = ensure(c, r.bs, sizeof(int) * (std::max(nn + 1, hist_n) / 2048 + 2)))) return rc;
+  int* const work = r.work.as<int>();
   auto at = [&](Slice k) { return work + slice * (size_t)k; };
-  int* const hist = c->cluster_hist.as<int>();
-  int* const bs = c->cluster_bs.as<int>();
-  Cloud& cl = c->cluster_cl;
-  cl.in = d_in;
-  cl.stride_f = stride_bytes / 4;
-  cl.n = n;
-  cl.ready = false;
-  double cell = c->cluster_cell;
-  rc = build_search_grid(c, cl, &cell, c->cluster_small.as<int>(), reinterpret_cast<int*>(c->cluster_h), who, "the cloud", "the clustering's grid");
-  cl.in = nullptr;  // (the caller's buffer is not kept beyond the call)
-  if (rc) return rc;
+  int* const hist = r.hist.as<int>();
+  int* const bs = r.bs.as<int>();
+  const Cloud& cl = r.f.cl;
+  double cell = 0.0;
+  if ((rc = index_cloud(c, r.f, d_in, stride_bytes / 4, n, who, "the cloud", "the clustering's grid", &cell))) return rc;
   HIPCHK(c, hipMemsetAsync(dev_stats(c), 0, sizeof(rgck::ClusterStats), s));
   // the components, their leaders and sizes, the kept leaders in input order
   const rgck::SortedCloud sc = cl.sorted();
@@ -117,20 +92,15 @@ int rgc_cluster_extract(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, 
   int* val[2] = {at(kLead), at(kPair4)};
   rgck::cluster_emit(s, n, at(kFlagL), at(kOffL), at(kCsize), key[0], val[0]);
   // the one read-back
-  HIPCHK(c, hipMemcpyAsync(c->cluster_h + kStatsAt, dev_stats(c), sizeof(rgck::ClusterStats), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(c->cluster_h + kCountsAt, at(kOffL) + n, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(c->cluster_h + kCountsAt + sizeof(int), at(kOffP) + n, sizeof(int), hipMemcpyDeviceToHost, s));
+  int* const h_counts = host_words(r.f);
+  HIPCHK(c, hipMemcpyAsync(r.f.h + kFrameStatsAt, dev_stats(c), sizeof(rgck::ClusterStats), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(h_counts, at(kOffL) + n, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(h_counts + 1, at(kOffP) + n, sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
-  const rgck::ClusterStats& st = *reinterpret_cast<const rgck::ClusterStats*>(c->cluster_h + kStatsAt);
+  const rgck::ClusterStats& st = *host_stats<rgck::ClusterStats>(r.f);
   if (st.err) return fail(c, RGC_ERR_HIP, "%s: a union-find loop ran past its iteration cap (error word %d): nothing was written", who, st.err);
-  const int m = reinterpret_cast<const int*>(c->cluster_h + kCountsAt)[0], mp = reinterpret_cast<const int*>(c->cluster_h + kCountsAt)[1];
-  unsigned long long candidates = 0, components = 0, largest = 0;
-  for (int j = 0; j < rgck::kClusterSlots; j++) {
-    candidates += st.words[j][0];
-    components += st.words[j][1];
-    largest = std::max(largest, st.words[j][2]);
-  }
+  const int m = h_counts[0], mp = h_counts[1];
   if (labels || offsets || indices) {
     // the leaders by n - size, stable over ascending leaders: size descending, leader ascending
     const int cur = rgck::cluster_radix_sort(s, m, bit_length((unsigned)(n - 1)), key, val, hist, hist + hist_slice, bs);
@@ -143,23 +113,23 @@ int rgc_cluster_extract(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, 
     if (indices && mp) {
       // the kept points, ascending in input index, by their cluster's rank: the rows
       const int curp = rgck::cluster_radix_sort(s, mp, m > 1 ? bit_length((unsigned)(m - 1)) : 0, key, val, hist, hist + hist_slice, bs);
-      HIPCHK(c, hipMemcpyAsync(indices, val[curp], sizeof(int) * (size_t)mp, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+      if ((rc = copy_out(c, indices, val[curp], sizeof(int) * (size_t)mp, on_device))) return rc;
     }
     if (!on_device) {
-      if (labels) HIPCHK(c, hipMemcpyAsync(labels, d_labels, sizeof(int) * nn, hipMemcpyDeviceToHost, s));
-      if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, d_offsets, sizeof(int) * ((size_t)m + 1), hipMemcpyDeviceToHost, s));
+      if ((rc = copy_out(c, labels, d_labels, sizeof(int) * nn, 0))) return rc;
+      if ((rc = copy_out(c, offsets, d_offsets, sizeof(int) * ((size_t)m + 1), 0))) return rc;
     }
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
   }
-  c->cluster_info.n = n;
-  c->cluster_info.n_components = (int)components;
-  c->cluster_info.n_clusters = m;
-  c->cluster_info.n_clustered = mp;
-  c->cluster_info.largest = (int)largest;
-  c->cluster_info.cell = cell;
-  c->cluster_info.cells = cl.grid.ncell;
-  c->cluster_info.candidates = (long long)candidates;
+  r.info.n = n;
+  r.info.n_components = (int)sum_words(st.words, 1);
+  r.info.n_clusters = m;
+  r.info.n_clustered = mp;
+  r.info.largest = (int)max_words(st.words, 2);
+  r.info.cell = cell;
+  r.info.cells = cl.grid.ncell;
+  r.info.candidates = (long long)sum_words(st.words, 0);
   *n_clusters = m;
   return RGC_OK;
 }

@@ -1,5 +1,5 @@
 // rgc_api_fpfh.hip -- host side of the FPFH descriptors (rgc_fpfh_*): pcl::FPFHEstimation of a cloud against a surface cloud (or itself) and that
-// surface's normals, on a grid of the call's own (rgc_ctx::fpfh_cl, built by build_search_grid like the normals': the same automatic cell rule).  The
+// surface's normals, on a grid of the call's own (rgcapi::FpfhRecord, built by index_cloud like the normals': the same automatic cell rule).  The
 // kernels are rgc_fpfh.hip's; the semantics are stated in include/rgc_hip.h.  One chain per call -- the finiteness check and the normals' float4 form, the
 // surface's grid, (a separate surface: the marks, their scan, the list,) the SPFH pass, the combine pass straight into the caller's device buffers (or
 // scratch for a host caller) -- and ONE read-back behind it (the read-out words and the list's length); what can refuse a call (the arguments, the grid
@@ -11,14 +11,8 @@ using namespace rgcapi;
 namespace {
 
 constexpr int kFpfhMaxPoints = 1 << 27;  // point_at's 32-bit byte offsets rely on it
-constexpr size_t kFlagAt = 32;           // rgc_ctx::fpfh_h: the 8 ints of the grid's measurement, the queries' non-finite flag, ...
-constexpr size_t kListAt = 36;           // ... the number of listed surface points ...
-constexpr size_t kStatsAt = 64;          // ... and (fpfh_small too) what the kernels post (rgck::FpfhStats)
-constexpr size_t kSmallBytes = 4096;
-static_assert(kStatsAt + sizeof(rgck::FpfhStats) <= kSmallBytes, "the read-out words fit");
 
-rgck::FpfhStats* dev_stats(rgc_ctx* c) { return reinterpret_cast<rgck::FpfhStats*>(c->fpfh_small.as<unsigned char>() + kStatsAt); }
-const rgck::FpfhStats* host_stats(rgc_ctx* c) { return reinterpret_cast<const rgck::FpfhStats*>(c->fpfh_h + kStatsAt); }
+rgck::FpfhStats* dev_stats(rgc_ctx* c) { return stats<rgck::FpfhStats>(c->fpfh.f); }  // (the frame's own words: the queries' non-finite flag, the number of listed surface points)
 
 }  // namespace
 
@@ -30,14 +24,12 @@ void rgc_default_fpfh_params(rgc_fpfh_params* p) {
 
 int rgc_fpfh_set_cell(rgc_ctx* c, double cell) {
   if (!c) return RGC_ERR_INVALID;
-  if (!std::isfinite(cell) || cell < 0.0) return fail(c, RGC_ERR_INVALID, "rgc_fpfh_set_cell: cell must be finite and >= 0");
-  c->fpfh_cell = cell;
-  return RGC_OK;
+  return set_cell_of(c, &c->fpfh.f.cell, cell, "rgc_fpfh_set_cell");
 }
 
 int rgc_fpfh_get_info(rgc_ctx* c, rgc_fpfh_info* info) {
   if (!c || !info) return RGC_ERR_INVALID;
-  *info = c->fpfh_info;
+  *info = c->fpfh.info;
   return RGC_OK;
 }
 
@@ -54,113 +46,89 @@ int rgc_fpfh_estimate(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, co
   if (n > kFpfhMaxPoints || (surface && n_surface > kFpfhMaxPoints)) return fail(c, RGC_ERR_INVALID, "rgc_fpfh_estimate: a cloud has more than 2^27 points");
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "rgc_fpfh_estimate: a solve is in flight");
   *n_valid = 0;
-  c->fpfh_info = rgc_fpfh_info{};
+  c->fpfh.info = rgc_fpfh_info{};
   if (n == 0) return RGC_OK;
   const int ns = surface ? n_surface : n;
   HIPCHK(c, hipSetDevice(c->device));
+  rgcapi::FpfhRecord& r = c->fpfh;
   int rc;
-  if ((rc = ensure(c, c->fpfh_small, kSmallBytes))) return rc;
-  if (!c->fpfh_h) HIPCHK(c, hipHostMalloc((void**)&c->fpfh_h, kSmallBytes, hipHostMallocDefault));
+  if ((rc = frame_open(c, r.f))) return rc;
   hipStream_t s = c->stream;
   const float *dq = nullptr, *dsurf = nullptr, *dnrm = nullptr;
   int qs = 0, ss = 0, nrs = 0;
-  if ((rc = stage_cloud(c, xyzc, n, stride_bytes, on_device, c->fpfh_q, "the query cloud", &dq, &qs))) return rc;
+  if ((rc = stage_cloud(c, xyzc, n, stride_bytes, on_device, r.q, "the query cloud", &dq, &qs))) return rc;
   if (surface) {
-    if ((rc = stage_cloud(c, surface, ns, surface_stride_bytes, on_device, c->fpfh_surf, "the surface cloud", &dsurf, &ss))) return rc;
+    if ((rc = stage_cloud(c, surface, ns, surface_stride_bytes, on_device, r.surf, "the surface cloud", &dsurf, &ss))) return rc;
   } else {
     dsurf = dq;
     ss = qs;
   }
-  if ((rc = stage_cloud(c, normals, ns, normal_stride_bytes, on_device, c->fpfh_nrm, "the normals", &dnrm, &nrs))) return rc;
+  if ((rc = stage_cloud(c, normals, ns, normal_stride_bytes, on_device, r.nrm, "the normals", &dnrm, &nrs))) return rc;
   const size_t nn = (size_t)n, nsz = (size_t)ns;
   float* d_out = nullptr;
   unsigned* d_spfh = nullptr;
   int *d_m = nullptr, *d_cnt = nullptr;
-  if ((rc = place_output(c, out_fpfh, 4 * RGC_FPFH_BINS * nn, on_device, c->fpfh_out, "out_fpfh", &d_out))) return rc;
-  if ((rc = place_output(c, out_count, 4 * nn, on_device, c->fpfh_cnt, "out_count", &d_cnt))) return rc;
+  if ((rc = place_output(c, out_fpfh, 4 * RGC_FPFH_BINS * nn, on_device, r.out, "out_fpfh", &d_out))) return rc;
+  if ((rc = place_output(c, out_count, 4 * nn, on_device, r.cnt, "out_count", &d_cnt))) return rc;
   // the first pass' counts and row sizes are the second pass' input: the caller's buffers where asked for (device), else scratch
-  if (on_device && out_spfh) {
-    if ((rc = check_device_range(c, out_spfh, 4 * RGC_FPFH_BINS * nsz, "out_spfh"))) return rc;
-    d_spfh = out_spfh;
-  } else {
-    if ((rc = ensure(c, c->fpfh_spfh, 4 * RGC_FPFH_BINS * nsz))) return rc;
-    d_spfh = c->fpfh_spfh.as<unsigned>();
-  }
-  if (on_device && out_spfh_count) {
-    if ((rc = check_device_range(c, out_spfh_count, 4 * nsz, "out_spfh_count"))) return rc;
-    d_m = out_spfh_count;
-  } else {
-    if ((rc = ensure(c, c->fpfh_m, 4 * nsz))) return rc;
-    d_m = c->fpfh_m.as<int>();
-  }
-  if ((rc = ensure(c, c->fpfh_n4, 16 * nsz))) return rc;
+  if ((rc = place_output(c, out_spfh, 4 * RGC_FPFH_BINS * nsz, on_device, r.spfh, "out_spfh", &d_spfh, true))) return rc;
+  if ((rc = place_output(c, out_spfh_count, 4 * nsz, on_device, r.m, "out_spfh_count", &d_m, true))) return rc;
+  if ((rc = ensure(c, r.n4, 16 * nsz))) return rc;
   if (surface) {
-    if ((rc = ensure(c, c->fpfh_flag, sizeof(int) * (nsz + 1)))) return rc;
-    if ((rc = ensure(c, c->fpfh_off, sizeof(int) * (nsz + 1)))) return rc;
-    if ((rc = ensure(c, c->fpfh_bs, sizeof(int) * ((nsz + 1) / 2048 + 2)))) return rc;
-    if ((rc = ensure(c, c->fpfh_list, sizeof(int) * nsz))) return rc;
+    if ((rc = ensure(c, r.flag, sizeof(int) * (nsz + 1)))) return rc;
+    if ((rc = ensure(c, r.off, sizeof(int) * (nsz + 1)))) return rc;
+    if ((rc = ensure(c, r.bs, sizeof(int) * ((nsz + 1) / 2048 + 2)))) return rc;
+    if ((rc = ensure(c, r.list, sizeof(int) * nsz))) return rc;
   }
   HIPCHK(c, hipMemsetAsync(dev_stats(c), 0, sizeof(rgck::FpfhStats), s));
-  int* const h_flag = reinterpret_cast<int*>(c->fpfh_h + kFlagAt);
-  int* const h_list = reinterpret_cast<int*>(c->fpfh_h + kListAt);
+  int* const h_flag = host_words(r.f);
+  int* const h_list = h_flag + 1;
   *h_flag = 0;
   *h_list = ns;
-  float4* const n4 = c->fpfh_n4.as<float4>();
+  float4* const n4 = r.n4.as<float4>();
   // (a cloud that is its own surface is checked by its grid build: a null query array)
   rgck::fpfh_check(s, surface ? dq : nullptr, qs, n, dnrm, nrs, ns, n4, &dev_stats(c)->nonfinite);
   if (surface) HIPCHK(c, hipMemcpyAsync(h_flag, &dev_stats(c)->nonfinite, sizeof(int), hipMemcpyDeviceToHost, s));  // (home with the grid's measurement)
-  Cloud& cl = c->fpfh_cl;
-  cl.in = dsurf;
-  cl.stride_f = ss;
-  cl.n = ns;
-  cl.ready = false;
-  double cell = c->fpfh_cell;
-  rc = build_search_grid(c, cl, &cell, c->fpfh_small.as<int>(), reinterpret_cast<int*>(c->fpfh_h), "rgc_fpfh_estimate", "the surface cloud", "the descriptors' grid");
-  cl.in = nullptr;  // (the caller's buffer is not kept beyond the call)
-  if (rc) return rc;
+  const Cloud& cl = r.f.cl;
+  double cell = 0.0;
+  if ((rc = index_cloud(c, r.f, dsurf, ss, ns, "rgc_fpfh_estimate", "the surface cloud", "the descriptors' grid", &cell))) return rc;
   if (*h_flag) return fail(c, RGC_ERR_NONFINITE, "rgc_fpfh_estimate: a query has a non-finite coordinate");
   const rgck::SortedCloud sc = cl.sorted();
   if (surface) {  // only the SPFHs some query's row holds: the marks, their scan, the list; the rest reads as "not computed"
-    int* const flag = c->fpfh_flag.as<int>();
-    int* const off = c->fpfh_off.as<int>();
+    int* const flag = r.flag.as<int>();
+    int* const off = r.off.as<int>();
     HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(int) * (nsz + 1), s));
     HIPCHK(c, hipMemsetAsync(d_spfh, 0, 4 * RGC_FPFH_BINS * nsz, s));
     HIPCHK(c, hipMemsetAsync(d_m, 0xff, 4 * nsz, s));
     rgck::fpfh_mark(s, dq, qs, n, sc, r2, radius, flag, dev_stats(c));
-    rgck::exclusive_scan(s, flag, off, ns + 1, c->fpfh_bs.as<int>());
-    rgck::fpfh_list(s, flag, off, ns, c->fpfh_list.as<int>());
+    rgck::exclusive_scan(s, flag, off, ns + 1, r.bs.as<int>());
+    rgck::fpfh_list(s, flag, off, ns, r.list.as<int>());
     HIPCHK(c, hipMemcpyAsync(h_list, off + ns, sizeof(int), hipMemcpyDeviceToHost, s));
-    rgck::fpfh_spfh(s, sc, c->fpfh_list.as<const int>(), off + ns, n4, r2, radius, d_spfh, d_m, dev_stats(c));
+    rgck::fpfh_spfh(s, sc, r.list.as<const int>(), off + ns, n4, r2, radius, d_spfh, d_m, dev_stats(c));
   } else {
     rgck::fpfh_spfh(s, sc, nullptr, nullptr, n4, r2, radius, d_spfh, d_m, dev_stats(c));
   }
   rgck::fpfh_combine(s, surface ? dq : nullptr, qs, n, sc, d_spfh, d_m, r2, radius, d_out, d_cnt, dev_stats(c));
-  HIPCHK(c, hipMemcpyAsync(c->fpfh_h + kStatsAt, dev_stats(c), sizeof(rgck::FpfhStats), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(r.f.h + kFrameStatsAt, dev_stats(c), sizeof(rgck::FpfhStats), hipMemcpyDeviceToHost, s));
   if (!on_device) {
-    if (out_fpfh) HIPCHK(c, hipMemcpyAsync(out_fpfh, d_out, 4 * RGC_FPFH_BINS * nn, hipMemcpyDeviceToHost, s));
-    if (out_count) HIPCHK(c, hipMemcpyAsync(out_count, d_cnt, 4 * nn, hipMemcpyDeviceToHost, s));
-    if (out_spfh) HIPCHK(c, hipMemcpyAsync(out_spfh, d_spfh, 4 * RGC_FPFH_BINS * nsz, hipMemcpyDeviceToHost, s));
-    if (out_spfh_count) HIPCHK(c, hipMemcpyAsync(out_spfh_count, d_m, 4 * nsz, hipMemcpyDeviceToHost, s));
+    if ((rc = copy_out(c, out_fpfh, d_out, 4 * RGC_FPFH_BINS * nn, 0))) return rc;
+    if ((rc = copy_out(c, out_count, d_cnt, 4 * nn, 0))) return rc;
+    if ((rc = copy_out(c, out_spfh, d_spfh, 4 * RGC_FPFH_BINS * nsz, 0))) return rc;
+    if ((rc = copy_out(c, out_spfh_count, d_m, 4 * nsz, 0))) return rc;
   }
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
-  const rgck::FpfhStats& st = *host_stats(c);
-  unsigned long long candidates = 0, pairs = 0, valid = 0;
-  for (int j = 0; j < rgck::kFpfhSlots; j++) {
-    candidates += st.words[j][0];
-    pairs += st.words[j][1];
-    valid += st.words[j][2];
-  }
-  rgc_fpfh_info& info = c->fpfh_info;
+  const rgck::FpfhStats& st = *host_stats<rgck::FpfhStats>(r.f);
+  rgc_fpfh_info& info = r.info;
   info.n = n;
   info.n_surface = ns;
-  info.n_valid = (int)valid;
+  info.n_valid = (int)sum_words(st.words, 2);
   info.n_spfh = *h_list;
   info.cell = cell;
   info.cells = cl.grid.ncell;
-  info.pairs = (long long)pairs;
-  info.candidates = (long long)candidates;
-  *n_valid = (int)valid;
+  info.pairs = (long long)sum_words(st.words, 1);
+  info.candidates = (long long)sum_words(st.words, 0);
+  *n_valid = info.n_valid;
   return RGC_OK;
 }
 

@@ -53,13 +53,13 @@ int rgc_plane_sample(unsigned long long seed, unsigned long long t, int n, int* 
 int rgc_plane_set_batch(rgc_ctx* c, int batch) {
   if (!c) return RGC_ERR_INVALID;
   if (batch < 0 || batch > RGC_PLANE_MAX_BATCH) return fail(c, RGC_ERR_INVALID, "rgc_plane_set_batch: batch in 0..%d (0 = automatic)", RGC_PLANE_MAX_BATCH);
-  c->plane_batch = batch;
+  c->plane.batch = batch;
   return RGC_OK;
 }
 
 int rgc_plane_get_info(rgc_ctx* c, rgc_plane_info* info) {
   if (!c || !info) return RGC_ERR_INVALID;
-  *info = c->plane_info;
+  *info = c->plane.info;
   return RGC_OK;
 }
 
@@ -93,9 +93,9 @@ int rgc_plane_segment(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, in
         return fail(c, RGC_ERR_INVALID, "%s: samples[%lld] = (%d, %d, %d): three distinct indices below %d", who, t, i0, i1, i2, n);
     }
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "%s: a solve is in flight", who);
-  c->plane_info = rgc_plane_info{};
-  c->plane_info.best_count = -1;
-  c->plane_info.best_position = -1;
+  c->plane.info = rgc_plane_info{};
+  c->plane.info.best_count = -1;
+  c->plane.info.best_position = -1;
   if (n == 0) {
     for (int a = 0; a < 4; a++) coeff[a] = 0.0;
     *n_out = 0;
@@ -104,50 +104,33 @@ int rgc_plane_segment(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, in
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   const size_t nn = (size_t)n;
+  rgcapi::PlaneRecord& r = c->plane;
   int rc;
-  const float* d_in = xyzc;
-  float* d_out = out_xyzc;
-  int* d_index = out_index;
-  // (what is read of the last record: x, y, z, and c too when records are written from records that have one)
-  const size_t in_bytes = nn * stride_bytes - (stride_bytes - (out_xyzc && stride_bytes >= 16 ? 16 : 12));
-  if (on_device) {
-    if ((rc = check_device_range(c, xyzc, in_bytes, "input cloud"))) return rc;
-    if (out_xyzc && (rc = check_device_range(c, out_xyzc, 16 * nn, "out_xyzc"))) return rc;
-    if (out_index && (rc = check_device_range(c, out_index, sizeof(int) * nn, "out_index"))) return rc;
-  } else {
-    if ((rc = ensure(c, c->plane_in, in_bytes))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->plane_in.p, xyzc, in_bytes, hipMemcpyHostToDevice, s));
-    d_in = c->plane_in.as<const float>();
-    if (out_xyzc) {
-      if ((rc = ensure(c, c->plane_out, 16 * nn))) return rc;
-      d_out = c->plane_out.as<float>();
-    }
-    if (out_index) {
-      if ((rc = ensure(c, c->plane_idx, sizeof(int) * nn))) return rc;
-      d_index = c->plane_idx.as<int>();
-    }
-  }
+  const float* d_in = nullptr;
+  float* d_out = nullptr;
+  int* d_index = nullptr;
+  if ((rc = stage_records(c, xyzc, n, stride_bytes, on_device, out_xyzc != nullptr, r.in, "input cloud", &d_in))) return rc;
+  if ((rc = place_output(c, out_xyzc, 16 * nn, on_device, r.sel.out, "out_xyzc", &d_out))) return rc;
+  if ((rc = place_output(c, out_index, sizeof(int) * nn, on_device, r.sel.idx, "out_index", &d_index))) return rc;
   const int stride_f = stride_bytes / 4;
   const long long T = samples ? (long long)n_samples : 10ll * prm->max_iterations;  // the stream's end
-  const int B = c->plane_batch > 0 ? c->plane_batch : std::min(prm->max_iterations, 64);
-  if ((rc = ensure(c, c->plane_bat, batch_bytes(B)))) return rc;
-  if ((rc = ensure(c, c->plane_fit, sizeof(rgck::PlaneFit)))) return rc;
-  if ((rc = ensure(c, c->plane_flag, sizeof(int) * (nn + 1)))) return rc;
-  if ((rc = ensure(c, c->plane_off, sizeof(int) * (nn + 1)))) return rc;
-  if ((rc = ensure(c, c->plane_bs, sizeof(int) * ((nn + 1) / 2048 + 2)))) return rc;
-  if (prm->optimize && (rc = ensure(c, c->plane_rows, sizeof(double) * rgck::kPlaneRowCols * (size_t)rgck::plane_moment_rows(n)))) return rc;
-  if (!c->plane_h) HIPCHK(c, hipHostMalloc((void**)&c->plane_h, kPinnedBytes, hipHostMallocDefault));
+  const int B = r.batch > 0 ? r.batch : std::min(prm->max_iterations, 64);
+  if ((rc = ensure(c, r.bat, batch_bytes(B)))) return rc;
+  if ((rc = ensure(c, r.fit, sizeof(rgck::PlaneFit)))) return rc;
+  if ((rc = selection_scratch(c, r.sel, n))) return rc;
+  if (prm->optimize && (rc = ensure(c, r.rows, sizeof(double) * rgck::kPlaneRowCols * (size_t)rgck::plane_moment_rows(n)))) return rc;
+  if (!r.h) HIPCHK(c, hipHostMalloc((void**)&r.h, kPinnedBytes, hipHostMallocDefault));
   if (samples && n_samples > 0) {
-    if ((rc = ensure(c, c->plane_samples, sizeof(int) * 3 * (size_t)n_samples))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->plane_samples.p, samples, sizeof(int) * 3 * (size_t)n_samples, hipMemcpyHostToDevice, s));
-    st.samples = c->plane_samples.as<const int>();
+    if ((rc = ensure(c, r.samples, sizeof(int) * 3 * (size_t)n_samples))) return rc;
+    HIPCHK(c, hipMemcpyAsync(r.samples.p, samples, sizeof(int) * 3 * (size_t)n_samples, hipMemcpyHostToDevice, s));
+    st.samples = r.samples.as<const int>();
   }
   st.seed = prm->seed;
-  unsigned char* const dbat = c->plane_bat.as<unsigned char>();
+  unsigned char* const dbat = r.bat.as<unsigned char>();
   const rgck::PlaneBatch bat{reinterpret_cast<int*>(dbat), reinterpret_cast<float4*>(dbat + kModelsAt), reinterpret_cast<int*>(dbat + kModelsAt + 16 * (size_t)B)};
-  const int* const h_nonfinite = reinterpret_cast<const int*>(c->plane_h);
-  const float4* const h_models = reinterpret_cast<const float4*>(c->plane_h + kModelsAt);
-  const int* const h_counts = reinterpret_cast<const int*>(c->plane_h + kModelsAt + 16 * (size_t)B);
+  const int* const h_nonfinite = reinterpret_cast<const int*>(r.h);
+  const float4* const h_models = reinterpret_cast<const float4*>(r.h + kModelsAt);
+  const int* const h_counts = reinterpret_cast<const int*>(r.h + kModelsAt + 16 * (size_t)B);
   HIPCHK(c, hipMemsetAsync(dbat, 0, kModelsAt, s));
 
   // ---- the decision: PCL's sequential loop, replayed over each batch's counts ----
@@ -159,7 +142,7 @@ int rgc_plane_segment(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, in
   bool stop = T == 0;
   if (stop) {  // an empty stream: the cloud is walked all the same, for the non-finite word
     rgck::plane_score(s, d_in, stride_f, n, thr, 0, 1, bat);
-    HIPCHK(c, hipMemcpyAsync(c->plane_h, dbat, kModelsAt, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(r.h, dbat, kModelsAt, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
     if (h_nonfinite[0]) return fail(c, RGC_ERR_NONFINITE, "%s: the cloud has a non-finite coordinate", who);
@@ -170,7 +153,7 @@ int rgc_plane_segment(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, in
     st.batch = b;
     rgck::plane_models(s, d_in, stride_f, n, st, bat);
     rgck::plane_score(s, d_in, stride_f, n, thr, b, launches == 0, bat);
-    HIPCHK(c, hipMemcpyAsync(c->plane_h, dbat, batch_bytes(B), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(r.h, dbat, batch_bytes(B), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
     if (launches == 0 && h_nonfinite[0]) return fail(c, RGC_ERR_NONFINITE, "%s: the cloud has a non-finite coordinate", who);
@@ -194,38 +177,30 @@ int rgc_plane_segment(rgc_ctx* c, const float* xyzc, int n, int stride_bytes, in
         if ((double)iterations >= k || iterations == prm->max_iterations) stop = true;
       }
       if (t0 + j + 1 == T) stop = true;
-      if (stop) c->plane_info.positions = t0 + j + 1;
+      if (stop) c->plane.info.positions = t0 + j + 1;
     }
     t0 += b;
   }
 
   // ---- the best model's inliers, the refinement, the records ----
-  rgck::PlaneFit* const h_fit = reinterpret_cast<rgck::PlaneFit*>(c->plane_h + kFitAt);
-  rgck::PlaneFit* const d_fit = c->plane_fit.as<rgck::PlaneFit>();
+  rgck::PlaneFit* const h_fit = reinterpret_cast<rgck::PlaneFit*>(r.h + kFitAt);
+  rgck::PlaneFit* const d_fit = r.fit.as<rgck::PlaneFit>();
   *h_fit = rgck::PlaneFit{};
   const float qnan = std::numeric_limits<float>::quiet_NaN();
   h_fit->model = best_position >= 0 ? best_model : make_float4(qnan, qnan, qnan, qnan);  // no model: no point is an inlier
   HIPCHK(c, hipMemcpyAsync(d_fit, h_fit, sizeof(rgck::PlaneFit), hipMemcpyHostToDevice, s));
-  if (prm->optimize && best >= 3) rgck::plane_refine(s, d_in, stride_f, n, thr, c->plane_rows.as<double>(), d_fit);
-  int* const flag = c->plane_flag.as<int>();
-  int* const off = c->plane_off.as<int>();
-  rgck::plane_flag(s, d_in, stride_f, n, thr, d_fit, negative, flag);
-  rgck::exclusive_scan(s, flag, off, n + 1, c->plane_bs.as<int>());
-  rgck::outlier_emit(s, d_in, stride_f, n, flag, off, d_out, d_index);
-  HIPCHK(c, hipMemcpyAsync(h_fit, d_fit, sizeof(rgck::PlaneFit), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(c->plane_h + kKeptAt, off + n, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  const int kept = *reinterpret_cast<const int*>(c->plane_h + kKeptAt);
-  if (!on_device) {
-    if (out_xyzc && kept) HIPCHK(c, hipMemcpyAsync(out_xyzc, d_out, 16 * (size_t)kept, hipMemcpyDeviceToHost, s));
-    if (out_index && kept) HIPCHK(c, hipMemcpyAsync(out_index, d_index, sizeof(int) * (size_t)kept, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-  }
+  if (prm->optimize && best >= 3) rgck::plane_refine(s, d_in, stride_f, n, thr, r.rows.as<double>(), d_fit);
+  rgck::plane_flag(s, d_in, stride_f, n, thr, d_fit, negative, r.sel.flag.as<int>());
+  int* const h_kept = reinterpret_cast<int*>(r.h + kKeptAt);
+  const EmitTo to{d_out, d_index, out_xyzc, out_index};
+  const EmitHome home{h_fit, d_fit, sizeof(rgck::PlaneFit), h_kept};
+  if ((rc = emit_selected(c, r.sel, d_in, stride_f, n, on_device, to, home))) return rc;
+  if (!on_device) HIPCHK(c, hipStreamSynchronize(s));
+  const int kept = *h_kept;
   const bool found = best_position >= 0;
   const float4 m = h_fit->model;
   coeff[0] = found ? (double)m.x : 0.0; coeff[1] = found ? (double)m.y : 0.0; coeff[2] = found ? (double)m.z : 0.0; coeff[3] = found ? (double)m.w : 0.0;
-  rgc_plane_info& info = c->plane_info;
+  rgc_plane_info& info = c->plane.info;
   info.n = n;
   info.n_inliers = negative ? n - kept : kept;
   info.iterations = iterations;

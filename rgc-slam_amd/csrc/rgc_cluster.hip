@@ -1,5 +1,5 @@
 // rgc_cluster.hip -- gfx950 kernels of Euclidean cluster extraction (rgc_cluster_*): pcl::EuclideanClusterExtraction of a cloud on a grid of its own
-// (rgc_ctx::cluster_cl).  The machinery is the outlier filters' (rgc_filters.hip, rgc_nn.h): the grid's contiguous row ranges, the fp32 key dist2 (never
+// (rgcapi::ClusterRecord).  The machinery is the outlier filters' (rgc_filters.hip, rgc_nn.h): the grid's contiguous row ranges, the fp32 key dist2 (never
 // FMA-contracted: -ffp-contract=off), the strict key < r2 ball walk by a group of lanes per sorted point.  What is new is a consumer that LINKS instead
 // of counting -- a lock-free union-find over the sorted positions -- and a stable global ordering of the result (an LSD radix sort; the library had no
 // global sort).  No output bit depends on the grid, the cell size, the launch shape or the run: the leader of a component is its smallest ORIGINAL
@@ -109,7 +109,7 @@ __device__ __forceinline__ void cl_stats_add(ClusterStats* st, unsigned long lon
     unsigned long long t = 0;
 #pragma unroll
     for (int j = 0; j < CL_T / CL_WAVE; j++) t = threadIdx.x < 2 ? t + part[j][threadIdx.x] : (part[j][2] > t ? part[j][2] : t);
-    unsigned long long* w = &st->words[blockIdx.x & (kClusterSlots - 1)][threadIdx.x];
+    unsigned long long* w = &st->words[blockIdx.x & (kStatSlots - 1)][threadIdx.x];
     if (t) {
       if (threadIdx.x < 2) atomicAdd(w, t);
       else atomicMax(w, t);

@@ -138,12 +138,13 @@ struct Cloud {
 };
 
 // ---- the registration methods beside VGICP: what each keeps between its calls.  bufs(): its device buffers, once (rgc_destroy walks them);
-// pinned(): its page-locked host mirrors.  `valid` = the frozen state is that of the present clouds and settings
+// pinned(): its page-locked host mirrors; clouds(): its clouds.  `valid` = the frozen state is that of the present clouds and settings
 struct Sums {  // where a method's term kernels fold to: per-block partials, the folded sums, their pinned mirror (32 doubles)
   DevBuf partials, out;
   double* h_out = nullptr;
   std::vector<DevBuf*> bufs() { return {&partials, &out}; }
   std::vector<void*> pinned() { return {h_out}; }
+  std::vector<Cloud*> clouds() { return {}; }
 };
 
 // NDT registration (rgc_ndt_*): two clouds of its own (0 target, 1 source) with their grids and voxel maps (Cloud::cell_voxel / vox / vox_cell,
@@ -164,6 +165,7 @@ struct NdtRecord {
   double Tlin[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::vector<DevBuf*> bufs() { return {&offs, &corr, &ipartials, &small, &sums.partials, &sums.out}; }
   std::vector<void*> pinned() { return {sums.h_out, h_small}; }
+  std::vector<Cloud*> clouds() { return {&cl[0], &cl[1]}; }
 };
 
 // FastGICP (rgc_gicp_*) on the context's own source and target: the pair list of the last rgc_gicp_linearize (per sorted source point the
@@ -175,6 +177,7 @@ struct GicpRecord {
   int n = 0, kept = 0;
   std::vector<DevBuf*> bufs() { return {&corr, &key, &M}; }
   std::vector<void*> pinned() { return {}; }
+  std::vector<Cloud*> clouds() { return {}; }
 };
 
 // FastGICPSingleThread (rgc_gicpst_*) on the same clouds: per sorted source point the pair, the keys to the nearest and the second nearest at
@@ -187,6 +190,7 @@ struct GicpStRecord {
   int n = 0, kept = 0, searched_n = 0;
   std::vector<DevBuf*> bufs() { return {&corr, &key1, &key2, &anchor, &M, &searched, &list, &count}; }
   std::vector<void*> pinned() { return {}; }
+  std::vector<Cloud*> clouds() { return {}; }
 };
 
 // FastGICPMultiPoints (rgc_gicpmp_*) on the same clouds: the merged list of the last rgc_gicpmp_linearize (rgck::kGicpMpMerged doubles per sorted
@@ -202,6 +206,107 @@ struct GicpMpRecord {
   float T32[16] = {0};
   std::vector<DevBuf*> bufs() { return {&merged, &cand, &scratch, &sums.partials, &sums.out}; }
   std::vector<void*> pinned() { return {sums.h_out}; }
+  std::vector<Cloud*> clouds() { return {}; }
+};
+
+// ---- the cloud operations (search index, outlier filters, clusters, plane, normals, FPFH): what each keeps between its calls, released like the
+// methods' records above.  The helpers of their common call frame are declared below (rgc_api_search.hip)
+// What five of them hold alike: a cloud used for its grid only (independent of the context's source and target, and of each other's), the read-out
+// words on the device -- the 8 ints of the grid's measurement, the call's own words at kFrameWordsAt, what the kernels post at kFrameStatsAt -- their
+// pinned mirror, and the cell-size knob (rgc_*_set_cell: 0 = the search index's automatic rule; the search index takes its cell with the cloud)
+struct OpFrame {
+  Cloud cl;
+  DevBuf small;
+  unsigned char* h = nullptr;
+  double cell = 0.0;
+};
+constexpr size_t kFrameBytes = 4096, kFrameWordsAt = 32, kFrameStatsAt = 64;
+template <class T> T* stats(const OpFrame& f) {
+  static_assert(kFrameStatsAt + sizeof(T) <= kFrameBytes, "the read-out words fit");
+  return reinterpret_cast<T*>(f.small.as<unsigned char>() + kFrameStatsAt);
+}
+template <class T> const T* host_stats(const OpFrame& f) { return reinterpret_cast<const T*>(f.h + kFrameStatsAt); }
+inline int* host_words(const OpFrame& f) { return reinterpret_cast<int*>(f.h + kFrameWordsAt); }  // the call's own words in the mirror
+
+// What emit_selected works on (the outlier filters, the plane's extraction): the flags in input order, their scan and its block sums, a host
+// caller's records and indices
+struct Selection {
+  DevBuf flag, off, bs, out, idx;
+};
+
+// The search index (rgc_search_*, rgc_api_search.hip): the indexed cloud (a host caller's points in Cloud::in_copy); the staged host queries, the query
+// calls' scratch (counts, offsets, block sums, fixed-width rows, packed entries and the long sort's second row, the results of a host caller); the
+// mirror holds rgck::SearchStats
+struct SearchRecord {
+  OpFrame f;
+  bool set = false;
+  rgc_search_info info{};
+  DevBuf q, cnt, off, bs, row_idx, row_sq, ent, tmp, idx, sq;
+  std::vector<DevBuf*> bufs() { return {&f.small, &q, &cnt, &off, &bs, &row_idx, &row_sq, &ent, &tmp, &idx, &sq}; }
+  std::vector<void*> pinned() { return {f.h}; }
+  std::vector<Cloud*> clouds() { return {&f.cl}; }
+};
+
+// The outlier filters (rgc_outlier_*, rgc_api_filters.hip): a host caller's staged records, the mean distances / counts, the selection, the
+// fixed-order sums' rows; the mirror holds the number kept and rgck::OutlierStats
+struct OutlierRecord {
+  OpFrame f;
+  rgc_outlier_info info{};
+  DevBuf in, val, partials;
+  Selection sel;
+  std::vector<DevBuf*> bufs() { return {&f.small, &in, &val, &partials, &sel.flag, &sel.off, &sel.bs, &sel.out, &sel.idx}; }
+  std::vector<void*> pinned() { return {f.h}; }
+  std::vector<Cloud*> clouds() { return {&f.cl}; }
+};
+
+// Euclidean cluster extraction (rgc_cluster_*, rgc_api_cluster.hip): a host caller's staged records; the int arrays of a call carved from ONE buffer
+// (the union-find, the per-point and per-cluster tables, the radix sort's two pairs of arrays, a host caller's results); the radix histograms and
+// the scans' block sums; the mirror holds the two counts and rgck::ClusterStats
+struct ClusterRecord {
+  OpFrame f;
+  rgc_cluster_info info{};
+  DevBuf in, work, hist, bs;
+  std::vector<DevBuf*> bufs() { return {&f.small, &in, &work, &hist, &bs}; }
+  std::vector<void*> pinned() { return {f.h}; }
+  std::vector<Cloud*> clouds() { return {&f.cl}; }
+};
+
+// RANSAC plane segmentation (rgc_plane_*, rgc_api_plane.hip), no grid: a host caller's staged records and samples; a batch's non-finite word, models
+// and counts (one contiguous read-back) with their pinned mirror of 32 KiB, which also holds the final rgck::PlaneFit and the number written; the
+// fixed-order sums' rows; the fit; the selection
+struct PlaneRecord {
+  rgc_plane_info info{};
+  int batch = 0;  // rgc_plane_set_batch: 0 = automatic
+  DevBuf in, samples, bat, rows, fit;
+  Selection sel;
+  unsigned char* h = nullptr;
+  std::vector<DevBuf*> bufs() { return {&in, &samples, &bat, &rows, &fit, &sel.flag, &sel.off, &sel.bs, &sel.out, &sel.idx}; }
+  std::vector<void*> pinned() { return {h}; }
+  std::vector<Cloud*> clouds() { return {}; }
+};
+
+// Surface normal estimation (rgc_normal_*, rgc_api_normals.hip): the surface cloud's grid; a host caller's staged queries and surface (12-byte
+// records) and results; the mirror holds the queries' flag and rgck::NormalStats
+struct NormalRecord {
+  OpFrame f;
+  rgc_normal_info info{};
+  DevBuf q, surf, n4, cov, cen, cnt;
+  std::vector<DevBuf*> bufs() { return {&f.small, &q, &surf, &n4, &cov, &cen, &cnt}; }
+  std::vector<void*> pinned() { return {f.h}; }
+  std::vector<Cloud*> clouds() { return {&f.cl}; }
+};
+
+// FPFH descriptors (rgc_fpfh_*, rgc_api_fpfh.hip): the surface cloud's grid; a host caller's staged queries, surface and normals (12-byte records);
+// the normals as float4 with their validity in w; the marks of a separate surface, their scan, its block sums and the list of marked sorted
+// positions; the SPFH counts and row sizes (scratch when the caller does not ask for them), a host caller's descriptors and counts; the mirror
+// holds the queries' flag, the list's length and rgck::FpfhStats
+struct FpfhRecord {
+  OpFrame f;
+  rgc_fpfh_info info{};
+  DevBuf q, surf, nrm, n4, flag, off, bs, list, spfh, m, out, cnt;
+  std::vector<DevBuf*> bufs() { return {&f.small, &q, &surf, &nrm, &n4, &flag, &off, &bs, &list, &spfh, &m, &out, &cnt}; }
+  std::vector<void*> pinned() { return {f.h}; }
+  std::vector<Cloud*> clouds() { return {&f.cl}; }
 };
 
 struct ProfRegion {
@@ -381,22 +486,13 @@ struct rgc_ctx {
   rgcapi::GicpRecord gicp;
   rgcapi::GicpStRecord gicp_st;
   rgcapi::GicpMpRecord gicp_mp;
-  // The search index (rgc_search_*, rgc_api_search.hip): a cloud of its own with the grid only, independent of the context's source and target; the
-  // staged host queries, the query calls' scratch (counts, offsets, block sums, fixed-width rows, packed entries and the long sort's second row, the
-  // results of a host caller), the read-out words on the device and their pinned mirror behind the eight ints of the grid's measurement
-  Cloud search_cl;
-  bool search_set = false;
-  rgc_search_info search_info{};
-  DevBuf search_q, search_cnt, search_off, search_bs, search_row_idx, search_row_sq, search_ent, search_tmp, search_idx, search_sq, search_small;
-  unsigned char* search_h = nullptr;  // pinned: int[8], then rgck::SearchStats
-  // The outlier filters (rgc_outlier_*, rgc_api_filters.hip): a cloud of their own with the grid only (the caller's search index, source and target are
-  // untouched); a host caller's staged records, the mean distances / counts, the flags and their scan, the fixed-order sums' rows, a host caller's
-  // results, the grid's measurement and the read-out words on the device with their pinned mirror (int[8], the number kept, rgck::OutlierStats)
-  Cloud filter_cl;
-  DevBuf filter_in, filter_val, filter_flag, filter_off, filter_bs, filter_partials, filter_out, filter_idx, filter_small;
-  unsigned char* filter_h = nullptr;
-  rgc_outlier_info outlier_info{};
-  double outlier_cell = 0.0;          // rgc_outlier_set_cell: 0 = the search index's automatic rule
+  // The cloud operations, each in a record of its own (rgcapi::SearchRecord and the five below it)
+  rgcapi::SearchRecord search;
+  rgcapi::OutlierRecord outlier;
+  rgcapi::ClusterRecord cluster;
+  rgcapi::PlaneRecord plane;
+  rgcapi::NormalRecord normal;
+  rgcapi::FpfhRecord fpfh;
   rgc_stats stats{};
   // profiling
   bool prof_on = false;
@@ -406,38 +502,6 @@ struct rgc_ctx {
   long long prof_launches[kProfKinds] = {0};
   double prof_ms[kProfKinds] = {0};
   long long prof_points[kProfKinds] = {0};
-  // Euclidean cluster extraction (rgc_cluster_*, rgc_api_cluster.hip), behind everything else so that no older member moves: a cloud of its own with the grid only; a host caller's staged records; the int
-  // arrays of a call carved from ONE buffer (the union-find, the per-point and per-cluster tables, the radix sort's two pairs of arrays, a host
-  // caller's results); the radix histograms and the scans' block sums; the grid's measurement, the counts and rgck::ClusterStats with their pinned mirror
-  Cloud cluster_cl;
-  DevBuf cluster_in, cluster_work, cluster_hist, cluster_bs, cluster_small;
-  unsigned char* cluster_h = nullptr;
-  rgc_cluster_info cluster_info{};
-  double cluster_cell = 0.0;          // rgc_cluster_set_cell: 0 = the search index's automatic rule
-  // RANSAC plane segmentation (rgc_plane_*, rgc_api_plane.hip), behind everything else again: a host caller's staged records and samples; a batch's
-  // non-finite word, models and counts (one contiguous read-back) with their pinned mirror, which also holds the final rgck::PlaneFit and the number
-  // written; the flags, their scan and its block sums; the fixed-order sums' rows; a host caller's results
-  DevBuf plane_in, plane_samples, plane_bat, plane_flag, plane_off, plane_bs, plane_rows, plane_out, plane_idx, plane_fit;
-  unsigned char* plane_h = nullptr;
-  rgc_plane_info plane_info{};
-  int plane_batch = 0;                // rgc_plane_set_batch: 0 = automatic
-  // Surface normal estimation (rgc_normal_*, rgc_api_normals.hip), behind everything else again: the surface cloud's grid (a cloud of its own, the grid
-  // only); a host caller's staged queries and surface (12-byte records) and results; the grid's measurement, the queries' flag and rgck::NormalStats
-  // with their pinned mirror
-  Cloud normal_cl;
-  DevBuf normal_q, normal_surf, normal_n4, normal_cov, normal_cen, normal_cnt, normal_small;
-  unsigned char* normal_h = nullptr;
-  rgc_normal_info normal_info{};
-  double normal_cell = 0.0;           // rgc_normal_set_cell: 0 = the search index's automatic rule
-  // FPFH descriptors (rgc_fpfh_*, rgc_api_fpfh.hip), behind everything else again: the surface cloud's grid (a cloud of its own, the grid only); a host
-  // caller's staged queries, surface and normals (12-byte records); the normals as float4 with their validity in w; the marks of a separate surface,
-  // their scan, its block sums and the list of marked sorted positions; the SPFH counts and row sizes (scratch when the caller does not ask for them), a
-  // host caller's descriptors and counts; the grid's measurement, the queries' flag and rgck::FpfhStats with their pinned mirror
-  Cloud fpfh_cl;
-  DevBuf fpfh_q, fpfh_surf, fpfh_nrm, fpfh_n4, fpfh_flag, fpfh_off, fpfh_bs, fpfh_list, fpfh_spfh, fpfh_m, fpfh_out, fpfh_cnt, fpfh_small;
-  unsigned char* fpfh_h = nullptr;
-  rgc_fpfh_info fpfh_info{};
-  double fpfh_cell = 0.0;             // rgc_fpfh_set_cell: 0 = the search index's automatic rule
 };
 
 namespace rgcapi {
@@ -501,22 +565,28 @@ int voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float 
                   int mode = rgck::kVgModeCentroid, int* out_index = nullptr);  // mode = rgck::kVgModePick: UniformSampling, out_index (nullable) as out_xyzi
 void host_eig3_sym(const double S[6], double ev[3], double V[9]);  // Jacobi; eigenvalues ASCENDING, columns of V
 
-// ---- rgc_api_search.hip ----
-// The measured grid of a cloud that is searched by the rows of its cells (the search index, the outlier filters).  *cell > 0: the cell size as given
-// (RGC_ERR_GRID_TOO_LARGE beyond max_cells); 0: chosen by the rule include/rgc_hip.h states for rgc_search_set_cloud, and returned.  dsm / hsm: eight
-// scratch ints on the device / the host; who: the entry point, name / grid_name: the cloud, in the error messages.  RGC_ERR_NONFINITE before anything is indexed
-int build_search_grid(rgc_ctx* c, Cloud& cl, double* cell, int* dsm, int* hsm, const char* who, const char* name, const char* grid_name);
-
-// ---- rgc_api_normals.hip: what the feature estimators (normals, FPFH) share ----
+// ---- rgc_api_search.hip: the call frame of the cloud operations (the records above) ----
+// the frame's device words and their pinned mirror (kFrameBytes each), allocated once
+int frame_open(rgc_ctx* c, OpFrame& f);
+// The frame's cloud pointed at d for the length of the call and its measured grid built, as the search index's (build_search_grid: RGC_ERR_NONFINITE before
+// anything is indexed; the frame's cell knob > 0 is the cell size, RGC_ERR_GRID_TOO_LARGE beyond max_cells; 0 selects it by the rule include/rgc_hip.h
+// states for rgc_search_set_cloud).  who: the entry point, name / grid_name: the cloud, in the error messages.  The caller's pointer is not kept,
+// whatever happens.  *cell: the cell size used; f.cl.grid and f.cl.sorted() are the call's to read afterwards
+int index_cloud(rgc_ctx* c, OpFrame& f, const float* d, int stride_f, int n, const char* who, const char* name, const char* grid_name, double* cell);
 // a cloud on the device: the caller's pointer, or a host caller's records packed to 12 bytes in `stage`
 int stage_cloud(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, DevBuf& stage, const char* what, const float** d, int* stride_f);
-// where an output goes on the device: the caller's buffer, or scratch for a host caller; nullptr when it is not asked for
+// What is read of n whole records: through x, y, z of the last one, and through its fourth float too when records are written out from records that
+// have one (`fourth`).  stage_records: the caller's device pointer, or a host caller's records up to there in `stage`; the stride stays the caller's
+inline size_t record_bytes(int n, int stride_bytes, bool fourth) { return (size_t)n * stride_bytes - (stride_bytes - (fourth && stride_bytes >= 16 ? 16 : 12)); }
+int stage_records(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, bool fourth, DevBuf& stage, const char* what, const float** d);
+// Where an output goes on the device: the caller's buffer, or scratch for a host caller; nullptr when it is not asked for -- unless the call
+// `need`s it as scratch anyway (the filters' per-point value, FPFH's first pass)
 template <class T>
-int place_output(rgc_ctx* c, T* user, size_t bytes, int on_device, DevBuf& scratch, const char* what, T** d) {
+int place_output(rgc_ctx* c, T* user, size_t bytes, int on_device, DevBuf& scratch, const char* what, T** d, bool need = false) {
   *d = nullptr;
-  if (!user) return RGC_OK;
+  if (!user && !need) return RGC_OK;
   int rc;
-  if (on_device) {
+  if (user && on_device) {
     if ((rc = check_device_range(c, user, bytes, what))) return rc;
     *d = user;
     return RGC_OK;
@@ -524,6 +594,41 @@ int place_output(rgc_ctx* c, T* user, size_t bytes, int on_device, DevBuf& scrat
   if ((rc = ensure(c, scratch, bytes))) return rc;
   *d = scratch.as<T>();
   return RGC_OK;
+}
+// a result on its way to the caller, behind the call's launches: a download, or a copy on the device for a device caller (dst nullable)
+int copy_out(rgc_ctx* c, void* dst, const void* src, size_t bytes, int on_device);
+// offsets[0] = 0 (nullable): all a call without points writes
+int write_empty_offsets(rgc_ctx* c, int* offsets, int on_device);
+// the selection's int arrays for n points: the flags, their scan, its block sums (out / idx are placed by the caller: place_output)
+int selection_scratch(rgc_ctx* c, Selection& sel, int n);
+// The tail that turns sel.flag into records: the scan, the records and indices (outlier_emit), then ONE read-back -- the call's own read-out
+// (home.h <- home.d, nullable) and the number kept (*home.h_kept, pinned) -- and the wait.  A host caller's kept rows are enqueued behind it: the
+// caller waits for them, behind whatever else it downloads
+struct EmitTo {  // where the records and indices go (each pair nullable together): on the device, and a host caller's own arrays
+  float* d_out;
+  int* d_index;
+  float* out_xyzc;
+  int* out_index;
+};
+struct EmitHome {  // what comes home behind the chain
+  void* h;
+  const void* d;
+  size_t bytes;
+  int* h_kept;
+};
+int emit_selected(rgc_ctx* c, Selection& sel, const float* d_in, int stride_f, int n, int on_device, const EmitTo& to, const EmitHome& home);
+// what the four rgc_*_set_cell share
+int set_cell_of(rgc_ctx* c, double* knob, double cell, const char* who);
+// the read-out words' slots folded: word k's sum, or its maximum
+inline unsigned long long sum_words(const rgck::StatWords& w, int k) {
+  unsigned long long a = 0;
+  for (int j = 0; j < rgck::kStatSlots; j++) a += w[j][k];
+  return a;
+}
+inline unsigned long long max_words(const rgck::StatWords& w, int k) {
+  unsigned long long a = 0;
+  for (int j = 0; j < rgck::kStatSlots; j++) a = w[j][k] > a ? w[j][k] : a;
+  return a;
 }
 
 // ---- rgc_api_lsq.hip: the LM driver of every registration method ----

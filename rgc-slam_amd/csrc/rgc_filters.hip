@@ -1,5 +1,5 @@
 // rgc_filters.hip -- gfx950 kernels of the outlier filters (rgc_outlier_*): pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval of a cloud
-// against itself, on a grid of the filters' own (rgc_ctx::filter_cl).  The machinery is the search index's (rgc_search.hip, rgc_nn.h): the grid's
+// against itself, on a grid of the filters' own (rgcapi::OutlierRecord).  The machinery is the search index's (rgc_search.hip, rgc_nn.h): the grid's
 // contiguous row ranges, the fp32 key dist2 (never FMA-contracted: -ffp-contract=off), cube_bound, a group of lanes per point.  What is new is a
 // consumer that never materialises the rows: the queries ARE the indexed points, walked in the grid's sorted order, and what leaves a group is one
 // float (the mean distance) or one int (the ball's count) at the point's ORIGINAL index.  No output bit depends on the grid or the cell size.
@@ -38,7 +38,7 @@ constexpr unsigned kFlNone = ~0u;  // an empty list slot: behind every key (a ke
 int outlier_group() { return FL_GROUP; }
 
 // the read-out words (OutlierStats::words): the group leaders' sums of a workgroup -- a wave's shuffle tree, the waves' sums through LDS -- added into the
-// workgroup's slot: one integer atomic per workgroup and word, spread over kOutlierSlots cache lines.  Called by every thread of the workgroup
+// workgroup's slot: one integer atomic per workgroup and word, spread over kStatSlots cache lines.  Called by every thread of the workgroup
 __device__ __forceinline__ void fl_stats_add(OutlierStats* st, unsigned long long cand, unsigned long long grew) {
   __shared__ unsigned long long part[FL_T / FL_WAVE][2];
   cand = wave_sum_u64(cand);
@@ -52,7 +52,7 @@ __device__ __forceinline__ void fl_stats_add(OutlierStats* st, unsigned long lon
     unsigned long long t = 0;
 #pragma unroll
     for (int j = 0; j < FL_T / FL_WAVE; j++) t += part[j][threadIdx.x];
-    if (t) atomicAdd(&st->words[blockIdx.x & (kOutlierSlots - 1)][threadIdx.x], t);
+    if (t) atomicAdd(&st->words[blockIdx.x & (kStatSlots - 1)][threadIdx.x], t);
   }
 }
 

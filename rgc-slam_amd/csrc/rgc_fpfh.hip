@@ -1,5 +1,5 @@
 // rgc_fpfh.hip -- gfx950 kernels of the FPFH descriptors (rgc_fpfh_*): pcl::FPFHEstimation, 33 bins per query from the normals of everything within a
-// radius, on a grid of the call's own over the surface cloud (rgc_ctx::fpfh_cl).  The grid walk is rgc_nn.h's ball walk (in step, three rows fetched
+// radius, on a grid of the call's own over the surface cloud (rgcapi::FpfhRecord).  The grid walk is rgc_nn.h's ball walk (in step, three rows fetched
 // together), as k_nrm_radius uses it.  The semantics are stated in include/rgc_hip.h.
 //
 // k_fpfh_check           a query with a non-finite coordinate raises the flag word (a plain store of 1); the normals of the surface cloud, whatever their
@@ -57,7 +57,7 @@ __device__ __forceinline__ void fpfh_stats_add(FpfhStats* st, unsigned long long
     unsigned long long t = 0;
 #pragma unroll
     for (int j = 0; j < FP_T / FP_WAVE; j++) t += part[j][threadIdx.x];
-    if (t) atomicAdd(&st->words[blockIdx.x & (kFpfhSlots - 1)][threadIdx.x], t);
+    if (t) atomicAdd(&st->words[blockIdx.x & (kStatSlots - 1)][threadIdx.x], t);
   }
 }
 

@@ -438,10 +438,12 @@ void search_sort_rows(hipStream_t s, const int* off, int nq, int longest, unsign
 void search_unpack(hipStream_t s, const unsigned long long* ent, long long total, int* idx, float* sq /* nullable */);
 // ---- the outlier filters (rgc_outlier_*, rgc_filters.hip): a cloud against itself on a grid of its own; every output at the ORIGINAL index ----
 // What a call reads back: SOR's statistics as k_sor_fold posts them, and the read-out words -- indexed points looked at (word 0), points whose cube of cells
-// grew (word 1) -- as kOutlierSlots partial sums a cache line apart: a workgroup adds its sums into slot (block & (kOutlierSlots - 1)), the host adds the
+// grew (word 1) -- as kStatSlots partial sums a cache line apart: a workgroup adds its sums into slot (block & (kStatSlots - 1)), the host adds the
 // slots.  (One word for every wave of a launch to add into serialises the launch: at 1 M points the kernels' time was the atomics', whatever the walk did.)
-constexpr int kOutlierSlots = 32;
-struct OutlierStats { double mean, stddev, threshold, pad; unsigned long long words[kOutlierSlots][8]; };
+// The clusters', the normals' and the descriptors' read-out words are laid out the same way, behind heads of their own
+constexpr int kStatSlots = 32;
+using StatWords = unsigned long long[kStatSlots][8];
+struct OutlierStats { double mean, stddev, threshold, pad; StatWords words; };
 constexpr int kOutlierMaxMeanK = 63;  // mean_k + 1 entries: the largest list tier of k_sor_meandist
 int  outlier_group();          // lanes per point of this build
 int  outlier_tier(int mean_k); // the list length k_sor_meandist runs mean_k with: 4, 8, 16, 32 or 64
@@ -459,10 +461,9 @@ void outlier_flag(hipStream_t s, const float* d, const int* cnt, int n, const Ou
 void outlier_emit(hipStream_t s, const float* in, int stride_f, int n, const int* flag, const int* off, float* out, int* out_index);
 // ---- Euclidean cluster extraction (rgc_cluster_*, rgc_cluster.hip): the connected components of the key < r2 graph of a cloud on a grid of its own ----
 // What a call reads back: the error word (!= 0: a find / unite loop ran past its iteration cap -- a logic error, RGC_ERR_HIP) and the read-out words as
-// kClusterSlots partial results a cache line apart, as OutlierStats': word 0 indexed points looked at (summed), word 1 components (summed), word 2 the
+// kStatSlots partial results a cache line apart, as OutlierStats': word 0 indexed points looked at (summed), word 1 components (summed), word 2 the
 // largest component's size (the slots' maximum)
-constexpr int kClusterSlots = 32;
-struct ClusterStats { int err; int pad[15]; unsigned long long words[kClusterSlots][8]; };
+struct ClusterStats { int err; int pad[15]; StatWords words; };
 constexpr int kClusterRadixTile = 1024;   // pairs per workgroup of a radix pass
 constexpr int kClusterRadixDigits = 256;  // 8-bit digits
 int  cluster_group();              // lanes per point of this build's linking kernel
@@ -484,10 +485,9 @@ void cluster_rank(hipStream_t s, int n, int m, const int* key, const int* val, i
 // labels[i] (nullable) = flag_p[i] ? rank_at[comp[i]] : -1; pkey / pval (nullable together) at off_p[i]: that rank and i, for the kept points
 void cluster_labels(hipStream_t s, int n, const int* flag_p, const int* off_p, const int* comp, const int* rank_at, int* labels, int* pkey, int* pval);
 // ---- surface normal estimation (rgc_normal_*, rgc_normals.hip): a normal and a curvature per query from its neighbourhood in a surface cloud's grid ----
-// What a call reads back: the queries' non-finite flag and the read-out words as kNormalSlots partial sums a cache line apart, as OutlierStats': word 0
+// What a call reads back: the queries' non-finite flag and the read-out words as kStatSlots partial sums a cache line apart, as OutlierStats': word 0
 // indexed points looked at, word 1 queries whose cube of cells grew (k route), word 2 valid queries (three members or more)
-constexpr int kNormalSlots = 32;
-struct NormalStats { int nonfinite; int pad[15]; unsigned long long words[kNormalSlots][8]; };
+struct NormalStats { int nonfinite; int pad[15]; StatWords words; };
 struct NormalSign { float vx, vy, vz; int flip; };                  // the viewpoint and the sign rule (rgc_normal_params)
 struct NormalOut { float* n4; double* cov6; double* cen; int* cnt; };  // per query, each nullable: (nx, ny, nz, curvature), {xx,xy,xz,yy,yz,zz}, the centroid, the members
 int  normal_group();         // lanes per query of this build's k route ...
@@ -503,9 +503,8 @@ void normal_knn(hipStream_t s, const float* Q, int qstride_f, int nq, const floa
 void normal_radius(hipStream_t s, const float* Q, int qstride_f, int nq, const SortedCloud& cl, float r2, double r, const NormalSign& sg, const NormalOut& out, NormalStats* st);
 // ---- FPFH descriptors (rgc_fpfh_*, rgc_fpfh.hip): 33 bins per query from the normals of a surface cloud's balls, in two passes over its grid ----
 // What a call reads back, as NormalStats: word 0 indexed points looked at (every pass), word 1 non-skipped pair terms, word 2 queries with a member
-constexpr int kFpfhSlots = 32;
 constexpr int kFpfhBins = 33;
-struct FpfhStats { int nonfinite; int pad[15]; unsigned long long words[kFpfhSlots][8]; };
+struct FpfhStats { int nonfinite; int pad[15]; StatWords words; };
 // *flag = 1 if a query has a non-finite coordinate (Q nullable: the cloud is its own surface, its grid build checks it); N4[i] = the normal of surface
 // point i with w = 1 where its three components are finite, else 0
 void fpfh_check(hipStream_t s, const float* Q, int qstride_f, int nq, const float* N, int nstride_f, int ns, float4* N4, int* flag);

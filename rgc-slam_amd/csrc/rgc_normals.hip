@@ -1,5 +1,5 @@
 // rgc_normals.hip -- gfx950 kernels of surface normal estimation (rgc_normal_*): pcl::NormalEstimation, a unit normal and a curvature per query from the
-// second moment of its neighbourhood in a surface cloud, on a grid of the call's own (rgc_ctx::normal_cl).  The machinery is shared: the grid walk, the
+// second moment of its neighbourhood in a surface cloud, on a grid of the call's own (rgcapi::NormalRecord).  The machinery is shared: the grid walk, the
 // per-lane (key, index) lists and cube_bound of rgc_nn.h, eig3_sym of rgc_cov.h, the shifted-origin fp64 moment of rgc_rbf.hip.  What is new is a
 // consumer that joins them without materialising a row: what leaves a group of lanes is the normal, the curvature and (where asked for) the covariance,
 // the centroid and the member count at the query's index.  The semantics are stated in include/rgc_hip.h.
@@ -66,7 +66,7 @@ __device__ __forceinline__ void nrm_stats_add(NormalStats* st, unsigned long lon
     unsigned long long t = 0;
 #pragma unroll
     for (int j = 0; j < NR_T / NR_WAVE; j++) t += part[j][threadIdx.x];
-    if (t) atomicAdd(&st->words[blockIdx.x & (kNormalSlots - 1)][threadIdx.x], t);
+    if (t) atomicAdd(&st->words[blockIdx.x & (kStatSlots - 1)][threadIdx.x], t);
   }
 }
 
