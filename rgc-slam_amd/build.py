@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("RGC_LIB_OUT") or os.path.join(HERE, "librgc_hip.so")
 OBJDIR = CSRC if not os.environ.get("RGC_LIB_OUT") else os.path.splitext(LIB)[0] + "_obj"
-SRCS = ["rgc_api.hip", "rgc_api_pre.hip", "rgc_api_mapping.hip", "rgc_api_lsq.hip", "rgc_api_ndt.hip", "rgc_api_gicp.hip", "rgc_api_pgo.hip", "rgc_api_search.hip", "rgc_api_filters.hip", "rgc_api_cluster.hip", "rgc_api_plane.hip", "rgc_api_normals.hip", "rgc_api_fpfh.hip", "rgc_kernels.hip", "rgc_pre.hip", "rgc_keyframes.hip", "rgc_ndt.hip", "rgc_gicp.hip", "rgc_gicp_st.hip", "rgc_gicp_mp.hip", "rgc_vgicp_radius.hip", "rgc_search.hip", "rgc_filters.hip", "rgc_cluster.hip", "rgc_plane.hip", "rgc_normals.hip", "rgc_fpfh.hip", "rgc_rbf.hip", "rgc_pgo.hip", "rgc_frontend.hip", "rgc_host.cpp"]
+SRCS = ["rgc_api.hip", "rgc_api_pre.hip", "rgc_api_frontend.hip", "rgc_api_mapreg.hip", "rgc_api_map.hip", "rgc_api_wire.hip", "rgc_api_icp.hip", "rgc_api_keyframes.hip", "rgc_api_lsq.hip", "rgc_api_ndt.hip", "rgc_api_gicp.hip", "rgc_api_pgo.hip", "rgc_api_search.hip", "rgc_api_filters.hip", "rgc_api_cluster.hip", "rgc_api_plane.hip", "rgc_api_normals.hip", "rgc_api_fpfh.hip", "rgc_kernels.hip", "rgc_pre.hip", "rgc_keyframes.hip", "rgc_ndt.hip", "rgc_gicp.hip", "rgc_gicp_st.hip", "rgc_gicp_mp.hip", "rgc_vgicp_radius.hip", "rgc_search.hip", "rgc_filters.hip", "rgc_cluster.hip", "rgc_plane.hip", "rgc_normals.hip", "rgc_fpfh.hip", "rgc_rbf.hip", "rgc_pgo.hip", "rgc_frontend.hip", "rgc_host.cpp"]
 DEPS = SRCS + ["rgc_ctx.h", "rgc_kernels.h", "rgc_nn.h", "rgc_lm.h", "rgc_lm_decide.h", "rgc_cov.h", "rgc_terms.h", "rgc_plane.h", os.path.join("..", "..", "include", "rgc_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",

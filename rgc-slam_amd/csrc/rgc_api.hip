@@ -1,7 +1,7 @@
 // rgc_api.hip -- host side of librgc_hip.so, the core: context, device buffers, the clouds' preparation, the VGICP registration
 // (rgc_align*, rgc_linearize, ...), its getters and setters, statistics and profiling.  The per-point work is in rgc_kernels.hip (the
 // linearisation under RGC_DIRECT_RADIUS: rgc_vgicp_radius.hip).  The
-// rest of the C-ABI of include/rgc_hip.h: rgc_api_pre.hip (B2 / B3 / B9, the front end), rgc_api_mapping.hip (f1-f5), rgc_api_lsq.hip
+// rest of the C-ABI of include/rgc_hip.h is in one rgc_api_*.hip per subsystem (the table in DESIGN.md), among them rgc_api_lsq.hip
 // (the LM driver of lsq_registration_impl.hpp:53-172 that rgc_align's host route shares with NDT and FastGICP); rgc_ctx.h is what they share.
 //
 // No CPU fallback exists: every entry point fails with RGC_ERR_HIP when the HIP runtime / device is missing.
@@ -67,6 +67,30 @@ int ensure(rgc_ctx* c, DevBuf& b, size_t bytes) {
   return RGC_OK;
 }
 
+int ensure_pinned(rgc_ctx* c, PinnedBuf& b, size_t need, size_t grow_to) {
+  if (need <= b.cap) return RGC_OK;
+  if (b.p) { HIPCHK(c, hipHostFree(b.p)); b.p = nullptr; b.cap = 0; }
+  HIPCHK(c, hipHostMalloc((void**)&b.p, grow_to, hipHostMallocDefault));
+  b.cap = grow_to;
+  return RGC_OK;
+}
+
+int grow_store(rgc_ctx* c, DevBuf& b, size_t held, size_t points, bool preserve) {
+  const size_t bytes = points * 16;
+  if (bytes <= b.cap && b.p) return RGC_OK;
+  void* np = nullptr;
+  const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 20);
+  HIPCHK(c, hipMalloc(&np, want));
+  if (b.p) {
+    if (preserve && held) HIPCHK(c, hipMemcpyAsync(np, b.p, held * 16, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipFree(b.p));
+  }
+  b.p = np;
+  b.cap = want;
+  return RGC_OK;
+}
+
 // An integrator's aid (RGC_CHECK_POINTERS=1; off by default: a look-up per pointer per call, microseconds on a frame's critical path): is what
 // the caller calls a device buffer one -- device memory of THIS context's device, with room for `bytes` behind p?  A host pointer handed to
 // a *_device entry, a buffer of another GPU, a count larger than the allocation: RGC_ERR_INVALID instead of a memory fault on the device.
@@ -104,7 +128,7 @@ static void release_cloud(Cloud& cl) {
   for (DevBuf* b : shared_bufs(cl)) release(*b);
   for (DevBuf* b : {&cl.need, &cl.qlist, &cl.cell_list, &cl.seed, &cl.nbr, &cl.rank_of, &cl.pos_of, &cl.qrank, &cl.map_copy, &cl.todo, &cl.cache_small}) release(*b);
 }
-// a record of a registration method or a cloud operation (rgc_ctx.h): its device buffers, its pinned mirrors, its clouds
+// a record of a subsystem (rgc_ctx.h): its device buffers, its pinned mirrors, its clouds
 template <class Record>
 static void release_record(Record& r) {
   for (DevBuf* b : r.bufs()) release(*b);
@@ -677,7 +701,7 @@ static CovRoute cov_route(const rgc_ctx* c, const Cloud& cl, bool is_target) {
   r.self_timed = profiled(c, is_target ? RGC_K_KNN_COV : RGC_K_KNN_COV_SRC) && rgck::knn_bulk_times_itself(is_target, n, k, r.bulk);
   const bool stage_prof = profiled(c, RGC_K_VOXEL) || profiled(c, RGC_K_KNN_COOP);
   const bool want = c->voxel_impl == 2 || (c->voxel_impl == 0 && c->src_held);
-  r.fused = is_target && &cl == &c->tgt && !c->tgt_owner && !c->map_bound && want && !stage_prof && k <= 32 && rgck::knn_bulk_fuses_voxels(true, n, k, r.bulk);
+  r.fused = is_target && &cl == &c->tgt && !c->tgt_owner && !c->map.bound && want && !stage_prof && k <= 32 && rgck::knn_bulk_fuses_voxels(true, n, k, r.bulk);
   r.stream_coop = !is_target && c->coop_stream_on && k <= 32 && !profiled(c, RGC_K_KNN_COOP_SRC);
   return r;
 }
@@ -820,7 +844,7 @@ int set_cloud(rgc_ctx* c, Cloud& cl, bool is_target, const float* xyz, int n, in
   cl.n = 0;
   drop_frozen(c);
   c->deferred_known = false;
-  if (is_target) c->map_bound = false;
+  if (is_target) c->map.bound = false;
   if (!xyz || n < 0) return fail(c, RGC_ERR_INVALID, "null cloud");
   if (!stride_ok(stride_bytes)) return fail(c, RGC_ERR_INVALID, "stride_bytes must be a multiple of 4 and >= 12");
   if (n > (1 << 27)) return fail(c, RGC_ERR_INVALID, "cloud has %d points, the limit is 2^27 (32-bit byte offsets into the sorted array)", n);
@@ -828,7 +852,7 @@ int set_cloud(rgc_ctx* c, Cloud& cl, bool is_target, const float* xyz, int n, in
     return fail(c, RGC_ERR_TOO_FEW_POINTS, "%s cloud has %d points, need >= k = %d", is_target ? "target" : "source", n, c->prm.k_correspondences);
   HIPCHK(c, hipSetDevice(c->device));
   const int stride_f = stride_bytes / 4;
-  if (on_device) { const int rk = check_device_range(c, xyz, (size_t)n * stride_bytes - (stride_bytes - 12), is_target ? "target cloud" : "source cloud"); if (rk) return rk; }
+  if (on_device) { const int rk = check_device_range(c, xyz, record_bytes(n, stride_bytes, false), is_target ? "target cloud" : "source cloud"); if (rk) return rk; }
   if (on_device) {
     cl.in = xyz;
     if (!is_target) c->src_in_pending = false;  // (no upload of this scan to wait for)
@@ -1245,9 +1269,9 @@ int rgc_create(int hip_device, const rgc_params* params, rgc_ctx** out) {
   ok = ok && hipEventCreateWithFlags(&c->src_read_done, kDevEvent) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->lm_tail, kDevEvent) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->tgt_prepared, kDevEvent) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&c->vg_done, hipEventDisableTiming) == hipSuccess;
-  ok = ok && hipHostMalloc((void**)&c->h_vg, 4 * sizeof(int), hipHostMallocDefault) == hipSuccess;
-  ok = ok && hipEventCreateWithFlags(&c->kf_uploaded, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&c->vg.done, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipHostMalloc((void**)&c->vg.h_res, 4 * sizeof(int), hipHostMallocDefault) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&c->kfs.uploaded, hipEventDisableTiming) == hipSuccess;
   if (const char* e = getenv("RGC_SPEC_GRID")) c->spec_on = atoi(e) != 0;
   if (const char* e = getenv("RGC_KNN_SEEDS")) c->seeds_on = atoi(e) != 0;
   if (const char* e = getenv("RGC_KNN_CACHE")) c->cache_on = atoi(e) != 0;
@@ -1279,16 +1303,8 @@ void rgc_destroy(rgc_ctx* c) {
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);
   release_cloud(c->src);
   release_cloud(c->tgt);
-  release_cloud(c->aux);
-  release_cloud(c->mr_map[0]);
-  release_cloud(c->mr_map[1]);
-  for (DevBuf& b : c->mr_feat) release(b);
-  for (DevBuf& b : c->mr_fac) release(b);
-  release(c->mr_partials);
-  release(c->mr_small);
-  for (DevBuf& b : c->fe) release(b);
-  for (DevBuf* b : {&c->map_store[0], &c->map_store[1], &c->map_target}) release(*b);
-  for (DevBuf* b : {&c->corr_v, &c->corr_M, &c->corr_v2, &c->corr_M2, &c->partials, &c->ipartials, &c->scratch, &c->pre_in, &c->pre_out, &c->vg_order, &c->vg_pos, &c->vg_tmp, &c->vg_leaf}) release(*b);
+  // the VGICP core, the one subsystem without a record (its two clouds above, the small words and mirrors below); everything else through its record
+  for (DevBuf* b : {&c->corr_v, &c->corr_M, &c->corr_v2, &c->corr_M2, &c->partials, &c->ipartials, &c->scratch, &c->lm_state, &c->fit_partials, &c->vr_offs}) release(*b);
   if (c->d_small) (void)hipFree(c->d_small);
   if (c->d_out) (void)hipFree(c->d_out);
   if (c->h_small) (void)hipHostFree(c->h_small);
@@ -1296,16 +1312,13 @@ void rgc_destroy(rgc_ctx* c) {
   if (c->h_lm) (void)hipHostFree(c->h_lm);
   if (c->h_post) (void)hipHostFree(c->h_post);
   if (c->h_early) (void)hipHostFree(c->h_early);
-  if (c->h_stage) (void)hipHostFree(c->h_stage);
-  release(c->lm_state);
-  release(c->fit_partials);
-  if (c->vg_done) (void)hipEventDestroy(c->vg_done);
-  if (c->h_vg) (void)hipHostFree(c->h_vg);
-  for (DevBuf* b : {&c->kf_store[0], &c->kf_store[1], &c->kf_store[2], &c->kf_table, &c->kf_raw, &c->kf_filt, &c->us_index, &c->kf_pos, &c->kf_travel,
-                    &c->kf_ids, &c->kf_flag, &c->kf_scan, &c->kf_bsum, &c->kf_sel, &c->kf_sel_out, &c->kf_small}) release(*b);
-  if (c->kf_h_table) (void)hipHostFree(c->kf_h_table);
-  for (DevBuf* b : {&c->pgo_i, &c->pgo_d, &c->pgo_M}) release(*b);
-  release(c->vr_offs);
+  if (c->vg.done) (void)hipEventDestroy(c->vg.done);
+  release_record(c->mapreg);
+  release_record(c->map);
+  release_record(c->kfs);
+  release_record(c->pgo);
+  release_record(c->vg);
+  release_record(c->fe);
   release_record(c->ndt);
   release_record(c->gicp_sums);
   release_record(c->gicp);
@@ -1317,7 +1330,7 @@ void rgc_destroy(rgc_ctx* c) {
   release_record(c->plane);
   release_record(c->normal);
   release_record(c->fpfh);
-  if (c->kf_uploaded) (void)hipEventDestroy(c->kf_uploaded);
+  if (c->kfs.uploaded) (void)hipEventDestroy(c->kfs.uploaded);
   if (c->src_ready) (void)hipEventDestroy(c->src_ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   if (c->main_mark) (void)hipEventDestroy(c->main_mark);
@@ -1435,7 +1448,7 @@ int rgc_share_target(rgc_ctx* c, rgc_ctx* owner) {
   c->tgt_owner = owner;
   c->tgt_owner_gen = owner->tgt_generation;
   c->tgt_owner_uid = owner->uid;
-  c->map_bound = false;
+  c->map.bound = false;
   drop_frozen(c);
   c->deferred_known = false;
   c->main_has_target_prep = false;
@@ -1460,7 +1473,7 @@ int rgc_set_regularization_method(rgc_ctx* c, int method) {
   if (method < RGC_REG_NONE || method > RGC_REG_FROBENIUS) return fail(c, RGC_ERR_INVALID, "rgc_set_regularization_method: %d is not a RegularizationMethod", method);
   if (method != c->reg_method) {  // the covariances of the clouds set so far were computed under the other method (the reference computes them at align())
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map.bound = false;
   }
   c->reg_method = method;
   return RGC_OK;
@@ -1471,7 +1484,7 @@ int rgc_set_covariance_estimation(rgc_ctx* c, int method) {
   if (method != RGC_COV_KNN && method != RGC_COV_RBF) return fail(c, RGC_ERR_INVALID, "rgc_set_covariance_estimation: %d is neither RGC_COV_KNN nor RGC_COV_RBF", method);
   if (method != c->cov_method) {  // the clouds' covariances were estimated the other way: the rule of rgc_set_regularization_method
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map.bound = false;
   }
   c->cov_method = method;
   return RGC_OK;
@@ -1492,7 +1505,7 @@ int rgc_set_rbf_kernel(rgc_ctx* c, double kernel_width, double max_dist) {
   if (max_dist <= 0.0) max_dist = 5.0 * kernel_width;  // fast_vgicp_cuda_impl.hpp:46-51
   if (c->cov_method == RGC_COV_RBF && (kernel_width != c->rbf_width || max_dist != c->rbf_max_dist)) {
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map.bound = false;
   }
   c->rbf_width = kernel_width;
   c->rbf_max_dist = max_dist;
@@ -1512,7 +1525,7 @@ int rgc_set_voxel_accumulation_mode(rgc_ctx* c, int mode) {
   const bool was = c->voxel_mode == RGC_VOXEL_MULTIPLICATIVE, is = mode == RGC_VOXEL_MULTIPLICATIVE;
   if (was != is) {  // (ADDITIVE <-> ADDITIVE_WEIGHTED changes nothing: one voxel class in the vendored FastVGICP, fast_vgicp_voxel.hpp:137-141)
     if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
+    c->src.ready = c->tgt.ready = false; drop_frozen(c); c->deferred_known = false; c->map.bound = false;
   }
   c->voxel_mode = mode;
   return RGC_OK;
@@ -1940,7 +1953,7 @@ int rgc_get_aligned_device(rgc_ctx* c, const float T[16], float* d_out, int stri
   if (!c || !T || !d_out) return RGC_ERR_INVALID;
   if (!c->src.ready) return fail(c, RGC_ERR_NO_INPUT, "source not set");
   if (!stride_ok(stride_bytes)) return fail(c, RGC_ERR_INVALID, "bad stride");
-  { int rk = check_device_range(c, d_out, (size_t)c->src.n * stride_bytes - (stride_bytes - 12), "rgc_get_aligned_device: d_out"); if (rk) return rk; }
+  { int rk = check_device_range(c, d_out, record_bytes(c->src.n, stride_bytes, false), "rgc_get_aligned_device: d_out"); if (rk) return rk; }
   HIPCHK(c, hipSetDevice(c->device));
   int rc = join_source(c);
   if (rc) return rc;
@@ -2088,7 +2101,7 @@ int rgc_clear_source(rgc_ctx* c) {
 int rgc_clear_target(rgc_ctx* c) {
   if (!c) return RGC_ERR_INVALID;
   if (solve_in_flight(c)) return fail(c, RGC_ERR_INVALID, "a solve is in flight on this context: call rgc_align_end first");
-  c->tgt.ready = false; c->tgt.n = 0; c->tgt.spec_used = false; drop_frozen(c); c->deferred_known = false; c->map_bound = false;
+  c->tgt.ready = false; c->tgt.n = 0; c->tgt.spec_used = false; drop_frozen(c); c->deferred_known = false; c->map.bound = false;
   return RGC_OK;
 }
 
@@ -2123,10 +2136,10 @@ int rgc_swap_source_and_target(rgc_ctx* c) {
   // A target bound to the resident map (rgc_map_commit) was set from the map's own filter output buffer, which the NEXT commit overwrites:
   // as the scan it would keep pointing there (tests/fuzz/fuzz_api.py: swapped back later, it was prepared from another cloud's
   // points).  It takes a copy of its own with it.
-  if (c->map_target.p && c->tgt.in == c->map_target.as<const float>()) {
+  if (c->map.target.p && c->tgt.in == c->map.target.as<const float>()) {
     const size_t bytes = (size_t)c->tgt.n * 16;
     if ((rc = ensure(c, c->tgt.in_copy, bytes))) { drop_kept(); return rc; }
-    if (hipMemcpyAsync(c->tgt.in_copy.p, c->map_target.p, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); drop_kept(); return fail(c, RGC_ERR_HIP, "swap: copy of the map's target failed"); }
+    if (hipMemcpyAsync(c->tgt.in_copy.p, c->map.target.p, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); drop_kept(); return fail(c, RGC_ERR_HIP, "swap: copy of the map's target failed"); }
     c->tgt.in = c->tgt.in_copy.as<const float>();
     c->tgt.stride_f = 4;
   }
@@ -2135,7 +2148,7 @@ int rgc_swap_source_and_target(rgc_ctx* c) {
   std::swap(c->src.stride_f, c->tgt.stride_f);
   std::swap(c->src.n, c->tgt.n);
   c->src.ready = c->tgt.ready = false;
-  drop_frozen(c); c->deferred_known = false; c->map_bound = false;
+  drop_frozen(c); c->deferred_known = false; c->map.bound = false;
   if ((rc = prepare_cloud(c, c->tgt, true, /*force_bbox=*/true))) { drop_kept(); return rc; }
   if ((rc = prepare_cloud(c, c->src, false, /*force_bbox=*/true))) { drop_kept(); return rc; }
   if (kept[0].on || kept[1].on) {

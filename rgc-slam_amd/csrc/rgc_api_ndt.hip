@@ -49,7 +49,7 @@ static int ndt_set_cloud(rgc_ctx* c, int which, const float* xyz, int n, int str
   if (n > (1 << 27)) return fail(c, RGC_ERR_INVALID, "cloud has %d points, the limit is 2^27", n);
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if (on_device && (rc = check_device_range(c, xyz, (size_t)n * stride_bytes - (stride_bytes - 12), which ? "rgc_ndt_set_source_device" : "rgc_ndt_set_target_device"))) return rc;
+  if (on_device && (rc = check_device_range(c, xyz, record_bytes(n, stride_bytes, false), which ? "rgc_ndt_set_source_device" : "rgc_ndt_set_target_device"))) return rc;
   Cloud& cl = c->ndt.cl[which];
   if ((rc = ensure(c, cl.in_copy, (size_t)n * 12))) return rc;
   HIPCHK(c, hipMemcpy2DAsync(cl.in_copy.p, 12, xyz, (size_t)stride_bytes, 12, (size_t)n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));

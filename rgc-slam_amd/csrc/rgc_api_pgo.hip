@@ -49,12 +49,12 @@ int pgo_build(rgc_ctx* c, const int* ids, int n_ids, const rgc_pgo_loop* loops, 
   P.n = n_ids;
   P.pose.resize(n_ids);
   P.x.resize((size_t)4 * n_ids);
-  std::vector<const rgc_ctx::KfRec*> rec(n_ids);
+  std::vector<const KeyframeRecord::KfRec*> rec(n_ids);
   for (int i = 0; i < n_ids; i++) {
-    const auto it = c->kf_index.find(ids[i]);
-    if (it == c->kf_index.end()) return fail(c, RGC_ERR_INVALID, "rgc_pgo: keyframe %d is not in the store", ids[i]);
+    const auto it = c->kfs.index.find(ids[i]);
+    if (it == c->kfs.index.end()) return fail(c, RGC_ERR_INVALID, "rgc_pgo: keyframe %d is not in the store", ids[i]);
     if (!pos.emplace(ids[i], i).second) return fail(c, RGC_ERR_INVALID, "rgc_pgo: keyframe %d is selected twice", ids[i]);
-    rec[i] = &c->kf[it->second];
+    rec[i] = &c->kfs.recs[it->second];
     P.pose[i] = rec[i]->pose;
     P.x[4 * i] = rec[i]->pose.yaw * rad2deg;                       // euler_array[keyI][0], :2355
     P.x[4 * i + 1] = rec[i]->pose.x; P.x[4 * i + 2] = rec[i]->pose.y; P.x[4 * i + 3] = rec[i]->pose.z;
@@ -126,12 +126,12 @@ int pgo_upload(rgc_ctx* c, PgoHost& P) {
   const size_t n = P.n, E = std::max(P.n_edges, 1), ns = P.sep.size();
   const size_t ni = 2 * E + (n + 1) + P.inc.size() + ns + n + 4;
   const size_t nd = 6 * E + 2 * 4 * n + 2 * rgck::kPgoTerm * E + 2 * 16 * n + 2 * 4 * n + 2 * 8 + rgck::kPgoWs * n + rgck::kPgoSlot * ns + 4 * n + 4 * n;
-  if ((rc = ensure(c, c->pgo_i, ni * sizeof(int)))) return rc;
-  if ((rc = ensure(c, c->pgo_d, nd * sizeof(double)))) return rc;
-  if ((rc = ensure(c, c->pgo_M, 16 * ns * ns * sizeof(double)))) return rc;
+  if ((rc = ensure(c, c->pgo.i, ni * sizeof(int)))) return rc;
+  if ((rc = ensure(c, c->pgo.d, nd * sizeof(double)))) return rc;
+  if ((rc = ensure(c, c->pgo.M, 16 * ns * ns * sizeof(double)))) return rc;
   std::vector<int> hi;
   hi.reserve(ni);
-  int* di = c->pgo_i.as<int>();
+  int* di = c->pgo.i.as<int>();
   auto put = [&](const std::vector<int>& v, size_t count) { const int* p = di + hi.size(); hi.insert(hi.end(), v.begin(), v.begin() + (long)count); return p; };
   P.G.n_nodes = P.n; P.G.n_edges = P.n_edges; P.G.fixed = P.fixed; P.G.n_sep = (int)ns;
   P.G.ij = put(P.ij, 2 * E);
@@ -141,7 +141,7 @@ int pgo_upload(rgc_ctx* c, PgoHost& P) {
   P.G.sep_of = put(P.sep_of, n);
   P.flag = di + hi.size();
   hi.resize(hi.size() + 4, 0);
-  double* dd = c->pgo_d.as<double>();
+  double* dd = c->pgo.d.as<double>();
   auto take = [&](size_t count) { double* p = dd; dd += count; return p; };
   double* meas = take(6 * E);
   P.G.meas = meas;
@@ -214,7 +214,7 @@ int rgc_pgo_optimize(rgc_ctx* c, const int* ids, int n_ids, const rgc_pgo_loop* 
     if (gmax <= 1e-10) { stop = RGC_PGO_STOP_GRADIENT; break; }
     const int nxt = cur ^ 1;
     HIPCHK(c, hipMemsetAsync(P.flag, 0, sizeof(int), s));
-    rgck::pgo_solve(s, P.G, P.terms[cur], P.D[cur], P.g[cur], radius, P.ws, P.slots, c->pgo_M.as<double>(), P.d, P.flag);
+    rgck::pgo_solve(s, P.G, P.terms[cur], P.D[cur], P.g[cur], radius, P.ws, P.slots, c->pgo.M.as<double>(), P.d, P.flag);
     rgck::pgo_step(s, P.G, P.terms[cur], P.D[cur], P.g[cur], P.x_dev[cur], P.d, P.x_dev[nxt], P.part, P.out[cur] + 2);
     rgck::pgo_evaluate(s, P.G, P.x_dev[nxt], P.terms[nxt], P.D[nxt], P.g[nxt], P.out[nxt]);
     HIPCHK(c, hipGetLastError());
@@ -274,7 +274,7 @@ int rgc_pgo_linearize(rgc_ctx* c, const int* ids, int n_ids, const rgc_pgo_loop*
   int hflag = 0;
   if (solve) {
     HIPCHK(c, hipMemsetAsync(P.flag, 0, sizeof(int), s));
-    rgck::pgo_solve(s, P.G, P.terms[0], P.D[0], P.g[0], radius, P.ws, P.slots, c->pgo_M.as<double>(), P.d, P.flag);
+    rgck::pgo_solve(s, P.G, P.terms[0], P.D[0], P.g[0], radius, P.ws, P.slots, c->pgo.M.as<double>(), P.d, P.flag);
     if ((rc = pgo_fetch(c, &hflag, P.flag, sizeof(int)))) return rc;
   }
   HIPCHK(c, hipGetLastError());

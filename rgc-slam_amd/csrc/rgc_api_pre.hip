@@ -1,6 +1,6 @@
 // rgc_api_pre.hip -- host side of the stages around the registration: B2 de-skew, B3 leaf filter, B9 re-framing (rgc_deskew,
-// rgc_transform_cloud, rgc_set_target_reframed, rgc_align_end_reframe, rgc_voxelgrid*) and the A1-A8 front end (rgc_frontend*).
-// The kernels are in rgc_pre.hip and rgc_frontend.hip.
+// rgc_transform_cloud, rgc_set_target_reframed, rgc_align_end_reframe, rgc_voxelgrid*, rgc_uniform_sampling) and the staging of a host
+// caller's cloud (stage_in).  The kernels are in rgc_pre.hip.
 #include "rgc_ctx.h"
 
 using namespace rgcapi;
@@ -9,15 +9,15 @@ using namespace rgcapi;
 int rgcapi::stage_in(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, const float** d_in) {
   if (n > (1 << 27)) return fail(c, RGC_ERR_INVALID, "cloud has %d points, the limit is 2^27", n);  // (every entry point that takes a cloud: one limit)
   if (on_device) {
-    if (n > 0) { const int rk = check_device_range(c, p, (size_t)n * stride_bytes - (stride_bytes - 12), "input cloud"); if (rk) return rk; }
+    if (n > 0) { const int rk = check_device_range(c, p, record_bytes(n, stride_bytes, false), "input cloud"); if (rk) return rk; }
     *d_in = p;
     return RGC_OK;
   }
   const size_t bytes = (size_t)n * stride_bytes;
-  int rc = ensure(c, c->pre_in, bytes);
+  int rc = ensure(c, c->vg.in, bytes);
   if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->pre_in.p, p, bytes, hipMemcpyHostToDevice, c->stream));
-  *d_in = c->pre_in.as<const float>();
+  HIPCHK(c, hipMemcpyAsync(c->vg.in.p, p, bytes, hipMemcpyHostToDevice, c->stream));
+  *d_in = c->vg.in.as<const float>();
   return RGC_OK;
 }
 
@@ -25,7 +25,7 @@ extern "C" {
 
 int rgc_deskew(rgc_ctx* c, float* xyzi, int n, int stride_bytes, const double q[4], const double t[3], int on_device) {
   if (!c || !xyzi || !q || !t || n < 0) return RGC_ERR_INVALID;
-  if (stride_bytes < 16 || (stride_bytes & 3) || stride_bytes > 4096) return fail(c, RGC_ERR_INVALID, "de-skew needs x,y,z,intensity: stride_bytes >= 16");
+  if (!stride4_ok(stride_bytes)) return fail(c, RGC_ERR_INVALID, "de-skew needs x,y,z,intensity: stride_bytes >= 16");
   if (n == 0) return RGC_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const float* d_in;
@@ -57,8 +57,8 @@ int rgc_transform_cloud(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, 
   if (rc) return rc;
   float* d_out = out_xyzi;
   if (!on_device) {
-    if ((rc = ensure(c, c->pre_out, sizeof(float) * 4 * (size_t)n))) return rc;
-    d_out = c->pre_out.as<float>();
+    if ((rc = ensure(c, c->vg.out, sizeof(float) * 4 * (size_t)n))) return rc;
+    d_out = c->vg.out.as<float>();
   }
   rgck::transform_q(c->stream, d_in, stride_bytes / 4, n, rgck::Quat{q[0], q[1], q[2], q[3]}, t, d_out, 4);
   if (!on_device) HIPCHK(c, hipMemcpyAsync(out_xyzi, d_out, sizeof(float) * 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
@@ -83,7 +83,7 @@ static int reframe_args_ok(rgc_ctx* c, const float* d_xyzi, int n, int stride_by
   const char* a0 = (const char*)d_xyzi; const char* a1 = a0 + (size_t)n * stride_bytes;
   const char* b0 = (const char*)d_scratch; const char* b1 = b0 + (size_t)n * 16;
   if (a0 < b1 && b0 < a1) return fail(c, RGC_ERR_INVALID, "rgc_set_target_reframed: d_scratch overlaps d_xyzi");
-  { int rk = check_device_range(c, d_xyzi, (size_t)n * stride_bytes - (stride_bytes - 12), "rgc_set_target_reframed: d_xyzi"); if (rk) return rk; }
+  { int rk = check_device_range(c, d_xyzi, record_bytes(n, stride_bytes, false), "rgc_set_target_reframed: d_xyzi"); if (rk) return rk; }
   { int rk = check_device_range(c, d_scratch, (size_t)n * 16, "rgc_set_target_reframed: d_scratch"); if (rk) return rk; }
   return RGC_OK;
 }
@@ -253,7 +253,7 @@ int rgc_align_end_reframe(rgc_ctx* c, rgc_ctx* next, double Tw[16], const float*
 }  // extern "C"
 
 // The rows chain of the leaf filter on box g (rgc_pre.hip); one read-back: *flags (bits as rgck::vg_rows documents) and *n_out.
-// h_result (nullable): the chain is only ENQUEUED -- its three result ints go to h_result (pinned), c->vg_done is recorded behind the
+// h_result (nullable): the chain is only ENQUEUED -- its three result ints go to h_result (pinned), c->vg.done is recorded behind the
 // copy, and the caller picks them up later (rgc_voxelgrid_begin / _end); flags / n_out are not written then.
 static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, float inv, const rgck::LeafGrid& g, int edge, bool dense, float* d_out,
                           int* flags, int* n_out, rgc_vg_route* rt, int* h_result = nullptr, int mode = rgck::kVgModeCentroid, float leaf = 0.f,
@@ -261,7 +261,7 @@ static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, fl
   hipStream_t s = c->stream;
   int* const d_res = c->d_small->leaf_rows.res;        // rgck::vg_rows' res[3]; res[1], the live flag word, is the block's guard
   const int* const h_res = c->h_small->leaf_rows.res;
-  Cloud& cl = c->aux;
+  Cloud& cl = c->vg.aux;
   int rc;
   // the sort's buckets: leaves for a dense cloud, whole grid rows for a sweep, and for a LARGE cloud in a box too big for leaf buckets
   // segments of a row, as many as keep the table near 4 n entries (the ranking pass is quadratic in a bucket's population: a ground-level
@@ -277,10 +277,10 @@ static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, fl
   const size_t nr1 = (size_t)g.div[1] * (size_t)g.div[2] * (size_t)rgck::vg_segments(g, seg_shift) + 1;   // buckets
   if ((rc = ensure(c, cl.cell_of, sizeof(int) * n))) return rc;                                                    // row of every point
   if ((rc = ensure(c, cl.slot_of, sizeof(int) * n))) return rc;                                                    // leaf x of every point
-  if ((rc = ensure(c, c->vg_pos, sizeof(int) * n))) return rc;                                                     // arrival slot, then output number
-  if ((rc = ensure(c, c->vg_order, sizeof(int) * n))) return rc;
-  if ((rc = ensure(c, c->vg_tmp, sizeof(long long) * n))) return rc;
-  if ((rc = ensure(c, c->vg_leaf, sizeof(long long) * n))) return rc;
+  if ((rc = ensure(c, c->vg.pos, sizeof(int) * n))) return rc;                                                     // arrival slot, then output number
+  if ((rc = ensure(c, c->vg.order, sizeof(int) * n))) return rc;
+  if ((rc = ensure(c, c->vg.tmp, sizeof(long long) * n))) return rc;
+  if ((rc = ensure(c, c->vg.leaf, sizeof(long long) * n))) return rc;
   if ((rc = ensure(c, cl.cnt, sizeof(int) * nr1))) return rc;
   if ((rc = ensure(c, cl.start, sizeof(int) * nr1))) return rc;
   const size_t row_bs = sizeof(long long) * (nr1 / 2048 + 2);
@@ -291,23 +291,23 @@ static int voxelgrid_rows(rgc_ctx* c, const float* d_in, int stride_f, int n, fl
     HIPCHK(c, hipMemsetAsync(cl.cnt.p, 0, fill, s));
   }
   cl.cnt_clean = std::max(cl.cnt_clean, nr1);  // (what lies beyond this call's rows was not touched: the scan's and the map's filter take turns)
-  if (!c->vg_flags_clean) HIPCHK(c, hipMemsetAsync(&c->d_small->leaf.guard, 0, sizeof(int), s));
-  c->vg_flags_clean = false;
-  const bool packed = rgck::vg_rows(s, d_in, stride_f, n, inv, g, edge, seg_shift, cl.cell_of.as<int>(), cl.slot_of.as<int>(), c->vg_pos.as<int>(), cl.cnt.as<int>(),
-                                    cl.start.as<int>(), cl.block_sums.p, c->vg_tmp.as<unsigned long long>(), c->vg_order.as<int>(), c->vg_leaf.as<unsigned long long>(),
+  if (!c->vg.flags_clean) HIPCHK(c, hipMemsetAsync(&c->d_small->leaf.guard, 0, sizeof(int), s));
+  c->vg.flags_clean = false;
+  const bool packed = rgck::vg_rows(s, d_in, stride_f, n, inv, g, edge, seg_shift, cl.cell_of.as<int>(), cl.slot_of.as<int>(), c->vg.pos.as<int>(), cl.cnt.as<int>(),
+                                    cl.start.as<int>(), cl.block_sums.p, c->vg.tmp.as<unsigned long long>(), c->vg.order.as<int>(), c->vg.leaf.as<unsigned long long>(),
                                     (int*)(cl.block_sums.as<char>() + row_bs), d_out, d_res, mode, leaf, d_index);
   rt->chain = 1; rt->leaf_buckets = dense ? 1 : 0; rt->seg_shift = seg_shift; rt->nseg = rgck::vg_segments(g, seg_shift); rt->packed = packed ? 1 : 0;
   rt->edge = edge; rt->flags = 0;
   for (int a = 0; a < 3; a++) { rt->minb[a] = g.minb[a]; rt->div[a] = g.div[a]; }
   if (h_result) {  // (the finished chain leaves the flag word zeroed: the next chain on this stream finds it so)
     HIPCHK(c, hipMemcpyAsync(h_result, d_res, sizeof(rgck::LeafRows::res), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->vg_done, s));
-    c->vg_flags_clean = true;
+    HIPCHK(c, hipEventRecord(c->vg.done, s));
+    c->vg.flags_clean = true;
     return RGC_OK;
   }
   HIPCHK(c, hipMemcpyAsync(c->h_small->leaf_rows.res, d_res, sizeof(rgck::LeafRows::res), hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
-  c->vg_flags_clean = true;
+  c->vg.flags_clean = true;
   *flags = h_res[0];
   *n_out = h_res[2];
   rt->flags = h_res[0];
@@ -318,9 +318,9 @@ static bool vg_rows_fit(const rgck::LeafGrid& g, int n) {  // sparse enough for 
   return ncell <= 2147483647.0 && ncell > 64.0 * (double)n && nrows <= 64.0e6;
 }
 
-int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt,
-                          int mode, int* out_index) {
-  HIPCHK(c, hipSetDevice(c->device));
+// rt: what rgc_voxelgrid_route reports, filled as the call goes (voxelgrid_routed adds status and n_out)
+static int voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt,
+                         int mode, int* out_index) {
   hipStream_t s = c->stream;
   const float* d_in;
   int rc = stage_in(c, xyzi, n, stride_bytes, on_device, &d_in);
@@ -331,14 +331,14 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
   rgck::SmallBlock* hsm = &c->h_small->leaf;
   float* d_out = out_xyzi;
   if (!on_device) {
-    if ((rc = ensure(c, c->pre_out, sizeof(float) * 4 * (size_t)n))) return rc;
-    d_out = c->pre_out.as<float>();
+    if ((rc = ensure(c, c->vg.out, sizeof(float) * 4 * (size_t)n))) return rc;
+    d_out = c->vg.out.as<float>();
   }
   // UniformSampling (mode = kVgModePick): the winners' input indices beside the points, staged like them for a host caller
   int* d_index = mode == rgck::kVgModePick ? out_index : nullptr;
   if (d_index && !on_device) {
-    if ((rc = ensure(c, c->us_index, sizeof(int) * (size_t)n))) return rc;
-    d_index = c->us_index.as<int>();
+    if ((rc = ensure(c, c->vg.us_index, sizeof(int) * (size_t)n))) return rc;
+    d_index = c->vg.us_index.as<int>();
   }
   // leaves added on every side of a measured box when the next cloud of this leaf size is filtered on it: 32 for a sweep (its rows are
   // what is counted and scanned), 8 for a dense cloud (its leaves are: a wider box is a longer scan)
@@ -348,8 +348,8 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
     for (int a = 0; a < 3; a++) { p.minb[a] -= pad; p.div[a] += 2 * pad; }
     return p;
   };
-  rgc_ctx::VgBox* box = nullptr;
-  for (auto& b : c->vg_box) if (b.leaf == leaf) box = &b;
+  LeafFilterRecord::VgBox* box = nullptr;
+  for (auto& b : c->vg.box) if (b.leaf == leaf) box = &b;
   bool done = false;
   rt.kept_box = !box ? 0 : box->valid ? 2 : 3;
   if (box && box->valid) {
@@ -374,19 +374,19 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
     rt.chain = rt.leaf_buckets = rt.seg_shift = rt.nseg = rt.packed = rt.edge = rt.flags = 0;  // (of the chain on the kept box)
     int init[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
     memcpy(hsm, init, sizeof(init));
-    c->vg_flags_clean = false;
+    c->vg.flags_clean = false;
     HIPCHK(c, hipMemcpyAsync(dsm, hsm, sizeof(init), hipMemcpyHostToDevice, s));
     rgck::vg_bbox(s, d_in, stride_f, n, inv, dsm->lo, &dsm->guard);
     HIPCHK(c, hipMemcpyAsync(hsm, dsm, offsetof(rgck::SmallBlock, nvox), hipMemcpyDeviceToHost, s));  // (box and guard)
     HIPCHK(c, hipStreamSynchronize(s));
     if (hsm->guard) return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)");
-    c->vg_flags_clean = true;
+    c->vg.flags_clean = true;
     rgck::LeafGrid g{};
     double ncell = 1.0;
     for (int a = 0; a < 3; a++) { g.minb[a] = hsm->lo[a]; g.div[a] = hsm->hi[a] - hsm->lo[a] + 1; ncell *= (double)g.div[a]; }
     for (int a = 0; a < 3; a++) { rt.minb[a] = g.minb[a]; rt.div[a] = g.div[a]; }
     {  // keep the measured box for the next cloud of this leaf size
-      if (!box) { box = &c->vg_box[c->vg_box_next]; c->vg_box_next = (c->vg_box_next + 1) % 4; box->leaf = leaf; }
+      if (!box) { box = &c->vg.box[c->vg.box_next]; c->vg.box_next = (c->vg.box_next + 1) % 4; box->leaf = leaf; }
       bool ok = ncell <= 2.0e9;
       for (int a = 0; a < 3; a++) if (g.minb[a] < -1000000000 || g.div[a] > 1000000000) ok = false;
       box->g = g;
@@ -420,19 +420,25 @@ int rgcapi::voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes
   return RGC_OK;
 }
 
+int rgcapi::voxelgrid_routed(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, int mode,
+                             int* out_index, int rc) {
+  rgc_vg_route rt{};
+  rt.n = n;
+  auto run = [&]() -> int { HIPCHK(c, hipSetDevice(c->device)); return voxelgrid_run(c, xyzi, n, stride_bytes, leaf, out_xyzi, n_out, on_device, rt, mode, out_index); };
+  if (n > 0 && !rc) rc = run();
+  rt.status = rc;
+  rt.n_out = *n_out;
+  c->vg.route = rt;
+  return rc;
+}
+
 extern "C" {
 
 int rgc_voxelgrid(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device) {
   if (!c || !xyzi || !out_xyzi || !n_out || n < 0) return RGC_ERR_INVALID;
   if (!stride_ok(stride_bytes) || !(leaf > 0.f) || !std::isfinite(leaf)) return fail(c, RGC_ERR_INVALID, "bad stride or leaf size");
   *n_out = 0;
-  rgc_vg_route rt{};
-  rt.n = n;
-  const int rc = n == 0 ? RGC_OK : voxelgrid_run(c, xyzi, n, stride_bytes, leaf, out_xyzi, n_out, on_device, rt);
-  rt.status = rc;
-  rt.n_out = *n_out;
-  c->vg_route = rt;
-  return rc;
+  return voxelgrid_routed(c, xyzi, n, stride_bytes, leaf, out_xyzi, n_out, on_device);
 }
 
 // pcl::UniformSampling: rgc_voxelgrid's chain with another last launch (rgck::k_us_rows_pick) -- the same routes, the same refusals
@@ -440,20 +446,14 @@ int rgc_uniform_sampling(rgc_ctx* c, const float* xyzc, int n, int stride_bytes,
   if (!c || !xyzc || !out_xyzc || !n_out || n < 0) return RGC_ERR_INVALID;
   if (!stride_ok(stride_bytes) || !(leaf > 0.f) || !std::isfinite(leaf)) return fail(c, RGC_ERR_INVALID, "bad stride or leaf size");
   *n_out = 0;
-  rgc_vg_route rt{};
-  rt.n = n;
   int rc = RGC_OK;
   if (n > 0 && on_device && out_index) rc = check_device_range(c, out_index, sizeof(int) * (size_t)n, "rgc_uniform_sampling: out_index");
-  if (n > 0 && !rc) rc = voxelgrid_run(c, xyzc, n, stride_bytes, leaf, out_xyzc, n_out, on_device, rt, rgck::kVgModePick, out_index);
-  rt.status = rc;
-  rt.n_out = *n_out;
-  c->vg_route = rt;
-  return rc;
+  return voxelgrid_routed(c, xyzc, n, stride_bytes, leaf, out_xyzc, n_out, on_device, rgck::kVgModePick, out_index, rc);
 }
 
 int rgc_voxelgrid_route(rgc_ctx* c, rgc_vg_route* out) {
   if (!c || !out) return RGC_ERR_INVALID;
-  *out = c->vg_route;
+  *out = c->vg.route;
   return RGC_OK;
 }
 
@@ -467,14 +467,14 @@ int rgc_voxelgrid_route(rgc_ctx* c, rgc_vg_route* out) {
 int rgc_voxelgrid_begin(rgc_ctx* c, const float* d_xyzi, int n, int stride_bytes, float leaf, float* d_out) {
   if (!c || !d_xyzi || !d_out || n < 0 || n > (1 << 27)) return RGC_ERR_INVALID;
   if (!stride_ok(stride_bytes) || !(leaf > 0.f) || !std::isfinite(leaf)) return fail(c, RGC_ERR_INVALID, "bad stride or leaf size");
-  if (c->vg_pend.active) return fail(c, RGC_ERR_INVALID, "rgc_voxelgrid_begin: the previous one has not been ended");
-  if (n > 0) { int rk = check_device_range(c, d_xyzi, (size_t)n * stride_bytes - (stride_bytes - 12), "rgc_voxelgrid_begin: d_xyzi"); if (rk) return rk; rk = check_device_range(c, d_out, (size_t)n * 16, "rgc_voxelgrid_begin: d_out"); if (rk) return rk; }
+  if (c->vg.pend.active) return fail(c, RGC_ERR_INVALID, "rgc_voxelgrid_begin: the previous one has not been ended");
+  if (n > 0) { int rk = check_device_range(c, d_xyzi, record_bytes(n, stride_bytes, false), "rgc_voxelgrid_begin: d_xyzi"); if (rk) return rk; rk = check_device_range(c, d_out, (size_t)n * 16, "rgc_voxelgrid_begin: d_out"); if (rk) return rk; }
   HIPCHK(c, hipSetDevice(c->device));
-  rgc_ctx::VgPending& pd_ = c->vg_pend;
-  pd_ = rgc_ctx::VgPending{};
+  LeafFilterRecord::VgPending& pd_ = c->vg.pend;
+  pd_ = LeafFilterRecord::VgPending{};
   pd_.d_in = d_xyzi; pd_.n = n; pd_.stride_bytes = stride_bytes; pd_.leaf = leaf; pd_.d_out = d_out;
-  rgc_ctx::VgBox* box = nullptr;
-  for (auto& b : c->vg_box) if (b.leaf == leaf) box = &b;
+  LeafFilterRecord::VgBox* box = nullptr;
+  for (auto& b : c->vg.box) if (b.leaf == leaf) box = &b;
   bool enqueued = false;
   if (n > 0 && box && box->valid) {
     constexpr int kPadSparse = 32, kPadDense = 8;   // as in rgc_voxelgrid
@@ -487,18 +487,18 @@ int rgc_voxelgrid_begin(rgc_ctx* c, const float* d_xyzi, int n, int stride_bytes
       pd_.route.kept_box = 1;
       pd_.route.path = RGC_VG_PATH_KEPT;
       int rc = voxelgrid_rows(c, d_xyzi, stride_bytes / 4, n, 1.0f / leaf, sparse ? ps : pdg, (sparse ? kPadSparse : kPadDense) / 2, !sparse, d_out, nullptr,
-                              nullptr, &pd_.route, c->h_vg);
+                              nullptr, &pd_.route, c->vg.h_res);
       if (rc) return rc;
       pd_.g = sparse ? ps : pdg;
       enqueued = true;
     }
   }
   if (!enqueued) {  // no box to trust yet: the whole filter now
-    const rgc_vg_route last = c->vg_route;
+    const rgc_vg_route last = c->vg.route;
     int rc = rgc_voxelgrid(c, d_xyzi, n, stride_bytes, leaf, d_out, &pd_.n_out, 1);
     if (rc) return rc;
-    pd_.route = c->vg_route;  // reported when this filter is ended; until then the context shows the filter before it
-    c->vg_route = last;
+    pd_.route = c->vg.route;  // reported when this filter is ended; until then the context shows the filter before it
+    c->vg.route = last;
     pd_.ready = true;
   }
   pd_.active = true;
@@ -507,233 +507,26 @@ int rgc_voxelgrid_begin(rgc_ctx* c, const float* d_xyzi, int n, int stride_bytes
 
 int rgc_voxelgrid_end(rgc_ctx* c, int* n_out) {
   if (!c || !n_out) return RGC_ERR_INVALID;
-  rgc_ctx::VgPending& pd_ = c->vg_pend;
+  LeafFilterRecord::VgPending& pd_ = c->vg.pend;
   if (!pd_.active) return fail(c, RGC_ERR_INVALID, "rgc_voxelgrid_end without rgc_voxelgrid_begin");
   pd_.active = false;
-  if (pd_.ready) { *n_out = pd_.n_out; c->vg_route = pd_.route; return RGC_OK; }
+  if (pd_.ready) { *n_out = pd_.n_out; c->vg.route = pd_.route; return RGC_OK; }
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->vg_done));
-  const int flags = c->h_vg[0], no = c->h_vg[2];
+  HIPCHK(c, hipEventSynchronize(c->vg.done));
+  const int flags = c->vg.h_res[0], no = c->vg.h_res[2];
   rgc_vg_route& rt = pd_.route;
   rt.flags = rt.kept_flags = flags;
-  if (flags & 1) { rt.status = RGC_ERR_NONFINITE; c->vg_route = rt; return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)"); }
-  rgc_ctx::VgBox* box = nullptr;
-  for (auto& b : c->vg_box) if (b.leaf == pd_.leaf) box = &b;
+  if (flags & 1) { rt.status = RGC_ERR_NONFINITE; c->vg.route = rt; return fail(c, RGC_ERR_NONFINITE, "cloud contains non-finite coordinates (PCL skips them; remove NaNs first)"); }
+  LeafFilterRecord::VgBox* box = nullptr;
+  for (auto& b : c->vg.box) if (b.leaf == pd_.leaf) box = &b;
   if (box && (flags & 6)) { box->valid = false; rt.box_invalidated = 1; }  // outside: measure and repeat now; near a face: measure at the next call
-  if (!(flags & 2)) { *n_out = no; rt.n_out = no; c->vg_route = rt; hint_from_leaf_grid(c, pd_.d_out, no, pd_.g, pd_.leaf); return RGC_OK; }
+  if (!(flags & 2)) { *n_out = no; rt.n_out = no; c->vg.route = rt; hint_from_leaf_grid(c, pd_.d_out, no, pd_.g, pd_.leaf); return RGC_OK; }
   const int rc = rgc_voxelgrid(c, pd_.d_in, pd_.n, pd_.stride_bytes, pd_.leaf, pd_.d_out, n_out, 1);  // (the kept box is invalid now: measured)
-  c->vg_route.repeated = 1;
-  c->vg_route.kept_box = 1;
-  c->vg_route.kept_flags = flags;
-  c->vg_route.box_invalidated = rt.box_invalidated;
+  c->vg.route.repeated = 1;
+  c->vg.route.kept_box = 1;
+  c->vg.route.kept_flags = flags;
+  c->vg.route.box_invalidated = rt.box_invalidated;
   return rc;
-}
-
-}  // extern "C"
-
-
-// ---- A1-A8: ScanRegistration::laserCloudHandler on the device (src/scanRegistration.cpp:89-730) ----
-void rgcapi::host_eig3_sym(const double S[6], double ev[3], double V[9]) {  // Jacobi; eigenvalues ASCENDING, columns of V
-  double A[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}}, U[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int sweep = 0; sweep < 60; sweep++) {
-    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-    const double dg = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-    if (off <= 1e-40 * dg || off == 0.0) break;
-    for (int p = 0; p < 2; p++)
-      for (int q = p + 1; q < 3; q++) {
-        if (A[p][q] == 0.0) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double cc = 1.0 / std::sqrt(t * t + 1.0), ss = t * cc;
-        for (int k = 0; k < 3; k++) { const double a = A[k][p], b = A[k][q]; A[k][p] = cc * a - ss * b; A[k][q] = ss * a + cc * b; }
-        for (int k = 0; k < 3; k++) { const double a = A[p][k], b = A[q][k]; A[p][k] = cc * a - ss * b; A[q][k] = ss * a + cc * b; }
-        for (int k = 0; k < 3; k++) { const double a = U[k][p], b = U[k][q]; U[k][p] = cc * a - ss * b; U[k][q] = ss * a + cc * b; }
-      }
-  }
-  int o[3] = {0, 1, 2};
-  const double e[3] = {A[0][0], A[1][1], A[2][2]};
-  for (int i = 0; i < 2; i++) for (int j = i + 1; j < 3; j++) if (e[o[j]] < e[o[i]]) std::swap(o[i], o[j]);
-  for (int j = 0; j < 3; j++) { ev[j] = e[o[j]]; for (int i = 0; i < 3; i++) V[i * 3 + j] = U[i][o[j]]; }
-}
-
-extern "C" {
-
-void rgc_default_fe_params(rgc_fe_params* p) {
-  if (!p) return;
-  p->n_scans = 16; p->min_range = 0.5; p->max_range = 80.0; p->use_intensity = 1;  // launch/run.launch:6,12-13,18
-}
-
-static int frontend_impl(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, const rgc_fe_params* prm, rgc_fe_out* out, int on_device, bool allow_spec = true);
-int rgc_frontend(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, const rgc_fe_params* prm, rgc_fe_out* out) {
-  return frontend_impl(c, xyzi, n, stride_bytes, prm, out, 0);
-}
-// the same with the sweep already on the device (e.g. rgc_pc2_unpack(..., out_on_device = 1)): no host copy of the input
-int rgc_frontend_device(rgc_ctx* c, const float* d_xyzi, int n, int stride_bytes, const rgc_fe_params* prm, rgc_fe_out* out) {
-  return frontend_impl(c, d_xyzi, n, stride_bytes, prm, out, 1);
-}
-static int frontend_impl(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, const rgc_fe_params* prm, rgc_fe_out* out, int on_device, bool allow_spec) {
-  if (!c || !xyzi || !prm || !out || n < 0 || n > (1 << 27)) return RGC_ERR_INVALID;
-  if (n > (1 << 24)) return fail(c, RGC_ERR_INVALID, "sweep has %d points, the front-end's limit is 2^24", n);  // 32-bit sizes and candidate lists below
-  if (stride_bytes < 16 || (stride_bytes & 3) || stride_bytes > 4096) return fail(c, RGC_ERR_INVALID, "front-end needs x,y,z,intensity: stride_bytes >= 16");
-  const int NS = prm->n_scans;
-  if (NS != 16 && NS != 32 && NS != 64) return fail(c, RGC_ERR_INVALID, "only 16, 32 or 64 scan lines (scanRegistration.cpp:69-72)");
-  out->n_cloud = out->n_sharp = out->n_sharp_own = out->n_flat = out->n_inten = out->n_ground = 0;
-  out->ground_valid = 0;
-  c->fe_n_cloud = 0;
-  memset(out->ring_count, 0, sizeof(out->ring_count));
-  if (n == 0) return RGC_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const int stride_f = stride_bytes / 4;
-  const float* d_in;
-  int rc = stage_in(c, xyzi, n, stride_bytes, on_device, &d_in);
-  if (rc) return rc;
-  const int nb = rgck::fe_blocks(n);
-  enum { RING, RANK, HIST, META, ST, CL, INUM2, INUM, RANGE, ANGLE, CURV, CURV2, ICURV, DSRC, OSRC, PICK, IPICK, LAB, ILAB, GMARK, MULT, SCNT,
-         SPOS, PART, OUTD, SLOTS, FLAGS, SHARP, FLAT, INTEN, GLIST, BSUM, SORTC, SORTI };
-  const int nu = NS * 6, fcap = nu * 41;
-  constexpr size_t kTailFlags = 304, kTailSt = 336, kTailFeat = 496;  // see OUTD below
-  const size_t n4 = (size_t)4 * n;
-  const size_t sizes[34] = {n4, n4, (size_t)4 * 64 * nb, 4u * 132, 4u * 8, 4 * n4, n4, n4, n4, n4, n4, n4, n4, n4,
-                            n4, n4, n4, n4, n4, n4, n4, n4, n4, (size_t)8 * 11 * nb, kTailFeat + 60u * (size_t)fcap,
-                            4u * (size_t)nu * rgck::fe_slot_ints(), 4u * 8, 64u, 64u, 64u, 16u * 10 * (size_t)n, 4u * ((size_t)n / 2048 + 4), n4, n4};
-  // OUTD is the sweep's "tail": ground sums / fit / distance sums (doubles 0..33), the flags, the filter's start-end state and the three
-  // feature clouds in ONE buffer laid out like the pinned staging area behind the meta block, so that everything the host needs at the
-  // end of the sweep comes down in ONE copy and the two small blocks are initialised by ONE
-  for (int b = 0; b < 34; b++) if ((rc = ensure(c, c->fe[b], sizes[b] + 64))) return rc;
-#define FE(i, T) (c->fe[i].as<T>())
-  unsigned char* const tail = c->fe[OUTD].as<unsigned char>();
-  int* const d_flags = (int*)(tail + kTailFlags);
-  int* const d_st = (int*)(tail + kTailSt);
-  float* const d_sharp = (float*)(tail + kTailFeat);
-  float* const d_flat = d_sharp + 5 * (size_t)fcap;
-  float* const d_inten = d_flat + 5 * (size_t)fcap;
-  const int init16[16] = {0, 0, 0, 0, 0, 0, 0, 0, INT_MAX, -1, INT_MAX, 0, 0, 0, 0, 0};  // flags (zero) + the filter's state
-  static_assert(sizeof(init16) == sizeof(rgck::SmallWords::fe), "the front-end's staged words");
-  memcpy(c->h_small->fe, init16, sizeof(init16));
-  HIPCHK(c, hipMemcpyAsync(d_flags, c->h_small->fe, sizeof(init16), hipMemcpyHostToDevice, s));
-  rgck::FeParams fp{NS, prm->min_range, prm->max_range};
-  rgck::fe_filter(s, d_in, stride_f, n, fp, FE(RING, int), d_st, FE(RANK, int), FE(HIST, int));
-  rgck::fe_half(s, d_in, stride_f, n, FE(RING, int), d_st);
-  rgck::fe_bucket(s, d_in, stride_f, n, NS, FE(RING, int), FE(RANK, int), FE(HIST, int), FE(META, int), d_st, FE(CL, float4), FE(INUM2, int),
-                  FE(PICK, int), FE(IPICK, int), FE(LAB, int), FE(ILAB, int));
-  // pinned staging: [0, 1024) meta + ground sums + flags, then the three feature clouds
-  const size_t stage_need = 1024 + 3 * 20u * (size_t)fcap;
-  if (c->h_stage_cap < stage_need) {
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    c->h_stage = nullptr; c->h_stage_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&c->h_stage, stage_need, hipHostMallocDefault));
-    c->h_stage_cap = stage_need;
-  }
-  int* meta = (int*)c->h_stage;                       // 129 ints
-  int* fl = (int*)(c->h_stage + 832);                 // 8 ints ([528, 800): the ground sums, fit and distance sums)
-  unsigned char* h_feat = c->h_stage + 1024;
-  // The sweep's size after the range filter and its ring sizes are known on the device (k_fe_hist_scan); the host needs them only to
-  // size launches and the selection kernel's LDS.  From the second sweep of a sequence on it does not wait for them: launches are sized
-  // by the raw point count, the kernels read the size themselves (csp), the selection kernel's window by the largest ring of the
-  // PREVIOUS sweep plus a quarter -- if a ring outgrows that (flag bit 1), the sweep is done again the slow way.
-  const bool spec = allow_spec && c->fe_spec_on && c->fe_last_ns == NS && c->fe_last_max_ring > 0 && !out->cloud;
-  int cs = n, max_ring = 0;
-  const int* csp = nullptr;
-  if (spec) {
-    csp = FE(META, int) + 128;
-    max_ring = std::min(n, c->fe_last_max_ring + c->fe_last_max_ring / 4 + 64);
-  } else {
-    HIPCHK(c, hipMemcpyAsync(meta, FE(META, int), sizeof(int) * 129, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    cs = meta[128];
-    out->n_cloud = cs;
-    for (int r = 0; r < NS; r++) { out->ring_count[r] = meta[r]; max_ring = std::max(max_ring, meta[r]); }
-    if (cs == 0) return RGC_OK;
-    if (out->cloud && out->cloud_cap < cs) return fail(c, RGC_ERR_INVALID, "cloud_cap %d < %d points", out->cloud_cap, cs);
-  }
-  rgck::fe_stencils(s, FE(CL, float4), cs, csp, FE(RANGE, float), FE(ANGLE, float), FE(INUM2, int), FE(INUM, int), FE(CURV, float), FE(CURV2, float),
-                    FE(ICURV, float), FE(DSRC, float), FE(OSRC, float), FE(PICK, int));
-  // A5: ground set (with multiplicities) -> weighted centroid / covariance -> plane (scanRegistration.cpp:308-431)
-  rgck::fe_ground(s, FE(CL, float4), cs, csp, NS, FE(RANGE, float), FE(META, int), FE(GMARK, int), FE(MULT, int), FE(SCNT, int), FE(PART, double), FE(OUTD, double),
-                  FE(OUTD, double) + 16);
-  // OUTD: [0..10] the ground sums, [16..31] the plane fit, [32..33] the distance sums -- fitted on the device, read back with the features
-  rgck::fe_ground_dist(s, FE(CL, float4), cs, csp, FE(MULT, int), FE(OUTD, double) + 16, FE(PART, double), FE(OUTD, double) + 32);
-  // /laser_cloud_ground: pushes in reference order (with duplicates); empty when no ground seed was found
-  // (only when the caller takes the list: the chained frame body does not, and these are four launches)
-  if (out->ground_pts && out->ground_cap > 0) {
-    rgck::exclusive_scan(s, FE(SCNT, int), FE(SPOS, int), cs, FE(BSUM, int));
-    const int gcap_dev = 10 * n;
-    rgck::fe_ground_list(s, FE(CL, float4), cs, csp, NS, FE(RANGE, float), FE(META, int), FE(SCNT, int), FE(SPOS, int), FE(GLIST, float4), gcap_dev);
-  }
-  // A7 + A8
-  rgck::fe_select(s, FE(CL, float4), NS, FE(META, int), FE(CURV, float), FE(CURV2, float), FE(ICURV, float), FE(INUM, int), FE(GMARK, int),
-                  FE(PICK, int), FE(IPICK, int), FE(LAB, int), FE(ILAB, int), FE(SLOTS, int), d_flags, max_ring, FE(SORTC, int), FE(SORTI, int));
-  rgck::fe_emit(s, FE(CL, float4), NS, FE(SLOTS, int), FE(DSRC, float), FE(OSRC, float), d_sharp, d_flat, d_inten, fcap,
-                d_flags + 4);
-  // flags and the three feature clouds (at their capacity: ~80 kB each for 16 rings) come down together into pinned memory, one
-  // synchronisation; the counts decide how much of each is handed to the caller
-  double* gd = (double*)(c->h_stage + 528);            // 34 doubles behind the 129 meta ints
-  static_assert(528 + kTailFlags == 832 && 528 + kTailFeat == 1024, "the device tail mirrors the staging area from gd on");
-  HIPCHK(c, hipMemcpyAsync(gd, tail, kTailFeat + 60u * (size_t)fcap, hipMemcpyDeviceToHost, s));
-  if (spec) HIPCHK(c, hipMemcpyAsync(meta, FE(META, int), sizeof(int) * 129, hipMemcpyDeviceToHost, s));
-  if (out->cloud) HIPCHK(c, hipMemcpyAsync(out->cloud, FE(CL, float4), sizeof(float) * 4 * (size_t)cs, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (spec) {
-    if (fl[0] & 2) {  // a ring outgrew the window sized from the previous sweep (or really holds an oversize sector): the slow way decides
-      c->fe_last_max_ring = 0;
-      return frontend_impl(c, xyzi, n, stride_bytes, prm, out, on_device, false);
-    }
-    cs = meta[128];
-    out->n_cloud = cs;
-    max_ring = 0;
-    for (int r = 0; r < NS; r++) { out->ring_count[r] = meta[r]; max_ring = std::max(max_ring, meta[r]); }
-    if (cs == 0) return RGC_OK;
-  }
-  if (fl[0] & 2) return fail(c, RGC_ERR_INVALID, "a ring sector holds more than 2048 points");
-  c->fe_n_cloud = cs;
-  c->fe_last_ns = NS; c->fe_last_max_ring = max_ring;
-  {  // ground message (:403-430) from the sums, the fit and the distance sums that just came down
-    const long long gsize = (long long)(gd[10] + 0.5);
-    if (gsize > 0) {
-      const double* nrm = gd + 19;
-      const double* V = gd + 22;
-      const double* d2 = gd + 32;
-      const double laderH = 0.56;  // :39
-      double distance = d2[1] / d2[0], src1 = d2[0] / (double)gsize;  // :403-404
-      if ((distance / laderH) > 1.1 || (distance / laderH) < 0.9) distance = laderH;  // :405-409
-      if (src1 < 0.9) distance = 0.9 * laderH + 0.1 * distance;                       // :410-413
-      double* g = out->groundparam;  // groundparam.msg order, :420-430
-      g[0] = nrm[0]; g[1] = nrm[1]; g[2] = nrm[2];
-      g[3] = V[1]; g[4] = V[4]; g[5] = V[7];
-      g[6] = V[2]; g[7] = V[5]; g[8] = V[8];
-      g[9] = distance; g[10] = 1 - src1;
-      out->ground_valid = 1;
-      out->n_ground = (int)gsize;
-      if (out->ground_pts && out->ground_cap > 0) {
-        const long long m = gsize < out->ground_cap ? gsize : out->ground_cap;
-        HIPCHK(c, hipMemcpyAsync(out->ground_pts, FE(GLIST, float4), sizeof(float) * 4 * (size_t)m, hipMemcpyDeviceToHost, s));
-      }
-    }
-  }
-  const int ns = fl[4], nf = fl[5], ni = fl[6];
-  out->n_sharp_own = ns; out->n_flat = nf; out->n_inten = ni;
-  const bool add_inten = prm->use_intensity && ((double)ns / (double)nf < 0.3);  // :645-656
-  out->n_sharp = ns + (add_inten ? ni : 0);
-  if (out->feat_cap < out->n_sharp || out->feat_cap < nf || out->feat_cap < ni) return fail(c, RGC_ERR_INVALID, "feat_cap too small");
-  if (ns) memcpy(out->sharp, h_feat, 20u * (size_t)ns);
-  if (nf) memcpy(out->flat, h_feat + 20u * (size_t)fcap, 20u * (size_t)nf);
-  if (ni) memcpy(out->inten, h_feat + 40u * (size_t)fcap, 20u * (size_t)ni);
-  if (add_inten && ni) memcpy(out->sharp + 5 * (size_t)ns, h_feat + 40u * (size_t)fcap, 20u * (size_t)ni);
-  const struct { void* dst; int src; } diag[7] = {{out->curvature, CURV}, {out->curvature2, CURV2}, {out->inten_curvature, ICURV}, {out->label, LAB},
-                                                   {out->inten_label, ILAB}, {out->picked, PICK}, {out->ground_marked, GMARK}};
-  for (auto& d : diag) if (d.dst) HIPCHK(c, hipMemcpyAsync(d.dst, c->fe[d.src].p, 4u * (size_t)cs, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-#undef FE
-  return RGC_OK;
-}
-
-int rgc_frontend_cloud_device(rgc_ctx* c, float** d_cloud, int* n) {
-  if (!c || !d_cloud || !n) return RGC_ERR_INVALID;
-  *d_cloud = c->fe_n_cloud > 0 ? c->fe[5].as<float>() : nullptr;  // CL: float4 {x, y, z, ring + 0.1 relTime}, ring-major
-  *n = c->fe_n_cloud;
-  return RGC_OK;
 }
 
 }  // extern "C"

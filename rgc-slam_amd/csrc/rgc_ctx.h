@@ -1,6 +1,6 @@
-// rgc_ctx.h -- internal to librgc_hip.so: what the host files of the C-ABI (rgc_api*.hip) share.  The build-flag defaults, the context
-// (struct rgc_ctx: opaque to callers, include/rgc_hip.h) with its buffer and cloud records, and the helpers more than one of those files
-// calls, in namespace rgcapi (-fvisibility=hidden keeps them out of the dynamic symbol table).  DESIGN.md says which file holds what.
+// rgc_ctx.h -- internal to librgc_hip.so: what the host files of the C-ABI (rgc_api*.hip, one per subsystem) share.  The build-flag defaults, the context
+// (struct rgc_ctx: opaque to callers, include/rgc_hip.h) with a record per subsystem beside the VGICP core's loose state, and the helpers more than one of those
+// files calls, in namespace rgcapi (-fvisibility=hidden keeps them out of the dynamic symbol table).  DESIGN.md says which file holds what.
 #pragma once
 #include "../../include/rgc_hip.h"
 
@@ -139,12 +139,15 @@ struct Cloud {
 
 // ---- the registration methods beside VGICP: what each keeps between its calls.  bufs(): its device buffers, once (rgc_destroy walks them);
 // pinned(): its page-locked host mirrors; clouds(): its clouds.  `valid` = the frozen state is that of the present clouds and settings
-struct Sums {  // where a method's term kernels fold to: per-block partials, the folded sums, their pinned mirror (32 doubles)
+struct NoLists {  // a record derives from it and states only the lists it has
+  std::vector<void*> pinned() { return {}; }
+  std::vector<Cloud*> clouds() { return {}; }
+};
+struct Sums : NoLists {  // where a method's term kernels fold to: per-block partials, the folded sums, their pinned mirror (32 doubles)
   DevBuf partials, out;
   double* h_out = nullptr;
   std::vector<DevBuf*> bufs() { return {&partials, &out}; }
   std::vector<void*> pinned() { return {h_out}; }
-  std::vector<Cloud*> clouds() { return {}; }
 };
 
 // NDT registration (rgc_ndt_*): two clouds of its own (0 target, 1 source) with their grids and voxel maps (Cloud::cell_voxel / vox / vox_cell,
@@ -170,33 +173,29 @@ struct NdtRecord {
 
 // FastGICP (rgc_gicp_*) on the context's own source and target: the pair list of the last rgc_gicp_linearize (per sorted source point the
 // neighbour's position in the target's sorted array or -1, and the fp32 key) and its Mahalanobis matrices
-struct GicpRecord {
+struct GicpRecord : NoLists {
   double dmax = (double)FLT_MAX;      // corr_dist_threshold_ (fast_gicp_impl.hpp:18: std::numeric_limits<float>::max())
   DevBuf corr, key, M;
   bool valid = false;
   int n = 0, kept = 0;
   std::vector<DevBuf*> bufs() { return {&corr, &key, &M}; }
-  std::vector<void*> pinned() { return {}; }
-  std::vector<Cloud*> clouds() { return {}; }
 };
 
 // FastGICPSingleThread (rgc_gicpst_*) on the same clouds: per sorted source point the pair, the keys to the nearest and the second nearest at
 // its anchor, the anchor and the Mahalanobis matrix of the pose it was last searched at (rgck::GicpStState), the compaction's list and
 // counter.  valid covers the anchors: it falls on rgc_gicpst_reset and at the start of rgc_gicpst_align too; the next linearisation then
 // searches every point
-struct GicpStRecord {
+struct GicpStRecord : NoLists {
   DevBuf corr, key1, key2, anchor, M, searched, list, count;
   bool valid = false;
   int n = 0, kept = 0, searched_n = 0;
   std::vector<DevBuf*> bufs() { return {&corr, &key1, &key2, &anchor, &M, &searched, &list, &count}; }
-  std::vector<void*> pinned() { return {}; }
-  std::vector<Cloud*> clouds() { return {}; }
 };
 
 // FastGICPMultiPoints (rgc_gicpmp_*) on the same clouds: the merged list of the last rgc_gicpmp_linearize (rgck::kGicpMpMerged doubles per sorted
 // source point), the fp32 pose and radius it was made under (the read-out of the members walks the candidates again).  valid falls on
 // rgc_gicpmp_set_params too
-struct GicpMpRecord {
+struct GicpMpRecord : NoLists {
   rgc_gicp_mp_params prm{0.5, 64, 1e-5, 1e-5};
   DevBuf merged, cand, scratch;
   Sums sums;
@@ -206,7 +205,6 @@ struct GicpMpRecord {
   float T32[16] = {0};
   std::vector<DevBuf*> bufs() { return {&merged, &cand, &scratch, &sums.partials, &sums.out}; }
   std::vector<void*> pinned() { return {sums.h_out}; }
-  std::vector<Cloud*> clouds() { return {}; }
 };
 
 // ---- the cloud operations (search index, outlier filters, clusters, plane, normals, FPFH): what each keeps between its calls, released like the
@@ -219,6 +217,11 @@ struct OpFrame {
   DevBuf small;
   unsigned char* h = nullptr;
   double cell = 0.0;
+};
+struct FrameLists {  // what a record around one OpFrame lists beside its buffers
+  OpFrame f;
+  std::vector<void*> pinned() { return {f.h}; }
+  std::vector<Cloud*> clouds() { return {&f.cl}; }
 };
 constexpr size_t kFrameBytes = 4096, kFrameWordsAt = 32, kFrameStatsAt = 64;
 template <class T> T* stats(const OpFrame& f) {
@@ -237,44 +240,35 @@ struct Selection {
 // The search index (rgc_search_*, rgc_api_search.hip): the indexed cloud (a host caller's points in Cloud::in_copy); the staged host queries, the query
 // calls' scratch (counts, offsets, block sums, fixed-width rows, packed entries and the long sort's second row, the results of a host caller); the
 // mirror holds rgck::SearchStats
-struct SearchRecord {
-  OpFrame f;
+struct SearchRecord : FrameLists {
   bool set = false;
   rgc_search_info info{};
   DevBuf q, cnt, off, bs, row_idx, row_sq, ent, tmp, idx, sq;
   std::vector<DevBuf*> bufs() { return {&f.small, &q, &cnt, &off, &bs, &row_idx, &row_sq, &ent, &tmp, &idx, &sq}; }
-  std::vector<void*> pinned() { return {f.h}; }
-  std::vector<Cloud*> clouds() { return {&f.cl}; }
 };
 
 // The outlier filters (rgc_outlier_*, rgc_api_filters.hip): a host caller's staged records, the mean distances / counts, the selection, the
 // fixed-order sums' rows; the mirror holds the number kept and rgck::OutlierStats
-struct OutlierRecord {
-  OpFrame f;
+struct OutlierRecord : FrameLists {
   rgc_outlier_info info{};
   DevBuf in, val, partials;
   Selection sel;
   std::vector<DevBuf*> bufs() { return {&f.small, &in, &val, &partials, &sel.flag, &sel.off, &sel.bs, &sel.out, &sel.idx}; }
-  std::vector<void*> pinned() { return {f.h}; }
-  std::vector<Cloud*> clouds() { return {&f.cl}; }
 };
 
 // Euclidean cluster extraction (rgc_cluster_*, rgc_api_cluster.hip): a host caller's staged records; the int arrays of a call carved from ONE buffer
 // (the union-find, the per-point and per-cluster tables, the radix sort's two pairs of arrays, a host caller's results); the radix histograms and
 // the scans' block sums; the mirror holds the two counts and rgck::ClusterStats
-struct ClusterRecord {
-  OpFrame f;
+struct ClusterRecord : FrameLists {
   rgc_cluster_info info{};
   DevBuf in, work, hist, bs;
   std::vector<DevBuf*> bufs() { return {&f.small, &in, &work, &hist, &bs}; }
-  std::vector<void*> pinned() { return {f.h}; }
-  std::vector<Cloud*> clouds() { return {&f.cl}; }
 };
 
 // RANSAC plane segmentation (rgc_plane_*, rgc_api_plane.hip), no grid: a host caller's staged records and samples; a batch's non-finite word, models
 // and counts (one contiguous read-back) with their pinned mirror of 32 KiB, which also holds the final rgck::PlaneFit and the number written; the
 // fixed-order sums' rows; the fit; the selection
-struct PlaneRecord {
+struct PlaneRecord : NoLists {
   rgc_plane_info info{};
   int batch = 0;  // rgc_plane_set_batch: 0 = automatic
   DevBuf in, samples, bat, rows, fit;
@@ -282,31 +276,123 @@ struct PlaneRecord {
   unsigned char* h = nullptr;
   std::vector<DevBuf*> bufs() { return {&in, &samples, &bat, &rows, &fit, &sel.flag, &sel.off, &sel.bs, &sel.out, &sel.idx}; }
   std::vector<void*> pinned() { return {h}; }
-  std::vector<Cloud*> clouds() { return {}; }
 };
 
 // Surface normal estimation (rgc_normal_*, rgc_api_normals.hip): the surface cloud's grid; a host caller's staged queries and surface (12-byte
 // records) and results; the mirror holds the queries' flag and rgck::NormalStats
-struct NormalRecord {
-  OpFrame f;
+struct NormalRecord : FrameLists {
   rgc_normal_info info{};
   DevBuf q, surf, n4, cov, cen, cnt;
   std::vector<DevBuf*> bufs() { return {&f.small, &q, &surf, &n4, &cov, &cen, &cnt}; }
-  std::vector<void*> pinned() { return {f.h}; }
-  std::vector<Cloud*> clouds() { return {&f.cl}; }
 };
 
 // FPFH descriptors (rgc_fpfh_*, rgc_api_fpfh.hip): the surface cloud's grid; a host caller's staged queries, surface and normals (12-byte records);
 // the normals as float4 with their validity in w; the marks of a separate surface, their scan, its block sums and the list of marked sorted
 // positions; the SPFH counts and row sizes (scratch when the caller does not ask for them), a host caller's descriptors and counts; the mirror
 // holds the queries' flag, the list's length and rgck::FpfhStats
-struct FpfhRecord {
-  OpFrame f;
+struct FpfhRecord : FrameLists {
   rgc_fpfh_info info{};
   DevBuf q, surf, nrm, n4, flag, off, bs, list, spfh, m, out, cnt;
   std::vector<DevBuf*> bufs() { return {&f.small, &q, &surf, &nrm, &n4, &flag, &off, &bs, &list, &spfh, &m, &out, &cnt}; }
-  std::vector<void*> pinned() { return {f.h}; }
-  std::vector<Cloud*> clouds() { return {&f.cl}; }
+};
+
+// ---- the mapping side and the stages around the registration, released like the records above.  PinnedBuf: a pinned host buffer that grows (ensure_pinned)
+struct PinnedBuf { unsigned char* p = nullptr; size_t cap = 0; };
+
+// f1, the mapping node's feature registration (rgc_mapreg_*, rgc_api_mapreg.hip): the corner / surf feature maps (grid only, kMapregCell), the four
+// feature sets (0/1 corner/surf of the current pose, 2/3 of the last) with their factors (8 doubles each), the term kernels' per-block rows, and 16 ints:
+// [0, 8) a measured grid's scratch, [8, 12) the factor counts.  small is BORROWED by rgc_icp_align for its target's grid (prepare_map_grid)
+struct MapregRecord : NoLists {
+  Cloud map[2];
+  DevBuf feat[4], fac[4], partials, small;
+  std::vector<DevBuf*> bufs() { return {&feat[0], &feat[1], &feat[2], &feat[3], &fac[0], &fac[1], &fac[2], &fac[3], &partials, &small}; }
+  std::vector<Cloud*> clouds() { return {&map[0], &map[1]}; }
+};
+
+// f2, the rolling local map (rgc_map_*, rgc_api_map.hip).  World-frame points (relative to origin, x,y,z,intensity, 16 B) of the live keyframes as
+// contiguous segments in insertion order in store[cur]; the other buffer is the compaction / re-basing target.  target: the committed, filtered map
+struct RollingMapRecord : NoLists {
+  struct MapKf { int id; size_t off; int n; double t[3]; };
+  DevBuf store[2], target;
+  int cur = 0, next_id = 0;
+  size_t n = 0;
+  std::vector<MapKf> kf;
+  double origin[3] = {0, 0, 0};
+  bool dirty = false;     // keyframes changed since the last commit
+  bool bound = false;     // the context's target IS the committed map (rgc_set_target* unbinds it)
+  float leaf = 0.f;       // of the last commit, which left ntarget points
+  int ntarget = 0;
+  unsigned long long rev = 0;
+  std::vector<DevBuf*> bufs() { return {&store[0], &store[1], &target}; }
+};
+
+// f5, the mapping node's keyframe store (rgc_kf_*, rgc_api_keyframes.hip; the pose graph reads recs and index).  Body-frame points (x,y,z,c, 16 B) per
+// kind in store[kind], a keyframe's clouds as one contiguous run each; the key poses (and the quaternions the reference's chain makes of them) stay on
+// the host and travel with every assembly's segment table (table; h_table its pinned staging, rewritten or freed only after `uploaded`); raw / filt: the
+// assembly when it is not written to the caller's buffer.  The selections: a device mirror of the key positions, float4 {x, y, z, position}, with the
+// travelled distances and the ids beside it -- uploaded when rev has moved since mirror_rev -- and their scratch
+struct KeyframeRecord : NoLists {
+  struct KfRec { int id; size_t off[RGC_KF_KINDS]; int n[RGC_KF_KINDS]; rgc_kf_pose pose; double q[4];
+                 float travel, travel_angle; };  // travelled distance / angle up to this keyframe, fixed at its push (src/RGC_mapping.cpp:1887-1908)
+  DevBuf store[RGC_KF_KINDS];
+  size_t n[RGC_KF_KINDS] = {0, 0, 0};
+  std::vector<KfRec> recs;
+  std::unordered_map<int, int> index;   // id -> position in recs
+  unsigned long long rev = 0;
+  DevBuf table, raw, filt;
+  PinnedBuf h_table;
+  hipEvent_t uploaded = nullptr;        // (created in rgc_create, destroyed in rgc_destroy)
+  bool upload_pending = false;
+  DevBuf pos, travel, ids, flag, scan, bsum, sel, sel_out, small;
+  unsigned long long mirror_rev = ~0ull;   // the revision the mirror holds
+  std::vector<DevBuf*> bufs() { return {&store[0], &store[1], &store[2], &table, &raw, &filt, &pos, &travel, &ids, &flag, &scan, &bsum, &sel, &sel_out, &small}; }
+  std::vector<void*> pinned() { return {h_table.p}; }
+};
+
+// The 4-DoF pose graph over the store's key poses (rgc_pgo_*, rgc_api_pgo.hip): the graph's index tables, every double array of a solve (two
+// evaluations: the accepted state and the candidate), the separators' dense system
+struct PgoRecord : NoLists {
+  DevBuf i, d, M;
+  std::vector<DevBuf*> bufs() { return {&i, &d, &M}; }
+};
+
+// The leaf filter and the staging of B2 / B3 / B9 (rgc_voxelgrid*, rgc_uniform_sampling, stage_in: rgc_api_pre.hip).  in / out: a host caller's cloud
+// on its way to the device and a result on its way back; the rows chain's arrays; us_index: the winners' indices of a host caller; aux: the chain's
+// grid scratch; the leaf boxes of earlier clouds by leaf size; the one filter in flight between rgc_voxelgrid_begin and _end with its event and its
+// three pinned result ints; the route of the last finished filter.  BORROWED for the length of a call: `in` by every entry point that stages a host
+// cloud (stage_in) and by rgc_pc2_unpack; `out` by rgc_transform_cloud, rgc_pc2_* and rgc_icp_align (its moving source); `aux` by rgc_icp_align (its target)
+struct LeafFilterRecord {
+  struct VgBox { float leaf = 0.f; bool valid = false; rgck::LeafGrid g{}; };
+  struct VgPending { bool active = false, ready = false; const float* d_in = nullptr; int n = 0, stride_bytes = 0; float leaf = 0.f; float* d_out = nullptr;
+                     rgck::LeafGrid g{};  // the leaf grid the pending filter was enqueued on
+                     int n_out = 0;
+                     rgc_vg_route route{}; };  // what rgc_voxelgrid_route reports once the pending filter is ended
+  DevBuf in, out, order, pos, tmp, leaf, us_index;
+  Cloud aux;
+  VgBox box[4];
+  int box_next = 0;
+  bool flags_clean = false;  // d_small->leaf.guard is known to be zero (a finished rows chain leaves it so)
+  VgPending pend;
+  rgc_vg_route route{};
+  hipEvent_t done = nullptr;  // (created in rgc_create, destroyed in rgc_destroy)
+  int* h_res = nullptr;
+  std::vector<DevBuf*> bufs() { return {&in, &out, &order, &pos, &tmp, &leaf, &us_index}; }
+  std::vector<void*> pinned() { return {h_res}; }
+  std::vector<Cloud*> clouds() { return {&aux}; }
+};
+
+// The A1-A8 front end (rgc_frontend*, rgc_api_frontend.hip): a sweep's arrays, one buffer each (frontend_impl sizes them), the pinned staging of its small
+// read-backs and feature clouds (a pageable copy is staged by the runtime anyway, one blocking hop per call), what the previous sweep leaves for the next
+enum FeBuf { FE_RING, FE_RANK, FE_HIST, FE_META, FE_ST, FE_CL, FE_INUM2, FE_INUM, FE_RANGE, FE_ANGLE, FE_CURV, FE_CURV2, FE_ICURV, FE_DSRC, FE_OSRC, FE_PICK, FE_IPICK, FE_LAB, FE_ILAB, FE_GMARK, FE_MULT,
+             FE_SCNT, FE_SPOS, FE_PART, FE_OUTD, FE_SLOTS, FE_FLAGS, FE_SHARP, FE_FLAT, FE_INTEN, FE_GLIST, FE_BSUM, FE_SORTC, FE_SORTI, kFeBufs };
+struct FrontendRecord : NoLists {
+  DevBuf buf[kFeBufs];
+  PinnedBuf stage;
+  bool spec_on = RGC_FE_SPEC != 0;  // (build flag) 0: read every sweep's size back before its stencil kernels
+  int last_ns = 0, last_max_ring = 0;  // the previous sweep's scan lines and largest ring: sizes the next sweep's launches without a read-back
+  int n_cloud = 0;                  // points of the last front-end's ring-major cloud (buf[FE_CL]), for rgc_frontend_cloud_device
+  std::vector<DevBuf*> bufs() { std::vector<DevBuf*> v; for (DevBuf& b : buf) v.push_back(&b); return v; }
+  std::vector<void*> pinned() { return {stage.p}; }
 };
 
 struct ProfRegion {
@@ -354,9 +440,6 @@ struct rgc_ctx {
   double* h_out = nullptr;    // pinned
   DevBuf scratch;             // getters
   DevBuf lm_state;            // the LM area (rgck::LmArea): the solve's two state images and the loose words behind them
-  // f1: mapping-node feature registration (corner / surf feature maps: grid only, 1.5 m cells)
-  Cloud mr_map[2];
-  DevBuf mr_feat[4], mr_fac[4], mr_partials, mr_small;
   bool deferred_known = false;  // stats.deferred_* are those of the current clouds (carried home by the last align)
   DevBuf fit_partials;        // fitness rows when it is chained behind the LM slots
   rgck::LmState* h_lm = nullptr;  // pinned mirror (the stream-ordered copy behind every batch of LM launches)
@@ -409,44 +492,12 @@ struct rgc_ctx {
   int map_wide_r = RGC_MAP_WIDE_R;          // (build flag; 0 = off, 2) block radius of the bulk kNN launch for a sparse map
   double map_wide_density = RGC_MAP_WIDE;   // (build flag) ... when the map has fewer points per grid cell than this
   double src_res_auto = 0.0;  // adaptive cell size of the scan's kNN grid, steered by how crowded its cells were in the previous frame (0 = voxel_res)
-  Cloud aux;                  // grid scratch of rgc_voxelgrid
-  DevBuf pre_in, pre_out, vg_order, vg_pos, vg_tmp, vg_leaf;  // B2/B3/B9 staging
-  DevBuf us_index;            // rgc_uniform_sampling: the winners' indices of a host caller
-  struct VgBox { float leaf = 0.f; bool valid = false; rgck::LeafGrid g{}; } vg_box[4];  // measured leaf boxes of earlier clouds, by leaf size
-  int vg_box_next = 0;
   // Bounding boxes the library knows WITHOUT measuring: rgc_set_target_reframed maps the input's box (measured once per input buffer)
   // through the transform it applies -- the box of a sub-map re-framed by a new pose (RGC_odometer.cpp:1248-1256) follows from the
   // pose.  The target's preparation takes its grid from the hint: no bounding-box kernel, no host round trip, and no speculative-grid
   // miss when the re-framed map's box swings with the vehicle's yaw.  k_count's guard still checks it.
   struct BoxHint { const void* p = nullptr; int n = 0; double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}; double reach_xy = 0, reach_z = 0; } box_hint[4];
   int box_hint_next = 0;
-  bool vg_flags_clean = false;  // d_small->leaf.guard is known to be zero (a finished rows chain leaves it so)
-  // rgc_voxelgrid_begin / _end: one filter of a device cloud in flight (enqueued on its kept box, result not yet looked at)
-  struct VgPending { bool active = false, ready = false; const float* d_in = nullptr; int n = 0, stride_bytes = 0; float leaf = 0.f; float* d_out = nullptr;
-                     rgck::LeafGrid g{};  // the leaf grid the pending filter was enqueued on
-                     int n_out = 0;
-                     rgc_vg_route route{};  // what rgc_voxelgrid_route reports once the pending filter is ended
-                     } vg_pend;
-  rgc_vg_route vg_route{};  // the last finished leaf filter (rgc_voxelgrid_route)
-  hipEvent_t vg_done = nullptr;
-  int* h_vg = nullptr;  // pinned: the pending filter's three result ints (h_small's words are all taken: the front-end stages 16 ints in SmallWords::fe)
-  DevBuf fe[34];              // front-end buffers
-  unsigned char* h_stage = nullptr;  // pinned staging of the front-end's small read-backs and feature clouds (a copy into pageable
-  size_t h_stage_cap = 0;            // memory is staged by the runtime anyway, one blocking hop per call)
-  bool fe_spec_on = RGC_FE_SPEC != 0;  // (build flag) 0: read every sweep's size back before its stencil kernels
-  int fe_last_ns = 0, fe_last_max_ring = 0;  // the previous sweep's scan lines and largest ring: sizes the next sweep's launches without a read-back
-  int fe_n_cloud = 0;         // points of the last front-end's ring-major cloud (fe[5]), for rgc_frontend_cloud_device
-  // f2: rolling local map.  World-frame points (relative to map_origin, x,y,z,intensity, 16 B) of the live keyframes as
-  // contiguous segments in insertion order in map_store[map_cur]; the other buffer is the compaction / re-basing target.
-  struct MapKf { int id; size_t off; int n; double t[3]; };
-  DevBuf map_store[2], map_target;
-  int map_cur = 0;
-  size_t map_n = 0;
-  std::vector<MapKf> map_kf;
-  int map_next_id = 0;
-  double map_origin[3] = {0, 0, 0};
-  bool map_dirty = false;     // keyframes changed since the last commit
-  bool map_bound = false;     // the context's target IS the committed map (rgc_set_target* unbinds it)
   unsigned long long tgt_generation = 0;   // bumped whenever this context prepares a target (what borrowers check)
   const rgc_ctx* tgt_owner = nullptr;      // rgc_share_target: whose target this context aliases, and at which generation
   unsigned long long tgt_owner_gen = 0, tgt_owner_uid = 0;
@@ -454,31 +505,13 @@ struct rgc_ctx {
   hipEvent_t tgt_prepared = nullptr;       // recorded on the main stream behind every target preparation (rgc_hold_source_until_target_of of another context waits for it)
   hipEvent_t src_read_done = nullptr;      // recorded on the main stream behind a kernel that reads the source's INPUT buffer (rgc_get_aligned*)
   bool src_read_pending = false;           // ... and not yet waited for by the stream a host source is copied on
-  float map_leaf = 0.f;
-  int map_ntarget = 0;
-  unsigned long long map_rev = 0;
-  // f5: the mapping node's keyframe store.  Body-frame points (x,y,z,c, 16 B) per kind in kf_store[kind], a keyframe's clouds as one
-  // contiguous run each; the key poses (and the quaternions the reference's chain makes of them) stay on the host and travel with every
-  // assembly's segment table.
-  struct KfRec { int id; size_t off[RGC_KF_KINDS]; int n[RGC_KF_KINDS]; rgc_kf_pose pose; double q[4];
-                 float travel, travel_angle; };  // travelled distance / angle up to this keyframe, fixed at its push (src/RGC_mapping.cpp:1887-1908)
-  DevBuf kf_store[RGC_KF_KINDS];
-  size_t kf_n[RGC_KF_KINDS] = {0, 0, 0};
-  std::vector<KfRec> kf;
-  std::unordered_map<int, int> kf_index;   // id -> position in kf
-  unsigned long long kf_rev = 0;
-  DevBuf kf_table, kf_raw, kf_filt;        // the segment table on the device; the unfiltered / filtered assembly when it is not written to the caller's buffer
-  unsigned char* kf_h_table = nullptr;     // pinned staging of the segment table
-  size_t kf_h_cap = 0;
-  hipEvent_t kf_uploaded = nullptr;        // recorded behind the table's copy: the staging is rewritten only after it
-  bool kf_upload_pending = false;
-  // the selections (rgc_kf_select_*, rgc_kf_detect_loop): a device mirror of the key positions, float4 {x, y, z, position}, with the travelled
-  // distances and the ids beside it -- uploaded when the store's revision has moved since the last upload -- and the selections' scratch
-  DevBuf kf_pos, kf_travel, kf_ids, kf_flag, kf_scan, kf_bsum, kf_sel, kf_sel_out, kf_small;
-  unsigned long long kf_mirror_rev = ~0ull;   // the revision the mirror holds
-  // the 4-DoF pose graph over the store's key poses (rgc_pgo_*): buffers of its own -- the graph's index tables, every double array of a solve
-  // (two evaluations: the accepted state and the candidate), the separators' dense system
-  DevBuf pgo_i, pgo_d, pgo_M;
+  // The mapping side and the stages around the registration, each in a record of its own (rgcapi::MapregRecord and the five below it)
+  rgcapi::MapregRecord mapreg;
+  rgcapi::RollingMapRecord map;
+  rgcapi::KeyframeRecord kfs;
+  rgcapi::PgoRecord pgo;
+  rgcapi::LeafFilterRecord vg;
+  rgcapi::FrontendRecord fe;
   // The registration methods beside VGICP, each in a record of its own (rgcapi::NdtRecord and the three below it): NDT on two clouds of its own, the three GICP variants on the
   // context's source and target.  gicp_sums is the fixed-order sums' scratch of FastGICP and FastGICPSingleThread, which never run at the same time.
   rgcapi::NdtRecord ndt;
@@ -523,6 +556,9 @@ inline void drop_frozen(rgc_ctx* c) { c->corr_valid = c->gicp.valid = c->gicp_st
 // ---- rgc_api.hip: errors, buffers, the clouds' preparation, the registration core ----
 int fail(rgc_ctx* c, int code, const char* fmt, ...);
 int ensure(rgc_ctx* c, DevBuf& b, size_t bytes);
+int ensure_pinned(rgc_ctx* c, PinnedBuf& b, size_t need, size_t grow_to);  // what b held is dropped; it grows to grow_to (>= need: each caller's own amount)
+// room for `points` 16-byte points in a store that holds `held` (the rolling map's, the keyframe store's): half again, 1 MiB at least; preserve: they move along
+int grow_store(rgc_ctx* c, DevBuf& b, size_t held, size_t points, bool preserve);
 int check_device_range(rgc_ctx* c, const void* p, size_t bytes, const char* what);
 bool ctx_alive(const rgc_ctx* c);
 const rgc_ctx::BoxHint* find_hint(const rgc_ctx* c, const void* p, int n);
@@ -550,6 +586,8 @@ inline bool solve_in_flight(const rgc_ctx* c) { return c->pend.active || c->gen_
 inline int min_cloud_points(const rgc_ctx* c) { return c->cov_method == RGC_COV_RBF ? 1 : c->prm.k_correspondences; }
 // what every entry point that takes a strided cloud accepts: x, y, z as floats at the head of each record
 inline bool stride_ok(int stride_bytes) { return stride_bytes >= 12 && !(stride_bytes & 3) && stride_bytes <= 4096; }
+// ... and where the fourth float is read too (x, y, z, intensity or class)
+inline bool stride4_ok(int stride_bytes) { return stride_bytes >= 16 && stride_ok(stride_bytes); }
 // the rotation and translation rows of a row-major 4x4 (or 3x4) pose
 template <class T>
 inline bool pose12_finite(const T* m) {
@@ -560,10 +598,12 @@ inline bool pose12_finite(const T* m) {
 
 // ---- rgc_api_pre.hip ----
 int stage_in(rgc_ctx* c, const float* p, int n, int stride_bytes, int on_device, const float** d_in);
-// rgc_voxelgrid after its argument checks; rt: what rgc_voxelgrid_route reports, filled as the call goes (the caller adds status and n_out)
-int voxelgrid_run(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device, rgc_vg_route& rt,
-                  int mode = rgck::kVgModeCentroid, int* out_index = nullptr);  // mode = rgck::kVgModePick: UniformSampling, out_index (nullable) as out_xyzi
-void host_eig3_sym(const double S[6], double ev[3], double V[9]);  // Jacobi; eigenvalues ASCENDING, columns of V
+// rgc_voxelgrid after its argument checks (nothing runs for n == 0, or behind a refusal rc the caller already has), its route recorded for rgc_voxelgrid_route
+int voxelgrid_routed(rgc_ctx* c, const float* xyzi, int n, int stride_bytes, float leaf, float* out_xyzi, int* n_out, int on_device,
+                     int mode = rgck::kVgModeCentroid, int* out_index = nullptr, int rc = RGC_OK);  // mode = rgck::kVgModePick: UniformSampling, out_index (nullable) as out_xyzi
+// rgc_api_mapreg.hip.  A caller's strided cloud, host or device, as a grid-only cloud: a device caller's pointer is looked up (what_device names it in the refusal),
+// a host caller's records are uploaded into cl.in_copy, both through x, y, z of the last record; then cl's measured grid at `cell` (the feature maps, the ICP target)
+int grid_strided_cloud(rgc_ctx* c, Cloud& cl, const float* p, int n, int stride_bytes, bool on_device, double cell, const char* what_device);
 
 // ---- rgc_api_search.hip: the call frame of the cloud operations (the records above) ----
 // the frame's device words and their pinned mirror (kFrameBytes each), allocated once

@@ -83,7 +83,7 @@ void ypr2R(const double ypr[3], double R[9]) {
 
 // f5: the rotation of a key pose as the mapping node's transformPointCloud(cloud, &pose6D) computes it (src/RGC_mapping.cpp:2575-2576):
 // q_temp = Utility::ypr2R(Vector3d(yaw, pitch, roll) * rad2deg) -- the float fields widened to fp64, rad2deg = 180.0 / M_PI (:197), ypr2R in
-// DEGREES (utility.h:123-147), the Matrix3d assigned to a Quaterniond.  Internal to the library (rgc_api_mapping.hip's rgc_kf_*), not exported.
+// DEGREES (utility.h:123-147), the Matrix3d assigned to a Quaterniond.  Internal to the library (rgc_api_keyframes.hip's rgc_kf_*), not exported.
 void rgc_host_key_pose_quat(float roll, float pitch, float yaw, double q_xyzw[4]) {
   const double rad2deg = 180.0 / M_PI;
   const double ypr[3] = {(double)yaw * rad2deg, (double)pitch * rad2deg, (double)roll * rad2deg};

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INDEX = os.path.join(ROOT, "tests", "golden", "reference_index.json")
 DEFAULT = ["include/rgc_hip.h", "oracle/rgc_oracle.c", "oracle/rgc_oracle_aux.c", "oracle/rgc_oracle_map.c", "oracle/rgc_oracle.h", "oracle/py_oracle.py", "oracle/py_frontend.py",
            "oracle/py_fusion.py", "oracle/py_icp.py", "oracle/py_mapreg.py", "oracle/py_odometer.py", "rgc-slam_amd/csrc/rgc_kernels.hip", "rgc-slam_amd/csrc/rgc_api.hip",
-           "rgc-slam_amd/csrc/rgc_api_pre.hip", "rgc-slam_amd/csrc/rgc_api_mapping.hip", "rgc-slam_amd/csrc/rgc_api_lsq.hip", "rgc-slam_amd/csrc/rgc_api_ndt.hip", "rgc-slam_amd/csrc/rgc_api_gicp.hip", "rgc-slam_amd/csrc/rgc_ctx.h",
+           "rgc-slam_amd/csrc/rgc_api_pre.hip", "rgc-slam_amd/csrc/rgc_api_frontend.hip", "rgc-slam_amd/csrc/rgc_api_mapreg.hip", "rgc-slam_amd/csrc/rgc_api_map.hip", "rgc-slam_amd/csrc/rgc_api_wire.hip", "rgc-slam_amd/csrc/rgc_api_icp.hip", "rgc-slam_amd/csrc/rgc_api_keyframes.hip", "rgc-slam_amd/csrc/rgc_api_lsq.hip", "rgc-slam_amd/csrc/rgc_api_ndt.hip", "rgc-slam_amd/csrc/rgc_api_gicp.hip", "rgc-slam_amd/csrc/rgc_ctx.h",
            "rgc-slam_amd/csrc/rgc_frontend.hip", "rgc-slam_amd/csrc/rgc_pre.hip", "rgc-slam_amd/csrc/rgc_host.cpp", "rgc-slam_amd/cpp/odometry_node.hpp",
            "rgc-slam_amd/cpp/fast_vgicp_hip.hpp", "rgc-slam_amd/odometry.py", "rgc-slam_amd/registration.py", "DESIGN.md", "INTEGRATION.md", "SURVEY.md"]
 CITE = re.compile(r"([\w/\.]*\b[\w]+\.(?:cpp|hpp|h|cu|cuh|launch|yaml|msg)):(\d+(?:-\d+)?(?:,\s?\d+(?:-\d+)?)*)")
